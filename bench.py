@@ -7,6 +7,7 @@ configs[2]/[3]: 65 536 envs per GPU, full skill chain (5 options), independent e
 collective ("scaling": "weak"); --shared-weights switches to configs[4] (RCCL all-reduce of dW).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]            (N > 1: starts its own N rank processes)
+    python bench.py ... --dump-outputs DIR                          (also writes the last timed step's outputs as .npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line. `roofline` prices the dominant kernel (td_kernel<FUSED>) from HIP events
@@ -207,6 +208,42 @@ def _time_steps(agent, steps, warmup, ramp=200):
     return (time.perf_counter() - t0) / steps
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240611
+
+
+def dump_outputs(agent, out_dir):
+    """--dump-outputs: what the timed path's caller holds after its last step — the env state SoA and the weights W — as
+    DIR/<name>.npy (float32 fields as float32, integer fields as float64: exact). Above 64 MB in all, the per-env arrays
+    are cut to a fixed, seeded sample of envs (the same indices for every field), written beside them as env_index.npy.
+    A directory created here gets a .gitignore of its own, so that a dump inside a checkout leaves `git status` clean."""
+    import numpy as np
+    import torch
+    if agent.W.is_cuda:
+        torch.cuda.synchronize(agent.W.device)
+    fields = {f: getattr(agent.state, f).cpu().numpy() for f in agent._STATE_FIELDS}
+    W = agent.W.cpu().numpy().astype(np.float32)
+    conv = {f: (a.astype(np.float32) if a.dtype in (np.float32, np.uint8) else a.astype(np.float64)) for f, a in fields.items()}
+    n = agent.n_envs
+    per_env = sum(a.nbytes for a in conv.values()) / n
+    idx = None
+    budget = DUMP_LIMIT_BYTES - W.nbytes - 4096                          # 4 KB: the .npy headers
+    if per_env * n > budget:
+        keep = int(budget // (per_env + 8))                               # + 8: the env's entry in env_index.npy
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+        conv = {f: a[..., idx] for f, a in conv.items()}          # env is the last axis of every field (qcache: [action, env])
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:
+            f.write("*\n")
+    for name, a in dict(conv, W=W).items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    if idx is not None:
+        np.save(os.path.join(out_dir, "env_index.npy"), idx.astype(np.float64))
+    return {"dir": out_dir, "arrays": sorted(list(conv) + ["W"] + (["env_index"] if idx is not None else [])),
+            "envs": n if idx is None else int(idx.size), "sampled": idx is not None}
+
+
 def extra_measurements(steps, warmup):
     """Two more single-GPU figures beside the headline (which keeps its synthetic nested-disc options so that rounds stay
     comparable): BASELINE configs[1] (4096 envs, root + 1 chained option) and configs[2] with DISCOVERED options — the outer
@@ -280,7 +317,11 @@ def main():
                     "(a 20-step run otherwise times a cold GPU and the first step's stand-alone sort)")
     ap.add_argument("--no-live-traffic", action="store_true", help="roofline.traffic from the tracked profile instead of two rocprofv3 counter "
                     "passes of this workload run first (single-GPU runs; skipped anyway with --no-extras, under a profiler, or when rocprofv3 is missing)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(rank 0's env state and weights W) as DIR/<name>.npy, at most 64 MB (a fixed, seeded env sample beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     live = None
     if ("WORLD_SIZE" not in os.environ and args.gpus == 1 and not args.no_live_traffic and not args.no_extras
@@ -376,6 +417,7 @@ def main():
     k_ms, k_n = C.c_double(), C.c_int64()
     lib.scg_profile_read(ctx, C.byref(k_ms), C.byref(k_n))
     lib.scg_profile_reset(ctx, 0)
+    dumped = dump_outputs(agent, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
     ar = agent.time_allreduce(0) if group is not None else None
     t = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
@@ -426,6 +468,8 @@ def main():
                          "note": "the fused kernel is compute- and latency-bound (f32 matrix pipe 50 % busy), not HBM-bound (SURVEY.md \u00a78d, "
                                  "DESIGN.md): see `mfma` for the binding roofline"},
         }
+        if dumped is not None:
+            out["outputs"] = dumped
         # the binding (matrix-pipe) roofline: algorithmic flops of the TD items this rank processed per step
         st = agent.state
         opt = st.option_id.cpu().numpy()

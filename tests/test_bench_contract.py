@@ -107,3 +107,57 @@ def test_live_traffic_never_starts_counter_passes_from_a_profiled_process(monkey
         monkeypatch.setenv(var, val)
         assert bench.live_traffic(65536, 5) is None, var
         monkeypatch.delenv(var)
+
+
+class _FakeAgent:
+    """What dump_outputs reads from a SkillChainingAgent: the env state SoA and W (host tensors here)."""
+    _STATE_FIELDS = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done")
+
+    def __init__(self, n):
+        import types
+        import torch
+        g = torch.Generator().manual_seed(1)
+        f32 = lambda *s: torch.randn(*s, generator=g)
+        i32 = lambda: torch.randint(-5, 3000, (n,), generator=g, dtype=torch.int32)
+        u8 = lambda: torch.randint(0, 5, (n,), generator=g, dtype=torch.uint8)
+        self.n_envs = n
+        self.W = f32(6, 5, 1296)
+        self.state = types.SimpleNamespace(x=f32(n), y=f32(n), vx=f32(n), vy=f32(n), option_id=i32(), opt_steps=i32(),
+                                           ep_steps=i32(), qcache=f32(5, n), action=u8(), reward=f32(n), done=u8())
+
+
+def test_dump_outputs_writes_every_array_exactly_and_samples_beyond_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    ag = _FakeAgent(4096)
+    d = tmp_path / "full"
+    info = bench.dump_outputs(ag, str(d))
+    assert not info["sampled"] and info["envs"] == 4096
+    assert (d / ".gitignore").read_text() == "*\n"
+    for f in ag._STATE_FIELDS + ("W",):
+        a = np.load(d / (f + ".npy"))
+        src = (ag.W if f == "W" else getattr(ag.state, f)).numpy()
+        assert a.dtype in (np.float32, np.float64) and a.shape == src.shape, f
+        assert np.array_equal(a, src.astype(a.dtype)) and np.array_equal(a.astype(src.dtype), src), f
+    assert not (d / "env_index.npy").exists()
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 18)                 # force the seeded sample
+    runs = []
+    for name in ("a", "b"):
+        info = bench.dump_outputs(ag, str(tmp_path / name))
+        assert info["sampled"] and 0 < info["envs"] < 4096
+        total = sum(p.stat().st_size for p in (tmp_path / name).glob("*.npy"))
+        assert total <= 1 << 18
+        runs.append({p.stem: np.load(p) for p in (tmp_path / name).glob("*.npy")})
+    idx = runs[0]["env_index"].astype(np.int64)
+    assert np.array_equal(runs[0]["env_index"], runs[1]["env_index"]) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(runs[0]["qcache"], ag.state.qcache.numpy()[:, idx])
+    assert np.array_equal(runs[0]["option_id"], ag.state.option_id.numpy()[idx].astype(np.float64))
+    assert np.array_equal(runs[0]["W"], ag.W.numpy())
+
+
+def test_bench_refuses_zero_timed_steps():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--steps" in r.stderr

@@ -1,7 +1,9 @@
 """CPU-side sanitizer runs (GPU sanitizers are not available on the pool):
  * the oracle built with AddressSanitizer + UBSan over the oracle-level tests (`make -C oracle asan-test`);
  * libscg_hip.so with its HOST half instrumented by ASan + UBSan: every C-ABI entry point's argument checks and error
-   paths, driven without a GPU."""
+   paths, driven without a GPU. The sanitized process is never given one: the ASan runtime also interposes the HSA
+   memory-pool calls, and a HIP device brought up under it fails its first pool allocation (an ASan out-of-memory
+   abort). HIP_VISIBLE_DEVICES=-1 hides every GPU, so the no-device path is taken on any machine."""
 import os
 import subprocess
 import sys
@@ -36,20 +38,17 @@ for kw in bad:
 assert lib.scg_create(None, None) == -1
 good = ScgConfig(n_envs=64, n_options=1, fourier_order=5, device=0)
 rc = lib.scg_create(C.byref(ctx), C.byref(good))
-if rc != 0:                                    # no GPU here: the no-device path
-    assert rc in (-2, -3) and not ctx.value
-    null = C.c_void_p()
-    z = [None] * 13
-    assert lib.scg_step(null, *z, 0, 0, 0, None) == -1
-    assert lib.scg_set_map(null, None, 0, None, 0, None, None) == -1
-    assert lib.scg_q_update(null, 0, 0, *[None] * 12, 0, None) == -1
-    assert lib.scg_q_values(null, 0, *[None] * 6, None) == -1
-    assert lib.scg_fit_initiation(null, 0, None, None, None, None, 0, C.c_float(0), C.c_float(0), None) == -1
-    assert lib.scg_harvest(null, 0, None, None, None, 0, None, 0, 0, None, None, None) == -1
-    assert lib.scg_set_option_parents(null, None) == -1 and lib.scg_invalidate_order(null) == -1
-    assert lib.scg_profile_reset(null, 0) == -1 and lib.scg_destroy(null) == 0
-else:
-    lib.scg_destroy(ctx)
+assert rc in (-2, -3) and not ctx.value, rc    # no GPU visible: the no-device path
+null = C.c_void_p()
+z = [None] * 13
+assert lib.scg_step(null, *z, 0, 0, 0, None) == -1
+assert lib.scg_set_map(null, None, 0, None, 0, None, None) == -1
+assert lib.scg_q_update(null, 0, 0, *[None] * 12, 0, None) == -1
+assert lib.scg_q_values(null, 0, *[None] * 6, None) == -1
+assert lib.scg_fit_initiation(null, 0, None, None, None, None, 0, C.c_float(0), C.c_float(0), None) == -1
+assert lib.scg_harvest(null, 0, None, None, None, 0, None, 0, 0, None, None, None) == -1
+assert lib.scg_set_option_parents(null, None) == -1 and lib.scg_invalidate_order(null) == -1
+assert lib.scg_profile_reset(null, 0) == -1 and lib.scg_destroy(null) == 0
 print("host-asan ok")
 """
 
@@ -62,6 +61,6 @@ def test_c_abi_host_paths_under_asan_ubsan():
                         capture_output=True, text=True).stdout.strip()
     assert os.path.exists(rt), rt
     env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1",
-               SCG_LIB=os.path.join(csrc, "libscg_hip_hostasan.so"))
+               SCG_LIB=os.path.join(csrc, "libscg_hip_hostasan.so"), HIP_VISIBLE_DEVICES="-1")
     r = subprocess.run([sys.executable, "-c", _DRIVER % {"root": ROOT}], capture_output=True, text=True, env=env)
     assert r.returncode == 0 and "host-asan ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
