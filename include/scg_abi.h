@@ -118,6 +118,35 @@ int scg_apply_update_packed(scg_ctx *ctx, float *W, const float *G_packed, void 
  * (An all-reduce's order of additions is the library's business: exact for two ranks, to rounding beyond.) */
 int scg_apply_update_slots(scg_ctx *ctx, float *W, const float *slots, int32_t n_slots, int64_t slot_stride, void *stream);
 
+/* ---- the peer transport of the order-pinned sum: no collective on the step path ----
+ * The ranks of ONE node (processes on one or several GPUs) each own a region of device memory (plain hipMalloc, ctx-owned):
+ * an epoch line, a void line and two packed operands (parity 0 / 1). Every rank maps the others' regions through HIP IPC once;
+ * per learning step-batch each rank publishes its operand and sums all of them in rank order itself, with the arithmetic of
+ * scg_apply_update_slots: the weights are bit for bit those of an all-gather + scg_apply_update_slots.
+ *   scg_peer_export          allocate the region (once; later calls return the same handle) and write its
+ *                            hipIpcMemHandle_t to handle_out (HOST, 64 bytes)
+ *   scg_peer_open            handles = n_ranks x 64 bytes (HOST) in rank order, as every rank's scg_peer_export left them;
+ *                            opens each peer region once (a region of this same process is used directly); n_ranks in [1, 8];
+ *                            SCG_ERR_STATE before scg_peer_export or when already open. scg_destroy closes the mappings and
+ *                            frees the region: destroy only after every rank has finished its last exchange
+ *   (step begin)             FOLDED INTO scg_step: while the peers are open, every scg_step(LEARN) leaves its packed operand in
+ *                            this rank's buffer of parity e & 1 (e = the ctx's private exchange counter), whatever
+ *                            scg_set_grad_buffer* said; SCG_STEP_APPLY is refused then
+ *   scg_peer_exchange_apply  after that step, on the same stream: (a) publish — the void flag of exchange e (set when a workgroup
+ *                            of the step gave up), a system-scope release, epoch := e + 1; (b) wait — ONE wave polls every rank's
+ *                            epoch until >= e + 1 (system-scope loads, s_sleep between them), bounded by scg_set_peer_timeout of
+ *                            wall clock: on expiry SCG_ASYNC_PEER_TIMEOUT is raised and W is left untouched; (c) apply — the
+ *                            sum of the n_ranks operands of parity e & 1 in rank order, applied as scg_apply_update_slots does;
+ *                            if ANY rank voided its step no rank touches W and each raises SCG_ASYNC_STEP_HANDOFF. Then e += 1.
+ *                            Launched even while an asynchronous failure is pending (the peers must not be left waiting); the
+ *                            pending failure is returned as SCG_ERR_ASYNC after the launches.
+ * The counter e is not the step counter t: a checkpoint reload rewinds t, not e. All ranks make one exchange per learning
+ * step-batch. Ranks sharing one GPU must keep the sum of their step grids below the chip's 256 workgroups (the waiting wave
+ * holds a CU slot); the Python layer checks that. */
+int scg_peer_export(scg_ctx *ctx, void *handle_out);
+int scg_peer_open(scg_ctx *ctx, int32_t n_ranks, int32_t rank, const void *handles);
+int scg_peer_exchange_apply(scg_ctx *ctx, float *W, void *stream);
+
 /* ---- un-fused entry points (same arithmetic; used by the API facade and the parity tests) ---- */
 
 /* PinballDomain.step (SPEC §1.3) with caller-given actions; no reset. goal[n] u8. */
@@ -208,14 +237,18 @@ int scg_set_gestation(scg_ctx *ctx, uint32_t gest_mask, int32_t *succ_counts);
  * the bound is only reached through a logic error or a hung wavefront). A poll that runs out raises
  * SCG_ASYNC_STEP_HANDOFF: that block's partial gradients are dropped (its slab counts read 0) and the step's other
  * outputs for the block's envs are unspecified — the state must be restored from a checkpoint.
+ * The peer exchange is the third (scg_peer_exchange_apply): SCG_ASYNC_PEER_TIMEOUT when a peer's epoch does not arrive in
+ * time, SCG_ASYNC_STEP_HANDOFF on every rank when any rank's step of that exchange was void; W is untouched in both cases.
  *   scg_async_status      the word (optional out) and its status; `synchronize` != 0 waits for `stream` first, which
  *                         makes the answer final for everything launched on it so far
  *   scg_decode_async_word the same mapping word -> status + text without a ctx (pure host code) */
 #define SCG_ASYNC_FIT_TIMEOUT 0x1u
 #define SCG_ASYNC_STEP_HANDOFF 0x2u
+#define SCG_ASYNC_PEER_TIMEOUT 0x4u   /* scg_peer_exchange_apply: a peer's epoch did not arrive within scg_set_peer_timeout; W untouched */
 int scg_async_status(scg_ctx *ctx, void *stream, int32_t synchronize, uint32_t *word_out);
 int scg_clear_async_error(scg_ctx *ctx);
 int scg_set_fit_timeout(scg_ctx *ctx, double seconds);
+int scg_set_peer_timeout(scg_ctx *ctx, double seconds);     /* the peer wait's bound (default 2 s), see scg_peer_exchange_apply */
 int scg_decode_async_word(uint32_t word, char *buf, int32_t buf_len);
 /* test hook: raise bits of the status word from the host, as a kernel would */
 int scg_debug_raise_async(scg_ctx *ctx, uint32_t word);

@@ -20,6 +20,9 @@ STEP_APPLY = 2
 ABI_VERSION = 5            # include/scg_abi.h SCG_ABI_VERSION
 ASYNC_FIT_TIMEOUT = 0x1
 ASYNC_STEP_HANDOFF = 0x2
+ASYNC_PEER_TIMEOUT = 0x4
+PEER_HANDLE_BYTES = 64      # hipIpcMemHandle_t
+PEER_MAX_RANKS = 8
 
 
 class ScgError(RuntimeError):
@@ -80,6 +83,10 @@ _SIGS = {
     "scg_async_status": (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_uint32)]),
     "scg_clear_async_error": (C.c_int, [_P]),
     "scg_set_fit_timeout": (C.c_int, [_P, C.c_double]),
+    "scg_set_peer_timeout": (C.c_int, [_P, C.c_double]),
+    "scg_peer_export": (C.c_int, [_P, _P]),
+    "scg_peer_open": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "scg_peer_exchange_apply": (C.c_int, [_P, _P, _P]),
     "scg_decode_async_word": (C.c_int, [C.c_uint32, C.c_char_p, C.c_int32]),
     "scg_debug_raise_async": (C.c_int, [_P, C.c_uint32]),
 }

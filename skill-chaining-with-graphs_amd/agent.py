@@ -21,7 +21,13 @@ from .pinball import PinballDomain
 
 class SkillChainingAgent:
     def __init__(self, pmap, n_envs: int, n_options: int = 0, *, device: int = 0, seed: int = 0,
-                 env_id_base: int = 0, group=None, ordered_sum: bool = False, **hparams):
+                 env_id_base: int = 0, group=None, ordered_sum: bool = False, transport: str = "collective", **hparams):
+        # transport (shared weights only): "collective" = a torch.distributed collective per learning step-batch; "peer" = the
+        # ranks of one node read each other's operands through HIP IPC and sum them in rank order on the device
+        if transport not in ("collective", "peer"):
+            raise ValueError("transport must be 'collective' or 'peer'")
+        if transport == "peer" and (group is None or not ordered_sum):
+            raise ValueError("transport='peer' needs group=... and ordered_sum=True (it is a transport of the order-pinned sum)")
         self.map: PinballMap = load_map(pmap) if isinstance(pmap, str) else pmap
         if group is not None and hparams.get("block_envs") is None and not os.environ.get("SCG_BLOCK_ENVS"):
             # a sharded run uses ONE block geometry (it orders the partial sums of G): the ranks agree on the largest any of them
@@ -41,6 +47,9 @@ class SkillChainingAgent:
         self.ordered_sum = bool(ordered_sum)   # shared weights summed in rank order from an all-gather (identical on every
         self._slots = None                     # rank of the run, reproduced by the oracle) instead of an all-reduce (exact for two ranks)
         self.allreduce_timing = None  # see time_allreduce()
+        self.transport = transport
+        if transport == "peer":
+            _dist.exchange_peer_handles(self.ctx, group)
         self.domain = PinballDomain(self.ctx)
         self.state: EnvState = self.domain.state
         self.options: List[Option] = [Option(self, k) for k in range(self.n_vf)]
@@ -218,6 +227,9 @@ class SkillChainingAgent:
     def step_batch(self, learn: bool = True) -> None:
         """One fused step-batch over all envs (act, physics, options, features, Q, TD, update)."""
         shared = self.group is not None and learn
+        if shared and self.transport == "peer":
+            self._step_batch_peer()
+            return
         if shared:
             gp = self.ctx.grad_packed()                  # G and the update counts: ONE all-reduce operand
         self.ctx.step(self.state, self.W, self.clf, self.enabled_mask, self.t, learn=learn, apply=not shared)
@@ -242,6 +254,23 @@ class SkillChainingAgent:
             else:
                 self.ctx.apply_update_packed(self.W, gp)
         self.t += 1
+
+    def _step_batch_peer(self) -> None:
+        """A learning step-batch over the peer transport: the step leaves the operand in this rank's peer region, then ONE
+        exchange call publishes it, waits for every rank's and applies their rank-order sum (no collective, no host wait)."""
+        self.ctx.step(self.state, self.W, self.clf, self.enabled_mask, self.t, learn=True, apply=False)
+        timing = self.allreduce_timing
+        sample = timing is not None and (self.t % timing["every"]) == 0
+        if sample:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        try:
+            self.ctx.peer_exchange_apply(self.W)
+        finally:
+            if sample:
+                e1.record()
+                timing["events"].append((e0, e1))
+            self.t += 1
 
     def time_allreduce(self, every: int = 0) -> Optional[dict]:
         """every > 0: bracket every `every`-th shared-weights all-reduce with an event pair on the current stream

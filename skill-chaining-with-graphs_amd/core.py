@@ -365,6 +365,38 @@ class ScgContext:
         """How long fit_initiation waits for a workgroup that is not running yet before it abandons that fit."""
         self._call("scg_set_fit_timeout", C.c_double(seconds))
 
+    # ------------------------------------------------------------------ peer transport (include/scg_abi.h, DESIGN §6)
+    def peer_export(self) -> bytes:
+        """Allocate this rank's peer region (once) and return its 64-byte IPC handle."""
+        buf = C.create_string_buffer(_lib.PEER_HANDLE_BYTES)
+        self._call("scg_peer_export", C.cast(buf, C.c_void_p))
+        return buf.raw
+
+    def peer_open(self, n_ranks: int, rank: int, handles) -> None:
+        """Map every rank's region: `handles` = the n_ranks 64-byte handles of peer_export, in rank order. From now on every
+        learning step leaves its packed operand in this rank's region (step(..., apply=False))."""
+        handles = [bytes(h) for h in handles]
+        if len(handles) != n_ranks or any(len(h) != _lib.PEER_HANDLE_BYTES for h in handles):
+            raise ScgError(f"peer_open: need {n_ranks} handles of {_lib.PEER_HANDLE_BYTES} bytes")
+        blob = C.create_string_buffer(b"".join(handles), n_ranks * _lib.PEER_HANDLE_BYTES)
+        self._call("scg_peer_open", C.c_int32(n_ranks), C.c_int32(rank), C.cast(blob, C.c_void_p))
+        self.peer_ranks = int(n_ranks)
+
+    def peer_exchange_apply(self, W: torch.Tensor) -> None:
+        """After a learning step: publish this rank's operand, wait for every rank's, apply their rank-order sum to W
+        (all on the device, on the current stream)."""
+        self._chk(W, torch.float32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
+        self._call("scg_peer_exchange_apply", _ptr(W), self._stream())
+
+    def set_peer_timeout(self, seconds: float) -> None:
+        """How long the peer wait polls for a rank's epoch before it gives up (SCG_ASYNC_PEER_TIMEOUT, W untouched)."""
+        self._call("scg_set_peer_timeout", C.c_double(seconds))
+
+    @property
+    def step_grid(self) -> int:
+        """Workgroups of one fused step launch (one block of block_envs envs each)."""
+        return -(-self.n_envs // self.block_envs)
+
 
 class EnvState:
     """SoA env batch in HBM (caller-owned torch tensors)."""

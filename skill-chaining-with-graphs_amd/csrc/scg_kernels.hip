@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
+#include <mutex>
 #include <new>
 #include <type_traits>
 #include <vector>
@@ -582,6 +583,96 @@ __global__ __launch_bounds__(256) void apply_slots_kernel(float *W, const float 
 }
 
 // ------------------------------------------------------------------------------------------------
+// The peer transport of the order-pinned sum: every rank of a node publishes its packed operand in a region of its
+// own (scg_peer_export), reads the others' through IPC mappings and sums all of them in rank order here. Region layout: line 0 the
+// epoch word, line 1 the void flags (one per parity), then the two packed operands (parity 0 / 1), each 256-B aligned.
+constexpr int PEER_MAX = 8;
+constexpr size_t PEER_HDR = 256;               // bytes: epoch line + void line (128 B each)
+
+struct PeerView {
+    const float *buf[PEER_MAX][2];             // rank r's packed operand of parity p (own region or IPC mapping)
+    const uint32_t *epoch[PEER_MAX];           // rank r's epoch word: the number of exchanges it has published
+    const uint32_t *voidw[PEER_MAX];           // rank r's void flags [2], by parity
+};
+
+__device__ __forceinline__ bool epoch_reached(uint32_t v, uint32_t need) { return (int32_t)(v - need) >= 0; }   // (wrap-safe)
+
+// Step (a), publish: the void flag of this exchange, a system-scope release, then the epoch. Stream order puts this behind the
+// reduce launch that wrote the operand (a kernel boundary: its stores are written back from the XCD's L2 at the launch's end).
+__global__ __launch_bounds__(64) void peer_publish_kernel(uint32_t *epoch, uint32_t *voidw, int parity, const int32_t *fail,
+                                                          uint32_t value) {
+    if (threadIdx.x != 0) return;
+    const int32_t f = __hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&voidw[parity], f ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");          // system scope (a peer may sit on another GPU)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (keep the fence's wait: cdna_hip_programming §6 G16, pitfall 12)
+    __hip_atomic_store(epoch, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Step (b), wait: ONE wave, lane r polls rank r's epoch until it reaches `need` (relaxed system-scope loads, s_sleep between
+// them), bounded by the 100 MHz wall clock. Then one system-scope acquire and the void flags. The verdict goes to `go` (read by
+// apply_peers_kernel, the next launch): 1 = apply, 0 = leave W alone (a peer timed out: SCG_ASYNC_PEER_TIMEOUT; a rank voided
+// its step: SCG_ASYNC_STEP_HANDOFF). This is the only kernel that spins.
+__global__ __launch_bounds__(64) void peer_wait_kernel(const PeerView P, int n_ranks, int parity, uint32_t need,
+                                                       unsigned long long timeout_ticks, int32_t *go, uint32_t *async_word) {
+    const int lane = threadIdx.x;
+    bool late = false, voided = false;
+    if (lane < n_ranks) {
+        unsigned long long t0 = 0;
+        int spins = 0;
+        while (!epoch_reached(__hip_atomic_load(P.epoch[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), need)) {
+            __builtin_amdgcn_s_sleep(2);
+            if ((++spins & 63) == 0) {
+                const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+                if (t0 == 0) t0 = now;
+                else if (now - t0 > timeout_ticks) { late = true; break; }
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");          // system scope: the void flags below are the peers' of THIS exchange
+    if (lane < n_ranks && !late)
+        voided = __hip_atomic_load(&P.voidw[lane][parity], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u;
+    const bool any_late = __ballot(late) != 0, any_void = __ballot(voided) != 0;
+    if (lane == 0) {
+        if (any_late) __hip_atomic_fetch_or(async_word, SCG_ASYNC_PEER_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        else if (any_void) __hip_atomic_fetch_or(async_word, SCG_ASYNC_STEP_HANDOFF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(go, (any_late || any_void) ? 0 : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// Step (c), apply: apply_slots_kernel's arithmetic on the n_ranks operands of one parity, read through their device pointers.
+// It never polls: lane 0 reads the verdict and the peers' epochs, then ONE system-scope acquire (this CU's L1 and its XCD's L2
+// may still hold a peer's buffer from exchange e - 2), and the workgroup barrier comes before any operand load.
+__global__ __launch_bounds__(256) void apply_peers_kernel(float *W, const PeerView P, int n_ranks, int parity, uint32_t need,
+                                                          const int32_t *go, int n_vf, const float *scale, float alpha,
+                                                          int nk_floor) {
+    __shared__ int s_ok;
+    if (threadIdx.x == 0) {
+        int ok = __hip_atomic_load(go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int r = 0; r < n_ranks; ++r)
+            ok &= epoch_reached(__hip_atomic_load(P.epoch[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), need) ? 1 : 0;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+        s_ok = ok;
+    }
+    __syncthreads();
+    if (!s_ok) return;
+    const int k = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= NACT * NF) return;
+    const size_t at = (size_t)k * NACT * NF + i, cnt_at = (size_t)n_vf * NACT * NF + k;
+    float g = P.buf[0][parity][at], nkf = P.buf[0][parity][cnt_at];
+    for (int r = 1; r < n_ranks; ++r) {
+        g = g + P.buf[r][parity][at];
+        nkf = nkf + P.buf[r][parity][cnt_at];                   // counts as floats: exact (far below 2^24)
+    }
+    const int nk = (int)(nkf + 0.5f);
+    if (nk <= 0) return;
+    const float step = alpha / (float)max(nk, nk_floor);
+    float *w = W + at;
+    *w = fmaf(step * scale[i % NF], g, *w);
+}
+
+// ------------------------------------------------------------------------------------------------
 // SPEC §5 env order: stable counting sort of the envs by option_id (6 keys), two tiny kernels per step.
 // Option-homogeneous workgroups turn five sparse option passes per workgroup into about one dense one.
 __global__ __launch_bounds__(256) void sort_hist_kernel(const int32_t *option_id, int n, int n_vf, int32_t *hist) {
@@ -1006,8 +1097,23 @@ struct scg_ctx {
     long long prof_seen;
     std::vector<hipEvent_t> *prof_ev;
     size_t prof_used;
+    // peer transport (scg_peer_*): this rank's region, the peers' mappings and the private exchange counter
+    char *peer_region;             // hipMalloc'd: [epoch line][void line][operand parity 0][operand parity 1]
+    size_t peer_bytes, peer_op_stride;        // region size; bytes from one operand to the next
+    hipIpcMemHandle_t peer_handle;
+    int peer_n, peer_rank;         // 0 = not opened
+    char *peer_base[PEER_MAX];     // every rank's region (own or mapped)
+    bool peer_mapped[PEER_MAX];    // opened with hipIpcOpenMemHandle (closed at destroy)
+    uint32_t peer_e;               // exchanges done: the epoch a rank publishes is peer_e + 1
+    int32_t *d_peer_go;            // peer_wait_kernel -> apply_peers_kernel: apply (1) or not (0)
+    double peer_timeout_s;
     char err[256];
 };
+
+// Regions exported by this process: a peer ctx in the SAME process is found here instead of being IPC-opened (the runtime may
+// refuse to open a handle of the calling process).
+static std::mutex g_peer_mu;
+static std::vector<std::pair<hipIpcMemHandle_t, char *>> g_peer_regions;
 
 static thread_local char g_err[256] = "";
 
@@ -1033,6 +1139,10 @@ static int decode_async(uint32_t word, char *buf, size_t n) {
             snprintf(buf, n, "an earlier scg_step gave up inside a workgroup: a bounded hand-off poll between its wavefront subsets ran "
                      "out (a logic error or a hung wavefront); the block's partial gradients were dropped and the step's outputs for "
                      "its envs are unspecified — restore the state. scg_clear_async_error() re-arms the context");
+        else if (word & SCG_ASYNC_PEER_TIMEOUT)
+            snprintf(buf, n, "an earlier scg_peer_exchange_apply gave up: the peer wait ran out (a peer rank did not publish its "
+                     "operand within the peer timeout: stopped, hung or out of step); the weights were left unchanged. "
+                     "scg_clear_async_error() re-arms the context");
         else if (word & SCG_ASYNC_FIT_TIMEOUT)
             snprintf(buf, n, "an earlier scg_fit_initiation gave up (problem mask 0x%x): its workgroups did not become "
                      "co-resident within the fit timeout (card shared with other work?); the affected classifier rows were "
@@ -1110,6 +1220,13 @@ int scg_set_fit_timeout(scg_ctx *c, double seconds) {
     if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_set_fit_timeout: null ctx");
     if (!(seconds >= 0.0) || seconds > 3600.0) return fail(c, SCG_ERR_INVALID, "scg_set_fit_timeout: seconds must be in [0, 3600]");
     c->fit_timeout_s = seconds;
+    return SCG_OK;
+}
+
+int scg_set_peer_timeout(scg_ctx *c, double seconds) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_set_peer_timeout: null ctx");
+    if (!(seconds >= 0.0) || seconds > 3600.0) return fail(c, SCG_ERR_INVALID, "scg_set_peer_timeout: seconds must be in [0, 3600]");
+    c->peer_timeout_s = seconds;
     return SCG_OK;
 }
 
@@ -1204,6 +1321,7 @@ int scg_create(scg_ctx **out, const scg_config *cfg) {
     for (int k = 1; k < MAX_VF; ++k) c->parents |= (uint32_t)(k - 1) << (3 * k);      // chain: 1 -> goal, k -> k-1
     c->G_out = c->d_G; c->nk_out = c->d_nk;
     c->fit_timeout_s = 2.0;
+    c->peer_timeout_s = 2.0;
     *out = c;
     return SCG_OK;
 }
@@ -1215,6 +1333,17 @@ int scg_destroy(scg_ctx *c) {
     (void)hipFree(c->d_edges); (void)hipFree(c->d_starts); (void)hipFree(c->d_scale); (void)hipFree(c->d_cellmask); (void)hipFree(c->d_perm); (void)hipFree(c->d_hist);
     (void)hipFree(c->d_fit_part); (void)hipFree(c->d_collect_rows); (void)hipFree(c->d_fail);
     if (c->h_async) (void)hipHostFree(c->h_async);
+    if (c->peer_region) {
+        DeviceGuard g(c->cfg.device);
+        for (int r = 0; r < PEER_MAX; ++r)
+            if (c->peer_mapped[r]) (void)hipIpcCloseMemHandle(c->peer_base[r]);
+        {
+            std::lock_guard<std::mutex> lk(g_peer_mu);
+            for (size_t i = 0; i < g_peer_regions.size(); ++i)
+                if (g_peer_regions[i].second == c->peer_region) { g_peer_regions.erase(g_peer_regions.begin() + i); break; }
+        }
+        (void)hipFree(c->peer_region); (void)hipFree(c->d_peer_go);
+    }
     if (c->prof_ev) {
         for (hipEvent_t e : *c->prof_ev) (void)hipEventDestroy(e);
         delete c->prof_ev;
@@ -1278,6 +1407,19 @@ int scg_set_map(scg_ctx *c, const float *edges, int32_t n_edges, const float *st
     return SCG_OK;
 }
 
+// While a peer region is open, a learning step leaves its packed operand in the region's buffer of parity peer_e & 1.
+struct PeerTarget {
+    scg_ctx *c;
+    float *G, *nkf;
+    int32_t *nk;
+    explicit PeerTarget(scg_ctx *ctx) : c(ctx), G(ctx->G_out), nkf(ctx->nkf_out), nk(ctx->nk_out) {
+        if (!c->peer_n) return;
+        float *op = reinterpret_cast<float *>(c->peer_region + PEER_HDR + (c->peer_e & 1u) * c->peer_op_stride);
+        c->G_out = op; c->nkf_out = op + (size_t)c->n_vf * NACT * NF; c->nk_out = c->d_nk;
+    }
+    ~PeerTarget() { c->G_out = G; c->nkf_out = nkf; c->nk_out = nk; }
+};
+
 static void fill_common(const scg_ctx *c, StepArgs &A) {
     memset(&A, 0, sizeof(A));
     A.n_vf = c->n_vf;
@@ -1340,6 +1482,8 @@ int scg_step(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *opti
     if (!x || !y || !vx || !vy || !option_id || !opt_steps || !ep_steps || !qcache || !action || !reward ||
         !done || !W || !clf)
         return fail(c, SCG_ERR_INVALID, "scg_step: null array argument");
+    if (c->peer_n && (flags & SCG_STEP_LEARN) && (flags & SCG_STEP_APPLY))
+        return fail(c, SCG_ERR_INVALID, "scg_step: SCG_STEP_APPLY with a peer region open (the update is scg_peer_exchange_apply's)");
     SCG_CHECK_ASYNC(c);
     SCG_ON_DEVICE(c, "scg_step");
     if (c->arm_bits) {
@@ -1406,6 +1550,8 @@ int scg_step(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *opti
     // results reach the caller's arrays through the commit workgroups of the reduce launch (or a commit launch)
     c->arm_rows_ready = c->arm_bits && c->events && c->ring_x;      // ... which also leave an announced trigger's row totals
     if (!(flags & SCG_STEP_LEARN)) return launch_reduce(c, W, 0u, c->nblk, s, &A, false, false);
+    // peer transport: the packed operand goes to this rank's buffer of the next exchange's parity (scg_peer_step_begin folded in)
+    PeerTarget peer_target(c);
     if (!fold) return launch_reduce(c, W, (flags & SCG_STEP_APPLY) ? 1u : 0u, c->nblk, s, &A, false);
     c->hist_dirty = true;                          // until the reduce launch has consumed and re-armed the counts
     const int rc = launch_reduce(c, W, (flags & SCG_STEP_APPLY) ? 1u : 0u, c->nblk, s, &A, true);
@@ -1596,6 +1742,107 @@ int scg_apply_update_slots(scg_ctx *c, float *W, const float *slots, int32_t n_s
     hipLaunchKernelGGL(apply_slots_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), W, slots, (int)n_slots,
                        (long)slot_stride, c->n_vf, c->d_scale, c->cfg.alpha, c->cfg.update_count_floor);
     SCG_HIP(c, hipGetLastError());
+    return SCG_OK;
+}
+
+int scg_peer_export(scg_ctx *c, void *handle_out) {
+    if (!c || !handle_out) return fail(c, SCG_ERR_INVALID, "scg_peer_export: null argument");
+    if (!c->peer_region) {
+        SCG_ON_DEVICE(c, "scg_peer_export");
+        const size_t op = ((size_t)c->n_vf * NACT * NF + c->n_vf) * sizeof(float);
+        c->peer_op_stride = (op + 255) & ~(size_t)255;
+        c->peer_bytes = PEER_HDR + 2 * c->peer_op_stride;
+        char *r = nullptr;
+        SCG_HIP(c, hipMalloc(reinterpret_cast<void **>(&r), c->peer_bytes));        // ONE allocation: an IPC handle names it whole
+        hipIpcMemHandle_t h;
+        if (hipMemset(r, 0, c->peer_bytes) != hipSuccess || hipMalloc(&c->d_peer_go, sizeof(int32_t)) != hipSuccess ||
+            hipIpcGetMemHandle(&h, r) != hipSuccess) {
+            (void)hipFree(r); (void)hipFree(c->d_peer_go); c->d_peer_go = nullptr;
+            return fail(c, SCG_ERR_HIP, "scg_peer_export: cannot allocate / export the peer region");
+        }
+        c->peer_region = r; c->peer_handle = h;
+        std::lock_guard<std::mutex> lk(g_peer_mu);
+        g_peer_regions.emplace_back(h, r);
+    }
+    memcpy(handle_out, &c->peer_handle, sizeof(hipIpcMemHandle_t));
+    return SCG_OK;
+}
+
+int scg_peer_open(scg_ctx *c, int32_t n_ranks, int32_t rank, const void *handles) {
+    if (!c || !handles) return fail(c, SCG_ERR_INVALID, "scg_peer_open: null argument");
+    if (n_ranks < 1 || n_ranks > PEER_MAX || rank < 0 || rank >= n_ranks)
+        return fail(c, SCG_ERR_INVALID, "scg_peer_open: n_ranks must be in [1, 8] and rank in [0, n_ranks)");
+    if (!c->peer_region) return fail(c, SCG_ERR_STATE, "scg_peer_open: scg_peer_export has not been called");
+    if (c->peer_n) return fail(c, SCG_ERR_STATE, "scg_peer_open: the peers are already open");
+    SCG_ON_DEVICE(c, "scg_peer_open");
+    const hipIpcMemHandle_t *hs = reinterpret_cast<const hipIpcMemHandle_t *>(handles);
+    char *base[PEER_MAX] = {};
+    bool mapped[PEER_MAX] = {};
+    int st = SCG_OK;
+    for (int r = 0; r < n_ranks && st == SCG_OK; ++r) {
+        if (r == rank) {
+            if (memcmp(&hs[r], &c->peer_handle, sizeof(hipIpcMemHandle_t)) != 0)
+                st = fail(c, SCG_ERR_INVALID, "scg_peer_open: handles[rank] is not this context's region");
+            base[r] = c->peer_region;
+            continue;
+        }
+        {
+            std::lock_guard<std::mutex> lk(g_peer_mu);
+            for (auto &e : g_peer_regions)
+                if (memcmp(&e.first, &hs[r], sizeof(hipIpcMemHandle_t)) == 0) base[r] = e.second;
+        }
+        if (base[r]) continue;                                   // a peer context of this process
+        void *p = nullptr;
+        if (hipIpcOpenMemHandle(&p, hs[r], hipIpcMemLazyEnablePeerAccess) != hipSuccess) {
+            snprintf(c->err, sizeof(c->err), "scg_peer_open: hipIpcOpenMemHandle of rank %d failed: %s", r,
+                     hipGetErrorString(hipGetLastError()));
+            st = SCG_ERR_HIP;
+            break;
+        }
+        base[r] = static_cast<char *>(p); mapped[r] = true;
+    }
+    if (st != SCG_OK) {
+        for (int r = 0; r < n_ranks; ++r)
+            if (mapped[r]) (void)hipIpcCloseMemHandle(base[r]);
+        return st;
+    }
+    for (int r = 0; r < PEER_MAX; ++r) { c->peer_base[r] = base[r]; c->peer_mapped[r] = mapped[r]; }
+    c->peer_n = n_ranks; c->peer_rank = rank;
+    return SCG_OK;
+}
+
+int scg_peer_exchange_apply(scg_ctx *c, float *W, void *stream) {
+    if (!c || !W) return fail(c, SCG_ERR_INVALID, "scg_peer_exchange_apply: null argument");
+    if (!c->peer_n) return fail(c, SCG_ERR_STATE, "scg_peer_exchange_apply: scg_peer_open has not been called");
+    if (!c->have_map) return fail(c, SCG_ERR_STATE, "scg_peer_exchange_apply: scg_set_map has not been called (scale table)");
+    // A pending failure does NOT stop the exchange: the peers wait for this rank's epoch, and a voided step must reach them
+    // as a void flag (no rank applies), not as a timeout. The failure is reported after the launches.
+    const bool pending = async_pending(c) != 0;
+    char why[256];
+    memcpy(why, c->err, sizeof(why));
+    SCG_ON_DEVICE(c, "scg_peer_exchange_apply");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PeerView P;
+    memset(&P, 0, sizeof(P));
+    for (int r = 0; r < c->peer_n; ++r) {
+        P.epoch[r] = reinterpret_cast<const uint32_t *>(c->peer_base[r]);
+        P.voidw[r] = reinterpret_cast<const uint32_t *>(c->peer_base[r] + 128);
+        for (int p = 0; p < 2; ++p) P.buf[r][p] = reinterpret_cast<const float *>(c->peer_base[r] + PEER_HDR + p * c->peer_op_stride);
+    }
+    const int parity = (int)(c->peer_e & 1u);
+    const uint32_t need = c->peer_e + 1u;
+    hipLaunchKernelGGL(peer_publish_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<uint32_t *>(c->peer_region),
+                       reinterpret_cast<uint32_t *>(c->peer_region + 128), parity, (const int32_t *)c->d_fail, need);
+    SCG_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(peer_wait_kernel, dim3(1), dim3(64), 0, s, P, c->peer_n, parity, need,
+                       (unsigned long long)(c->peer_timeout_s * 1e8), c->d_peer_go, c->d_async);
+    SCG_HIP(c, hipGetLastError());
+    dim3 grid((NACT * NF + 255) / 256, c->n_vf);
+    hipLaunchKernelGGL(apply_peers_kernel, grid, dim3(256), 0, s, W, P, c->peer_n, parity, need, (const int32_t *)c->d_peer_go,
+                       c->n_vf, c->d_scale, c->cfg.alpha, c->cfg.update_count_floor);
+    SCG_HIP(c, hipGetLastError());
+    c->peer_e += 1u;
+    if (pending) { memcpy(c->err, why, sizeof(why)); return SCG_ERR_ASYNC; }
     return SCG_OK;
 }
 

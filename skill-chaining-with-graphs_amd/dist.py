@@ -87,3 +87,46 @@ def allgather_rows(t: torch.Tensor, group) -> torch.Tensor:
     dist.all_gather(parts, pad, group=group)
     out = torch.cat([p[:s] for p, s in zip(parts, sizes)])
     return out.to(t.device)
+
+
+PEER_MAX_RANKS = 8
+CHIP_WORKGROUPS = 256       # MI355X: one step workgroup per CU
+
+
+def check_peer_layout(infos) -> None:
+    """Refuse a peer-transport layout the exchange cannot serve. `infos`: one dict per rank (rank order) with `host`,
+    `device` (ordinal), `device_id` (identity of the GPU) and `grid` (workgroups of the rank's step launch).
+     * every rank on one host (HIP IPC maps memory within a node);
+     * at most 8 ranks;
+     * ranks that share ONE GPU keep the sum of their step grids below the chip's 256 workgroups: a rank's waiting wave holds a
+       CU slot while a peer's step still has to be placed. Ranks on different GPUs have no such limit."""
+    if len(infos) > PEER_MAX_RANKS:
+        raise ValueError(f"transport='peer' serves at most {PEER_MAX_RANKS} ranks, the group has {len(infos)}")
+    hosts = sorted({i["host"] for i in infos})
+    if len(hosts) > 1:
+        raise ValueError(f"transport='peer' needs every rank on one host (HIP IPC), the group spans {hosts}")
+    if len(infos) > 1 and len({i["device_id"] for i in infos}) == 1:
+        total = sum(int(i["grid"]) for i in infos)
+        if total >= CHIP_WORKGROUPS:
+            raise ValueError(f"transport='peer' with {len(infos)} ranks on one GPU: their step grids add up to {total} workgroups; "
+                             f"keep the sum below {CHIP_WORKGROUPS} (fewer envs per rank, or one GPU per rank)")
+
+
+def exchange_peer_handles(ctx, group) -> None:
+    """Give every rank of `group` the peer regions of all (once, at construction; any backend: this is not on the step path):
+    export this rank's region, all_gather_object the 64-byte handles with host name, device ordinal and step grid, check the
+    layout (check_peer_layout), then map the peers' regions (ctx.peer_open)."""
+    import socket
+    import torch.distributed as dist
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    if world > PEER_MAX_RANKS:
+        raise ValueError(f"transport='peer' serves at most {PEER_MAX_RANKS} ranks, the group has {world}")
+    dev = ctx.device
+    props = torch.cuda.get_device_properties(dev) if dev.type == "cuda" else None
+    dev_id = str(getattr(props, "uuid", "")) or f"ordinal {dev.index}"
+    mine = {"handle": ctx.peer_export(), "host": socket.gethostname(), "device": dev.index, "device_id": dev_id,
+            "grid": int(ctx.step_grid)}
+    infos = [None] * world
+    dist.all_gather_object(infos, mine, group=group)
+    check_peer_layout(infos)
+    ctx.peer_open(world, rank, [i["handle"] for i in infos])
