@@ -469,7 +469,8 @@ void sco_step(const sco_params *p, float *x, float *y, float *vx, float *vy, int
                 nx = p->starts[2 * si]; ny = p->starts[2 * si + 1]; nvx = 0.0f; nvy = 0.0f;
             }
             rec[i].sn[0] = nx; rec[i].sn[1] = ny; rec[i].sn[2] = nvx; rec[i].sn[3] = nvy;
-            int o = option_id[e] > 0 ? option_id[e] : 0;        /* (-k: inside option k's initiation set, staying with the root) */
+            /* (-k: inside option k's initiation set, staying with the root; an id outside (-n_vf, n_vf) names no option, SPEC §4.2) */
+            int o = option_id[e] > 0 && option_id[e] < n_vf ? option_id[e] : 0;
             int keep = 0;
             ro[i] = 0.0f; co[i] = 0.0f; xo[i] = 0; xg[i] = 0; rootmax[i] = 0.0f;
             if (o >= 1) {

@@ -627,7 +627,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 for (int aa = 0; aa < NACT; ++aa) qc[aa] = A.qcache[(size_t)aa * N + e];
                 ep0 = A.ep_steps[e]; o = A.option_id[e]; osteps = A.opt_steps[e];
                 o_in = o;                              // (-k: inside option k's initiation set, staying out of it — SPEC §4.2)
-                o = max(o, 0);
+                o = (o >= 1 && o < A.n_vf) ? o : 0;    // SPEC §4.2: an id outside (-n_vf, n_vf) names no option, the env runs the root
                 s_s[0 * BLOCK_ENVS + i] = sx; s_s[1 * BLOCK_ENVS + i] = sy;
                 s_s[2 * BLOCK_ENVS + i] = svx; s_s[3 * BLOCK_ENVS + i] = svy;
                 s_ot[i] = (uint8_t)o;
@@ -741,7 +741,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 if (o >= 1) {
                     const unsigned par2 = (A.parents >> (3 * (o & 7))) & 7u;       // SPEC §4.2: target of option o
                     const bool succ = (par2 == 0) ? goal : ((inA >> par2) & 1u);
-                    const bool fail = !succ && !((inA >> (o & 31)) & 1u);
+                    const bool fail = !succ && !((inA >> o) & 1u);
                     const bool otime = osteps + 1 >= A.max_opt;
                     const bool term = (dn != 0) || succ || fail || otime;
                     ro = rew + (succ ? A.r_succ : 0.0f);
@@ -765,7 +765,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 s_on[i] = (uint8_t)on;
                 s_gs[i] = (uint8_t)inS; s_ia[i] = (uint8_t)((inA & 0x3Eu) | (goal ? 1u : 0u) | ((!keep && on >= 1) ? IA_ENTERING : 0u));
                 {   // bit masks of the VFs with items / update items here: OR over the wave's lanes first, then one LDS atomic per wave
-                    const unsigned pm = (1u << (o & 31)) | (1u << (on & 31)) | inS, um = (1u << (o & 31)) | inS;
+                    const unsigned pm = (1u << o) | (1u << (on & 31)) | inS, um = (1u << o) | inS;
                     unsigned pw = 0, uw = 0;
 #pragma unroll
                     for (int k = 0; k < MAX_VF + 1; ++k) {

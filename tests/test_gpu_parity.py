@@ -264,7 +264,7 @@ def test_order_pinned_slot_sum_is_the_sequential_float_sum(n_slots):
 
 @pytest.mark.parametrize("n,dist", [
     (127, "uniform"), (129, "uniform"), (1000, "all3"), (1000, "none"), (1000, "heavy"), (4100, "uniform"),
-    (4100, "one_each"), (4100, "heavy"), (2048, "no_root"),
+    (4100, "one_each"), (4100, "heavy"), (2048, "no_root"), (1000, "wild"),
 ])
 def test_env_order_layouts_bit_exact(n, dist):
     """SPEC §5's env order in all its regimes — chunked and padded layouts, ragged last block, empty runs, no
@@ -288,6 +288,8 @@ def test_env_order_layouts_bit_exact(n, dist):
         opt = np.where(rng.random(n) < 0.95, rng.integers(1, nopt + 1, n), 0)
     elif dist == "one_each":
         opt = np.zeros(n, int); opt[[5, 700, 1300, 2500, 4000]] = [1, 2, 3, 4, 5]
+    elif dist == "wild":                                 # caller-written ids outside (-n_vf, n_vf): no option (SPEC §4.2)
+        opt = np.where(rng.random(n) < 0.2, rng.choice([33, 257, nopt + 1, -(nopt + 1), -40], n), rng.integers(0, nopt + 1, n))
     else:                                                # no_root: nobody can serve as filler
         opt = rng.integers(1, nopt + 1, n)
     st_o["option_id"][:] = opt

@@ -1,0 +1,198 @@
+"""The HIP path against the independent float64 model (tests/ref64.py): the fused step-batch under every block geometry and
+at the headline shape, the primitives at their edges, and the named edge cases of tests/test_ref64_oracle.py. Parity with
+the oracle says the two sides agree; these say that the HIP path does what SPEC §2-§7 mean."""
+import numpy as np
+import pytest
+import torch
+
+import skill_chaining_with_graphs_amd as scg
+from gpu_util import dev, set_block_envs
+from ref64 import C_G, C_PHI, U32, q_model, q_update_model
+from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
+from test_ref64_oracle import CASES, EDGES, OracleRunner, assert_rarely_ambiguous, check_step, pre_state, sweep_case
+from util import HP, SCALE, chain_classifiers, fourier_reference, random_weights
+
+pytestmark = pytest.mark.gpu
+
+STATE = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done")
+
+
+class GpuRunner(OracleRunner):
+    """The system under test on the GPU: ScgContext.step (LEARN | APPLY) from a pre-state copied to the device. The oracle
+    of the base class is kept only for the borrowed physics of the model."""
+
+    def __init__(self, map_name, n, n_options, *, seed=0, env_id_base=0, parents=None, gest=0, **hp):
+        super().__init__(map_name, n, n_options, seed=seed, env_id_base=env_id_base, parents=parents, gest=gest, **hp)
+        kw = dict(HP)
+        kw.update(hp)
+        self.ctx = ScgContext(n, n_options, self.map, device=0, seed=seed, env_id_base=env_id_base,
+                              block_envs=_BLOCK[0], **kw)
+        if parents is not None:
+            self.ctx.set_option_parents(parents)
+        self.gs = self.ctx.set_gestation(gest) if gest else None
+        self.trace = self.ctx.set_trace_buffers(8)
+        self.G, self.n_k = self.ctx.grad_buffers()
+
+    def step(self, pre, W, clf, t, enabled):
+        st = EnvState(len(pre["x"]), self.ctx.device, self.map)
+        for k in STATE:
+            getattr(st, k).copy_(dev(pre[k]))
+        W_d, clf_d = dev(W.copy()), dev(clf)
+        gs0 = self.gs.cpu().numpy().copy() if self.gs is not None else None
+        self.ctx.step(st, W_d.view(-1), clf_d.view(-1), enabled, t)
+        torch.cuda.synchronize()
+        out = {k: getattr(st, k).cpu().numpy() for k in STATE}
+        gsn = self.gs.cpu().numpy() - gs0 if self.gs is not None else np.zeros(len(W), np.int32)
+        return dict(st=out, G=self.G.cpu().numpy(), n_k=self.n_k.cpu().numpy(), W=W_d.cpu().numpy(),
+                    events=self.trace[2].cpu().numpy(), ev_len=self.trace[3].cpu().numpy(), gest_succ=gsn)
+
+
+_BLOCK = [256]
+
+
+@pytest.fixture
+def block_envs(request):
+    _BLOCK[0] = request.param
+    set_block_envs(request.param)
+    yield request.param
+    _BLOCK[0] = 256
+    set_block_envs(None)
+
+
+@pytest.mark.parametrize("cfg,block_envs", CASES, indirect=["block_envs"],
+                         ids=[f"b{b}-{c[0]}-{c[1]}-{c[2]}opt-{c[9]}" for c, b in CASES])
+def test_hip_step_matches_the_float64_model(cfg, block_envs):
+    sweep_case(GpuRunner, cfg, block_envs)
+
+
+@pytest.mark.parametrize("block_envs", [256], indirect=True)
+def test_hip_step_headline_shape(block_envs):
+    """65 536 envs, 5 options, pinball_simple: single-item resolution is lost at this size, so exact n_k and exact discrete
+    fields carry the per-item check; qcache, G and W are within tolerance."""
+    n, nopt = 65536, 5
+    r = GpuRunner("pinball_simple", n, nopt, seed=2024, env_id_base=0)
+    clf = chain_classifiers(r.map, nopt)
+    rng = np.random.default_rng(65536)
+    W = random_weights(nopt + 1, 77, std=1e-3)
+    n_amb = 0
+    for t in (0, 1, 2):
+        pre = pre_state(r.map, n, nopt, rng, max_ep=HP["max_episode_steps"], max_opt=HP["max_option_steps"])
+        n_amb += check_step(r, pre, W, clf, t, 0b111110, msg=f"t={t}")[2]
+    assert_rarely_ambiguous(n_amb, 3 * n)
+
+
+@pytest.mark.parametrize("edge", EDGES, ids=[e.__name__[5:] for e in EDGES])
+@pytest.mark.parametrize("block_envs", [256, 64], indirect=True)
+def test_hip_edge_case(edge, block_envs):
+    edge(GpuRunner)
+
+
+# ---------------------------------------------------------------------------------------------------- primitives
+
+def _edge_states():
+    g = np.array([0.0, 0.25, 0.5, 0.75, 1.0], np.float32)
+    v = np.array([-2.0, -1.0, 0.0, 1.0, 2.0], np.float32)             # s^ = 0, 0.25, 0.5, 0.75, 1
+    x, y, vx, vy = [a.ravel().copy() for a in np.meshgrid(g, g, v, v, indexing="ij")]
+    rng = np.random.default_rng(0)
+    xr, yr = rng.random(500).astype(np.float32), rng.random(500).astype(np.float32)
+    vr = rng.uniform(-2, 2, (2, 500)).astype(np.float32)
+    return np.concatenate([x, xr]), np.concatenate([y, yr]), np.concatenate([vx, vr[0]]), np.concatenate([vy, vr[1]])
+
+
+def test_features_and_q_values_at_edge_states_match_float64():
+    ctx = ScgContext(1125, 0, scg.load_map("pinball_empty"), **HP)
+    s = _edge_states()
+    d = [dev(a) for a in s]
+    phi = ctx.features(d).cpu().numpy().astype(np.float64)
+    assert np.max(np.abs(phi - fourier_reference(*s))) <= C_PHI
+    for std in (1.0, 1e3):
+        W = random_weights(1, 5, std=std)[0]
+        q = ctx.q_values(d, dev(W).view(-1)).cpu().numpy().astype(np.float64).T
+        ref, tol = q_model(*s, W)
+        assert np.all(np.abs(q - ref) <= tol), np.max(np.abs(q - ref) - tol)
+
+
+@pytest.mark.parametrize("n", [1, 257, 700])
+def test_q_update_on_explicit_transitions_matches_float64(n):
+    m = scg.load_map("pinball_simple")
+    ctx = ScgContext(700, 1, m, **HP)
+    rng = np.random.default_rng(n)
+    from util import random_states
+    s = random_states(m, n, n + 1)
+    sn = random_states(m, n, n + 2)
+    a = rng.integers(0, 5, n).astype(np.uint8)
+    r = rng.choice([-1.0, -5.0, 10000.0], n).astype(np.float32)
+    cont = np.where(rng.random(n) < 0.3, 0.0, 0.99).astype(np.float32)
+    if n > 1:
+        cont[:3] = 0.0
+    W = random_weights(2, n, std=0.05)
+    W_d = dev(W.copy())
+    G_d, n_d = ctx.grad_buffers()
+    ctx.q_update(1, [dev(v) for v in s], dev(a), dev(r), dev(cont), [dev(v) for v in sn], W_d.view(-1))
+    G, tol = q_update_model(s, a.astype(np.int64), r, cont, sn, W[1])
+    assert int(n_d.cpu().numpy()[1]) == n
+    got = G_d[1].cpu().numpy().astype(np.float64)
+    assert np.all(np.abs(got - G) <= tol), np.max(np.abs(got - G) - tol)
+    step = float(np.float32(HP["alpha"])) / n
+    Wn = W[1].astype(np.float64) + step * SCALE[None, :] * G
+    Wtol = step * SCALE[None, :] * (tol + 4 * U32 * np.abs(G)) + 2 * U32 * np.abs(Wn)
+    assert np.all(np.abs(W_d[1].cpu().numpy() - Wn) <= Wtol)
+    assert np.array_equal(W_d[0].cpu().numpy(), W[0])
+
+
+def test_apply_update_with_a_count_floor_matches_float64():
+    m = scg.load_map("pinball_simple")
+    ctx = ScgContext(256, 3, m, **dict(HP, update_count_floor=64))
+    rng = np.random.default_rng(9)
+    W = random_weights(4, 10, std=0.05)
+    G = (rng.standard_normal((4, 5, 1296)) * 10).astype(np.float32)
+    n_k = np.array([1000, 7, 0, 64], np.int32)
+    W_d = dev(W.copy())
+    ctx.apply_update(W_d.view(-1), dev(G), dev(n_k))
+    got = W_d.cpu().numpy().astype(np.float64)
+    alpha = float(np.float32(HP["alpha"]))
+    for k in range(4):
+        if n_k[k] == 0:
+            assert np.array_equal(got[k], W[k])
+            continue
+        step = alpha / max(int(n_k[k]), 64)
+        want = W[k].astype(np.float64) + step * SCALE[None, :] * G[k]
+        tol = 4 * U32 * (np.abs(want) + step * SCALE[None, :] * np.abs(G[k]))
+        assert np.all(np.abs(got[k] - want) <= tol), k
+
+
+def _fit_float64(xy, lab, w, iters, lr, l2):
+    w = w.astype(np.float64).copy()
+    u, v = 2.0 * xy[:, 0] - 1.0, 2.0 * xy[:, 1] - 1.0
+    psi = np.stack([np.ones_like(u), u, v, u * u, u * v, v * v], 1)
+    bound = np.zeros(6)
+    for _ in range(iters):
+        z = psi @ w[:6]
+        p = 1.0 / (1.0 + np.exp(-z))
+        e = p - lab
+        g = psi.T @ e / len(lab)
+        gt = (C_G * np.sqrt(len(lab) / 8192 + 40) * U32 * (np.abs(e) @ np.abs(psi)) + 1e-6 * np.abs(psi).sum(0)) / len(lab)
+        reg = np.r_[0.0, l2 * w[1:6]]
+        # a carried error is multiplied by I - lr H (0 <= H <= 6/4 + l2: |psi|^2 <= 6, sigmoid' <= 1/4): norm <= 1 for lr <= 1.3
+        bound = bound * max(1.0, abs(1 - lr * (1.5 + l2))) + lr * gt + 4 * U32 * (np.abs(w[:6]) + lr * np.abs(g + reg))
+        w[:6] = w[:6] - lr * (g + reg)
+    return w, bound
+
+
+@pytest.mark.parametrize("M", [1, 8191, 8192, 8193, 70000])
+def test_fit_initiation_matches_float64_gradient_descent(M):
+    ctx = ScgContext(256, 2, scg.load_map("pinball_simple"), **HP)
+    rng = np.random.default_rng(M)
+    xy = rng.random((M, 2)).astype(np.float32)
+    lab = (((xy[:, 0] - 0.6) ** 2 + (xy[:, 1] - 0.4) ** 2) < 0.3 ** 2).astype(np.uint8)
+    off = np.array([0, M, M], np.int32)                      # the second problem is empty: its weights stay untouched
+    w0 = np.zeros((2, 8), np.float32)
+    w0[0, :6] = [0.1, -0.2, 0.3, 0.05, -0.1, 0.2]
+    w0[1, :6] = [1.5, 2.5, -3.5, 4.5, 5.5, -6.5]
+    w_d = dev(w0.copy())
+    iters, lr, l2 = 20, 1.0, 1e-3
+    ctx.fit_initiation(dev(xy).view(-1), dev(lab), dev(off), w_d.view(-1), iters=iters, lr=lr, l2=l2)
+    got = w_d.cpu().numpy()
+    assert np.array_equal(got[1], w0[1])
+    want, bound = _fit_float64(xy.astype(np.float64), lab.astype(np.float64), w0[0], iters, lr, l2)
+    assert np.all(np.abs(got[0, :6] - want[:6]) <= bound), (got[0, :6], want[:6], bound)
