@@ -196,12 +196,6 @@ constexpr int RED_SPW = 2;         // segments per wave and round
 constexpr int RED_COLS = NACT * NF / 4;                              // float4 columns per value function
 constexpr int RED_NCOL = (RED_COLS + 63) / 64;
 
-__device__ __forceinline__ int sort_key(const int32_t *option_id, int e, int n, int n_vf) {
-    int o = e < n ? option_id[e] : -1;
-    if (o < 0 || o >= n_vf) o = e < n ? n_vf : -1;
-    return o;
-}
-
 // SPEC §5 env order from the key totals (all lanes compute the same few integers). Runs of the keys 1..6 follow one
 // another in key order; envs of key 0 (running no option) are the filler:
 //  * chunked layout (the normal case): every workgroup gets at most c envs of one option's run at its start and
@@ -1313,7 +1307,7 @@ int scg_create(scg_ctx **out, const scg_config *cfg) {
         scg_destroy(c);
         return st;
     }
-#if defined(SCG_STAMPS) || defined(SCG_STAMPS_LITE)
+#ifdef SCG_STAMPS_LITE
     if (hipMalloc(&c->d_stamps, (size_t)c->nblk * STAMP_SLOTS * sizeof(unsigned long long)) == hipSuccess)
         (void)hipMemset(c->d_stamps, 0, (size_t)c->nblk * STAMP_SLOTS * sizeof(unsigned long long));
 #endif
@@ -1568,8 +1562,8 @@ int scg_invalidate_order(scg_ctx *c) {
     return SCG_OK;
 }
 
-#if defined(SCG_STAMPS) || defined(SCG_STAMPS_LITE)
-extern "C" int scg_diag_stamps(scg_ctx *c, unsigned long long *host_out /*[nblk][16]*/, int32_t reset) {
+#ifdef SCG_STAMPS_LITE
+extern "C" int scg_diag_stamps(scg_ctx *c, unsigned long long *host_out /*[nblk][STAMP_SLOTS]*/, int32_t reset) {
     if (!c || !c->d_stamps) return SCG_ERR_STATE;
     if (host_out && hipMemcpy(host_out, c->d_stamps, (size_t)c->nblk * STAMP_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return SCG_ERR_HIP;
     if (reset) (void)hipMemset(c->d_stamps, 0, (size_t)c->nblk * STAMP_SLOTS * sizeof(unsigned long long));

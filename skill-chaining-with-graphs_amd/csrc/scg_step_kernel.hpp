@@ -26,10 +26,8 @@
 
 constexpr int P_WAVES = BLOCK_ENVS / 64;      // phase P: one lane per env on full waves
 constexpr int LIST0 = P_WAVES;                // waves LIST0 .. LIST0 + LIST_WAVES - 1 build the passes' flags and lists
-#ifndef SCG_HELPER0
-#define SCG_HELPER0 7          // (7 pool + 9 helper waves measured +1.2 % over 8 + 8, 6 + 10 +0.6 %)
-#endif
-constexpr int HELPER0 = SCG_HELPER0;          // waves HELPER0.. work under phase P (learning steps)
+constexpr int HELPER0 = 7;                    // waves HELPER0.. work under phase P (learning steps)
+                                              // (7 pool + 9 helper waves measured +1.2 % over 8 + 8, 6 + 10 +0.6 %)
 constexpr int N_HELP = WAVES - HELPER0;
 constexpr int P_POOL = HELPER0;               // waves 0..P_POOL-1 share the physics' (env, edge) pair groups
 static_assert(HELPER0 >= P_WAVES && N_HELP >= 8 && N_HELP * 64 * 3 >= 12 * 2 * 64, "stage_w by the helper waves: at most three float4 per thread");
@@ -59,37 +57,16 @@ constexpr int OFF_QSA = OFF_MAXQ + 2 * BLOCK_ENVS * 4;         // float qsa[2][B
 constexpr int OFF_EFLAG = OFF_QSA + 2 * BLOCK_ENVS * 4;        // uint8 eflag[B / 8]: per position group, bit v = value function v needs it
 constexpr int OFF_CLF = OFF_EFLAG + 64;                        // float clf[6][8]
 constexpr int OFF_MISC = OFF_CLF + MAX_VF * CLF_STRIDE * 4;    // int misc[128]
-#ifdef SCG_STAMPS
-constexpr int STAMP_SLOTS = 48;                                // 32 sections of wave 0 + the E phase of every wave
-constexpr int OFF_STAMP = OFF_MISC + 512;                      // unsigned stamp[STAMP_SLOTS] (diagnostic build)
-constexpr int LDS_BYTES = OFF_STAMP + STAMP_SLOTS * 4;
-#else
 constexpr int LDS_BYTES = OFF_MISC + 512;
-#endif
 #ifdef SCG_STAMPS_LITE
-// The light timing build (round 5): the full stamps build runs 7 % slower than the product and a change that took 3 % off ITS kernel
-// took nothing off the product's — it measures another kernel. Here four waves (an env wave, a pool wave, the first and the last
-// helper) read the clock at eight phase boundaries into scalar registers and write them out once, at the end: no LDS, no branches
-// on the way. Slots per block: [wave role 0..3][8 boundaries] cycles since the wave's kernel entry, [32] start and [33] end on the
-// 100 MHz wall clock (launch ramp across the chip).
+// The light timing build (round 5; it replaced a full stamps build that ran 7 % slower than the product). Four waves (an env wave, a
+// pool wave, the first and the last helper) read the clock at eight phase boundaries into scalar registers and write them out once,
+// at the end: no LDS, no branches on the way. Slots per block: [wave role 0..3][8 boundaries] cycles since the wave's kernel entry,
+// [32] start and [33] end on the 100 MHz wall clock (launch ramp across the chip), [34..41] the waves' HW_IDs, [42] the pair groups.
 constexpr int STAMP_SLOTS = 48;
-#if SCG_STAMPS_LITE == 3      // variant: waves 12, 13 (two of the no-op's), 0 and 3 stamp INSIDE U2 of pass 0 (tools/lite_report.py --u2)
-#define SCG_LITE(I) do { if (MODE == MODE_FUSED && lite_role >= 0 && ((I) == 0 || (I) == 7)) lt[(I)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define SCG_LITEP(I) do { } while (0)
-#define SCG_LITEU(I) do { if (MODE == MODE_FUSED && lite_role >= 0 && pass == 0) lt[(I)] = __builtin_amdgcn_s_memtime(); } while (0)
-#elif SCG_STAMPS_LITE == 2    // variant: the env wave's eight boundaries lie INSIDE phase P (the other roles keep theirs)
-#define SCG_LITE(I) do { if (MODE == MODE_FUSED && (lite_role >= 1 || (I) == 0)) lt[(I)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define SCG_LITEP(I) do { if (MODE == MODE_FUSED && lite_role == 0) lt[(I)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
 #define SCG_LITE(I) do { if (MODE == MODE_FUSED && lite_role >= 0) lt[(I)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define SCG_LITEP(I) do { } while (0)
-#endif
 #else
 #define SCG_LITE(I) do { } while (0)
-#define SCG_LITEP(I) do { } while (0)
-#endif
-#ifndef SCG_LITEU
-#define SCG_LITEU(I) do { } while (0)
 #endif
 static_assert(BLOCK_ENVS / 8 <= 64, "eflag area");
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget: one workgroup per CU");
@@ -117,37 +94,15 @@ static_assert(LIST_WAVES * 16 <= M_GROUPS && P_WAVES <= 4, "s_misc layout");
 enum { MODE_FUSED = 0, MODE_TRANS = 1, MODE_QVAL = 2 };
 constexpr unsigned IA_ENTERING = 0x40u;     // s_ia bit 6: the env is about to ENTER option s_on (SPEC §4.2 value-gated entry)
 constexpr unsigned OREC_DECLINED = 0x7fc0deadu;   // result line word [3].y: the env stays with the root after all (commit_row: option 0, the root's Q values)
-// Build-time knobs for tools/ab_bench.py (the variants measured and dropped in round 4 — evaluation-only value functions on the
-// vector pipe or behind the passes, static deals of E's and U1's units, E rebalancing — are kept as
-// profiles/r04_dropped_kernel_variants.diff with their numbers in profiles/r04_td_kernel_ab_log.txt).
-#ifndef SCG_E_TG
-#define SCG_E_TG 4            // row tiles per operand group of the LDS-fed contraction (12 % SCG_E_TG == 0)
-#endif
-#ifndef SCG_EO_TG
-#define SCG_EO_TG 3           // row tiles whose operands contract_g fetches together (register budget: 9 per tile)
-#endif
-#ifndef SCG_PRIO_P
-#define SCG_PRIO_P 2          // env waves during phase P
-#endif
-#ifndef SCG_PRIO_HELP
-#define SCG_PRIO_HELP 0       // helper waves during phase P
-#endif
-#ifndef SCG_PRIO_LIST
-#define SCG_PRIO_LIST 1       // list waves (0..3) after phase P
-#endif
-
-#ifdef SCG_STAMPS
-#define SCG_STAMP(SEC)                                                                   \
-    do {                                                                                 \
-        if (MODE == MODE_FUSED && A.stamps && tid == 0) {                                \
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime();                  \
-            s_stamp[(SEC)] += (unsigned)(t_ - stamp_prev);                               \
-            stamp_prev = t_;                                                             \
-        }                                                                                \
-    } while (0)
-#else
-#define SCG_STAMP(SEC) do { } while (0)
-#endif
+// Tuning constants, settled by round-4 A/Bs (tools/ab_bench.py; to measure one again, edit it in a worktree: tools/ab_trees.py). The
+// variants measured and dropped in round 4 — evaluation-only value functions on the vector pipe or behind the passes, static deals
+// of E's and U1's units, E rebalancing — are kept as profiles/r04_dropped_kernel_variants.diff with their numbers in
+// profiles/r04_td_kernel_ab_log.txt.
+constexpr int E_TG = 4;               // row tiles per operand group of the LDS-fed contraction (12 % E_TG == 0)
+constexpr int EO_TG = 3;              // row tiles whose operands contract_g fetches together (register budget: 9 per tile)
+constexpr int PRIO_P = 2;             // env waves during phase P
+constexpr int PRIO_HELP = 0;          // helper waves during phase P
+constexpr int PRIO_LIST = 1;          // list waves (0..3) after phase P
 
 template <int M>
 __device__ __forceinline__ int sel5(const int (&v)[M], int a) {          // v[a], a < 5, without a dynamically indexed array
@@ -253,28 +208,15 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     int *s_misc = reinterpret_cast<int *>(smem + OFF_MISC);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef SCG_DIAG_ROTATE          // (diagnostic: workgroup p works on block (p + SCG_DIAG_ROTATE) % grid — same results; do the slow blocks follow the DATA or the PLACE? tools/straggler_report.py)
-    const int b = (int)((blockIdx.x + SCG_DIAG_ROTATE) % gridDim.x);
-#else
     const int b = blockIdx.x;
-#endif
     const int e0 = b * BLOCK_ENVS;
     const int nb = min(BLOCK_ENVS, A.n - e0);
     const int N = A.n;
 #ifdef SCG_STAMPS_LITE
-#if SCG_STAMPS_LITE == 3
-    const int lite_role = wave == 12 ? 0 : wave == 13 ? 1 : wave == 0 ? 2 : wave == 3 ? 3 : -1;
-#else
     const int lite_role = wave == 0 ? 0 : wave == P_WAVES ? 1 : wave == HELPER0 ? 2 : wave == WAVES - 1 ? 3 : -1;
-#endif
     unsigned long long lt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long lite_r0 = __builtin_amdgcn_s_memrealtime();
     SCG_LITE(0);
-#endif
-#ifdef SCG_STAMPS
-    unsigned *s_stamp = reinterpret_cast<unsigned *>(smem + OFF_STAMP);
-    if (tid < STAMP_SLOTS) s_stamp[tid] = 0;
-    unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
 #endif
 
     // private tables of one 8-item column block from the builder lane's item `it` (already clamped by the caller),
@@ -458,7 +400,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     };
     // ... A operands from the value function staged at float offset `wofs` of region W (two ds_read_b128 + one ds_read_b32 per tile)
     auto contract = [&](int wofs, const float (&B)[9], float (&qo)[NACT], int n16, int g, const f4v *w4, const float *w8, const float *ab_lane) {
-        contract_with(std::integral_constant<int, SCG_E_TG>{}, [&](int t, f4v &a0, f4v &a1, float &a8) {
+        contract_with(std::integral_constant<int, E_TG>{}, [&](int t, f4v &a0, f4v &a1, float &a8) {
             a0 = w4[wofs / 4 + (t * 2) * 64]; a1 = w4[wofs / 4 + (t * 2 + 1) * 64]; a8 = w8[wofs + t * 64];
         }, B, qo, g, ab_lane);
     };
@@ -467,7 +409,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     // envs that ENTER an option nobody in the block runs: its weights are not staged anywhere in this workgroup.
     auto contract_g = [&](const float *Wk, const float (&B)[9], float (&qo)[NACT], int n16, int g, const float *ab_lane) {
         struct __attribute__((packed, aligned(4))) F4U { float x, y, z, w; };
-        contract_with(std::integral_constant<int, SCG_EO_TG>{}, [&](int t, f4v &a0, f4v &a1, float &a8) {
+        contract_with(std::integral_constant<int, EO_TG>{}, [&](int t, f4v &a0, f4v &a1, float &a8) {
             const int row = 16 * t + n16;
             a0 = (f4v){0.0f, 0.0f, 0.0f, 0.0f}; a1 = a0; a8 = 0.0f;
             if (row < NACT * 36) {
@@ -609,7 +551,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     }
 
     // ------------------------------------------------------------------ phase P
-    if (helpers) { if (wave < P_WAVES) __builtin_amdgcn_s_setprio(SCG_PRIO_P); else if (wave >= HELPER0) __builtin_amdgcn_s_setprio(SCG_PRIO_HELP); }
+    if (helpers) { if (wave < P_WAVES) __builtin_amdgcn_s_setprio(PRIO_P); else if (wave >= HELPER0) __builtin_amdgcn_s_setprio(PRIO_HELP); }
     if (wave < P_WAVES) {                             // one lane per env on P_WAVES full waves
         const int i = tid;
         const bool valid = i < nb;
@@ -635,8 +577,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 s_ot[i] = 255;
             }
             lds_arrive(&s_misc[M_C_PUBS], 64);
-            SCG_LITEP(1);                                         // entry state gathered and published
-            SCG_STAMP(17);                                        // P: perm + state gathers
             if (valid) {
                 // act (SPEC §2, §4.3)
                 const uint64_t gid = (uint64_t)(A.env_base + e);
@@ -655,9 +595,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             } else {
                 s_a[i] = 0;
             }
-            SCG_STAMP(16);                                        // P: qcache gathers, Philox, action
             lds_arrive(&s_misc[M_C_PUB], 64);                                     // state, action and option id of this wave's envs are out
-            SCG_LITEP(2);
             // physics (SPEC §1.3), the whole wave together
             bool goal;
             // the envs' own wave settles free flight and lists the (env, candidate edge) pairs of the others in groups of 64;
@@ -665,26 +603,10 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             bool par;
             float *xs_mine = s_s + 4 * BLOCK_ENVS + wave * 64;
             lds_await(&s_misc[M_C_TOP], WAVES - P_WAVES);                         // the edge and classifier tables are in LDS
-#ifdef SCG_DIAG_NO_PHYSICS         // (diagnostic, WRONG results: prices a step kernel WITHOUT phase P's physics at its head — VERDICT r4 item 1c)
-            goal = false; par = false;                  // free flight through everything (20 fmas; keeps the batch moving so that the
-            {                                           // option / action mix of the timed workload stays what it is with physics)
-                const float DV = 0x1.99999ap-3f;
-                svx = fminf(fmaxf(a == 0 ? svx + DV : (a == 2 ? svx - DV : svx), -2.0f), 2.0f);
-                svy = fminf(fmaxf(a == 1 ? svy + DV : (a == 3 ? svy - DV : svy), -2.0f), 2.0f);
-                for (int q = 0; q < 20; ++q) { sx = fmaf(svx, A.ms.hstep, sx); sy = fmaf(svy, A.ms.hstep, sy); }
-                if (sx < 0.0f || sx > 1.0f) svx = -svx;
-                if (sy < 0.0f || sy > 1.0f) svy = -svy;
-                svx *= 0x1.fd70a4p-1f; svy *= 0x1.fd70a4p-1f;
-                sx = fminf(fmaxf(sx, 0.0f), 1.0f); sy = fminf(fmaxf(sy, 0.0f), 1.0f);
-            }
-            const float rew = a == 4 ? -1.0f : -5.0f;
-#else
             const int groups = pinball_wave_prepare_any(s_edges, A.cellmask, A.ms, valid, sx, sy, svx, svy, a, goal, par,
                                                         s_pitems + wave * PITEMS, xs_mine, BLOCK_ENVS);
             if (lane == 0) s_misc[M_GROUPS + wave] = groups;
             lds_arrive(&s_misc[M_C_PREP], 1);
-            SCG_LITEP(3);                                         // own part of the physics done, pair groups listed
-            SCG_STAMP(18);                                        // P: physics, own part (refinement, free flight, pair lists)
             {
                 lds_await(&s_misc[M_C_PREP], P_WAVES);
                 int gsum[P_WAVES + 1];
@@ -708,9 +630,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 lds_await(&s_misc[M_C_POOL], P_POOL);
             }
             const float rew = pinball_wave_finish(par, sx, sy, svx, svy, a, goal, xs_mine, BLOCK_ENVS, s_ia + wave * 64);
-#endif
-            SCG_LITEP(4);                                         // pooled pair groups done (everybody's), results read back
-            SCG_STAMP(2);                                         // P: physics, the pooled pair groups + hand-offs
             int hkey = -1;
             if (valid) {
                 // bookkeeping (SPEC §1.4)
@@ -795,8 +714,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                                           __int_as_float(osn), __int_as_float(epn));
                     reinterpret_cast<float *>(orec + 3)[1] = 0.0f;        // not declined (this lane alone writes the word: here and in gate())
                 }
-                SCG_LITEP(5);
-                SCG_STAMP(19);                                        // P: bookkeeping, option logic, result line
                 if (A.ring_x) {                                       // SPEC §7: trajectory ring + events
                     const size_t row = (size_t)(ep0 & A.ring_mask) * N + e;
                     A.ring_x[row] = s_s[0 * BLOCK_ENVS + i]; A.ring_y[row] = s_s[1 * BLOCK_ENVS + i];
@@ -819,7 +736,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                     rem &= ~m;
                 }
             }
-            SCG_LITEP(6);                                         // trace, events, histogram issued
         } else if (valid) {
             if (MODE == MODE_TRANS) {
                 s_s[0 * BLOCK_ENVS + i] = A.x[e]; s_s[1 * BLOCK_ENVS + i] = A.y[e];
@@ -839,7 +755,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             s_a[i] = 0; s_ot[i] = 255; s_on[i] = 255; s_gs[i] = 0; s_ia[i] = 0;
         }
     } else if (MODE == MODE_FUSED && wave < P_POOL) {   // no envs of its own: takes its share of the physics' pair groups
-#ifndef SCG_DIAG_NO_PHYSICS
         lds_await(&s_misc[M_C_PREP], P_WAVES);
         int gsum[P_WAVES + 1];
         gsum[0] = 0;
@@ -853,19 +768,10 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                                s_s + 4 * BLOCK_ENVS + owner * 64, BLOCK_ENVS, s_ia + owner * 64);
         }
         lds_arrive(&s_misc[M_C_POOL], 1);
-#endif
     } else if (helpers && wave >= HELPER0) {
         const int ht = tid - HELPER0 * 64, hw = wave - HELPER0;       // helper thread / wave index
         constexpr int NHT = N_HELP * 64;
-#ifdef SCG_STAMPS
-#define SCG_HSTAMP(SEC) do { if (ht == 0 && A.stamps) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); s_stamp[(SEC)] += (unsigned)(t_ - hprev); hprev = t_; } } while (0)
-        unsigned long long hprev = stamp_prev;
-#else
-#define SCG_HSTAMP(SEC) do { } while (0)
-#endif
-        SCG_HSTAMP(10);
         lds_await(&s_misc[M_C_PUBS], 64 * P_WAVES);                                    // the P waves have published s and the option ids
-        SCG_HSTAMP(11);
         decide_b();
         if (hw == 0 && lane == 0) { s_misc[M_KB] = kB; s_misc[M_MB] = mB; }
         if (kB >= 1) stage_w(A.W + (size_t)kB * NACT * NF, W_FLOATS, ht, NHT);
@@ -882,9 +788,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         }
         // the root's update list (every env, one run per action, block order inside a run): each helper wave derives the
         // run geometry itself from ballots; helper wave 0 writes the list
-        SCG_HSTAMP(12);
         lds_await(&s_misc[M_C_PUB], 64 * P_WAVES);                                     // ... and the actions
-        SCG_HSTAMP(13);
         {
             uint64_t mk[P_WAVES][NACT];
             int at[P_WAVES];
@@ -907,37 +811,18 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
 #endif
         lds_arrive(&s_misc[M_C_HELP], 1);
         lds_await(&s_misc[M_C_HELP], N_HELP);                                  // W_0, W_kB, Z(s) and the list are complete
-        SCG_HSTAMP(14);
-#ifdef SCG_DIAG_SIMD0_FREE      // (diagnostic, correct results) the helper waves that share SIMD 0 with env wave 0 leave U1 to the others
-        if ((wave & 3) != 0)
-#endif
         run_u1_dyn();
-#ifdef SCG_STAMPS
-        if (ht == 0 && A.stamps) s_stamp[28] += (unsigned)(__builtin_amdgcn_s_memtime() - stamp_prev);   // helper wave 0: start -> done
-#endif
     }
     else if (MODE == MODE_FUSED && wave == HELPER0) {      // acting-only steps: this wave still settles the block's option
         lds_await(&s_misc[M_C_PUBS], 64 * P_WAVES);
         decide_b();
         if (lane == 0) { s_misc[M_KB] = kB; s_misc[M_MB] = mB; }
     }
-#ifdef SCG_DIAG_NO_PHYSICS
-    if (helpers && wave < HELPER0) {                    // (diagnostic) with no physics to run, waves 0..HELPER0-1 join the helpers' U1
-        lds_await(&s_misc[M_C_HELP], N_HELP);
-        mB = s_misc[M_MB];
-        uint64_t mk[P_WAVES][NACT];
-        int at[P_WAVES];
-        u1_geometry(mk, at);
-        run_u1_dyn();
-    }
-#endif
-    if (helpers) { if ((unsigned)(wave - LIST0) < (unsigned)LIST_WAVES) __builtin_amdgcn_s_setprio(SCG_PRIO_LIST); else __builtin_amdgcn_s_setprio(0); }
+    if (helpers) { if ((unsigned)(wave - LIST0) < (unsigned)LIST_WAVES) __builtin_amdgcn_s_setprio(PRIO_LIST); else __builtin_amdgcn_s_setprio(0); }
     SCG_LITE(2);                                            // this wave's own phase-P work is done
     block_lds_sync();
     SCG_LITE(3);                                            // ... everybody's
-    SCG_LITEP(7);
 
-    SCG_STAMP(0);   // phase P
     // ------------------------------------------------------------------ phase Z (SPEC §3): Z_d^1 of s_next (and of s where no helper did it)
     for (int u = tid; u < BLOCK_ENVS * 8; u += THREADS) {     // thread -> (state sg, env i, variable d): four consecutive lanes write one env's 32 bytes
         const int i = (u >> 2) & (BLOCK_ENVS - 1), d = u & 3, sg = u / (4 * BLOCK_ENVS);      // (one lane per env and variable 64 bytes apart was a 32-way bank conflict)
@@ -1015,7 +900,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         if (MODE == MODE_FUSED && pass > 0 && kA == __builtin_ctz(single0)) {      // first single pass: save the root's max_a Q_0(s_next, a) of pass 0
             if (tid < nb) s_qsa[BLOCK_ENVS + tid] = s_maxq[tid];                 // before this pass's E reuses s_maxq (s_qsa's second half: B's Q(s, a), pass 0 only)
         }
-        SCG_STAMP(pass == 0 ? 5 : 12);   // (diagnostic) wait at the pass's first barrier
         // ---- per-env flags of the pass (SPEC §5): ev bit v = the env needs Q_v(s_next, .) (bootstrap target and/or next
         // action); update items of A (all of them in pass 0 of a fused step: the root updates on every env) with their action
         // The flags and lists are made by waves LIST0 .. LIST0 + 3 (thread ft <-> position ft), not by the env waves 0..3: those still
@@ -1080,16 +964,13 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 }
             }
         }
-        SCG_STAMP(23);                                       // (diagnostic) flags + ballots
         if (!u1_done) {                                      // (the helper waves staged W_0 / W_kB under phase P)
             // (kA / kBp are wave-uniform: readfirstlane keeps the pointer arithmetic on the scalar unit)
             const float *Wa = A.W + (MODE == MODE_QVAL ? 0 : (size_t)__builtin_amdgcn_readfirstlane(kA) * NACT * NF);
             stage_w_cold(Wa, s_W, tid);
             if (kBp >= 1) stage_w_cold(A.W + (size_t)__builtin_amdgcn_readfirstlane(kBp) * NACT * NF, s_W + W_FLOATS, tid);
         }
-        SCG_STAMP(24);                                       // (diagnostic) W staging
         block_lds_sync();
-        SCG_STAMP(25);                                       // (diagnostic) wait at the barrier behind the staging
         int n_cmp = 0, nupdB = 0;
         {
             int se = 0;
@@ -1161,7 +1042,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             A.cnts[(size_t)b * A.n_vf + kA] = nupd;
             if (kBp >= 1) A.cnts[(size_t)b * A.n_vf + kBp] = nupdB;
         }
-        SCG_STAMP(pass == 0 ? 1 : 8);    // phase Z (first pass only) + list build + W staging
         if (pass == 0) SCG_LITE(4);                         // E starts
         // ---- E: Q_v(s_next, .), one 8-item column block per wave-iteration (SPEC §3.1); the tables of a block are built
         // once and serve both value functions. Units [0, npg) are position groups (dense pass), the rest 8-item blocks of
@@ -1172,9 +1052,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         const int n_units = npg + n_own + eo_units;
         if (n_units + nupd == 0) continue;
         {
-#ifdef SCG_STAMPS
-        const unsigned long long e_t0 = __builtin_amdgcn_s_memtime();
-#endif
         // Dealing: units are taken from a counter in LDS by whichever wave is free (a static deal left the four top waves —
         // the youngest of their SIMDs — 15k cycles behind the others). Order: the compacted units first (the pass's own list,
         // then the evaluation-only value functions', which wait on memory for their operands and want LDS-fed units beside
@@ -1262,19 +1139,13 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             }
             wave_lds_sync();
         }
-#ifdef SCG_STAMPS
-        if (pass == 0 && MODE == MODE_FUSED && A.stamps && lane == 0) s_stamp[32 + wave] += (unsigned)(__builtin_amdgcn_s_memtime() - e_t0);
-#endif
         }
-        SCG_STAMP(pass == 0 ? 3 : 10);   // E (wave 0's share)
         // ---- U1 (pass 0 of a learning step: ran under phase P on the helper waves)
         if (MODE != MODE_QVAL && nupd > 0 && !u1_done) run_u1(wave, WAVES, n_units);   // dealt on behind E's blocks
         if (MODE == MODE_QVAL || nupd == 0) continue;
-        SCG_STAMP(pass == 0 ? 4 : 11);   // U1 (wave 0's share)
         if (pass == 0) SCG_LITE(5);                         // this wave's E is done
         block_lds_sync();                                   // s_maxq, s_qsa cross waves; the staging area changes hands
         if (pass == 0) SCG_LITE(6);                         // ... everybody's: U2 starts
-        SCG_STAMP(pass == 0 ? 7 : 14);   // wait for the other waves
 
         // ---- U2: the block partials (SPEC §5). Every action run of A's list is padded with null items to a multiple of 4
         // (groups of four items); run a has Ga groups, the first GBa of which also carry items of B. The groups are laid out in
@@ -1382,9 +1253,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         };
         auto u2_mfma = [&](int ch, const float *tab) {
             if (!worker) return;
-#ifdef SCG_DIAG_FREE_BORDER         // (diagnostic, WRONG results: prices U2's five border tiles at zero — the ceiling of "border tiles on the vector pipe")
-            if (jm == 2) return;
-#endif
             int gb[NACT], gc[NACT], co[NACT + 1];
             chunk_geo(ch, gb, gc, co);
             const float *ptabA = tab, *ctab = tab + 2 * 36 * USX;                // (PT_B lies between them)
@@ -1401,7 +1269,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             // group (tools/u2_loop_probe.hip). Hence: straight-line loops (the groups that carry items of B — the one group that can hold
             // null items peeled off —, then the rest) on two operand sets, the NEXT group's operands fetched before this group's products
             // are issued; a fetch past the run's end reads inside the chunk tables.
-            // The whole walk is ONE asm statement on fixed operand registers (v108..v127), accumulators tied (vdst = srcC). As builtins the
+            // The whole walk is ONE asm statement on fixed operand registers (v100..v119), accumulators tied (vdst = srcC). As builtins the
             // register allocator kept two copies of every accumulator round the loops: per iteration of 12 products `s_nop 6` (the copies
             // read MFMA results: the pipe drains), 10-18 v_mov_b64 on the pipe the products use and two taken branches — the 1.35-1.8x
             // between this loop in the kernel and in the probe (profiles/r05_u2_anatomy.txt item 5; found by reading the ISA). The compiler's
@@ -1471,20 +1339,12 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
 #undef U2_LDS
             accU[0][0] = x0; accU[0][1] = x1; accU[0][2] = x2; accU[1][0] = y0; accU[1][1] = y1; accU[1][2] = y2;
         };
-        SCG_LITEU(1);                                            // (light stamps, variant 3) U2 starts
         for (int ch = 0; ch < nch; ++ch) {
-            if (ch > 0) { block_lds_sync(); SCG_LITEU(4); }                   // previous chunk's operands consumed
-            SCG_STAMP(20);                                                    // (diagnostic) U2: MFMAs of the previous chunk + wait
+            if (ch > 0) block_lds_sync();                        // previous chunk's operands consumed
             u2_build(ch, s_R, wave);
-            SCG_STAMP(21);                                       // (diagnostic) U2: build
             block_lds_sync();                                    // operands visible
-            SCG_STAMP(22);                                       // (diagnostic) U2: wait for the other waves' build
-            if (ch == 0) SCG_LITEU(2); else SCG_LITEU(5);
             u2_mfma(ch, s_R);
-            if (ch == 0) SCG_LITEU(3); else SCG_LITEU(6);
-            SCG_STAMP(9);                                        // (diagnostic) U2: this wave's own products of the chunk
         }
-        SCG_STAMP(pass == 0 ? 6 : 13);   // U2
         // the block partials straight from the accumulators (zeros for an empty run). The tiles were accumulated
         // TRANSPOSED (A operand = CDT rows, B operand = PT rows; fma(a, b, c) = fma(b, a, c)), so register v of lane (n16, g)
         // of tile (mi, ni) is G[a][c12 = 16 mi + n16][c34 = 16 ni + 4 g + v]: one 16-byte store per lane and tile
@@ -1506,7 +1366,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             A.cnts[(size_t)b * A.n_vf + kA] = 0;
             if (kBp >= 1) A.cnts[(size_t)b * A.n_vf + kBp] = 0;
         }
-        SCG_STAMP(15);                // slab stores issued
         if (pass == 0) SCG_LITE(7);                         // pass 0 done (slab stores issued)
         if (pass > 0) gate(kA);
     }
@@ -1533,12 +1392,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         unsigned hwid;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
         reinterpret_cast<unsigned *>(A.stamps + (size_t)blockIdx.x * STAMP_SLOTS + 34)[wave] = hwid;
-    }
-#endif
-#ifdef SCG_STAMPS
-    if (MODE == MODE_FUSED && A.stamps) {
-        __syncthreads();
-        if (tid < STAMP_SLOTS) A.stamps[(size_t)blockIdx.x * STAMP_SLOTS + tid] += s_stamp[tid];
     }
 #endif
 }

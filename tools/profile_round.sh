@@ -1,5 +1,6 @@
 #!/bin/bash
-# The per-round evidence set behind DESIGN §5 / profiles/rNN_*: run on the GPU box from the repo root,
+# The per-round evidence set behind DESIGN §5 / profiles/rNN_*: run on the GPU box from the repo root, after the light timing build,
+#   make -C skill-chaining-with-graphs_amd/csrc lite
 #   bash tools/profile_round.sh gpurun_out/<dir>
 # then copy <dir>/{bench_default.json,bench_20_steps.json,kernel_stats.csv,pmc.csv,stamps.txt,traffic.json} into profiles/.
 # Counter passes are separate rocprofv3 runs with --kernel-trace only (never combined with other trace domains).
@@ -21,6 +22,6 @@ done
 cd "$root"
 python tools/pmc_summary.py "$out"/pmc[0-9] > "$out/pmc.csv"
 python tools/pmc_summary.py --traffic "$out/pmc.csv" > "$out/traffic.json"
-python tools/stamp_report.py > "$out/stamps.txt" 2>&1
+python tools/lite_report.py > "$out/stamps.txt" 2>&1
 rm -rf "$out"/pmc[0-9] "$out/stats"
 echo "profile set written to $1"

@@ -6,9 +6,7 @@ import argparse, ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 ap = argparse.ArgumentParser(); ap.add_argument("--launches", type=int, default=24)
-ap.add_argument("--rotate", type=int, default=0, help="the library was built with -DSCG_DIAG_ROTATE=R (make lite_rot: 100): workgroup p holds block (p + R) %% grid")
 ap.add_argument("--pad-kb", type=int, default=0, help="allocate this much device memory BEFORE the agent's buffers (moves every buffer: does the slow set follow the addresses?)")
-ap.add_argument("--p-internal", action="store_true", help="the library is the SCG_STAMPS_LITE=2 build (make lite_p): env wave 0's boundaries lie INSIDE phase P")
 ap.add_argument("--options", type=int, default=5); ap.add_argument("--seed", type=int, default=1000)
 args = ap.parse_args()
 from skill_chaining_with_graphs_amd import _lib
@@ -70,8 +68,6 @@ for it in range(args.launches):
     agent.step_batch(); torch.cuda.synchronize()
     out = np.zeros((nblk, 48), np.uint64)
     lib.scg_diag_stamps(ctx, out.ctypes.data_as(C.c_void_p), 0)
-    if args.rotate:                                        # stamps are stored per WORKGROUP: re-index them by the block the workgroup held
-        out = out[(np.arange(nblk) - args.rotate) % nblk]
     dur = (out[:, 33].astype(np.int64) - out[:, 32].astype(np.int64)) / 100.0
     groups.append(out[:, 42].astype(np.float64))
     ticks.append(out[:, :8].astype(np.float64))           # env wave 0: [0] whole kernel, [1..7] the phase boundaries (s_memtime since entry)
@@ -126,18 +122,6 @@ for gv in np.unique(G):
     m = G == gv
     print(f"   {int(gv):3d} groups: {int(m.sum()):6d} blocks  {d[m].mean():6.2f} us   {is_max[m].sum() / args.launches:5.2f}")
 seg = np.stack([tk[:, 3], tk[:, 4] - tk[:, 3], tk[:, 6] - tk[:, 4], tk[:, 7] - tk[:, 6], tk[:, 0] - tk[:, 7]], 1)
-if args.p_internal:
-    slow = d >= np.percentile(d, 97); rest = d <= np.percentile(d, 60)
-    names = ["entry state gathered + published", "action chosen + published", "own physics done, pair groups listed", "pooled pair groups done, results read back", "result line written",
-             "trace, events, histogram issued", "phase-P barrier passed"]
-    print(f"phase P of env wave 0 (s_memtime since entry), slowest 3 % of the blocks ({int(slow.sum())}) against the lower 60 % ({int(rest.sum())}): wall {d[slow].mean():.2f} / {d[rest].mean():.2f} us")
-    prev_s = prev_r = 0.0
-    for i, nm in enumerate(names, 1):
-        a, b_ = tk[slow, i].mean(), tk[rest, i].mean()
-        print(f"  {nm:44s} {a:9.0f} {b_:9.0f}   step {a - prev_s:7.0f} {b_ - prev_r:7.0f}  {(a - prev_s) - (b_ - prev_r):+7.0f}")
-        prev_s, prev_r = a, b_
-    print(f"  {'whole kernel':44s} {tk[slow, 0].mean():9.0f} {tk[rest, 0].mean():9.0f}")
-    sys.exit(0)
 lab = ["head (-> P barrier)", "Z + lists", "E (-> barrier)", "U2", "tail"]
 slow = d >= np.percentile(d, 97); rest = d <= np.percentile(d, 60)
 print(f"same launches, env wave 0's s_memtime ticks: slowest 3 % of the blocks ({int(slow.sum())}) against the lower 60 % ({int(rest.sum())})")
@@ -149,10 +133,6 @@ bi = r[:, 6].astype(int)
 cnt = np.bincount(bi[slow], minlength=nblk)
 print("blocks most often among the slowest 3 %:", [(int(b), int(c)) for b, c in zip(np.argsort(cnt)[::-1][:14], np.sort(cnt)[::-1][:14])])
 print("... by position in the env order (16 bins of 16 blocks), share of the slow set:", " ".join(f"{cnt[16 * k:16 * k + 16].sum() / max(cnt.sum(), 1):.2f}" for k in range(16)))
-if args.rotate:
-    pc = cnt[(np.arange(nblk) + args.rotate) % nblk]      # pc[p] = how often WORKGROUP p was slow
-    print(f"(rotated by {args.rotate}: block = (workgroup + {args.rotate}) % {nblk}) by WORKGROUP position (16 bins):", " ".join(f"{pc[16 * k:16 * k + 16].sum() / max(pc.sum(), 1):.2f}" for k in range(16)))
-    print("... by XCD of the WORKGROUP (workgroup % 8):", " ".join(f"{pc[x::8].sum() / max(pc.sum(), 1):.2f}" for x in range(8)))
 print("... by XCD (block % 8):", " ".join(f"{cnt[x::8].sum() / max(cnt.sum(), 1):.2f}" for x in range(8)))
 
 ex = np.stack(extra, 0).astype(np.float64)          # [launch, block, feature]
