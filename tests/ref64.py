@@ -6,8 +6,9 @@ of absolute values (constants below), so that it checks WHAT is summed — which
 with which target — and not how.
 
 Borrowed piece: the physics (SPEC §1.3). `s'`, the reward and the goal flag come from the oracle's `pinball_step` on the
-pre-state and the model's own action. The physics has known answers and property tests of its own
-(tests/test_oracle_pinball.py), and a float64 physics would make collision ties a project of its own.
+pre-state and the model's own action, so that the rest of the step follows the binary32 physics exactly. The borrowed
+physics is checked: on every env that the float64 physics model (tests/phys64.py) does not call ambiguous, `s'` agrees
+with it to its tolerance and the reward and the goal flag exactly.
 
 Everything else is computed here: Philox4x32-10 in vectorised numpy (pinned by the published vectors), the action, the episode
 bookkeeping, the classifier (float64 quadratic), the option logic, the value gate, the update items and their targets, the
@@ -22,6 +23,7 @@ from __future__ import annotations
 
 import numpy as np
 
+import phys64
 from util import fourier_reference
 
 NACT, NF = 5, 1296
@@ -141,6 +143,7 @@ class StepModel:
         s = [pre[k].astype(np.float32).copy() for k in ("x", "y", "vx", "vy")]
         sp = [v.copy() for v in s]
         reward, goal = self.orc.pinball_step(*sp, a.astype(np.uint8))          # the borrowed physics: s', reward, goal
+        phys64.compare(phys64.step(self.map, *s, a), *sp, reward, goal, msg="borrowed physics against tests/phys64.py:")
         reward = reward.astype(np.float64)
         goal = goal.astype(bool)
         eps1 = pre["ep_steps"].astype(np.int64) + 1

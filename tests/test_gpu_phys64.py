@@ -1,0 +1,248 @@
+"""The HIP physics at the limits of its candidate pruning and pair dealing, against the oracle (bit for bit) and the float64
+model of SPEC §1.3 (tests/phys64.py, to tolerance).
+
+Every case runs through ScgContext.pinball_step (pinball_kernel) and through one fused step-batch (ScgContext.step, acting
+only and learning) from the constructed states, on the 256-, 128- and 64-env builds:
+- reach: balls at the corners of their 32 x 32 cell at full diagonal speed that first touch an edge on sub-step 18, 19 or
+  20 — the edges lie beyond the cell-mask reach a smaller vmax would give, and beyond a smaller refined reach — and balls
+  in free flight that reach the goal on those sub-steps;
+- saturated dealing: every env of a block with exactly 8 candidate edges (8 pair groups per wave, 32 per 256-env block),
+  the wasteful run pattern, waves that mix free flight, 7, 8, 9 and 13 candidates, and a block wholly in the per-lane loop;
+- decoys: edges that are candidates but provably never intercept push one set of trajectories through free flight, pair
+  runs of every length 1..8 and the per-lane loop; every variant must give the same bits;
+- mask words: maps of 64 / 65 / 128 / 129 / 256 edges with balls hitting edges 63, 64, 127, 128 and 255.
+Candidate counts and group counts come from the host restatement in tests/util.py."""
+import numpy as np
+import pytest
+import torch
+
+import phys64
+import sc_oracle
+from gpu_util import assert_state_equal, dev, set_block_envs, state_to_device
+from skill_chaining_with_graphs_amd.core import ScgContext
+from test_phys64_oracle import BOUNDARY_EDGES, boundary_states
+from util import (CELL_G, HP, SCALE, edge_count_map, kernel_candidates, pair_groups, pocket_map)
+
+pytestmark = pytest.mark.gpu
+
+f32 = np.float32
+SQ8 = float(np.sqrt(f32(8.0)))
+KW = dict(HP, epsilon=0.0)                 # greedy on a one-hot qcache: the fused step takes the action the test gives
+
+
+@pytest.fixture(params=[256, 128, 64], ids=lambda b: f"b{b}")
+def block(request):
+    set_block_envs(request.param)
+    yield request.param
+    set_block_envs(None)
+
+
+def run_all(m, block, x, y, vx, vy, a, msg=""):
+    """pinball_step and the fused step (acting, learning) from the same states: each bit for bit against the oracle, and
+    against the float64 model. Returns (model result, pinball_step outputs)."""
+    n = len(x)
+    x, y, vx, vy = (np.asarray(v, f32) for v in (x, y, vx, vy))
+    a = np.broadcast_to(np.asarray(a, np.uint8), (n,)).copy()
+    res = phys64.step(m, x, y, vx, vy, a)
+    ctx = ScgContext(n, 0, m, device=0, block_envs=block, **KW)
+    orc = sc_oracle.Oracle(m, SCALE, n_envs=n, n_options=0, n_threads=8, **KW)
+    try:
+        # the un-fused kernel
+        s = [dev(v.copy()) for v in (x, y, vx, vy)]
+        r_d, g_d = ctx.pinball_step(s, dev(a))
+        torch.cuda.synchronize()
+        got = [t.cpu().numpy() for t in s] + [r_d.cpu().numpy(), g_d.cpu().numpy()]
+        want = [v.copy() for v in (x, y, vx, vy)]
+        r_o, g_o = orc.pinball_step(*want, a)
+        for k, gv, wv in zip(("x", "y", "vx", "vy", "reward", "goal"), got, want + [r_o, g_o]):
+            assert np.array_equal(gv.view(np.uint32) if gv.dtype == f32 else gv, wv.view(np.uint32) if wv.dtype == f32 else wv), \
+                f"{msg} pinball_step {k}: {np.sum(gv != wv)} envs differ from the oracle"
+        namb = phys64.compare(res, *got, msg=f"{msg} pinball_step")
+        assert namb == 0, f"{msg}: {namb} ambiguous envs in a constructed case"
+        # the fused step, acting only and learning
+        for learn in (False, True):
+            st = sc_oracle.new_state(n, m)
+            st["x"][:], st["y"][:], st["vx"][:], st["vy"][:] = x, y, vx, vy
+            st["qcache"][a, np.arange(n)] = 1.0
+            W = np.zeros((1, 5, 1296), f32)
+            clf = np.zeros((1, 8), f32)
+            st_d = state_to_device(st, ctx)
+            ctx.step(st_d, dev(W).view(-1), dev(clf).view(-1), 0, 0, learn=learn, apply=learn)
+            orc.step(st, W, clf, 0, enabled_mask=0)
+            torch.cuda.synchronize()
+            assert_state_equal(st_d, st, msg=f"{msg} fused learn={learn}")
+            assert np.array_equal(st["action"], a)
+            goal = st["done"] == 1
+            assert np.array_equal(goal[~res["ambiguous"]], res["goal"][~res["ambiguous"]]), f"{msg} fused: goal"
+            live = ~goal
+            sub = {k: v[live] for k, v in res.items() if isinstance(v, np.ndarray) and v.shape == (n,)}
+            phys64.compare(sub, st["x"][live], st["y"][live], st["vx"][live], st["vy"][live], st["reward"][live],
+                           np.zeros(int(live.sum()), bool), msg=f"{msg} fused")
+    finally:
+        ctx.close()
+    return res, got
+
+
+def first_hit(res, n):
+    env, sub, _ = res["hits"]
+    out = np.full(n, -1)
+    for e, s in sorted(zip(env.tolist(), sub.tolist()), reverse=True):
+        out[e] = s
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- reach
+
+def reach_case():
+    """Twelve balls at the corners of their cells (four corners x first touch on sub-step 18, 19, 20) moving diagonally
+    away from the cell centre at |v| = 2 sqrt(2) into a 45-degree edge, and twelve balls in free flight on the diagonals of
+    the target that enter it on those sub-steps. Distances put the touch half a sub-step of travel past the contact
+    (a margin of ~0.07 R in position, 10^4 times the model's bound)."""
+    R = 0.02
+    step = SQ8 * R / 20
+    tris, balls, subs = [], [], []
+    sites = [(0.15, 0.15), (0.38, 0.15), (0.61, 0.15), (0.84, 0.15), (0.15, 0.36), (0.38, 0.36), (0.61, 0.36),
+             (0.84, 0.36), (0.15, 0.57), (0.38, 0.57), (0.61, 0.57), (0.84, 0.57)]
+    k = 0
+    for corner in ((0, 0), (1, 0), (0, 1), (1, 1)):
+        sx, sy = (-1.0 if corner[0] == 0 else 1.0), (-1.0 if corner[1] == 0 else 1.0)
+        for i in (17, 18, 19):
+            bx, by = sites[k]
+            k += 1
+            cx, cy = int(bx * CELL_G), int(by * CELL_G)
+            px = f32((cx + corner[0]) / CELL_G)
+            py = f32((cy + corner[1]) / CELL_G)
+            if corner[0]:
+                px = np.nextafter(px, f32(0))
+            if corner[1]:
+                py = np.nextafter(py, f32(0))
+            D = R + (i + 0.5) * step
+            u = np.array([sx, sy]) / np.sqrt(2)
+            foot = np.array([px, py], np.float64) + u * D
+            tris.append((foot, u))
+            balls.append((px, py, 2.0 * sx, 2.0 * sy))
+            subs.append(i)
+    tx, ty, tr = 0.5, 0.83, 0.03
+    goal_balls = []
+    for sx, sy in ((-1, -1), (1, -1), (-1, 1), (1, 1)):
+        for i in (17, 18, 19):
+            rho = tr + (i + 0.5) * step
+            goal_balls.append((tx + sx * rho / np.sqrt(2), ty + sy * rho / np.sqrt(2), -2.0 * sx, -2.0 * sy))
+    lines = [f"ball {R}", f"target {tx} {ty} {tr}", "start 0.5 0.5"] + \
+        ["polygon 0.0 0.0 0.0 0.01 1.0 0.01 1.0 0.0", "polygon 0.0 0.0 0.01 0.0 0.01 1.0 0.0 1.0",
+         "polygon 0.0 1.0 0.0 0.99 1.0 0.99 1.0 1.0", "polygon 1.0 1.0 0.99 1.0 0.99 0.0 1.0 0.0"]
+    for foot, u in tris:
+        t = np.array([-u[1], u[0]]) * 1.5 * R
+        back = foot + u * 1.0 * R
+        lines.append("polygon " + " ".join(f"{float(v)!r}" for v in (*(foot - t), *back, *(foot + t))))
+    import skill_chaining_with_graphs_amd as scg
+    m = scg.parse_map("\n".join(lines), "reach")
+    b = np.array(balls + goal_balls, np.float64)
+    return m, b, np.array(subs + subs)
+
+
+def test_reach_cases(block):
+    m, b, subs = reach_case()
+    n = len(b)
+    x, y, vx, vy = (b[:, c].astype(f32) for c in range(4))
+    cand = kernel_candidates(m, x, y, vx, vy, np.full(n, 4), margin=0.01)
+    assert np.all(cand[:12].sum(1) >= 1) and np.all(cand[12:].sum(1) == 0)        # edge cases paired, goal cases free
+    res, got = run_all(m, block, x, y, vx, vy, 4, msg=f"b{block} reach")
+    fh = first_hit(res, n)
+    assert fh[:12].tolist() == subs[:12].tolist(), f"first touch {fh[:12].tolist()}"
+    assert np.all(res["goal"][12:]) and not np.any(res["goal"][:12])
+    print(f"b{block} reach: first touch {fh[:12].tolist()}, goal {got[5][12:].tolist()}")
+
+
+# ---------------------------------------------------------------------------------------------------- pockets
+
+R_P = 0.02
+DECOY_D = 4.05          # between R (1 + 1.05 |v|) = 3.97 R and R (1.02 + 1.10 |v|) = 4.13 R at |v| = 2 sqrt(2)
+DECOY_HALF = 4.05 * np.tan(np.pi / 12) * 0.98      # twelve sides round a pocket; endpoints at 4.19 R, beyond the reach
+WALL = (np.pi / 4, 2.5, 3.6)                       # a wall the (2, 2) ball hits on sub-step 10; endpoints at 4.38 R
+
+
+def decoy_sides(k):
+    return [(np.pi / 12 + 2 * np.pi * s / 12, DECOY_D, DECOY_HALF) for s in range(k)]
+
+
+DIRS = ((2.0, 2.0), (-2.0, 2.0), (2.0, -2.0), (-2.0, -2.0))
+SITES = [(0.2, 0.2), (0.5, 0.2), (0.8, 0.2), (0.2, 0.8), (0.5, 0.8), (0.8, 0.8)]
+
+
+def wave_groups(cand, block):
+    counts = cand.sum(1)
+    waves = [pair_groups(counts[w:w + 64])[0] for w in range(0, len(counts), 64)]
+    per_block = [sum(waves[b:b + block // 64]) for b in range(0, len(waves), block // 64)]
+    return counts, waves, per_block
+
+
+@pytest.mark.parametrize("k", list(range(13)))
+def test_decoys_leave_trajectories_unchanged(block, k):
+    """Pockets of k decoy sides (k = 0: free flight, 1..8: pair runs of that length, 9..12: the per-lane loop) round the
+    same 24 balls (six sites x four diagonals at |v| = 2 sqrt(2)): the final states, rewards and goal flags are the same
+    bits for every k."""
+    m = pocket_map([(cx, cy, decoy_sides(k)) for cx, cy in SITES], radius=R_P, name=f"decoys{k}")
+    n = 256
+    i = np.arange(n) % 24
+    x = np.array([SITES[j // 4][0] for j in i], f32)
+    y = np.array([SITES[j // 4][1] for j in i], f32)
+    vx = np.array([DIRS[j % 4][0] for j in i], f32)
+    vy = np.array([DIRS[j % 4][1] for j in i], f32)
+    cand = kernel_candidates(m, x, y, vx, vy, np.full(n, 4), margin=0.01)
+    assert np.all(cand.sum(1) == k)
+    res, got = run_all(m, block, x, y, vx, vy, 4, msg=f"b{block} decoys{k}")
+    assert len(res["hits"][0]) == 0                      # the model confirms: no decoy ever intercepts
+    ref = _DECOY_REF.setdefault(block, got)
+    for a_, b_ in zip(got, ref):
+        assert np.array_equal(a_, b_), f"k = {k}: the decoys changed the result"
+
+
+_DECOY_REF = {}
+
+
+def dealing_map():
+    """Pockets with a wall and 7, 6, 8 or 12 decoys: 8, 7, 9 and 13 candidates for a ball at their centre; a free site."""
+    pockets = [(0.2, 0.2, decoy_sides(7) + [WALL]), (0.5, 0.2, decoy_sides(6) + [WALL]),
+               (0.8, 0.2, decoy_sides(8) + [WALL]), (0.2, 0.8, decoy_sides(12) + [WALL])]
+    return pocket_map(pockets, radius=R_P, target=(0.8, 0.8, 0.03), name="dealing"), \
+        {8: (0.2, 0.2), 7: (0.5, 0.2), 9: (0.8, 0.2), 13: (0.2, 0.8), 0: (0.5, 0.8)}
+
+
+def test_saturated_pair_dealing(block):
+    """Four 256-env runs: all envs with 8 candidates; the wasteful pattern (a run of 8 then seven of 7 per group: 7 pad
+    slots in every group); free flight, 7, 8, 9 and 13 candidates mixed in every wave; all envs in the per-lane loop."""
+    m, site = dealing_map()
+    pat = {"all8": [8] * 256, "waste": ([8] + [7] * 7) * 32, "mixed": [0, 7, 8, 9, 13, 8, 7, 8] * 32,
+           "loop": [9, 13] * 128}
+    kinds = np.concatenate([pat[p] for p in ("all8", "waste", "mixed", "loop")])
+    n = len(kinds)
+    d = np.arange(n) % 4
+    x = np.array([site[k][0] for k in kinds], f32)
+    y = np.array([site[k][1] for k in kinds], f32)
+    vx = np.array([DIRS[j][0] for j in d], f32)
+    vy = np.array([DIRS[j][1] for j in d], f32)
+    cand = kernel_candidates(m, x, y, vx, vy, np.full(n, 4), margin=0.01)
+    counts, waves, per_block = wave_groups(cand, block)
+    assert np.array_equal(counts, kinds), "candidate counts differ from the construction"
+    assert max(waves) == 8 and max(per_block) == 8 * block // 64, (waves, per_block)
+    _, pads = pair_groups(counts[256:320])
+    assert pads == 7 * 7                                  # the wasteful pattern: 7 empty slots closing each of the first 7 groups
+    assert all(w == 0 for w in waves[12:16])              # the last 256 envs: per-lane loop only
+    res, _ = run_all(m, block, x, y, vx, vy, 4, msg=f"b{block} dealing")
+    env, sub, j = res["hits"]
+    walled = np.nonzero((d == 0) & (kinds != 0))[0]       # moving (2, 2) in a pocket: into its wall, hit on sub-step 10
+    assert np.array_equal(np.unique(env), walled) and np.all(sub == 10)
+    print(f"b{block} dealing: max pair groups per wave {max(waves)}, per block {max(per_block)}; groups per wave {waves}")
+
+
+# ---------------------------------------------------------------------------------------------------- mask words
+
+@pytest.mark.parametrize("n_edges", sorted(BOUNDARY_EDGES))
+def test_mask_word_boundaries(block, n_edges):
+    m = edge_count_map(n_edges)
+    rng = np.random.default_rng(n_edges)
+    x, y, vx, vy = boundary_states(m, BOUNDARY_EDGES[n_edges], rng, n_each=24)
+    res, _ = run_all(m, block, x, y, vx, vy, 4, msg=f"b{block} edges{n_edges}")
+    hit = set(res["hits"][2].tolist())
+    assert set(BOUNDARY_EDGES[n_edges]) <= hit, f"edges {BOUNDARY_EDGES[n_edges]} not all hit: {sorted(hit)}"

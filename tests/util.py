@@ -85,3 +85,134 @@ def hub_map(n_spokes=12, r_in=0.035, r_out=0.30, half_width=0.006):
                (0.5 + r_in * c + half_width * s_, 0.5 + r_in * s_ - half_width * c)]
         lines.append("polygon " + " ".join(f"{px:.6f} {py:.6f}" for px, py in pts))
     return scg.parse_map("\n".join(lines), f"hub_{n_spokes}")
+
+
+_BORDER = ["polygon 0.0 0.0 0.0 0.01 1.0 0.01 1.0 0.0", "polygon 0.0 0.0 0.01 0.0 0.01 1.0 0.0 1.0",
+           "polygon 0.0 1.0 0.0 0.99 1.0 0.99 1.0 1.0", "polygon 1.0 1.0 0.99 1.0 0.99 0.0 1.0 0.0"]
+
+
+def _poly(pts):
+    return "polygon " + " ".join(f"{float(px)!r} {float(py)!r}" for px, py in pts)
+
+
+def edge_count_map(n_edges, radius=0.01):
+    """A synthetic map of exactly `n_edges` edges (16 border edges, then squares on an 8 x 8 grid and, where n_edges - 16 is
+    not a multiple of 4, one regular polygon of 5..7 vertices in the last slot). Every obstacle is convex and stands alone,
+    so every edge can be hit from outside: the edges at the mask-word boundaries (63 / 64, 127 / 128, 255) included."""
+    k = n_edges - 16
+    assert 4 <= k <= 240
+    q, r = divmod(k, 4)
+    sizes = [4] * q if r == 0 else [4] * (q - 1) + [4 + r]
+    lines = [f"ball {radius}", "target 0.955 0.955 0.02", "start 0.92 0.08"] + _BORDER
+    for s, nv in enumerate(sizes):
+        cx, cy = 0.1 + 0.1 * (s % 8), 0.1 + 0.1 * (s // 8)
+        ph = np.pi / 4 if nv == 4 else 0.3
+        rad = 0.02 * np.sqrt(2) if nv == 4 else 0.025
+        lines.append(_poly([(cx + rad * np.cos(ph + 2 * np.pi * i / nv), cy + rad * np.sin(ph + 2 * np.pi * i / nv))
+                            for i in range(nv)]))
+    m = scg.parse_map("\n".join(lines), f"edges_{n_edges}")
+    assert m.n_edges == n_edges
+    return m
+
+
+def edge_normals(m):
+    """Unit outward normals [n_edges, 2] (float64) of the convex obstacles of a map: from each polygon's centroid."""
+    out = []
+    for poly in m.polygons:
+        p = poly.astype(np.float64)
+        c = p.mean(0)
+        for i in range(len(p)):
+            a, b = p[i], p[(i + 1) % len(p)]
+            e = b - a
+            nrm = np.array([e[1], -e[0]]) / np.hypot(*e)
+            if np.dot(nrm, (a + b) / 2 - c) < 0:
+                nrm = -nrm
+            out.append(nrm)
+    return np.array(out)
+
+
+def edge_hit_state(m, j, gap, speed=1.0, along=0.5):
+    """A ball at `gap` radii (float64) outside edge j, opposite the point at fraction `along` of the edge, moving head-on into
+    it at `speed`: (x, y, vx, vy) float32 scalars."""
+    E = m.edges.astype(np.float64)[j]
+    nrm = edge_normals(m)[j]
+    p = E[0:2] + along * E[2:4] + nrm * float(m.radius) * (1.0 + gap)
+    v = -nrm * speed
+    return np.float32(p[0]), np.float32(p[1]), np.float32(v[0]), np.float32(v[1])
+
+
+def pocket_map(pockets, radius=0.02, target=(0.5, 0.5, 0.03), name="pockets"):
+    """Pockets of thin triangles round given ball positions. `pockets`: list of (cx, cy, sides), sides a list of
+    (angle, distance, half_length) in radians / ball radii: a triangle whose long edge faces (cx, cy) at `distance` along
+    `angle`, `half_length` to either side, with its apex behind it (away from the pocket centre, far enough that the two
+    short edges are no nearer to the centre than the long edge's endpoints). Used to give a ball an exact number of
+    candidate edges of the HIP physics and to place edges that are candidates but can never be intercepted."""
+    R = radius
+    lines = [f"ball {R}", f"target {target[0]} {target[1]} {target[2]}", f"start {target[0]} {target[1] - 0.1}"] + _BORDER
+    for cx, cy, sides in pockets:
+        for ang, dist, half in sides:
+            c, s = np.cos(ang), np.sin(ang)
+            d, hl = dist * R, half * R
+            depth = max(0.5 * d, hl * hl / d + 0.2 * R)
+            lines.append(_poly([(cx + d * c - hl * s, cy + d * s + hl * c), (cx + (d + depth) * c, cy + (d + depth) * s),
+                                (cx + d * c + hl * s, cy + d * s - hl * c)]))
+    return scg.parse_map("\n".join(lines), name)
+
+
+# ---- host restatement of the HIP physics' candidate pruning (an acceleration outside the arithmetic contract, SPEC §1.3 last
+# paragraph). Restated from the code, not from the SPEC: the refined reach of pinball_wave_prepare (scg_device.hpp) and the
+# cell-mask reach of scg_set_map (scg_kernels.hip). If either changes in the code, change it here.
+CELL_G = 32
+REFINE_A, REFINE_B = 1.02, 1.10                       # rr = fmaf(1.10f, |v|, 1.02f); candidate if edge_d2 <= R2 rr^2
+CELL_VMAX = 2.0 * np.sqrt(2.0) * 1.001                # scg_set_map: vmax of the cell-mask reach
+CELL_SLACK = 1.01                                     # ... R (1.02 + 1.10 vmax) * 1.01 + half a cell diagonal + 1e-6
+PCAP = 8                                              # candidate edges per env that the (env, edge) pair form takes
+
+
+def cell_reach(R):
+    return float(R) * (REFINE_A + REFINE_B * CELL_VMAX) * CELL_SLACK + 0.5 * np.sqrt(2.0) / CELL_G + 1e-6
+
+
+def cell_of(x, y):
+    """The kernel's cell of a position: (int)(x * 32.0f), clamped to 0..31."""
+    cx = np.clip((np.asarray(x, np.float32) * np.float32(CELL_G)).astype(np.int64), 0, CELL_G - 1)
+    cy = np.clip((np.asarray(y, np.float32) * np.float32(CELL_G)).astype(np.int64), 0, CELL_G - 1)
+    return cx, cy
+
+
+def kernel_candidates(m, x, y, vx, vy, action, margin=0.0):
+    """Candidate-edge mask [n, n_edges] of the HIP physics for pre-step states, in float64: edges of the cell mask (within
+    cell_reach of the cell centre) that lie within R (1.02 + 1.10 |v|) of the ball, |v| after the impulse and the clip.
+    With margin > 0, also asserts that no edge lies within a factor 1 +- margin of either boundary (so that binary32
+    rounding cannot change the count)."""
+    from phys64 import DV, VMAX, seg_dist
+    a = np.asarray(action)
+    vx = np.clip(np.asarray(vx, np.float32).astype(np.float64) + np.where(a == 0, DV, np.where(a == 2, -DV, 0.0)), -VMAX, VMAX)
+    vy = np.clip(np.asarray(vy, np.float32).astype(np.float64) + np.where(a == 1, DV, np.where(a == 3, -DV, 0.0)), -VMAX, VMAX)
+    R = float(m.radius)
+    px, py = np.asarray(x, np.float32).astype(np.float64), np.asarray(y, np.float32).astype(np.float64)
+    reach = R * (REFINE_A + REFINE_B * np.hypot(vx, vy))[:, None]
+    d = seg_dist(m.edges, px, py)
+    cx, cy = cell_of(x, y)
+    dc = seg_dist(m.edges, (cx + 0.5) / CELL_G, (cy + 0.5) / CELL_G)
+    cr = cell_reach(R)
+    if margin > 0:
+        assert not np.any(np.abs(d / reach - 1.0) < margin), "a state lies within the margin of the refined reach"
+        assert not np.any((d <= reach) & (np.abs(dc / cr - 1.0) < margin)), "a cell centre lies within the margin of the cell-mask reach"
+    return (d <= reach) & (dc <= cr)
+
+
+def pair_groups(counts):
+    """The run-pushing rule of pinball_wave_prepare for one wave of 64 envs: envs with 1..PCAP candidates take runs of
+    consecutive slots in lane order, and a run that would straddle a group of 64 slots starts the next group. Returns
+    (groups, pad slots) of the wave."""
+    p, pad = 0, 0
+    for c in counts:
+        if not 1 <= c <= PCAP:
+            continue
+        if p // 64 != (p + c - 1) // 64:
+            nxt = (p // 64 + 1) * 64
+            pad += nxt - p
+            p = nxt
+        p += c
+    return -(-p // 64), pad
