@@ -97,6 +97,41 @@ int scg_step(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *op
              uint8_t *done, float *W, const float *clf, uint32_t enabled_mask, uint64_t t,
              uint32_t flags, void *stream);
 
+/* ---- acting rollouts (SPEC §8): K acting steps in ONE launch, no learning ----
+ * scg_rollout advances the envs n_steps times from t0 exactly as n_steps calls of scg_step(flags = 0) at t = t0 .. t0+n_steps-1
+ * would (state, option_id, opt_steps, ep_steps and qcache after every step; action / reward / done of the last step), bit for
+ * bit and whatever the block build. A workgroup owns a fixed range of envs for the whole launch and nothing crosses
+ * workgroups: the launch cannot hang and raises no asynchronous failure bit. It never writes the trace buffers, events,
+ * ev_len, gestation success counts, gradient buffers or W, and it does not read or clear an announced collect trigger.
+ * Afterwards the ctx's prepared env order is invalid, as after scg_invalidate_order.
+ *   SCG_ROLLOUT_BEGIN        every env starts a new episode first, with the RNG at t0 (SPEC §1.4's reset, done forced to 2, then
+ *                            §4.2's selection on the start state with o = 0); the n_steps steps then run at t0+1 .. t0+n_steps.
+ *                            BEGIN zeroes stats->ep_return and stats->finished. n_steps = 0 is allowed with BEGIN only; such a
+ *                            launch leaves action / reward / done untouched
+ *   SCG_ROLLOUT_ONE_EPISODE  an env whose stats->finished[e] != 0 at entry is not stepped (none of its arrays is written); a
+ *                            step that ends an episode sets finished[e] = 1 (with or without this flag)
+ * `stats` (HOST struct of DEVICE pointers, may be NULL; any member may be NULL = not kept): in/out per-env counters, so one
+ * evaluation may span several launches (SPEC §8 table). The caller zeroes them; BEGIN zeroes ep_return and finished.
+ * SCG_ERR_INVALID: null ctx or array, n_steps outside [0, SCG_ROLLOUT_MAX_STEPS], n_steps == 0 without BEGIN, ONE_EPISODE
+ * without stats->finished. SCG_ERR_STATE before scg_set_map. The cap keeps one launch to tens of milliseconds at the largest
+ * batch sizes. The launch geometry (envs per wave, 2 .. 32) is picked from N; the environment variable SCG_ROLLOUT_EPW pins it
+ * (tests, measurements; results do not depend on it; another value is SCG_ERR_INVALID). */
+typedef struct {
+    float *ep_return;              /* [N] return of the running episode */
+    double *ret_sum;               /* [N] sum of the recorded episodes' returns */
+    int32_t *episodes, *goals, *len_sum;        /* [N] episodes recorded, of them ended in the goal, their summed lengths */
+    int32_t *vf_steps, *entries, *declines, *successes;   /* [n_vf][N] each: steps run per VF, option entries, value-gate
+                                                             declines, option successes */
+    uint8_t *finished;             /* [N] an episode has ended since BEGIN */
+} scg_rollout_stats;
+#define SCG_ROLLOUT_BEGIN 1u
+#define SCG_ROLLOUT_ONE_EPISODE 2u
+#define SCG_ROLLOUT_MAX_STEPS 1024
+int scg_rollout(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                uint32_t flags, const scg_rollout_stats *stats, void *stream);
+
 /* Device pointers of the ctx-owned reduced gradient G[n_vf][5][1296] and counts n_k[n_vf] (int32)
  * left by the last scg_step(LEARN) — the buffers a multi-rank caller all-reduces (SPEC §5). */
 int scg_grad_buffers(scg_ctx *ctx, float **G, int32_t **n_k);

@@ -17,6 +17,9 @@ def __getattr__(name):
     if name in ("ScgContext", "EnvState", "fourier_scale_table"):
         from . import core
         return getattr(core, name)
+    if name == "EpisodeStats":
+        from .evaluation import EpisodeStats
+        return EpisodeStats
     if name == "FourierBasis":
         from .fourier import FourierBasis
         return FourierBasis

@@ -17,6 +17,9 @@ CLF_STRIDE = 8
 
 STEP_LEARN = 1
 STEP_APPLY = 2
+ROLLOUT_BEGIN = 1          # include/scg_abi.h SCG_ROLLOUT_*
+ROLLOUT_ONE_EPISODE = 2
+ROLLOUT_MAX_STEPS = 1024
 ABI_VERSION = 5            # include/scg_abi.h SCG_ABI_VERSION
 ASYNC_FIT_TIMEOUT = 0x1
 ASYNC_STEP_HANDOFF = 0x2
@@ -48,6 +51,22 @@ class ScgConfig(C.Structure):
     ]
 
 
+class RolloutStats(C.Structure):
+    """scg_rollout_stats: device pointers of the per-env counters of SPEC §8 (NULL = not kept)."""
+    _fields_ = [
+        ("ep_return", C.c_void_p),
+        ("ret_sum", C.c_void_p),
+        ("episodes", C.c_void_p),
+        ("goals", C.c_void_p),
+        ("len_sum", C.c_void_p),
+        ("vf_steps", C.c_void_p),
+        ("entries", C.c_void_p),
+        ("declines", C.c_void_p),
+        ("successes", C.c_void_p),
+        ("finished", C.c_void_p),
+    ]
+
+
 _P = C.c_void_p
 _SIGS = {
     "scg_abi_version": (C.c_int, []),
@@ -59,6 +78,7 @@ _SIGS = {
     "scg_set_hparams": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "scg_set_map": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     "scg_step": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_uint32, _P]),
+    "scg_rollout": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(RolloutStats), _P]),
     "scg_grad_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "scg_set_grad_buffers": (C.c_int, [_P, _P, _P]),
     "scg_apply_update": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -6,11 +6,13 @@ named after north_star. Per-step work is one scg_step launch pair (fused kernel 
 nothing on the per-step path synchronises with or copies to the host."""
 from __future__ import annotations
 
+import ctypes as C
 import os
 from typing import List, Optional
 
 import torch
 
+from . import _lib
 from . import dist as _dist
 from ._lib import CLF_STRIDE, NUM_ACTIONS, NUM_FEATURES, ScgError, auto_block_envs
 from .core import EnvState, ScgContext
@@ -344,6 +346,48 @@ class SkillChainingAgent:
         """Batched intra-option Q-learning update of VF k on explicit transitions (SPEC §5):
         delta = r + cont * max_a' Q_k(s',a') - Q_k(s,a);  W_k[a] += alpha/n * scale * sum delta*phi(s)."""
         self.ctx.q_update(k, s, action, r, cont, s_next, self.W, apply=apply)
+
+    def evaluate(self, n_episodes: int = 4096, epsilon: float = 0.0, seed: Optional[int] = None, steps_per_launch: int = 64,
+                 per_env: bool = False):
+        """How good the current policy is: one episode per env on `n_episodes` envs of a separate evaluation context (cached per
+        n_episodes; another seed replaces the entry), acting with `epsilon` and the current W, clf and enabled options, weights
+        frozen (SPEC §8). Returns
+        EpisodeStats.summary(): episodes, success_rate, mean_return, mean_length and per value function steps_share, entries,
+        declines, successes; with per_env=True also the per-env counter tensors, as (summary, dict).
+        One BEGIN | ONE_EPISODE launch, then ONE_EPISODE launches up to ceil(max_episode_steps / steps_per_launch) in all: every
+        episode has ended by then (time limit), and nothing is read back before the end. The training run is left alone: W,
+        state, t, the training context's env order, trace ring, gestation counts and peer exchange counter are untouched.
+        A sharded agent evaluates its own rank's policy copy on this rank only: there is no collective here."""
+        from .evaluation import EpisodeStats
+        n, spl = int(n_episodes), int(steps_per_launch)
+        if n < 1:
+            raise ValueError("n_episodes must be >= 1")
+        if not (1 <= spl <= _lib.ROLLOUT_MAX_STEPS):
+            raise ValueError(f"steps_per_launch must be in [1, {_lib.ROLLOUT_MAX_STEPS}]")
+        c = self.ctx.cfg
+        seed = int(c.seed) if seed is None else int(seed)
+        # one evaluation context per n_episodes; the seed is a create-time setting, so another seed replaces that entry (a
+        # caller sweeping seeds holds one context, not one per seed)
+        cache = self.__dict__.setdefault("_eval_ctx", {})
+        if n not in cache or cache[n][0].cfg.seed != seed:
+            if n in cache:
+                cache.pop(n)[0].close()
+            ectx = ScgContext(n, self.n_options, self.map, device=self.ctx.device.index, seed=seed, env_id_base=0,
+                              block_envs=self.ctx.block_envs)
+            cache[n] = (ectx, EnvState(n, ectx.device, self.map), EpisodeStats(self.n_vf, n, ectx.device))
+        ectx, st, stats = cache[n]
+        ectx.set_hparams(gamma=c.gamma, alpha=c.alpha, epsilon=float(epsilon), r_option_success=c.r_option_success,
+                         max_episode_steps=c.max_episode_steps, max_option_steps=c.max_option_steps,
+                         update_count_floor=c.update_count_floor, reoffer_period=c.reoffer_period)
+        ectx.set_option_parents([int(v) for v in self.ctx.parents])
+        ectx._call("scg_set_gestation", C.c_uint32(self.gest_mask), None)      # classifiers in use, no success counts kept
+        stats.zero_()
+        launches = -(-int(c.max_episode_steps) // spl)
+        for i in range(launches):
+            ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
+                         begin=(i == 0), one_episode=True)
+        out = stats.summary()
+        return (out, stats.per_env()) if per_env else out
 
     def rollout(self, steps: int, learn: bool = True) -> None:
         for _ in range(steps):

@@ -145,6 +145,46 @@ class ScgContext:
         self._step_args = (key, ptrs)
         self._call("scg_step", *ptrs, C.c_uint32(enabled_mask), C.c_uint64(t), C.c_uint32(flags), self._stream())
 
+    def rollout(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, n_steps: int,
+                stats=None, begin: bool = False, one_episode: bool = False) -> None:
+        """SPEC §8: n_steps acting steps in ONE launch, bit for bit n_steps calls of step(learn=False) at t0 .. t0+n_steps-1
+        (with `begin`: a new episode for every env at t0 first, the steps at t0+1 .. t0+n_steps). W is read, never written.
+        `stats` (EpisodeStats of this context's n_vf and n_envs, on its device) receives the episode counters; `one_episode`
+        leaves envs alone whose `stats.finished` is set. The step's prepared env order is invalid afterwards."""
+        N = self.n_envs
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        self._chk(st.x, f32, N, "x"); self._chk(st.y, f32, N, "y")
+        self._chk(st.vx, f32, N, "vx"); self._chk(st.vy, f32, N, "vy")
+        self._chk(st.option_id, i32, N, "option_id"); self._chk(st.opt_steps, i32, N, "opt_steps")
+        self._chk(st.ep_steps, i32, N, "ep_steps"); self._chk(st.qcache, f32, NUM_ACTIONS * N, "qcache")
+        self._chk(st.action, u8, N, "action"); self._chk(st.reward, f32, N, "reward")
+        self._chk(st.done, u8, N, "done")
+        self._chk(W, f32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
+        self._chk(clf, f32, self.n_vf * CLF_STRIDE, "clf")
+        n_steps, t0 = int(n_steps), int(t0)
+        if not (0 <= n_steps <= _lib.ROLLOUT_MAX_STEPS) or (n_steps == 0 and not begin):
+            raise ScgError(f"rollout: n_steps must be in [1, {_lib.ROLLOUT_MAX_STEPS}] ([0, ...] with begin=True)")
+        if not (0 <= t0 < 2 ** 64):
+            raise ScgError("rollout: t0 must be a 64-bit unsigned step counter")
+        cs = None
+        if stats is not None:
+            if stats.n != N or stats.n_vf != self.n_vf:
+                raise ScgError(f"rollout: stats are for {stats.n} envs x {stats.n_vf} VFs, the context has {N} x {self.n_vf}")
+            self._chk(stats.ep_return, f32, N, "stats.ep_return"); self._chk(stats.ret_sum, torch.float64, N, "stats.ret_sum")
+            for f in ("episodes", "goals", "len_sum"):
+                self._chk(getattr(stats, f), i32, N, "stats." + f)
+            for f in ("vf_steps", "entries", "declines", "successes"):
+                self._chk(getattr(stats, f), i32, self.n_vf * N, "stats." + f)
+            self._chk(stats.finished, u8, N, "stats.finished")
+            cs = stats.c_struct()
+        elif one_episode:
+            raise ScgError("rollout: one_episode needs stats (its `finished` flags)")
+        flags = (_lib.ROLLOUT_BEGIN if begin else 0) | (_lib.ROLLOUT_ONE_EPISODE if one_episode else 0)
+        self._call("scg_rollout", _ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id), _ptr(st.opt_steps),
+                   _ptr(st.ep_steps), _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done), _ptr(W), _ptr(clf),
+                   C.c_uint32(enabled_mask), C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags),
+                   None if cs is None else C.byref(cs), self._stream())
+
     def invalidate_order(self) -> None:
         """Tell the library that option ids were written outside scg_step (reset, restore): re-sort next step."""
         self._step_args = self._step_keep = None

@@ -6,6 +6,8 @@
 // block's option run as ONE merged pass on shared tables of Fourier factors.
 //   reduce_kernel  slabs -> 16-block segment sums -> G, n_k, W += alpha/n_k * scale * G; commit + next env order (+ an
 //                  announced example trigger's row totals)
+// rollout_kernel (scg_rollout_kernel.hpp): K acting steps (SPEC §8) in one launch; a workgroup owns a fixed range of envs
+// for the whole launch and never talks to another one.
 // fit_kernel: SPEC §6 on 8 workgroups x 1024 chains per option behind tagged-word exchanges; a fit whose workgroups cannot run
 // together gives up after a wall-clock wait, leaves its row untouched and raises the ctx's asynchronous status word.
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
@@ -150,6 +152,7 @@ __device__ __forceinline__ void item_tree_sum(float (&q)[M]) {
 }
 
 #include "scg_step_kernel.hpp"
+#include "scg_rollout_kernel.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // slabs -> G (SPEC §5 two-level block order), n_k, optional apply; the next step's env order rides along
@@ -1553,6 +1556,55 @@ int scg_step(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *opti
     c->hist_dirty = false;
     c->hist_parity ^= 1;
     c->order_valid = true; c->order_ids = option_id;
+    return SCG_OK;
+}
+
+int scg_rollout(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                uint32_t flags, const scg_rollout_stats *stats, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_rollout: null ctx");
+    if (!c->have_map) return fail(c, SCG_ERR_STATE, "scg_rollout: scg_set_map has not been called");
+    if (!x || !y || !vx || !vy || !option_id || !opt_steps || !ep_steps || !qcache || !action || !reward ||
+        !done || !W || !clf)
+        return fail(c, SCG_ERR_INVALID, "scg_rollout: null array argument");
+    if (flags & ~(SCG_ROLLOUT_BEGIN | SCG_ROLLOUT_ONE_EPISODE)) return fail(c, SCG_ERR_INVALID, "scg_rollout: unknown flag");
+    if (n_steps < 0 || n_steps > SCG_ROLLOUT_MAX_STEPS)
+        return fail(c, SCG_ERR_INVALID, "scg_rollout: n_steps out of range [0, SCG_ROLLOUT_MAX_STEPS]");
+    if (n_steps == 0 && !(flags & SCG_ROLLOUT_BEGIN)) return fail(c, SCG_ERR_INVALID, "scg_rollout: n_steps == 0 without SCG_ROLLOUT_BEGIN");
+    if ((flags & SCG_ROLLOUT_ONE_EPISODE) && !(stats && stats->finished))
+        return fail(c, SCG_ERR_INVALID, "scg_rollout: SCG_ROLLOUT_ONE_EPISODE needs stats->finished");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_rollout");
+    RolloutArgs R;
+    memset(&R, 0, sizeof(R));
+    R.x = x; R.y = y; R.vx = vx; R.vy = vy; R.option_id = option_id; R.opt_steps = opt_steps; R.ep_steps = ep_steps;
+    R.qcache = qcache; R.action = action; R.reward = reward; R.done = done; R.W = W; R.clf = clf;
+    R.edges = c->d_edges; R.cellmask = c->d_cellmask; R.starts = c->d_starts;
+    if (stats) R.st = *stats;
+    R.n = c->cfg.n_envs; R.n_vf = c->n_vf; R.n_steps = n_steps;
+    R.begin = (flags & SCG_ROLLOUT_BEGIN) ? 1u : 0u; R.one_episode = (flags & SCG_ROLLOUT_ONE_EPISODE) ? 1u : 0u;
+    R.enabled = enabled_mask; R.gest = c->gest; R.parents = c->parents;
+    R.t0 = t0; R.seed = c->cfg.seed; R.env_base = c->cfg.env_id_base;
+    R.epsilon = c->cfg.epsilon; R.max_ep = c->cfg.max_episode_steps; R.max_opt = c->cfg.max_option_steps;
+    R.reoffer_mask = c->cfg.reoffer_period > 1 ? (uint32_t)(c->cfg.reoffer_period - 1) : 0u;
+    R.ms = c->ms;
+    // envs per wave: the largest of 2 .. 32 that still gives every CU a workgroup (one 8-wave workgroup per CU: LDS); the
+    // results do not depend on it
+    int epw = 2;
+    while (epw < RO_MAX_EPW && (long long)(c->cfg.n_envs) >= (long long)c->n_cu * RO_WAVES * epw * 2) epw *= 2;
+    // SCG_ROLLOUT_EPW (2, 4, 8, 16 or 32) pins the launch geometry instead: a hook for tests and measurements, which run every
+    // geometry at any env count (the results are the same by construction; the tests check that they are)
+    if (const char *ov = getenv("SCG_ROLLOUT_EPW")) {
+        const int v = atoi(ov);
+        if (v < 2 || v > RO_MAX_EPW || (v & (v - 1))) return fail(c, SCG_ERR_INVALID, "scg_rollout: SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
+        epw = v;
+    }
+    R.epw = epw;
+    const int grid = (c->cfg.n_envs + RO_WAVES * epw - 1) / (RO_WAVES * epw);
+    c->order_valid = false;                               // the ids change under the step's prepared env order
+    hipLaunchKernelGGL(rollout_kernel, dim3(grid), dim3(RO_THREADS), 0, reinterpret_cast<hipStream_t>(stream), R);
+    SCG_HIP(c, hipGetLastError());
     return SCG_OK;
 }
 

@@ -1,0 +1,382 @@
+// scg_rollout_kernel.hpp — rollout_kernel: K acting steps (SPEC §8) in ONE launch (included by scg_kernels.hip).
+//
+// With the weights frozen no env's step reads another env's result, so a workgroup owns a fixed range of RO_WAVES * epw
+// consecutive envs (env-id order) for the whole launch and never talks to another workgroup: no grid barrier, no polling,
+// no atomics outside LDS. Per step:
+//   P  each wave, one lane per env (lanes < epw): act from qcache, Pinball physics on the wave's own (env, edge) pair list
+//      (pinball_wave_*), episode bookkeeping, SPEC §4.2 option logic; Z_d^1 of s_next to LDS; the (env, value function)
+//      pairs that need Q(s_next, .) — the VF the env runs next, plus the root for an entering env — compacted into one
+//      list per value function (ballot / popcount, an LDS counter per list)
+//   E  the lists in 8-item units dealt over the workgroup's waves: one table build, then SPEC §3.1's contraction on
+//      v_mfma_f32_16x16x4_f32 (W_k the A operand: W_0 from LDS, staged once per launch; other VFs straight from memory),
+//      the AB fold and the butterfly
+//   G  each lane again: the value gate, the caller-visible ids, qcache, the statistics counters
+// State, qcache and counters stay in registers across the steps and are written once at the end. Finished envs (ONE_EPISODE)
+// and envs beyond N drop out of the lists; a workgroup with nothing left to step leaves the loop.
+#pragma once
+
+constexpr int RO_WAVES = 8;                    // waves per workgroup
+constexpr int RO_THREADS = RO_WAVES * 64;
+constexpr int RO_MAX_EPW = 32;                 // envs per wave (launch parameter epw in 2..32, a power of two)
+constexpr int RO_MAX_ENVS = RO_WAVES * RO_MAX_EPW;
+constexpr int RO_WAVE_FLOATS = E_TAB_FLOATS;   // per wave: tables of one unit (E) / the physics' pair list + states (P)
+static_assert(PITEMS + 4 * 64 + 16 <= RO_WAVE_FLOATS, "the pair list, the states and the goal flags fit a wave's table area");
+static_assert(RO_MAX_ENVS <= 256, "list entries are 8-bit env indices");
+
+struct RolloutArgs {
+    float *x, *y, *vx, *vy;
+    int32_t *option_id, *opt_steps, *ep_steps;
+    float *qcache;                 // [5][n]
+    uint8_t *action;
+    float *reward;
+    uint8_t *done;
+    const float *W;                // [n_vf][5][1296]
+    const float *clf;              // [n_vf][8]
+    const float *edges;
+    const uint64_t *cellmask;
+    const float *starts;
+    scg_rollout_stats st;          // device pointers, any may be null
+    int32_t n, n_vf, epw, n_steps;
+    uint32_t begin, one_episode;
+    uint32_t enabled, gest, parents;
+    uint64_t t0, seed;
+    int64_t env_base;
+    float epsilon;
+    int32_t max_ep, max_opt;
+    uint32_t reoffer_mask;
+    MapScalars ms;
+};
+
+// per-VF counters of one launch, six 16-bit fields in three words (a launch takes at most 1 + SCG_ROLLOUT_MAX_STEPS steps)
+struct Ctr16 {
+    uint32_t w[3];
+    __device__ __forceinline__ void add(int k, bool on) {
+        const uint32_t inc = on ? (1u << (16 * (k & 1))) : 0u;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) w[j] += (k >> 1) == j ? inc : 0u;
+    }
+    __device__ __forceinline__ int get(int k) const {
+        uint32_t v = 0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) v = (k >> 1) == j ? w[j] : v;
+        return (int)((v >> (16 * (k & 1))) & 0xffffu);
+    }
+};
+static_assert(SCG_ROLLOUT_MAX_STEPS + 1 < 65536, "16-bit launch counters");
+
+__global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs A) {
+    __shared__ __attribute__((aligned(16))) float s_w0[W_FLOATS];                 // W_0 in A-operand order (stage_w_cold's layout)
+    __shared__ __attribute__((aligned(16))) float s_edges[MAX_EDGES * 8];
+    __shared__ __attribute__((aligned(16))) float s_wave[RO_WAVES][RO_WAVE_FLOATS];
+    __shared__ __attribute__((aligned(16))) float2 s_z1[RO_MAX_ENVS][4];          // Z_d^1 of each env's s_next
+    __shared__ float s_qv[2][NACT][RO_MAX_ENVS];                                   // [0]: the VF the env runs next; [1]: the root (entering)
+    __shared__ uint16_t s_list[MAX_VF][RO_MAX_ENVS];                               // env index | slot << 8
+    __shared__ int s_cnt[2][MAX_VF];                                               // list lengths, by step parity
+    __shared__ float s_clf[MAX_VF * CLF_STRIDE];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int epw = A.epw, N = A.n;
+    const int il = wave * epw + lane;                          // this lane's env within the workgroup (lanes < epw)
+    const int e = blockIdx.x * RO_WAVES * epw + il;
+    const bool mine = lane < epw && e < N;
+
+    // ---- entry: the env's state into registers
+    float sx = 0.5f, sy = 0.5f, svx = 0.0f, svy = 0.0f, qc[NACT] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    int oid = 0, osteps = 0, eps = 0, last_a = 0, last_dn = 0;
+    float last_r = 0.0f, ep_ret = 0.0f;
+    double ret_sum = 0.0;
+    int episodes = 0, goals = 0, len_sum = 0;
+    bool finished = false;
+    Ctr16 c_vf = {{0u, 0u, 0u}}, c_en = {{0u, 0u, 0u}}, c_de = {{0u, 0u, 0u}}, c_su = {{0u, 0u, 0u}};
+    if (mine) {
+        sx = A.x[e]; sy = A.y[e]; svx = A.vx[e]; svy = A.vy[e];
+#pragma unroll
+        for (int a = 0; a < NACT; ++a) qc[a] = A.qcache[(size_t)a * N + e];
+        oid = A.option_id[e]; osteps = A.opt_steps[e]; eps = A.ep_steps[e];
+        if (A.st.finished && !A.begin) finished = A.st.finished[e] != 0;
+        if (A.st.ep_return && !A.begin) ep_ret = A.st.ep_return[e];
+        if (A.st.ret_sum) ret_sum = A.st.ret_sum[e];
+        if (A.st.episodes) episodes = A.st.episodes[e];
+        if (A.st.goals) goals = A.st.goals[e];
+        if (A.st.len_sum) len_sum = A.st.len_sum[e];
+    }
+    const bool skip = !mine || (A.one_episode && finished);   // not stepped at all in this launch: nothing of it is written
+    if (!__syncthreads_or(!skip)) return;                     // (workgroup-uniform) every env of the workgroup is finished
+    bool alive = !skip;
+
+    // ---- once per launch: W_0, the edge table and the classifiers to LDS
+    for (int i = tid; i < W_FLOATS; i += RO_THREADS) {
+        int t, kb, ln, dst;
+        if (i < W_TAIL) { const int q = i >> 2; t = q >> 7; ln = q & 63; kb = 4 * ((q >> 6) & 1) + (i & 3); dst = i; }
+        else { const int q = i - W_TAIL; t = q >> 6; ln = q & 63; kb = 8; dst = i; }
+        const int row = 16 * t + (ln & 15);
+        s_w0[dst] = row < NACT * 36 ? A.W[row * 36 + 9 * (ln >> 4) + kb] : 0.0f;
+    }
+    for (int i = tid; i < A.ms.n_edges * 8; i += RO_THREADS) s_edges[i] = A.edges[i];
+    if (tid < A.n_vf * CLF_STRIDE) s_clf[tid] = A.clf[tid];
+    if (tid < 2 * MAX_VF) (&s_cnt[0][0])[tid] = 0;
+    __syncthreads();
+
+    const unsigned known = A.enabled | A.gest;
+    const int total = A.n_steps + (A.begin ? 1 : 0);
+    float *sw = s_wave[wave];
+    for (int j = 0; j < total; ++j) {
+        const bool is_begin = A.begin && j == 0;
+        const uint64_t t = A.t0 + (uint64_t)j;
+        const int par = j & 1;
+        // ------------------------------------------------------------ P
+        bool valid = alive;
+        uint32_t u[4] = {0u, 0u, 0u, 0u};
+        if (valid) {
+            const uint64_t gid = (uint64_t)(A.env_base + e);
+            philox4x32_10((uint32_t)gid, (uint32_t)(t & 0xffffffffu), (uint32_t)(t >> 32), 0u,
+                          (uint32_t)(A.seed & 0xffffffffu), (uint32_t)(A.seed >> 32), u);
+        }
+        int a = NACT - 1;
+        if (valid && !is_begin) {
+            const bool explore = (float)(u[0] >> 8) * 0x1p-24f < A.epsilon;
+            const int a_rand = (int)__umulhi(u[1], 5u);
+            int a_greedy = 0;
+            float best = qc[0];
+#pragma unroll
+            for (int aa = 1; aa < NACT; ++aa) if (qc[aa] > best) { best = qc[aa]; a_greedy = aa; }
+            a = explore ? a_rand : a_greedy;
+        }
+        float px = sx, py = sy, pvx = svx, pvy = svy, rew = 0.0f;
+        bool goal = false;
+        if (!is_begin) {                                       // (wave-uniform)
+            bool pr;
+            const bool phys = valid;
+            uint32_t *items = reinterpret_cast<uint32_t *>(sw);
+            float *xs = sw + PITEMS;
+            uint8_t *gfl = reinterpret_cast<uint8_t *>(sw + PITEMS + 4 * 64);
+            const int groups = pinball_wave_prepare_any(s_edges, A.cellmask, A.ms, phys, px, py, pvx, pvy, a, goal, pr, items, xs, 64);
+            wave_lds_sync();
+            for (int q = 0; q < groups; ++q) pinball_wave_group(s_edges, A.ms, items + 64 * q, xs, 64, gfl);
+            wave_lds_sync();
+            rew = pinball_wave_finish(pr, px, py, pvx, pvy, a, goal, xs, 64, gfl);
+        }
+        const int o = (oid >= 1 && oid < A.n_vf) ? oid : 0;
+        const int eps1 = eps + 1;
+        int dn = 0;
+        float nx = px, ny = py, nvx = pvx, nvy = pvy;
+        bool keep = false, succ = false;
+        int cand = 0, on = 0, stay = 0;
+        if (valid) {
+            dn = is_begin ? 2 : (goal ? 1 : (eps1 >= A.max_ep ? 2 : 0));
+            if (dn) {
+                const uint32_t si = __umulhi(u[2], (uint32_t)A.ms.n_starts);
+                nx = A.starts[2 * si]; ny = A.starts[2 * si + 1]; nvx = 0.0f; nvy = 0.0f;
+            }
+            unsigned inA = 0, inB = 0;
+#pragma unroll
+            for (int k = 1; k < MAX_VF; ++k) {
+                if (k < A.n_vf && ((known >> k) & 1u)) {
+                    const float *w = s_clf + CLF_STRIDE * k;
+                    if (!is_begin && clf_z(w, px, py) > 0.0f) inA |= 1u << k;
+                    if (clf_z(w, nx, ny) > 0.0f) inB |= 1u << k;
+                }
+            }
+            if (!is_begin && o >= 1) {
+                const unsigned p2 = (A.parents >> (3 * (o & 7))) & 7u;
+                succ = (p2 == 0) ? goal : ((inA >> p2) & 1u);
+                const bool fail = !succ && !((inA >> o) & 1u);
+                const bool otime = osteps + 1 >= A.max_opt;
+                keep = !((dn != 0) || succ || fail || otime);
+            }
+            unsigned tgtB = 0;
+#pragma unroll
+            for (int k = 1; k < MAX_VF; ++k) {
+                const unsigned p2 = (A.parents >> (3 * k)) & 7u;
+                if (p2 != 0 && ((inB >> p2) & 1u)) tgtB |= 1u << k;
+            }
+            const unsigned sel = inB & ~tgtB & A.enabled;
+            cand = keep ? o : (sel ? __builtin_ctz(sel) : 0);
+            const int o_in = is_begin ? 0 : oid;
+            stay = (!keep && cand >= 1 && dn == 0 && o_in == -cand &&
+                    (((uint32_t)t + (uint32_t)(A.env_base + e)) & A.reoffer_mask) != 0u) ? cand : 0;
+            on = stay ? 0 : cand;
+            const float sh[4] = {nx, ny, fmaf(nvx, 0.25f, 0.5f), fmaf(nvy, 0.25f, 0.5f)};
+#pragma unroll
+            for (int d = 0; d < 4; ++d) s_z1[il][d] = sincospi_cs(sh[d]);
+        }
+        const bool entering = valid && !keep && on >= 1;
+        // compaction: slot 0 -> the list of VF `on`, slot 1 (entering) -> the root's list
+#pragma unroll
+        for (int k = 0; k < MAX_VF; ++k) {
+            const bool w0 = valid && on == k, w1 = entering && k == 0;
+            const uint64_t b0 = __ballot(w0), b1 = __ballot(w1);
+            const int n0 = __popcll(b0), n1 = __popcll(b1);
+            if (n0 + n1 == 0) continue;                         // (wave-uniform)
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&s_cnt[par][k], n0 + n1);
+            base = __shfl(base, 0, 64);
+            const uint64_t below = (1ull << lane) - 1ull;
+            if (w0) s_list[k][base + __popcll(b0 & below)] = (uint16_t)il;
+            if (w1) s_list[k][base + n0 + __popcll(b1 & below)] = (uint16_t)(il | 0x100);
+        }
+        __syncthreads();
+        // ------------------------------------------------------------ E
+        int cnt[MAX_VF], units = 0;
+#pragma unroll
+        for (int k = 0; k < MAX_VF; ++k) { cnt[k] = k < A.n_vf ? s_cnt[par][k] : 0; units += (cnt[k] + 7) >> 3; }
+        if (units == 0) break;                                 // (workgroup-uniform) nothing left to step
+        {
+            const int n16 = lane & 15, g = lane >> 4, bi = lane & 7, cp = lane >> 3;
+            const int bcol = 8 * (bi >> 2) + (bi & 3);
+            const int ocol_item = 4 * (n16 >> 3) + (n16 & 3);
+            const bool out_lane = (g == 0) && !(n16 & 4);
+            float *cdk = sw, *abq = sw + 36 * 16;
+            for (int uu = wave; uu < units; uu += RO_WAVES) {
+                int k = 0, ub = uu;
+#pragma unroll
+                for (int kk = 0; kk < MAX_VF - 1; ++kk) {
+                    const int nu = (cnt[k] + 7) >> 3;
+                    if (ub >= nu) { ub -= nu; ++k; }
+                }
+                const int nk = cnt[k] - 8 * ub;                    // items of this unit still ahead in the list (>= 1)
+                const uint16_t *lst = &s_list[k][8 * ub];
+                if (cp < 6) {
+                    float2 ab[6], cd[6];
+                    item_entries(s_z1[lst[min(bi, nk - 1)] & 0xff], cp, ab, cd);
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) {
+                        abq[bcol * AS + 6 * c + cp] = ab[c].x; abq[(bcol + 4) * AS + 6 * c + cp] = -ab[c].y;
+                        cdk[(6 * c + cp) * 16 + bcol] = cd[c].x; cdk[(6 * c + cp) * 16 + bcol + 4] = cd[c].y;
+                    }
+                }
+                wave_lds_sync();
+                float B[9];
+#pragma unroll
+                for (int kb = 0; kb < 9; ++kb) B[kb] = cdk[(9 * g + kb) * 16 + n16];
+                f4v acc[12];
+                if (k == 0) {                                      // W_0 from LDS (two ds_read_b128 + one b32 per tile)
+                    const f4v *w4 = reinterpret_cast<const f4v *>(s_w0) + lane;
+                    const float *w8 = s_w0 + W_TAIL + lane;
+#pragma unroll
+                    for (int tt = 0; tt < 12; ++tt) {
+                        const f4v a0 = w4[(tt * 2) * 64], a1 = w4[(tt * 2 + 1) * 64];
+                        f4v c = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                        for (int kb = 0; kb < 4; ++kb) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[kb], B[kb], c, 0, 0, 0);
+#pragma unroll
+                        for (int kb = 0; kb < 4; ++kb) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[kb], B[4 + kb], c, 0, 0, 0);
+                        acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w8[tt * 64], B[8], c, 0, 0, 0);
+                    }
+                } else {                                           // W_k straight from memory (L2-resident: 26 KB per VF)
+                    const float *Wk = A.W + (size_t)k * NACT * NF + 9 * g;
+#pragma unroll
+                    for (int tt = 0; tt < 12; ++tt) {
+                        const int row = 16 * tt + n16;
+                        float aop[9];
+#pragma unroll
+                        for (int kb = 0; kb < 9; ++kb) aop[kb] = row < NACT * 36 ? Wk[row * 36 + kb] : 0.0f;
+                        f4v c = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                        for (int kb = 0; kb < 9; ++kb) c = __builtin_amdgcn_mfma_f32_16x16x4f32(aop[kb], B[kb], c, 0, 0, 0);
+                        acc[tt] = c;
+                    }
+                }
+                // AB fold: rows 16 t + 4 g + v of action a, c12 increasing within the lane's row group (SPEC §3.1)
+                float q[NACT];
+#pragma unroll
+                for (int aa = 0; aa < NACT; ++aa) {
+                    const int t0 = (36 * aa) >> 4;
+                    float qs = 0.0f;
+#pragma unroll
+                    for (int tt = 0; tt < 3; ++tt) {
+                        const int r0 = 16 * (t0 + tt) + 4 * g - 36 * aa;
+                        const bool in = r0 >= 0 && r0 < 36;
+                        const f4v ab4 = *reinterpret_cast<const f4v *>(abq + n16 * AS + (in ? r0 : 0));
+                        float xq = qs;
+#pragma unroll
+                        for (int vv = 0; vv < 4; ++vv) xq = fmaf(acc[t0 + tt][vv], ab4[vv], xq);
+                        qs = in ? xq : qs;
+                    }
+                    q[aa] = qs;
+                }
+                item_tree_sum<NACT>(q);
+                if (out_lane && ocol_item < nk) {
+                    const int ent = lst[ocol_item];
+#pragma unroll
+                    for (int aa = 0; aa < NACT; ++aa) s_qv[ent >> 8][aa][ent & 0xff] = q[aa];
+                }
+                wave_lds_sync();                                   // the tables are rewritten by the next unit
+            }
+        }
+        __syncthreads();
+        if (tid < MAX_VF) s_cnt[par][tid] = 0;                   // next used at step j + 2, behind step j + 1's barrier
+        // ------------------------------------------------------------ G
+        if (valid) {
+            float qa[NACT];
+#pragma unroll
+            for (int aa = 0; aa < NACT; ++aa) qa[aa] = s_qv[0][aa][il];
+            bool declined = false;
+            if (entering) {
+                float q0[NACT];
+#pragma unroll
+                for (int aa = 0; aa < NACT; ++aa) q0[aa] = s_qv[1][aa][il];
+                float mc = qa[0], m0 = q0[0];
+#pragma unroll
+                for (int aa = 1; aa < NACT; ++aa) { mc = fmaxf(mc, qa[aa]); m0 = fmaxf(m0, q0[aa]); }
+                declined = !(mc >= m0);
+                if (declined) {
+#pragma unroll
+                    for (int aa = 0; aa < NACT; ++aa) qa[aa] = q0[aa];
+                }
+            }
+#pragma unroll
+            for (int aa = 0; aa < NACT; ++aa) qc[aa] = qa[aa];
+            sx = nx; sy = ny; svx = nvx; svy = nvy;
+            oid = (declined || stay) ? -cand : cand;
+            osteps = keep ? osteps + 1 : 0;
+            eps = dn ? 0 : eps1;
+            c_en.add(cand, entering && !declined);
+            c_de.add(cand, declined);
+            if (!is_begin) {
+                last_a = a; last_r = rew; last_dn = dn;
+                c_vf.add(o, true);
+                c_su.add(o, o >= 1 && succ);
+                const float r = ep_ret + rew;
+                if (dn) {
+                    episodes += 1; goals += dn == 1 ? 1 : 0; len_sum += eps1;
+                    ret_sum = ret_sum + (double)r;
+                    ep_ret = 0.0f;
+                    finished = true;
+                    if (A.one_episode) alive = false;
+                } else {
+                    ep_ret = r;
+                }
+            } else {
+                ep_ret = 0.0f;
+                finished = false;
+            }
+        }
+    }
+
+    // ---- exit: the stepped envs' results, once. The output pointers are fetched from the kernel arguments again here, through
+    // an opaque copy of the argument pointer: otherwise the compiler keeps the 21 pointers it loaded at entry live in scalar
+    // registers across the whole step loop, where they crowd the loop's own scalars out into spill slots
+    if (skip) return;
+    const RolloutArgs *K = (const RolloutArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(K));
+    K->x[e] = sx; K->y[e] = sy; K->vx[e] = svx; K->vy[e] = svy;
+#pragma unroll
+    for (int a = 0; a < NACT; ++a) K->qcache[(size_t)a * N + e] = qc[a];
+    K->option_id[e] = oid; K->opt_steps[e] = osteps; K->ep_steps[e] = eps;
+    if (K->n_steps > 0) { K->action[e] = (uint8_t)last_a; K->reward[e] = last_r; K->done[e] = (uint8_t)last_dn; }
+    const scg_rollout_stats &S = K->st;
+    if (S.ep_return) S.ep_return[e] = ep_ret;
+    if (S.ret_sum) S.ret_sum[e] = ret_sum;
+    if (S.episodes) S.episodes[e] = episodes;
+    if (S.goals) S.goals[e] = goals;
+    if (S.len_sum) S.len_sum[e] = len_sum;
+    if (S.finished) S.finished[e] = finished ? 1 : 0;
+    for (int k = 0; k < K->n_vf; ++k) {
+        const size_t at = (size_t)k * N + e;
+        if (S.vf_steps) S.vf_steps[at] += c_vf.get(k);
+        if (S.entries) S.entries[at] += c_en.get(k);
+        if (S.declines) S.declines[at] += c_de.get(k);
+        if (S.successes) S.successes[at] += c_su.get(k);
+    }
+}

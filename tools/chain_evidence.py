@@ -25,6 +25,7 @@ ap.add_argument("--r-succ", type=float, default=0.0, help="option completion rew
 ap.add_argument("--reoffer", type=int, default=4, help="SPEC 4.2 reoffer_period")
 ap.add_argument("--floor-div", type=int, default=16, help="update_count_floor = envs / this (0: no floor)")
 ap.add_argument("--max-option-steps", type=int, default=200)
+ap.add_argument("--eval-episodes", type=int, default=4096, help="episodes of each greedy evaluate() (SPEC §8; 0: none)")
 ap.add_argument("--json", default=None, help="also write the rows as JSON lines to this file")
 a = ap.parse_args()
 HP = dict(alpha=a.alpha, epsilon=0.05, gamma=0.99, max_episode_steps=2000, max_option_steps=a.max_option_steps, r_option_success=a.r_succ,
@@ -40,6 +41,14 @@ def run(ag, steps):
     return 1000.0 * float(goals) / max(steps * a.envs, 1)
 
 
+def evaluate(ag):
+    """The greedy policy's success rate and mean episode length (SkillChainingAgent.evaluate), or NaNs without evaluation."""
+    if not a.eval_episodes:
+        return float("nan"), float("nan")
+    r = ag.evaluate(n_episodes=a.eval_episodes)
+    return r["success_rate"], r["mean_length"]
+
+
 rows = []
 for seed in a.seeds:
     res = {}
@@ -52,12 +61,14 @@ for seed in a.seeds:
                                  gestation=a.gestation if mode == "chain+gest" else 0)
         discovery_steps = ag.t - t0
         after_rate = run(ag, a.after)
+        ev_succ, ev_len = evaluate(ag)
         inside = [int((ag.state.option_id == k).sum()) for k in range(a.options + 1)]
         res[mode] = dict(seed=seed, mode=mode, warm_rate=warm_rate, discovery_steps=discovery_steps, after_rate=after_rate,
+                         eval_success=ev_succ, eval_length=ev_len,
                          options=[{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()} for r in report],
                          envs_per_option=inside, edges=sorted(ag.skill_graph().edges()))
-        print(f"seed {seed} {mode:10s}: warm {warm_rate:6.3f} -> after {after_rate:6.3f} goals/1k env-steps "
-              f"({len(report)} options, {discovery_steps} discovery step-batches, envs per option {inside})", flush=True)
+        print(f"seed {seed} {mode:10s}: warm {warm_rate:6.3f} -> after {after_rate:6.3f} goals/1k env-steps, "
+              f"eval success {ev_succ:6.3f} mean length {ev_len:7.1f} ({len(report)} options, {discovery_steps} discovery step-batches, envs per option {inside})", flush=True)
         for r in res[mode]["options"]:
             print("    created", r, flush=True)
         del ag
@@ -66,9 +77,11 @@ for seed in a.seeds:
     warm_rate = run(ag, a.warm)
     run(ag, res["chain"]["discovery_steps"])
     after_rate = run(ag, a.after)
-    res["root-only"] = dict(seed=seed, mode="root-only", warm_rate=warm_rate, after_rate=after_rate)
-    print(f"seed {seed} root-only : warm {warm_rate:6.3f} -> after {after_rate:6.3f} goals/1k env-steps "
-          f"(same env-steps as the chain run)", flush=True)
+    ev_succ, ev_len = evaluate(ag)
+    res["root-only"] = dict(seed=seed, mode="root-only", warm_rate=warm_rate, after_rate=after_rate, eval_success=ev_succ,
+                            eval_length=ev_len)
+    print(f"seed {seed} root-only : warm {warm_rate:6.3f} -> after {after_rate:6.3f} goals/1k env-steps, "
+          f"eval success {ev_succ:6.3f} mean length {ev_len:7.1f} (same env-steps as the chain run)", flush=True)
     del ag
     c, g, r0 = res["chain"]["after_rate"], res["chain+gest"]["after_rate"], after_rate
     print(f"seed {seed} verdict   : chain / root-only = {c / max(r0, 1e-9):.2f}, chain+gest / root-only = {g / max(r0, 1e-9):.2f}", flush=True)

@@ -1,4 +1,5 @@
-"""Diagnostic: does the batched root Q-learning actually learn Pinball? Prints goal arrivals per 1000 env-steps."""
+"""Diagnostic: does the batched root Q-learning actually learn Pinball? Prints goal arrivals per 1000 env-steps during training
+and, beside them, the greedy policy's success rate and mean episode length from SkillChainingAgent.evaluate() (SPEC §8)."""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
@@ -10,6 +11,7 @@ ap.add_argument("--alpha", type=float, default=0.02); ap.add_argument("--eps", t
 ap.add_argument("--gamma", type=float, default=0.99); ap.add_argument("--iters", type=int, default=30)
 ap.add_argument("--chunk", type=int, default=500); ap.add_argument("--maxep", type=int, default=2000)
 ap.add_argument("--seed", type=int, default=1)
+ap.add_argument("--eval-episodes", type=int, default=4096, help="episodes of each evaluate() (0: no evaluation column)")
 a = ap.parse_args()
 ag = SkillChainingAgent(a.map, a.envs, 0, seed=a.seed, alpha=a.alpha, epsilon=a.eps, gamma=a.gamma, max_episode_steps=a.maxep)
 print(f"# learning_curve map {a.map} envs {a.envs} alpha {a.alpha} eps {a.eps} gamma {a.gamma} seed {a.seed}", flush=True)
@@ -19,4 +21,8 @@ for it in range(a.iters):
         ag.step_batch()
         goals += (ag.state.done == 1).sum(); touts += (ag.state.done == 2).sum()
     g, t = int(goals), int(touts)
-    print(f"iter {it:3d}  goals/1k env-steps {1000*g/(a.chunk*a.envs):7.3f}  timeouts {t:6d}  |W|max {float(ag.W.abs().max()):9.3f}", flush=True)
+    ev = ""
+    if a.eval_episodes:
+        r = ag.evaluate(n_episodes=a.eval_episodes)
+        ev = f"  eval success {r['success_rate']:6.3f}  mean length {r['mean_length']:7.1f}"
+    print(f"iter {it:3d}  goals/1k env-steps {1000*g/(a.chunk*a.envs):7.3f}  timeouts {t:6d}  |W|max {float(ag.W.abs().max()):9.3f}{ev}", flush=True)
