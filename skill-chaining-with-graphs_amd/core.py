@@ -108,6 +108,19 @@ class ScgContext:
     def _step_flags(self, learn: bool, apply: bool) -> int:
         return (STEP_LEARN if learn else 0) | (STEP_APPLY if (learn and apply) else 0)
 
+    def _chk_operands(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor) -> None:
+        """The env state, weight and classifier tensors step() and rollout() hand to the library."""
+        N = self.n_envs
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        self._chk(st.x, f32, N, "x"); self._chk(st.y, f32, N, "y")
+        self._chk(st.vx, f32, N, "vx"); self._chk(st.vy, f32, N, "vy")
+        self._chk(st.option_id, i32, N, "option_id"); self._chk(st.opt_steps, i32, N, "opt_steps")
+        self._chk(st.ep_steps, i32, N, "ep_steps"); self._chk(st.qcache, f32, NUM_ACTIONS * N, "qcache")
+        self._chk(st.action, u8, N, "action"); self._chk(st.reward, f32, N, "reward")
+        self._chk(st.done, u8, N, "done")
+        self._chk(W, f32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
+        self._chk(clf, f32, self.n_vf * CLF_STRIDE, "clf")
+
     def step(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t: int,
              learn: bool = True, apply: bool = True) -> None:
         # the validated, pre-marshalled pointer arguments of the last call are reused while the same tensors come back
@@ -123,16 +136,7 @@ class ScgContext:
             _lib.check(self._step_fn(self._ctx, *cached[1], C.c_uint32(enabled_mask), C.c_uint64(t), C.c_uint32(flags),
                                      self._stream()), self._ctx, "scg_step")
             return
-        N = self.n_envs
-        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
-        self._chk(st.x, f32, N, "x"); self._chk(st.y, f32, N, "y")
-        self._chk(st.vx, f32, N, "vx"); self._chk(st.vy, f32, N, "vy")
-        self._chk(st.option_id, i32, N, "option_id"); self._chk(st.opt_steps, i32, N, "opt_steps")
-        self._chk(st.ep_steps, i32, N, "ep_steps"); self._chk(st.qcache, f32, NUM_ACTIONS * N, "qcache")
-        self._chk(st.action, u8, N, "action"); self._chk(st.reward, f32, N, "reward")
-        self._chk(st.done, u8, N, "done")
-        self._chk(W, f32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
-        self._chk(clf, f32, self.n_vf * CLF_STRIDE, "clf")
+        self._chk_operands(st, W, clf)
         flags = self._step_flags(learn, apply)
         if st is not getattr(self, "_last_state", None):      # another state object (its memory may be recycled)
             self.invalidate_order()
@@ -151,16 +155,8 @@ class ScgContext:
         (with `begin`: a new episode for every env at t0 first, the steps at t0+1 .. t0+n_steps). W is read, never written.
         `stats` (EpisodeStats of this context's n_vf and n_envs, on its device) receives the episode counters; `one_episode`
         leaves envs alone whose `stats.finished` is set. The step's prepared env order is invalid afterwards."""
+        self._chk_operands(st, W, clf)
         N = self.n_envs
-        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
-        self._chk(st.x, f32, N, "x"); self._chk(st.y, f32, N, "y")
-        self._chk(st.vx, f32, N, "vx"); self._chk(st.vy, f32, N, "vy")
-        self._chk(st.option_id, i32, N, "option_id"); self._chk(st.opt_steps, i32, N, "opt_steps")
-        self._chk(st.ep_steps, i32, N, "ep_steps"); self._chk(st.qcache, f32, NUM_ACTIONS * N, "qcache")
-        self._chk(st.action, u8, N, "action"); self._chk(st.reward, f32, N, "reward")
-        self._chk(st.done, u8, N, "done")
-        self._chk(W, f32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
-        self._chk(clf, f32, self.n_vf * CLF_STRIDE, "clf")
         n_steps, t0 = int(n_steps), int(t0)
         if not (0 <= n_steps <= _lib.ROLLOUT_MAX_STEPS) or (n_steps == 0 and not begin):
             raise ScgError(f"rollout: n_steps must be in [1, {_lib.ROLLOUT_MAX_STEPS}] ([0, ...] with begin=True)")
@@ -170,12 +166,12 @@ class ScgContext:
         if stats is not None:
             if stats.n != N or stats.n_vf != self.n_vf:
                 raise ScgError(f"rollout: stats are for {stats.n} envs x {stats.n_vf} VFs, the context has {N} x {self.n_vf}")
-            self._chk(stats.ep_return, f32, N, "stats.ep_return"); self._chk(stats.ret_sum, torch.float64, N, "stats.ret_sum")
+            self._chk(stats.ep_return, torch.float32, N, "stats.ep_return"); self._chk(stats.ret_sum, torch.float64, N, "stats.ret_sum")
             for f in ("episodes", "goals", "len_sum"):
-                self._chk(getattr(stats, f), i32, N, "stats." + f)
+                self._chk(getattr(stats, f), torch.int32, N, "stats." + f)
             for f in ("vf_steps", "entries", "declines", "successes"):
-                self._chk(getattr(stats, f), i32, self.n_vf * N, "stats." + f)
-            self._chk(stats.finished, u8, N, "stats.finished")
+                self._chk(getattr(stats, f), torch.int32, self.n_vf * N, "stats." + f)
+            self._chk(stats.finished, torch.uint8, N, "stats.finished")
             cs = stats.c_struct()
         elif one_episode:
             raise ScgError("rollout: one_episode needs stats (its `finished` flags)")

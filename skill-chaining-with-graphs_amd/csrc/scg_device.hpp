@@ -370,6 +370,79 @@ __device__ __forceinline__ float clf_z(const float *w, float x, float y) {
     return z;
 }
 
+// ------------------------------------------------------------------ SPEC §2, §4.3: one env's draw and action
+__device__ __forceinline__ void env_draw(uint64_t gid, uint64_t t, uint64_t seed, uint32_t (&u)[4]) {
+    philox4x32_10((uint32_t)gid, (uint32_t)(t & 0xffffffffu), (uint32_t)(t >> 32), 0u, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), u);
+}
+// epsilon-greedy on the cached Q(s, .): explore with u[0], a uniform action from u[1]; the greedy action is the first maximum
+__device__ __forceinline__ int act_spec(const uint32_t (&u)[4], const float (&qc)[NACT], float epsilon) {
+    const bool explore = (float)(u[0] >> 8) * 0x1p-24f < epsilon;
+    const int a_rand = (int)__umulhi(u[1], 5u);
+    int a_greedy = 0;
+    float best = qc[0];
+#pragma unroll
+    for (int a = 1; a < NACT; ++a) {
+        if (qc[a] > best) { best = qc[a]; a_greedy = a; }
+    }
+    return explore ? a_rand : a_greedy;
+}
+
+// ------------------------------------------------------------------ SPEC §1.4
+// episode end after step eps1 (the episode's step count with this one): 1 goal, 2 time-out, 0 none
+__device__ __forceinline__ int episode_end(bool goal, int eps1, int max_ep) { return goal ? 1 : (eps1 >= max_ep ? 2 : 0); }
+// the restart state of an ended episode: start u2 * n_starts / 2^32, at rest
+__device__ __forceinline__ void restart_state(uint32_t u2, const float *starts, int n_starts, float &x, float &y, float &vx, float &vy) {
+    const uint32_t si = __umulhi(u2, (uint32_t)n_starts);
+    x = starts[2 * si]; y = starts[2 * si + 1]; vx = 0.0f; vy = 0.0f;
+}
+
+// ------------------------------------------------------------------ SPEC §4.2
+// target of option k: the option whose initiation set k leads into, 0 = the task goal (3 bits per option in `parents`)
+__device__ __forceinline__ unsigned target_of(uint32_t parents, int k) { return (parents >> (3 * (k & 7))) & 7u; }
+// membership masks of s' (inA) and s_next (inB): bit k = the point lies in option k's initiation set, over the options k < n_vf in `known`
+__device__ __forceinline__ void member_masks(const float *clf, int n_vf, unsigned known, float x1, float y1, float xn, float yn,
+                                             unsigned &inA, unsigned &inB) {
+    inA = 0; inB = 0;
+#pragma unroll
+    for (int k = 1; k < MAX_VF; ++k) {
+        if (k < n_vf && ((known >> k) & 1u)) {
+            const float *w = clf + CLF_STRIDE * k;
+            if (clf_z(w, x1, y1) > 0.0f) inA |= 1u << k;
+            if (clf_z(w, xn, yn) > 0.0f) inB |= 1u << k;
+        }
+    }
+}
+// option k reached its target from a state with membership mask `in` (bit 0 unused) and goal flag `goal`
+__device__ __forceinline__ bool option_succ(uint32_t parents, int k, unsigned in, bool goal) {
+    const unsigned p = target_of(parents, k);
+    return p == 0 ? goal : (bool)((in >> p) & 1u);
+}
+// option end of an env that ran option o >= 1 for osteps + 1 steps into s' (membership inA, goal, episode end dn): the option goes on
+// (keep) unless the episode ended, it succeeded (succ), s' left its initiation set or it timed out
+__device__ __forceinline__ bool option_keep(uint32_t parents, int o, unsigned inA, bool goal, int dn, int osteps, int max_opt, bool &succ) {
+    succ = option_succ(parents, o, inA, goal);
+    const bool fail = !succ && !((inA >> o) & 1u);
+    const bool otime = osteps + 1 >= max_opt;
+    return !((dn != 0) || succ || fail || otime);
+}
+// selection: the smallest enabled option k with s_next in its initiation set and outside its target region (0: none)
+__device__ __forceinline__ int select_option(uint32_t parents, unsigned inB, unsigned enabled) {
+    unsigned tgtB = 0;                                     // bit k: s_next already lies in option k's target region
+#pragma unroll
+    for (int k = 1; k < MAX_VF; ++k) {
+        const unsigned p = target_of(parents, k);
+        if (p != 0 && ((inB >> p) & 1u)) tgtB |= 1u << k;
+    }
+    const unsigned sel = inB & ~tgtB & enabled;            // a gestating option is never selected
+    return sel ? __builtin_ctz(sel) : 0;
+}
+// re-offer: an env that stayed out of option k (option id o_in = -k) and still has k as its candidate is offered k again only every
+// reoffer_period-th step (staggered by env id; a new episode is a new offer) — in between it stays out (returns k) without a new
+// comparison, i.e. without the option's value function being evaluated for it
+__device__ __forceinline__ int reoffer_stay(bool keep, int cand, int dn, int o_in, uint64_t t, uint64_t gid, uint32_t reoffer_mask) {
+    return (!keep && cand >= 1 && dn == 0 && o_in == -cand && (((uint32_t)t + (uint32_t)gid) & reoffer_mask) != 0u) ? cand : 0;
+}
+
 // ------------------------------------------------------------------ SPEC §6
 __device__ __forceinline__ float sigmoid_spec(float z) {
     const float LOG2E = 0x1.715476p+0f, LN2HI = 0x1.63p-1f, LN2LO = -0x1.bd0106p-13f;

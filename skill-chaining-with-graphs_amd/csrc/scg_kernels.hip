@@ -107,50 +107,7 @@ __device__ __forceinline__ bool in_set(const StepArgs &A, int k, float x, float 
     return clf_z(A.clf + CLF_STRIDE * k, x, y) > 0.0f;
 }
 
-// ------------------------------------------------------------------------------------------------
-// SPEC §3 tables of one item from its four Z_d^1 (z1p: 4 float2 in LDS). The calling lane owns second index
-// `cp` (c2 of AB, c4 of CD; cp < 6) and gets, for the first index c = 0..5, AB[6c + cp] and CD[6c + cp]:
-// AB[c2] = Z_1^c2, AB[c1*6 + c2] = cmul(AB[(c1-1)*6 + c2], Z_0^1) (CD likewise from Z_3, Z_2), Z^0 = (1, 0), Z^k = cmul(Z^(k-1), Z^1):
-// five chained products per table column instead of a power chain plus a product per entry.
-__device__ __forceinline__ float2 zpow_sel(float2 z, int c) {
-    float2 cur = z, out = make_float2(1.0f, 0.0f);
-#pragma unroll
-    for (int j = 1; j <= 5; ++j) {
-        if (c == j) out = cur;
-        if (j < 5) cur = cmul(cur, z);
-    }
-    return out;
-}
-__device__ __forceinline__ void item_entries(const float2 *z1p, int cp, float2 (&ab)[6], float2 (&cd)[6]) {
-    const float4 za = *reinterpret_cast<const float4 *>(z1p), zc = *reinterpret_cast<const float4 *>(z1p + 2);
-    const float2 z0 = make_float2(za.x, za.y), z1 = make_float2(za.z, za.w);
-    const float2 z2 = make_float2(zc.x, zc.y), z3 = make_float2(zc.z, zc.w);
-    ab[0] = zpow_sel(z1, cp); cd[0] = zpow_sel(z3, cp);
-#pragma unroll
-    for (int c = 1; c < 6; ++c) {
-        ab[c] = cmul(ab[c - 1], z0);
-        cd[c] = cmul(cd[c - 1], z2);
-    }
-}
-
-// SPEC §3.1 butterfly over the 16 partial sums of one item (4 row groups x re|im, the item's 8 columns hold
-// [re x 4 items, im x 4 items]): u_g = q_re + q_im (lane xor 4), then (u_0 + u_1) + (u_2 + u_3) (lane xor 16, 32)
-template <int M>
-__device__ __forceinline__ void item_tree_sum(float (&q)[M]) {
-#pragma unroll
-    for (int a = 0; a < M; ++a) q[a] = q[a] + swz_xor4(q[a]);
-#pragma unroll
-    for (int a = 0; a < M; ++a) {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(q[a]), __float_as_uint(q[a]), false, false);
-        q[a] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-#pragma unroll
-    for (int a = 0; a < M; ++a) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(q[a]), __float_as_uint(q[a]), false, false);
-        q[a] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-}
-
+#include "scg_eval.hpp"
 #include "scg_step_kernel.hpp"
 #include "scg_rollout_kernel.hpp"
 
@@ -1417,18 +1374,24 @@ struct PeerTarget {
     ~PeerTarget() { c->G_out = G; c->nkf_out = nkf; c->nk_out = nk; }
 };
 
-static void fill_common(const scg_ctx *c, StepArgs &A) {
+// the per-context parameters of the step and the rollout kernel (StepArgs, RolloutArgs); every other field zero
+extern "C++" template <typename Args>
+static void fill_shared(const scg_ctx *c, Args &A) {
     memset(&A, 0, sizeof(A));
-    A.n_vf = c->n_vf;
+    A.n = c->cfg.n_envs; A.n_vf = c->n_vf;
     A.seed = c->cfg.seed; A.env_base = c->cfg.env_id_base;
-    A.gamma = c->cfg.gamma; A.epsilon = c->cfg.epsilon; A.r_succ = c->cfg.r_option_success;
-    A.max_ep = c->cfg.max_episode_steps; A.max_opt = c->cfg.max_option_steps;
+    A.epsilon = c->cfg.epsilon; A.max_ep = c->cfg.max_episode_steps; A.max_opt = c->cfg.max_option_steps;
     A.reoffer_mask = c->cfg.reoffer_period > 1 ? (uint32_t)(c->cfg.reoffer_period - 1) : 0u;
+    A.parents = c->parents; A.gest = c->gest;
     A.ms = c->ms;
     A.edges = c->d_edges; A.starts = c->d_starts; A.cellmask = c->d_cellmask;
+}
+
+static void fill_common(const scg_ctx *c, StepArgs &A) {
+    fill_shared(c, A);
+    A.gamma = c->cfg.gamma; A.r_succ = c->cfg.r_option_success;
     A.slabs = c->d_slabs; A.cnts = c->d_cnts;
-    A.parents = c->parents;
-    A.gest = c->gest; A.gest_succ = c->gest_succ;
+    A.gest_succ = c->gest_succ;
     A.ring_x = c->ring_x; A.ring_y = c->ring_y; A.events = c->events; A.ev_len = c->ev_len;
     A.ring_mask = c->ring_len > 0 ? c->ring_len - 1 : 0;
     A.stamps = c->d_stamps;
@@ -1506,7 +1469,7 @@ int scg_step(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *opti
     A.option_id = option_id; A.opt_steps = opt_steps; A.ep_steps = ep_steps; A.qcache = qcache;
     A.action = action; A.reward = reward; A.done = done;
     A.W = W; A.clf = clf;
-    A.n = c->cfg.n_envs; A.k_lo = 0; A.k_hi = c->n_vf - 1;
+    A.k_lo = 0; A.k_hi = c->n_vf - 1;
     A.enabled = enabled_mask; A.learn = (flags & SCG_STEP_LEARN) ? 1u : 0u; A.t = t;
     if (flags & 0x100u) A.k_hi = -1;     // diagnostic only (bench.py --diag-no-td): skip the TD passes
     // env order of this step (SPEC §5): counting sort by the option ids the previous step left
@@ -1577,18 +1540,13 @@ int scg_rollout(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *o
     SCG_CHECK_ASYNC(c);
     SCG_ON_DEVICE(c, "scg_rollout");
     RolloutArgs R;
-    memset(&R, 0, sizeof(R));
+    fill_shared(c, R);
     R.x = x; R.y = y; R.vx = vx; R.vy = vy; R.option_id = option_id; R.opt_steps = opt_steps; R.ep_steps = ep_steps;
     R.qcache = qcache; R.action = action; R.reward = reward; R.done = done; R.W = W; R.clf = clf;
-    R.edges = c->d_edges; R.cellmask = c->d_cellmask; R.starts = c->d_starts;
     if (stats) R.st = *stats;
-    R.n = c->cfg.n_envs; R.n_vf = c->n_vf; R.n_steps = n_steps;
+    R.n_steps = n_steps;
     R.begin = (flags & SCG_ROLLOUT_BEGIN) ? 1u : 0u; R.one_episode = (flags & SCG_ROLLOUT_ONE_EPISODE) ? 1u : 0u;
-    R.enabled = enabled_mask; R.gest = c->gest; R.parents = c->parents;
-    R.t0 = t0; R.seed = c->cfg.seed; R.env_base = c->cfg.env_id_base;
-    R.epsilon = c->cfg.epsilon; R.max_ep = c->cfg.max_episode_steps; R.max_opt = c->cfg.max_option_steps;
-    R.reoffer_mask = c->cfg.reoffer_period > 1 ? (uint32_t)(c->cfg.reoffer_period - 1) : 0u;
-    R.ms = c->ms;
+    R.enabled = enabled_mask; R.t0 = t0;
     // envs per wave: the largest of 2 .. 32 that still gives every CU a workgroup (one 8-wave workgroup per CU: LDS); the
     // results do not depend on it
     int epw = 2;

@@ -7,9 +7,8 @@
 //      (pinball_wave_*), episode bookkeeping, SPEC §4.2 option logic; Z_d^1 of s_next to LDS; the (env, value function)
 //      pairs that need Q(s_next, .) — the VF the env runs next, plus the root for an entering env — compacted into one
 //      list per value function (ballot / popcount, an LDS counter per list)
-//   E  the lists in 8-item units dealt over the workgroup's waves: one table build, then SPEC §3.1's contraction on
-//      v_mfma_f32_16x16x4_f32 (W_k the A operand: W_0 from LDS, staged once per launch; other VFs straight from memory),
-//      the AB fold and the butterfly
+//   E  the lists in 8-item units dealt over the workgroup's waves: the E unit of scg_eval.hpp (one table build, then SPEC §3.1's
+//      contraction with W_k the A operand: W_0 from LDS, staged once per launch; other VFs straight from memory)
 //   G  each lane again: the value gate, the caller-visible ids, qcache, the statistics counters
 // State, qcache and counters stay in registers across the steps and are written once at the end. Finished envs (ONE_EPISODE)
 // and envs beyond N drop out of the lists; a workgroup with nothing left to step leaves the loop.
@@ -106,11 +105,10 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs A
 
     // ---- once per launch: W_0, the edge table and the classifiers to LDS
     for (int i = tid; i < W_FLOATS; i += RO_THREADS) {
-        int t, kb, ln, dst;
-        if (i < W_TAIL) { const int q = i >> 2; t = q >> 7; ln = q & 63; kb = 4 * ((q >> 6) & 1) + (i & 3); dst = i; }
-        else { const int q = i - W_TAIL; t = q >> 6; ln = q & 63; kb = 8; dst = i; }
-        const int row = 16 * t + (ln & 15);
-        s_w0[dst] = row < NACT * 36 ? A.W[row * 36 + 9 * (ln >> 4) + kb] : 0.0f;
+        const int z = i - W_TAIL;
+        int src;
+        const bool in = i < W_TAIL ? w_a_src(i >> 9, 4 * ((i >> 8) & 1) + (i & 3), (i >> 2) & 63, src) : w_a_src(z >> 6, 8, z & 63, src);
+        s_w0[i] = in ? A.W[src] : 0.0f;
     }
     for (int i = tid; i < A.ms.n_edges * 8; i += RO_THREADS) s_edges[i] = A.edges[i];
     if (tid < A.n_vf * CLF_STRIDE) s_clf[tid] = A.clf[tid];
@@ -126,22 +124,11 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs A
         const int par = j & 1;
         // ------------------------------------------------------------ P
         bool valid = alive;
+        const uint64_t gid = (uint64_t)(A.env_base + e);
         uint32_t u[4] = {0u, 0u, 0u, 0u};
-        if (valid) {
-            const uint64_t gid = (uint64_t)(A.env_base + e);
-            philox4x32_10((uint32_t)gid, (uint32_t)(t & 0xffffffffu), (uint32_t)(t >> 32), 0u,
-                          (uint32_t)(A.seed & 0xffffffffu), (uint32_t)(A.seed >> 32), u);
-        }
+        if (valid) env_draw(gid, t, A.seed, u);
         int a = NACT - 1;
-        if (valid && !is_begin) {
-            const bool explore = (float)(u[0] >> 8) * 0x1p-24f < A.epsilon;
-            const int a_rand = (int)__umulhi(u[1], 5u);
-            int a_greedy = 0;
-            float best = qc[0];
-#pragma unroll
-            for (int aa = 1; aa < NACT; ++aa) if (qc[aa] > best) { best = qc[aa]; a_greedy = aa; }
-            a = explore ? a_rand : a_greedy;
-        }
+        if (valid && !is_begin) a = act_spec(u, qc, A.epsilon);
         float px = sx, py = sy, pvx = svx, pvy = svy, rew = 0.0f;
         bool goal = false;
         if (!is_begin) {                                       // (wave-uniform)
@@ -163,38 +150,13 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs A
         bool keep = false, succ = false;
         int cand = 0, on = 0, stay = 0;
         if (valid) {
-            dn = is_begin ? 2 : (goal ? 1 : (eps1 >= A.max_ep ? 2 : 0));
-            if (dn) {
-                const uint32_t si = __umulhi(u[2], (uint32_t)A.ms.n_starts);
-                nx = A.starts[2 * si]; ny = A.starts[2 * si + 1]; nvx = 0.0f; nvy = 0.0f;
-            }
-            unsigned inA = 0, inB = 0;
-#pragma unroll
-            for (int k = 1; k < MAX_VF; ++k) {
-                if (k < A.n_vf && ((known >> k) & 1u)) {
-                    const float *w = s_clf + CLF_STRIDE * k;
-                    if (!is_begin && clf_z(w, px, py) > 0.0f) inA |= 1u << k;
-                    if (clf_z(w, nx, ny) > 0.0f) inB |= 1u << k;
-                }
-            }
-            if (!is_begin && o >= 1) {
-                const unsigned p2 = (A.parents >> (3 * (o & 7))) & 7u;
-                succ = (p2 == 0) ? goal : ((inA >> p2) & 1u);
-                const bool fail = !succ && !((inA >> o) & 1u);
-                const bool otime = osteps + 1 >= A.max_opt;
-                keep = !((dn != 0) || succ || fail || otime);
-            }
-            unsigned tgtB = 0;
-#pragma unroll
-            for (int k = 1; k < MAX_VF; ++k) {
-                const unsigned p2 = (A.parents >> (3 * k)) & 7u;
-                if (p2 != 0 && ((inB >> p2) & 1u)) tgtB |= 1u << k;
-            }
-            const unsigned sel = inB & ~tgtB & A.enabled;
-            cand = keep ? o : (sel ? __builtin_ctz(sel) : 0);
-            const int o_in = is_begin ? 0 : oid;
-            stay = (!keep && cand >= 1 && dn == 0 && o_in == -cand &&
-                    (((uint32_t)t + (uint32_t)(A.env_base + e)) & A.reoffer_mask) != 0u) ? cand : 0;
+            dn = is_begin ? 2 : episode_end(goal, eps1, A.max_ep);
+            if (dn) restart_state(u[2], A.starts, A.ms.n_starts, nx, ny, nvx, nvy);
+            unsigned inA, inB;
+            member_masks(s_clf, A.n_vf, known, px, py, nx, ny, inA, inB);
+            if (!is_begin && o >= 1) keep = option_keep(A.parents, o, inA, goal, dn, osteps, A.max_opt, succ);
+            cand = keep ? o : select_option(A.parents, inB, A.enabled);
+            stay = reoffer_stay(keep, cand, dn, is_begin ? 0 : oid, t, gid, A.reoffer_mask);
             on = stay ? 0 : cand;
             const float sh[4] = {nx, ny, fmaf(nvx, 0.25f, 0.5f), fmaf(nvy, 0.25f, 0.5f)};
 #pragma unroll
@@ -222,11 +184,14 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs A
         for (int k = 0; k < MAX_VF; ++k) { cnt[k] = k < A.n_vf ? s_cnt[par][k] : 0; units += (cnt[k] + 7) >> 3; }
         if (units == 0) break;                                 // (workgroup-uniform) nothing left to step
         {
-            const int n16 = lane & 15, g = lane >> 4, bi = lane & 7, cp = lane >> 3;
+            const int n16 = lane & 15, g = lane >> 4, bi = lane & 7, cp = lane >> 3;           // lane roles: scg_eval.hpp
             const int bcol = 8 * (bi >> 2) + (bi & 3);
             const int ocol_item = 4 * (n16 >> 3) + (n16 & 3);
             const bool out_lane = (g == 0) && !(n16 & 4);
             float *cdk = sw, *abq = sw + 36 * 16;
+            const float *ab_lane = abq + n16 * AS + 4 * g;
+            const f4v *w4 = reinterpret_cast<const f4v *>(s_w0) + lane;
+            const float *w8 = s_w0 + W_TAIL + lane;
             for (int uu = wave; uu < units; uu += RO_WAVES) {
                 int k = 0, ub = uu;
 #pragma unroll
@@ -236,66 +201,12 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs A
                 }
                 const int nk = cnt[k] - 8 * ub;                    // items of this unit still ahead in the list (>= 1)
                 const uint16_t *lst = &s_list[k][8 * ub];
-                if (cp < 6) {
-                    float2 ab[6], cd[6];
-                    item_entries(s_z1[lst[min(bi, nk - 1)] & 0xff], cp, ab, cd);
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) {
-                        abq[bcol * AS + 6 * c + cp] = ab[c].x; abq[(bcol + 4) * AS + 6 * c + cp] = -ab[c].y;
-                        cdk[(6 * c + cp) * 16 + bcol] = cd[c].x; cdk[(6 * c + cp) * 16 + bcol + 4] = cd[c].y;
-                    }
-                }
+                build_tables(s_z1[lst[min(bi, nk - 1)] & 0xff], cp, bcol, cdk, abq);
                 wave_lds_sync();
-                float B[9];
-#pragma unroll
-                for (int kb = 0; kb < 9; ++kb) B[kb] = cdk[(9 * g + kb) * 16 + n16];
-                f4v acc[12];
-                if (k == 0) {                                      // W_0 from LDS (two ds_read_b128 + one b32 per tile)
-                    const f4v *w4 = reinterpret_cast<const f4v *>(s_w0) + lane;
-                    const float *w8 = s_w0 + W_TAIL + lane;
-#pragma unroll
-                    for (int tt = 0; tt < 12; ++tt) {
-                        const f4v a0 = w4[(tt * 2) * 64], a1 = w4[(tt * 2 + 1) * 64];
-                        f4v c = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                        for (int kb = 0; kb < 4; ++kb) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[kb], B[kb], c, 0, 0, 0);
-#pragma unroll
-                        for (int kb = 0; kb < 4; ++kb) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[kb], B[4 + kb], c, 0, 0, 0);
-                        acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w8[tt * 64], B[8], c, 0, 0, 0);
-                    }
-                } else {                                           // W_k straight from memory (L2-resident: 26 KB per VF)
-                    const float *Wk = A.W + (size_t)k * NACT * NF + 9 * g;
-#pragma unroll
-                    for (int tt = 0; tt < 12; ++tt) {
-                        const int row = 16 * tt + n16;
-                        float aop[9];
-#pragma unroll
-                        for (int kb = 0; kb < 9; ++kb) aop[kb] = row < NACT * 36 ? Wk[row * 36 + kb] : 0.0f;
-                        f4v c = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                        for (int kb = 0; kb < 9; ++kb) c = __builtin_amdgcn_mfma_f32_16x16x4f32(aop[kb], B[kb], c, 0, 0, 0);
-                        acc[tt] = c;
-                    }
-                }
-                // AB fold: rows 16 t + 4 g + v of action a, c12 increasing within the lane's row group (SPEC §3.1)
-                float q[NACT];
-#pragma unroll
-                for (int aa = 0; aa < NACT; ++aa) {
-                    const int t0 = (36 * aa) >> 4;
-                    float qs = 0.0f;
-#pragma unroll
-                    for (int tt = 0; tt < 3; ++tt) {
-                        const int r0 = 16 * (t0 + tt) + 4 * g - 36 * aa;
-                        const bool in = r0 >= 0 && r0 < 36;
-                        const f4v ab4 = *reinterpret_cast<const f4v *>(abq + n16 * AS + (in ? r0 : 0));
-                        float xq = qs;
-#pragma unroll
-                        for (int vv = 0; vv < 4; ++vv) xq = fmaf(acc[t0 + tt][vv], ab4[vv], xq);
-                        qs = in ? xq : qs;
-                    }
-                    q[aa] = qs;
-                }
-                item_tree_sum<NACT>(q);
+                float B[9], q[NACT];
+                load_b(cdk, n16, g, B);
+                if (k == 0) contract_lds<E_TG>(0, B, q, g, w4, w8, ab_lane);      // W_0 from LDS
+                else contract_mem<EO_TG>(A.W + (size_t)k * NACT * NF, B, q, n16, g, ab_lane);      // W_k straight from memory (L2-resident: 26 KB per VF)
                 if (out_lane && ocol_item < nk) {
                     const int ent = lst[ocol_item];
 #pragma unroll

@@ -39,10 +39,6 @@ constexpr int OFF_Z1 = OFF_INT + 6 * BLOCK_ENVS;               // float2 z1[B][2
 //   P, Z  : s[4][B], sn[4][B] (the envs' states), the edge table [256][8] and the pair lists, inside the table area of waves 0..7
 //   E, U1 : W_A | W_B staged in A-operand order (12 row tiles x 9 k-blocks x 64 lanes each) + per wave CDk[36][16] + ABq[16][AS]
 //   U2    : PT_A[36][US], PT_B[36][US], CDT[36][US] (one chunk of U2_CH padded slots = 2 U2_CH K-steps)
-constexpr int W_FLOATS = 12 * 9 * 64;
-constexpr int W_TAIL = 12 * 2 * 64 * 4;                        // k-block 8 of every tile sits behind the two float4 groups
-constexpr int AS = 40;                                         // row stride of ABq (floats): the fold's ds_read_b128 conflict-free
-constexpr int E_TAB_FLOATS = 36 * 16 + 16 * AS;
 constexpr int U2_CH = 9 * WAVES;                               // U2 chunk: padded slots, nine per builder wave (54 of 64 lanes busy)
 constexpr int US = 2 * U2_CH + 4;                              // row stride of the chunk tables (floats): 292 = 36 mod 64, operand reads conflict-free
 constexpr int R_TAB = 2 * W_FLOATS;                            // private tables start behind the staged W_A, W_B
@@ -98,8 +94,6 @@ constexpr unsigned OREC_DECLINED = 0x7fc0deadu;   // result line word [3].y: the
 // variants measured and dropped in round 4 — evaluation-only value functions on the vector pipe or behind the passes, static deals
 // of E's and U1's units, E rebalancing — are kept as profiles/r04_dropped_kernel_variants.diff with their numbers in
 // profiles/r04_td_kernel_ab_log.txt.
-constexpr int E_TG = 4;               // row tiles per operand group of the LDS-fed contraction (12 % E_TG == 0)
-constexpr int EO_TG = 3;              // row tiles whose operands contract_g fetches together (register budget: 9 per tile)
 constexpr int PRIO_P = 2;             // env waves during phase P
 constexpr int PRIO_HELP = 0;          // helper waves during phase P
 constexpr int PRIO_LIST = 1;          // list waves (0..3) after phase P
@@ -109,14 +103,9 @@ __device__ __forceinline__ int sel5(const int (&v)[M], int a) {          // v[a]
     return a == 0 ? v[0] : a == 1 ? v[1] : a == 2 ? v[2] : a == 3 ? v[3] : v[4];
 }
 
-// Lane roles. As an MFMA operand lane (16x16x4): n16 = lane & 15 is the tile row (A) / column (B, C, D), g = lane >> 4
-// the k index (A, B) / the row group (C, D: rows 4 g + v). As a table builder: bi = lane & 7 is the item of an
-// 8-item column block, cp = lane >> 3 the second index (c2 / c4; lanes with cp >= 6 idle).
-// Columns of an 8-item block: item j = 4 h + i  (h = 0, 1; i = 0..3) has its real-part column at 8 h + i and its
-// imaginary-part column at 8 h + 4 + i.
-// Every phase derives them afresh from an opaque copy of the lane id: kept live from the top of the kernel, these dozen
-// values (and the per-lane LDS addresses made from them) were what the register allocator spilled to scratch at every
-// phase boundary — 1024 threads x 256 workgroups going to memory together, on the critical path (round 4 stamps).
+// Lane roles of the E unit (scg_eval.hpp). Every phase derives them afresh from an opaque copy of the lane id: kept live from
+// the top of the kernel, these dozen values (and the per-lane LDS addresses made from them) were what the register allocator
+// spilled to scratch at every phase boundary — 1024 threads x 256 workgroups going to memory together, on the critical path (round 4 stamps).
 #define SCG_LANE_ROLES()                                                                                          \
     int lane_r = lane;                                                                                            \
     asm volatile("" : "+v"(lane_r));                                                                              \
@@ -162,19 +151,15 @@ __device__ __attribute__((noinline)) void stage_w_cold(const float *Wk, float *s
     for (int i = 0; i < 2; ++i) {
         const int d = tid + i * THREADS;
         v[i] = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
-        if (d < N4) {
-            const int t2h = d >> 6, ln = d & 63, row = 16 * (t2h >> 1) + (ln & 15), col = 9 * (ln >> 4) + 4 * (t2h & 1);
-            if (row < NACT * 36) {
-                const F4U w = *reinterpret_cast<const F4U *>(Wk + row * 36 + col);
-                v[i] = (f4v){w.x, w.y, w.z, w.w};
-            }
+        int src;
+        if (d < N4 && w_a_src(d >> 7, 4 * ((d >> 6) & 1), d & 63, src)) {
+            const F4U w = *reinterpret_cast<const F4U *>(Wk + src);
+            v[i] = (f4v){w.x, w.y, w.z, w.w};
         }
     }
     float tl = 0.0f;
-    if (tid < N1) {
-        const int ln = tid & 63, row = 16 * (tid >> 6) + (ln & 15);
-        if (row < NACT * 36) tl = Wk[row * 36 + 9 * (ln >> 4) + 8];
-    }
+    int src;
+    if (tid < N1 && w_a_src(tid >> 6, 8, tid & 63, src)) tl = Wk[src];
 #pragma unroll
     for (int i = 0; i < 2; ++i) { const int d = tid + i * THREADS; if (d < N4) dst4[d] = v[i]; }
     if (tid < N1) s_dst[W_TAIL + tid] = tl;
@@ -219,20 +204,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     SCG_LITE(0);
 #endif
 
-    // private tables of one 8-item column block from the builder lane's item `it` (already clamped by the caller),
-    // state sg (0 = s, 1 = s_next): CDk[c34][col], ABq[col][c12] with ABsel = (Re AB | -Im AB)
-    auto build_tables = [&](int it, int sg, int cp, int bcol, float *cdk, float *abq) {
-        if (cp < 6) {
-            float2 ab[6], cd[6];
-            item_entries(s_z1 + (it * 2 + sg) * 4, cp, ab, cd);
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                abq[bcol * AS + 6 * c + cp] = ab[c].x; abq[(bcol + 4) * AS + 6 * c + cp] = -ab[c].y;
-                cdk[(6 * c + cp) * 16 + bcol] = cd[c].x; cdk[(6 * c + cp) * 16 + bcol + 4] = cd[c].y;
-            }
-        }
-    };
-
     // A operands come from the staged W (value function v of the pass at s_W + v W_FLOATS), per row tile two ds_read_b128
     // (k-blocks 0..3, 4..7) and one ds_read_b32 (k-block 8): w4 / w8 of SCG_LANE_ROLES
     // The pass's update list (s_ulist: items of value function A sorted by action, block order inside a run) and its geometry;
@@ -251,11 +222,10 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             const int cnt = sel5(run_len, a), cntB = sel5(nBa, a), ro = sel5(run_off, a);
             const uint16_t *lst = s_ulist + ro;
             {
-                build_tables(lst[8 * cb + min(bi, cnt - 8 * cb - 1)], 0, cp, bcol, cdk, abq);
+                build_tables(s_z1 + (lst[8 * cb + min(bi, cnt - 8 * cb - 1)] * 2 + 0) * 4, cp, bcol, cdk, abq);    // (tables of s)
                 wave_lds_sync();
                 float B[9];
-#pragma unroll
-                for (int kb = 0; kb < 9; ++kb) B[kb] = cdk[(9 * g + kb) * 16 + n16];
+                load_b(cdk, n16, g, B);
                 // both value functions' three row tiles as independent MFMA chains, interleaved (a column block that still holds
                 // B items runs 6 chains x 9 MFMAs back to back instead of two times 3 dependent ones)
                 auto tiles = [&](auto nv_c) {
@@ -345,83 +315,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             u1_block(a, j);
         }
     };
-    // Q(sigma, .) of the 8 items whose tables sit in this wave's private area, for the value function staged at float offset
-    // `wofs` of region W (SPEC §3.1): T = W (180 x 36) x [Re CD | Im CD] on the matrix pipe — rows 16 t + 4 g + v -> action
-    // rho / 36, c12 = rho % 36; a lane's four rows never straddle actions — then the fold with the AB factors and the butterfly.
-    // The twelve row tiles are taken in two halves of six (MFMAs, then the fold of those six accumulators into the per-action
-    // chains, tile order kept): 24 accumulator registers instead of 48 at the kernel's register peak. The finished sums are in
-    // the lanes with out_lane.
-    auto contract_with = [&](auto tg_c, auto load_a, const float (&B)[9], float (&qo)[NACT], int g, const float *ab_lane) {
-        constexpr int TG = decltype(tg_c)::value;             // row tiles per group (operands of a group are fetched together)
-        float q[NACT + 1] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        // the operands of group hh + 1 are fetched before the products of group hh are issued (two operand sets in registers)
-        f4v a0[2][TG], a1[2][TG];
-        float a8[2][TG];
-#pragma unroll
-        for (int tt = 0; tt < TG; ++tt) load_a(tt, a0[0][tt], a1[0][tt], a8[0][tt]);
-#pragma unroll
-        for (int hh = 0; hh < 12 / TG; ++hh) {
-            if (hh + 1 < 12 / TG) {
-#pragma unroll
-                for (int tt = 0; tt < TG; ++tt) load_a(TG * (hh + 1) + tt, a0[(hh + 1) & 1][tt], a1[(hh + 1) & 1][tt], a8[(hh + 1) & 1][tt]);
-            }
-            f4v acc[TG];
-#pragma unroll
-            for (int tt = 0; tt < TG; ++tt) {
-                f4v c = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[hh & 1][tt][kb], B[kb], c, 0, 0, 0);
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[hh & 1][tt][kb], B[4 + kb], c, 0, 0, 0);
-                acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a8[hh & 1][tt], B[8], c, 0, 0, 0);
-            }
-#pragma unroll
-            for (int tt = 0; tt < TG; ++tt) {
-                const int t = TG * hh + tt;
-                const int Ct = (16 * t) % 36, At = (16 * t) / 36;
-                if (Ct + 12 < 36) {                          // the tile's 16 rows belong to one action
-                    const f4v ab4 = *reinterpret_cast<const f4v *>(ab_lane + Ct);
-#pragma unroll
-                    for (int vv = 0; vv < 4; ++vv) q[At] = fmaf(acc[tt][vv], ab4[vv], q[At]);
-                } else {                                     // row groups g >= (36 - Ct) / 4 belong to the next action
-                    const bool wrap = 4 * g >= 36 - Ct;
-                    const f4v ab4 = *reinterpret_cast<const f4v *>(ab_lane + (wrap ? Ct - 36 : Ct));
-                    float xq = wrap ? q[At + 1] : q[At];
-#pragma unroll
-                    for (int vv = 0; vv < 4; ++vv) xq = fmaf(acc[tt][vv], ab4[vv], xq);
-                    q[At] = wrap ? q[At] : xq;
-                    q[At + 1] = wrap ? xq : q[At + 1];
-                }
-            }
-        }
-#pragma unroll
-        for (int a = 0; a < NACT; ++a) qo[a] = q[a];
-        item_tree_sum<NACT>(qo);
-    };
-    // ... A operands from the value function staged at float offset `wofs` of region W (two ds_read_b128 + one ds_read_b32 per tile)
-    auto contract = [&](int wofs, const float (&B)[9], float (&qo)[NACT], int n16, int g, const f4v *w4, const float *w8, const float *ab_lane) {
-        contract_with(std::integral_constant<int, E_TG>{}, [&](int t, f4v &a0, f4v &a1, float &a8) {
-            a0 = w4[wofs / 4 + (t * 2) * 64]; a1 = w4[wofs / 4 + (t * 2 + 1) * 64]; a8 = w8[wofs + t * 64];
-        }, B, qo, g, ab_lane);
-    };
-    // ... A operands straight from the caller's W_k[5][36][36] in memory: lane (n16, g) of tile t owns the nine consecutive floats
-    // W[16 t + n16][9 g .. 9 g + 8] (two 16-byte loads at 4-byte-aligned addresses and one float; rows >= 180: zeros). For the few
-    // envs that ENTER an option nobody in the block runs: its weights are not staged anywhere in this workgroup.
-    auto contract_g = [&](const float *Wk, const float (&B)[9], float (&qo)[NACT], int n16, int g, const float *ab_lane) {
-        struct __attribute__((packed, aligned(4))) F4U { float x, y, z, w; };
-        contract_with(std::integral_constant<int, EO_TG>{}, [&](int t, f4v &a0, f4v &a1, float &a8) {
-            const int row = 16 * t + n16;
-            a0 = (f4v){0.0f, 0.0f, 0.0f, 0.0f}; a1 = a0; a8 = 0.0f;
-            if (row < NACT * 36) {
-                const float *pw = Wk + row * 36 + 9 * g;
-                const F4U u0 = *reinterpret_cast<const F4U *>(pw), u1 = *reinterpret_cast<const F4U *>(pw + 4);
-                a0 = (f4v){u0.x, u0.y, u0.z, u0.w}; a1 = (f4v){u1.x, u1.y, u1.z, u1.w}; a8 = pw[8];
-            }
-        }, B, qo, g, ab_lane);
-    };
-    // W_k -> region W (+ dstf floats) in A-operand order (12 row tiles of the 180 x 36 matrix; entry (tile t, k-block kb,
-    // lane (n16, g)) = W[16 t + n16][9 g + kb], rows >= 180 zero; per tile and lane the k-blocks 0..3 and 4..7 form two
-    // float4 — one ds_read_b128 feeds four MFMAs — and k-block 8 sits apart), by `nth` threads with index `ht`: one thread
+    // W_k -> region W (+ dstf floats) in the A-operand layout (scg_eval.hpp) by `nth` threads with index `ht`: one thread
     // per DESTINATION float4, a 16-byte load at a 4-byte-aligned source address, one linear ds_write_b128.
     struct WStage { f4v v[3]; float tl[2]; };
     auto stage_w_load = [&](const float *Wk, int ht, int nth, WStage &st) {
@@ -433,22 +327,18 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         for (int i = 0; i < MAXI; ++i) {
             const int d = ht + i * nth;
             st.v[i] = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
-            if (d < N4) {
-                const int t2h = d >> 6, ln = d & 63, row = 16 * (t2h >> 1) + (ln & 15), col = 9 * (ln >> 4) + 4 * (t2h & 1);
-                if (row < NACT * 36) {
-                    const F4U w = *reinterpret_cast<const F4U *>(Wk + row * 36 + col);
-                    st.v[i] = (f4v){w.x, w.y, w.z, w.w};
-                }
+            int src;
+            if (d < N4 && w_a_src(d >> 7, 4 * ((d >> 6) & 1), d & 63, src)) {
+                const F4U w = *reinterpret_cast<const F4U *>(Wk + src);
+                st.v[i] = (f4v){w.x, w.y, w.z, w.w};
             }
         }
 #pragma unroll
         for (int i = 0; i < MAXT; ++i) {                                          // k-block 8 of every tile
             const int z = ht + i * nth;
             st.tl[i] = 0.0f;
-            if (z < N1) {
-                const int ln = z & 63, row = 16 * (z >> 6) + (ln & 15);
-                if (row < NACT * 36) st.tl[i] = Wk[row * 36 + 9 * (ln >> 4) + 8];
-            }
+            int src;
+            if (z < N1 && w_a_src(z >> 6, 8, z & 63, src)) st.tl[i] = Wk[src];
         }
     };
     auto stage_w_store = [&](int dstf, int ht, int nth, const WStage &st) {
@@ -579,18 +469,8 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             lds_arrive(&s_misc[M_C_PUBS], 64);
             if (valid) {
                 // act (SPEC §2, §4.3)
-                const uint64_t gid = (uint64_t)(A.env_base + e);
-                philox4x32_10((uint32_t)gid, (uint32_t)(A.t & 0xffffffffu), (uint32_t)(A.t >> 32), 0u,
-                              (uint32_t)(A.seed & 0xffffffffu), (uint32_t)(A.seed >> 32), u);
-                const bool explore = (float)(u[0] >> 8) * 0x1p-24f < A.epsilon;
-                const int a_rand = (int)__umulhi(u[1], 5u);
-                int a_greedy = 0;
-                float best = qc[0];
-#pragma unroll
-                for (int aa = 1; aa < NACT; ++aa) {
-                    if (qc[aa] > best) { best = qc[aa]; a_greedy = aa; }
-                }
-                a = explore ? a_rand : a_greedy;
+                env_draw((uint64_t)(A.env_base + e), A.t, A.seed, u);
+                a = act_spec(u, qc, A.epsilon);
                 s_a[i] = (uint8_t)a;
             } else {
                 s_a[i] = 0;
@@ -634,52 +514,29 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             if (valid) {
                 // bookkeeping (SPEC §1.4)
                 const int eps1 = ep0 + 1;
-                const bool timeout = !goal && eps1 >= A.max_ep;
-                const int dn = goal ? 1 : (timeout ? 2 : 0);
+                const int dn = episode_end(goal, eps1, A.max_ep);
                 float nx = sx, ny = sy, nvx = svx, nvy = svy;
-                if (dn) {
-                    const uint32_t si = __umulhi(u[2], (uint32_t)A.ms.n_starts);
-                    nx = A.starts[2 * si]; ny = A.starts[2 * si + 1]; nvx = 0.0f; nvy = 0.0f;
-                }
+                if (dn) restart_state(u[2], A.starts, A.ms.n_starts, nx, ny, nvx, nvy);
                 s_s[4 * BLOCK_ENVS + i] = nx; s_s[5 * BLOCK_ENVS + i] = ny;
                 s_s[6 * BLOCK_ENVS + i] = nvx; s_s[7 * BLOCK_ENVS + i] = nvy;
                 // options (SPEC §4.2), branch-free: membership bit masks of s' and s_next over all options
-                unsigned inA = 0, inB = 0, inS = 0;   // bit k: in_k(s'), in_k(s_next); gestating k only: in_k(s)
-                const unsigned known = A.enabled | A.gest;
+                unsigned inA, inB, inS = 0;           // bit k: in_k(s'), in_k(s_next); gestating k only: in_k(s)
+                member_masks(s_clf, A.n_vf, A.enabled | A.gest, sx, sy, nx, ny, inA, inB);
 #pragma unroll
                 for (int k = 1; k < MAX_VF; ++k) {
-                    if (k < A.n_vf && ((known >> k) & 1u)) {
-                        const float *w = s_clf + CLF_STRIDE * k;
-                        if (clf_z(w, sx, sy) > 0.0f) inA |= 1u << k;
-                        if (clf_z(w, nx, ny) > 0.0f) inB |= 1u << k;
-                        if (((A.gest >> k) & 1u) && clf_z(w, s_s[0 * BLOCK_ENVS + i], s_s[1 * BLOCK_ENVS + i]) > 0.0f) inS |= 1u << k;
-                    }
+                    if (k < A.n_vf && ((A.gest >> k) & 1u) && clf_z(s_clf + CLF_STRIDE * k, s_s[0 * BLOCK_ENVS + i], s_s[1 * BLOCK_ENVS + i]) > 0.0f)
+                        inS |= 1u << k;
                 }
                 bool keep = false;
                 float ro = 0.0f, co = 0.0f;
                 if (o >= 1) {
-                    const unsigned par2 = (A.parents >> (3 * (o & 7))) & 7u;       // SPEC §4.2: target of option o
-                    const bool succ = (par2 == 0) ? goal : ((inA >> par2) & 1u);
-                    const bool fail = !succ && !((inA >> o) & 1u);
-                    const bool otime = osteps + 1 >= A.max_opt;
-                    const bool term = (dn != 0) || succ || fail || otime;
+                    bool succ;
+                    keep = option_keep(A.parents, o, inA, goal, dn, osteps, A.max_opt, succ);
                     ro = rew + (succ ? A.r_succ : 0.0f);
-                    co = term ? 0.0f : A.gamma;
-                    keep = !term;
+                    co = keep ? A.gamma : 0.0f;
                 }
-                // smallest k with in_k(s_next) and s_next outside k's target region
-                unsigned tgtB = 0;                    // bit k: s_next already lies in option k's target region
-#pragma unroll
-                for (int k = 1; k < MAX_VF; ++k) {
-                    const unsigned par2 = (A.parents >> (3 * k)) & 7u;
-                    if (par2 != 0 && ((inB >> par2) & 1u)) tgtB |= 1u << k;
-                }
-                const unsigned sel = inB & ~tgtB & A.enabled;         // a gestating option is never selected
-                const int cand = keep ? o : (sel ? __builtin_ctz(sel) : 0);
-                // SPEC §4.2: an env that stayed out of option k (option_id = -k) and still has k as its candidate is offered k again only
-                // every reoffer_period-th step (staggered by env id; a new episode is a new offer) — in between it stays out without
-                // a new comparison, i.e. without the option's value function being evaluated for it
-                const int stay = (!keep && cand >= 1 && dn == 0 && o_in == -cand && (((uint32_t)A.t + (uint32_t)(A.env_base + e)) & A.reoffer_mask) != 0u) ? cand : 0;
+                const int cand = keep ? o : select_option(A.parents, inB, A.enabled);
+                const int stay = reoffer_stay(keep, cand, dn, o_in, A.t, (uint64_t)(A.env_base + e), A.reoffer_mask);
                 const int on = stay ? 0 : cand;
                 s_on[i] = (uint8_t)on;
                 s_gs[i] = (uint8_t)inS; s_ia[i] = (uint8_t)((inA & 0x3Eu) | (goal ? 1u : 0u) | ((!keep && on >= 1) ? IA_ENTERING : 0u));
@@ -699,7 +556,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 if (inS && A.gest_succ) {                             // SPEC §4.4: gestation successes (integer counts: order-free)
 #pragma unroll
                     for (int k = 1; k < MAX_VF; ++k) {
-                        const unsigned par2 = (A.parents >> (3 * k)) & 7u;
+                        const unsigned par2 = target_of(A.parents, k);
                         if (((inS >> k) & 1u) && ((par2 == 0) ? goal : (bool)((inA >> par2) & 1u))) atomicAdd(&A.gest_succ[k], 1);
                     }
                 }
@@ -917,8 +774,8 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             if (MODE == MODE_FUSED && kA != 0) {
                 if (ot == kA) { rk = s_ro[ft]; cont = s_co[ft]; }
                 else {                                    // as if the env ran option kA: no time-out, no selection
-                    const unsigned ia = s_ia[ft], par2 = (A.parents >> (3 * kA)) & 7u;
-                    const bool succ = (par2 == 0) ? (ia & 1u) : ((ia >> par2) & 1u);
+                    const unsigned ia = s_ia[ft];
+                    const bool succ = option_succ(A.parents, kA, ia, ia & 1u);
                     const bool fail = !succ && !((ia >> kA) & 1u);
                     rk = rk + (succ ? A.r_succ : 0.0f);
                     cont = (cont == 0.0f || succ || fail) ? 0.0f : A.gamma;
@@ -1084,19 +941,18 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             SCG_LANE_ROLES();                               // (per unit: nothing of it lives across the loop)
             {
                 const int j = min(bi, cnt - 1);
-                build_tables(du ? base + j : (int)s_elist[base + j], 1, cp, bcol, cdk, abq);
+                build_tables(s_z1 + ((du ? base + j : (int)s_elist[base + j]) * 2 + 1) * 4, cp, bcol, cdk, abq);      // (tables of s_next)
             }
             wave_lds_sync();
             float B[9];
-#pragma unroll
-            for (int kb = 0; kb < 9; ++kb) B[kb] = cdk[(9 * g + kb) * 16 + n16];
+            load_b(cdk, n16, g, B);
             const bool have = ocol_item < cnt;
             const int il = du ? base + min(ocol_item, cnt - 1) : (int)s_elist[base + min(ocol_item, cnt - 1)];
             if (kg >= 1) {                                   // an evaluation-only value function: only the next action's values are needed
                 float qo[NACT];
                 int n16o = n16, go = g;                      // (opaque copies: the twelve per-lane row addresses are loop-invariant and
                 asm volatile("" : "+v"(n16o), "+v"(go));     //  would otherwise be hoisted out of the unit loop and spilled)
-                contract_g(A.W + (size_t)kg * NACT * NF, B, qo, n16o, go, ab_lane);
+                contract_mem<EO_TG>(A.W + (size_t)kg * NACT * NF, B, qo, n16o, go, ab_lane);      // (its weights are not staged anywhere here)
                 if (out_lane && have) {
                     float4 *orec = A.outrec + (size_t)(e0 + il) * OREC;
                     orec[2] = make_float4(qo[0], qo[1], qo[2], qo[3]);
@@ -1113,7 +969,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             for (int v = 0; v < 2; ++v) {
                 if (!((fl >> v) & 1u)) continue;
                 float qo[NACT];
-                contract(v * W_FLOATS, B, qo, n16, g, w4, w8, ab_lane);
+                contract_lds<E_TG>(v * W_FLOATS, B, qo, g, w4, w8, ab_lane);
                 if (out_lane && have && ((s_ev[il] >> v) & 1)) {
                     const int kv = v ? kBp : kA;
                     if (MODE == MODE_FUSED) {             // into the env's result line; commit_row writes qcache
