@@ -132,6 +132,38 @@ int scg_rollout(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t 
                 const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
                 uint32_t flags, const scg_rollout_stats *stats, void *stream);
 
+/* ---- option trials (SPEC §9): each entry runs one option from a given state until that option terminates ----
+ * Entry i (0 <= i < n) runs option k = option[i] from s0 = (x, y, vx, vy)[i]: Q_k(s0, .) first (no physics, no RNG draw), then
+ * steps j = 0, 1, ... at t = t0 + j with RNG key (env_id_base + i, t), each bit for bit what scg_step(flags = 0) does for an env
+ * with option_id = k, opt_steps = j, ep_steps = j (act, physics, done, SPEC §4.2's termination of k; no selection, value gate,
+ * re-offer or reset), until the option terminates: after at most min(max_option_steps, max_episode_steps) steps. W and clf are
+ * frozen; parents, the gestation mask and the hyper-parameters are the ctx's; k counts as known when it is in enabled | gest.
+ * `out` is a HOST struct of DEVICE pointers, each [n]: outcome is required, any other member may be NULL (not written).
+ *   outcome  0 not run (k outside 1..n_options or not known: no other output of the entry is written), else the reason the
+ *            terminating step ended the option, first match wins: SUCCESS (target reached), EPISODE_END (done != 0),
+ *            LEFT_INITIATION (s' outside I_k), TIMEOUT (max_option_steps)
+ *   steps    steps taken (>= 1);  ret  sequential binary32 sum of r_o = reward + (succ ? r_option_success : 0)
+ *   disc_ret sum of gamma^j r_o (g = 1, d = 0; per step d = d + g r_o, g = g gamma, each product and sum rounded, no fma)
+ *   v0       max_a Q_k(s0, a) (SPEC §5's max order);  end_x/y/vx/vy  s' of the terminating step (after the physics)
+ * n is any value >= 1, unrelated to cfg.n_envs. Results do not depend on the launch geometry (SCG_ROLLOUT_EPW pins it, as for
+ * scg_rollout) or the block build. A trial writes nothing else: no env arrays, trace buffers, events, gestation counts, gradient
+ * buffers or W; an announced collect trigger and the prepared env order are left alone. No asynchronous failure bit is raised.
+ * SCG_ERR_INVALID: null ctx, array, out or out->outcome; n < 1; min(max_option_steps, max_episode_steps) > SCG_TRIAL_MAX_STEPS.
+ * SCG_ERR_STATE before scg_set_map. */
+typedef struct {
+    uint8_t *outcome;
+    int32_t *steps;
+    float *ret, *disc_ret, *v0, *end_x, *end_y, *end_vx, *end_vy;
+} scg_trial_out;
+#define SCG_TRIAL_SUCCESS 1u
+#define SCG_TRIAL_EPISODE_END 2u
+#define SCG_TRIAL_LEFT_INITIATION 3u
+#define SCG_TRIAL_TIMEOUT 4u
+#define SCG_TRIAL_MAX_STEPS SCG_ROLLOUT_MAX_STEPS
+int scg_option_trials(scg_ctx *ctx, int32_t n, const float *x, const float *y, const float *vx, const float *vy,
+                      const int32_t *option, const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0,
+                      const scg_trial_out *out, void *stream);
+
 /* Device pointers of the ctx-owned reduced gradient G[n_vf][5][1296] and counts n_k[n_vf] (int32)
  * left by the last scg_step(LEARN) — the buffers a multi-rank caller all-reduces (SPEC §5). */
 int scg_grad_buffers(scg_ctx *ctx, float **G, int32_t **n_k);

@@ -17,6 +17,9 @@ def __getattr__(name):
     if name in ("ScgContext", "EnvState", "fourier_scale_table"):
         from . import core
         return getattr(core, name)
+    if name == "TrialResult":
+        from .trials import TrialResult
+        return TrialResult
     if name == "EpisodeStats":
         from .evaluation import EpisodeStats
         return EpisodeStats

@@ -20,6 +20,11 @@ STEP_APPLY = 2
 ROLLOUT_BEGIN = 1          # include/scg_abi.h SCG_ROLLOUT_*
 ROLLOUT_ONE_EPISODE = 2
 ROLLOUT_MAX_STEPS = 1024
+TRIAL_SUCCESS = 1          # include/scg_abi.h SCG_TRIAL_*: the outcome of an option trial (0: not run)
+TRIAL_EPISODE_END = 2
+TRIAL_LEFT_INITIATION = 3
+TRIAL_TIMEOUT = 4
+TRIAL_MAX_STEPS = ROLLOUT_MAX_STEPS
 ABI_VERSION = 5            # include/scg_abi.h SCG_ABI_VERSION
 ASYNC_FIT_TIMEOUT = 0x1
 ASYNC_STEP_HANDOFF = 0x2
@@ -67,6 +72,21 @@ class RolloutStats(C.Structure):
     ]
 
 
+class TrialOut(C.Structure):
+    """scg_trial_out: device pointers of the per-entry outputs of SPEC §9 (outcome required, any other NULL = not written)."""
+    _fields_ = [
+        ("outcome", C.c_void_p),
+        ("steps", C.c_void_p),
+        ("ret", C.c_void_p),
+        ("disc_ret", C.c_void_p),
+        ("v0", C.c_void_p),
+        ("end_x", C.c_void_p),
+        ("end_y", C.c_void_p),
+        ("end_vx", C.c_void_p),
+        ("end_vy", C.c_void_p),
+    ]
+
+
 _P = C.c_void_p
 _SIGS = {
     "scg_abi_version": (C.c_int, []),
@@ -79,6 +99,7 @@ _SIGS = {
     "scg_set_map": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     "scg_step": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_uint32, _P]),
     "scg_rollout": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(RolloutStats), _P]),
+    "scg_option_trials": (C.c_int, [_P, C.c_int32] + [_P] * 7 + [C.c_uint32, C.c_uint64, C.POINTER(TrialOut), _P]),
     "scg_grad_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "scg_set_grad_buffers": (C.c_int, [_P, _P, _P]),
     "scg_apply_update": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -10,6 +10,7 @@ import ctypes as C
 import os
 from typing import List, Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -389,6 +390,107 @@ class SkillChainingAgent:
         out = stats.summary()
         return (out, stats.per_env()) if per_env else out
 
+    # ------------------------------------------------------------------ option trials (SPEC §9)
+    def _trial_context(self, seed: int, epsilon: float) -> ScgContext:
+        """The cached context trials run on (one, replaced when another seed is asked for): the training run's
+        hyper-parameters (epsilon aside), parents and gestation mask copied in; its own state, t and counters untouched."""
+        tc = self.__dict__.get("_trial_ctx")
+        if tc is None or tc.cfg.seed != seed:
+            if tc is not None:
+                tc.close()
+            tc = self._trial_ctx = ScgContext(1, self.n_options, self.map, device=self.ctx.device.index, seed=seed,
+                                              env_id_base=0, block_envs=self.ctx.block_envs)
+        c = self.ctx.cfg
+        tc.set_hparams(gamma=c.gamma, alpha=c.alpha, epsilon=float(epsilon), r_option_success=c.r_option_success,
+                       max_episode_steps=c.max_episode_steps, max_option_steps=c.max_option_steps,
+                       update_count_floor=c.update_count_floor, reoffer_period=c.reoffer_period)
+        tc.set_option_parents([int(v) for v in self.ctx.parents])
+        tc._call("scg_set_gestation", C.c_uint32(self.gest_mask), None)      # classifiers in use, no success counts kept
+        return tc
+
+    def option_trials(self, option, x, y, vx=None, vy=None, epsilon: float = 0.0, seed: Optional[int] = None):
+        """Run option `option` (an int, or one id per start state) from each start state (x, y, vx, vy; velocities default to
+        zero) until it terminates, with the current W, clf and enabled / gestating options, weights frozen (SPEC §9). Returns a
+        TrialResult (outcome, steps, ret, disc_ret, v0, end state; summary() per option). Runs on a separate cached context
+        at t0 = 0: W, state, t, the training context's env order, trace ring and counters are untouched."""
+        from .trials import TrialResult
+        dev = self.W.device
+        f32 = lambda v: torch.as_tensor(v, dtype=torch.float32).to(dev).contiguous().view(-1)
+        x, y = f32(x), f32(y)
+        n = x.numel()
+        vx = torch.zeros(n, dtype=torch.float32, device=dev) if vx is None else f32(vx)
+        vy = torch.zeros(n, dtype=torch.float32, device=dev) if vy is None else f32(vy)
+        opt = torch.full((n,), int(option), dtype=torch.int32, device=dev) if isinstance(option, int) \
+            else torch.as_tensor(option, dtype=torch.int32).to(dev).contiguous().view(-1)
+        tc = self._trial_context(int(self.ctx.cfg.seed) if seed is None else int(seed), epsilon)
+        res = TrialResult(n, opt, dev)
+        tc.option_trials(x, y, vx, vy, res.option, self.W.view(-1), self.clf.view(-1), self.enabled_mask, 0, res)
+        return res
+
+    def _start_states(self, states, n_states: int, seed: int):
+        """(x, y, vx, vy) as float32 device tensors: from `states` ((x, y) or (x, y, vx, vy)), else n_states map.sample_free
+        positions drawn with `seed`; missing velocities are zero."""
+        if states is None:
+            pos = self.map.sample_free(int(n_states), np.random.default_rng(seed))
+            states = (pos[:, 0], pos[:, 1])
+        dev = self.W.device
+        st = [torch.as_tensor(v, dtype=torch.float32).to(dev).contiguous().view(-1) for v in states]
+        if len(st) not in (2, 4) or any(v.numel() != st[0].numel() for v in st):
+            raise ValueError("states must be (x, y) or (x, y, vx, vy) of one length")
+        if len(st) == 2:
+            st += [torch.zeros_like(st[0]), torch.zeros_like(st[0])]
+        return st
+
+    def initiation_report(self, k: int, states=None, n_states: int = 8192, seed: int = 0) -> dict:
+        """Does initiation set k hold exactly the states from which option k reaches its target? Trials of option k (greedy)
+        from `states` ((x, y) or (x, y, vx, vy); default: n_states map.sample_free positions at rest, drawn with `seed`), each
+        start classified by in_k(s0). Returns tp / fp / fn / tn (predicted in I_k x trial succeeded), precision, recall,
+        success_in / success_out (success rate inside / outside the predicted set; NaN when empty), outcomes (count per
+        outcome) and, per entry, trials (the TrialResult), predicted (uint8) and states (x, y, vx, vy)."""
+        from .trials import OUTCOMES
+        if not (1 <= k <= self.n_options) or not ((self.enabled_mask | self.gest_mask) >> k) & 1:
+            raise ValueError(f"option {k} is not enabled or gestating")
+        xs, ys, vxs, vys = self._start_states(states, n_states, seed)
+        res = self.option_trials(k, xs, ys, vxs, vys)
+        pred = self._trial_ctx.classifier_predict(xs, ys, self.clf[k].contiguous())
+        p = pred.cpu().numpy().astype(bool)
+        oc = res.outcome.cpu().numpy()
+        s = oc == _lib.TRIAL_SUCCESS
+        tp, fp, fn, tn = (int(v) for v in (np.sum(p & s), np.sum(p & ~s), np.sum(~p & s), np.sum(~p & ~s)))
+        nan = float("nan")
+        return {
+            "option": int(k), "n": int(oc.size),
+            "tp": tp, "fp": fp, "fn": fn, "tn": tn,
+            "precision": tp / (tp + fp) if tp + fp else nan,
+            "recall": tp / (tp + fn) if tp + fn else nan,
+            "success_in": tp / (tp + fp) if tp + fp else nan,
+            "success_out": fn / (fn + tn) if fn + tn else nan,
+            "outcomes": {name: int(np.sum(oc == code)) for code, name in OUTCOMES.items()},
+            "trials": res, "predicted": pred,
+            "states": (xs, ys, vxs, vys),
+        }
+
+    def refine_initiation(self, k: int, states=None, n_states: int = 8192, iters: int = 400, lr: float = 3.0,
+                          l2: float = 1e-4, seed: int = 0):
+        """Refine initiation set k from option k's own executions (Konidaris & Barto 2009): trials from `states` (as in
+        initiation_report) label each start state positive iff the trial ended in SUCCESS; classifier k is then fitted,
+        starting from its current row, on the option's collected examples (if any are held) followed by the trial-labelled
+        states (scg_fit_initiation). Returns (report before, report after), the second from new trials with the refitted
+        classifier on the same states. Not available on a sharded agent."""
+        if self.group is not None:
+            raise ValueError("refine_initiation is not available on a sharded agent")
+        before = self.initiation_report(k, states, n_states, seed)
+        xs, ys, vxs, vys = before["states"]
+        lab = (before["trials"].outcome == _lib.TRIAL_SUCCESS).to(torch.uint8)
+        xy = torch.stack((xs, ys), 1)
+        if k in getattr(self, "_ex", {}):
+            ex_xy, ex_lab = self.examples(k)
+            xy, lab = torch.cat((ex_xy, xy)), torch.cat((ex_lab, lab))
+        self.options[k].initiation_classifier.fit(xy.contiguous(), lab.contiguous(), iters=iters, lr=lr, l2=l2, warm_start=True)
+        after = self.initiation_report(k, (xs, ys, vxs, vys))
+        return before, after
+
     def rollout(self, steps: int, learn: bool = True) -> None:
         for _ in range(steps):
             self.step_batch(learn)
+

@@ -181,6 +181,30 @@ class ScgContext:
                    C.c_uint32(enabled_mask), C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags),
                    None if cs is None else C.byref(cs), self._stream())
 
+    def option_trials(self, x: torch.Tensor, y: torch.Tensor, vx: torch.Tensor, vy: torch.Tensor, option: torch.Tensor,
+                      W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, out) -> None:
+        """SPEC §9: entry i runs option option[i] from (x, y, vx, vy)[i] until the option terminates, all in ONE launch, each
+        step bit for bit an acting step(learn=False) of an env running that option. `out` (TrialResult of the same length, on
+        this device) receives outcome, steps, ret, disc_ret, v0 and the end state; an entry whose option is not known
+        (enabled_mask | the gestation mask) is not run (outcome 0). W and clf are read only; nothing else is written."""
+        n = x.numel()
+        if n < 1:
+            raise ScgError("option_trials: need at least one start state")
+        x, y, vx, vy = self._chk4((x, y, vx, vy), n, "state")
+        self._chk(option, torch.int32, n, "option")
+        self._chk(W, torch.float32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
+        self._chk(clf, torch.float32, self.n_vf * CLF_STRIDE, "clf")
+        if out.n != n:
+            raise ScgError(f"option_trials: out holds {out.n} entries, the call has {n}")
+        self._chk(out.outcome, torch.uint8, n, "out.outcome"); self._chk(out.steps, torch.int32, n, "out.steps")
+        for f in out.FIELDS[2:]:
+            self._chk(getattr(out, f), torch.float32, n, "out." + f)
+        if not (0 <= int(t0) < 2 ** 64):
+            raise ScgError("option_trials: t0 must be a 64-bit unsigned step counter")
+        cs = out.c_struct()
+        self._call("scg_option_trials", C.c_int32(n), _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(option), _ptr(W), _ptr(clf),
+                   C.c_uint32(enabled_mask), C.c_uint64(int(t0)), C.byref(cs), self._stream())
+
     def invalidate_order(self) -> None:
         """Tell the library that option ids were written outside scg_step (reset, restore): re-sort next step."""
         self._step_args = self._step_keep = None

@@ -8,6 +8,8 @@
 //                  announced example trigger's row totals)
 // rollout_kernel (scg_rollout_kernel.hpp): K acting steps (SPEC §8) in one launch; a workgroup owns a fixed range of envs
 // for the whole launch and never talks to another one.
+// trial_kernel (scg_trial_kernel.hpp): option trials (SPEC §9), each from its start state to the option's termination, in one
+// launch with the rollout's geometry.
 // fit_kernel: SPEC §6 on 8 workgroups x 1024 chains per option behind tagged-word exchanges; a fit whose workgroups cannot run
 // together gives up after a wall-clock wait, leaves its row untouched and raises the ctx's asynchronous status word.
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
@@ -110,6 +112,7 @@ __device__ __forceinline__ bool in_set(const StepArgs &A, int k, float x, float 
 #include "scg_eval.hpp"
 #include "scg_step_kernel.hpp"
 #include "scg_rollout_kernel.hpp"
+#include "scg_trial_kernel.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // slabs -> G (SPEC §5 two-level block order), n_k, optional apply; the next step's env order rides along
@@ -1522,6 +1525,21 @@ int scg_step(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *opti
     return SCG_OK;
 }
 
+// envs per wave of a rollout_kernel / trial_kernel launch over n items: the largest of 2 .. 32 that still gives every CU a
+// workgroup (one 8-wave workgroup per CU: LDS); the results do not depend on it. SCG_ROLLOUT_EPW (2, 4, 8, 16 or 32) pins the
+// launch geometry instead: a hook for tests and measurements, which run every geometry at any count (the results are the same
+// by construction; the tests check that they are). false: SCG_ROLLOUT_EPW holds another value
+static bool rollout_epw(const scg_ctx *c, int n, int &epw) {
+    epw = 2;
+    while (epw < RO_MAX_EPW && (long long)n >= (long long)c->n_cu * RO_WAVES * epw * 2) epw *= 2;
+    if (const char *ov = getenv("SCG_ROLLOUT_EPW")) {
+        const int v = atoi(ov);
+        if (v < 2 || v > RO_MAX_EPW || (v & (v - 1))) return false;
+        epw = v;
+    }
+    return true;
+}
+
 int scg_rollout(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
                 int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
                 const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
@@ -1547,21 +1565,39 @@ int scg_rollout(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *o
     R.n_steps = n_steps;
     R.begin = (flags & SCG_ROLLOUT_BEGIN) ? 1u : 0u; R.one_episode = (flags & SCG_ROLLOUT_ONE_EPISODE) ? 1u : 0u;
     R.enabled = enabled_mask; R.t0 = t0;
-    // envs per wave: the largest of 2 .. 32 that still gives every CU a workgroup (one 8-wave workgroup per CU: LDS); the
-    // results do not depend on it
-    int epw = 2;
-    while (epw < RO_MAX_EPW && (long long)(c->cfg.n_envs) >= (long long)c->n_cu * RO_WAVES * epw * 2) epw *= 2;
-    // SCG_ROLLOUT_EPW (2, 4, 8, 16 or 32) pins the launch geometry instead: a hook for tests and measurements, which run every
-    // geometry at any env count (the results are the same by construction; the tests check that they are)
-    if (const char *ov = getenv("SCG_ROLLOUT_EPW")) {
-        const int v = atoi(ov);
-        if (v < 2 || v > RO_MAX_EPW || (v & (v - 1))) return fail(c, SCG_ERR_INVALID, "scg_rollout: SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
-        epw = v;
-    }
+    int epw;
+    if (!rollout_epw(c, c->cfg.n_envs, epw)) return fail(c, SCG_ERR_INVALID, "scg_rollout: SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
     R.epw = epw;
     const int grid = (c->cfg.n_envs + RO_WAVES * epw - 1) / (RO_WAVES * epw);
     c->order_valid = false;                               // the ids change under the step's prepared env order
     hipLaunchKernelGGL(rollout_kernel, dim3(grid), dim3(RO_THREADS), 0, reinterpret_cast<hipStream_t>(stream), R);
+    SCG_HIP(c, hipGetLastError());
+    return SCG_OK;
+}
+
+int scg_option_trials(scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,
+                      const int32_t *option, const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0,
+                      const scg_trial_out *out, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_option_trials: null ctx");
+    if (!c->have_map) return fail(c, SCG_ERR_STATE, "scg_option_trials: scg_set_map has not been called");
+    if (!x || !y || !vx || !vy || !option || !W || !clf || !out || !out->outcome)
+        return fail(c, SCG_ERR_INVALID, "scg_option_trials: null array argument (or out->outcome)");
+    if (n < 1) return fail(c, SCG_ERR_INVALID, "scg_option_trials: n must be >= 1");
+    if (std::min(c->cfg.max_option_steps, c->cfg.max_episode_steps) > SCG_TRIAL_MAX_STEPS)
+        return fail(c, SCG_ERR_INVALID, "scg_option_trials: min(max_option_steps, max_episode_steps) exceeds SCG_TRIAL_MAX_STEPS");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_option_trials");
+    TrialArgs T;
+    fill_shared(c, T);
+    T.n = n;
+    T.x = x; T.y = y; T.vx = vx; T.vy = vy; T.option = option; T.out = *out; T.W = W; T.clf = clf;
+    T.enabled = enabled_mask; T.t0 = t0;
+    T.gamma = c->cfg.gamma; T.r_succ = c->cfg.r_option_success;
+    int epw;
+    if (!rollout_epw(c, n, epw)) return fail(c, SCG_ERR_INVALID, "scg_option_trials: SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
+    T.epw = epw;
+    const int grid = (int)(((long long)n + RO_WAVES * epw - 1) / (RO_WAVES * epw));
+    hipLaunchKernelGGL(trial_kernel, dim3(grid), dim3(RO_THREADS), 0, reinterpret_cast<hipStream_t>(stream), T);
     SCG_HIP(c, hipGetLastError());
     return SCG_OK;
 }

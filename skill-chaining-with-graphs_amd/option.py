@@ -69,6 +69,10 @@ class Option:
         """Greedy primitive action per env (first maximum), uint8 [n]."""
         return self.q_values(state).argmax(0).to(torch.uint8)
 
+    def trial(self, x, y, vx=None, vy=None, epsilon: float = 0.0, seed: Optional[int] = None):
+        """Run this option from each start state until it terminates (SPEC §9): SkillChainingAgent.option_trials."""
+        return self.agent.option_trials(self.index, x, y, vx, vy, epsilon=epsilon, seed=seed)
+
     def in_initiation_set(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         if self.index == 0:
             return torch.ones_like(x, dtype=torch.uint8)
