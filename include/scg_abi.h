@@ -164,6 +164,42 @@ int scg_option_trials(scg_ctx *ctx, int32_t n, const float *x, const float *y, c
                       const int32_t *option, const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0,
                       const scg_trial_out *out, void *stream);
 
+/* ---- recorded rollouts and trials (SPEC §10): the per-step rows of a window of envs / entries ----
+ * scg_rollout_record and scg_option_trials_record are scg_rollout and scg_option_trials plus a record `rec` (HOST struct of
+ * DEVICE pointers). Recording changes nothing else: every output and counter of the launch is bit for bit the same as without.
+ * The record covers envs (rollout) or entries (trials) first .. first+n-1, rows rows each; every field is a [rows][n] array,
+ * element (j, r) at j * n + r with r = e - first. Row j is pseudo-step j of the launch:
+ *   x, y, vx, vy  s' (the state after the step's physics, before SPEC §1.4's reset; the begin row: the episode's start state)
+ *   action (255 on the begin row), reward, done (SPEC §1.4; 2 on the begin row)
+ *   vf        o, the value function that ran the step (the option id at entry, out-of-range and negative ids giving 0)
+ *   option_id the id the step writes (after the selection and the value gate)
+ *   term      0 while the option goes on or for o = 0, else the SCG_TRIAL_* code of the step (first match wins)
+ * len[r] (required) is the number of rows written, always a prefix: every pseudo-step, or with ONE_EPISODE up to and including
+ * the step that ended the episode, 0 for an env skipped at entry; for trials min(steps, rows), 0 for an entry not run. Rows at
+ * or beyond len are not written; any field but len may be NULL (not recorded). With BEGIN (or BEGIN_AT) row 0 is the begin
+ * pseudo-step and the steps fill rows 1 .. n_steps. Trials: vf = option_id = k on every row, and the last row's term is the
+ * outcome. rec = NULL is the call without a record.
+ *   SCG_ROLLOUT_BEGIN_AT  BEGIN with SPEC §1.4's reset replaced by the caller's state: (x, y, vx, vy)[e] as given (velocities
+ *                         kept, not validated), ep_steps = 0, no RNG draw for a start index; then §4.2's selection with o = 0, as
+ *                         BEGIN. scg_rollout_record only; not together with BEGIN.
+ * SCG_ERR_INVALID, beyond scg_rollout's / scg_option_trials' own: rec without len; rec->n < 1; rec->first < 0; first + n beyond
+ * N (cfg.n_envs, or the trials' n); rollout rows < n_steps + (BEGIN or BEGIN_AT); trial rows < 1; BEGIN together with BEGIN_AT. */
+typedef struct {
+    int32_t first, n, rows;                /* envs / entries first .. first+n-1, rows per env */
+    int32_t *len;                          /* [n], required */
+    float *x, *y, *vx, *vy, *reward;       /* [rows][n]; any may be NULL = not recorded */
+    uint8_t *action, *done, *vf, *term;
+    int8_t *option_id;
+} scg_record;
+#define SCG_ROLLOUT_BEGIN_AT 4u
+int scg_rollout_record(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                       int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                       const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                       uint32_t flags, const scg_rollout_stats *stats, const scg_record *rec, void *stream);
+int scg_option_trials_record(scg_ctx *ctx, int32_t n, const float *x, const float *y, const float *vx, const float *vy,
+                             const int32_t *option, const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0,
+                             const scg_trial_out *out, const scg_record *rec, void *stream);
+
 /* Device pointers of the ctx-owned reduced gradient G[n_vf][5][1296] and counts n_k[n_vf] (int32)
  * left by the last scg_step(LEARN) — the buffers a multi-rank caller all-reduces (SPEC §5). */
 int scg_grad_buffers(scg_ctx *ctx, float **G, int32_t **n_k);

@@ -19,6 +19,7 @@ STEP_LEARN = 1
 STEP_APPLY = 2
 ROLLOUT_BEGIN = 1          # include/scg_abi.h SCG_ROLLOUT_*
 ROLLOUT_ONE_EPISODE = 2
+ROLLOUT_BEGIN_AT = 4
 ROLLOUT_MAX_STEPS = 1024
 TRIAL_SUCCESS = 1          # include/scg_abi.h SCG_TRIAL_*: the outcome of an option trial (0: not run)
 TRIAL_EPISODE_END = 2
@@ -87,6 +88,27 @@ class TrialOut(C.Structure):
     ]
 
 
+class Record(C.Structure):
+    """scg_record: the per-step rows of SPEC §10 for envs / entries first .. first+n-1, rows rows each; device pointers of
+    [rows][n] arrays (len [n] required, any other NULL = not recorded)."""
+    _fields_ = [
+        ("first", C.c_int32),
+        ("n", C.c_int32),
+        ("rows", C.c_int32),
+        ("len", C.c_void_p),
+        ("x", C.c_void_p),
+        ("y", C.c_void_p),
+        ("vx", C.c_void_p),
+        ("vy", C.c_void_p),
+        ("reward", C.c_void_p),
+        ("action", C.c_void_p),
+        ("done", C.c_void_p),
+        ("vf", C.c_void_p),
+        ("term", C.c_void_p),
+        ("option_id", C.c_void_p),
+    ]
+
+
 _P = C.c_void_p
 _SIGS = {
     "scg_abi_version": (C.c_int, []),
@@ -100,6 +122,10 @@ _SIGS = {
     "scg_step": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_uint32, _P]),
     "scg_rollout": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(RolloutStats), _P]),
     "scg_option_trials": (C.c_int, [_P, C.c_int32] + [_P] * 7 + [C.c_uint32, C.c_uint64, C.POINTER(TrialOut), _P]),
+    "scg_rollout_record": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(RolloutStats),
+                                                         C.POINTER(Record), _P]),
+    "scg_option_trials_record": (C.c_int, [_P, C.c_int32] + [_P] * 7 + [C.c_uint32, C.c_uint64, C.POINTER(TrialOut),
+                                                                       C.POINTER(Record), _P]),
     "scg_grad_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "scg_set_grad_buffers": (C.c_int, [_P, _P, _P]),
     "scg_apply_update": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -349,7 +349,7 @@ class SkillChainingAgent:
         self.ctx.q_update(k, s, action, r, cont, s_next, self.W, apply=apply)
 
     def evaluate(self, n_episodes: int = 4096, epsilon: float = 0.0, seed: Optional[int] = None, steps_per_launch: int = 64,
-                 per_env: bool = False):
+                 per_env: bool = False, states=None):
         """How good the current policy is: one episode per env on `n_episodes` envs of a separate evaluation context (cached per
         n_episodes; another seed replaces the entry), acting with `epsilon` and the current W, clf and enabled options, weights
         frozen (SPEC §8). Returns
@@ -358,8 +358,41 @@ class SkillChainingAgent:
         One BEGIN | ONE_EPISODE launch, then ONE_EPISODE launches up to ceil(max_episode_steps / steps_per_launch) in all: every
         episode has ended by then (time limit), and nothing is read back before the end. The training run is left alone: W,
         state, t, the training context's env order, trace ring, gestation counts and peer exchange counter are untouched.
-        A sharded agent evaluates its own rank's policy copy on this rank only: there is no collective here."""
+        A sharded agent evaluates its own rank's policy copy on this rank only: there is no collective here.
+        With `states` ((x, y) or (x, y, vx, vy); velocities default to zero) episode i starts from state i instead of a drawn
+        start state (SPEC §10's BEGIN_AT), and n_episodes is the number of states."""
+        ectx, st, stats, launches = self._eval_setup(n_episodes, epsilon, seed, steps_per_launch, states)
+        spl = int(steps_per_launch)
+        for i in range(launches):
+            ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
+                         begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None))
+        out = stats.summary()
+        return (out, stats.per_env()) if per_env else out
+
+    def record_episodes(self, n_episodes: int = 256, states=None, epsilon: float = 0.0, seed: Optional[int] = None,
+                        steps_per_launch: int = 64):
+        """evaluate() with every step recorded (SPEC §10): the same launches on the same evaluation context, each with a record
+        of all envs that is appended to a Trajectory after the launch. Returns (Trajectory, the EpisodeStats summary, equal to
+        evaluate()'s with the same arguments). Row 0 of each env is its begin row. The training run is left alone."""
+        from .trajectory import Trajectory
+        ectx, st, stats, launches = self._eval_setup(n_episodes, epsilon, seed, steps_per_launch, states)
+        spl = int(steps_per_launch)
+        traj = Trajectory(ectx.n_envs, spl + 1, 0, ectx.device, n_vf=self.n_vf)
+        for i in range(launches):
+            ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
+                         begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None),
+                         record=traj)
+            traj.append()
+        return traj, stats.summary()
+
+    def _eval_setup(self, n_episodes, epsilon, seed, steps_per_launch, states):
+        """The evaluation context of evaluate() / record_episodes() for this episode count and seed, its hyper-parameters set
+        from training (epsilon aside), stats zeroed and, with `states`, the start states written into its env state. Returns
+        (context, EnvState, EpisodeStats, launches)."""
         from .evaluation import EpisodeStats
+        if states is not None:
+            states = self._start_states(states, 0, 0)
+            n_episodes = states[0].numel()
         n, spl = int(n_episodes), int(steps_per_launch)
         if n < 1:
             raise ValueError("n_episodes must be >= 1")
@@ -383,12 +416,10 @@ class SkillChainingAgent:
         ectx.set_option_parents([int(v) for v in self.ctx.parents])
         ectx._call("scg_set_gestation", C.c_uint32(self.gest_mask), None)      # classifiers in use, no success counts kept
         stats.zero_()
-        launches = -(-int(c.max_episode_steps) // spl)
-        for i in range(launches):
-            ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
-                         begin=(i == 0), one_episode=True)
-        out = stats.summary()
-        return (out, stats.per_env()) if per_env else out
+        if states is not None:
+            for dst, src in zip((st.x, st.y, st.vx, st.vy), states):
+                dst.copy_(src.to(dst.device))
+        return ectx, st, stats, -(-int(c.max_episode_steps) // spl)
 
     # ------------------------------------------------------------------ option trials (SPEC §9)
     def _trial_context(self, seed: int, epsilon: float) -> ScgContext:
@@ -408,11 +439,13 @@ class SkillChainingAgent:
         tc._call("scg_set_gestation", C.c_uint32(self.gest_mask), None)      # classifiers in use, no success counts kept
         return tc
 
-    def option_trials(self, option, x, y, vx=None, vy=None, epsilon: float = 0.0, seed: Optional[int] = None):
+    def option_trials(self, option, x, y, vx=None, vy=None, epsilon: float = 0.0, seed: Optional[int] = None,
+                      record: Optional[int] = None):
         """Run option `option` (an int, or one id per start state) from each start state (x, y, vx, vy; velocities default to
         zero) until it terminates, with the current W, clf and enabled / gestating options, weights frozen (SPEC §9). Returns a
         TrialResult (outcome, steps, ret, disc_ret, v0, end state; summary() per option). Runs on a separate cached context
-        at t0 = 0: W, state, t, the training context's env order, trace ring and counters are untouched."""
+        at t0 = 0: W, state, t, the training context's env order, trace ring and counters are untouched. With `record` (rows
+        per entry) every step is recorded (SPEC §10) into res.trajectory, a Trajectory over all entries."""
         from .trials import TrialResult
         dev = self.W.device
         f32 = lambda v: torch.as_tensor(v, dtype=torch.float32).to(dev).contiguous().view(-1)
@@ -424,7 +457,13 @@ class SkillChainingAgent:
             else torch.as_tensor(option, dtype=torch.int32).to(dev).contiguous().view(-1)
         tc = self._trial_context(int(self.ctx.cfg.seed) if seed is None else int(seed), epsilon)
         res = TrialResult(n, opt, dev)
-        tc.option_trials(x, y, vx, vy, res.option, self.W.view(-1), self.clf.view(-1), self.enabled_mask, 0, res)
+        traj = None
+        if record is not None:
+            from .trajectory import Trajectory
+            traj = Trajectory(n, int(record), 0, dev, n_vf=self.n_vf)
+        tc.option_trials(x, y, vx, vy, res.option, self.W.view(-1), self.clf.view(-1), self.enabled_mask, 0, res, record=traj)
+        if traj is not None:
+            res.trajectory = traj.append()
         return res
 
     def _start_states(self, states, n_states: int, seed: int):

@@ -149,16 +149,33 @@ class ScgContext:
         self._step_args = (key, ptrs)
         self._call("scg_step", *ptrs, C.c_uint32(enabled_mask), C.c_uint64(t), C.c_uint32(flags), self._stream())
 
+    def _chk_record(self, record, N: int, min_rows: int, what: str):
+        """The scg_record of a Trajectory whose window lies inside N items, on this device (SPEC §10)."""
+        if record.device != self.device:
+            raise ScgError(f"{what}: the record is on {record.device}, the context on {self.device}")
+        if record.first + record.n > N:
+            raise ScgError(f"{what}: record window {record.first}..{record.first + record.n - 1} outside {N} items")
+        if record.rows < min_rows:
+            raise ScgError(f"{what}: the record has {record.rows} rows, the launch needs {min_rows}")
+        self._chk(record.len, torch.int32, record.n, "record.len")
+        for f in record.fields:
+            self._chk(getattr(record, f), record.DTYPES[f], record.rows * record.n, "record." + f)
+        return record.c_struct()
+
     def rollout(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, n_steps: int,
-                stats=None, begin: bool = False, one_episode: bool = False) -> None:
+                stats=None, begin: bool = False, one_episode: bool = False, record=None, begin_at: bool = False) -> None:
         """SPEC §8: n_steps acting steps in ONE launch, bit for bit n_steps calls of step(learn=False) at t0 .. t0+n_steps-1
         (with `begin`: a new episode for every env at t0 first, the steps at t0+1 .. t0+n_steps). W is read, never written.
         `stats` (EpisodeStats of this context's n_vf and n_envs, on its device) receives the episode counters; `one_episode`
-        leaves envs alone whose `stats.finished` is set. The step's prepared env order is invalid afterwards."""
+        leaves envs alone whose `stats.finished` is set. The step's prepared env order is invalid afterwards.
+        SPEC §10: `record` (a Trajectory) receives the per-step rows of its window of envs; `begin_at` is `begin` from the
+        state in `st` (x, y, vx, vy as given) instead of a drawn start. Neither changes any other output."""
         self._chk_operands(st, W, clf)
         N = self.n_envs
         n_steps, t0 = int(n_steps), int(t0)
-        if not (0 <= n_steps <= _lib.ROLLOUT_MAX_STEPS) or (n_steps == 0 and not begin):
+        if begin and begin_at:
+            raise ScgError("rollout: begin and begin_at together")
+        if not (0 <= n_steps <= _lib.ROLLOUT_MAX_STEPS) or (n_steps == 0 and not (begin or begin_at)):
             raise ScgError(f"rollout: n_steps must be in [1, {_lib.ROLLOUT_MAX_STEPS}] ([0, ...] with begin=True)")
         if not (0 <= t0 < 2 ** 64):
             raise ScgError("rollout: t0 must be a 64-bit unsigned step counter")
@@ -176,17 +193,26 @@ class ScgContext:
         elif one_episode:
             raise ScgError("rollout: one_episode needs stats (its `finished` flags)")
         flags = (_lib.ROLLOUT_BEGIN if begin else 0) | (_lib.ROLLOUT_ONE_EPISODE if one_episode else 0)
+        if record is not None or begin_at:
+            rc = None if record is None else self._chk_record(record, N, n_steps + (1 if begin or begin_at else 0), "rollout")
+            flags |= _lib.ROLLOUT_BEGIN_AT if begin_at else 0
+            self._call("scg_rollout_record", _ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id),
+                       _ptr(st.opt_steps), _ptr(st.ep_steps), _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done),
+                       _ptr(W), _ptr(clf), C.c_uint32(enabled_mask), C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags),
+                       None if cs is None else C.byref(cs), None if rc is None else C.byref(rc), self._stream())
+            return
         self._call("scg_rollout", _ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id), _ptr(st.opt_steps),
                    _ptr(st.ep_steps), _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done), _ptr(W), _ptr(clf),
                    C.c_uint32(enabled_mask), C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags),
                    None if cs is None else C.byref(cs), self._stream())
 
     def option_trials(self, x: torch.Tensor, y: torch.Tensor, vx: torch.Tensor, vy: torch.Tensor, option: torch.Tensor,
-                      W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, out) -> None:
+                      W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, out, record=None) -> None:
         """SPEC §9: entry i runs option option[i] from (x, y, vx, vy)[i] until the option terminates, all in ONE launch, each
         step bit for bit an acting step(learn=False) of an env running that option. `out` (TrialResult of the same length, on
         this device) receives outcome, steps, ret, disc_ret, v0 and the end state; an entry whose option is not known
-        (enabled_mask | the gestation mask) is not run (outcome 0). W and clf are read only; nothing else is written."""
+        (enabled_mask | the gestation mask) is not run (outcome 0). W and clf are read only; nothing else is written.
+        `record` (a Trajectory over entries) receives the per-step rows of SPEC §10; it changes no other output."""
         n = x.numel()
         if n < 1:
             raise ScgError("option_trials: need at least one start state")
@@ -202,6 +228,11 @@ class ScgContext:
         if not (0 <= int(t0) < 2 ** 64):
             raise ScgError("option_trials: t0 must be a 64-bit unsigned step counter")
         cs = out.c_struct()
+        if record is not None:
+            rc = self._chk_record(record, n, 1, "option_trials")
+            self._call("scg_option_trials_record", C.c_int32(n), _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(option), _ptr(W),
+                       _ptr(clf), C.c_uint32(enabled_mask), C.c_uint64(int(t0)), C.byref(cs), C.byref(rc), self._stream())
+            return
         self._call("scg_option_trials", C.c_int32(n), _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(option), _ptr(W), _ptr(clf),
                    C.c_uint32(enabled_mask), C.c_uint64(int(t0)), C.byref(cs), self._stream())
 

@@ -77,6 +77,13 @@ __device__ __forceinline__ float2 pow_at(const float2 *pw, int d, int k) {   // 
     return k == 0 ? make_float2(1.0f, 0.0f) : v;
 }
 
+// a wave's LDS hand-off between its own lanes: release, wave barrier, acquire (no workgroup barrier)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ------------------------------------------------------------------ 64-lane butterfly (SPEC §6)
 // for m in (1,2,4,8,16,32): v_l = v_l + v_(l xor m). Stages 1..8 are DPP adds inside a 16-lane row
 // (after stages 1,2 a quad is uniform, so row_half_mirror == xor 4; after stage 4, row_mirror == xor 8);

@@ -10,6 +10,7 @@
 // for the whole launch and never talks to another one.
 // trial_kernel (scg_trial_kernel.hpp): option trials (SPEC §9), each from its start state to the option's termination, in one
 // launch with the rollout's geometry.
+// rollout_kernel<true> / trial_kernel<true> (scg_record_kernels.hip): the same two kernels with SPEC §10's per-step record.
 // fit_kernel: SPEC §6 on 8 workgroups x 1024 chains per option behind tagged-word exchanges; a fit whose workgroups cannot run
 // together gives up after a wall-clock wait, leaves its row untouched and raises the ctx's asynchronous status word.
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
@@ -89,12 +90,6 @@ struct StepArgs {
     MapScalars ms;
 };
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Workgroup barrier for LDS hand-offs only. __syncthreads() carries a workgroup-scope release fence, which on
 // gfx9 means s_waitcnt vmcnt(0): every barrier after a global store waits for the store to be acknowledged.
 // Nothing in td_kernel passes data between threads through global memory, so the barriers only need this wave's
@@ -113,6 +108,10 @@ __device__ __forceinline__ bool in_set(const StepArgs &A, int k, float x, float 
 #include "scg_step_kernel.hpp"
 #include "scg_rollout_kernel.hpp"
 #include "scg_trial_kernel.hpp"
+
+// the recording instantiations (SPEC §10), compiled and launched in scg_record_kernels.hip
+__attribute__((visibility("hidden"))) hipError_t launch_rollout_record(const RolloutRecArgs &A, int grid, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_trial_record(const TrialRecArgs &A, int grid, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // slabs -> G (SPEC §5 two-level block order), n_k, optional apply; the next step's env order rides along
@@ -1540,23 +1539,46 @@ static bool rollout_epw(const scg_ctx *c, int n, int &epw) {
     return true;
 }
 
-int scg_rollout(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
-                int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
-                const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
-                uint32_t flags, const scg_rollout_stats *stats, void *stream) {
-    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_rollout: null ctx");
-    if (!c->have_map) return fail(c, SCG_ERR_STATE, "scg_rollout: scg_set_map has not been called");
+// a record's window and rows against N items and at least min_rows rows (SPEC §10); the error text is `what`'s
+// an error of entry point `fn`: "fn: why"
+static int fail_in(scg_ctx *c, int code, const char *fn, const char *why) {
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: %s", fn, why);
+    return fail(c, code, msg);
+}
+
+static int check_record(scg_ctx *c, const char *fn, const scg_record *rec, int N, long long min_rows) {
+    const char *why = !rec->len ? "rec->len is required" : rec->n < 1 ? "rec->n must be >= 1"
+                    : rec->first < 0 || (long long)rec->first + rec->n > N ? "rec->first .. first+n-1 outside the envs / entries"
+                    : rec->rows < min_rows ? "rec->rows too small for the launch's pseudo-steps" : nullptr;
+    return why ? fail_in(c, SCG_ERR_INVALID, fn, why) : SCG_OK;
+}
+
+// scg_rollout, and scg_rollout_record (`fn` names the caller in error texts) with `rec` or `at` (BEGIN_AT, passed as BEGIN in
+// `flags`): the recording instantiation
+static int rollout_launch(const char *fn, scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                          int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                          const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                          uint32_t flags, const scg_rollout_stats *stats, const scg_record *rec, bool at, void *stream) {
+    if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
+    if (!c->have_map) return fail_in(c, SCG_ERR_STATE, fn, "scg_set_map has not been called");
     if (!x || !y || !vx || !vy || !option_id || !opt_steps || !ep_steps || !qcache || !action || !reward ||
         !done || !W || !clf)
-        return fail(c, SCG_ERR_INVALID, "scg_rollout: null array argument");
-    if (flags & ~(SCG_ROLLOUT_BEGIN | SCG_ROLLOUT_ONE_EPISODE)) return fail(c, SCG_ERR_INVALID, "scg_rollout: unknown flag");
+        return fail_in(c, SCG_ERR_INVALID, fn, "null array argument");
+    if (flags & ~(SCG_ROLLOUT_BEGIN | SCG_ROLLOUT_ONE_EPISODE)) return fail_in(c, SCG_ERR_INVALID, fn, "unknown flag");
     if (n_steps < 0 || n_steps > SCG_ROLLOUT_MAX_STEPS)
-        return fail(c, SCG_ERR_INVALID, "scg_rollout: n_steps out of range [0, SCG_ROLLOUT_MAX_STEPS]");
-    if (n_steps == 0 && !(flags & SCG_ROLLOUT_BEGIN)) return fail(c, SCG_ERR_INVALID, "scg_rollout: n_steps == 0 without SCG_ROLLOUT_BEGIN");
+        return fail_in(c, SCG_ERR_INVALID, fn, "n_steps out of range [0, SCG_ROLLOUT_MAX_STEPS]");
+    if (n_steps == 0 && !(flags & SCG_ROLLOUT_BEGIN))
+        return fail_in(c, SCG_ERR_INVALID, fn, "n_steps == 0 without SCG_ROLLOUT_BEGIN (or _BEGIN_AT)");
     if ((flags & SCG_ROLLOUT_ONE_EPISODE) && !(stats && stats->finished))
-        return fail(c, SCG_ERR_INVALID, "scg_rollout: SCG_ROLLOUT_ONE_EPISODE needs stats->finished");
+        return fail_in(c, SCG_ERR_INVALID, fn, "SCG_ROLLOUT_ONE_EPISODE needs stats->finished");
+    if (rec) {
+        const int rc = check_record(c, fn, rec, c->cfg.n_envs, (long long)n_steps + ((flags & SCG_ROLLOUT_BEGIN) ? 1 : 0));
+        if (rc != SCG_OK) return rc;
+    }
     SCG_CHECK_ASYNC(c);
-    SCG_ON_DEVICE(c, "scg_rollout");
+    DeviceGuard dev_guard_(c->cfg.device);
+    if (!dev_guard_.ok) return fail_in(c, SCG_ERR_HIP, fn, "cannot make the context's device current");
     RolloutArgs R;
     fill_shared(c, R);
     R.x = x; R.y = y; R.vx = vx; R.vy = vy; R.option_id = option_id; R.opt_steps = opt_steps; R.ep_steps = ep_steps;
@@ -1566,27 +1588,62 @@ int scg_rollout(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *o
     R.begin = (flags & SCG_ROLLOUT_BEGIN) ? 1u : 0u; R.one_episode = (flags & SCG_ROLLOUT_ONE_EPISODE) ? 1u : 0u;
     R.enabled = enabled_mask; R.t0 = t0;
     int epw;
-    if (!rollout_epw(c, c->cfg.n_envs, epw)) return fail(c, SCG_ERR_INVALID, "scg_rollout: SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
+    if (!rollout_epw(c, c->cfg.n_envs, epw)) return fail_in(c, SCG_ERR_INVALID, fn, "SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
     R.epw = epw;
     const int grid = (c->cfg.n_envs + RO_WAVES * epw - 1) / (RO_WAVES * epw);
     c->order_valid = false;                               // the ids change under the step's prepared env order
-    hipLaunchKernelGGL(rollout_kernel, dim3(grid), dim3(RO_THREADS), 0, reinterpret_cast<hipStream_t>(stream), R);
+    if (rec || at) {
+        RolloutRecArgs RR;
+        memset(&RR, 0, sizeof(RR));
+        static_cast<RolloutArgs &>(RR) = R;
+        if (rec) RR.rec = *rec;                           // else n = 0: nothing recorded
+        RR.begin_at = at ? 1u : 0u;
+        SCG_HIP(c, launch_rollout_record(RR, grid, reinterpret_cast<hipStream_t>(stream)));
+        return SCG_OK;
+    }
+    hipLaunchKernelGGL((rollout_kernel<false, RolloutArgs>), dim3(grid), dim3(RO_THREADS), 0, reinterpret_cast<hipStream_t>(stream), R);
     SCG_HIP(c, hipGetLastError());
     return SCG_OK;
 }
 
-int scg_option_trials(scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,
-                      const int32_t *option, const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0,
-                      const scg_trial_out *out, void *stream) {
-    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_option_trials: null ctx");
-    if (!c->have_map) return fail(c, SCG_ERR_STATE, "scg_option_trials: scg_set_map has not been called");
+int scg_rollout(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                uint32_t flags, const scg_rollout_stats *stats, void *stream) {
+    return rollout_launch("scg_rollout", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
+                          enabled_mask, t0, n_steps, flags, stats, nullptr, false, stream);
+}
+
+int scg_rollout_record(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                       int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                       const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                       uint32_t flags, const scg_rollout_stats *stats, const scg_record *rec, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_rollout_record: null ctx");
+    const bool at = (flags & SCG_ROLLOUT_BEGIN_AT) != 0;
+    if (at && (flags & SCG_ROLLOUT_BEGIN))
+        return fail(c, SCG_ERR_INVALID, "scg_rollout_record: SCG_ROLLOUT_BEGIN and SCG_ROLLOUT_BEGIN_AT together");
+    const uint32_t fl = at ? (flags & ~SCG_ROLLOUT_BEGIN_AT) | SCG_ROLLOUT_BEGIN : flags;
+    return rollout_launch("scg_rollout_record", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done,
+                          W, clf, enabled_mask, t0, n_steps, fl, stats, rec, at, stream);
+}
+
+static int trials_launch(const char *fn, scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,
+                         const int32_t *option, const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0,
+                         const scg_trial_out *out, const scg_record *rec, void *stream) {
+    if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
+    if (!c->have_map) return fail_in(c, SCG_ERR_STATE, fn, "scg_set_map has not been called");
     if (!x || !y || !vx || !vy || !option || !W || !clf || !out || !out->outcome)
-        return fail(c, SCG_ERR_INVALID, "scg_option_trials: null array argument (or out->outcome)");
-    if (n < 1) return fail(c, SCG_ERR_INVALID, "scg_option_trials: n must be >= 1");
+        return fail_in(c, SCG_ERR_INVALID, fn, "null array argument (or out->outcome)");
+    if (n < 1) return fail_in(c, SCG_ERR_INVALID, fn, "n must be >= 1");
     if (std::min(c->cfg.max_option_steps, c->cfg.max_episode_steps) > SCG_TRIAL_MAX_STEPS)
-        return fail(c, SCG_ERR_INVALID, "scg_option_trials: min(max_option_steps, max_episode_steps) exceeds SCG_TRIAL_MAX_STEPS");
+        return fail_in(c, SCG_ERR_INVALID, fn, "min(max_option_steps, max_episode_steps) exceeds SCG_TRIAL_MAX_STEPS");
+    if (rec) {
+        const int rc = check_record(c, fn, rec, n, 1);
+        if (rc != SCG_OK) return rc;
+    }
     SCG_CHECK_ASYNC(c);
-    SCG_ON_DEVICE(c, "scg_option_trials");
+    DeviceGuard dev_guard_(c->cfg.device);
+    if (!dev_guard_.ok) return fail_in(c, SCG_ERR_HIP, fn, "cannot make the context's device current");
     TrialArgs T;
     fill_shared(c, T);
     T.n = n;
@@ -1594,12 +1651,32 @@ int scg_option_trials(scg_ctx *c, int32_t n, const float *x, const float *y, con
     T.enabled = enabled_mask; T.t0 = t0;
     T.gamma = c->cfg.gamma; T.r_succ = c->cfg.r_option_success;
     int epw;
-    if (!rollout_epw(c, n, epw)) return fail(c, SCG_ERR_INVALID, "scg_option_trials: SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
+    if (!rollout_epw(c, n, epw)) return fail_in(c, SCG_ERR_INVALID, fn, "SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
     T.epw = epw;
     const int grid = (int)(((long long)n + RO_WAVES * epw - 1) / (RO_WAVES * epw));
-    hipLaunchKernelGGL(trial_kernel, dim3(grid), dim3(RO_THREADS), 0, reinterpret_cast<hipStream_t>(stream), T);
+    if (rec) {
+        TrialRecArgs TR;
+        memset(&TR, 0, sizeof(TR));
+        static_cast<TrialArgs &>(TR) = T;
+        TR.rec = *rec;
+        SCG_HIP(c, launch_trial_record(TR, grid, reinterpret_cast<hipStream_t>(stream)));
+        return SCG_OK;
+    }
+    hipLaunchKernelGGL((trial_kernel<false, TrialArgs>), dim3(grid), dim3(RO_THREADS), 0, reinterpret_cast<hipStream_t>(stream), T);
     SCG_HIP(c, hipGetLastError());
     return SCG_OK;
+}
+
+int scg_option_trials(scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,
+                      const int32_t *option, const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0,
+                      const scg_trial_out *out, void *stream) {
+    return trials_launch("scg_option_trials", c, n, x, y, vx, vy, option, W, clf, enabled_mask, t0, out, nullptr, stream);
+}
+
+int scg_option_trials_record(scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,
+                             const int32_t *option, const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0,
+                             const scg_trial_out *out, const scg_record *rec, void *stream) {
+    return trials_launch("scg_option_trials_record", c, n, x, y, vx, vy, option, W, clf, enabled_mask, t0, out, rec, stream);
 }
 
 int scg_invalidate_order(scg_ctx *c) {

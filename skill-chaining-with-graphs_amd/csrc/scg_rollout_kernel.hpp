@@ -45,6 +45,11 @@ struct RolloutArgs {
     uint32_t reoffer_mask;
     MapScalars ms;
 };
+// the recording instantiation's arguments (SPEC §10): RolloutArgs at offset 0, so the exit's re-read holds for both
+struct RolloutRecArgs : RolloutArgs {
+    scg_record rec;                // device pointers; n = 0: nothing recorded
+    uint32_t begin_at;             // BEGIN's reset replaced by the state given
+};
 
 // per-VF counters of one launch, six 16-bit fields in three words (a launch takes at most 1 + SCG_ROLLOUT_MAX_STEPS steps)
 struct Ctr16 {
@@ -63,7 +68,26 @@ struct Ctr16 {
 };
 static_assert(SCG_ROLLOUT_MAX_STEPS + 1 < 65536, "16-bit launch counters");
 
-__global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs A) {
+// the kernel arguments through an opaque copy of the argument pointer: the record's pointers are fetched at the store site this
+// way (as the exit fetches the outputs); kept live from the entry they would sit in scalar registers across the whole step loop
+template <typename Args>
+__device__ __forceinline__ const Args *kernel_args() {
+    const Args *K = (const Args *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(K));
+    return K;
+}
+// len of env e (0: skipped) when e lies in the record's window. The record is taken BY VALUE wherever it is read: through a
+// reference the compiler cannot tell the record's own stores from the kernel arguments and reloads every pointer after each
+// store, one memory round trip at a time
+__device__ __forceinline__ void record_len(const scg_record R, int e, bool mine, int len) {
+    const int r = e - R.first;
+    if (mine && r >= 0 && r < R.n) R.len[r] = len;
+}
+
+// <false, RolloutArgs>: scg_rollout's kernel. <true, RolloutRecArgs>: the same steps, plus SPEC §10's rows of the envs in the
+// record's window, and BEGIN_AT (scg_rollout_record)
+template <bool REC, typename Args>
+__global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
     __shared__ __attribute__((aligned(16))) float s_w0[W_FLOATS];                 // W_0 in A-operand order (stage_w_cold's layout)
     __shared__ __attribute__((aligned(16))) float s_edges[MAX_EDGES * 8];
     __shared__ __attribute__((aligned(16))) float s_wave[RO_WAVES][RO_WAVE_FLOATS];
@@ -100,8 +124,17 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs A
         if (A.st.len_sum) len_sum = A.st.len_sum[e];
     }
     const bool skip = !mine || (A.one_episode && finished);   // not stepped at all in this launch: nothing of it is written
-    if (!__syncthreads_or(!skip)) return;                     // (workgroup-uniform) every env of the workgroup is finished
+    if (!__syncthreads_or(!skip)) {                           // (workgroup-uniform) every env of the workgroup is finished
+        if constexpr (REC) record_len(kernel_args<RolloutRecArgs>()->rec, e, mine, 0);
+        return;
+    }
     bool alive = !skip;
+    int nrow = 0;                                             // REC: rows recorded
+    int rr = -1;                                              // REC: this env's column in the record, -1: outside its window
+    if constexpr (REC) {
+        const scg_record R = kernel_args<RolloutRecArgs>()->rec;
+        if (e - R.first >= 0 && e - R.first < R.n) rr = e - R.first;
+    }
 
     // ---- once per launch: W_0, the edge table and the classifiers to LDS
     for (int i = tid; i < W_FLOATS; i += RO_THREADS) {
@@ -148,13 +181,16 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs A
         int dn = 0;
         float nx = px, ny = py, nvx = pvx, nvy = pvy;
         bool keep = false, succ = false;
-        int cand = 0, on = 0, stay = 0;
+        int cand = 0, on = 0, stay = 0, term = 0;
         if (valid) {
             dn = is_begin ? 2 : episode_end(goal, eps1, A.max_ep);
-            if (dn) restart_state(u[2], A.starts, A.ms.n_starts, nx, ny, nvx, nvy);
+            if (dn && !(REC && is_begin && kernel_args<RolloutRecArgs>()->begin_at)) restart_state(u[2], A.starts, A.ms.n_starts, nx, ny, nvx, nvy);
             unsigned inA, inB;
             member_masks(s_clf, A.n_vf, known, px, py, nx, ny, inA, inB);
             if (!is_begin && o >= 1) keep = option_keep(A.parents, o, inA, goal, dn, osteps, A.max_opt, succ);
+            if (REC && !is_begin && o >= 1 && !keep)          // SPEC §9's outcome code, first match wins
+                term = succ ? (int)SCG_TRIAL_SUCCESS : dn ? (int)SCG_TRIAL_EPISODE_END
+                     : !((inA >> o) & 1u) ? (int)SCG_TRIAL_LEFT_INITIATION : (int)SCG_TRIAL_TIMEOUT;
             cand = keep ? o : select_option(A.parents, inB, A.enabled);
             stay = reoffer_stay(keep, cand, dn, is_begin ? 0 : oid, t, gid, A.reoffer_mask);
             on = stay ? 0 : cand;
@@ -262,12 +298,30 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs A
                 ep_ret = 0.0f;
                 finished = false;
             }
+            if constexpr (REC) {                                 // SPEC §10's row j of this env
+                if (rr >= 0) {
+                    const scg_record R = kernel_args<RolloutRecArgs>()->rec;  // by value: see record_len
+                    const size_t at = (size_t)j * R.n + rr;
+                    if (R.x) R.x[at] = is_begin ? sx : px;
+                    if (R.y) R.y[at] = is_begin ? sy : py;
+                    if (R.vx) R.vx[at] = is_begin ? svx : pvx;
+                    if (R.vy) R.vy[at] = is_begin ? svy : pvy;
+                    if (R.reward) R.reward[at] = rew;
+                    if (R.action) R.action[at] = is_begin ? (uint8_t)255 : (uint8_t)a;
+                    if (R.done) R.done[at] = (uint8_t)dn;
+                    if (R.vf) R.vf[at] = is_begin ? (uint8_t)0 : (uint8_t)o;
+                    if (R.term) R.term[at] = (uint8_t)term;
+                    if (R.option_id) R.option_id[at] = (int8_t)oid;
+                }
+                nrow += 1;
+            }
         }
     }
 
     // ---- exit: the stepped envs' results, once. The output pointers are fetched from the kernel arguments again here, through
     // an opaque copy of the argument pointer: otherwise the compiler keeps the 21 pointers it loaded at entry live in scalar
     // registers across the whole step loop, where they crowd the loop's own scalars out into spill slots
+    if constexpr (REC) record_len(kernel_args<RolloutRecArgs>()->rec, e, mine, nrow);     // (skipped: 0)
     if (skip) return;
     const RolloutArgs *K = (const RolloutArgs *)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(K));

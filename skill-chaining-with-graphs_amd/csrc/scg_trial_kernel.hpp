@@ -31,8 +31,14 @@ struct TrialArgs {
     uint32_t reoffer_mask;         // (set by fill_shared; a trial never re-offers)
     MapScalars ms;
 };
+struct TrialRecArgs : TrialArgs {  // the recording instantiation's arguments (SPEC §10)
+    scg_record rec;
+};
 
-__global__ __launch_bounds__(RO_THREADS) void trial_kernel(const TrialArgs A) {
+// <false, TrialArgs>: scg_option_trials' kernel. <true, TrialRecArgs>: the same trials plus SPEC §10's rows of the entries in the
+// record's window
+template <bool REC, typename Args>
+__global__ __launch_bounds__(RO_THREADS) void trial_kernel(const Args A) {
     __shared__ __attribute__((aligned(16))) float s_edges[MAX_EDGES * 8];
     __shared__ __attribute__((aligned(16))) float s_wave[RO_WAVES][RO_WAVE_FLOATS];
     __shared__ __attribute__((aligned(16))) float2 s_z1[RO_MAX_ENVS][4];          // Z_d^1 of each entry's current state
@@ -59,6 +65,7 @@ __global__ __launch_bounds__(RO_THREADS) void trial_kernel(const TrialArgs A) {
     const bool run = k != 0;
     if (!__syncthreads_or(run)) {                              // (workgroup-uniform) nothing to run here
         if (mine) A.out.outcome[i] = 0;
+        if constexpr (REC) record_len(kernel_args<TrialRecArgs>()->rec, i, mine, 0);
         return;
     }
     for (int q = tid; q < A.ms.n_edges * 8; q += RO_THREADS) s_edges[q] = A.edges[q];
@@ -87,6 +94,11 @@ __global__ __launch_bounds__(RO_THREADS) void trial_kernel(const TrialArgs A) {
     float v0 = 0.0f, ret = 0.0f, dret = 0.0f, gk = 1.0f;
     int steps = 0, outcome = 0;
     float *sw = s_wave[wave];
+    int rr = -1;                                               // REC: this entry's column in the record, -1: outside its window
+    if constexpr (REC) {
+        const scg_record R = kernel_args<TrialRecArgs>()->rec;
+        if (i - R.first >= 0 && i - R.first < R.n) rr = i - R.first;
+    }
     for (;;) {
         __syncthreads();
         // ------------------------------------------------------------ E
@@ -176,6 +188,22 @@ __global__ __launch_bounds__(RO_THREADS) void trial_kernel(const TrialArgs A) {
                         : !((inA >> k) & 1u) ? (int)SCG_TRIAL_LEFT_INITIATION : (int)SCG_TRIAL_TIMEOUT;
                 alive = false;
             }
+            if constexpr (REC) {                                 // SPEC §10's row steps - 1 of this entry
+                const scg_record R = kernel_args<TrialRecArgs>()->rec;        // by value: see record_len
+                if (rr >= 0 && steps <= R.rows) {
+                    const size_t at = (size_t)(steps - 1) * R.n + rr;
+                    if (R.x) R.x[at] = px;
+                    if (R.y) R.y[at] = py;
+                    if (R.vx) R.vx[at] = pvx;
+                    if (R.vy) R.vy[at] = pvy;
+                    if (R.reward) R.reward[at] = rew;
+                    if (R.action) R.action[at] = (uint8_t)a;
+                    if (R.done) R.done[at] = (uint8_t)dn;
+                    if (R.vf) R.vf[at] = (uint8_t)k;
+                    if (R.term) R.term[at] = (uint8_t)(keep ? 0 : outcome);
+                    if (R.option_id) R.option_id[at] = (int8_t)k;
+                }
+            }
         }
 #pragma unroll
         for (int kk = 1; kk < MAX_VF; ++kk) {
@@ -190,6 +218,10 @@ __global__ __launch_bounds__(RO_THREADS) void trial_kernel(const TrialArgs A) {
 
     // ---- exit: each output once. The pointers are fetched again through an opaque copy of the argument pointer, as in
     // rollout_kernel, so that the loop does not hold them in scalar registers
+    if constexpr (REC) {
+        const scg_record R = kernel_args<TrialRecArgs>()->rec;
+        record_len(R, i, mine, min(steps, R.rows));                                  // (not run: 0)
+    }
     if (!mine) return;
     const TrialArgs *K = (const TrialArgs *)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(K));

@@ -1,0 +1,151 @@
+"""Trajectory — the per-step rows of recorded rollouts and option trials (SPEC §10) and their host-side views."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ._lib import TRIAL_EPISODE_END, TRIAL_LEFT_INITIATION, TRIAL_SUCCESS, TRIAL_TIMEOUT, Record
+
+TERMS = {0: "", TRIAL_SUCCESS: "SUCCESS", TRIAL_EPISODE_END: "EPISODE_END", TRIAL_LEFT_INITIATION: "LEFT_INITIATION",
+         TRIAL_TIMEOUT: "TIMEOUT"}
+BEGIN_ACTION = 255         # the action of a begin row (SPEC §10)
+
+
+class Trajectory:
+    """Record buffers of SPEC §10 for envs (or trial entries) first .. first+n-1, `rows` rows per launch, plus the rows of the
+    launches appended so far, per env, on the host. Device side: `len` [n] int32 and one [rows][n] tensor per field, the
+    buffers one launch writes (`c_struct()`); `append()` copies a launch's rows (cut to len) behind the earlier ones."""
+
+    FIELDS = ("x", "y", "vx", "vy", "reward", "action", "done", "vf", "term", "option_id")
+    DTYPES = {"x": torch.float32, "y": torch.float32, "vx": torch.float32, "vy": torch.float32, "reward": torch.float32,
+              "action": torch.uint8, "done": torch.uint8, "vf": torch.uint8, "term": torch.uint8, "option_id": torch.int8}
+
+    def __init__(self, n: int, rows: int, first: int = 0, device="cpu", fields=FIELDS, n_vf=None):
+        self.first, self.n, self.rows = int(first), int(n), int(rows)
+        self.n_vf = None if n_vf is None else int(n_vf)   # value functions of the context (root + options), sizes summary()'s lists
+        if self.n < 1 or self.rows < 1 or self.first < 0:
+            raise ValueError("a record needs n >= 1, rows >= 1 and first >= 0")
+        dev = torch.device(device)
+        self.fields = tuple(fields)
+        if any(f not in self.DTYPES for f in self.fields):
+            raise ValueError(f"unknown record field in {self.fields}")
+        self.len = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        for f in self.FIELDS:
+            setattr(self, f, torch.zeros((self.rows, self.n), dtype=self.DTYPES[f], device=dev) if f in self.fields else None)
+        self._chunks = [[] for _ in range(self.n)]       # per env: one dict of numpy rows per appended launch
+
+    @property
+    def device(self) -> torch.device:
+        return self.len.device
+
+    def c_struct(self) -> Record:
+        """The scg_record of these buffers (device pointers; the tensors must stay alive while it is in use)."""
+        p = {f: C.c_void_p(getattr(self, f).data_ptr()) for f in self.fields}
+        return Record(first=self.first, n=self.n, rows=self.rows, len=C.c_void_p(self.len.data_ptr()), **p)
+
+    def append(self, launch=None) -> "Trajectory":
+        """Append one launch's rows: `launch` maps "len" ([n]) and the recorded fields ([rows][n]) to tensors or arrays;
+        default: this trajectory's own buffers, as the last launch left them. Each env's first len rows go behind its
+        earlier ones."""
+        if launch is None:
+            launch = {f: getattr(self, f) for f in ("len",) + self.fields}
+        host = {f: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for f, v in launch.items()}
+        ln = host["len"].astype(np.int64)
+        if ln.shape != (self.n,):
+            raise ValueError(f"len must hold {self.n} entries")
+        for r in range(self.n):
+            if ln[r] > 0:
+                self._chunks[r].append({f: host[f][: ln[r], r].copy() for f in self.fields})
+        return self
+
+    def per_env(self, i: int) -> dict:
+        """Env first + i's appended rows: one numpy array per recorded field, all of one length."""
+        ch = self._chunks[int(i)]
+        return {f: np.concatenate([c[f] for c in ch]) if ch else np.zeros(0, _np_dtype(self.DTYPES[f])) for f in self.fields}
+
+    def length(self, i: int) -> int:
+        return int(sum(len(c[self.fields[0]]) for c in self._chunks[int(i)]))
+
+    def segments(self, i: int) -> list:
+        """Runs of rows of env i under one value function: dicts with vf, start and end (row indices, inclusive), steps, the
+        last row's term and done (0 for a begin row). A run also ends after a row whose option ended (term != 0) and after an episode's last
+        step (done != 0 on a row that is not a begin row). Runs under the root are kept; a declined offer shows as root
+        rows with option_id < 0. Needs the vf, term, done and action fields."""
+        e = self.per_env(i)
+        vf, term, done, act = e["vf"], e["term"], e["done"], e["action"]
+        out, start = [], 0
+        for j in range(len(vf)):
+            last = (j + 1 == len(vf) or vf[j + 1] != vf[j] or term[j] != 0
+                    or (done[j] != 0 and act[j] != BEGIN_ACTION))
+            if last:
+                out.append({"vf": int(vf[j]), "start": start, "end": j, "steps": j - start + 1, "term": int(term[j]),
+                            "done": int(done[j]) if act[j] != BEGIN_ACTION else 0})
+                start = j + 1
+        return out
+
+    def describe(self, i: int) -> str:
+        """One line per env: its segments in order, e.g. `root×12 → 3×40 SUCCESS → 1×9 EPISODE_END(goal)`; the begin row
+        counts with the root segment it opens."""
+        parts = []
+        for s in self.segments(i):
+            name = "root" if s["vf"] == 0 else str(s["vf"])
+            txt = f"{name}×{s['steps']}"
+            if s["term"]:
+                txt += " " + TERMS[s["term"]]
+            if s["done"] and not s["term"]:
+                txt += " EPISODE_END"
+            if s["done"] == 1:
+                txt += "(goal)"
+            parts.append(txt)
+        return " → ".join(parts)
+
+    def summary(self) -> dict:
+        """Over all envs, on the host in float64: per value function k (index 0 = the root) the number of segments, their mean
+        length in steps (begin rows not counted; NaN without a segment) and the histogram of their terminating term (index =
+        code), with one entry per value function of the context (n_vf given at construction; else up to the largest vf seen);
+        declined_rows: rows with option_id < 0, i.e. steps that end outside an option whose initiation set holds the next state, its
+        offer declined by the value gate or not re-offered yet (a declined offer stays negative over several rows, so
+        this is not evaluate()'s count of value-gate declines); episodes (steps with done != 0), goals and goal_rate."""
+        seen = 1 + max([int(s["vf"]) for i in range(self.n) for s in self.segments(i)] + [0])
+        n_vf = seen if self.n_vf is None else max(self.n_vf, seen)
+        seg = np.zeros(n_vf, np.int64)
+        steps = np.zeros(n_vf, np.float64)
+        hist = np.zeros((n_vf, len(TERMS)), np.int64)
+        episodes = goals = declined_rows = 0
+        for i in range(self.n):
+            e = self.per_env(i)
+            real = e["action"] != BEGIN_ACTION
+            for s in self.segments(i):
+                k = s["vf"]
+                seg[k] += 1
+                steps[k] += float(np.sum(real[s["start"]: s["end"] + 1]))
+                hist[k, s["term"]] += 1
+            episodes += int(np.sum((e["done"] != 0) & real))
+            goals += int(np.sum((e["done"] == 1) & real))
+            if "option_id" in e:
+                declined_rows += int(np.sum(e["option_id"] < 0))
+        nan = float("nan")
+        return {
+            "segments": [int(v) for v in seg],
+            "mean_steps": [float(steps[k] / seg[k]) if seg[k] else nan for k in range(n_vf)],
+            "term_hist": [[int(v) for v in hist[k]] for k in range(n_vf)],
+            "declined_rows": declined_rows,
+            "episodes": episodes,
+            "goals": goals,
+            "goal_rate": goals / episodes if episodes else nan,
+        }
+
+    def to_numpy(self) -> dict:
+        """Every env's rows flattened for saving: `offsets` [n + 1] into the concatenated fields, plus `first`."""
+        per = [self.per_env(i) for i in range(self.n)]
+        off = np.zeros(self.n + 1, np.int64)
+        off[1:] = np.cumsum([len(p[self.fields[0]]) for p in per])
+        out = {f: np.concatenate([p[f] for p in per]) for f in self.fields}
+        out["offsets"], out["first"] = off, np.int64(self.first)
+        return out
+
+
+def _np_dtype(dt: torch.dtype):
+    return torch.empty(0, dtype=dt).numpy().dtype

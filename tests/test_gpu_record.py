@@ -1,0 +1,542 @@
+"""SPEC §10 recorded rollouts and trials on the GPU: every row equals the step loop (and a numpy model of the option ends),
+recording changes no other output on any launch geometry or block build and writes nothing outside its window, ONE_EPISODE's
+lengths, BEGIN_AT, recorded trials, the agent's record_episodes / evaluate(states=...) / option_trials(record=...), and the
+refusals of the C-ABI."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import sc_oracle
+import skill_chaining_with_graphs_amd as scg
+from skill_chaining_with_graphs_amd import _lib
+from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
+from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
+from skill_chaining_with_graphs_amd.trajectory import Trajectory
+from skill_chaining_with_graphs_amd.trials import TrialResult
+from gpu_util import dev, make_pair, state_to_device
+from util import HP, chain_classifiers, dense_map, hub_map, random_states, random_weights
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done")
+STATS = EpisodeStats.FIELDS
+GUARD = 64
+
+
+def _map(name):
+    return dense_map() if name == "dense" else hub_map() if name == "hub" else scg.load_map(name)
+
+
+def _setup(m, n, n_opt, block=None, parents=None, gest=0, seed=3, **hp):
+    kw = dict(HP)
+    kw.update(hp)
+    ctx = ScgContext(n, n_opt, m, device=0, block_envs=block, seed=seed, **kw)
+    if parents is not None:
+        ctx.set_option_parents(parents)
+    if gest:
+        ctx.set_gestation(gest)
+    clf = dev(chain_classifiers(m, n_opt)).view(-1)
+    W = dev(random_weights(n_opt + 1, seed, std=0.1)).view(-1)
+    return ctx, W, clf
+
+
+def _state(ctx, m, n, n_opt, seed):
+    rng = np.random.default_rng(seed)
+    st = EnvState(n, ctx.device, m)
+    x, y, vx, vy = random_states(m, n, seed, vmax=1.5)
+    st.x.copy_(dev(x)); st.y.copy_(dev(y)); st.vx.copy_(dev(vx)); st.vy.copy_(dev(vy))
+    st.option_id.copy_(dev(rng.integers(-n_opt - 1, n_opt + 2, n).astype(np.int32)))
+    st.opt_steps.copy_(dev(rng.integers(0, 20, n).astype(np.int32)))
+    st.ep_steps.copy_(dev(rng.integers(0, ctx.cfg.max_episode_steps, n).astype(np.int32)))
+    st.qcache.copy_(dev(rng.standard_normal((5, n)).astype(np.float32)))
+    return st
+
+
+def _clone(st):
+    c = object.__new__(EnvState)
+    c.n = st.n
+    for f in FIELDS:
+        setattr(c, f, getattr(st, f).clone())
+    return c
+
+
+def _bits(a):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return np.ascontiguousarray(a).view(np.uint8)
+
+
+def _assert_same(a, b, fields, msg):
+    for f in fields:
+        assert np.array_equal(_bits(getattr(a, f)), _bits(getattr(b, f))), f"{msg}: {f} differs"
+
+
+def _guarded(n, rows, first=0, sentinel=77):
+    """A Trajectory whose buffers sit inside larger ones filled with a sentinel (GUARD elements on each side)."""
+    tr = Trajectory(n, rows, first, "cuda:0")
+    tr.big = {}
+    for f in ("len",) + tr.fields:
+        dt = torch.int32 if f == "len" else Trajectory.DTYPES[f]
+        size = n if f == "len" else rows * n
+        big = torch.full((size + 2 * GUARD,), sentinel, dtype=dt, device="cuda:0")
+        tr.big[f] = big
+        view = big[GUARD: GUARD + size]
+        setattr(tr, f, view if f == "len" else view.view(rows, n))
+    return tr
+
+
+def _assert_guarded(tr, sentinel=77):
+    """Nothing written outside [rows][n] or at / beyond len."""
+    ln = tr.len.cpu().numpy()
+    for f, big in tr.big.items():
+        h = big.cpu().numpy()
+        s = np.array(sentinel).astype(h.dtype)
+        assert (h[:GUARD] == s).all() and (h[-GUARD:] == s).all(), f"{f}: written outside the record"
+        if f == "len":
+            continue
+        body = h[GUARD:-GUARD].reshape(tr.rows, tr.n)
+        beyond = np.arange(tr.rows)[:, None] >= ln[None, :]
+        assert (body[beyond] == s).all(), f"{f}: a row at or beyond len was written"
+
+
+CASES = [
+    # map, n, options, enabled, gestating, parents, reoffer, epsilon, env_id_base, block
+    ("pinball_simple", 4096, 3, 0b1010, 0b0100, None, 4, 0.1, 0, None),
+    ("pinball_simple", 1000, 3, 0b1110, 0, [0, 0, 1, 1], 1, 0.0, 12345, 64),
+    ("pinball_simple", 257, 3, 0b1110, 0, [0, 0, 1, 2], 8, 0.1, 7, 128),
+    ("dense", 1000, 2, 0b110, 0, None, 4, 0.1, 0, 256),
+    ("hub", 257, 2, 0b110, 0, None, 4, 0.0, 3, None),
+    ("pinball_simple", 1000, 5, 0b111110, 0, None, 4, 0.1, 0, None),
+    ("pinball_simple", 300, 0, 0, 0, None, 4, 0.1, 0, None),
+]
+
+
+def _term_model(ctx, clf, known, parents, sp, goal, done, o, osteps):
+    """SPEC §4.2 / §9 on the host: the term of a step of value function o (numpy arrays over envs) into s' = sp."""
+    n_vf = ctx.n_vf
+    W8 = clf.view(n_vf, -1)
+    inA = np.zeros(len(o), np.int64)
+    for k in range(1, n_vf):
+        if (known >> k) & 1:
+            inA |= ctx.classifier_predict(sp[0], sp[1], W8[k].contiguous()).cpu().numpy().astype(np.int64) << k
+    p = np.asarray(parents, np.int64)[np.clip(o, 0, n_vf - 1)]
+    succ = np.where(p == 0, goal != 0, (inA >> p) & 1 == 1)
+    fail = ~succ & ((inA >> o) & 1 == 0)
+    otime = osteps + 1 >= ctx.cfg.max_option_steps
+    keep = ~((done != 0) | succ | fail | otime)
+    term = np.where(succ, 1, np.where(done != 0, 2, np.where(fail, 3, 4)))
+    term = np.where((o >= 1) & ~keep, term, 0)
+    return term, keep
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0]}-{c[1]}-o{c[2]}-b{c[9]}")
+def test_rows_equal_step_loop(case):
+    name, n, n_opt, mask, gest, parents, reoffer, eps, base, block = case
+    m = _map(name)
+    ctx, W, clf = _setup(m, n, n_opt, block, parents, gest, reoffer_period=reoffer, epsilon=eps, env_id_base=base)
+    st = _state(ctx, m, n, n_opt, seed=n + n_opt)
+    twin = _clone(st)
+    K, t0 = 24, 1000
+    tr = Trajectory(n, K, 0, ctx.device)
+    ctx.rollout(st, W, clf, mask, t0, K, record=tr)
+    known, par = mask | gest, [int(v) for v in ctx.parents]
+    rows = {f: getattr(tr, f).cpu().numpy() for f in tr.fields}
+    assert np.array_equal(tr.len.cpu().numpy(), np.full(n, K, np.int32))
+    ends = 0
+    for j, t in enumerate(range(t0, t0 + K)):
+        s_before = [getattr(twin, f).clone() for f in ("x", "y", "vx", "vy")]
+        oid = twin.option_id.cpu().numpy()
+        osteps = twin.opt_steps.cpu().numpy().astype(np.int64)
+        o = np.where((oid >= 1) & (oid < ctx.n_vf), oid, 0).astype(np.int64)
+        ctx.step(twin, W, clf, mask, t, learn=False)
+        act = twin.action.clone()
+        _, goal = ctx.pinball_step(s_before, act)          # s' of step j, before the reset
+        done = twin.done.cpu().numpy()
+        ends += int((done != 0).sum())
+        for f, want in (("action", act), ("reward", twin.reward), ("done", twin.done), ("option_id", twin.option_id)):
+            got = rows[f][j]
+            want = want.cpu().numpy().astype(got.dtype)
+            assert np.array_equal(_bits(got), _bits(want)), f"row {j}: {f}"
+        for f, want in zip(("x", "y", "vx", "vy"), s_before):
+            assert np.array_equal(_bits(rows[f][j]), _bits(want)), f"row {j}: {f} is not s'"
+        assert np.array_equal(rows["vf"][j], o.astype(np.uint8)), f"row {j}: vf"
+        term, keep = _term_model(ctx, clf, known, par, s_before, goal.cpu().numpy(), done, o, osteps)
+        assert np.array_equal(rows["term"][j], term.astype(np.uint8)), f"row {j}: term"
+        on = o >= 1
+        assert np.array_equal(rows["term"][j][on] == 0, keep[on])
+    torch.cuda.synchronize()
+    _assert_same(st, twin, FIELDS, "recorded rollout vs step loop")
+    assert ends > 0, "the case ends no episode"
+    if n_opt:
+        assert len(set(rows["term"].ravel().tolist())) >= 3, "the case sees too few option ends"
+
+
+def test_rows_equal_oracle_step_loop():
+    n, n_opt, mask = 257, 2, 0b110
+    ctx, orc, m = make_pair("pinball_simple", n, n_options=n_opt, seed=9, enabled_mask=mask)
+    clf = chain_classifiers(m, n_opt)
+    W = random_weights(n_opt + 1, 4, std=0.1)
+    st_o = sc_oracle.new_state(n, m)
+    rng = np.random.default_rng(5)
+    st_o["x"][:], st_o["y"][:], st_o["vx"][:], st_o["vy"][:] = random_states(m, n, 5, vmax=1.5)
+    st_o["option_id"][:] = rng.integers(-n_opt, n_opt + 1, n)
+    st_o["ep_steps"][:] = rng.integers(0, HP["max_episode_steps"], n)
+    st_o["qcache"][:] = rng.standard_normal((5, n)).astype(np.float32)
+    st_d = state_to_device(st_o, ctx)
+    K, t0 = 12, 77
+    tr = Trajectory(n, K, 0, ctx.device)
+    ctx.rollout(st_d, dev(W).view(-1), dev(clf).view(-1), mask, t0, K, record=tr)
+    for j, t in enumerate(range(t0, t0 + K)):
+        orc.step(st_o, W, clf, t)
+        for f in ("action", "reward", "done", "option_id"):
+            got = getattr(tr, f)[j].cpu().numpy()
+            assert np.array_equal(_bits(got), _bits(st_o[f].astype(got.dtype))), f"row {j}: {f} vs oracle"
+        alive = st_o["done"] == 0                          # s' is the oracle's state where no reset followed
+        for f in ("x", "y", "vx", "vy"):
+            assert np.array_equal(_bits(getattr(tr, f)[j].cpu().numpy()[alive]), _bits(st_o[f][alive])), f"row {j}: {f}"
+
+
+def _run(ctx, st, W, clf, mask, t0, K, stats, rec=None, **kw):
+    ctx.rollout(st, W, clf, mask, t0, K, stats, record=rec, **kw)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("block", [64, 128, 256])
+def test_recording_is_invisible(block, monkeypatch):
+    """With and without a record (full, at a workgroup edge, one env, the tail), every output and counter is bit-identical
+    on every launch geometry, and nothing is written outside the record's window or at / beyond len."""
+    m = scg.load_map("pinball_simple")
+    n, n_opt, mask, gest = 1000, 3, 0b1010, 0b0100
+    ctx, W, clf = _setup(m, n, n_opt, block, [0, 0, 1, 1], gest, reoffer_period=4, epsilon=0.1, env_id_base=17)
+    st0 = _state(ctx, m, n, n_opt, seed=41)
+    K = 40
+    epws = (2, 4, 8, 16, 32) if block == 256 else (8,)
+    for epw in epws:
+        monkeypatch.setenv("SCG_ROLLOUT_EPW", str(epw))
+        for flags in (dict(begin=True, one_episode=True), dict()):
+            ref_st, ref_stats = _clone(st0), EpisodeStats(ctx.n_vf, n, ctx.device)
+            _run(ctx, ref_st, W, clf, mask, 7, K, ref_stats, **flags)
+            rows = K + (1 if flags else 0)
+            for first, cnt in ((0, n), (8 * epw, 37), (5, 1), (n - 19, 19)):
+                s, stats = _clone(st0), EpisodeStats(ctx.n_vf, n, ctx.device)
+                tr = _guarded(cnt, rows, first)
+                _run(ctx, s, W, clf, mask, 7, K, stats, tr, **flags)
+                _assert_same(s, ref_st, FIELDS, f"epw {epw} {flags} window {first}+{cnt}")
+                _assert_same(stats, ref_stats, STATS, f"epw {epw} {flags} window {first}+{cnt} stats")
+                _assert_guarded(tr)
+                ln = tr.len.cpu().numpy()
+                if flags:
+                    assert ln.min() >= 1 and ln.max() <= rows
+                else:
+                    assert (ln == rows).all()
+
+
+def test_one_episode_lengths_and_append():
+    """ONE_EPISODE: len = the steps each env took (its vf_steps delta) plus the begin row, 0 for a skipped env; appended over
+    several launches, each env's rows give the counters' episode length, return (sequential binary32 sum) and goal."""
+    m = scg.load_map("pinball_simple")
+    n, n_opt, mask = 3000, 3, 0b1110
+    ctx, W, clf = _setup(m, n, n_opt, None, None, 0, epsilon=0.1, max_episode_steps=90)
+    st = _state(ctx, m, n, n_opt, seed=8)
+    stats = EpisodeStats(ctx.n_vf, n, ctx.device)
+    spl = 32
+    tr = Trajectory(n, spl + 1, 0, ctx.device)
+    launches = -(-90 // spl)
+    for i in range(launches):
+        before = stats.vf_steps.sum(0).clone()
+        fin = stats.finished.clone()
+        ctx.rollout(st, W, clf, mask, 0 if i == 0 else 1 + i * spl, spl, stats, begin=(i == 0), one_episode=True,
+                    record=tr)
+        delta = (stats.vf_steps.sum(0) - before).cpu().numpy()
+        ln = tr.len.cpu().numpy()
+        assert np.array_equal(ln, delta + (1 if i == 0 else 0)), f"launch {i}: len"
+        if i > 0:
+            assert (ln[fin.cpu().numpy() != 0] == 0).all(), "a finished env got rows"
+        tr.append()
+    assert int(stats.episodes.sum()) == n
+    lens, goals = stats.len_sum.cpu().numpy(), stats.goals.cpu().numpy()
+    ret = stats.ret_sum.cpu().numpy()
+    for i in range(n):
+        e = tr.per_env(i)
+        real = e["action"] != 255
+        assert e["action"][0] == 255 and real[1:].all()
+        assert int(real.sum()) == lens[i]
+        r = np.float32(0.0)
+        for v in e["reward"][real]:
+            r = np.float32(r + v)
+        assert float(r) == ret[i], f"env {i}: return"
+        assert int(e["done"][-1] == 1) == goals[i] and e["done"][-1] != 0
+
+
+def test_begin_at_drawn_starts_equals_begin():
+    m = scg.load_map("pinball_simple")
+    n, n_opt, mask, gest = 2000, 3, 0b1010, 0b0100
+    ctx, W, clf = _setup(m, n, n_opt, None, [0, 0, 1, 1], gest, reoffer_period=4, epsilon=0.1)
+    st0 = _state(ctx, m, n, n_opt, seed=13)
+    probe = _clone(st0)
+    ctx.rollout(probe, W, clf, mask, 50, 0, begin=True)         # the start states BEGIN draws at t0 = 50
+    K = 30
+    a, sa, ta = _clone(st0), EpisodeStats(ctx.n_vf, n, ctx.device), Trajectory(n, K + 1, 0, ctx.device)
+    ctx.rollout(a, W, clf, mask, 50, K, sa, begin=True, record=ta)
+    b, sb, tb = _clone(st0), EpisodeStats(ctx.n_vf, n, ctx.device), Trajectory(n, K + 1, 0, ctx.device)
+    b.x.copy_(probe.x); b.y.copy_(probe.y); b.vx.zero_(); b.vy.zero_()
+    ctx.rollout(b, W, clf, mask, 50, K, sb, begin_at=True, record=tb)
+    torch.cuda.synchronize()
+    _assert_same(a, b, FIELDS, "BEGIN_AT vs BEGIN")
+    _assert_same(sa, sb, STATS, "BEGIN_AT vs BEGIN stats")
+    _assert_same(ta, tb, ("len",) + Trajectory.FIELDS, "BEGIN_AT vs BEGIN rows")
+    assert (tb.action[0] == 255).all() and (tb.done[0] == 2).all() and (tb.vf[0] == 0).all()
+    assert torch.equal(tb.x[0], probe.x) and torch.equal(tb.vx[0], torch.zeros_like(probe.vx))
+
+
+def test_begin_at_selection_and_steps():
+    """From free states with velocities: the begin pseudo-step's selection equals a host model (candidate, value gate,
+    qcache), and the steps that follow equal the step loop."""
+    m = scg.load_map("pinball_simple")
+    n, n_opt, mask, gest = 2000, 3, 0b1110, 0
+    ctx, W, clf = _setup(m, n, n_opt, None, None, gest, epsilon=0.1)
+    st0 = _state(ctx, m, n, n_opt, seed=21)
+    tx, ty, _ = m.target
+    rng = np.random.default_rng(3)                             # half the starts near the goal's nested sets
+    pool = m.sample_free(8 * n, rng)
+    near = pool[np.hypot(pool[:, 0] - tx, pool[:, 1] - ty) < 0.5][: n // 2]
+    st0.x[: len(near)] = dev(near[:, 0].astype(np.float32)); st0.y[: len(near)] = dev(near[:, 1].astype(np.float32))
+    s = _clone(st0)
+    ctx.rollout(s, W, clf, mask, 9, 0, begin_at=True)
+    torch.cuda.synchronize()
+    sv = [getattr(st0, f) for f in ("x", "y", "vx", "vy")]
+    Wv = W.view(ctx.n_vf, -1)
+    q = [ctx.q_values(sv, Wv[k].contiguous()).cpu().numpy() for k in range(ctx.n_vf)]
+    W8 = clf.view(ctx.n_vf, -1)
+    inB = np.zeros(n, np.int64)
+    for k in range(1, ctx.n_vf):
+        if not (mask | gest) >> k & 1:
+            continue
+        inB |= ctx.classifier_predict(sv[0], sv[1], W8[k].contiguous()).cpu().numpy().astype(np.int64) << k
+    par = [int(v) for v in ctx.parents]
+    cand = np.zeros(n, np.int64)
+    for i in range(n):
+        tgt = 0
+        for k in range(1, ctx.n_vf):
+            if par[k] != 0 and (inB[i] >> par[k]) & 1:
+                tgt |= 1 << k
+        sel = int(inB[i]) & ~tgt & mask
+        cand[i] = (sel & -sel).bit_length() - 1 if sel else 0
+    mc = np.array([q[c][:, i].max() for i, c in enumerate(cand)], np.float32)
+    m0 = q[0].max(axis=0)
+    declined = (cand >= 1) & ~(mc >= m0)
+    oid = np.where(declined, -cand, cand)
+    qc = np.stack([q[0][:, i] if (declined[i] or cand[i] == 0) else q[cand[i]][:, i] for i in range(n)], axis=1)
+    assert np.array_equal(s.option_id.cpu().numpy(), oid.astype(np.int32))
+    assert np.array_equal(_bits(s.qcache.view(5, n)), _bits(qc))
+    for f in ("x", "y", "vx", "vy"):
+        assert torch.equal(getattr(s, f), getattr(st0, f)), f"BEGIN_AT moved {f}"
+    assert (s.ep_steps == 0).all() and (s.opt_steps == 0).all()
+    assert (cand >= 1).sum() > 100 and declined.sum() > 0 and (oid > 0).sum() > 0, "the model sees too few offers"
+    K = 20
+    a = _clone(st0)
+    ctx.rollout(a, W, clf, mask, 9, K, begin_at=True)
+    for t in range(10, 10 + K):
+        ctx.step(s, W, clf, mask, t, learn=False)
+    torch.cuda.synchronize()
+    _assert_same(a, s, FIELDS, "BEGIN_AT + K steps vs BEGIN_AT + the step loop")
+
+
+def _trial_case(n=3000, rows=None, max_opt=25):
+    m = scg.load_map("pinball_simple")
+    n_opt, mask = 3, 0b1110
+    kw = dict(HP)
+    kw.update(epsilon=0.2, r_option_success=100.0, max_option_steps=max_opt, max_episode_steps=60)
+    ctx = ScgContext(n, n_opt, m, device=0, seed=4, env_id_base=3, **kw)
+    clf = dev(chain_classifiers(m, n_opt)).view(-1)
+    W = dev(random_weights(n_opt + 1, 5, std=0.1)).view(-1)
+    rng = np.random.default_rng(2)
+    x, y, vx, vy = random_states(m, n, 2, vmax=1.0)
+    tx, ty, _ = m.target
+    pool = m.sample_free(16 * n, rng)
+    near = pool[np.hypot(pool[:, 0] - tx, pool[:, 1] - ty) < 0.5][: n // 2]
+    x[: len(near)], y[: len(near)] = near[:, 0], near[:, 1]
+    opt = rng.integers(1, n_opt + 1, n).astype(np.int32)
+    opt[rng.random(n) < 0.1] = 0
+    return ctx, W, clf, mask, [dev(v.astype(np.float32)) for v in (x, y, vx, vy)], opt
+
+
+def _trials(ctx, s0, opt, W, clf, mask, rec=None):
+    res = TrialResult(len(opt), opt, ctx.device)
+    ctx.option_trials(*s0, res.option, W, clf, mask, 11, res, record=rec)
+    torch.cuda.synchronize()
+    return res
+
+
+def test_trial_rows():
+    ctx, W, clf, mask, s0, opt = _trial_case()
+    n = len(opt)
+    ref = _trials(ctx, s0, opt, W, clf, mask)
+    rows = int(ctx.cfg.max_option_steps)
+    tr = _guarded(n, rows)
+    res = _trials(ctx, s0, opt, W, clf, mask, tr)
+    _assert_same(res, ref, TrialResult.FIELDS, "recorded trials")
+    _assert_guarded(tr)
+    steps, oc = res.steps.cpu().numpy(), res.outcome.cpu().numpy()
+    run = oc != 0
+    ln = tr.len.cpu().numpy()
+    assert np.array_equal(ln[run], steps[run]) and (ln[~run] == 0).all()
+    h = {f: getattr(tr, f).cpu().numpy() for f in tr.fields}
+    last = np.maximum(ln - 1, 0)
+    idx = np.arange(n)
+    assert np.array_equal(h["term"][last, idx][run], oc[run])
+    for f, e in (("x", "end_x"), ("y", "end_y"), ("vx", "end_vx"), ("vy", "end_vy")):
+        assert np.array_equal(_bits(h[f][last, idx][run]), _bits(getattr(res, e).cpu().numpy()[run]))
+    # the pinball_step chain of every run entry, and the return
+    s = [v.clone() for v in s0]
+    for j in range(int(ln.max())):
+        live = ln > j
+        act = torch.tensor(np.where(live, h["action"][j], 0).astype(np.uint8), device=ctx.device)
+        r, _ = ctx.pinball_step(s, act)
+        for f, v in zip(("x", "y", "vx", "vy"), s):
+            assert np.array_equal(_bits(h[f][j][live]), _bits(v.cpu().numpy()[live])), f"row {j}: {f}"
+        assert np.array_equal(_bits(h["reward"][j][live]), _bits(r.cpu().numpy()[live])), f"row {j}: reward"
+        assert (h["vf"][j][live] == opt[live]).all() and (h["option_id"][j][live] == opt[live]).all()
+        assert (h["term"][j][live & (ln > j + 1)] == 0).all()
+    ret = res.ret.cpu().numpy()
+    for i in np.flatnonzero(run)[:500]:
+        acc = np.float32(0.0)
+        for j in range(ln[i]):
+            acc = np.float32(acc + np.float32(h["reward"][j, i] + (np.float32(100.0) if h["term"][j, i] == 1 else 0)))
+        assert acc == ret[i], f"entry {i}: ret"
+    assert len(set(oc[run].tolist())) >= 3
+
+
+def test_trial_rows_truncated_and_windowed():
+    ctx, W, clf, mask, s0, opt = _trial_case(n=2000, max_opt=40)
+    ref = _trials(ctx, s0, opt, W, clf, mask)
+    rows = 3
+    tr = _guarded(500, rows, first=1500)
+    res = _trials(ctx, s0, opt, W, clf, mask, tr)
+    _assert_same(res, ref, TrialResult.FIELDS, "truncated record")
+    _assert_guarded(tr)
+    steps = ref.steps.cpu().numpy()[1500:]
+    oc = ref.outcome.cpu().numpy()[1500:]
+    want = np.where(oc != 0, np.minimum(steps, rows), 0)
+    assert np.array_equal(tr.len.cpu().numpy(), want)
+    assert (steps[oc != 0] > rows).any()
+
+
+def _agent(n=2048, n_opt=2, seed=1):
+    from skill_chaining_with_graphs_amd.agent import SkillChainingAgent
+    m = scg.load_map("pinball_simple")
+    kw = dict(HP)
+    kw.update(max_episode_steps=100)
+    ag = SkillChainingAgent(m, n, n_opt, seed=seed, block_envs=256, **kw)
+    ag.init_weights(std=0.05, seed=3)
+    ag.clf.copy_(dev(chain_classifiers(m, n_opt)))
+    ag.enable_option(1)
+    ag.gest_mask = 0b100
+    ag.gest_counts = ag.ctx.set_gestation(ag.gest_mask)
+    x, y, vx, vy = random_states(m, n, 7, vmax=1.0)
+    for t, v in zip(ag.state.state(), (x, y, vx, vy)):
+        t.copy_(dev(v))
+    ag.ctx.invalidate_order()
+    return ag
+
+
+def test_agent_record_episodes():
+    a, b = _agent(), _agent()
+    for ag in (a, b):
+        ag.ctx.set_trace_buffers(64)
+    calls = []
+    orig_call, orig_step = a.ctx._call, a.ctx.step
+
+    def guarded(fn, **kw):
+        a.ctx._call = lambda name, *args: (calls.append(name), orig_call(name, *args))[1]
+        a.ctx.step = lambda *args, **k: (calls.append("step"), orig_step(*args, **k))[1]
+        try:
+            return fn(**kw)
+        finally:
+            a.ctx._call, a.ctx.step = orig_call, orig_step
+
+    for i in range(30):
+        if i in (0, 17):
+            guarded(a.record_episodes, n_episodes=300, steps_per_launch=32)
+        a.step_batch()
+        b.step_batch()
+    torch.cuda.synchronize()
+    assert calls == [], f"record_episodes() called into the training context: {calls}"
+    assert torch.equal(a.W, b.W)
+    for f in FIELDS:
+        assert torch.equal(getattr(a.state, f), getattr(b.state, f)), f
+    for x, y in zip(a.ctx._trace, b.ctx._trace):
+        assert torch.equal(x, y)
+    assert torch.equal(a.gest_counts, b.gest_counts) and a.t == b.t == 30
+    tr, summ = a.record_episodes(n_episodes=300, steps_per_launch=32, seed=5)
+    assert summ == a.evaluate(n_episodes=300, steps_per_launch=32, seed=5)
+    ts = tr.summary()
+    assert len(ts["segments"]) == len(summ["entries"]) == a.n_vf
+    for k in range(1, a.n_vf):                      # a run per entry (none after an entry on an episode's last step)
+        assert ts["segments"][k] <= summ["entries"][k] and ts["term_hist"][k][1] == summ["successes"][k]
+    assert ts["episodes"] == summ["episodes"] == 300
+    assert ts["goal_rate"] == summ["success_rate"]
+    assert sum(tr.length(i) - 1 for i in range(300)) == round(summ["mean_length"] * 300)
+    m = a.map
+    pos = m.sample_free(200, np.random.default_rng(4))
+    vel = np.random.default_rng(5).uniform(-0.5, 0.5, (2, 200)).astype(np.float32)
+    states = (pos[:, 0], pos[:, 1], vel[0], vel[1])
+    tr2, s2 = a.record_episodes(states=states, steps_per_launch=32, seed=5)
+    assert a.evaluate(states=states, steps_per_launch=32, seed=5) == s2 and s2["episodes"] == 200
+    for i in (0, 57, 199):
+        e = tr2.per_env(i)
+        assert e["x"][0] == np.float32(pos[i, 0]) and e["vy"][0] == vel[1, i]
+    xs, ys = (dev(pos[:, 0].astype(np.float32)), dev(pos[:, 1].astype(np.float32)))
+    r0 = a.option_trials(1, xs, ys)
+    r1 = a.option_trials(1, xs, ys, record=300)
+    _assert_same(r1, r0, TrialResult.FIELDS + ("option",), "option_trials(record=...)")
+    run = r1.outcome.cpu().numpy() != 0
+    assert np.array_equal(r1.trajectory.len.cpu().numpy()[run], r1.steps.cpu().numpy()[run])
+    assert calls == []
+
+
+def test_refusals():
+    m = scg.load_map("pinball_simple")
+    n, n_opt, mask = 300, 2, 0b110
+    ctx, W, clf = _setup(m, n, n_opt)
+    st = _state(ctx, m, n, n_opt, seed=1)
+    stats = EpisodeStats(ctx.n_vf, n, ctx.device)
+    lib = ctx.lib
+    P = lambda t: C.c_void_p(t.data_ptr())
+    base = [P(st.x), P(st.y), P(st.vx), P(st.vy), P(st.option_id), P(st.opt_steps), P(st.ep_steps), P(st.qcache),
+            P(st.action), P(st.reward), P(st.done), P(W), P(clf), C.c_uint32(mask), C.c_uint64(0)]
+    cs = stats.c_struct()
+
+    def roll(n_steps, flags, rec):
+        return lib.scg_rollout_record(ctx._ctx, *base, C.c_int32(n_steps), C.c_uint32(flags), C.byref(cs),
+                                      None if rec is None else C.byref(rec), None)
+
+    tr = Trajectory(n, 9, 0, ctx.device)
+
+    def rec(**kw):
+        r = tr.c_struct()
+        for k, v in kw.items():
+            setattr(r, k, v)
+        return r
+
+    B, AT, ONE = _lib.ROLLOUT_BEGIN, _lib.ROLLOUT_BEGIN_AT, _lib.ROLLOUT_ONE_EPISODE
+    assert roll(8, B, rec()) == 0 and roll(9, 0, rec()) == 0 and roll(8, AT | ONE, rec()) == 0 and roll(8, AT, None) == 0
+    for n_steps, flags, r in ((8, 0, rec(len=None)), (8, 0, rec(n=0)), (8, 0, rec(first=-1)), (8, 0, rec(first=1)),
+                              (8, 0, rec(first=n - 1, n=2)), (9, B, rec()), (9, AT, rec()), (10, 0, rec()),
+                              (8, B | AT, rec()), (8, B | AT, None), (0, 0, rec()), (8, 8, rec())):
+        assert roll(n_steps, flags, r) == -1, (n_steps, flags, r.first, r.n)
+    assert lib.scg_rollout(ctx._ctx, *base, C.c_int32(8), C.c_uint32(AT), C.byref(cs), None) == -1
+    res = TrialResult(n, np.ones(n, np.int32), ctx.device)
+    out = res.c_struct()
+    targs = [C.c_int32(n), P(st.x), P(st.y), P(st.vx), P(st.vy), P(res.option), P(W), P(clf), C.c_uint32(mask),
+             C.c_uint64(0), C.byref(out)]
+    trial = lambda r: lib.scg_option_trials_record(ctx._ctx, *targs, None if r is None else C.byref(r), None)
+    assert trial(rec()) == 0 and trial(None) == 0 and trial(rec(rows=1)) == 0
+    for r in (rec(len=None), rec(n=0), rec(first=-1), rec(first=1), rec(rows=0)):
+        assert trial(r) == -1
+    torch.cuda.synchronize()
+    with pytest.raises(scg.ScgError):
+        ctx.rollout(st, W, clf, mask, 0, 9, record=Trajectory(n, 9, 0, ctx.device), begin=True)
+    with pytest.raises(scg.ScgError):
+        ctx.rollout(st, W, clf, mask, 0, 4, begin=True, begin_at=True)

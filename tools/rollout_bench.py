@@ -2,9 +2,10 @@
 
 Root + 5 options (chain classifiers, all enabled), bench-like weights (std 1e-3), 4096 and 65 536 envs, K = 64. Each side is
 warmed up and synchronised, and the two are timed alternately (rounds of rollout, step loop, rollout, ...); the line per size
-gives the median over the rounds.
+gives the median over the rounds. --record adds rollouts that record every step (SPEC §10) of all envs (`all`) or of the
+first N envs (`N`), timed in the same alternation (`none` is the plain rollout, always timed).
 
-    python tools/rollout_bench.py [--sizes 4096 65536] [--k 64] [--rounds 7] [--epw 2 4 8 16 32]
+    python tools/rollout_bench.py [--sizes 4096 65536] [--k 64] [--rounds 7] [--epw 2 4 8 16 32] [--record none 1024 all]
 """
 import argparse
 import json
@@ -20,6 +21,7 @@ import torch  # noqa: E402
 
 import skill_chaining_with_graphs_amd as scg  # noqa: E402
 from skill_chaining_with_graphs_amd.core import EnvState, ScgContext  # noqa: E402
+from skill_chaining_with_graphs_amd.trajectory import Trajectory  # noqa: E402
 
 
 def chain_classifiers(m, n_options):
@@ -51,7 +53,7 @@ def _time(fn, reps):
     return (time.perf_counter() - t0) / reps
 
 
-def bench(n, k, rounds, n_opt=5, epw=None):
+def bench(n, k, rounds, n_opt=5, epw=None, record=()):
     m = scg.load_map("pinball_simple")
     ctx = ScgContext(n, n_opt, m, device=0, seed=7, epsilon=0.05, max_episode_steps=2000)
     mask = ((1 << (n_opt + 1)) - 1) & ~1
@@ -75,15 +77,34 @@ def bench(n, k, rounds, n_opt=5, epw=None):
             ctx.step(st_s, W, clf, mask, t["s"], learn=False)
             t["s"] += 1
 
+    recs = []                                             # (label, its own state and step counter, the record)
+    for spec in record:
+        nr = n if spec == "all" else min(int(spec), n)
+        recs.append((spec, {"st": _state(ctx, m, n), "t": 0}, Trajectory(nr, k, 0, ctx.device)))
+
+    def roll_rec(r):
+        ctx.rollout(r[1]["st"], W, clf, mask, r[1]["t"], k, record=r[2])
+        r[1]["t"] += k
+
     roll(); loop(); roll(); loop()                        # warm-up (first launches, allocator, code objects)
-    r_us, s_us = [], []
+    for r in recs:
+        roll_rec(r); roll_rec(r)
+    r_us, s_us, rec_us = [], [], {r[0]: [] for r in recs}
     for _ in range(rounds):
         r_us.append(_time(roll, 3) * 1e6 / k)
         s_us.append(_time(loop, 3) * 1e6 / k)
+        for r in recs:
+            rec_us[r[0]].append(_time(lambda: roll_rec(r), 3) * 1e6 / k)
     r, s = float(np.median(r_us)), float(np.median(s_us))
-    return {"n_envs": n, "k": k, "epw": epw or "auto", "options": n_opt, "rollout_us_per_step": round(r, 2), "step_loop_us_per_step": round(s, 2),
-            "speedup": round(s / r, 2), "rollout_rounds_us": [round(v, 2) for v in r_us],
-            "step_loop_rounds_us": [round(v, 2) for v in s_us]}
+    out = {"n_envs": n, "k": k, "epw": epw or "auto", "options": n_opt, "rollout_us_per_step": round(r, 2), "step_loop_us_per_step": round(s, 2),
+           "speedup": round(s / r, 2), "rollout_rounds_us": [round(v, 2) for v in r_us],
+           "step_loop_rounds_us": [round(v, 2) for v in s_us]}
+    for label, v in rec_us.items():
+        med = float(np.median(v))
+        out[f"record_{label}_us_per_step"] = round(med, 2)
+        out[f"record_{label}_cost_pct"] = round(100.0 * (med / r - 1.0), 1)
+        out[f"record_{label}_rounds_us"] = [round(x, 2) for x in v]
+    return out
 
 
 def main():
@@ -93,9 +114,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--epw", type=int, nargs="*", default=None,
                     help="also time the rollout at these pinned launch geometries (envs per wave: 2, 4, 8, 16, 32)")
+    ap.add_argument("--record", nargs="+", default=["none"],
+                    help="also time recorded rollouts: `all` envs or the first N envs (`none`: the plain rollout only)")
     a = ap.parse_args()
+    rec = [r for r in a.record if r != "none"]
+    for r in rec:
+        if r != "all" and not r.isdigit():
+            ap.error(f"--record takes none, all or an env count, not {r}")
     for n in a.sizes:
-        print(json.dumps(bench(n, a.k, a.rounds)), flush=True)
+        print(json.dumps(bench(n, a.k, a.rounds, record=rec)), flush=True)
         for epw in a.epw or []:
             print(json.dumps(bench(n, a.k, a.rounds, epw=epw)), flush=True)
 

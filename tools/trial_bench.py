@@ -5,7 +5,9 @@ Workload: root + a 5-option chain (chain classifiers, all enabled), bench-like w
 free positions and velocities), option k = 1 + (i mod 5) for entry i, max_option_steps = 250. The two sides are warmed up and
 timed alternately; the line gives the medians over the rounds (ms per batch of trials) and the step count of the longest trial.
 
-    python tools/trial_bench.py [--n 65536] [--rounds 5] [--max-option-steps 250]
+With --record ROWS the trials are also timed with every step recorded (SPEC §10, ROWS rows per entry), in the same alternation.
+
+    python tools/trial_bench.py [--n 65536] [--rounds 5] [--max-option-steps 250] [--record 250]
 """
 import argparse
 import json
@@ -22,6 +24,7 @@ import torch  # noqa: E402
 
 import skill_chaining_with_graphs_amd as scg  # noqa: E402
 from skill_chaining_with_graphs_amd.core import EnvState, ScgContext  # noqa: E402
+from skill_chaining_with_graphs_amd.trajectory import Trajectory  # noqa: E402
 from skill_chaining_with_graphs_amd.trials import TrialResult  # noqa: E402
 from rollout_bench import chain_classifiers  # noqa: E402
 
@@ -34,7 +37,7 @@ def _time(fn):
     return time.perf_counter() - t0
 
 
-def bench(n, rounds, max_opt, n_opt=5):
+def bench(n, rounds, max_opt, n_opt=5, rows=0):
     m = scg.load_map("pinball_simple")
     ctx = ScgContext(n, n_opt, m, device=0, seed=7, epsilon=0.05, max_episode_steps=2000, max_option_steps=max_opt)
     mask = ((1 << (n_opt + 1)) - 1) & ~1
@@ -67,16 +70,28 @@ def bench(n, rounds, max_opt, n_opt=5):
             ctx.step(st, W, clf, mask, t, learn=False)
 
     loop()
-    tr, lp = [], []
+    rec = Trajectory(n, rows, 0, ctx.device) if rows else None
+    res_rec = TrialResult(n, opt, ctx.device)
+    trials_rec = lambda: ctx.option_trials(*s0, opt, W, clf, mask, 0, res_rec, record=rec)
+    if rec is not None:
+        trials_rec()
+    tr, lp, rr = [], [], []
     for _ in range(rounds):
         tr.append(_time(trials) * 1e3)
         lp.append(_time(loop) * 1e3)
+        if rec is not None:
+            rr.append(_time(trials_rec) * 1e3)
     a, b = float(np.median(tr)), float(np.median(lp))
     hist = np.bincount(res.outcome.cpu().numpy(), minlength=5)[1:].tolist()
-    return {"n": n, "options": n_opt, "max_option_steps": max_opt, "longest_trial_steps": longest,
+    out = {"n": n, "options": n_opt, "max_option_steps": max_opt, "longest_trial_steps": longest,
             "mean_steps": round(float(res.steps.double().mean()), 2), "outcomes_succ_end_left_timeout": hist,
             "trials_ms": round(a, 3), "step_loop_ms": round(b, 3), "speedup": round(b / a, 2),
             "trials_rounds_ms": [round(x, 3) for x in tr], "step_loop_rounds_ms": [round(x, 3) for x in lp]}
+    if rec is not None:
+        c = float(np.median(rr))
+        out.update({"record_rows": rows, "trials_record_ms": round(c, 3), "record_cost_pct": round(100.0 * (c / a - 1.0), 1),
+                    "trials_record_rounds_ms": [round(x, 3) for x in rr]})
+    return out
 
 
 def main():
@@ -84,8 +99,9 @@ def main():
     ap.add_argument("--n", type=int, default=65536)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--max-option-steps", type=int, default=250)
+    ap.add_argument("--record", type=int, default=0, help="also time the trials recorded with this many rows per entry")
     a = ap.parse_args()
-    print(json.dumps(bench(a.n, a.rounds, a.max_option_steps)), flush=True)
+    print(json.dumps(bench(a.n, a.rounds, a.max_option_steps, rows=a.record)), flush=True)
 
 
 if __name__ == "__main__":
