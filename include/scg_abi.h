@@ -200,6 +200,25 @@ int scg_option_trials_record(scg_ctx *ctx, int32_t n, const float *x, const floa
                              const int32_t *option, const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0,
                              const scg_trial_out *out, const scg_record *rec, void *stream);
 
+/* ---- interrupting rollouts (SPEC §11): §8's rollout with a running option cut short where the root's value is higher ----
+ * scg_rollout_interrupt is scg_rollout_record with one change on every step of an env whose option o >= 1 goes on (SPEC §4.2's
+ * keep): with V_k = max_a Q_k(s', a) (this launch's W, §5's max order), the step is interrupted unless V_o >= V_0 (ties keep the
+ * option, a NaN on either side interrupts). An interrupted step writes option_id = -c, with c the smallest enabled option whose
+ * initiation set holds s' and whose target region does not (0 if none: option_id = 0), opt_steps = 0 and qcache = Q_0(s', .):
+ * the root runs next and c is offered again on §4.2's re-offer schedule. Nothing else of the step changes (action, physics, done,
+ * reset, the §8 counters); the begin pseudo-step never interrupts.
+ * `interrupts` (DEVICE [n_vf][N] int32, in/out, may be NULL = not kept): interrupts[o][e] += 1 per interrupted step.
+ * `rec` (may be NULL) as for scg_rollout_record; an interrupted row has vf = o, the option_id written, term =
+ * SCG_ROLLOUT_TERM_INTERRUPTED (never together with another code: an interrupt needs keep). Flags BEGIN, ONE_EPISODE and
+ * BEGIN_AT, validated as for scg_rollout_record, with the same errors. Results do not depend on the launch geometry or the block
+ * build. scg_rollout and scg_rollout_record never interrupt. */
+#define SCG_ROLLOUT_TERM_INTERRUPTED 5u
+int scg_rollout_interrupt(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                          int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                          const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                          uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, const scg_record *rec,
+                          void *stream);
+
 /* Device pointers of the ctx-owned reduced gradient G[n_vf][5][1296] and counts n_k[n_vf] (int32)
  * left by the last scg_step(LEARN) — the buffers a multi-rank caller all-reduces (SPEC §5). */
 int scg_grad_buffers(scg_ctx *ctx, float **G, int32_t **n_k);

@@ -26,6 +26,7 @@ TRIAL_EPISODE_END = 2
 TRIAL_LEFT_INITIATION = 3
 TRIAL_TIMEOUT = 4
 TRIAL_MAX_STEPS = ROLLOUT_MAX_STEPS
+ROLLOUT_TERM_INTERRUPTED = 5   # include/scg_abi.h SCG_ROLLOUT_TERM_INTERRUPTED: a recorded row's term where an option was interrupted
 ABI_VERSION = 5            # include/scg_abi.h SCG_ABI_VERSION
 ASYNC_FIT_TIMEOUT = 0x1
 ASYNC_STEP_HANDOFF = 0x2
@@ -126,6 +127,8 @@ _SIGS = {
                                                          C.POINTER(Record), _P]),
     "scg_option_trials_record": (C.c_int, [_P, C.c_int32] + [_P] * 7 + [C.c_uint32, C.c_uint64, C.POINTER(TrialOut),
                                                                        C.POINTER(Record), _P]),
+    "scg_rollout_interrupt": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(RolloutStats),
+                                                            _P, C.POINTER(Record), _P]),
     "scg_grad_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "scg_set_grad_buffers": (C.c_int, [_P, _P, _P]),
     "scg_apply_update": (C.c_int, [_P, _P, _P, _P, _P]),

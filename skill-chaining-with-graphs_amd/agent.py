@@ -349,7 +349,7 @@ class SkillChainingAgent:
         self.ctx.q_update(k, s, action, r, cont, s_next, self.W, apply=apply)
 
     def evaluate(self, n_episodes: int = 4096, epsilon: float = 0.0, seed: Optional[int] = None, steps_per_launch: int = 64,
-                 per_env: bool = False, states=None):
+                 per_env: bool = False, states=None, interrupt: bool = False):
         """How good the current policy is: one episode per env on `n_episodes` envs of a separate evaluation context (cached per
         n_episodes; another seed replaces the entry), acting with `epsilon` and the current W, clf and enabled options, weights
         frozen (SPEC §8). Returns
@@ -360,20 +360,24 @@ class SkillChainingAgent:
         state, t, the training context's env order, trace ring, gestation counts and peer exchange counter are untouched.
         A sharded agent evaluates its own rank's policy copy on this rank only: there is no collective here.
         With `states` ((x, y) or (x, y, vx, vy); velocities default to zero) episode i starts from state i instead of a drawn
-        start state (SPEC §10's BEGIN_AT), and n_episodes is the number of states."""
+        start state (SPEC §10's BEGIN_AT), and n_episodes is the number of states.
+        With `interrupt` a running option is cut short wherever the root's value at the next state is higher (SPEC §11's
+        interrupting rollout); the summary then also holds interrupts per value function."""
         ectx, st, stats, launches = self._eval_setup(n_episodes, epsilon, seed, steps_per_launch, states)
         spl = int(steps_per_launch)
         for i in range(launches):
             ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
-                         begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None))
+                         begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None),
+                         interrupt=interrupt)
         out = stats.summary()
         return (out, stats.per_env()) if per_env else out
 
     def record_episodes(self, n_episodes: int = 256, states=None, epsilon: float = 0.0, seed: Optional[int] = None,
-                        steps_per_launch: int = 64):
+                        steps_per_launch: int = 64, interrupt: bool = False):
         """evaluate() with every step recorded (SPEC §10): the same launches on the same evaluation context, each with a record
         of all envs that is appended to a Trajectory after the launch. Returns (Trajectory, the EpisodeStats summary, equal to
-        evaluate()'s with the same arguments). Row 0 of each env is its begin row. The training run is left alone."""
+        evaluate()'s with the same arguments). Row 0 of each env is its begin row. The training run is left alone.
+        `interrupt`: as for evaluate(); an interrupted step's row has term INTERRUPTED (SPEC §11)."""
         from .trajectory import Trajectory
         ectx, st, stats, launches = self._eval_setup(n_episodes, epsilon, seed, steps_per_launch, states)
         spl = int(steps_per_launch)
@@ -381,7 +385,7 @@ class SkillChainingAgent:
         for i in range(launches):
             ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
                          begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None),
-                         record=traj)
+                         record=traj, interrupt=interrupt)
             traj.append()
         return traj, stats.summary()
 

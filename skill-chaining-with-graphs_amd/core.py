@@ -163,13 +163,17 @@ class ScgContext:
         return record.c_struct()
 
     def rollout(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, n_steps: int,
-                stats=None, begin: bool = False, one_episode: bool = False, record=None, begin_at: bool = False) -> None:
+                stats=None, begin: bool = False, one_episode: bool = False, record=None, begin_at: bool = False,
+                interrupt: bool = False, interrupts=None) -> None:
         """SPEC §8: n_steps acting steps in ONE launch, bit for bit n_steps calls of step(learn=False) at t0 .. t0+n_steps-1
         (with `begin`: a new episode for every env at t0 first, the steps at t0+1 .. t0+n_steps). W is read, never written.
         `stats` (EpisodeStats of this context's n_vf and n_envs, on its device) receives the episode counters; `one_episode`
         leaves envs alone whose `stats.finished` is set. The step's prepared env order is invalid afterwards.
         SPEC §10: `record` (a Trajectory) receives the per-step rows of its window of envs; `begin_at` is `begin` from the
-        state in `st` (x, y, vx, vy as given) instead of a drawn start. Neither changes any other output."""
+        state in `st` (x, y, vx, vy as given) instead of a drawn start. Neither changes any other output.
+        SPEC §11: `interrupt` cuts a running option short wherever max_a Q_0(s', .) exceeds max_a Q_o(s', .) (scg_rollout_interrupt);
+        `interrupts` ([n_vf][n_envs] int32, in/out) counts the interrupted steps per option, by default into `stats.interrupts`
+        (which then shows in stats.summary())."""
         self._chk_operands(st, W, clf)
         N = self.n_envs
         n_steps, t0 = int(n_steps), int(t0)
@@ -193,6 +197,23 @@ class ScgContext:
         elif one_episode:
             raise ScgError("rollout: one_episode needs stats (its `finished` flags)")
         flags = (_lib.ROLLOUT_BEGIN if begin else 0) | (_lib.ROLLOUT_ONE_EPISODE if one_episode else 0)
+        if interrupts is not None and not interrupt:
+            raise ScgError("rollout: interrupts without interrupt=True")
+        if interrupt:
+            if interrupts is None and stats is not None:
+                interrupts = stats.interrupts
+            if interrupts is not None:
+                self._chk(interrupts, torch.int32, self.n_vf * N, "interrupts")
+            rc = None if record is None else self._chk_record(record, N, n_steps + (1 if begin or begin_at else 0), "rollout")
+            flags |= _lib.ROLLOUT_BEGIN_AT if begin_at else 0
+            self._call("scg_rollout_interrupt", _ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id),
+                       _ptr(st.opt_steps), _ptr(st.ep_steps), _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done),
+                       _ptr(W), _ptr(clf), C.c_uint32(enabled_mask), C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags),
+                       None if cs is None else C.byref(cs), None if interrupts is None else _ptr(interrupts),
+                       None if rc is None else C.byref(rc), self._stream())
+            if stats is not None and interrupts is stats.interrupts:
+                stats.interrupting = True
+            return
         if record is not None or begin_at:
             rc = None if record is None else self._chk_record(record, N, n_steps + (1 if begin or begin_at else 0), "rollout")
             flags |= _lib.ROLLOUT_BEGIN_AT if begin_at else 0

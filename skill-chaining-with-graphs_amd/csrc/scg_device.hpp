@@ -449,6 +449,14 @@ __device__ __forceinline__ int select_option(uint32_t parents, unsigned inB, uns
 __device__ __forceinline__ int reoffer_stay(bool keep, int cand, int dn, int o_in, uint64_t t, uint64_t gid, uint32_t reoffer_mask) {
     return (!keep && cand >= 1 && dn == 0 && o_in == -cand && (((uint32_t)t + (uint32_t)gid) & reoffer_mask) != 0u) ? cand : 0;
 }
+// the value gate's comparison (SPEC §4.2; §11's interruption): max_a qk >= max_a q0, each max in SPEC §5's order (IEEE maxNum).
+// Ties hold; a NaN on either side fails
+__device__ __forceinline__ bool gate_holds(const float (&qk)[NACT], const float (&q0)[NACT]) {
+    float mk = qk[0], m0 = q0[0];
+#pragma unroll
+    for (int a = 1; a < NACT; ++a) { mk = fmaxf(mk, qk[a]); m0 = fmaxf(m0, q0[a]); }
+    return mk >= m0;
+}
 
 // ------------------------------------------------------------------ SPEC §6
 __device__ __forceinline__ float sigmoid_spec(float z) {

@@ -11,6 +11,8 @@
 // trial_kernel (scg_trial_kernel.hpp): option trials (SPEC §9), each from its start state to the option's termination, in one
 // launch with the rollout's geometry.
 // rollout_kernel<true> / trial_kernel<true> (scg_record_kernels.hip): the same two kernels with SPEC §10's per-step record.
+// rollout_kernel on RolloutIntArgs / RolloutIntRecArgs (scg_record_kernels.hip): SPEC §11's interrupting rollout, without and
+// with the record.
 // fit_kernel: SPEC §6 on 8 workgroups x 1024 chains per option behind tagged-word exchanges; a fit whose workgroups cannot run
 // together gives up after a wall-clock wait, leaves its row untouched and raises the ctx's asynchronous status word.
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
@@ -112,6 +114,9 @@ __device__ __forceinline__ bool in_set(const StepArgs &A, int k, float x, float 
 // the recording instantiations (SPEC §10), compiled and launched in scg_record_kernels.hip
 __attribute__((visibility("hidden"))) hipError_t launch_rollout_record(const RolloutRecArgs &A, int grid, hipStream_t s);
 __attribute__((visibility("hidden"))) hipError_t launch_trial_record(const TrialRecArgs &A, int grid, hipStream_t s);
+// the interrupting instantiations (SPEC §11), in the same translation unit
+__attribute__((visibility("hidden"))) hipError_t launch_rollout_interrupt(const RolloutIntArgs &A, int grid, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_rollout_interrupt_record(const RolloutIntRecArgs &A, int grid, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // slabs -> G (SPEC §5 two-level block order), n_k, optional apply; the next step's env order rides along
@@ -1555,11 +1560,12 @@ static int check_record(scg_ctx *c, const char *fn, const scg_record *rec, int N
 }
 
 // scg_rollout, and scg_rollout_record (`fn` names the caller in error texts) with `rec` or `at` (BEGIN_AT, passed as BEGIN in
-// `flags`): the recording instantiation
+// `flags`): the recording instantiation; scg_rollout_interrupt (`intr`): the interrupting ones, counting into `interrupts`
 static int rollout_launch(const char *fn, scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
                           int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
                           const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
-                          uint32_t flags, const scg_rollout_stats *stats, const scg_record *rec, bool at, void *stream) {
+                          uint32_t flags, const scg_rollout_stats *stats, const scg_record *rec, bool at, void *stream,
+                          bool intr = false, int32_t *interrupts = nullptr) {
     if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
     if (!c->have_map) return fail_in(c, SCG_ERR_STATE, fn, "scg_set_map has not been called");
     if (!x || !y || !vx || !vy || !option_id || !opt_steps || !ep_steps || !qcache || !action || !reward ||
@@ -1592,6 +1598,24 @@ static int rollout_launch(const char *fn, scg_ctx *c, float *x, float *y, float 
     R.epw = epw;
     const int grid = (c->cfg.n_envs + RO_WAVES * epw - 1) / (RO_WAVES * epw);
     c->order_valid = false;                               // the ids change under the step's prepared env order
+    if (intr && (rec || at)) {
+        RolloutIntRecArgs RR;
+        memset(&RR, 0, sizeof(RR));
+        static_cast<RolloutArgs &>(RR) = R;
+        if (rec) RR.rec = *rec;
+        RR.begin_at = at ? 1u : 0u;
+        RR.interrupts = interrupts;
+        SCG_HIP(c, launch_rollout_interrupt_record(RR, grid, reinterpret_cast<hipStream_t>(stream)));
+        return SCG_OK;
+    }
+    if (intr) {
+        RolloutIntArgs RI;
+        memset(&RI, 0, sizeof(RI));
+        static_cast<RolloutArgs &>(RI) = R;
+        RI.interrupts = interrupts;
+        SCG_HIP(c, launch_rollout_interrupt(RI, grid, reinterpret_cast<hipStream_t>(stream)));
+        return SCG_OK;
+    }
     if (rec || at) {
         RolloutRecArgs RR;
         memset(&RR, 0, sizeof(RR));
@@ -1625,6 +1649,20 @@ int scg_rollout_record(scg_ctx *c, float *x, float *y, float *vx, float *vy, int
     const uint32_t fl = at ? (flags & ~SCG_ROLLOUT_BEGIN_AT) | SCG_ROLLOUT_BEGIN : flags;
     return rollout_launch("scg_rollout_record", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done,
                           W, clf, enabled_mask, t0, n_steps, fl, stats, rec, at, stream);
+}
+
+int scg_rollout_interrupt(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                          int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                          const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                          uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, const scg_record *rec,
+                          void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_rollout_interrupt: null ctx");
+    const bool at = (flags & SCG_ROLLOUT_BEGIN_AT) != 0;
+    if (at && (flags & SCG_ROLLOUT_BEGIN))
+        return fail(c, SCG_ERR_INVALID, "scg_rollout_interrupt: SCG_ROLLOUT_BEGIN and SCG_ROLLOUT_BEGIN_AT together");
+    const uint32_t fl = at ? (flags & ~SCG_ROLLOUT_BEGIN_AT) | SCG_ROLLOUT_BEGIN : flags;
+    return rollout_launch("scg_rollout_interrupt", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done,
+                          W, clf, enabled_mask, t0, n_steps, fl, stats, rec, at, stream, true, interrupts);
 }
 
 static int trials_launch(const char *fn, scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,

@@ -44,11 +44,21 @@ struct RolloutArgs {
     int32_t max_ep, max_opt;
     uint32_t reoffer_mask;
     MapScalars ms;
+    static constexpr bool INT = false;   // SPEC §11's interruption: a compile-time flag of the argument type (kernel symbols unchanged)
 };
 // the recording instantiation's arguments (SPEC §10): RolloutArgs at offset 0, so the exit's re-read holds for both
 struct RolloutRecArgs : RolloutArgs {
     scg_record rec;                // device pointers; n = 0: nothing recorded
     uint32_t begin_at;             // BEGIN's reset replaced by the state given
+};
+// the interrupting instantiations' arguments (SPEC §11), without and with the record; the base at offset 0 as above
+struct RolloutIntArgs : RolloutArgs {
+    static constexpr bool INT = true;
+    int32_t *interrupts;           // [n_vf][N] in/out, may be null
+};
+struct RolloutIntRecArgs : RolloutRecArgs {
+    static constexpr bool INT = true;
+    int32_t *interrupts;
 };
 
 // per-VF counters of one launch, six 16-bit fields in three words (a launch takes at most 1 + SCG_ROLLOUT_MAX_STEPS steps)
@@ -85,9 +95,11 @@ __device__ __forceinline__ void record_len(const scg_record R, int e, bool mine,
 }
 
 // <false, RolloutArgs>: scg_rollout's kernel. <true, RolloutRecArgs>: the same steps, plus SPEC §10's rows of the envs in the
-// record's window, and BEGIN_AT (scg_rollout_record)
+// record's window, and BEGIN_AT (scg_rollout_record). <false, RolloutIntArgs> / <true, RolloutIntRecArgs>: the same with
+// SPEC §11's interruption (scg_rollout_interrupt); INT = Args::INT
 template <bool REC, typename Args>
 __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
+    constexpr bool INT = Args::INT;
     __shared__ __attribute__((aligned(16))) float s_w0[W_FLOATS];                 // W_0 in A-operand order (stage_w_cold's layout)
     __shared__ __attribute__((aligned(16))) float s_edges[MAX_EDGES * 8];
     __shared__ __attribute__((aligned(16))) float s_wave[RO_WAVES][RO_WAVE_FLOATS];
@@ -111,6 +123,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
     int episodes = 0, goals = 0, len_sum = 0;
     bool finished = false;
     Ctr16 c_vf = {{0u, 0u, 0u}}, c_en = {{0u, 0u, 0u}}, c_de = {{0u, 0u, 0u}}, c_su = {{0u, 0u, 0u}};
+    Ctr16 c_in = {{0u, 0u, 0u}};                               // INT: interrupted steps per option
     if (mine) {
         sx = A.x[e]; sy = A.y[e]; svx = A.vx[e]; svy = A.vy[e];
 #pragma unroll
@@ -182,6 +195,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         float nx = px, ny = py, nvx = pvx, nvy = pvy;
         bool keep = false, succ = false;
         int cand = 0, on = 0, stay = 0, term = 0;
+        int ic = 0;                                            // INT: §4.2's cand of a keeping env, as if its option had ended
         if (valid) {
             dn = is_begin ? 2 : episode_end(goal, eps1, A.max_ep);
             if (dn && !(REC && is_begin && kernel_args<RolloutRecArgs>()->begin_at)) restart_state(u[2], A.starts, A.ms.n_starts, nx, ny, nvx, nvy);
@@ -192,6 +206,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
                 term = succ ? (int)SCG_TRIAL_SUCCESS : dn ? (int)SCG_TRIAL_EPISODE_END
                      : !((inA >> o) & 1u) ? (int)SCG_TRIAL_LEFT_INITIATION : (int)SCG_TRIAL_TIMEOUT;
             cand = keep ? o : select_option(A.parents, inB, A.enabled);
+            if constexpr (INT) ic = keep ? select_option(A.parents, inB, A.enabled) : 0;
             stay = reoffer_stay(keep, cand, dn, is_begin ? 0 : oid, t, gid, A.reoffer_mask);
             on = stay ? 0 : cand;
             const float sh[4] = {nx, ny, fmaf(nvx, 0.25f, 0.5f), fmaf(nvy, 0.25f, 0.5f)};
@@ -199,10 +214,11 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
             for (int d = 0; d < 4; ++d) s_z1[il][d] = sincospi_cs(sh[d]);
         }
         const bool entering = valid && !keep && on >= 1;
-        // compaction: slot 0 -> the list of VF `on`, slot 1 (entering) -> the root's list
+        // compaction: slot 0 -> the list of VF `on`, slot 1 (entering; INT: keeping too) -> the root's list. An env is entering
+        // or keeping, never both, and either way runs on >= 1 next: the root's list still holds at most one item per env
 #pragma unroll
         for (int k = 0; k < MAX_VF; ++k) {
-            const bool w0 = valid && on == k, w1 = entering && k == 0;
+            const bool w0 = valid && on == k, w1 = (entering || (INT && keep)) && k == 0;
             const uint64_t b0 = __ballot(w0), b1 = __ballot(w1);
             const int n0 = __popcll(b0), n1 = __popcll(b1);
             if (n0 + n1 == 0) continue;                         // (wave-uniform)
@@ -272,11 +288,29 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
                     for (int aa = 0; aa < NACT; ++aa) qa[aa] = q0[aa];
                 }
             }
+            bool interrupted = false;                          // SPEC §11: the gate's comparison on every step an option goes on
+            if constexpr (INT) {
+                if (keep) {
+                    float q0[NACT];
+#pragma unroll
+                    for (int aa = 0; aa < NACT; ++aa) q0[aa] = s_qv[1][aa][il];
+                    interrupted = !gate_holds(qa, q0);         // V_o against V_0 at s_next: ties keep the option
+                    if (interrupted) {
+#pragma unroll
+                        for (int aa = 0; aa < NACT; ++aa) qa[aa] = q0[aa];
+                    }
+                }
+            }
 #pragma unroll
             for (int aa = 0; aa < NACT; ++aa) qc[aa] = qa[aa];
             sx = nx; sy = ny; svx = nvx; svy = nvy;
             oid = (declined || stay) ? -cand : cand;
             osteps = keep ? osteps + 1 : 0;
+            if constexpr (INT) {
+                if (interrupted) { oid = -ic; osteps = 0; }    // the root runs, staying out of ic (0: none) until its re-offer
+                c_in.add(o, interrupted);
+                if (interrupted) term = (int)SCG_ROLLOUT_TERM_INTERRUPTED;
+            }
             eps = dn ? 0 : eps1;
             c_en.add(cand, entering && !declined);
             c_de.add(cand, declined);
@@ -343,5 +377,10 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         if (S.entries) S.entries[at] += c_en.get(k);
         if (S.declines) S.declines[at] += c_de.get(k);
         if (S.successes) S.successes[at] += c_su.get(k);
+    }
+    if constexpr (INT) {
+        int32_t *const I = kernel_args<Args>()->interrupts;
+        if (I)
+            for (int k = 0; k < K->n_vf; ++k) I[(size_t)k * N + e] += c_in.get(k);
     }
 }

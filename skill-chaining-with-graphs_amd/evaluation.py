@@ -1,4 +1,5 @@
-"""EpisodeStats — the per-env counters of an acting rollout (SPEC §8, scg_rollout) and their host-side summary."""
+"""EpisodeStats — the per-env counters of an acting rollout (SPEC §8, scg_rollout; §11, scg_rollout_interrupt) and their
+host-side summary."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,7 +12,9 @@ from ._lib import RolloutStats
 
 class EpisodeStats:
     """Counter tensors of SPEC §8 for `n` envs and `n_vf` value functions (root + options), zeroed. They are in/out:
-    several rollout launches add up into one evaluation; `zero_()` starts a new one."""
+    several rollout launches add up into one evaluation; `zero_()` starts a new one. `interrupts` ([n_vf][n], SPEC §11) is kept
+    apart from FIELDS (the scg_rollout_stats members): an interrupting rollout counts into it and sets `interrupting`, which
+    adds it to per_env() and summary()."""
 
     FIELDS = ("ep_return", "ret_sum", "episodes", "goals", "len_sum", "vf_steps", "entries", "declines", "successes",
               "finished")
@@ -26,6 +29,8 @@ class EpisodeStats:
         self.vf_steps, self.entries = z((n_vf, n), torch.int32), z((n_vf, n), torch.int32)
         self.declines, self.successes = z((n_vf, n), torch.int32), z((n_vf, n), torch.int32)
         self.finished = z(n, torch.uint8)
+        self.interrupts = z((n_vf, n), torch.int32)
+        self.interrupting = False
 
     @property
     def device(self) -> torch.device:
@@ -34,6 +39,8 @@ class EpisodeStats:
     def zero_(self) -> "EpisodeStats":
         for f in self.FIELDS:
             getattr(self, f).zero_()
+        self.interrupts.zero_()
+        self.interrupting = False
         return self
 
     def c_struct(self) -> RolloutStats:
@@ -41,12 +48,15 @@ class EpisodeStats:
         return RolloutStats(**{f: C.c_void_p(getattr(self, f).data_ptr()) for f in self.FIELDS})
 
     def per_env(self) -> dict:
-        return {f: getattr(self, f) for f in self.FIELDS}
+        out = {f: getattr(self, f) for f in self.FIELDS}
+        if self.interrupting:
+            out["interrupts"] = self.interrupts
+        return out
 
     def summary(self) -> dict:
         """Aggregate over the envs on the host in float64, in env order: episodes, success_rate, mean_return, mean_length
         (NaN with no episode recorded) and per value function k (index 0 = the root): steps_share (fraction of all steps
-        run under k), entries, declines, successes."""
+        run under k), entries, declines, successes; after an interrupting rollout also interrupts (SPEC §11)."""
         host = {f: getattr(self, f).detach().cpu().numpy() for f in self.FIELDS}
         eps = int(host["episodes"].astype(np.int64).sum())
         goals = int(host["goals"].astype(np.int64).sum())
@@ -56,7 +66,7 @@ class EpisodeStats:
         steps = host["vf_steps"].astype(np.int64).sum(axis=1)
         all_steps = int(steps.sum())
         nan = float("nan")
-        return {
+        out = {
             "episodes": eps,
             "success_rate": goals / eps if eps else nan,
             "mean_return": ret_total / eps if eps else nan,
@@ -66,3 +76,6 @@ class EpisodeStats:
             "declines": [int(v) for v in host["declines"].astype(np.int64).sum(axis=1)],
             "successes": [int(v) for v in host["successes"].astype(np.int64).sum(axis=1)],
         }
+        if self.interrupting:
+            out["interrupts"] = [int(v) for v in self.interrupts.detach().cpu().numpy().astype(np.int64).sum(axis=1)]
+        return out

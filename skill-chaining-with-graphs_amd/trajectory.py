@@ -6,10 +6,12 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import TRIAL_EPISODE_END, TRIAL_LEFT_INITIATION, TRIAL_SUCCESS, TRIAL_TIMEOUT, Record
+from ._lib import (ROLLOUT_TERM_INTERRUPTED, TRIAL_EPISODE_END, TRIAL_LEFT_INITIATION, TRIAL_SUCCESS, TRIAL_TIMEOUT,
+                   Record)
 
 TERMS = {0: "", TRIAL_SUCCESS: "SUCCESS", TRIAL_EPISODE_END: "EPISODE_END", TRIAL_LEFT_INITIATION: "LEFT_INITIATION",
-         TRIAL_TIMEOUT: "TIMEOUT"}
+         TRIAL_TIMEOUT: "TIMEOUT", ROLLOUT_TERM_INTERRUPTED: "INTERRUPTED"}
+HIST_TERMS = 5             # summary()'s term_hist: codes 0 .. 4; INTERRUPTED (SPEC §11) is counted apart
 BEGIN_ACTION = 255         # the action of a begin row (SPEC §10)
 
 
@@ -107,12 +109,14 @@ class Trajectory:
         code), with one entry per value function of the context (n_vf given at construction; else up to the largest vf seen);
         declined_rows: rows with option_id < 0, i.e. steps that end outside an option whose initiation set holds the next state, its
         offer declined by the value gate or not re-offered yet (a declined offer stays negative over several rows, so
-        this is not evaluate()'s count of value-gate declines); episodes (steps with done != 0), goals and goal_rate."""
+        this is not evaluate()'s count of value-gate declines); episodes (steps with done != 0), goals and goal_rate. Only
+        when some segment ends in INTERRUPTED (SPEC §11): interrupted, those segments per value function (not in term_hist)."""
         seen = 1 + max([int(s["vf"]) for i in range(self.n) for s in self.segments(i)] + [0])
         n_vf = seen if self.n_vf is None else max(self.n_vf, seen)
         seg = np.zeros(n_vf, np.int64)
         steps = np.zeros(n_vf, np.float64)
-        hist = np.zeros((n_vf, len(TERMS)), np.int64)
+        hist = np.zeros((n_vf, HIST_TERMS), np.int64)
+        intr = np.zeros(n_vf, np.int64)
         episodes = goals = declined_rows = 0
         for i in range(self.n):
             e = self.per_env(i)
@@ -121,13 +125,16 @@ class Trajectory:
                 k = s["vf"]
                 seg[k] += 1
                 steps[k] += float(np.sum(real[s["start"]: s["end"] + 1]))
-                hist[k, s["term"]] += 1
+                if s["term"] == ROLLOUT_TERM_INTERRUPTED:
+                    intr[k] += 1
+                else:
+                    hist[k, s["term"]] += 1
             episodes += int(np.sum((e["done"] != 0) & real))
             goals += int(np.sum((e["done"] == 1) & real))
             if "option_id" in e:
                 declined_rows += int(np.sum(e["option_id"] < 0))
         nan = float("nan")
-        return {
+        out = {
             "segments": [int(v) for v in seg],
             "mean_steps": [float(steps[k] / seg[k]) if seg[k] else nan for k in range(n_vf)],
             "term_hist": [[int(v) for v in hist[k]] for k in range(n_vf)],
@@ -136,6 +143,9 @@ class Trajectory:
             "goals": goals,
             "goal_rate": goals / episodes if episodes else nan,
         }
+        if intr.any():
+            out["interrupted"] = [int(v) for v in intr]
+        return out
 
     def to_numpy(self) -> dict:
         """Every env's rows flattened for saving: `offsets` [n + 1] into the concatenated fields, plus `first`."""

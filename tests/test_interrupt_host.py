@@ -1,0 +1,207 @@
+"""SPEC §11 interrupting rollouts, host side (no GPU): the header and every build carry scg_rollout_interrupt and
+SCG_ROLLOUT_TERM_INTERRUPTED, a null ctx is refused before anything else, ScgContext.rollout refuses bad arguments before any
+library call, and EpisodeStats / Trajectory summaries show interrupts only where there are any."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "scg_abi.h")
+
+
+def test_header_declares_the_entry_point_and_code():
+    src = open(HEADER).read()
+    assert re.search(r"int\s+scg_rollout_interrupt\s*\(", src)
+    assert "#define SCG_ROLLOUT_TERM_INTERRUPTED 5u" in src
+    assert "#define SCG_ABI_VERSION 5" in src
+    decl = re.search(r"int\s+scg_rollout_interrupt\s*\(([^;]*)\);", src).group(1)
+    assert "int32_t *interrupts" in decl and "const scg_record *rec" in decl
+
+
+def test_every_build_exports_the_entry_point():
+    from skill_chaining_with_graphs_amd import _lib
+    assert _lib.ROLLOUT_TERM_INTERRUPTED == 5
+    assert "scg_rollout_interrupt" in _lib.EXPORTED_SYMBOLS
+    for blk in _lib.BLOCK_ENVS_BUILDS:
+        path = _lib.lib_path(blk)
+        assert os.path.exists(path), f"{path} not built"
+        assert hasattr(C.CDLL(path), "scg_rollout_interrupt"), path
+
+
+def test_null_ctx_is_refused_first():
+    from skill_chaining_with_graphs_amd import _lib
+    from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
+    from skill_chaining_with_graphs_amd.trajectory import Trajectory
+    lib = _lib.load(256)
+    tr = Trajectory(4, 3)
+    rec = tr.c_struct()
+    p = C.c_void_p(tr.x.data_ptr())                         # any non-null address: nothing is launched
+    es = EpisodeStats(2, 4)
+    st = es.c_struct()
+    intr = C.c_void_p(es.interrupts.data_ptr())
+    # a null ctx wins over every other fault: bad flags, BEGIN with BEGIN_AT, n_steps out of range, null arrays
+    for flags, n_steps, arrays in ((0, 2, [p] * 13), (0x80, 2, [p] * 13),
+                                   (_lib.ROLLOUT_BEGIN | _lib.ROLLOUT_BEGIN_AT, 2, [p] * 13),
+                                   (0, _lib.ROLLOUT_MAX_STEPS + 1, [p] * 13), (0, 2, [None] * 13)):
+        args = arrays + [C.c_uint32(0b10), C.c_uint64(0), C.c_int32(n_steps), C.c_uint32(flags), C.byref(st), intr,
+                         C.byref(rec), None]
+        assert lib.scg_rollout_interrupt(None, *args) == -1
+        assert lib.scg_last_error(None).decode() == "scg_rollout_interrupt: null ctx"
+
+
+class _StubCtx:
+    """Just enough of an ScgContext for rollout()'s own checks; reaching the library is a failure."""
+
+    def __init__(self, n, n_vf):
+        from skill_chaining_with_graphs_amd.core import ScgContext
+        self.rollout = ScgContext.rollout.__get__(self)
+        self._chk = ScgContext._chk.__get__(self)
+        self._chk_operands = ScgContext._chk_operands.__get__(self)
+        self._chk_record = ScgContext._chk_record.__get__(self)
+        self.n_envs, self.n_vf, self.device = n, n_vf, torch.device("cpu")
+
+    def _call(self, name, *a):
+        raise AssertionError(f"the library was called: {name}")
+
+    def _stream(self):
+        return None
+
+
+def _operands(n, n_vf):
+    from skill_chaining_with_graphs_amd._lib import CLF_STRIDE, NUM_ACTIONS, NUM_FEATURES
+    from skill_chaining_with_graphs_amd.core import EnvState
+    st = object.__new__(EnvState)
+    st.n = n
+    for f, dt, k in (("x", torch.float32, 1), ("y", torch.float32, 1), ("vx", torch.float32, 1), ("vy", torch.float32, 1),
+                     ("option_id", torch.int32, 1), ("opt_steps", torch.int32, 1), ("ep_steps", torch.int32, 1),
+                     ("qcache", torch.float32, NUM_ACTIONS), ("action", torch.uint8, 1), ("reward", torch.float32, 1),
+                     ("done", torch.uint8, 1)):
+        setattr(st, f, torch.zeros(k * n, dtype=dt))
+    W = torch.zeros(n_vf * NUM_ACTIONS * NUM_FEATURES)
+    clf = torch.zeros(n_vf * CLF_STRIDE)
+    return st, W, clf
+
+
+def test_rollout_refuses_bad_arguments_before_the_library():
+    from skill_chaining_with_graphs_amd import ScgError, _lib
+    from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
+    from skill_chaining_with_graphs_amd.trajectory import Trajectory
+    n, n_vf = 8, 3
+    ctx = _StubCtx(n, n_vf)
+    st, W, clf = _operands(n, n_vf)
+    stats = EpisodeStats(n_vf, n)
+    bad = [
+        dict(n_steps=2, begin=True, begin_at=True),                             # BEGIN with BEGIN_AT
+        dict(n_steps=0),                                                        # n_steps = 0 without a begin
+        dict(n_steps=_lib.ROLLOUT_MAX_STEPS + 1),                               # n_steps out of range
+        dict(n_steps=-1, begin=True),
+        dict(n_steps=2, one_episode=True, stats=None),                          # ONE_EPISODE without `finished`
+        dict(n_steps=2, interrupts=torch.zeros(n_vf * n, dtype=torch.int64)),   # interrupts of the wrong type
+        dict(n_steps=2, interrupts=torch.zeros((n_vf - 1) * n, dtype=torch.int32)),   # ... or size
+        dict(n_steps=2, record=Trajectory(4, 2, first=6)),                      # record window beyond the envs
+        dict(n_steps=2, record=Trajectory(4, 2), begin=True),                   # too few rows for the begin row + 2 steps
+        dict(n_steps=2, stats=EpisodeStats(n_vf, n + 1)),                       # stats of another size
+    ]
+    for kw in bad:
+        kw = dict(kw)
+        kw.setdefault("stats", stats)
+        with pytest.raises(ScgError):
+            ctx.rollout(st, W, clf, 0b110, 0, interrupt=True, **kw)
+    with pytest.raises(ScgError):                                               # interrupts belong to an interrupting rollout
+        ctx.rollout(st, W, clf, 0b110, 0, 2, stats, interrupts=torch.zeros(n_vf * n, dtype=torch.int32))
+    with pytest.raises(AssertionError, match="library was called: scg_rollout_interrupt"):   # well-formed: on to the library
+        ctx.rollout(st, W, clf, 0b110, 0, 2, stats, interrupt=True)
+
+
+def _stats():
+    from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
+    s = EpisodeStats(3, 4)
+    s.episodes.copy_(torch.tensor([1, 1, 0, 2], dtype=torch.int32))
+    s.goals.copy_(torch.tensor([1, 0, 0, 1], dtype=torch.int32))
+    s.len_sum.copy_(torch.tensor([10, 60, 0, 30], dtype=torch.int32))
+    s.ret_sum.copy_(torch.tensor([9990.0, -300.0, 0.0, 9000.5], dtype=torch.float64))
+    s.vf_steps.copy_(torch.tensor([[5, 60, 7, 20], [5, 0, 0, 10], [0, 0, 3, 0]], dtype=torch.int32))
+    s.entries.copy_(torch.tensor([[0, 0, 0, 0], [1, 0, 0, 2], [0, 0, 1, 0]], dtype=torch.int32))
+    return s
+
+
+PLAIN_KEYS = ["episodes", "success_rate", "mean_return", "mean_length", "steps_share", "entries", "declines", "successes"]
+
+
+def test_episode_stats_summary_with_and_without_interrupts():
+    from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
+    s = _stats()
+    plain = s.summary()
+    assert list(plain) == PLAIN_KEYS                          # the existing summary keeps its keys, in order
+    assert list(s.per_env()) == list(EpisodeStats.FIELDS)
+    assert "interrupts" not in EpisodeStats.FIELDS            # not a scg_rollout_stats member
+    s.interrupts.copy_(torch.tensor([[0, 0, 0, 0], [2, 0, 0, 5], [0, 0, 1, 0]], dtype=torch.int32))
+    assert s.summary() == plain                               # counted, but not an interrupting evaluation
+    s.interrupting = True
+    r = s.summary()
+    assert list(r) == PLAIN_KEYS + ["interrupts"]
+    assert r["interrupts"] == [0, 7, 1]
+    assert {k: v for k, v in r.items() if k != "interrupts"} == plain
+    assert list(s.per_env()) == list(EpisodeStats.FIELDS) + ["interrupts"]
+    s.zero_()
+    assert not s.interrupting and int(s.interrupts.abs().sum()) == 0 and "interrupts" not in s.summary()
+
+
+def _launch(rows, n, cols):
+    """A hand-made launch: cols maps a field to a list (per env) of row lists; len = each env's row count."""
+    from skill_chaining_with_graphs_amd.trajectory import Trajectory
+    out = {"len": torch.tensor([len(cols["vf"][r]) for r in range(n)], dtype=torch.int32)}
+    for f in Trajectory.FIELDS:
+        a = torch.full((rows, n), 77, dtype=Trajectory.DTYPES[f])
+        for r in range(n):
+            v = cols.get(f, [[0] * len(cols["vf"][r])] * n)[r]
+            if v:
+                a[: len(v), r] = torch.tensor(v, dtype=Trajectory.DTYPES[f])
+        out[f] = a
+    return out
+
+
+def test_trajectory_with_interrupted_rows():
+    from skill_chaining_with_graphs_amd.trajectory import TERMS, Trajectory
+    assert TERMS[5] == "INTERRUPTED"
+    tr = Trajectory(2, 7, n_vf=3)
+    # env 0: begin row straight into option 1, interrupted on its second step with option 2 as the next candidate (-2); two
+    # root steps; the re-offer enters option 2, which succeeds
+    # env 1: begin row, a root step, option 2 for one step, interrupted with no candidate (option_id 0), then the goal
+    tr.append(_launch(7, 2, {
+        "vf":        [[0, 1, 1, 0, 0, 2, 2], [0, 0, 2, 0, 0]],
+        "option_id": [[1, 1, -2, -2, 2, 2, 0], [0, 2, 0, 0, 0]],
+        "term":      [[0, 0, 5, 0, 0, 0, 1], [0, 0, 5, 0, 0]],
+        "done":      [[2, 0, 0, 0, 0, 0, 0], [2, 0, 0, 0, 1]],
+        "action":    [[255, 1, 2, 3, 0, 4, 4], [255, 2, 2, 1, 1]],
+    }))
+    assert tr.segments(0) == [
+        {"vf": 0, "start": 0, "end": 0, "steps": 1, "term": 0, "done": 0},
+        {"vf": 1, "start": 1, "end": 2, "steps": 2, "term": 5, "done": 0},
+        {"vf": 0, "start": 3, "end": 4, "steps": 2, "term": 0, "done": 0},
+        {"vf": 2, "start": 5, "end": 6, "steps": 2, "term": 1, "done": 0},
+    ]
+    assert tr.describe(0) == "root×1 → 1×2 INTERRUPTED → root×2 → 2×2 SUCCESS"
+    assert tr.describe(1) == "root×2 → 2×1 INTERRUPTED → root×2 EPISODE_END(goal)"
+    s = tr.summary()
+    assert len(s["term_hist"][0]) == 5                          # term_hist keeps codes 0 .. 4
+    assert s["term_hist"][1] == [0, 0, 0, 0, 0] and s["term_hist"][2] == [0, 1, 0, 0, 0]
+    assert s["interrupted"] == [0, 1, 1]
+    assert s["segments"] == [4, 1, 2]
+    assert s["declined_rows"] == 2 and s["episodes"] == 1 and s["goals"] == 1
+
+
+def test_trajectory_summary_keeps_its_shape_without_interrupts():
+    from skill_chaining_with_graphs_amd.trajectory import Trajectory
+    tr = Trajectory(1, 4, n_vf=2)
+    tr.append(_launch(4, 1, {"vf": [[0, 1, 1]], "term": [[0, 0, 3]], "action": [[255, 0, 0]], "done": [[2, 0, 0]]}))
+    s = tr.summary()
+    assert list(s) == ["segments", "mean_steps", "term_hist", "declined_rows", "episodes", "goals", "goal_rate"]
+    assert s["term_hist"] == [[1, 0, 0, 0, 0], [0, 0, 0, 1, 0]]
+    assert math.isnan(Trajectory(1, 2).summary()["goal_rate"]) and "interrupted" not in Trajectory(1, 2).summary()
+    assert np.array_equal(tr.per_env(0)["term"], np.array([0, 0, 3], np.uint8))

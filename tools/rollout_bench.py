@@ -3,9 +3,11 @@
 Root + 5 options (chain classifiers, all enabled), bench-like weights (std 1e-3), 4096 and 65 536 envs, K = 64. Each side is
 warmed up and synchronised, and the two are timed alternately (rounds of rollout, step loop, rollout, ...); the line per size
 gives the median over the rounds. --record adds rollouts that record every step (SPEC §10) of all envs (`all`) or of the
-first N envs (`N`), timed in the same alternation (`none` is the plain rollout, always timed).
+first N envs (`N`), timed in the same alternation (`none` is the plain rollout, always timed). --interrupt adds interrupting
+rollouts (SPEC §11, scg_rollout_interrupt) on a state of their own, timed in the same alternation.
 
     python tools/rollout_bench.py [--sizes 4096 65536] [--k 64] [--rounds 7] [--epw 2 4 8 16 32] [--record none 1024 all]
+                                  [--interrupt]
 """
 import argparse
 import json
@@ -53,7 +55,7 @@ def _time(fn, reps):
     return (time.perf_counter() - t0) / reps
 
 
-def bench(n, k, rounds, n_opt=5, epw=None, record=()):
+def bench(n, k, rounds, n_opt=5, epw=None, record=(), interrupt=False):
     m = scg.load_map("pinball_simple")
     ctx = ScgContext(n, n_opt, m, device=0, seed=7, epsilon=0.05, max_episode_steps=2000)
     mask = ((1 << (n_opt + 1)) - 1) & ~1
@@ -86,15 +88,25 @@ def bench(n, k, rounds, n_opt=5, epw=None, record=()):
         ctx.rollout(r[1]["st"], W, clf, mask, r[1]["t"], k, record=r[2])
         r[1]["t"] += k
 
+    ist = {"st": _state(ctx, m, n), "t": 0, "intr": torch.zeros((n_opt + 1) * n, dtype=torch.int32, device=ctx.device)}
+
+    def roll_int():
+        ctx.rollout(ist["st"], W, clf, mask, ist["t"], k, interrupt=True, interrupts=ist["intr"])
+        ist["t"] += k
+
     roll(); loop(); roll(); loop()                        # warm-up (first launches, allocator, code objects)
     for r in recs:
         roll_rec(r); roll_rec(r)
-    r_us, s_us, rec_us = [], [], {r[0]: [] for r in recs}
+    if interrupt:
+        roll_int(); roll_int()
+    r_us, s_us, rec_us, int_us = [], [], {r[0]: [] for r in recs}, []
     for _ in range(rounds):
         r_us.append(_time(roll, 3) * 1e6 / k)
         s_us.append(_time(loop, 3) * 1e6 / k)
         for r in recs:
             rec_us[r[0]].append(_time(lambda: roll_rec(r), 3) * 1e6 / k)
+        if interrupt:
+            int_us.append(_time(roll_int, 3) * 1e6 / k)
     r, s = float(np.median(r_us)), float(np.median(s_us))
     out = {"n_envs": n, "k": k, "epw": epw or "auto", "options": n_opt, "rollout_us_per_step": round(r, 2), "step_loop_us_per_step": round(s, 2),
            "speedup": round(s / r, 2), "rollout_rounds_us": [round(v, 2) for v in r_us],
@@ -104,6 +116,12 @@ def bench(n, k, rounds, n_opt=5, epw=None, record=()):
         out[f"record_{label}_us_per_step"] = round(med, 2)
         out[f"record_{label}_cost_pct"] = round(100.0 * (med / r - 1.0), 1)
         out[f"record_{label}_rounds_us"] = [round(x, 2) for x in v]
+    if interrupt:
+        med = float(np.median(int_us))
+        out["interrupt_us_per_step"] = round(med, 2)
+        out["interrupt_cost_pct"] = round(100.0 * (med / r - 1.0), 1)
+        out["interrupt_rounds_us"] = [round(x, 2) for x in int_us]
+        out["interrupts_per_env_step"] = round(float(ist["intr"].sum()) / (ist["t"] * n), 4)
     return out
 
 
@@ -116,13 +134,14 @@ def main():
                     help="also time the rollout at these pinned launch geometries (envs per wave: 2, 4, 8, 16, 32)")
     ap.add_argument("--record", nargs="+", default=["none"],
                     help="also time recorded rollouts: `all` envs or the first N envs (`none`: the plain rollout only)")
+    ap.add_argument("--interrupt", action="store_true", help="also time interrupting rollouts (SPEC §11)")
     a = ap.parse_args()
     rec = [r for r in a.record if r != "none"]
     for r in rec:
         if r != "all" and not r.isdigit():
             ap.error(f"--record takes none, all or an env count, not {r}")
     for n in a.sizes:
-        print(json.dumps(bench(n, a.k, a.rounds, record=rec)), flush=True)
+        print(json.dumps(bench(n, a.k, a.rounds, record=rec, interrupt=a.interrupt)), flush=True)
         for epw in a.epw or []:
             print(json.dumps(bench(n, a.k, a.rounds, epw=epw)), flush=True)
 

@@ -7,9 +7,11 @@ checkpoint saved with SkillChainingAgent.save (--load; the map, env count and op
 episode, e.g. `root×12 → 3×40 SUCCESS → 2×31 SUCCESS → 1×9 EPISODE_END(goal)` (the count includes the begin row; a declined
 offer stays in the root's run; `out` counts the episode's rows with a negative option id: steps that end outside an option
 whose set holds the next state, declined by the value gate or not re-offered yet), then Trajectory.summary(). --out writes every row to an .npz
-(Trajectory.to_numpy(): the fields concatenated over episodes, `offsets` per episode).
+(Trajectory.to_numpy(): the fields concatenated over episodes, `offsets` per episode). --interrupt records interrupting
+episodes (SPEC §11): a running option is cut short where the root's value is higher, shown as `INTERRUPTED`.
 
     python tools/trajectories.py [--envs 8192] [--options 5] [--seed 1] [--episodes 64] [--load ckpt.pt] [--out traj.npz]
+                                [--interrupt]
 """
 import argparse
 import json
@@ -29,11 +31,12 @@ ap.add_argument("--warm", type=int, default=3000); ap.add_argument("--after", ty
 ap.add_argument("--episodes", type=int, default=64); ap.add_argument("--free-starts", action="store_true")
 ap.add_argument("--load", default=None); ap.add_argument("--out", default=None)
 ap.add_argument("--print", type=int, default=32, help="episode lines to print")
+ap.add_argument("--interrupt", action="store_true", help="interrupting episodes (SPEC §11)")
 a = ap.parse_args()
 HP = dict(alpha=0.02, epsilon=0.05, gamma=0.99, max_episode_steps=2000, max_option_steps=200, r_option_success=0.0,
           update_count_floor=a.envs // 16, reoffer_period=4)
 print(f"# trajectories map {a.map} envs {a.envs} options {a.options} seed {a.seed} warm {a.warm} after {a.after} "
-      f"episodes {a.episodes} free_starts {a.free_starts} load {a.load} hparams {HP}", flush=True)
+      f"episodes {a.episodes} free_starts {a.free_starts} load {a.load} interrupt {a.interrupt} hparams {HP}", flush=True)
 ag = SkillChainingAgent(a.map, a.envs, a.options, seed=a.seed, **HP)
 if a.load:
     ag.load(a.load)
@@ -48,7 +51,7 @@ states = None
 if a.free_starts:
     pos = ag.map.sample_free(a.episodes, np.random.default_rng(a.seed))
     states = (pos[:, 0], pos[:, 1])
-tr, ev = ag.record_episodes(n_episodes=a.episodes, states=states, seed=a.seed)
+tr, ev = ag.record_episodes(n_episodes=a.episodes, states=states, seed=a.seed, interrupt=a.interrupt)
 print("evaluate", json.dumps({k: ([round(x, 4) for x in v] if isinstance(v, list) else round(v, 4)) for k, v in ev.items()}),
       flush=True)
 for i in range(min(a.print, tr.n)):
