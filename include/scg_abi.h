@@ -67,6 +67,10 @@ typedef struct {
 /* flags for scg_step */
 #define SCG_STEP_LEARN 1u        /* accumulate the TD gradient (otherwise act + physics + qcache only) */
 #define SCG_STEP_APPLY 2u        /* apply it to W in the same call (single-rank path) */
+#define SCG_STEP_INTERRUPT 4u    /* SPEC §12, with SCG_STEP_LEARN only: an option that would go on is interrupted when max_a Q_o(s_next, a) <
+                                  * max_a Q_0(s_next, a); its update item then bootstraps from the root's max, and the env runs the root next
+                                  * (option_id -c or 0, opt_steps 0, qcache = Q_0(s_next, .)). Without SCG_STEP_LEARN: SCG_ERR_INVALID, nothing
+                                  * is launched (acting-only interruption is scg_rollout_interrupt) */
 
 int scg_abi_version(void);
 int scg_block_envs(void);            /* SPEC §5 block size this library was built with (one 16-wavefront workgroup per block): 256 for libscg_hip.so;

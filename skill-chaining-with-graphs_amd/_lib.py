@@ -17,6 +17,7 @@ CLF_STRIDE = 8
 
 STEP_LEARN = 1
 STEP_APPLY = 2
+STEP_INTERRUPT = 4   # include/scg_abi.h SCG_STEP_INTERRUPT: SPEC §12, the interrupting learner (with STEP_LEARN only)
 ROLLOUT_BEGIN = 1          # include/scg_abi.h SCG_ROLLOUT_*
 ROLLOUT_ONE_EPISODE = 2
 ROLLOUT_BEGIN_AT = 4

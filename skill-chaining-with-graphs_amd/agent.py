@@ -24,7 +24,8 @@ from .pinball import PinballDomain
 
 class SkillChainingAgent:
     def __init__(self, pmap, n_envs: int, n_options: int = 0, *, device: int = 0, seed: int = 0,
-                 env_id_base: int = 0, group=None, ordered_sum: bool = False, transport: str = "collective", **hparams):
+                 env_id_base: int = 0, group=None, ordered_sum: bool = False, transport: str = "collective",
+                 interrupt_learning: bool = False, **hparams):
         # transport (shared weights only): "collective" = a torch.distributed collective per learning step-batch; "peer" = the
         # ranks of one node read each other's operands through HIP IPC and sum them in rank order on the device
         if transport not in ("collective", "peer"):
@@ -51,6 +52,9 @@ class SkillChainingAgent:
         self._slots = None                     # rank of the run, reproduced by the oracle) instead of an all-reduce (exact for two ranks)
         self.allreduce_timing = None  # see time_allreduce()
         self.transport = transport
+        # SPEC §12: learning step-batches interrupt options (settable between steps; not a part of state_dict(), like the
+        # hyper-parameters). Acting-only step-batches never interrupt: evaluate(interrupt=True) does that for acting
+        self.interrupt_learning = bool(interrupt_learning)
         if transport == "peer":
             _dist.exchange_peer_handles(self.ctx, group)
         self.domain = PinballDomain(self.ctx)
@@ -228,14 +232,17 @@ class SkillChainingAgent:
 
     # ------------------------------------------------------------------ the hot path
     def step_batch(self, learn: bool = True) -> None:
-        """One fused step-batch over all envs (act, physics, options, features, Q, TD, update)."""
+        """One fused step-batch over all envs (act, physics, options, features, Q, TD, update). A learning step-batch interrupts
+        options when `interrupt_learning` is set (SPEC §12); an acting-only one (learn=False) never does — evaluate(interrupt=True)
+        is the acting counterpart."""
         shared = self.group is not None and learn
         if shared and self.transport == "peer":
             self._step_batch_peer()
             return
         if shared:
             gp = self.ctx.grad_packed()                  # G and the update counts: ONE all-reduce operand
-        self.ctx.step(self.state, self.W, self.clf, self.enabled_mask, self.t, learn=learn, apply=not shared)
+        self.ctx.step(self.state, self.W, self.clf, self.enabled_mask, self.t, learn=learn, apply=not shared,
+                      interrupt=learn and self.interrupt_learning)
         if shared:
             timing = self.allreduce_timing
             sample = timing is not None and (self.t % timing["every"]) == 0
@@ -261,7 +268,8 @@ class SkillChainingAgent:
     def _step_batch_peer(self) -> None:
         """A learning step-batch over the peer transport: the step leaves the operand in this rank's peer region, then ONE
         exchange call publishes it, waits for every rank's and applies their rank-order sum (no collective, no host wait)."""
-        self.ctx.step(self.state, self.W, self.clf, self.enabled_mask, self.t, learn=True, apply=False)
+        self.ctx.step(self.state, self.W, self.clf, self.enabled_mask, self.t, learn=True, apply=False,
+                      interrupt=self.interrupt_learning)
         timing = self.allreduce_timing
         sample = timing is not None and (self.t % timing["every"]) == 0
         if sample:

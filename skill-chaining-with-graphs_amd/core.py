@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (CLF_STRIDE, MAX_OPTIONS, NUM_ACTIONS, NUM_FEATURES, STEP_APPLY, STEP_LEARN, ScgConfig,
+from ._lib import (CLF_STRIDE, MAX_OPTIONS, NUM_ACTIONS, NUM_FEATURES, STEP_APPLY, STEP_INTERRUPT, STEP_LEARN, ScgConfig,
                    ScgError)
 from .maps import PinballMap
 
@@ -105,8 +105,9 @@ class ScgContext:
                    c.max_episode_steps, c.max_option_steps, c.update_count_floor, c.reoffer_period)
 
     # ------------------------------------------------------------------ fused step-batch
-    def _step_flags(self, learn: bool, apply: bool) -> int:
-        return (STEP_LEARN if learn else 0) | (STEP_APPLY if (learn and apply) else 0)
+    def _step_flags(self, learn: bool, apply: bool, interrupt: bool = False) -> int:
+        # (interrupt is passed on as given: without learn the library refuses it, SPEC §12)
+        return (STEP_LEARN if learn else 0) | (STEP_APPLY if (learn and apply) else 0) | (STEP_INTERRUPT if interrupt else 0)
 
     def _chk_operands(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor) -> None:
         """The env state, weight and classifier tensors step() and rollout() hand to the library."""
@@ -122,7 +123,10 @@ class ScgContext:
         self._chk(clf, f32, self.n_vf * CLF_STRIDE, "clf")
 
     def step(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t: int,
-             learn: bool = True, apply: bool = True) -> None:
+             learn: bool = True, apply: bool = True, interrupt: bool = False) -> None:
+        """One fused step-batch (SPEC §1.3-§5). `interrupt` (learning steps only; with learn=False it raises ScgError): SPEC §12's
+        interrupting learner — an option that would go on stops where the root's value at the next state is higher, and its
+        update item bootstraps from the root's value."""
         # the validated, pre-marshalled pointer arguments of the last call are reused while the same tensors come back
         # (one step is two kernel launches: the host side of a call matters in short runs)
         # (the key holds every tensor's storage address, not only the Python ids: `.data =` / `set_()` on the same object
@@ -132,12 +136,12 @@ class ScgContext:
                st.action.data_ptr(), st.reward.data_ptr(), st.done.data_ptr(), W.data_ptr(), clf.data_ptr())
         cached = getattr(self, "_step_args", None)
         if cached is not None and cached[0] == key:
-            flags = self._step_flags(learn, apply)
+            flags = self._step_flags(learn, apply, interrupt)
             _lib.check(self._step_fn(self._ctx, *cached[1], C.c_uint32(enabled_mask), C.c_uint64(t), C.c_uint32(flags),
                                      self._stream()), self._ctx, "scg_step")
             return
         self._chk_operands(st, W, clf)
-        flags = self._step_flags(learn, apply)
+        flags = self._step_flags(learn, apply, interrupt)
         if st is not getattr(self, "_last_state", None):      # another state object (its memory may be recycled)
             self.invalidate_order()
             self._last_state = st

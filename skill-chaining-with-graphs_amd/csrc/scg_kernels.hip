@@ -1451,6 +1451,8 @@ int scg_step(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *opti
         return fail(c, SCG_ERR_INVALID, "scg_step: null array argument");
     if (c->peer_n && (flags & SCG_STEP_LEARN) && (flags & SCG_STEP_APPLY))
         return fail(c, SCG_ERR_INVALID, "scg_step: SCG_STEP_APPLY with a peer region open (the update is scg_peer_exchange_apply's)");
+    if ((flags & SCG_STEP_INTERRUPT) && !(flags & SCG_STEP_LEARN))
+        return fail(c, SCG_ERR_INVALID, "scg_step: SCG_STEP_INTERRUPT without SCG_STEP_LEARN (acting-only interruption is scg_rollout_interrupt)");
     SCG_CHECK_ASYNC(c);
     SCG_ON_DEVICE(c, "scg_step");
     if (c->arm_bits) {
@@ -1511,7 +1513,10 @@ int scg_step(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *opti
         c->prof_used += 2;
         SCG_HIP(c, hipEventRecord(ev0, s));
     }
-    hipLaunchKernelGGL(td_kernel<MODE_FUSED>, dim3(c->nblk), dim3(THREADS), 0, s, A);
+    if (flags & SCG_STEP_INTERRUPT)                 // SPEC §12: the interrupting learner (only the targets and results of interrupted envs differ)
+        hipLaunchKernelGGL(td_kernel<MODE_FUSED_INT>, dim3(c->nblk), dim3(THREADS), 0, s, A);
+    else
+        hipLaunchKernelGGL(td_kernel<MODE_FUSED>, dim3(c->nblk), dim3(THREADS), 0, s, A);
     SCG_HIP(c, hipGetLastError());
     if (ev1) SCG_HIP(c, hipEventRecord(ev1, s));
     // results reach the caller's arrays through the commit workgroups of the reduce launch (or a commit launch)

@@ -87,9 +87,10 @@ constexpr int M_C_TOP = 92;         // waves without envs have put the edge and 
 constexpr int M_INTS = 128;
 static_assert(LIST_WAVES * 16 <= M_GROUPS && P_WAVES <= 4, "s_misc layout");
 
-enum { MODE_FUSED = 0, MODE_TRANS = 1, MODE_QVAL = 2 };
+enum { MODE_FUSED = 0, MODE_TRANS = 1, MODE_QVAL = 2, MODE_FUSED_INT = 3 };   // MODE_FUSED_INT: the fused step with SPEC §12's interruption
 constexpr unsigned IA_ENTERING = 0x40u;     // s_ia bit 6: the env is about to ENTER option s_on (SPEC §4.2 value-gated entry)
 constexpr unsigned OREC_DECLINED = 0x7fc0deadu;   // result line word [3].y: the env stays with the root after all (commit_row: option 0, the root's Q values)
+constexpr unsigned IC_KEEP = 0x80u;         // s_ic (interrupting step only, SPEC §12): the env's option goes on; bits 0..2: §4.2's candidate as if it had ended
 // Tuning constants, settled by round-4 A/Bs (tools/ab_bench.py; to measure one again, edit it in a worktree: tools/ab_trees.py). The
 // variants measured and dropped in round 4 — evaluation-only value functions on the vector pipe or behind the passes, static deals
 // of E's and U1's units, E rebalancing — are kept as profiles/r04_dropped_kernel_variants.diff with their numbers in
@@ -167,9 +168,14 @@ __device__ __attribute__((noinline)) void stage_w_cold(const float *Wk, float *s
 
 template <int MODE>
 __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
+    // FUSED: the fused step-batch, td_kernel<MODE_FUSED> or — INT — td_kernel<MODE_FUSED_INT>, SPEC §12's interrupting learner (scg_step
+    // with SCG_STEP_INTERRUPT). Every branch of the rule sits under `if constexpr (INT)`: the other instantiations keep their code.
+    constexpr bool INT = MODE == MODE_FUSED_INT, FUSED = MODE == MODE_FUSED || INT;
     // STATIC LDS: its addresses are compile-time literals. As dynamic LDS (extern __shared__[]) every address was base symbol + offset
     // — an s_add the compiler hoisted out of the pass loop and parked in spilled SGPRs (109 of them, 172 SGPR spills; 126 now): +0.65 %
-    __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
+    // (INT: one more byte per position behind the map, s_ic)
+    static_assert(LDS_BYTES + BLOCK_ENVS <= 160 * 1024, "LDS budget of the interrupting step");
+    __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES + (INT ? BLOCK_ENVS : 0)];
     float *s_R = reinterpret_cast<float *>(smem + OFF_R);
     float *s_s = s_R + R_S;                                             // [8][B]: s then sn   (region R, phases P and Z)
     float *s_edges = s_R + R_EDGES;                                     // [n_edges][8]        (region R, phase P)
@@ -191,6 +197,8 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     float *s_W = s_R;                                                   // region W = the head of region R: W_A then W_B
     float *s_clf = reinterpret_cast<float *>(smem + OFF_CLF);
     int *s_misc = reinterpret_cast<int *>(smem + OFF_MISC);
+    uint8_t *s_ic = reinterpret_cast<uint8_t *>(smem + LDS_BYTES);     // INT only: IC_KEEP | the candidate c of SPEC §12 (0: the option ended)
+    (void)s_ic;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.x;
@@ -377,7 +385,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     int kB = -1, mB = 0;
     auto decide_b = [&]() {
         kB = -1; mB = 0;
-        if (MODE != MODE_FUSED || nb <= 0) return;
+        if (!FUSED || nb <= 0) return;
         const int k0 = s_ot[0];
         if (k0 < 1 || k0 >= A.n_vf || ((A.gest >> k0) & 1u)) return;
         int m = 0;
@@ -414,7 +422,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     };
     // With learning on, waves 8..15 ("helpers") have nothing to do in phase P: they stage W_0 (and W_kB), take Z_d^1 of
     // the entry states, build the root's update list and run U1 of both value functions under it.
-    const bool helpers = MODE == MODE_FUSED && A.learn && A.k_hi >= 0;
+    const bool helpers = FUSED && A.learn && A.k_hi >= 0;
 
     // ------------------------------------------------------------------ kernel start (round 5)
     // The first round trips of a launch are cold ones (4-6k cycles each). The old start — edge table -> barrier -> perm -> state
@@ -426,7 +434,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     block_lds_sync();
     SCG_LITE(1);                                            // behind the start barrier
     int e_pre = e0 + tid;                                   // env waves: this position's env
-    if (MODE == MODE_FUSED) {
+    if (FUSED) {
         if (wave < P_WAVES) {
             if (tid < nb && A.perm) e_pre = A.perm[e0 + tid];
         } else {
@@ -446,7 +454,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         const int i = tid;
         const bool valid = i < nb;
         const int e = e_pre;
-        if (MODE == MODE_FUSED) {
+        if (FUSED) {
             uint32_t u[4] = {0u, 0u, 0u, 0u};
             int a = NACT - 1, ep0 = 0, o = 0, o_in = 0, osteps = 0;
             float sx = 0.5f, sy = 0.5f, svx = 0.0f, svy = 0.0f;
@@ -539,6 +547,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 const int stay = reoffer_stay(keep, cand, dn, o_in, A.t, (uint64_t)(A.env_base + e), A.reoffer_mask);
                 const int on = stay ? 0 : cand;
                 s_on[i] = (uint8_t)on;
+                if constexpr (INT) s_ic[i] = (uint8_t)(keep ? IC_KEEP | (unsigned)select_option(A.parents, inB, A.enabled) : 0u);      // SPEC §12: c
                 s_gs[i] = (uint8_t)inS; s_ia[i] = (uint8_t)((inA & 0x3Eu) | (goal ? 1u : 0u) | ((!keep && on >= 1) ? IA_ENTERING : 0u));
                 {   // bit masks of the VFs with items / update items here: OR over the wave's lanes first, then one LDS atomic per wave
                     const unsigned pm = (1u << o) | (1u << (on & 31)) | inS, um = (1u << o) | inS;
@@ -579,6 +588,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 hkey = (e >> 8) * 8 + on;                             // next step's counting sort: (row of 256 envs, option id; a declined entry is moved to 0 by gate())
             } else {
                 s_on[i] = 255; s_gs[i] = 0; s_ia[i] = 0;
+                if constexpr (INT) s_ic[i] = 0;
             }
             if (A.hist_next) {
                 // one atomic per distinct (row, option id) of the wave instead of one per env: neighbours in the env order are
@@ -611,7 +621,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         } else {
             s_a[i] = 0; s_ot[i] = 255; s_on[i] = 255; s_gs[i] = 0; s_ia[i] = 0;
         }
-    } else if (MODE == MODE_FUSED && wave < P_POOL) {   // no envs of its own: takes its share of the physics' pair groups
+    } else if (FUSED && wave < P_POOL) {   // no envs of its own: takes its share of the physics' pair groups
         lds_await(&s_misc[M_C_PREP], P_WAVES);
         int gsum[P_WAVES + 1];
         gsum[0] = 0;
@@ -670,7 +680,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         lds_await(&s_misc[M_C_HELP], N_HELP);                                  // W_0, W_kB, Z(s) and the list are complete
         run_u1_dyn();
     }
-    else if (MODE == MODE_FUSED && wave == HELPER0) {      // acting-only steps: this wave still settles the block's option
+    else if (FUSED && wave == HELPER0) {      // acting-only steps: this wave still settles the block's option
         lds_await(&s_misc[M_C_PUBS], 64 * P_WAVES);
         decide_b();
         if (lane == 0) { s_misc[M_KB] = kB; s_misc[M_MB] = mB; }
@@ -688,19 +698,19 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             s_z1[(i * 2 + sg) * 4 + d] = sincospi_cs(d < 2 ? sv : fmaf(sv, 0.25f, 0.5f));
         }
     }
-    if (MODE == MODE_FUSED && A.k_hi >= 0) {                // the block's option, settled by wave HELPER0 before the barrier
+    if (FUSED && A.k_hi >= 0) {                // the block's option, settled by wave HELPER0 before the barrier
         kB = __builtin_amdgcn_readfirstlane(s_misc[M_KB]); mB = __builtin_amdgcn_readfirstlane(s_misc[M_MB]);
     } else { kB = -1; mB = 0; }
 
     // ------------------------------------------------------------------ phase TD (SPEC §3.1, §5) on the matrix pipe
-    const unsigned present = (MODE == MODE_FUSED) ? (unsigned)__builtin_amdgcn_readfirstlane(s_misc[M_PRESENT]) : ~0u;
-    const unsigned updm = (MODE == MODE_FUSED) ? (A.learn ? (unsigned)__builtin_amdgcn_readfirstlane(s_misc[M_UPD]) : 0u) : ~0u;
+    const unsigned present = (FUSED) ? (unsigned)__builtin_amdgcn_readfirstlane(s_misc[M_PRESENT]) : ~0u;
+    const unsigned updm = (FUSED) ? (A.learn ? (unsigned)__builtin_amdgcn_readfirstlane(s_misc[M_UPD]) : 0u) : ~0u;
     // Passes: pass 0 = the merged pass (value function A = the root — or the caller's VF in the un-fused modes — and B = the
     // block's option, if any); then one single-VF pass per other value function with update items here. Value functions
     // that only have envs ENTERING them (no update item) skip the pass machinery: see the tail of the kernel.
-    unsigned single = (MODE == MODE_FUSED && A.k_hi >= 0) ? (updm & present & ~1u & ~(kB >= 1 ? 1u << kB : 0u)) : 0u;
-    const unsigned eval_only = (MODE == MODE_FUSED && A.k_hi >= 0) ? (present & ~updm & ~1u & ~(kB >= 1 ? 1u << kB : 0u)) : 0u;
-    if (MODE == MODE_FUSED && tid < A.n_vf && A.cnts && tid != 0 && tid != kB && !((single >> tid) & 1u))
+    unsigned single = (FUSED && A.k_hi >= 0) ? (updm & present & ~1u & ~(kB >= 1 ? 1u << kB : 0u)) : 0u;
+    const unsigned eval_only = (FUSED && A.k_hi >= 0) ? (present & ~updm & ~1u & ~(kB >= 1 ? 1u << kB : 0u)) : 0u;
+    if (FUSED && tid < A.n_vf && A.cnts && tid != 0 && tid != kB && !((single >> tid) & 1u))
         A.cnts[(size_t)b * A.n_vf + tid] = 0;               // value functions without a pass here leave no slab
     const int n_pass0 = A.k_hi >= A.k_lo ? 1 : 0;
     const unsigned single0 = single;
@@ -710,7 +720,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     // single pass has just run. A declined env gets option 0 in the block's flags, the mark in its result line (commit_row then takes
     // the root's Q values the root's unit left beside the line) and its share of the next order's histogram moved to key 0.
     auto gate = [&](int kdec) {
-        if (MODE != MODE_FUSED) return;
+        if (!FUSED) return;
         int ln;                                             // (the thread id is re-made from the hardware lane counter: the kernel's own `tid`, kept
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));      //  live across the pass loop for this, is what the
         const int ti = (wave << 6) | ln;                    //  register allocator spills — see the top of the pass loop)
@@ -729,9 +739,37 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             atomicAdd(&A.hist_next[(e >> 8) * 8], 1);
         }
     };
+    // SPEC §12, the interrupting learner: an env whose option o goes on leaves it when max_a Q_o(s_next, a) < max_a Q_0(s_next, a) (a NaN
+    // on either side leaves it too). Its update item of VF o has already taken the root's max as its bootstrap (U2); here its result line is
+    // rewritten as gate() does for a declined entry — commit_row writes the root's Q values (qalt, left by the root's E unit) and the id
+    // -c (0: no candidate), where c is the candidate P worked out as if the option had ended — with opt_steps 0, and its share of the next
+    // order's histogram moves from key o to key 0. kdec < 0: the block's option kB after pass 0 (both maxima in s_maxq); kdec = k: option k's
+    // own single pass has just run (its max in s_maxq's first half, the root's saved in s_qsa's second half).
+    auto interrupt_rewrite = [&](int kdec) {
+        if constexpr (INT) {
+            int ln;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+            const int ti = (wave << 6) | ln;
+            if (ti >= nb || !(s_ic[ti] & IC_KEEP)) return;
+            const int o = s_ot[ti];
+            if (o != (kdec < 0 ? kB : kdec)) return;
+            const float mo = kdec < 0 ? s_maxq[BLOCK_ENVS + ti] : s_maxq[ti];
+            const float m0 = kdec < 0 ? s_maxq[ti] : s_qsa[BLOCK_ENVS + ti];
+            if (mo >= m0) return;
+            float *rec = reinterpret_cast<float *>(A.outrec + (size_t)(e0 + ti) * OREC);
+            rec[5] = __uint_as_float((unsigned)s_a[ti] | ((s_ic[ti] & 7u) << 16));      // the bits: action, done 0, on = c, stay 0 (the option went on)
+            rec[6] = __int_as_float(0);                                               // opt_steps
+            rec[13] = __uint_as_float(OREC_DECLINED);                                 // commit_row: the id -c and the root's Q values
+            if (A.hist_next) {
+                const int e = A.perm ? A.perm[e0 + ti] : e0 + ti;
+                atomicAdd(&A.hist_next[(e >> 8) * 8 + o], -1);
+                atomicAdd(&A.hist_next[(e >> 8) * 8], 1);
+            }
+        }
+    };
     // A hand-off poll of phase P that ran out leaves LDS data unpublished (lists, tables, the physics' results): the block goes inert —
     // no pass, no slab, counts 0 — instead of computing on them; the step as a whole is voided by the reduce launch
-    const bool blk_fail = MODE == MODE_FUSED && __builtin_amdgcn_readfirstlane(s_misc[M_FAIL]) != 0;
+    const bool blk_fail = FUSED && __builtin_amdgcn_readfirstlane(s_misc[M_FAIL]) != 0;
     if (blk_fail && tid < A.n_vf && A.cnts) A.cnts[(size_t)b * A.n_vf + tid] = 0;
     for (int pass = 0; pass < n_pass0 + MAX_VF && !blk_fail; ++pass) {
         // Opaque copies of the thread and lane ids for the pass: every per-lane address of the pass body is loop-invariant, and
@@ -747,14 +785,14 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         bool dense;                                         // E over position groups (pass 0) or over the compacted eval list
         if (pass == 0) {
             if (!n_pass0) continue;
-            kA = MODE == MODE_FUSED ? 0 : A.k_lo; kBp = kB; dense = true;
+            kA = FUSED ? 0 : A.k_lo; kBp = kB; dense = true;
         } else {
             if (!single) break;
             kA = __builtin_ctz(single); single &= single - 1; kBp = -1; dense = false;
         }
         const bool u1_done = helpers && pass == 0;          // the helper waves ran U1 and built the list under phase P
         if (pass > 0) block_lds_sync();                     // (pass 0 starts behind the barrier that ends phase P)
-        if (MODE == MODE_FUSED && pass > 0 && kA == __builtin_ctz(single0)) {      // first single pass: save the root's max_a Q_0(s_next, a) of pass 0
+        if (FUSED && pass > 0 && kA == __builtin_ctz(single0)) {      // first single pass: save the root's max_a Q_0(s_next, a) of pass 0
             if (tid < nb) s_qsa[BLOCK_ENVS + tid] = s_maxq[tid];                 // before this pass's E reuses s_maxq (s_qsa's second half: B's Q(s, a), pass 0 only)
         }
         // ---- per-env flags of the pass (SPEC §5): ev bit v = the env needs Q_v(s_next, .) (bootstrap target and/or next
@@ -767,11 +805,11 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         int at = -1;
         if ((unsigned)ft < (unsigned)nb) {
             const int ot = s_ot[ft], on = s_on[ft];
-            const bool own = (MODE == MODE_FUSED && kA == 0) || ot == kA;
-            const bool gst = MODE == MODE_FUSED && !own && ((s_gs[ft] >> kA) & 1);       // SPEC §4.4 off-policy item
+            const bool own = (FUSED && kA == 0) || ot == kA;
+            const bool gst = FUSED && !own && ((s_gs[ft] >> kA) & 1);       // SPEC §4.4 off-policy item
             up = (MODE != MODE_QVAL) && A.learn && (own || gst);
             float rk = s_r0[ft], cont = s_c0[ft];
-            if (MODE == MODE_FUSED && kA != 0) {
+            if (FUSED && kA != 0) {
                 if (ot == kA) { rk = s_ro[ft]; cont = s_co[ft]; }
                 else {                                    // as if the env ran option kA: no time-out, no selection
                     const unsigned ia = s_ia[ft];
@@ -782,7 +820,8 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 }
                 s_rk[ft] = rk; s_ck[ft] = cont;
             }
-            evA = (on == kA) || (up && cont > 0.0f) || (MODE == MODE_FUSED && kA == 0 && (s_ia[ft] & IA_ENTERING));      // (SPEC §4.2: the gate compares with the root)
+            evA = (on == kA) || (up && cont > 0.0f) || (FUSED && kA == 0 && (s_ia[ft] & IA_ENTERING));      // (SPEC §4.2: the gate compares with the root)
+            if constexpr (INT) evA = evA || (kA == 0 && (s_ic[ft] & IC_KEEP));        // (SPEC §12: ... and so does every option that goes on)
             if (kBp >= 1) evB = (on == kBp) || (ot == kBp && A.learn && s_co[ft] > 0.0f);
             at = s_a[ft];
             s_ev[ft] = (uint8_t)((evA ? 1 : 0) | (evB ? 2 : 0));
@@ -790,7 +829,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         // compacted list: single passes -> the eval items of A; pass 0 -> the envs that need Q_B but lie outside B's prefix groups
         const int pg_b = (mB + 7) >> 3;                     // position groups that hold B's prefix
         const bool cmp = dense ? (evB && (ft >> 3) >= pg_b) : evA;
-        const bool eo_pass = pass == 0 && MODE == MODE_FUSED && eval_only != 0;
+        const bool eo_pass = pass == 0 && FUSED && eval_only != 0;
         const int on_me = (unsigned)ft < (unsigned)nb ? (int)s_on[ft] : 0;
         const bool eo = eo_pass && (unsigned)ft < (unsigned)nb && ((eval_only >> (on_me & 7)) & 1u);       // this env enters an evaluation-only value function
         uint64_t me[MAX_VF];
@@ -972,8 +1011,10 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 contract_lds<E_TG>(v * W_FLOATS, B, qo, g, w4, w8, ab_lane);
                 if (out_lane && have && ((s_ev[il] >> v) & 1)) {
                     const int kv = v ? kBp : kA;
-                    if (MODE == MODE_FUSED) {             // into the env's result line; commit_row writes qcache
-                        if (kv == 0 && (s_ia[il] & IA_ENTERING)) {      // SPEC §4.2: the root's values, should the env stay with the root after all
+                    if (FUSED) {             // into the env's result line; commit_row writes qcache
+                        bool alt = kv == 0 && (s_ia[il] & IA_ENTERING);      // SPEC §4.2: the root's values, should the env stay with the root after all
+                        if constexpr (INT) alt = alt || (kv == 0 && (s_ic[il] & IC_KEEP));          // (SPEC §12: ... or leave its option)
+                        if (alt) {
                             float4 *qa = A.qalt + (size_t)(e0 + il) * 2;
                             qa[0] = make_float4(qo[0], qo[1], qo[2], qo[3]);
                             qa[1].x = qo[4];
@@ -1042,7 +1083,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
 #pragma unroll
             for (int s = 0; s < 3; ++s) accU[v][s] = zero4();
         }
-        const float *rA = (MODE == MODE_FUSED && kA != 0) ? s_rk : s_r0, *cA = (MODE == MODE_FUSED && kA != 0) ? s_ck : s_c0;
+        const float *rA = (FUSED && kA != 0) ? s_rk : s_r0, *cA = (FUSED && kA != 0) ? s_ck : s_c0;
         const int bi9 = lane_u % 9, cp9 = lane_u / 9;       // builder lanes of a chunk: (slot 9 w + bi9, second index cp9 < 6)
         // this chunk's share of every run: groups [gb[a], gb[a] + gc[a]) at slots [co[a], co[a + 1])
         auto chunk_geo = [&](int ch, int (&gb)[NACT], int (&gc)[NACT], int (&co)[NACT + 1]) {
@@ -1072,8 +1113,12 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                     const float rr = rA[il], cont = cA[il];
                     // SPEC §4.2 exit rule (single passes of an option): the option ended (continuation 0) but the episode goes on -> the
                     // root's value of where the env goes next (kept in s_qsa's second half by the first single pass)
-                    const bool boot = MODE == MODE_FUSED && kA != 0 && cont == 0.0f && s_c0[il] > 0.0f;
-                    const float target = boot ? fmaf(A.gamma, s_qsa[BLOCK_ENVS + il], rr) : (cont > 0.0f ? fmaf(cont, s_maxq[il], rr) : rr);
+                    const bool boot = FUSED && kA != 0 && cont == 0.0f && s_c0[il] > 0.0f;
+                    float target = boot ? fmaf(A.gamma, s_qsa[BLOCK_ENVS + il], rr) : (cont > 0.0f ? fmaf(cont, s_maxq[il], rr) : rr);
+                    if constexpr (INT) {                     // SPEC §12: the env's own option goes on but is interrupted -> the exit rule's bootstrap
+                        if (kA != 0 && (s_ic[il] & IC_KEEP) && s_ot[il] == kA && !(s_maxq[il] >= s_qsa[BLOCK_ENVS + il]))
+                            target = fmaf(A.gamma, s_qsa[BLOCK_ENVS + il], rr);
+                    }
                     const float d = target - s_qsa[li];
                     float2 ab[6], cd[6];
                     item_entries(s_z1 + (il * 2 + 0) * 4, cp9, ab, cd);
@@ -1084,8 +1129,11 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                     }
                     if (j < nbq) {                           // the item also updates value function B
                         const float rb = s_ro[il], cb2 = s_co[il];
-                        const float tb = (cb2 == 0.0f && s_c0[il] > 0.0f) ? fmaf(A.gamma, s_maxq[il], rb)          // (exit rule: s_maxq[il] is the root's max in pass 0)
-                                                                         : (cb2 > 0.0f ? fmaf(cb2, s_maxq[BLOCK_ENVS + il], rb) : rb);
+                        float tb = (cb2 == 0.0f && s_c0[il] > 0.0f) ? fmaf(A.gamma, s_maxq[il], rb)          // (exit rule: s_maxq[il] is the root's max in pass 0)
+                                                                   : (cb2 > 0.0f ? fmaf(cb2, s_maxq[BLOCK_ENVS + il], rb) : rb);
+                        if constexpr (INT) {                 // SPEC §12 (every item of B is an env running B)
+                            if ((s_ic[il] & IC_KEEP) && !(s_maxq[BLOCK_ENVS + il] >= s_maxq[il])) tb = fmaf(A.gamma, s_maxq[il], rb);
+                        }
                         const float db = tb - s_qsa[BLOCK_ENVS + li];
 #pragma unroll
                         for (int c = 0; c < 6; ++c)
@@ -1224,12 +1272,13 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         }
         if (pass == 0) SCG_LITE(7);                         // pass 0 done (slab stores issued)
         if (pass > 0) gate(kA);
+        if constexpr (INT) { if (pass > 0 || kB >= 1) interrupt_rewrite(pass > 0 ? kA : -1); }
     }
-    if (MODE == MODE_FUSED && n_pass0 && !blk_fail) {       // the candidates evaluated in pass 0 (their maxima are in s_maxq's second half, which
+    if (FUSED && n_pass0 && !blk_fail) {       // the candidates evaluated in pass 0 (their maxima are in s_maxq's second half, which
         if (!A.learn) block_lds_sync();                     // no later pass touches; acting-only steps: pass 0 ended behind E, without a barrier)
         gate(-1);
     }
-    if (MODE == MODE_FUSED && A.async_word) {               // a hand-off poll ran out somewhere in this block: tell the host (sticky)
+    if (FUSED && A.async_word) {               // a hand-off poll ran out somewhere in this block: tell the host (sticky)
         block_lds_sync();
         if (tid == 0 && s_misc[M_FAIL]) {
             __hip_atomic_fetch_or(A.async_word, SCG_ASYNC_STEP_HANDOFF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1237,14 +1286,14 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         }
     }
 #ifdef SCG_STAMPS_LITE
-    if (MODE == MODE_FUSED && A.stamps && lite_role >= 0 && lane == 0) {
+    if (FUSED && A.stamps && lite_role >= 0 && lane == 0) {
         unsigned long long *o = A.stamps + (size_t)blockIdx.x * STAMP_SLOTS;
 #pragma unroll
         for (int i = 1; i < 8; ++i) o[lite_role * 8 + i] += lt[i] ? lt[i] - lt[0] : 0ull;
         o[lite_role * 8] += __builtin_amdgcn_s_memtime() - lt[0];                 // [0]: the wave's whole kernel
         if (lite_role == 0) { o[32] = lite_r0; o[33] = __builtin_amdgcn_s_memrealtime(); }
     }
-    if (MODE == MODE_FUSED && A.stamps && lane == 0) {      // slots 34..41: HW_REG_HW_ID of each of the 16 waves (last launch): where the dispatcher put wave w (tools/wave_placement.py)
+    if (FUSED && A.stamps && lane == 0) {      // slots 34..41: HW_REG_HW_ID of each of the 16 waves (last launch): where the dispatcher put wave w (tools/wave_placement.py)
         unsigned hwid;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
         reinterpret_cast<unsigned *>(A.stamps + (size_t)blockIdx.x * STAMP_SLOTS + 34)[wave] = hwid;

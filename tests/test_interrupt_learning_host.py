@@ -1,0 +1,121 @@
+"""SPEC §12 interrupting learner, host side (no GPU): the header and every build carry SCG_STEP_INTERRUPT, the emulator of
+tests/interrupt_learning_model.py rebuilds sco_step's G and n_k bit for bit when nothing is interrupted (both env order layouts,
+every block size: the order and the per-block recomputation are right), its acting outputs agree with a step-by-step oracle
+emulation of §11's rule, and the Python flag plumbing."""
+import os
+
+import numpy as np
+import pytest
+
+import sc_oracle
+import interrupt_learning_model as ilm
+from ref64 import env_order_layout
+from util import HP, SCALE
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_header_and_python_carry_the_flag():
+    src = open(os.path.join(ROOT, "include", "scg_abi.h")).read()
+    assert "#define SCG_STEP_INTERRUPT 4u" in src
+    assert "#define SCG_ABI_VERSION 5" in src
+    from skill_chaining_with_graphs_amd import _lib
+    from skill_chaining_with_graphs_amd.core import ScgContext
+    assert _lib.STEP_INTERRUPT == 4 and _lib.STEP_LEARN == 1 and _lib.STEP_APPLY == 2
+    flags = ScgContext._step_flags
+    assert flags(None, True, True) == 3 and flags(None, False, True) == 0            # unchanged without interrupt
+    assert flags(None, True, True, True) == 7 and flags(None, True, False, True) == 5
+    assert flags(None, False, False, True) == 4                                      # passed on: the library refuses it
+
+
+def test_every_build_holds_the_interrupting_step_kernel():
+    from skill_chaining_with_graphs_amd import _lib
+    for blk in _lib.BLOCK_ENVS_BUILDS:
+        path = _lib.lib_path(blk)
+        assert os.path.exists(path), f"{path} not built"
+        assert b"_Z9td_kernelILi3EEv8StepArgs" in open(path, "rb").read(), path      # td_kernel<MODE_FUSED_INT>
+
+
+def _case(name, n, n_opt, block, seed, run_share, gest=0, layout=None):
+    sc_oracle.use_block_envs(block)
+    import skill_chaining_with_graphs_amd as scg
+    m = scg.load_map(name)
+    n_vf = n_opt + 1
+    mask = ((1 << n_vf) - 1) & ~1 & ~gest
+    orc = sc_oracle.Oracle(m, SCALE, n_envs=n, n_options=n_opt, seed=seed, enabled_mask=mask, n_threads=4, reoffer_period=4, **HP)
+    if gest:
+        orc.set_gestation(gest)
+    st = ilm.entry_state(m, n, n_opt, seed, run_share, HP["max_episode_steps"])
+    return orc, m, st, ilm.crossing_weights(n_vf, seed), ilm.wide_chain(m, n_opt), mask
+
+
+CASES = [
+    # map, envs, options, block, seed, share of envs running an option, gestating, layout
+    ("pinball_simple", 2048, 3, 256, 1, 0.3, 0, "chunked"),
+    ("pinball_simple", 1000, 5, 256, 2, 0.6, 0, "padded"),          # (full blocks <= runs)
+    ("pinball_maze", 1536, 4, 128, 3, 0.5, 0b10000, "chunked"),     # a gestating option's off-policy items
+    ("pinball_maze", 300, 5, 64, 4, 0.9, 0, "padded"),
+    ("pinball_simple", 1200, 3, 64, 5, 0.25, 0, "chunked"),
+]
+
+
+@pytest.fixture(autouse=True)
+def _restore_block():
+    yield
+    sc_oracle.use_block_envs(256)
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0]}-n{c[1]}-o{c[2]}-b{c[3]}")
+def test_emulator_reproduces_sco_step_without_interrupts(case):
+    orc, m, st, W, clf, mask = _case(*case)
+    layout = env_order_layout(st["option_id"], orc.n_vf, case[3])
+    assert layout == case[7]
+    gest = case[6]
+    plain = ilm.copy_state(st)
+    G, n_k = orc.step(plain, W, clf, 11, mask)
+    post, Ge, nke, info = ilm.step(orc, st, W, clf, 11, mask, gest=gest, interrupt=False, recompute=True)
+    assert info["keep"].sum() > 0
+    for f in ilm.FIELDS:
+        assert np.array_equal(post[f].view(np.uint8), plain[f].view(np.uint8)), f
+    assert np.array_equal(nke, n_k)
+    for k in range(orc.n_vf):
+        assert n_k[k] > 0, k
+        assert np.array_equal(Ge[k], G[k]), f"VF {k}: {np.sum(Ge[k] != G[k])} elements differ"
+
+
+def test_emulator_acting_equals_a_step_by_step_oracle_emulation_of_section_11():
+    """The emulator's interrupted envs, found from the physics and the classifiers, against §11's rule applied to sco_step's outputs
+    the way the §11 tests do it: kept = opt_steps went up, V_o from the option's qcache, V_0 from q_values, c from the classifiers."""
+    n, n_opt = 1500, 4
+    orc, m, st, W, clf, mask = _case("pinball_simple", n, n_opt, 256, 7, 0.5)
+    n_vf = n_opt + 1
+    parents = [int(orc.p.parents[k]) for k in range(8)]
+    total = 0
+    for t in range(30, 34):
+        post, G, n_k, info = ilm.step(orc, st, W, clf, t, mask, interrupt=True, recompute=False)
+        ref = ilm.copy_state(st)
+        orc.step(ref, W, clf, t, mask)
+        kept = (st["option_id"] >= 1) & (st["option_id"] < n_vf) & (ref["opt_steps"] == st["opt_steps"] + 1)
+        idx = np.nonzero(kept)[0]
+        s = [np.ascontiguousarray(ref[f][idx]) for f in ("x", "y", "vx", "vy")]
+        q0 = orc.q_values(*s, W[0])
+        cut = ~(ilm.vmax(ref["qcache"][:, idx]) >= ilm.vmax(q0))
+        in_n = np.zeros((8, len(idx)), bool)
+        for k in range(1, n_vf):
+            in_n[k] = orc.classifier_predict(s[0], s[1], clf[k]) != 0
+        c = ilm.candidates(in_n, mask, parents, n_vf)
+        e = idx[cut]
+        ref["option_id"][e] = -c[cut]
+        ref["opt_steps"][e] = 0
+        ref["qcache"][:, e] = q0[:, cut]
+        assert np.array_equal(np.nonzero(info["interrupted"])[0], e)
+        for f in ilm.FIELDS:
+            assert np.array_equal(post[f].view(np.uint8), ref[f].view(np.uint8)), f"t {t}: {f}"
+        total += len(e)
+        st = post
+    assert total > 0
+
+
+def test_fmaf_is_fused():
+    a, b, c = np.float32(1 + 2 ** -12), np.float32(1 - 2 ** -12), np.float32(-1)
+    assert ilm.fmaf(a, b, c) == np.float32(-2.0 ** -24)        # a*b - 1 exactly; unfused it rounds to 0
