@@ -341,6 +341,18 @@ int scg_collect_examples(scg_ctx *ctx, uint32_t event_bits, uint8_t *prev_in, in
  * (hipPointerGetAttributes: memory handed back to the DRIVER is noticed and refused with SCG_ERR_STATE; memory a caching allocator
  * such as torch's has merely recycled still reads as a device allocation and is NOT noticed) — the rule above is the contract. */
 int scg_arm_collect(scg_ctx *ctx, uint32_t event_bits, const uint8_t *prev_in, int32_t l_pos, int32_t l_neg, const int32_t *count);
+/* scg_collect_frontier: frontier collection for skill-tree growth (SPEC §13), two launches, nothing returns to the host. Nodes
+ * p = 0..n_options: node 0 is the goal (events bit 0), node p >= 1 initiation set p (events bit p). An env with ev_len >= 1
+ * hits node p when bit p of target_mask and of its events byte are set and its s_t = ring[(ev_len-1) & (ring_len-1)] lies in
+ * no initiation set of cover_mask (SPEC §4.1's z > 0 with clf row k, f32[n_vf][8]; no `known` term); it then appends its
+ * min(l_pos + l_neg, ev_len, ring_len) most recent ring states behind count[p] in node p's buffer ex_xy[n_vf][cap][2] /
+ * ex_label[n_vf][cap] (1 = one of the last l_pos states, 0 = older), in env order; what does not fit is dropped and
+ * count[p] = min(cap, count[p] + rows). An env may hit several nodes. Stateless: no prev_in, and an announced
+ * scg_arm_collect trigger is neither read nor cleared. Refused (SCG_ERR_INVALID, nothing launched): target_mask bits at or
+ * beyond n_vf, cover_mask bit 0 or bits beyond n_options, a target option outside cover_mask, cap < 1, l_pos or l_neg < 0,
+ * l_pos + l_neg < 1, a null pointer; SCG_ERR_STATE without trace buffers. target_mask = 0 appends nothing. */
+int scg_collect_frontier(scg_ctx *ctx, uint32_t target_mask, uint32_t cover_mask, const float *clf, int32_t l_pos, int32_t l_neg,
+                         float *ex_xy, uint8_t *ex_label, int32_t *count, int32_t cap, void *stream);
 
 /* Gestation (SPEC §4.4; Konidaris & Barto 2009: a new option learns off-policy before it may run). Bit k of gest_mask:
  * option k's classifier is in use (initiation / target tests, event bits) but the option is never selected; every env

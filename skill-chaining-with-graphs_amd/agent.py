@@ -22,6 +22,31 @@ from .option import Option
 from .pinball import PinballDomain
 
 
+def frontier_masks(k: int, enabled_mask: int, gest_mask: int, parents, max_children: Optional[int] = None):
+    """SPEC §13's nodes for creating option k: (target_mask, cover_mask). Targets: the goal (node 0) and every enabled,
+    not gestating option j < k that fewer than `max_children` known options target already (None: no cap). Cover: every
+    known option (enabled | gest). parent[k] < k keeps the graph acyclic by construction."""
+    known = (enabled_mask | gest_mask) & ~1
+    target = 1
+    for j in range(1, k):
+        if not ((enabled_mask >> j) & 1) or (gest_mask >> j) & 1:
+            continue
+        children = sum(1 for i in range(1, len(parents)) if (known >> i) & 1 and int(parents[i]) == j)
+        if max_children is None or children < max_children:
+            target |= 1 << j
+    return target, known
+
+
+def choose_parent(counts, target_mask: int, min_examples: int) -> Optional[int]:
+    """SPEC §13: the target node holding the most examples (ties: the lower node id), or None when it holds fewer than
+    `min_examples` (growth stops)."""
+    best = None
+    for p, c in enumerate(counts):
+        if (target_mask >> p) & 1 and (best is None or c > counts[best]):
+            best = p
+    return best if best is not None and counts[best] >= min_examples else None
+
+
 class SkillChainingAgent:
     def __init__(self, pmap, n_envs: int, n_options: int = 0, *, device: int = 0, seed: int = 0,
                  env_id_base: int = 0, group=None, ordered_sum: bool = False, transport: str = "collective",
@@ -190,20 +215,89 @@ class SkillChainingAgent:
                 self.poll_gestation()
             if got < min_examples:
                 break
-            acc = self.create_option(k, gestation=gestation, **fit)
-            gsteps = 0
-            while (self.gest_mask >> k) & 1 and gsteps < gestation_steps:
-                for _ in range(poll_every):
-                    self.step_batch()
-                gsteps += poll_every
-                self.poll_gestation()
-            if (self.gest_mask >> k) & 1:            # did not see enough successes: enable anyway, as the paper's
-                self.gest_mask &= ~(1 << k)          # fixed-length gestation period would
-                self.ctx.set_gestation(self.gest_mask)
-                self.enable_option(k)
+            acc, gsteps = self._fit_and_gestate(k, gestation, gestation_steps, poll_every, fit)
             cov = float(self.options[k].initiation_classifier.predict(sx, sy).float().mean())
             report.append(dict(option=k, parent=int(self.ctx.parents[k]), steps=steps, examples=got,
                                accuracy=acc, start_coverage=cov, gestation_steps=gsteps))
+            if cov >= start_coverage:
+                break
+        return report
+
+    def _fit_and_gestate(self, k: int, gestation: int, gestation_steps: int, poll_every: int, fit: dict):
+        """Fit option k on its example buffer (create_option) and run its gestation: step-batches until the success counters
+        enable it, at most `gestation_steps` of them, then enable it anyway. Returns (training accuracy, gestation step-batches)."""
+        acc = self.create_option(k, gestation=gestation, **fit)
+        gsteps = 0
+        while (self.gest_mask >> k) & 1 and gsteps < gestation_steps:
+            for _ in range(poll_every):
+                self.step_batch()
+            gsteps += poll_every
+            self.poll_gestation()
+        if (self.gest_mask >> k) & 1:            # did not see enough successes: enable anyway, as the paper's
+            self.gest_mask &= ~(1 << k)          # fixed-length gestation period would
+            self.ctx.set_gestation(self.gest_mask)
+            self.enable_option(k)
+        return acc, gsteps
+
+    def grow_skill_tree(self, steps_per_option: int = 300, min_examples: int = 2000, max_examples: int = 40000,
+                        l_pos: int = 24, l_neg: int = 24, start_coverage: float = 0.5, poll_every: int = 8,
+                        max_children: Optional[int] = None, gestation: int = 0, gestation_steps: int = 200, **fit) -> list:
+        """Skill-tree discovery (SPEC §13; the extension Konidaris & Barto 2009 discuss): like chain_skills, but a new option
+        may target the goal or ANY enabled option, not only the one created last. For each free option index k in order,
+        step-batches run with the device-side frontier collection behind each (one buffer per node of the graph: envs that
+        enter a target node from territory no known option covers), until `steps_per_option` step-batches have run or a
+        node holds `max_examples`; the host reads the per-node counts every `poll_every` step-batches. The node holding the
+        most examples (ties: the lower id) becomes parent[k]; below `min_examples` growth stops. Option k is fitted on that
+        node's rows (they become its example buffer: examples(k), state_dict()), started from the root's weights and
+        gestated exactly as in chain_skills. Growth stops once the union of the known options' initiation sets covers
+        `start_coverage` of the map's start states. `max_children` caps the options that may target one option (None: no
+        cap). Returns one report dict per created option."""
+        if self.group is not None:
+            raise ValueError("grow_skill_tree: a sharded agent (group=...) cannot grow a skill tree yet; use chain_skills")
+        if getattr(self, "trace", None) is None:
+            raise ScgError("grow_skill_tree: tracing is off (enable_tracing)")
+        report = []
+        dev = self.W.device
+        sx = torch.as_tensor(self.map.starts[:, 0].copy(), device=dev)
+        sy = torch.as_tensor(self.map.starts[:, 1].copy(), device=dev)
+        cap = min(max_examples, self._ex_cap)
+        node_xy = torch.zeros((self.n_vf, cap, 2), dtype=torch.float32, device=dev)
+        node_lab = torch.zeros((self.n_vf, cap), dtype=torch.uint8, device=dev)
+        node_cnt = torch.zeros(self.n_vf, dtype=torch.int32, device=dev)
+        self._frontier = (node_xy, node_lab, node_cnt)      # the per-node buffers (kept for inspection)
+        for k in range(1, self.n_options + 1):
+            if ((self.enabled_mask | self.gest_mask) >> k) & 1:
+                continue
+            target, cover = frontier_masks(k, self.enabled_mask, self.gest_mask, self.ctx.parents, max_children)
+            node_cnt.zero_()
+            counts, steps = [0] * self.n_vf, 0
+            while steps < steps_per_option and max(counts[p] for p in range(self.n_vf) if (target >> p) & 1) < cap:
+                for _ in range(min(poll_every, steps_per_option - steps)):
+                    self.step_batch()
+                    self.ctx.collect_frontier(target, cover, self.clf.view(-1), l_pos, l_neg, node_xy.view(-1),
+                                              node_lab.view(-1), node_cnt)
+                    steps += 1
+                counts = [int(c) for c in node_cnt.tolist()]
+                self.poll_gestation()
+            p = choose_parent(counts, target, min_examples)
+            if p is None:
+                break
+            parents = self.ctx.parents.copy()
+            parents[k] = p
+            self.set_option_parents(parents)
+            self._ex.pop(k, None)                   # option k's buffer now belongs to its new parent
+            xy, lab, cnt, _ = self._ex_buffers(k)
+            n = counts[p]
+            xy[:n].copy_(node_xy[p, :n]); lab[:n].copy_(node_lab[p, :n]); cnt.fill_(n)
+            acc, gsteps = self._fit_and_gestate(k, gestation, gestation_steps, poll_every, fit)
+            known = self.enabled_mask | self.gest_mask
+            cover_start = torch.zeros_like(sx, dtype=torch.bool)
+            for j in range(1, self.n_options + 1):
+                if (known >> j) & 1:
+                    cover_start |= self.options[j].initiation_classifier.predict(sx, sy).bool()
+            cov = float(cover_start.float().mean())
+            report.append(dict(option=k, parent=p, steps=steps, examples=n, node_examples=counts, accuracy=acc,
+                               start_coverage=cov, gestation_steps=gsteps))
             if cov >= start_coverage:
                 break
         return report

@@ -339,6 +339,27 @@ class ScgContext:
         else:
             self.disarm_collect()
 
+    def collect_frontier(self, target_mask: int, cover_mask: int, clf: torch.Tensor, l_pos: int, l_neg: int,
+                         ex_xy: torch.Tensor, ex_label: torch.Tensor, count: torch.Tensor) -> None:
+        """SPEC §13 frontier collection, one buffer per node p = 0..n_options (0 = the goal, p = initiation set p): an env
+        whose step ended in a node of `target_mask` while its s_t lay in no initiation set of `cover_mask` (classifier rows
+        of clf[n_vf, 8]) appends its most recent ring states to ex_xy[n_vf, cap, 2] / ex_label[n_vf, cap] behind count[p]
+        (device int32[n_vf], in/out). Two small launches; stateless (no prev_in, an announced collect_examples trigger is
+        left alone); nothing comes back to the host."""
+        if getattr(self, "_trace", None) is None:
+            raise ScgError("collect_frontier: trace buffers are not attached (set_trace_buffers)")
+        cap = ex_label.numel() // self.n_vf
+        if cap < 1 or ex_label.numel() != self.n_vf * cap:
+            raise ScgError(f"collect_frontier: ex_label must hold n_vf = {self.n_vf} buffers of cap >= 1 examples")
+        self._chk(ex_xy, torch.float32, 2 * self.n_vf * cap, "ex_xy"); self._chk(ex_label, torch.uint8, self.n_vf * cap, "ex_label")
+        self._chk(count, torch.int32, self.n_vf, "count"); self._chk(clf, torch.float32, self.n_vf * CLF_STRIDE, "clf")
+        nodes = (1 << self.n_vf) - 1
+        if l_pos < 0 or l_neg < 0 or l_pos + l_neg < 1 or not (0 <= target_mask <= nodes) or not (0 <= cover_mask <= nodes) \
+                or cover_mask & 1 or target_mask & ~cover_mask & ~1:
+            raise ScgError("collect_frontier: bad argument")
+        self._call("scg_collect_frontier", C.c_uint32(target_mask), C.c_uint32(cover_mask), _ptr(clf), l_pos, l_neg, _ptr(ex_xy),
+                   _ptr(ex_label), _ptr(count), cap, self._stream())
+
     def disarm_collect(self) -> None:
         self._call("scg_arm_collect", C.c_uint32(0), None, 0, 0, None)
         self._armed = None

@@ -828,6 +828,123 @@ __global__ __launch_bounds__(COL_ROW) void collect_scatter_kernel(int n, const u
     }
 }
 
+// SPEC §13 frontier collection: §7's collect with one example buffer per node of the skill graph (node 0 = the goal, events
+// bit 0; node p >= 1 = initiation set p, events bit p) and a stateless entry test in place of prev_in: an env hits node p when
+// p is a target, its step ended in node p, and s_t (ring[(ev_len - 1) & (ring_len - 1)], harvest age 0) lies in no set of
+// cover_mask (§4.1's z, no `known` term). The same two launches over rows of COL_ROW envs as collect_*_kernel:
+//   frontier_count_kernel    per-row totals of v PER NODE -> rowsum[p][row]; node p's fill level -> rowsum[p][nrows]
+//   frontier_scatter_kernel  node by node: offset of a row = fill level + totals of the rows before it, ballots + scans per
+//                            wave, the hit env's rows gathered by the lanes of its wave (lane j = age j)
+// Integer prefix sums in env order only; the classifier rows are staged in LDS once per workgroup; s_t is read once per env
+// (and only for an env whose step ended in a target node).
+__device__ __forceinline__ uint32_t frontier_hits(int e, int n, const uint8_t *events, const int32_t *ev_len, const float *ring_x,
+                                                  const float *ring_y, int ring_len, const float *s_clf, uint32_t target_mask,
+                                                  uint32_t cover_mask, int L, int &v, int &evl) {
+    v = 0; evl = 0;
+    if (e >= n) return 0u;
+    const uint32_t cand = events[e] & target_mask;
+    if (!cand) return 0u;
+    const int el = ev_len[e];
+    if (el < 1) return 0u;
+    const size_t row = (size_t)((el - 1) & (ring_len - 1)) * n + e;
+    const float x = ring_x[row], y = ring_y[row];
+    for (uint32_t m = cover_mask; m; m &= m - 1)
+        if (clf_z(s_clf + CLF_STRIDE * __builtin_ctz(m), x, y) > 0.0f) return 0u;     // s_t is covered: not an entry
+    v = min(min(L, el), ring_len);
+    evl = el;
+    return cand;
+}
+
+__global__ __launch_bounds__(COL_ROW) void frontier_count_kernel(int n, const uint8_t *events, const int32_t *ev_len,
+                                                                 const float *ring_x, const float *ring_y, int ring_len,
+                                                                 const float *clf, int n_vf, uint32_t target_mask,
+                                                                 uint32_t cover_mask, int L, int32_t *rowsum, int nrows,
+                                                                 const int32_t *count) {
+    __shared__ float s_clf[MAX_VF * CLF_STRIDE];
+    __shared__ int s_w[MAX_VF][COL_ROW / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < n_vf * CLF_STRIDE) s_clf[tid] = clf[tid];
+    __syncthreads();
+    int v, evl;
+    const uint32_t hit = frontier_hits(blockIdx.x * COL_ROW + tid, n, events, ev_len, ring_x, ring_y, ring_len, s_clf,
+                                       target_mask, cover_mask, L, v, evl);
+#pragma unroll
+    for (int p = 0; p < MAX_VF; ++p) {
+        if (!((target_mask >> p) & 1u)) continue;
+        int vp = ((hit >> p) & 1u) ? v : 0;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) vp += __shfl_xor(vp, m, 64);
+        if (lane == 0) s_w[p][wave] = vp;
+    }
+    __syncthreads();
+    if (tid < MAX_VF && ((target_mask >> tid) & 1u)) {
+        int t = 0;
+#pragma unroll
+        for (int w2 = 0; w2 < COL_ROW / 64; ++w2) t += s_w[tid][w2];
+        rowsum[(size_t)tid * (nrows + 1) + blockIdx.x] = t;
+        if (blockIdx.x == 0) rowsum[(size_t)tid * (nrows + 1) + nrows] = count[tid];
+    }
+}
+
+__global__ __launch_bounds__(COL_ROW) void frontier_scatter_kernel(int n, const uint8_t *events, const int32_t *ev_len,
+                                                                   const float *ring_x, const float *ring_y, int ring_len,
+                                                                   const float *clf, int n_vf, uint32_t target_mask,
+                                                                   uint32_t cover_mask, int l_pos, int l_neg, float *ex_xy,
+                                                                   uint8_t *ex_label, int32_t *count, int cap,
+                                                                   const int32_t *rowsum, int nrows) {
+    __shared__ float s_clf[MAX_VF * CLF_STRIDE];
+    __shared__ int s_w[MAX_VF][COL_ROW / 64], s_pre[MAX_VF][COL_ROW / 64], s_tot[MAX_VF][COL_ROW / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = blockIdx.x;
+    if (tid < n_vf * CLF_STRIDE) s_clf[tid] = clf[tid];
+    __syncthreads();
+    const int e = row * COL_ROW + tid;
+    int v, evl;
+    const uint32_t hit = frontier_hits(e, n, events, ev_len, ring_x, ring_y, ring_len, s_clf, target_mask, cover_mask,
+                                       l_pos + l_neg, v, evl);
+    for (int p = 0; p < n_vf; ++p) {                      // uniform over the workgroup: the barrier below is reached by all
+        if (!((target_mask >> p) & 1u)) continue;
+        const int32_t *rs = rowsum + (size_t)p * (nrows + 1);
+        const int vp = ((hit >> p) & 1u) ? v : 0;
+        int before = 0, all = 0;
+        for (int r = tid; r < nrows; r += COL_ROW) { const int t = rs[r]; all += t; if (r < row) before += t; }
+        int incl = vp;                                    // inclusive prefix of vp inside the wave
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const int t = __shfl_up(incl, m, 64);
+            if (lane >= m) incl += t;
+        }
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) { before += __shfl_xor(before, m, 64); all += __shfl_xor(all, m, 64); }
+        if (lane == 63) s_w[p][wave] = incl;              // each node has its own LDS slots: no barrier before the next node's writes
+        if (lane == 0) { s_pre[p][wave] = before; s_tot[p][wave] = all; }
+        __syncthreads();
+        int base = rs[nrows], woff = 0, total = 0;
+#pragma unroll
+        for (int w2 = 0; w2 < COL_ROW / 64; ++w2) {
+            base += s_pre[p][w2]; total += s_tot[p][w2];
+            if (w2 < wave) woff += s_w[p][w2];
+        }
+        if (row == 0 && tid == 0) count[p] = min(rs[nrows] + total, cap);
+        const int pos0 = base + woff + incl - vp;
+        float *xy_p = ex_xy + (size_t)p * cap * 2;
+        uint8_t *lab_p = ex_label + (size_t)p * cap;
+        uint64_t hits = __ballot(vp > 0);
+        while (hits) {
+            const int src = (int)__builtin_ctzll(hits);
+            hits &= hits - 1;
+            const int he = __shfl(e, src, 64), hv = __shfl(vp, src, 64), hp = __shfl(pos0, src, 64), hl = __shfl(evl, src, 64);
+            for (int j = lane; j < hv; j += 64) {
+                const int pos = hp + j;
+                if ((unsigned)pos < (unsigned)cap) {            // (a negative fill level handed in writes nothing either)
+                    const size_t rrow = (size_t)((hl - 1 - j) & (ring_len - 1)) * n + he;
+                    xy_p[2 * (size_t)pos] = ring_x[rrow]; xy_p[2 * (size_t)pos + 1] = ring_y[rrow];
+                    lab_p[pos] = j < l_pos ? 1 : 0;
+                }
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // un-fused kernels
 __global__ __launch_bounds__(256) void pinball_kernel(int n, float *x, float *y, float *vx, float *vy,
@@ -1020,6 +1137,8 @@ struct scg_ctx {
     uint64_t *d_cellmask;
     int32_t *d_perm, *d_hist;      // SPEC §5 env order of the current step (d_hist: scratch of the stand-alone sort)
     int32_t *d_collect_rows;       // scg_collect_examples: per-row totals [rows of COL_ROW envs] + the buffer's fill level
+    int32_t *d_frontier_rows;      // scg_collect_frontier: the same per node [MAX_VF][rows + 1] (its own: an announced
+                                   // trigger's totals in d_collect_rows survive a frontier collection)
     uint32_t arm_bits;             // scg_arm_collect: the announced trigger (0 = none) ...
     const uint8_t *arm_prev;
     const int32_t *arm_count;
@@ -1250,6 +1369,7 @@ int scg_create(scg_ctx **out, const scg_config *cfg) {
         if (hipMalloc(&c->d_perm, (size_t)c->nblk * BLOCK_ENVS * sizeof(int32_t)) != hipSuccess) { st = SCG_ERR_HIP; break; }
         if (hipMalloc(&c->d_hist, (size_t)((c->cfg.n_envs + 255) / 256) * HSTRIDE * sizeof(int32_t)) != hipSuccess) { st = SCG_ERR_HIP; break; }
         if (hipMalloc(&c->d_collect_rows, (size_t)((cfg->n_envs + COL_ROW - 1) / COL_ROW + 1) * sizeof(int32_t)) != hipSuccess) { st = SCG_ERR_HIP; break; }
+        if (hipMalloc(&c->d_frontier_rows, (size_t)MAX_VF * ((cfg->n_envs + COL_ROW - 1) / COL_ROW + 1) * sizeof(int32_t)) != hipSuccess) { st = SCG_ERR_HIP; break; }
         if (hipMalloc(&c->d_fit_part, (size_t)FIT_BATCH * 2 * FIT_G * 8 * sizeof(unsigned long long)) != hipSuccess) { st = SCG_ERR_HIP; break; }
         if (hipHostMalloc(reinterpret_cast<void **>(&c->h_async), 64, hipHostMallocMapped) != hipSuccess) { st = SCG_ERR_HIP; break; }
         *c->h_async = 0u;
@@ -1292,7 +1412,7 @@ int scg_destroy(scg_ctx *c) {
     (void)hipFree(c->d_slabs); (void)hipFree(c->d_cnts); (void)hipFree(c->d_G); (void)hipFree(c->d_nk);
     (void)hipFree(c->d_hist2[0]); (void)hipFree(c->d_hist2[1]); (void)hipFree(c->d_outrec); (void)hipFree(c->d_qalt); (void)hipFree(c->d_invperm);
     (void)hipFree(c->d_edges); (void)hipFree(c->d_starts); (void)hipFree(c->d_scale); (void)hipFree(c->d_cellmask); (void)hipFree(c->d_perm); (void)hipFree(c->d_hist);
-    (void)hipFree(c->d_fit_part); (void)hipFree(c->d_collect_rows); (void)hipFree(c->d_fail);
+    (void)hipFree(c->d_fit_part); (void)hipFree(c->d_collect_rows); (void)hipFree(c->d_frontier_rows); (void)hipFree(c->d_fail);
     if (c->h_async) (void)hipHostFree(c->h_async);
     if (c->peer_region) {
         DeviceGuard g(c->cfg.device);
@@ -1780,6 +1900,33 @@ int scg_collect_examples(scg_ctx *c, uint32_t event_bits, uint8_t *prev_in, int3
     hipLaunchKernelGGL(collect_scatter_kernel, dim3(nrows), dim3(COL_ROW), 0, s, c->cfg.n_envs, c->events, prev_in, event_bits,
                        c->ring_x, c->ring_y, c->ring_len, c->ev_len, l_pos, l_neg, ex_xy, ex_label, count, cap,
                        c->d_collect_rows, nrows);
+    SCG_HIP(c, hipGetLastError());
+    return SCG_OK;
+}
+
+int scg_collect_frontier(scg_ctx *c, uint32_t target_mask, uint32_t cover_mask, const float *clf, int32_t l_pos, int32_t l_neg,
+                         float *ex_xy, uint8_t *ex_label, int32_t *count, int32_t cap, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_collect_frontier: null ctx");
+    if (!c->ring_x || !c->events) return fail(c, SCG_ERR_STATE, "scg_collect_frontier: trace buffers are not attached");
+    const uint32_t nodes = (1u << c->n_vf) - 1u, opts = nodes & ~1u;
+    if (target_mask & ~nodes) return fail(c, SCG_ERR_INVALID, "scg_collect_frontier: target_mask names no node of this context");
+    if (cover_mask & ~opts) return fail(c, SCG_ERR_INVALID, "scg_collect_frontier: cover_mask must name options 1..n_options only");
+    if (target_mask & opts & ~cover_mask)
+        return fail(c, SCG_ERR_INVALID, "scg_collect_frontier: a target option must be part of the cover");
+    if (cap < 1 || l_pos < 0 || l_neg < 0 || (int64_t)l_pos + l_neg < 1 || (int64_t)l_pos + l_neg > INT32_MAX || !clf || !ex_xy ||
+        !ex_label || !count)
+        return fail(c, SCG_ERR_INVALID, "scg_collect_frontier: bad argument");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_collect_frontier");
+    if (!target_mask) return SCG_OK;                         // no node: nothing to append
+    const int nrows = (c->cfg.n_envs + COL_ROW - 1) / COL_ROW;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(frontier_count_kernel, dim3(nrows), dim3(COL_ROW), 0, s, c->cfg.n_envs, c->events, c->ev_len, c->ring_x,
+                       c->ring_y, c->ring_len, clf, c->n_vf, target_mask, cover_mask, l_pos + l_neg, c->d_frontier_rows, nrows,
+                       count);
+    hipLaunchKernelGGL(frontier_scatter_kernel, dim3(nrows), dim3(COL_ROW), 0, s, c->cfg.n_envs, c->events, c->ev_len, c->ring_x,
+                       c->ring_y, c->ring_len, clf, c->n_vf, target_mask, cover_mask, l_pos, l_neg, ex_xy, ex_label, count, cap,
+                       c->d_frontier_rows, nrows);
     SCG_HIP(c, hipGetLastError());
     return SCG_OK;
 }
