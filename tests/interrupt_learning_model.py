@@ -198,7 +198,8 @@ def step(orc, pre, W, clf, t, enabled, gest=0, interrupt=True, recompute=True):
                 boot = np.where(io, term[items] & (dn[items] == 0), (dn[items] == 0) & (succ_k[items] | fail_k[items]))
                 tgt = np.where(boot, fmaf(gamma, m[0][items], r),
                                np.where(cont > 0, fmaf(cont, m[k][items], r), r)).astype(np.float32)
-                cut = interrupted[items]                           # SPEC §12: the exit rule's bootstrap
+                cut = interrupted[items] & io                      # SPEC §12: the exit rule's bootstrap (own items only: an
+                                                                   #  env's gestation items of another option are unchanged)
                 tgt[cut] = fmaf(gamma, m[0][items][cut], r[cut])
                 Gb, cnt = orc.q_update_grad([v[items] for v in s], a[items], tgt, np.zeros(len(items), np.float32),
                                             [v[items] for v in sn], W[k])

@@ -18,6 +18,12 @@ Ambiguity. A binary32 decision can differ from the float64 one where the float64
 binary32 evaluation: a classifier `|z| <= tol_z` or a gate `|V_k - V_0| <= tol_V`. Such an env is AMBIGUOUS: the model takes the
 decision the system under test made (where it can be read off the outputs) and carries on from it; it reports the env. When
 `W_k` and `W_0` are bitwise identical the tie is exact (both sides evaluate the same sum in the same order) and the env enters.
+
+Interruption (SPEC §11 acting, §12 learning), `step(..., interrupt=True)`: an env whose option o goes on is interrupted when
+`!(V_o >= V_0)` at s_next. It is ambiguous where `|V_o - V_0| <= tol_V_o + tol_V_0` and W_o, W_0 are not bitwise equal; the model
+then takes the SUT's decision (a kept env whose written id is not o, or whose opt_steps is 0, was interrupted). Equal weights
+tie exactly and keep the option; a NaN on either side interrupts. An interrupted env's candidate c follows the SUT where a
+membership at s_next is ambiguous, as the selection does.
 """
 from __future__ import annotations
 
@@ -133,11 +139,14 @@ class StepModel:
         return np.where(explore, a_rand, a_greedy), mulhi32(u2, len(self.map.starts))
 
     # ------------------------------------------------------------------ the step-batch
-    def step(self, pre, W, clf, t, enabled, gest=0, sut=None):
+    def step(self, pre, W, clf, t, enabled, gest=0, sut=None, learn=True, interrupt=False):
         """pre: the pre-step state dict (numpy, not modified). W [n_vf, 5, 1296] f32, clf [n_vf, 8]. sut: the outputs of the
         system under test (state dict after its step + 'events'), used only to follow it on ambiguous decisions.
-        Returns a dict of model outputs, tolerances, resolutions and the ambiguous envs."""
+        learn=False: the acting outputs only (SPEC §8's acting step); G, n_k, W and their tolerances are None.
+        interrupt: an option that goes on is interrupted where the root's value at s_next is higher (SPEC §11 acting, §12 with
+        learn). Returns a dict of model outputs, tolerances, resolutions and the ambiguous envs."""
         n, nvf, gam = len(pre["x"]), self.n_vf, self.gamma
+        ar = np.arange(n)
         known = enabled | gest
         a, si = self.act(pre, t)
         s = [pre[k].astype(np.float32).copy() for k in ("x", "y", "vx", "vy")]
@@ -178,7 +187,9 @@ class StepModel:
             rows = amA.any(0)
             for k in range(1, nvf):
                 inA[k, rows] = ((ev[rows] >> k) & 1).astype(bool)
-        amb |= amA.any(0) | amS.any(0)
+        amb |= amA.any(0)
+        if learn:                        # in_k(s) only makes gestation items
+            amb |= amS.any(0)
 
         # ---- SPEC §4.2: the env's own option, termination, selection
         oid = pre["option_id"].astype(np.int64)
@@ -194,14 +205,14 @@ class StepModel:
         cont_o = np.where(term, 0.0, gam)
         exit_o = running & term & (done == 0)
 
-        cand = np.zeros(n, np.int64)
+        free = np.zeros(n, np.int64)                          # the candidate as if the env's option had ended (SPEC §11's c)
         for k in range(nvf - 1, 0, -1):                       # the lowest-numbered qualifying option wins
             if not (enabled >> k) & 1:
                 continue
             pk = self.parents[k]
             tgt = inB[pk] if pk != 0 else np.zeros(n, bool)
-            cand = np.where(inB[k] & ~tgt, k, cand)
-        cand = np.where(keep, o, cand)
+            free = np.where(inB[k] & ~tgt, k, free)
+        cand = np.where(keep, o, free)
         amb_b = ~keep & amB.any(0)
         if sut is not None:
             cand = np.where(amb_b, np.abs(sut["option_id"].astype(np.int64)), cand)
@@ -221,7 +232,8 @@ class StepModel:
         V_tol = np.stack([tq.max(1) for tq in qn_tol])
         ci = np.clip(cand, 0, nvf - 1)
         Vc, V0 = V[ci, np.arange(n)], V[0]
-        exact_tie = np.array([np.array_equal(W[k].view(np.uint32), W[0].view(np.uint32)) for k in range(nvf)])[ci]
+        same = np.array([np.array_equal(W[k].view(np.uint32), W[0].view(np.uint32)) for k in range(nvf)])
+        exact_tie = same[ci]
         accept = Vc >= V0                                      # NaN on either side: False (declines)
         gate_amb = entering & ~exact_tie & np.isfinite(Vc) & np.isfinite(V0) & (np.abs(Vc - V0) <= V_tol[ci, np.arange(n)] + V_tol[0])
         accept = np.where(entering & exact_tie & ~np.isnan(Vc), True, accept)
@@ -229,10 +241,41 @@ class StepModel:
             accept = np.where(gate_amb, sut["option_id"].astype(np.int64) > 0, accept)
         amb |= gate_amb
         declined = entering & ~accept
-        o_next = np.where(stay | declined, 0, cand)
-        option_id_next = np.where(stay | declined, -cand, cand)
+
+        # ---- SPEC §11 / §12: an option that goes on is interrupted where the root's value at s_next is higher
+        interrupted, c = np.zeros(n, bool), np.zeros(n, np.int64)
+        if interrupt:
+            m_o, m_0 = V[o, ar], V[0]
+            nan = np.isnan(m_o) | np.isnan(m_0)
+            tie = same[o] & ~nan                               # bitwise-equal weights: an exact tie, which keeps the option
+            interrupted = keep & ~tie & ~(m_o >= m_0)          # a NaN on either side interrupts
+            amb_i = keep & ~tie & ~nan & (np.abs(m_o - m_0) <= V_tol[o, ar] + V_tol[0])
+            if sut is not None:                                # the SUT interrupted where it wrote an id other than o, or opt_steps 0
+                cut = (sut["option_id"].astype(np.int64) != o) | (sut["opt_steps"].astype(np.int64) == 0)
+                interrupted = np.where(amb_i, cut, interrupted)
+            c = np.where(interrupted, free, 0)
+            amb_c = interrupted & amB.any(0)
+            if sut is not None:
+                c = np.where(amb_c, np.abs(sut["option_id"].astype(np.int64)), c)
+            amb |= amb_i | amb_c
+        o_next = np.where(stay | declined | interrupted, 0, cand)
+        option_id_next = np.where(interrupted, -c, np.where(stay | declined, -cand, cand))
         qcache = np.stack([qn[k][np.arange(n), :] for k in range(nvf)])[o_next, np.arange(n)].T       # [5, n]
         qcache_tol = np.stack(qn_tol)[o_next, np.arange(n)].T
+        code = np.where(succ_o, 1, np.where(done != 0, 2, np.where(fail_o, 3, 4)))      # SPEC §9's outcome, first match wins
+        events = goal.astype(np.int64)
+        for k in range(1, min(nvf, 6)):
+            events |= inA[k].astype(np.int64) << k
+        out = dict(
+            x=sn[0], y=sn[1], vx=sn[2], vy=sn[3], action=a, reward=reward, done=done,
+            option_id=option_id_next, opt_steps=np.where(keep & ~interrupted, pre["opt_steps"].astype(np.int64) + 1, 0),
+            ep_steps=np.where(done != 0, 0, eps1), events=events, ev_len=eps1, qcache=qcache, qcache_tol=qcache_tol,
+            ambiguous=np.nonzero(amb)[0], entering=entering, stay=stay, declined=declined, cand=cand, keep=keep,
+            interrupted=interrupted, c=c, vf=o, succ_o=succ_o, sp=sp,
+            term=np.where(interrupted, 5, np.where(running & term, code, 0)),      # SPEC §10's record code, 5: §11's interrupt
+            G=None, G_tol=None, n_k=None, W=None, W_tol=None, gest_succ=None, resolution=None, items=None)
+        if not learn:
+            return out
 
         # ---- SPEC §5: update items, targets, deltas, G
         del tab_n
@@ -260,7 +303,7 @@ class StepModel:
                 upd = own | gst
                 r = np.where(own, r_o, reward + np.where(succ_k, self.r_succ, 0.0))
                 cont = np.where(own, cont_o, np.where((done != 0) | succ_k | fail_k, 0.0, gam))
-                boot = np.where(own, exit_o, (succ_k | fail_k) & (done == 0)) & upd
+                boot = np.where(own, exit_o | interrupted, (succ_k | fail_k) & (done == 0)) & upd     # §12: r_o + γ m_0
             m_k, tm_k = V[k], V_tol[k]
             target = np.where(boot, r + gam * V[0], np.where(cont > 0, r + cont * m_k, r))
             t_tol = np.where(boot, gam * V_tol[0], np.where(cont > 0, cont * tm_k, 0.0)) + U32 * 4 * np.abs(target)
@@ -291,16 +334,8 @@ class StepModel:
                 W_next[k] = W64[k] + st * self.scale[None, :] * G[k]
                 W_tol[k] = st * self.scale[None, :] * (G_tol[k] + 4 * U32 * np.abs(G[k])) + 2 * U32 * np.abs(W_next[k])
 
-        events = goal.astype(np.int64)
-        for k in range(1, min(nvf, 6)):
-            events |= inA[k].astype(np.int64) << k
-        return dict(
-            x=sn[0], y=sn[1], vx=sn[2], vy=sn[3], action=a, reward=reward, done=done,
-            option_id=option_id_next, opt_steps=np.where(keep, pre["opt_steps"].astype(np.int64) + 1, 0),
-            ep_steps=np.where(done != 0, 0, eps1), events=events, ev_len=eps1,
-            qcache=qcache, qcache_tol=qcache_tol, G=G, G_tol=G_tol, n_k=n_k, W=W_next, W_tol=W_tol,
-            gest_succ=gest_succ, resolution=resolution, ambiguous=np.nonzero(amb)[0], items=items,
-            entering=entering, stay=stay, declined=declined, cand=cand)
+        out.update(G=G, G_tol=G_tol, n_k=n_k, W=W_next, W_tol=W_tol, gest_succ=gest_succ, resolution=resolution, items=items)
+        return out
 
 
 def env_order_layout(option_id, n_vf, block_envs):
@@ -317,7 +352,7 @@ def env_order_layout(option_id, n_vf, block_envs):
 def compare(m, got, G, n_k, W, events=None, ev_len=None, gest_succ=None, check_resolution=False, msg=""):
     """Assert that the outputs of a system under test (state dict `got`, G, n_k, W after apply, trace / gestation counters
     when given) agree with the model output `m`: discrete fields exactly (ambiguous envs excepted), floats to tolerance.
-    Returns the number of ambiguous envs."""
+    An acting step (a model of learn=False) passes n_k = G = W = None. Returns the number of ambiguous envs."""
     n = len(m["x"])
     ok = np.ones(n, bool)
     ok[m["ambiguous"]] = False
@@ -332,15 +367,18 @@ def compare(m, got, G, n_k, W, events=None, ev_len=None, gest_succ=None, check_r
         assert np.array_equal(np.asarray(ev_len).astype(np.int64), m["ev_len"]), f"{msg} ev_len"
     if gest_succ is not None:
         assert np.array_equal(np.asarray(gest_succ).astype(np.int64), m["gest_succ"]), f"{msg} gest_succ {gest_succ} model {m['gest_succ']}"
-    assert np.array_equal(np.asarray(n_k).astype(np.int64), m["n_k"]), f"{msg} n_k {np.asarray(n_k).tolist()} model {m['n_k'].tolist()}"
+    if n_k is not None:
+        assert np.array_equal(np.asarray(n_k).astype(np.int64), m["n_k"]), f"{msg} n_k {np.asarray(n_k).tolist()} model {m['n_k'].tolist()}"
     q = np.asarray(got["qcache"]).astype(np.float64)
     err = np.abs(q - m["qcache"])[:, ok]
     fin = np.isfinite(m["qcache"][:, ok])
     assert np.array_equal(np.isfinite(q[:, ok]), fin), f"{msg} qcache: finiteness differs"
     assert np.all(err[fin] <= m["qcache_tol"][:, ok][fin]), f"{msg} qcache: max excess {np.max(err[fin] - m['qcache_tol'][:, ok][fin])}"
     for name, got_a, want, tol in (("G", G, m["G"], m["G_tol"]), ("W", W, m["W"], m["W_tol"])):
+        if got_a is None:
+            continue
         got_a = np.asarray(got_a).astype(np.float64)
-        for k in range(len(m["n_k"])):
+        for k in range(len(want)):
             fin = np.isfinite(want[k])
             assert np.array_equal(np.isfinite(got_a[k]), fin), f"{msg} {name}[{k}]: finiteness differs"
             e = np.abs(got_a[k] - want[k])[fin]

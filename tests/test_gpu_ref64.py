@@ -19,7 +19,9 @@ STATE = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "
 
 class GpuRunner(OracleRunner):
     """The system under test on the GPU: ScgContext.step (LEARN | APPLY) from a pre-state copied to the device. The oracle
-    of the base class is kept only for the borrowed physics of the model."""
+    of the base class is kept only for the borrowed physics of the model. `interrupt`: SPEC §12's interrupting learner."""
+
+    interrupt = False
 
     def __init__(self, map_name, n, n_options, *, seed=0, env_id_base=0, parents=None, gest=0, **hp):
         super().__init__(map_name, n, n_options, seed=seed, env_id_base=env_id_base, parents=parents, gest=gest, **hp)
@@ -39,7 +41,7 @@ class GpuRunner(OracleRunner):
             getattr(st, k).copy_(dev(pre[k]))
         W_d, clf_d = dev(W.copy()), dev(clf)
         gs0 = self.gs.cpu().numpy().copy() if self.gs is not None else None
-        self.ctx.step(st, W_d.view(-1), clf_d.view(-1), enabled, t)
+        self.ctx.step(st, W_d.view(-1), clf_d.view(-1), enabled, t, interrupt=self.interrupt)
         torch.cuda.synchronize()
         out = {k: getattr(st, k).cpu().numpy() for k in STATE}
         gsn = self.gs.cpu().numpy() - gs0 if self.gs is not None else np.zeros(len(W), np.int32)

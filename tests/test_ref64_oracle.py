@@ -50,9 +50,11 @@ class OracleRunner:
 
 
 def check_step(runner, pre, W, clf, t, enabled, check_resolution=False, msg=""):
-    """One step of the system under test from `pre` against the model: (model output, SUT output, ambiguous env count)."""
+    """One step of the system under test from `pre` against the model: (model output, SUT output, ambiguous env count).
+    A runner whose `interrupt` is set steps with SPEC §12's interruption, and so does the model."""
     got = runner.step(pre, W, clf, t, enabled)
-    out = runner.model.step(pre, W, clf, t, enabled, runner.gest, sut=dict(got["st"], events=got["events"]))
+    out = runner.model.step(pre, W, clf, t, enabled, runner.gest, sut=dict(got["st"], events=got["events"]),
+                            interrupt=getattr(runner, "interrupt", False))
     n_amb = compare(out, got["st"], got["G"], got["n_k"], got["W"], events=got["events"], ev_len=got["ev_len"],
                     gest_succ=got["gest_succ"], check_resolution=check_resolution, msg=msg)
     return out, got, n_amb
