@@ -329,7 +329,12 @@ int scg_harvest(scg_ctx *ctx, int32_t n_sel, const int32_t *sel_env, const float
  * whose `events` byte has one of `event_bits` set — with prev_in (u8[N], in/out) only on the step the bit goes up —
  * appends its min(L, ev_len, ring_len) most recent ring states behind the *count (device int32, in/out) examples
  * already in ex_xy[cap][2] / ex_label[cap] (1 = one of the last l_pos states, 0 = older), in env order; what does not
- * fit is dropped. The trace buffers of scg_set_trace_buffers are read. */
+ * fit is dropped. The trace buffers of scg_set_trace_buffers are read. *count = min(cap, *count + rows); cap = 0 is admitted
+ * (nothing is written, *count becomes 0). A negative *count is not an error: rows whose position falls outside [0, cap) are
+ * dropped, so nothing is ever written in front of the buffer, and *count = min(cap, *count + rows) as usual (the same holds
+ * for scg_collect_frontier's count[p]). Refused (SCG_ERR_INVALID, nothing launched): event_bits = 0, l_pos or l_neg < 0,
+ * l_pos + l_neg < 1 or beyond INT32_MAX (the sum is formed in 64 bits by all four collector entry points), cap < 0, a null
+ * ex_xy / ex_label / count. */
 int scg_collect_examples(scg_ctx *ctx, uint32_t event_bits, uint8_t *prev_in, int32_t l_pos, int32_t l_neg,
                          float *ex_xy, uint8_t *ex_label, int32_t *count, int32_t cap, void *stream);
 /* Optional: announce the trigger the NEXT scg_collect_examples will be called with (same event_bits, prev_in, l_pos + l_neg and
@@ -339,7 +344,13 @@ int scg_collect_examples(scg_ctx *ctx, uint32_t event_bits, uint8_t *prev_in, in
  * event_bits = 0 withdraws the announcement. prev_in and count are READ by every following scg_step until then (device
  * pointers kept in the ctx): keep them alive, or withdraw the announcement before freeing them. scg_step checks them best-effort
  * (hipPointerGetAttributes: memory handed back to the DRIVER is noticed and refused with SCG_ERR_STATE; memory a caching allocator
- * such as torch's has merely recycled still reads as a device allocation and is NOT noticed) — the rule above is the contract. */
+ * such as torch's has merely recycled still reads as a device allocation and is NOT noticed) — the rule above is the contract.
+ * The step also takes its copy of *count (the level the one-launch collect appends behind) while it commits. So between a
+ * scg_step and the matching scg_collect_examples behind it the caller must not write *count or prev_in: a fill level reset
+ * there would be ignored and the rows appended behind the old one. Reset them after the collect (before the next scg_step),
+ * or withdraw the announcement first; scg_collect_examples itself and scg_arm_collect both drop the step's totals, so a
+ * second collect without a step in between reads the buffers afresh. (SkillChainingAgent resets a level only when an
+ * option's collection starts or ends, never between a step-batch and its collect.) */
 int scg_arm_collect(scg_ctx *ctx, uint32_t event_bits, const uint8_t *prev_in, int32_t l_pos, int32_t l_neg, const int32_t *count);
 /* scg_collect_frontier: frontier collection for skill-tree growth (SPEC §13), two launches, nothing returns to the host. Nodes
  * p = 0..n_options: node 0 is the goal (events bit 0), node p >= 1 initiation set p (events bit p). An env with ev_len >= 1

@@ -819,7 +819,7 @@ __global__ __launch_bounds__(COL_ROW) void collect_scatter_kernel(int n, const u
         const int he = __shfl(e, src, 64), hv = __shfl(v, src, 64), hp = __shfl(pos0, src, 64), hl = __shfl(evl, src, 64);
         for (int j = lane; j < hv; j += 64) {
             const int pos = hp + j;
-            if (pos < cap) {
+            if ((unsigned)pos < (unsigned)cap) {            // (a negative fill level handed in writes nothing in front of the buffer)
                 const size_t rrow = (size_t)((hl - 1 - j) & (ring_len - 1)) * n + he;
                 ex_xy[2 * (size_t)pos] = ring_x[rrow]; ex_xy[2 * (size_t)pos + 1] = ring_y[rrow];
                 ex_label[pos] = j < l_pos ? 1 : 0;
@@ -1885,7 +1885,8 @@ int scg_collect_examples(scg_ctx *c, uint32_t event_bits, uint8_t *prev_in, int3
                          uint8_t *ex_label, int32_t *count, int32_t cap, void *stream) {
     if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_collect_examples: null ctx");
     if (!c->ring_x || !c->events) return fail(c, SCG_ERR_STATE, "scg_collect_examples: trace buffers are not attached");
-    if (!event_bits || l_pos < 0 || l_neg < 0 || l_pos + l_neg < 1 || !ex_xy || !ex_label || !count || cap < 0)
+    if (!event_bits || l_pos < 0 || l_neg < 0 || (int64_t)l_pos + l_neg < 1 || (int64_t)l_pos + l_neg > INT32_MAX || !ex_xy ||
+        !ex_label || !count || cap < 0)
         return fail(c, SCG_ERR_INVALID, "scg_collect_examples: bad argument");
     SCG_CHECK_ASYNC(c);
     SCG_ON_DEVICE(c, "scg_collect_examples");
@@ -1935,7 +1936,8 @@ int scg_arm_collect(scg_ctx *c, uint32_t event_bits, const uint8_t *prev_in, int
     if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_arm_collect: null ctx");
     c->arm_rows_ready = false;
     if (event_bits == 0) { c->arm_bits = 0; return SCG_OK; }
-    if (l_pos < 0 || l_neg < 0 || l_pos + l_neg < 1 || !count) return fail(c, SCG_ERR_INVALID, "scg_arm_collect: bad argument");
+    if (l_pos < 0 || l_neg < 0 || (int64_t)l_pos + l_neg < 1 || (int64_t)l_pos + l_neg > INT32_MAX || !count)
+        return fail(c, SCG_ERR_INVALID, "scg_arm_collect: bad argument");
     if (!c->ring_x || !c->events) return fail(c, SCG_ERR_STATE, "scg_arm_collect: trace buffers are not attached");
     c->arm_bits = event_bits; c->arm_prev = prev_in; c->arm_count = count; c->arm_L = l_pos + l_neg;
     return SCG_OK;
@@ -1956,7 +1958,8 @@ int scg_harvest(scg_ctx *c, int32_t n_sel, const int32_t *sel_env, const float *
                 int32_t ring_len, const int32_t *ev_len, int32_t l_pos, int32_t l_neg, float *out_xy,
                 uint8_t *out_label, void *stream) {
     if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_harvest: null ctx");
-    if (n_sel < 0 || l_pos < 0 || l_neg < 0 || l_pos + l_neg < 1 || ring_len < 1 || (ring_len & (ring_len - 1)) ||
+    if (n_sel < 0 || l_pos < 0 || l_neg < 0 || (int64_t)l_pos + l_neg < 1 || (int64_t)l_pos + l_neg > INT32_MAX || ring_len < 1 ||
+        (ring_len & (ring_len - 1)) ||
         !sel_env || !ring_x || !ring_y || !ev_len || !out_xy || !out_label)
         return fail(c, SCG_ERR_INVALID, "scg_harvest: bad argument");
     SCG_CHECK_ASYNC(c);

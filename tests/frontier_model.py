@@ -20,16 +20,26 @@ def covered(x, y, clf, cover_mask):
     return cov
 
 
-def collect_frontier(ring_x, ring_y, events, ev_len, target_mask, cover_mask, clf, l_pos, l_neg, ex_xy, ex_label, count):
-    """Append every node's hits in place: ex_xy[n_vf, cap, 2] f32, ex_label[n_vf, cap] u8, count[n_vf] i32."""
+_oracle_covered = covered          # (collect_frontier's `covered=` argument shadows the name)
+
+
+def collect_frontier(ring_x, ring_y, events, ev_len, target_mask, cover_mask, clf, l_pos, l_neg, ex_xy, ex_label, count,
+                     covered=None, cap=None):
+    """Append every node's hits in place: ex_xy[n_vf, cap, 2] f32, ex_label[n_vf, cap] u8, count[n_vf] i32. `covered` (bool per
+    env: s_t lies in a set of cover_mask) replaces the oracle's predict when the test decides the cover itself; `cap` is given
+    when the arrays carry a guard region behind each node's buffer."""
     ring_len, n = ring_x.shape
-    n_vf, cap = ex_label.shape
+    n_vf = ex_label.shape[0]
+    cap = ex_label.shape[1] if cap is None else int(cap)
     L = l_pos + l_neg
     el = np.asarray(ev_len, np.int64)
     live = el >= 1
     age0 = (np.maximum(el, 1) - 1) & (ring_len - 1)
     envs = np.arange(n)
-    unc = ~covered(ring_x[age0, envs], ring_y[age0, envs], clf, cover_mask)
+    if covered is None:
+        unc = ~_oracle_covered(ring_x[age0, envs], ring_y[age0, envs], clf, cover_mask)
+    else:
+        unc = ~np.asarray(covered, bool)
     v = np.minimum(np.minimum(L, el), ring_len)
     for p in range(n_vf):
         if not (target_mask >> p) & 1:

@@ -120,7 +120,8 @@ def test_frontier_refusals_launch_nothing():
     ctx.set_trace_buffers(16)
     bad = [args(1 << 3, 0), args(1 << 8, 0), args(1, 0b001), args(1, 0b1000), args(0b010, 0b100), args(0b110, 0b010),
            args(1, 0, cp=0), args(1, 0, lp=-1), args(1, 0, ln=-1), args(1, 0, lp=0, ln=0), args(1, 0, c_=None),
-           args(1, 0, x_=None), args(1, 0, l_=None), args(1, 0, n_=None)]
+           args(1, 0, x_=None), args(1, 0, l_=None), args(1, 0, n_=None),
+           args(1, 0, lp=2 ** 31 - 1, ln=1), args(1, 0, lp=2 ** 30, ln=2 ** 30)]        # the sum is formed in 64 bits
     for a in bad:
         assert fn(*a) == -1, a                                    # SCG_ERR_INVALID
     from skill_chaining_with_graphs_amd import ScgError
