@@ -42,6 +42,11 @@ class ScgContext:
                  max_option_steps: int = 250, update_count_floor: int = 0, reoffer_period: int = 4,
                  block_envs: Optional[int] = None,
                  library: Optional[str] = None):
+        # SPEC §2's run identity: refused here, before any device call (ctypes would mask them into range silently)
+        if not (0 <= int(seed) < 2 ** 64):
+            raise ScgError("seed must be a 64-bit unsigned integer")
+        if not (-2 ** 63 <= int(env_id_base) < 2 ** 63):
+            raise ScgError("env_id_base must be a 64-bit signed integer")
         if not torch.cuda.is_available():
             raise ScgError("no GPU visible to torch: the HIP path cannot run and there is no CPU fallback")
         if not (0 <= n_options <= MAX_OPTIONS):
@@ -127,6 +132,8 @@ class ScgContext:
         """One fused step-batch (SPEC §1.3-§5). `interrupt` (learning steps only; with learn=False it raises ScgError): SPEC §12's
         interrupting learner — an option that would go on stops where the root's value at the next state is higher, and its
         update item bootstraps from the root's value."""
+        if not (0 <= t < 2 ** 64):                            # (before the cached fast path: C.c_uint64 would wrap it silently)
+            raise ScgError("step: t must be a 64-bit unsigned step counter")
         # the validated, pre-marshalled pointer arguments of the last call are reused while the same tensors come back
         # (one step is two kernel launches: the host side of a call matters in short runs)
         # (the key holds every tensor's storage address, not only the Python ids: `.data =` / `set_()` on the same object

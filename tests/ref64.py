@@ -125,7 +125,8 @@ class StepModel:
     # ------------------------------------------------------------------ SPEC §2, §4.3
     def act(self, st, t):
         n = len(st["x"])
-        g = np.arange(n, dtype=np.uint64) + np.uint64(self.env_id_base)
+        t = int(t) % 2 ** 64                                  # Python ints: a 64-bit counter or id does not fit float64 or int64
+        g = np.array([(self.env_id_base + e) % 2 ** 32 for e in range(n)], np.uint64)      # c0 = g mod 2^32 (two's complement)
         u0, u1, u2, _ = philox4x32_10(g, np.full(n, t & 0xFFFFFFFF, np.uint64), np.full(n, t >> 32, np.uint64),
                                       np.zeros(n, np.uint64), self.seed & 0xFFFFFFFF, self.seed >> 32)
         explore = (u0 >> np.uint64(8)).astype(np.float64) * 2.0 ** -24 < self.epsilon
@@ -217,8 +218,9 @@ class StepModel:
         if sut is not None:
             cand = np.where(amb_b, np.abs(sut["option_id"].astype(np.int64)), cand)
         amb |= amb_b
-        g = np.arange(n, dtype=np.int64) + self.env_id_base
-        stagger = ((t + g) % self.period) != 0
+        # (t + g) mod 2^64 in Python ints (t = 2^64 - 1 overflows int64), g the 64-bit two's complement of env_id_base + e
+        tg = [(int(t) + self.env_id_base + e) % 2 ** 64 for e in range(n)]
+        stagger = np.array([v % self.period != 0 for v in tg], bool)
         stay = ~keep & (cand >= 1) & (done == 0) & (oid == -cand) & stagger
         entering = ~keep & (cand >= 1) & ~stay
 

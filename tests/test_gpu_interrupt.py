@@ -188,11 +188,11 @@ CASES = [
 ]
 
 
-def _run_case(name, n, n_opt, mask, gest, parents, eps, splits, mode, seed=3):
+def _run_case(name, n, n_opt, mask, gest, parents, eps, splits, mode, seed=3, t0=500, **hp):
     if mode == "begin" and eps == 0.0:
         eps = 0.05            # greedy episodes from the map's few start states would all be one and the same episode
     ctx, m, W, clf = _setup(name, n, n_opt, parents, gest, seed=seed, epsilon=eps, reoffer_period=4, max_episode_steps=40,
-                            max_option_steps=20)
+                            max_option_steps=20, **hp)
     st = _state(ctx, m, n, n_opt, seed=n + n_opt)
     twin = _clone(st)
     n_vf = n_opt + 1
@@ -200,7 +200,7 @@ def _run_case(name, n, n_opt, mask, gest, parents, eps, splits, mode, seed=3):
     ref_int = np.zeros((n_vf, n), np.int64)
     emu = Emulator(ctx, W, clf, mask, gest)
     begin, at, one = mode == "begin", mode == "begin_at", mode in ("begin", "begin_at", "one_episode")
-    t = 500
+    t = t0
     for i, K in enumerate(splits):
         first = i == 0
         emu.run(st, t, K, s_ref, ref_int, begin=begin and first, begin_at=at and first, one_episode=one)

@@ -210,12 +210,12 @@ CASES = [
 ]
 
 
-def _setup(case, block=None):
+def _setup(case, block=None, seed=4):
     name, n, n_opt, mask, gest, parents, eps, r_succ, max_opt, max_ep, base = case
     m = _map(name)
     kw = dict(HP)
     kw.update(epsilon=eps, r_option_success=r_succ, max_option_steps=max_opt, max_episode_steps=max_ep)
-    ctx = ScgContext(n, n_opt, m, device=0, seed=4, env_id_base=base, block_envs=block, **kw)
+    ctx = ScgContext(n, n_opt, m, device=0, seed=seed, env_id_base=base, block_envs=block, **kw)
     if parents is not None:
         ctx.set_option_parents(parents)
     if gest:

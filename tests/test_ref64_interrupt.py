@@ -61,11 +61,11 @@ def case_ids(cases):
     return [f"b{b}-{c[0]}-{c[1]}-{c[2]}opt-{c[9]}" for c, b in cases]
 
 
-def interrupt_sweep_case(make, cfg, block_envs, steps=(0, 1, 2)):
+def interrupt_sweep_case(make, cfg, block_envs, steps=(0, 1, 2), seed=None):
     """One configuration of tests/test_ref64_oracle.py's sweep with interruption: fresh pre-states every step, a share of the option
     runners seated inside their sets. Asserts that the case is not vacuous; returns (layouts, interrupted, ambiguous)."""
     map_name, n, nopt, parents, gest, period, floor, eps, base, dist = cfg
-    r = make(map_name, n, nopt, seed=11 + n, env_id_base=base, parents=parents, gest=gest, reoffer_period=period,
+    r = make(map_name, n, nopt, seed=11 + n if seed is None else seed, env_id_base=base, parents=parents, gest=gest, reoffer_period=period,
              update_count_floor=floor, epsilon=eps)
     enabled = ((1 << (nopt + 1)) - 2) & ~gest
     clf = tree_classifiers(r.map)[:nopt + 1] if parents is not None else chain_classifiers(r.map, nopt)

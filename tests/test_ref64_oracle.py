@@ -120,12 +120,12 @@ def assert_rarely_ambiguous(n_amb, n_env_steps, msg=""):
 
 
 @pytest.mark.parametrize("cfg,block_envs", CASES, ids=[f"b{b}-{c[0]}-{c[1]}-{c[2]}opt-{c[9]}" for c, b in CASES])
-def sweep_case(make, cfg, block_envs, steps=(0, 1, 2)):
+def sweep_case(make, cfg, block_envs, steps=(0, 1, 2), seed=None):
     """One configuration of the sweep: fresh pre-states every step (errors do not pile up), both env-order layouts where
-    the option mix calls for them."""
+    the option mix calls for them. `steps` and `seed` (default 11 + N) may be any 64-bit values (test_wide_identity.py)."""
     map_name, n, nopt, parents, gest, period, floor, eps, base, dist = cfg
-    runner = make(map_name, n, nopt, seed=11 + n, env_id_base=base, parents=parents, gest=gest, reoffer_period=period,
-                  update_count_floor=floor, epsilon=eps)
+    runner = make(map_name, n, nopt, seed=11 + n if seed is None else seed, env_id_base=base, parents=parents, gest=gest,
+                  reoffer_period=period, update_count_floor=floor, epsilon=eps)
     enabled = ((1 << (nopt + 1)) - 2) & ~gest
     clf = tree_classifiers(runner.map)[:nopt + 1] if parents is not None else chain_classifiers(runner.map, nopt)
     rng = np.random.default_rng(n * 7 + nopt)
@@ -255,9 +255,10 @@ def edge_gestation_has_no_timeout(make, n=512):
     assert out["n_k"][2] > 50
 
 
-def edge_reoffer_stagger_uses_global_id(make, n=256):
-    """An env staying out of option k (option_id = -k) is offered k again when (t + global env id) mod reoffer_period == 0."""
-    r = make("pinball_simple", n, 1, seed=7, env_id_base=4097, epsilon=0.0, reoffer_period=4)
+def edge_reoffer_stagger_uses_global_id(make, n=256, seed=7, env_id_base=4097, period=4, steps=(0, 1)):
+    """An env staying out of option k (option_id = -k) is offered k again when (t + global env id) mod reoffer_period == 0
+    (the sum taken mod 2^64: test_wide_identity.py passes counters and ids round 2^32 and 2^64)."""
+    r = make("pinball_simple", n, 1, seed=seed, env_id_base=env_id_base, epsilon=0.0, reoffer_period=period)
     clf = chain_classifiers(r.map, 1)
     rng = np.random.default_rng(5)
     pre = pre_state(r.map, n, 1, rng, max_ep=60, max_opt=25)
@@ -267,11 +268,12 @@ def edge_reoffer_stagger_uses_global_id(make, n=256):
     pre["vx"][:] = 0.0; pre["vy"][:] = 0.0; pre["ep_steps"][:] = 0
     pre["option_id"][:] = -1
     W = random_weights(2, 6, std=0.05)
-    for t in (0, 1):
+    for t in steps:
         out, got, _ = check_step(r, pre, W, clf, t, 0b10)
         stays = out["stay"]
-        assert 0.6 * n < stays.sum() < 0.9 * n
-        assert not stays[((t + 4097 + np.arange(n)) % 4) == 0].any()
+        assert (1 - 1 / period - 0.15) * n < stays.sum() < (1 - 1 / period + 0.15) * n
+        offered = np.array([(t + env_id_base + e) % 2 ** 64 % period == 0 for e in range(n)])
+        assert not stays[offered].any()
 
 
 def edge_out_of_range_ids(make, n=512):
