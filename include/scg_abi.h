@@ -81,12 +81,18 @@ const char *scg_last_error(const scg_ctx *ctx);
 
 int scg_create(scg_ctx **out, const scg_config *cfg);
 int scg_destroy(scg_ctx *ctx);
-/* change hyper-parameters between steps (n_envs / n_options / device are fixed at create) */
+/* change hyper-parameters between steps (n_envs / n_options / device are fixed at create). Validated before anything is assigned:
+ * a refused call (SCG_ERR_INVALID: update_count_floor < 0, reoffer_period negative or no power of two; the same two checks as
+ * scg_create) changes nothing, and every field of an accepted one holds from the next launch of any entry point on.
+ * Domains the fields are defined on: gamma in [0, 1], alpha >= 0, epsilon in [0, 1], r_option_success any finite value,
+ * max_episode_steps >= 1, max_option_steps >= 1, update_count_floor >= 0, reoffer_period 0 or a power of two up to 2^30 (values
+ * outside the first six are not validated and have no defined meaning). */
 int scg_set_hparams(scg_ctx *ctx, float gamma, float alpha, float epsilon, float r_option_success,
                     int32_t max_episode_steps, int32_t max_option_steps, int32_t update_count_floor, int32_t reoffer_period);
 
 /* SPEC §1.1. All HOST pointers, copied. edges[n_edges][8], starts[n_starts][2], scale[1296].
- * map_scalars = {R, hstep, R2, TX, TY, TR2}. */
+ * map_scalars = {R, hstep, R2, TX, TY, TR2}. May be called again between steps: the next launch then sees the new map only
+ * (edge count, start list and its length, cell masks); the env states are the caller's and must be valid for it. */
 int scg_set_map(scg_ctx *ctx, const float *edges, int32_t n_edges, const float *starts, int32_t n_starts,
                 const float map_scalars[6], const float *scale);
 

@@ -68,10 +68,7 @@ class ScgContext:
         _lib.check(self.lib.scg_create(C.byref(self._ctx), C.byref(self.cfg)), None, "scg_create")
         self.scale = fourier_scale_table()
         self.parents = np.arange(-1, n_options, dtype=np.int32).clip(0)      # default chain k -> k-1
-        edges, starts, sc = pmap.edges, np.ascontiguousarray(pmap.starts, np.float32), pmap.scalars
-        self._call("scg_set_map", edges.ctypes.data_as(C.c_void_p), len(edges),
-                   starts.ctypes.data_as(C.c_void_p), len(starts), sc.ctypes.data_as(C.c_void_p),
-                   self.scale.ctypes.data_as(C.c_void_p))
+        self.set_map(pmap)
 
     # ------------------------------------------------------------------ plumbing
     def _call(self, name: str, *args) -> None:
@@ -100,14 +97,29 @@ class ScgContext:
         except Exception:
             pass
 
+    _HPARAMS = ("gamma", "alpha", "epsilon", "r_option_success", "max_episode_steps", "max_option_steps",
+                "update_count_floor", "reoffer_period")          # what scg_set_hparams takes (the rest is fixed at create)
+
     def set_hparams(self, **kw) -> None:
-        for k, v in kw.items():
-            if not hasattr(self.cfg, k):
+        """Change hyper-parameters between steps. A refused call changes nothing: neither the library's settings nor `cfg`."""
+        for k in kw:
+            if k not in self._HPARAMS:
                 raise ScgError(f"unknown hyper-parameter {k}")
-            setattr(self.cfg, k, v)
-        c = self.cfg
+        c = ScgConfig.from_buffer_copy(self.cfg)            # the new settings on a copy: `cfg` follows only an accepted call
+        for k, v in kw.items():
+            setattr(c, k, v)
         self._call("scg_set_hparams", c.gamma, c.alpha, c.epsilon, c.r_option_success,
                    c.max_episode_steps, c.max_option_steps, c.update_count_floor, c.reoffer_period)
+        self.cfg = c
+
+    def set_map(self, pmap: PinballMap) -> None:
+        """SPEC §1.1: the map (edges, start list, scalars) of every following step, between steps. Env states are the caller's:
+        they must be valid for the new map."""
+        edges, starts, sc = pmap.edges, np.ascontiguousarray(pmap.starts, np.float32), pmap.scalars
+        self._call("scg_set_map", edges.ctypes.data_as(C.c_void_p), len(edges),
+                   starts.ctypes.data_as(C.c_void_p), len(starts), sc.ctypes.data_as(C.c_void_p),
+                   self.scale.ctypes.data_as(C.c_void_p))
+        self.map = pmap
 
     # ------------------------------------------------------------------ fused step-batch
     def _step_flags(self, learn: bool, apply: bool, interrupt: bool = False) -> int:

@@ -1436,11 +1436,13 @@ int scg_destroy(scg_ctx *c) {
 int scg_set_hparams(scg_ctx *c, float gamma, float alpha, float epsilon, float r_option_success,
                     int32_t max_episode_steps, int32_t max_option_steps, int32_t update_count_floor, int32_t reoffer_period) {
     if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_set_hparams: null ctx");
+    // validate first: a refused call changes nothing (the same two checks as scg_create)
+    if (update_count_floor < 0) return fail(c, SCG_ERR_INVALID, "scg_set_hparams: update_count_floor must be >= 0");
+    if (reoffer_period < 0 || (reoffer_period & (reoffer_period - 1))) return fail(c, SCG_ERR_INVALID, "scg_set_hparams: reoffer_period must be a power of two (or 0)");
     c->cfg.gamma = gamma; c->cfg.alpha = alpha; c->cfg.epsilon = epsilon;
     c->cfg.r_option_success = r_option_success;
     c->cfg.max_episode_steps = max_episode_steps; c->cfg.max_option_steps = max_option_steps;
-    c->cfg.update_count_floor = update_count_floor < 0 ? 0 : update_count_floor;
-    if (reoffer_period < 0 || (reoffer_period & (reoffer_period - 1))) return fail(c, SCG_ERR_INVALID, "scg_set_hparams: reoffer_period must be a power of two (or 0)");
+    c->cfg.update_count_floor = update_count_floor;
     c->cfg.reoffer_period = reoffer_period;
     return SCG_OK;
 }

@@ -220,7 +220,7 @@ class StepModel:
         amb |= amb_b
         # (t + g) mod 2^64 in Python ints (t = 2^64 - 1 overflows int64), g the 64-bit two's complement of env_id_base + e
         tg = [(int(t) + self.env_id_base + e) % 2 ** 64 for e in range(n)]
-        stagger = np.array([v % self.period != 0 for v in tg], bool)
+        stagger = np.array([v % max(self.period, 1) != 0 for v in tg], bool)          # §4.2: a period of 0 means 1
         stay = ~keep & (cand >= 1) & (done == 0) & (oid == -cand) & stagger
         entering = ~keep & (cand >= 1) & ~stay
 
@@ -290,7 +290,7 @@ class StepModel:
         n_k = np.zeros(nvf, np.int64)
         resolution = np.full((nvf, NACT), np.inf)
         gest_succ = np.zeros(nvf, np.int64)
-        items = {}
+        items, item_targets, item_rewards = {}, {}, {}
         for k in range(nvf):
             if k == 0:
                 upd = np.ones(n, bool)
@@ -314,6 +314,7 @@ class StepModel:
             idx = np.nonzero(upd)[0]
             n_k[k] = len(idx)
             items[k] = idx
+            item_targets[k], item_rewards[k] = target[idx], np.asarray(r, np.float64)[idx]
             nblk = max(1, -(-n // 256))
             Lg = L_BLOCK + -(-nblk // 16)
             for act in range(NACT):
@@ -336,7 +337,8 @@ class StepModel:
                 W_next[k] = W64[k] + st * self.scale[None, :] * G[k]
                 W_tol[k] = st * self.scale[None, :] * (G_tol[k] + 4 * U32 * np.abs(G[k])) + 2 * U32 * np.abs(W_next[k])
 
-        out.update(G=G, G_tol=G_tol, n_k=n_k, W=W_next, W_tol=W_tol, gest_succ=gest_succ, resolution=resolution, items=items)
+        out.update(G=G, G_tol=G_tol, n_k=n_k, W=W_next, W_tol=W_tol, gest_succ=gest_succ, resolution=resolution, items=items,
+                   item_targets=item_targets, item_rewards=item_rewards)
         return out
 
 
