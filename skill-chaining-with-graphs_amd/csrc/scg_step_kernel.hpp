@@ -24,6 +24,80 @@
 // Every sum has the pinned order of SPEC §3.1 / §5 (no atomics on data): the CPU oracle reproduces every bit.
 #pragma once
 
+template <typename T>
+__device__ __forceinline__ void gstore(T *p, T v) { *p = v; }
+
+// 16-byte WRITE-THROUGH store (sc1) for data that only the NEXT launch reads — the slabs: 27 MB per step-batch. A plain store
+// leaves the lines dirty in the XCD's L2 and the kernel boundary then waits for their write-back (MI355X_MICROARCH.md, "boundary":
+// + B / 6 TB/s); written through, they are in the memory-side cache by then, where the reduce launch (other XCDs) reads them
+// anyway: +1.1 % env-steps/s. (`nt` stores, round 2, bypassed that cache too and cost the reduce launch 5.7 us.)
+// The trailing s_nop is part of the instruction's contract here: gfx9 reads the data VGPRs of a store wider than 8 bytes a
+// few cycles AFTER issue, and a vector write to one of them in the next two wait states corrupts the stored value. hipcc's
+// hazard recognizer pads its own stores; inline asm is opaque to it (round 4: the compiler reused v[26:27] of the data for the
+// next address right behind the store and 4 x 8 entries of a tile came out as address bits — tools/debug_u2.py found it).
+__device__ __forceinline__ void store_wt(float *p, f4v v) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 2" :: "v"(p), "v"(v) : "memory");
+}
+
+constexpr int OREC = 4;        // float4 per result line (64 bytes): [0] state', [1] {reward, bits, counters}, [2..3] Q(s', .) of the VF acting next
+
+struct StepArgs {
+    // env state (FUSED: in/out; TRANS/QVAL: in)
+    float *x, *y, *vx, *vy;
+    int32_t *option_id, *opt_steps, *ep_steps;
+    int32_t *hist_next;        // [rows of 256 envs][HSTRIDE] counts of the SORT KEYS (sort_key) this step leaves (null = off)
+    float4 *qalt;              // FUSED: [positions][2] SPEC §4.2: the root's Q(s', .) of an env about to enter an option (read by commit_row if the env is declined)
+    float4 *outrec;            // FUSED: [positions][OREC] per-env results in env-ORDER position (one 64-byte line:
+                               // state', {reward, bits, counters}, Q(s', .) of the VF acting next), committed to the
+                               // caller's arrays by commit_row (coalesced) instead of 4-byte scatters from here
+    float *qcache;                 // [5][n]  (QVAL: output q)
+    uint8_t *action;               // FUSED: out; TRANS: in
+    float *reward;                 // FUSED: out; TRANS: in (r)
+    uint8_t *done;
+    const float *cont_in;          // TRANS
+    const float *xn, *yn, *vxn, *vyn;   // TRANS
+    const float *W;                // [n_vf][5][1296] (QVAL: one VF)
+    const float *clf;              // [n_vf][8]
+    const float *edges;            // device [n_edges][8]
+    const uint64_t *cellmask;      // device [32*32][4] candidate-edge masks per grid cell
+    const int32_t *perm;           // FUSED: envs in (option_id, env) order (SPEC §5); NULL = identity
+    float *ring_x, *ring_y;        // SPEC §7 trace buffers (NULL = off)
+    uint8_t *events;
+    int32_t *ev_len;
+    int32_t ring_mask;             // ring_len - 1
+    const float *starts;           // device [n_starts][2]
+    float *slabs;                  // [nblk][n_vf][5][1296]
+    int32_t *cnts;                 // [nblk][n_vf]
+    unsigned long long *stamps;    // diagnostic build only
+    uint32_t *async_word;          // host-visible sticky status word (a hand-off poll that runs out is reported there)
+    int32_t *fail_flag;            // ... and its device-side twin: the reduce launch of the same step reads it (no apply, no commit)
+    int32_t n, n_vf, k_lo, k_hi;
+    uint32_t enabled, learn;       // learn: 1 = learning step
+    uint32_t gest;                 // SPEC §4.4: options in gestation (classifier known, not selectable, learning off-policy)
+    int32_t *gest_succ;            // [n_vf] successes seen from inside a gestating option's initiation set (atomic counts)
+    uint32_t parents;              // 3 bits per option k at [3k, 3k+3): target option of k (0 = the task goal)
+    uint64_t t, seed;
+    int64_t env_base;
+    float gamma, epsilon, r_succ;
+    int32_t max_ep, max_opt;
+    uint32_t reoffer_mask;         // SPEC §4.2: reoffer_period - 1 (0: an option is offered every step)
+    MapScalars ms;
+};
+
+// Workgroup barrier for LDS hand-offs only. __syncthreads() carries a workgroup-scope release fence, which on
+// gfx9 means s_waitcnt vmcnt(0): every barrier after a global store waits for the store to be acknowledged.
+// Nothing in td_kernel passes data between threads through global memory, so the barriers only need this wave's
+// LDS traffic done.
+__device__ __forceinline__ void block_lds_sync() {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+__device__ __forceinline__ bool in_set(const StepArgs &A, int k, float x, float y) {
+    if (k < 1 || k >= A.n_vf) return false;
+    if (!((A.enabled >> k) & 1u)) return false;
+    return clf_z(A.clf + CLF_STRIDE * k, x, y) > 0.0f;
+}
+
 constexpr int P_WAVES = BLOCK_ENVS / 64;      // phase P: one lane per env on full waves
 constexpr int LIST0 = P_WAVES;                // waves LIST0 .. LIST0 + LIST_WAVES - 1 build the passes' flags and lists
 constexpr int HELPER0 = 7;                    // waves HELPER0.. work under phase P (learning steps)

@@ -27,7 +27,7 @@ lib.scg_diag_stamps.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
 B = lib.scg_block_envs(); nblk = n // B
 lib.scg_diag_stamps(ctx, None, 1)
 def env_order(key):
-    """SPEC §5's CHUNKED layout restated on the host (csrc/scg_kernels.hip order_layout / order_posk / order_pos0): every block starts with at most c envs of
+    """SPEC §5's CHUNKED layout restated on the host (csrc/scg_order.hpp order_layout / order_posk / order_pos0): every block starts with at most c envs of
     ONE option's run and is filled with root-keyed envs behind them; ranks inside a key are by env id. Returns order[pos] = env."""
     nk = 7
     tot = np.bincount(key, minlength=nk)
