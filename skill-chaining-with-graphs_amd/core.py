@@ -219,7 +219,8 @@ class ScgContext:
             cs = stats.c_struct()
         elif one_episode:
             raise ScgError("rollout: one_episode needs stats (its `finished` flags)")
-        flags = (_lib.ROLLOUT_BEGIN if begin else 0) | (_lib.ROLLOUT_ONE_EPISODE if one_episode else 0)
+        flags = ((_lib.ROLLOUT_BEGIN if begin else 0) | (_lib.ROLLOUT_ONE_EPISODE if one_episode else 0)
+                 | (_lib.ROLLOUT_BEGIN_AT if begin_at else 0))
         if interrupts is not None and not interrupt:
             raise ScgError("rollout: interrupts without interrupt=True")
         if interrupt:
@@ -227,28 +228,20 @@ class ScgContext:
                 interrupts = stats.interrupts
             if interrupts is not None:
                 self._chk(interrupts, torch.int32, self.n_vf * N, "interrupts")
-            rc = None if record is None else self._chk_record(record, N, n_steps + (1 if begin or begin_at else 0), "rollout")
-            flags |= _lib.ROLLOUT_BEGIN_AT if begin_at else 0
-            self._call("scg_rollout_interrupt", _ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id),
-                       _ptr(st.opt_steps), _ptr(st.ep_steps), _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done),
-                       _ptr(W), _ptr(clf), C.c_uint32(enabled_mask), C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags),
-                       None if cs is None else C.byref(cs), None if interrupts is None else _ptr(interrupts),
-                       None if rc is None else C.byref(rc), self._stream())
+        rc = None if record is None else self._chk_record(record, N, n_steps + (1 if begin or begin_at else 0), "rollout")
+        # the arguments every entry point starts with; each appends its own tail
+        head = (_ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id), _ptr(st.opt_steps), _ptr(st.ep_steps),
+                _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done), _ptr(W), _ptr(clf), C.c_uint32(enabled_mask),
+                C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags), None if cs is None else C.byref(cs))
+        rc_ref = None if rc is None else C.byref(rc)
+        if interrupt:
+            self._call("scg_rollout_interrupt", *head, None if interrupts is None else _ptr(interrupts), rc_ref, self._stream())
             if stats is not None and interrupts is stats.interrupts:
                 stats.interrupting = True
-            return
-        if record is not None or begin_at:
-            rc = None if record is None else self._chk_record(record, N, n_steps + (1 if begin or begin_at else 0), "rollout")
-            flags |= _lib.ROLLOUT_BEGIN_AT if begin_at else 0
-            self._call("scg_rollout_record", _ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id),
-                       _ptr(st.opt_steps), _ptr(st.ep_steps), _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done),
-                       _ptr(W), _ptr(clf), C.c_uint32(enabled_mask), C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags),
-                       None if cs is None else C.byref(cs), None if rc is None else C.byref(rc), self._stream())
-            return
-        self._call("scg_rollout", _ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id), _ptr(st.opt_steps),
-                   _ptr(st.ep_steps), _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done), _ptr(W), _ptr(clf),
-                   C.c_uint32(enabled_mask), C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags),
-                   None if cs is None else C.byref(cs), self._stream())
+        elif record is not None or begin_at:
+            self._call("scg_rollout_record", *head, rc_ref, self._stream())
+        else:
+            self._call("scg_rollout", *head, self._stream())
 
     def option_trials(self, x: torch.Tensor, y: torch.Tensor, vx: torch.Tensor, vy: torch.Tensor, option: torch.Tensor,
                       W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, out, record=None) -> None:

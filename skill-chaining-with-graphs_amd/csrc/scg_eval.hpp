@@ -23,6 +23,13 @@ constexpr int E_TAB_FLOATS = 36 * 16 + 16 * AS;                // one wave's tab
 constexpr int E_TG = 4;                                        // ... of the LDS-fed contraction
 constexpr int EO_TG = 3;                                       // ... of the contraction from memory (register budget: 9 per tile)
 
+// four floats from a 4-byte-aligned address, as one 16-byte load
+__device__ __forceinline__ f4v load4_unaligned(const float *p) {
+    struct __attribute__((packed, aligned(4))) F4U { float x, y, z, w; };
+    const F4U u = *reinterpret_cast<const F4U *>(p);
+    return (f4v){u.x, u.y, u.z, u.w};
+}
+
 // entry (tile t, k-block kb, lane ln) of the A-operand layout = W_k[16 t + (ln & 15)][9 (ln >> 4) + kb] = W_k[src]; rows >= 180 are zeros (false)
 __device__ __forceinline__ bool w_a_src(int t, int kb, int ln, int &src) {
     const int row = 16 * t + (ln & 15);
@@ -159,14 +166,12 @@ __device__ __forceinline__ void contract_lds(int wofs, const float (&B)[9], floa
 // W[16 t + n16][9 g .. 9 g + 8] (two 16-byte loads at 4-byte-aligned addresses and one float; rows >= 180: zeros)
 template <int TG>
 __device__ __forceinline__ void contract_mem(const float *Wk, const float (&B)[9], float (&qo)[NACT], int n16, int g, const float *ab_lane) {
-    struct __attribute__((packed, aligned(4))) F4U { float x, y, z, w; };
     contract_with<TG>([&](int t, f4v &a0, f4v &a1, float &a8) {
         const int row = 16 * t + n16;
         a0 = (f4v){0.0f, 0.0f, 0.0f, 0.0f}; a1 = a0; a8 = 0.0f;
         if (row < NACT * 36) {
             const float *pw = Wk + row * 36 + 9 * g;
-            const F4U u0 = *reinterpret_cast<const F4U *>(pw), u1 = *reinterpret_cast<const F4U *>(pw + 4);
-            a0 = (f4v){u0.x, u0.y, u0.z, u0.w}; a1 = (f4v){u1.x, u1.y, u1.z, u1.w}; a8 = pw[8];
+            a0 = load4_unaligned(pw); a1 = load4_unaligned(pw + 4); a8 = pw[8];
         }
     }, B, qo, g, ab_lane);
 }

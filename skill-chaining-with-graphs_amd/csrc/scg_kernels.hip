@@ -5,6 +5,7 @@
 //   scg_eval.hpp             the per-env step and the E unit shared by the step, rollout and trial kernels
 //   scg_step_kernel.hpp      StepArgs + td_kernel: one step-batch (SPEC §5) = td_kernel<FUSED> -> the reduce launch. A workgroup = 16
 //                            wavefronts owns 256 consecutive positions of the option-sorted env order and the whole LDS of its CU
+//   scg_wave_phases.hpp      the rollout / trial launch geometry and the phases the two kernels share (included by the next header)
 //   scg_rollout_kernel.hpp   rollout_kernel: K acting steps (SPEC §8) in one launch, a fixed range of envs per workgroup
 //   scg_trial_kernel.hpp     trial_kernel: option trials (SPEC §9) with the rollout's geometry
 //   scg_order.hpp            SPEC §5 env order: sort key, layout of the option runs, the stand-alone sort (sort_hist / sort_scatter,

@@ -13,14 +13,7 @@
 // State, qcache and counters stay in registers across the steps and are written once at the end. Finished envs (ONE_EPISODE)
 // and envs beyond N drop out of the lists; a workgroup with nothing left to step leaves the loop.
 #pragma once
-
-constexpr int RO_WAVES = 8;                    // waves per workgroup
-constexpr int RO_THREADS = RO_WAVES * 64;
-constexpr int RO_MAX_EPW = 32;                 // envs per wave (launch parameter epw in 2..32, a power of two)
-constexpr int RO_MAX_ENVS = RO_WAVES * RO_MAX_EPW;
-constexpr int RO_WAVE_FLOATS = E_TAB_FLOATS;   // per wave: tables of one unit (E) / the physics' pair list + states (P)
-static_assert(PITEMS + 4 * 64 + 16 <= RO_WAVE_FLOATS, "the pair list, the states and the goal flags fit a wave's table area");
-static_assert(RO_MAX_ENVS <= 256, "list entries are 8-bit env indices");
+#include "scg_wave_phases.hpp"
 
 struct RolloutArgs {
     float *x, *y, *vx, *vy;
@@ -77,22 +70,6 @@ struct Ctr16 {
     }
 };
 static_assert(SCG_ROLLOUT_MAX_STEPS + 1 < 65536, "16-bit launch counters");
-
-// the kernel arguments through an opaque copy of the argument pointer: the record's pointers are fetched at the store site this
-// way (as the exit fetches the outputs); kept live from the entry they would sit in scalar registers across the whole step loop
-template <typename Args>
-__device__ __forceinline__ const Args *kernel_args() {
-    const Args *K = (const Args *)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(K));
-    return K;
-}
-// len of env e (0: skipped) when e lies in the record's window. The record is taken BY VALUE wherever it is read: through a
-// reference the compiler cannot tell the record's own stores from the kernel arguments and reloads every pointer after each
-// store, one memory round trip at a time
-__device__ __forceinline__ void record_len(const scg_record R, int e, bool mine, int len) {
-    const int r = e - R.first;
-    if (mine && r >= 0 && r < R.n) R.len[r] = len;
-}
 
 // <false, RolloutArgs>: scg_rollout's kernel. <true, RolloutRecArgs>: the same steps, plus SPEC §10's rows of the envs in the
 // record's window, and BEGIN_AT (scg_rollout_record). <false, RolloutIntArgs> / <true, RolloutIntRecArgs>: the same with
@@ -177,18 +154,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         if (valid && !is_begin) a = act_spec(u, qc, A.epsilon);
         float px = sx, py = sy, pvx = svx, pvy = svy, rew = 0.0f;
         bool goal = false;
-        if (!is_begin) {                                       // (wave-uniform)
-            bool pr;
-            const bool phys = valid;
-            uint32_t *items = reinterpret_cast<uint32_t *>(sw);
-            float *xs = sw + PITEMS;
-            uint8_t *gfl = reinterpret_cast<uint8_t *>(sw + PITEMS + 4 * 64);
-            const int groups = pinball_wave_prepare_any(s_edges, A.cellmask, A.ms, phys, px, py, pvx, pvy, a, goal, pr, items, xs, 64);
-            wave_lds_sync();
-            for (int q = 0; q < groups; ++q) pinball_wave_group(s_edges, A.ms, items + 64 * q, xs, 64, gfl);
-            wave_lds_sync();
-            rew = pinball_wave_finish(pr, px, py, pvx, pvy, a, goal, xs, 64, gfl);
-        }
+        if (!is_begin) rew = wave_physics(s_edges, A.cellmask, A.ms, sw, valid, px, py, pvx, pvy, a, goal);      // (wave-uniform)
         const int o = (oid >= 1 && oid < A.n_vf) ? oid : 0;
         const int eps1 = eps + 1;
         int dn = 0;
@@ -209,9 +175,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
             if constexpr (INT) ic = keep ? select_option(A.parents, inB, A.enabled) : 0;
             stay = reoffer_stay(keep, cand, dn, is_begin ? 0 : oid, t, gid, A.reoffer_mask);
             on = stay ? 0 : cand;
-            const float sh[4] = {nx, ny, fmaf(nvx, 0.25f, 0.5f), fmaf(nvy, 0.25f, 0.5f)};
-#pragma unroll
-            for (int d = 0; d < 4; ++d) s_z1[il][d] = sincospi_cs(sh[d]);
+            store_z1(s_z1[il], nx, ny, nvx, nvy);
         }
         const bool entering = valid && !keep && on >= 1;
         // compaction: slot 0 -> the list of VF `on`, slot 1 (entering; INT: keeping too) -> the root's list. An env is entering
@@ -223,7 +187,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
             const int n0 = __popcll(b0), n1 = __popcll(b1);
             if (n0 + n1 == 0) continue;                         // (wave-uniform)
             int base = 0;
-            if (lane == 0) base = atomicAdd(&s_cnt[par][k], n0 + n1);
+            if (lane == 0) base = atomicAdd(&s_cnt[par][k], n0 + n1);       // ONE atomic for both slots (the trial's single append: list_append)
             base = __shfl(base, 0, 64);
             const uint64_t below = (1ull << lane) - 1ull;
             if (w0) s_list[k][base + __popcll(b0 & below)] = (uint16_t)il;
@@ -279,10 +243,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
                 float q0[NACT];
 #pragma unroll
                 for (int aa = 0; aa < NACT; ++aa) q0[aa] = s_qv[1][aa][il];
-                float mc = qa[0], m0 = q0[0];
-#pragma unroll
-                for (int aa = 1; aa < NACT; ++aa) { mc = fmaxf(mc, qa[aa]); m0 = fmaxf(m0, q0[aa]); }
-                declined = !(mc >= m0);
+                declined = !gate_holds(qa, q0);
                 if (declined) {
 #pragma unroll
                     for (int aa = 0; aa < NACT; ++aa) qa[aa] = q0[aa];
@@ -352,13 +313,11 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         }
     }
 
-    // ---- exit: the stepped envs' results, once. The output pointers are fetched from the kernel arguments again here, through
-    // an opaque copy of the argument pointer: otherwise the compiler keeps the 21 pointers it loaded at entry live in scalar
-    // registers across the whole step loop, where they crowd the loop's own scalars out into spill slots
+    // ---- exit: the stepped envs' results, once. The output pointers are fetched from the kernel arguments again here (kernel_args):
+    // otherwise the compiler keeps the 21 pointers it loaded at entry live in scalar registers across the whole step loop
     if constexpr (REC) record_len(kernel_args<RolloutRecArgs>()->rec, e, mine, nrow);     // (skipped: 0)
     if (skip) return;
-    const RolloutArgs *K = (const RolloutArgs *)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(K));
+    const RolloutArgs *K = kernel_args<RolloutArgs>();
     K->x[e] = sx; K->y[e] = sy; K->vx[e] = svx; K->vy[e] = svy;
 #pragma unroll
     for (int a = 0; a < NACT; ++a) K->qcache[(size_t)a * N + e] = qc[a];

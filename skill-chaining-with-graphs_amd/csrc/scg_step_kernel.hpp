@@ -217,7 +217,6 @@ __device__ __forceinline__ int zero_i() {
 // reload sites at pass level (16 MB of scratch writes per launch) instead of 2 (round 5).
 __device__ __attribute__((noinline)) void stage_w_cold(const float *Wk, float *s_dst, int tid) {
     // (all THREADS threads; every thread's loads are issued before its first LDS store: one memory round trip)
-    struct __attribute__((packed, aligned(4))) F4U { float x, y, z, w; };
     f4v *dst4 = reinterpret_cast<f4v *>(s_dst);
     constexpr int N4 = 12 * 2 * 64, N1 = 12 * 64;
     static_assert(2 * THREADS >= N4 && THREADS >= N1, "two float4 and one float per thread");
@@ -228,8 +227,7 @@ __device__ __attribute__((noinline)) void stage_w_cold(const float *Wk, float *s
         v[i] = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
         int src;
         if (d < N4 && w_a_src(d >> 7, 4 * ((d >> 6) & 1), d & 63, src)) {
-            const F4U w = *reinterpret_cast<const F4U *>(Wk + src);
-            v[i] = (f4v){w.x, w.y, w.z, w.w};
+            v[i] = load4_unaligned(Wk + src);
         }
     }
     float tl = 0.0f;
@@ -403,7 +401,6 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     auto stage_w_load = [&](const float *Wk, int ht, int nth, WStage &st) {
         // (all of a thread's loads are issued before its first LDS store: one memory round trip per staging, not one per
         //  loop iteration — the helper waves' W_0 took 10k cycles as three dependent load -> store rounds; nth >= 512)
-        struct __attribute__((packed, aligned(4))) F4U { float x, y, z, w; };
         constexpr int N4 = 12 * 2 * 64, N1 = 12 * 64, MAXI = 3, MAXT = 2;
 #pragma unroll
         for (int i = 0; i < MAXI; ++i) {
@@ -411,8 +408,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             st.v[i] = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
             int src;
             if (d < N4 && w_a_src(d >> 7, 4 * ((d >> 6) & 1), d & 63, src)) {
-                const F4U w = *reinterpret_cast<const F4U *>(Wk + src);
-                st.v[i] = (f4v){w.x, w.y, w.z, w.w};
+                st.v[i] = load4_unaligned(Wk + src);
             }
         }
 #pragma unroll

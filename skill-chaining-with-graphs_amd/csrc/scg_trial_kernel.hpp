@@ -1,5 +1,5 @@
 // scg_trial_kernel.hpp — trial_kernel: option trials (SPEC §9) in ONE launch (included by scg_kernels.hip, after
-// scg_rollout_kernel.hpp, whose geometry it shares).
+// scg_rollout_kernel.hpp; the geometry and the phases it shares with rollout_kernel are scg_wave_phases.hpp's).
 //
 // Entry i runs option k = option[i] from s0 = (x, y, vx, vy)[i] until the option terminates. With the weights frozen no trial
 // reads another one's result, so a workgroup owns RO_WAVES * epw consecutive entries for the whole launch, as rollout_kernel
@@ -73,22 +73,11 @@ __global__ __launch_bounds__(RO_THREADS) void trial_kernel(const Args A) {
     if (tid < 2 * MAX_VF) (&s_cnt[0][0])[tid] = 0;
     __syncthreads();
     // the entry pass's lists: Q_k(s0, .)
-    if (run) {
-        const float sh[4] = {sx, sy, fmaf(svx, 0.25f, 0.5f), fmaf(svy, 0.25f, 0.5f)};
-#pragma unroll
-        for (int d = 0; d < 4; ++d) s_z1[il][d] = sincospi_cs(sh[d]);
-    }
+    if (run) store_z1(s_z1[il], sx, sy, svx, svy);
     bool alive = run;
     int par = 0;
 #pragma unroll
-    for (int kk = 1; kk < MAX_VF; ++kk) {
-        const uint64_t b = __ballot(alive && k == kk);
-        if (!b) continue;                                      // (wave-uniform)
-        int base = 0;
-        if (lane == 0) base = atomicAdd(&s_cnt[par][kk], __popcll(b));
-        base = __shfl(base, 0, 64);
-        if (alive && k == kk) s_list[kk][base + __popcll(b & ((1ull << lane) - 1ull))] = (uint16_t)il;
-    }
+    for (int kk = 1; kk < MAX_VF; ++kk) list_append(&s_cnt[par][kk], s_list[kk], alive && k == kk, (uint16_t)il, lane);
 
     float qc[NACT] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     float v0 = 0.0f, ret = 0.0f, dret = 0.0f, gk = 1.0f;
@@ -155,17 +144,8 @@ __global__ __launch_bounds__(RO_THREADS) void trial_kernel(const Args A) {
         int a = NACT - 1;
         if (alive) { env_draw(gid, t, A.seed, u); a = act_spec(u, qc, A.epsilon); }
         float px = sx, py = sy, pvx = svx, pvy = svy;
-        bool goal = false, pr = false;
-        {
-            uint32_t *items = reinterpret_cast<uint32_t *>(sw);
-            float *xs = sw + PITEMS;
-            uint8_t *gfl = reinterpret_cast<uint8_t *>(sw + PITEMS + 4 * 64);
-            const int groups = pinball_wave_prepare_any(s_edges, A.cellmask, A.ms, alive, px, py, pvx, pvy, a, goal, pr, items, xs, 64);
-            wave_lds_sync();
-            for (int q = 0; q < groups; ++q) pinball_wave_group(s_edges, A.ms, items + 64 * q, xs, 64, gfl);
-            wave_lds_sync();
-        }
-        const float rew = pinball_wave_finish(pr, px, py, pvx, pvy, a, goal, sw + PITEMS, 64, reinterpret_cast<uint8_t *>(sw + PITEMS + 4 * 64));
+        bool goal = false;
+        const float rew = wave_physics(s_edges, A.cellmask, A.ms, sw, alive, px, py, pvx, pvy, a, goal);
         bool keep = false;
         if (alive) {
             const int dn = episode_end(goal, steps + 1, A.max_ep);
@@ -179,11 +159,8 @@ __global__ __launch_bounds__(RO_THREADS) void trial_kernel(const Args A) {
             gk = __fmul_rn(gk, A.gamma);
             sx = px; sy = py; svx = pvx; svy = pvy;
             steps += 1;
-            if (keep) {
-                const float sh[4] = {px, py, fmaf(pvx, 0.25f, 0.5f), fmaf(pvy, 0.25f, 0.5f)};
-#pragma unroll
-                for (int d = 0; d < 4; ++d) s_z1[il][d] = sincospi_cs(sh[d]);
-            } else {                                           // first match wins: succ, done, fail (s' left I_k), time-out
+            if (keep) store_z1(s_z1[il], px, py, pvx, pvy);
+            else {                                             // first match wins: succ, done, fail (s' left I_k), time-out
                 outcome = succ ? (int)SCG_TRIAL_SUCCESS : dn ? (int)SCG_TRIAL_EPISODE_END
                         : !((inA >> k) & 1u) ? (int)SCG_TRIAL_LEFT_INITIATION : (int)SCG_TRIAL_TIMEOUT;
                 alive = false;
@@ -206,26 +183,17 @@ __global__ __launch_bounds__(RO_THREADS) void trial_kernel(const Args A) {
             }
         }
 #pragma unroll
-        for (int kk = 1; kk < MAX_VF; ++kk) {
-            const uint64_t b = __ballot(keep && k == kk);
-            if (!b) continue;                                  // (wave-uniform)
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&s_cnt[par][kk], __popcll(b));
-            base = __shfl(base, 0, 64);
-            if (keep && k == kk) s_list[kk][base + __popcll(b & ((1ull << lane) - 1ull))] = (uint16_t)il;
-        }
+        for (int kk = 1; kk < MAX_VF; ++kk) list_append(&s_cnt[par][kk], s_list[kk], keep && k == kk, (uint16_t)il, lane);
     }
 
-    // ---- exit: each output once. The pointers are fetched again through an opaque copy of the argument pointer, as in
-    // rollout_kernel, so that the loop does not hold them in scalar registers
+    // ---- exit: each output once. The pointers are fetched again (kernel_args), as in rollout_kernel, so that the loop does not
+    // hold them in scalar registers
     if constexpr (REC) {
         const scg_record R = kernel_args<TrialRecArgs>()->rec;
         record_len(R, i, mine, min(steps, R.rows));                                  // (not run: 0)
     }
     if (!mine) return;
-    const TrialArgs *K = (const TrialArgs *)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(K));
-    const scg_trial_out &O = K->out;
+    const scg_trial_out &O = kernel_args<TrialArgs>()->out;
     O.outcome[i] = (uint8_t)outcome;
     if (!run) return;
     if (O.steps) O.steps[i] = steps;
