@@ -5,6 +5,7 @@ import torch
 import sc_oracle
 import skill_chaining_with_graphs_amd as scg
 from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
+from bits import assert_bits_equal
 from util import HP, SCALE
 
 
@@ -44,4 +45,7 @@ def assert_state_equal(st_dev, st_np, keys=None, msg=""):
     keys = keys or ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done")
     for k in keys:
         got = getattr(st_dev, k).cpu().numpy()
-        assert np.array_equal(got, st_np[k]), f"{msg} field {k}: {np.sum(got != st_np[k])} of {got.size} differ"
+        if got.dtype == np.float32:                    # by bits: the sign of a zero and every subnormal count, a NaN is a difference
+            assert_bits_equal(got, st_np[k], msg=f"{msg} field {k}:")
+        else:
+            assert np.array_equal(got, st_np[k]), f"{msg} field {k}: {np.sum(got != st_np[k])} of {got.size} differ"

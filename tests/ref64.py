@@ -50,6 +50,17 @@ C_Z = 12 * U32
 # is the probabilistic one of Higham & Mary (2019) with lambda = 8: C_G sqrt(L) U sum_i |delta_i| (|Re AB Re CD| + |Im AB Im CD|)
 C_G = 8.0
 L_BLOCK = 2 * 256 + 16
+# ---- absolute terms: below 2^-126 a binary32 rounding is no longer relative to the value but at most half a unit of the
+# subnormal grid, 2^-150. A tolerance that has to hold for subnormal results adds that once per rounding of the chain.
+SUB = 2.0 ** -150
+# Q of SPEC §3.1: per (c12, part) a chain of 36 fmas (2 * 36 * 36), the 2 * 36 fmas over c12, 4 + 2 + 1 adds
+N_Q = 2 * 36 * 36 + 2 * 36 + 7
+Q_FLOOR = N_Q * SUB
+# sigmoid of SPEC §6 against the exact logistic of the clamped argument, RELATIVE to the value: the two-step reduction of a
+# leaves r with one rounding of a value below 0.35 (n * LN2HI is exact), the degree-7 polynomial truncates exp(r) by
+# 0.35^8 / 8! < 0.1 U and rounds 7 times at values between 0.7 and 1.5, the scaling by 2^n is exact (n >= -126 and
+# p >= 1: e stays normal), then 1 + e and the division: under 12 roundings. z >= 0 gives 1/(1+e), relative to a value >= 1/2.
+C_SIG = 16 * U32
 
 
 def philox4x32_10(c0, c1, c2, c3, k0, k1):
@@ -419,3 +430,55 @@ def q_update_model(s, a, r, cont, sn, Wk):
             ad = np.abs(delta[ii])
             G_tol[act] = d_tol[ii] @ np.abs(phi[ii]) + C_PHI * ad.sum() + C_G * np.sqrt(Lg) * U32 * (ad @ h[ii])
     return G, G_tol
+
+
+def q_update_floor(a, n_vf_blocks=1):
+    """The absolute term of q_update_model's G tolerance where delta, P and G are subnormal, per action [5]: every item of
+    the action carries the floors of Q(s, a) and of max Q(s', .) (Q_FLOOR each), one rounding each for the target's fma and
+    the subtraction, two for P = delta * (AB.re, -AB.im) and two for its fmas into G (|phi|, |AB|, |CD| <= 1); then the
+    block and segment additions, one rounding per block of the segment chain and 16 per segment."""
+    n = len(a)
+    nblk = max(1, -(-n // 256))
+    per_item = 2 * Q_FLOOR + 6 * SUB
+    return np.array([np.sum(np.asarray(a) == act) * per_item + (16 + -(-nblk // 16)) * SUB for act in range(NACT)])
+
+
+def sigmoid_model(z):
+    """SPEC §6's sigmoid in float64: the exact logistic of the argument clamped to |z| <= 87 (`a = max(-|z|, -87)` is part of
+    the formula, so sigmoid(-100) is sigmoid(-87) ~ 1.64e-38 and not 3.7e-44), and its binary32 error bound C_SIG * p."""
+    z = np.clip(np.asarray(z, np.float64), -87.0, 87.0)
+    e = np.exp(-np.abs(z))
+    p = np.where(z >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+    return p, C_SIG * p
+
+
+def fit_model(xy, lab, w, iters, lr, l2):
+    """SPEC §6 in float64: `iters` steps of full-batch gradient descent from w [8]; returns (w, per-weight bound [6]).
+    The gradient descent of tests/test_gpu_ref64.py with a bound that stays meaningful where the sigmoid saturates: the
+    sigmoid is the clamped one with a relative error (C_SIG), and every chain carries the absolute term of its roundings
+    (SUB), so that gradients of 1e-38 and the subnormal weights they produce are resolved. The gradient sum keeps that
+    test's constant (C_G sqrt(M / 8192 + 40) U32 sum |e| |psi|), psi adds 4 roundings (u, v, their products)."""
+    w = np.asarray(w, np.float64).copy()
+    xy, lab = np.asarray(xy, np.float64), np.asarray(lab, np.float64)
+    M = len(lab)
+    u, v = 2.0 * xy[:, 0] - 1.0, 2.0 * xy[:, 1] - 1.0
+    psi = np.stack([np.ones_like(u), u, v, u * u, u * v, v * v], 1)
+    apsi = np.abs(psi)
+    n_sum = -(-M // 8192) + 6 + 15 + 7                  # roundings of one g_j: the chain, the butterfly, 15 + 7 ordered adds
+    carry = np.r_[1.0, np.full(5, 1.0 + lr * l2)]       # a carried error of w_j comes back through l2 w_j (and through z, below)
+    bound = np.zeros(6)
+    for _ in range(iters):
+        z = psi @ w[:6]
+        tz = C_Z * ((apsi + U32) @ np.abs(w[:6])) + apsi @ bound          # binary32 z of the binary32 weights against this z
+        p, tp = sigmoid_model(z)
+        e = p - lab
+        # sigmoid' = p (1 - p) changes by at most e^|dz| over dz; where both arguments are certain to be clamped it is 0
+        te = tp + np.where(np.abs(z) - tz < 87.0, p * (1.0 - p) * np.exp(np.minimum(tz, 50.0)) * tz, 0.0) + U32 * np.abs(e)
+        g = psi.T @ e / M
+        gt = (te @ apsi + (4 + C_G * np.sqrt(M / 8192 + 40)) * U32 * (np.abs(e) @ apsi) + n_sum * SUB) / M
+        reg = np.r_[0.0, l2 * w[1:6]]
+        w_new = w[:6] - lr * (g + reg)
+        # invM, g invM, l2 w, their sum and lr (..): 5 relative roundings and 2 that can be subnormal; then the subtraction
+        bound = carry * bound + lr * (gt + 6 * U32 * (np.abs(g) + np.abs(reg)) + 2 * SUB) + U32 * np.abs(w_new) + SUB
+        w[:6] = w_new
+    return w, bound

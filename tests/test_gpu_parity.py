@@ -7,6 +7,7 @@ import torch
 
 import sc_oracle
 import skill_chaining_with_graphs_amd as scg
+from bits import assert_bits_equal
 from gpu_util import assert_state_equal, dev, make_pair, state_to_device
 from util import chain_classifiers, random_states, random_weights
 
@@ -27,8 +28,9 @@ def test_pinball_step_bit_exact(map_name):
         r_o, g_o = orc.pinball_step(x, y, vx, vy, act)
         r_d, g_d = ctx.pinball_step(d, dev(act))
         for name, a, b in zip("x y vx vy".split(), d, (x, y, vx, vy)):
-            assert np.array_equal(a.cpu().numpy(), b), (it, name)
-        assert np.array_equal(r_d.cpu().numpy(), r_o) and np.array_equal(g_d.cpu().numpy(), g_o)
+            assert_bits_equal(a.cpu().numpy(), b, msg=f"{it} {name}:")
+        assert_bits_equal(r_d.cpu().numpy(), r_o, msg=f"{it} reward:")
+        assert np.array_equal(g_d.cpu().numpy(), g_o)
         if it == 0:
             assert g_o[:64].all() and 0 < g_o.sum() < n
 
@@ -50,8 +52,9 @@ def test_pinball_step_dense_map_four_mask_words_bit_exact():
         r_o, g_o = orc.pinball_step(x, y, vx, vy, act)
         r_d, g_d = ctx.pinball_step(d, dev(act))
         for name, a, b in zip("x y vx vy".split(), d, (x, y, vx, vy)):
-            assert np.array_equal(a.cpu().numpy(), b), (it, name)
-        assert np.array_equal(r_d.cpu().numpy(), r_o) and np.array_equal(g_d.cpu().numpy(), g_o)
+            assert_bits_equal(a.cpu().numpy(), b, msg=f"{it} {name}:")
+        assert_bits_equal(r_d.cpu().numpy(), r_o, msg=f"{it} reward:")
+        assert np.array_equal(g_d.cpu().numpy(), g_o)
 
 
 def test_features_and_q_values_bit_exact():
@@ -59,10 +62,10 @@ def test_features_and_q_values_bit_exact():
     ctx, orc, m = make_pair("pinball_simple", n)
     x, y, vx, vy = random_states(m, n, 3, vmax=2.8)
     d = [dev(a) for a in (x, y, vx, vy)]
-    assert np.array_equal(ctx.features(d).cpu().numpy(), orc.features(x, y, vx, vy))
+    assert_bits_equal(ctx.features(d).cpu().numpy(), orc.features(x, y, vx, vy), msg="features:")
     W = random_weights(1, 4, std=1.0)[0]
     q = ctx.q_values(d, dev(W).view(-1))
-    assert np.array_equal(q.cpu().numpy(), orc.q_values(x, y, vx, vy, W))
+    assert_bits_equal(q.cpu().numpy(), orc.q_values(x, y, vx, vy, W), msg="q_values:")
 
 
 def test_classifier_predict_and_fit_bit_exact():
@@ -76,7 +79,7 @@ def test_classifier_predict_and_fit_bit_exact():
     w_d = dev(w_o.copy())
     orc.fit_initiation(xy, lab, off, w_o, iters=150, lr=3.0, l2=1e-4)
     ctx.fit_initiation(dev(xy).view(-1), dev(lab), dev(off), w_d.view(-1), iters=150, lr=3.0, l2=1e-4)
-    assert np.array_equal(w_d.cpu().numpy(), w_o)
+    assert_bits_equal(w_d.cpu().numpy(), w_o, msg="fitted weights:")
     x, y = xy[:, 0].copy(), xy[:, 1].copy()
     pred = ctx.classifier_predict(dev(x), dev(y), w_d[0].contiguous())
     assert np.array_equal(pred.cpu().numpy(), orc.classifier_predict(x, y, w_o[0]))
@@ -97,7 +100,7 @@ def test_fit_many_examples_and_many_problems_bit_exact():
     w_d = dev(w_o.copy())
     orc.fit_initiation(xy, lab, off, w_o, iters=12, lr=2.0, l2=1e-3)
     ctx.fit_initiation(dev(xy).view(-1), dev(lab), dev(off), w_d.view(-1), iters=12, lr=2.0, l2=1e-3)
-    assert np.array_equal(w_d.cpu().numpy(), w_o)
+    assert_bits_equal(w_d.cpu().numpy(), w_o, msg="fitted weights:")
 
 
 @pytest.mark.parametrize("n,k", [(1, 0), (700, 0), (700, 2)])
@@ -120,8 +123,8 @@ def test_q_update_bit_exact(n, k):
     ctx.q_update(k, [dev(a) for a in (x, y, vx, vy)], dev(act), dev(r), dev(cont),
                  [dev(a) for a in (xn, yn, vxn, vyn)], W_d.view(-1))
     assert n_d.cpu().numpy().tolist() == n_k.tolist()
-    assert np.array_equal(G_d[k].cpu().numpy(), G_o)
-    assert np.array_equal(W_d.cpu().numpy(), W_o)
+    assert_bits_equal(G_d[k].cpu().numpy(), G_o, msg="G:")
+    assert_bits_equal(W_d.cpu().numpy(), W_o, msg="W:")
 
 
 @pytest.mark.parametrize("map_name,n,n_options,steps", [
@@ -149,8 +152,8 @@ def test_fused_step_rollout_bit_exact(map_name, n, n_options, steps):
         ctx.step(st_d, W_d.view(-1), clf_d.view(-1), mask, t)
         assert_state_equal(st_d, st_o, msg=f"t={t}")
         assert np.array_equal(n_d.cpu().numpy(), n_k), t
-        assert np.array_equal(G_d.cpu().numpy(), G), t
-        assert np.array_equal(W_d.cpu().numpy(), W_o), t
+        assert_bits_equal(G_d.cpu().numpy(), G, msg=f"t={t} G:")
+        assert_bits_equal(W_d.cpu().numpy(), W_o, msg=f"t={t} W:")
         seen_done |= set(np.unique(st_o["done"]).tolist())
     if n >= 1000:
         assert {0, 2} <= seen_done                     # time-limit resets happened
@@ -170,13 +173,14 @@ def test_fused_step_act_only_and_split_apply():
     ctx.step(st_d, W_d.view(-1), clf_d.view(-1), mask, 0, learn=False)
     orc.step(st_o, W_o, clf, 0)
     assert_state_equal(st_d, st_o)
-    assert np.array_equal(W_d.cpu().numpy(), W_o)
+    assert_bits_equal(W_d.cpu().numpy(), W_o, msg="W:")
     ctx.step(st_d, W_d.view(-1), clf_d.view(-1), mask, 1, learn=True, apply=False)
     G, n_k = orc.step(st_o, W_o, clf, 1)
-    assert np.array_equal(W_d.cpu().numpy(), W_o) and np.array_equal(G_d.cpu().numpy(), G)
+    assert_bits_equal(W_d.cpu().numpy(), W_o, msg="W:")
+    assert_bits_equal(G_d.cpu().numpy(), G, msg="G:")
     ctx.apply_update(W_d.view(-1), G_d, n_d)
     orc.apply(W_o, G, n_k)
-    assert np.array_equal(W_d.cpu().numpy(), W_o)
+    assert_bits_equal(W_d.cpu().numpy(), W_o, msg="W:")
 
 
 def test_env_order_prepared_by_the_previous_step_and_invalidated_on_outside_writes():
@@ -208,8 +212,8 @@ def test_env_order_prepared_by_the_previous_step_and_invalidated_on_outside_writ
         assert_state_equal(st_d, st_o, msg=f"t={t}")
         if learn:
             orc.apply(W_o, G, n_k)
-            assert np.array_equal(G_d.cpu().numpy(), G), t
-        assert np.array_equal(W_d.cpu().numpy(), W_o), t
+            assert_bits_equal(G_d.cpu().numpy(), G, msg=f"t={t} G:")
+        assert_bits_equal(W_d.cpu().numpy(), W_o, msg=f"t={t} W:")
     assert n_k[1:].sum() > 0
 
 
@@ -231,10 +235,10 @@ def test_packed_gradient_operand_matches_the_split_pair():
         orc.apply(W_o, G, n_k)
         ctx.step(st_d, W_d.view(-1), clf_d.view(-1), mask, t, learn=True, apply=False)
         flat = gp.cpu().numpy()
-        assert np.array_equal(flat[:G.size].reshape(G.shape), G)
-        assert np.array_equal(flat[G.size:], n_k.astype(np.float32))
+        assert_bits_equal(flat[:G.size].reshape(G.shape), G, msg=f"t={t} packed G:")
+        assert_bits_equal(flat[G.size:], n_k.astype(np.float32), msg=f"t={t} packed counts:")
         ctx.apply_update_packed(W_d.view(-1), gp)
-        assert np.array_equal(W_d.cpu().numpy(), W_o), t
+        assert_bits_equal(W_d.cpu().numpy(), W_o, msg=f"t={t} W:")
     assert n_k[1:].sum() > 0
 
 
@@ -257,7 +261,7 @@ def test_order_pinned_slot_sum_is_the_sequential_float_sum(n_slots):
     for r in range(1, n_slots):
         g = (g + slots[r, :per - (nopt + 1)]).astype(np.float32)
     orc.apply(W_o, g.reshape(nopt + 1, 5, 1296), counts.sum(axis=0).astype(np.int32))
-    assert np.array_equal(W_d.cpu().numpy(), W_o)
+    assert_bits_equal(W_d.cpu().numpy(), W_o, msg="W:")
     with pytest.raises(scg.ScgError):
         ctx.apply_update_slots(W_d.view(-1), dev(slots)[:, :-1].contiguous())
 
@@ -304,8 +308,8 @@ def test_env_order_layouts_bit_exact(n, dist):
         ctx.step(st_d, W_d.view(-1), clf_d.view(-1), mask, t)
         assert_state_equal(st_d, st_o, msg=f"t={t}")
         assert np.array_equal(n_d.cpu().numpy(), n_k), t
-        assert np.array_equal(G_d.cpu().numpy(), G), t
-        assert np.array_equal(W_d.cpu().numpy(), W_o), t
+        assert_bits_equal(G_d.cpu().numpy(), G, msg=f"t={t} G:")
+        assert_bits_equal(W_d.cpu().numpy(), W_o, msg=f"t={t} W:")
 
 
 def test_host_checks_fail_before_any_launch():
@@ -347,7 +351,7 @@ def test_skill_tree_rollout_bit_exact_and_graph_export():
         orc.apply(W_o, G, n_k)
         ctx.step(st_d, W_d.view(-1), clf_d.view(-1), mask, t)
         assert_state_equal(st_d, st_o, msg=f"t={t}")
-        assert np.array_equal(W_d.cpu().numpy(), W_o), t
+        assert_bits_equal(W_d.cpu().numpy(), W_o, msg=f"t={t} W:")
         seen |= set(np.unique(st_o["option_id"]).tolist())
     assert {1, 2, 3, 4, 5} <= seen
     for bad in ([0, 2, 1, 0, 0, 0], [0, 0, 0, 3, 0, 0], [0, 0, 0, 0, 0, 9]):      # 1<->2 cycle, self loop, out of range
