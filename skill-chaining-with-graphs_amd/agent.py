@@ -392,7 +392,7 @@ class SkillChainingAgent:
         return {"samples": len(us), "mean_us": sum(us) / len(us), "max_us": max(us)}
 
     # ------------------------------------------------------------------ checkpoint / resume
-    _STATE_FIELDS = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done")
+    _STATE_FIELDS = EnvState.FIELDS
 
     def state_dict(self) -> dict:
         """Everything a bit-identical continuation needs: the env SoA, W, the classifier table, the option graph, the

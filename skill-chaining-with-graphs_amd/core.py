@@ -550,6 +550,8 @@ class ScgContext:
 class EnvState:
     """SoA env batch in HBM (caller-owned torch tensors)."""
 
+    FIELDS = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done")
+
     def __init__(self, n: int, device: torch.device, pmap: PinballMap):
         z = lambda dt: torch.zeros(n, dtype=dt, device=device)
         sx, sy = float(pmap.starts[0][0]), float(pmap.starts[0][1])

@@ -16,10 +16,10 @@ import ctypes.util
 import numpy as np
 
 import sc_oracle
+from skill_chaining_with_graphs_amd.core import EnvState
 from util import disc_weights, random_states, random_weights
 
 NACT, NF, SEG = 5, 1296, 16
-FIELDS = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done")
 
 _libm = C.CDLL(ctypes.util.find_library("m"))
 _libm.fmaf.restype = C.c_float
@@ -119,7 +119,7 @@ def entry_state(m, n, n_opt, seed, run_share, max_episode_steps):
 
 
 def copy_state(st):
-    return {f: np.array(st[f], copy=True) for f in FIELDS}
+    return {f: np.array(st[f], copy=True) for f in EnvState.FIELDS}
 
 
 def step(orc, pre, W, clf, t, enabled, gest=0, interrupt=True, recompute=True):

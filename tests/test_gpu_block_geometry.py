@@ -16,9 +16,8 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(params=[64, 128])
 def small_blocks(request):
-    gpu_util.set_block_envs(request.param)
-    yield request.param
-    gpu_util.set_block_envs(None)
+    with gpu_util.block_build(request.param) as b:
+        yield b
 
 
 def test_fused_rollouts_bit_exact(small_blocks):

@@ -64,14 +64,11 @@ def _frontier_rollout(n, steps, H, l_pos, l_neg, cap, seed):
 
 @pytest.mark.parametrize("block_envs", [256, 64])
 def test_frontier_collect_bit_exact_against_the_model(block_envs):
-    gpu_util.set_block_envs(block_envs)
-    try:
+    with gpu_util.block_build(block_envs):
         cnt = _frontier_rollout(4000, 30, 32, 12, 12, 30000, seed=50)             # roomy buffers
         assert cnt.min() > 0, cnt
         cnt = _frontier_rollout(2000, 16, 8, 6, 7, 150, seed=60)                  # ring_len 8 < L = 13; caps overflow
         assert (cnt == 150).sum() >= 2, cnt
-    finally:
-        gpu_util.set_block_envs(None)
 
 
 def test_frontier_goal_node_equals_the_existing_goal_collector():

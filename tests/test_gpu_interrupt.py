@@ -9,107 +9,42 @@ import numpy as np
 import pytest
 import torch
 
+import interrupt_learning_model as ilm
 import sc_oracle
 import skill_chaining_with_graphs_amd as scg
 from skill_chaining_with_graphs_amd import _lib
-from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
+from skill_chaining_with_graphs_amd.core import EnvState
 from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
 from skill_chaining_with_graphs_amd.trajectory import Trajectory
-from gpu_util import dev, make_pair, state_to_device
-from util import HP, chain_classifiers, disc_weights, random_states, random_weights
+from gpu_util import (as_bytes, assert_same_bits, clone_state, crossing_agent, dev, make_context, make_pair, spy_calls,
+                      state_to_device)
+from util import HP, chain_classifiers, random_env_state, random_states
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done")
 STATS = EpisodeStats.FIELDS
-
-
-def _weights(n_vf, seed, noise=0.05):
-    """Option weights of the root's scale plus noise: V_o and V_0 cross both ways."""
-    W = random_weights(n_vf, seed, std=0.1)
-    rng = np.random.default_rng(seed + 1000)
-    W[1:] = W[0] + (rng.standard_normal(W[1:].shape) * noise).astype(np.float32)
-    return W
-
-
-def _wide_chain(m, n_opt):
-    """Nested discs round the goal, of radius 0.3 (option 1) up to 1.05 (the last option): the outermost holds the maps' start
-    states, so options are entered from the first step of an episode."""
-    clf = np.zeros((n_opt + 1, 8), np.float32)
-    tx, ty, _ = m.target
-    for k in range(1, n_opt + 1):
-        clf[k] = disc_weights(tx, ty, 0.3 + 0.75 * (k - 1) / max(n_opt - 1, 1))
-    return clf
 
 
 def _setup(name, n, n_opt, parents=None, gest=0, seed=3, block=None, **hp):
     m = scg.load_map(name)
-    kw = dict(HP)
-    kw.update(hp)
-    ctx = ScgContext(n, n_opt, m, device=0, seed=seed, block_envs=block, **kw)
-    if parents is not None:
-        ctx.set_option_parents(parents)
-    if gest:
-        ctx.set_gestation(gest)
-    clf = dev(_wide_chain(m, n_opt)).view(-1)
-    W = dev(_weights(n_opt + 1, seed)).view(-1)
+    ctx = make_context(m, n, n_opt, block, parents, gest, seed, **hp)
+    clf = dev(ilm.wide_chain(m, n_opt)).view(-1)
+    W = dev(ilm.crossing_weights(n_opt + 1, seed)).view(-1)
     return ctx, m, W, clf
 
 
 def _state(ctx, m, n, n_opt, seed):
-    rng = np.random.default_rng(seed)
-    st = EnvState(n, ctx.device, m)
-    x, y, vx, vy = random_states(m, n, seed, vmax=1.5)
-    st.x.copy_(dev(x)); st.y.copy_(dev(y)); st.vx.copy_(dev(vx)); st.vy.copy_(dev(vy))
-    st.option_id.copy_(dev(rng.integers(-n_opt, n_opt + 1, n).astype(np.int32)))
-    st.opt_steps.copy_(dev(rng.integers(0, 10, n).astype(np.int32)))
-    st.ep_steps.copy_(dev(rng.integers(0, ctx.cfg.max_episode_steps, n).astype(np.int32)))
-    st.qcache.copy_(dev(rng.standard_normal((5, n)).astype(np.float32)))
-    return st
-
-
-def _clone(st):
-    c = object.__new__(EnvState)
-    c.n = st.n
-    for f in FIELDS:
-        setattr(c, f, getattr(st, f).clone())
-    return c
-
-
-def _bits(a):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def _assert_same(a, b, fields, msg):
-    for f in fields:
-        assert np.array_equal(_bits(getattr(a, f)), _bits(getattr(b, f))), f"{msg}: {f} differs"
-
-
-def _vmax(q):
-    """max over actions in SPEC §5's order (IEEE maxNum, a = 0 first); q [5][m]."""
-    m = q[0].copy()
-    for a in range(1, q.shape[0]):
-        m = np.fmax(m, q[a])
-    return m
+    return state_to_device(random_env_state(m, n, n_opt, seed, id_lo=-n_opt, id_hi=n_opt, opt_steps_hi=10,
+                                            max_episode_steps=ctx.cfg.max_episode_steps), ctx)
 
 
 def _candidates(predict, x, y, n_vf, known, enabled, parents):
-    """SPEC §4.2's cand at s' = (x, y): the smallest enabled option whose initiation set holds s' and whose target region does not."""
-    inB = np.zeros(len(x), np.int64)
+    """SPEC §4.2's cand at s' = (x, y), by ilm.candidates from the known options' membership bits (no bit for the others)."""
+    in_n = np.zeros((n_vf, len(x)), bool)
     for k in range(1, n_vf):
         if (known >> k) & 1:
-            inB |= predict(k, x, y).astype(np.int64) << k
-    tgt = np.zeros_like(inB)
-    for k in range(1, n_vf):
-        p = int(parents[k])
-        if p != 0:
-            tgt |= ((inB >> p) & 1) << k
-    sel = inB & ~tgt & enabled
-    c = np.zeros(len(x), np.int64)
-    for k in range(n_vf - 1, 0, -1):
-        c = np.where((sel >> k) & 1 == 1, k, c)
-    return c
+            in_n[k] = predict(k, x, y) != 0
+    return ilm.candidates(in_n, enabled, parents, n_vf)
 
 
 class Emulator:
@@ -156,7 +91,7 @@ class Emulator:
                 s = [getattr(st, f)[it].contiguous() for f in ("x", "y", "vx", "vy")]
                 q0 = self.ctx.q_values(s, self.W0).cpu().numpy()
                 qo = st.qcache.view(5, self.n)[:, it].cpu().numpy()
-                cut = ~(_vmax(qo) >= _vmax(q0))
+                cut = ~(ilm.vmax(qo) >= ilm.vmax(q0))
                 if cut.any():
                     xs, ys = s[0].cpu().numpy(), s[1].cpu().numpy()
                     c = _candidates(self._predict, xs[cut], ys[cut], n_vf, self.known, self.mask, self.parents)
@@ -194,7 +129,7 @@ def _run_case(name, n, n_opt, mask, gest, parents, eps, splits, mode, seed=3, t0
     ctx, m, W, clf = _setup(name, n, n_opt, parents, gest, seed=seed, epsilon=eps, reoffer_period=4, max_episode_steps=40,
                             max_option_steps=20, **hp)
     st = _state(ctx, m, n, n_opt, seed=n + n_opt)
-    twin = _clone(st)
+    twin = clone_state(st)
     n_vf = n_opt + 1
     s_ref, s_int = EpisodeStats(n_vf, n, ctx.device), EpisodeStats(n_vf, n, ctx.device)
     ref_int = np.zeros((n_vf, n), np.int64)
@@ -208,8 +143,8 @@ def _run_case(name, n, n_opt, mask, gest, parents, eps, splits, mode, seed=3, t0
                     interrupt=True)
         t += K + (1 if (begin or at) and first else 0)
     torch.cuda.synchronize()
-    _assert_same(twin, st, FIELDS, f"{name} {mode}")
-    _assert_same(s_int, s_ref, STATS, f"{name} {mode} stats")
+    assert_same_bits(twin, st, EnvState.FIELDS, f"{name} {mode}")
+    assert_same_bits(s_int, s_ref, STATS, f"{name} {mode} stats")
     assert np.array_equal(s_int.interrupts.cpu().numpy(), ref_int), f"{name} {mode}: interrupts differ"
     assert emu.interrupted > 0 and emu.kept > emu.interrupted, \
         f"the case never interrupts, or never keeps an option (kept {emu.kept}, interrupted {emu.interrupted})"
@@ -232,7 +167,7 @@ def test_interrupt_equals_oracle_emulator():
     n, n_opt, mask = 1000, 3, 0b1110
     ctx, orc, m = make_pair("pinball_simple", n, n_options=n_opt, seed=9, enabled_mask=mask, reoffer_period=4)
     clf = chain_classifiers(m, n_opt)
-    W = _weights(n_opt + 1, 4)
+    W = ilm.crossing_weights(n_opt + 1, 4)
     n_vf = n_opt + 1
     st_o = sc_oracle.new_state(n, m)
     rng = np.random.default_rng(5)
@@ -254,7 +189,7 @@ def test_interrupt_equals_oracle_emulator():
             continue
         s = [np.ascontiguousarray(st_o[f][idx]) for f in ("x", "y", "vx", "vy")]
         q0 = orc.q_values(*s, W[0])
-        cut = ~(_vmax(st_o["qcache"][:, idx]) >= _vmax(q0))
+        cut = ~(ilm.vmax(st_o["qcache"][:, idx]) >= ilm.vmax(q0))
         c = _candidates(lambda k, x, y: orc.classifier_predict(x, y, clf[k]), s[0][cut], s[1][cut], n_vf, mask, mask, parents)
         e = idx[cut]
         st_o["option_id"][e] = -c
@@ -266,8 +201,8 @@ def test_interrupt_equals_oracle_emulator():
     ctx.rollout(st_d, dev(W).view(-1), dev(clf).view(-1), mask, t0, K, interrupt=True, interrupts=intr)
     torch.cuda.synchronize()
     assert cuts > 0
-    for f in FIELDS:
-        assert np.array_equal(_bits(getattr(st_d, f)), _bits(st_o[f])), f"oracle emulator: {f} differs"
+    for f in EnvState.FIELDS:
+        assert np.array_equal(as_bytes(getattr(st_d, f)), as_bytes(st_o[f])), f"oracle emulator: {f} differs"
     assert np.array_equal(intr.cpu().numpy(), ref_int)
 
 
@@ -291,13 +226,13 @@ def test_every_launch_geometry_and_block_build(monkeypatch):
     for epw in (2, 4, 8, 16, 32):
         monkeypatch.setenv("SCG_ROLLOUT_EPW", str(epw))
         st, stats, _ = _interrupt_launch("pinball_simple", n, n_opt, mask)
-        _assert_same(st, ref_st, FIELDS, f"epw {epw}")
-        _assert_same(stats, ref_stats, STATS + ("interrupts",), f"epw {epw} stats")
+        assert_same_bits(st, ref_st, EnvState.FIELDS, f"epw {epw}")
+        assert_same_bits(stats, ref_stats, STATS + ("interrupts",), f"epw {epw} stats")
     monkeypatch.delenv("SCG_ROLLOUT_EPW")
     for block in (64, 128, 256):
         st, stats, _ = _interrupt_launch("pinball_simple", n, n_opt, mask, block=block)
-        _assert_same(st, ref_st, FIELDS, f"block {block}")
-        _assert_same(stats, ref_stats, STATS + ("interrupts",), f"block {block} stats")
+        assert_same_bits(st, ref_st, EnvState.FIELDS, f"block {block}")
+        assert_same_bits(stats, ref_stats, STATS + ("interrupts",), f"block {block} stats")
 
 
 def test_ties_never_interrupt():
@@ -306,13 +241,13 @@ def test_ties_never_interrupt():
     ctx, m, W, clf = _setup("pinball_simple", n, n_opt, epsilon=0.1)
     Wt = W.view(n_opt + 1, -1)[0].repeat(n_opt + 1).contiguous()
     st = _state(ctx, m, n, n_opt, seed=21)
-    twin = _clone(st)
+    twin = clone_state(st)
     a, b = EpisodeStats(n_opt + 1, n, ctx.device), EpisodeStats(n_opt + 1, n, ctx.device)
     ctx.rollout(st, Wt, clf, mask, 40, 48, a, begin=True)
     ctx.rollout(twin, Wt, clf, mask, 40, 48, b, begin=True, interrupt=True)
     torch.cuda.synchronize()
-    _assert_same(twin, st, FIELDS, "ties")
-    _assert_same(b, a, STATS, "ties stats")
+    assert_same_bits(twin, st, EnvState.FIELDS, "ties")
+    assert_same_bits(b, a, STATS, "ties stats")
     assert int(b.interrupts.sum()) == 0 and b.summary()["interrupts"] == [0] * (n_opt + 1)
     assert int(a.vf_steps[1:].sum()) > 0, "no option ran: the tie check is vacuous"
 
@@ -322,7 +257,7 @@ def test_record_rows_equal_emulator(mode):
     n, n_opt, mask = 4096, 3, 0b1110
     ctx, m, W, clf = _setup("pinball_simple", n, n_opt, epsilon=0.1, reoffer_period=4, max_episode_steps=30)
     st = _state(ctx, m, n, n_opt, seed=31)
-    twin, plain = _clone(st), _clone(st)
+    twin, plain = clone_state(st), clone_state(st)
     emu = Emulator(ctx, W, clf, mask, 0)
     s_ref, s_int, s_plain = (EpisodeStats(n_opt + 1, n, ctx.device) for _ in range(3))
     ref_int = np.zeros((n_opt + 1, n), np.int64)
@@ -333,9 +268,9 @@ def test_record_rows_equal_emulator(mode):
     ctx.rollout(twin, W, clf, mask, 9, K, s_int, begin=True, one_episode=one, interrupt=True, record=tr)
     ctx.rollout(plain, W, clf, mask, 9, K, s_plain, begin=True, one_episode=one, interrupt=True)
     torch.cuda.synchronize()
-    _assert_same(twin, st, FIELDS, "recorded")
-    _assert_same(plain, twin, FIELDS, "recording changed the outputs")
-    _assert_same(s_plain, s_int, STATS + ("interrupts",), "recording changed the counters")
+    assert_same_bits(twin, st, EnvState.FIELDS, "recorded")
+    assert_same_bits(plain, twin, EnvState.FIELDS, "recording changed the outputs")
+    assert_same_bits(s_plain, s_int, STATS + ("interrupts",), "recording changed the counters")
     assert np.array_equal(s_int.interrupts.cpu().numpy(), ref_int)
     rows, ln = emu.record()
     got_len = tr.len.cpu().numpy()
@@ -345,7 +280,7 @@ def test_record_rows_equal_emulator(mode):
     valid = np.arange(K + 1)[:, None] < got_len[None, :]
     for f in tr.fields:
         g = getattr(tr, f).cpu().numpy()
-        assert np.array_equal(_bits(g[valid]), _bits(rows[f][valid])), f"record field {f}"
+        assert np.array_equal(as_bytes(g[valid]), as_bytes(rows[f][valid])), f"record field {f}"
     term = tr.term.cpu().numpy()
     cut = (term == _lib.ROLLOUT_TERM_INTERRUPTED) & valid
     assert int(cut.sum()) == int(s_int.interrupts.sum()) > 0
@@ -361,7 +296,7 @@ def test_c_abi_refusals():
     ctx, m, W, clf = _setup("pinball_simple", n, n_opt)
     st = _state(ctx, m, n, n_opt, seed=1)
     lib = ctx.lib
-    arr = [C.c_void_p(getattr(st, f).data_ptr()) for f in FIELDS] + [C.c_void_p(W.data_ptr()), C.c_void_p(clf.data_ptr())]
+    arr = [C.c_void_p(getattr(st, f).data_ptr()) for f in EnvState.FIELDS] + [C.c_void_p(W.data_ptr()), C.c_void_p(clf.data_ptr())]
     stats = EpisodeStats(n_opt + 1, n, ctx.device)
     cs = stats.c_struct()
     nofin = EpisodeStats(n_opt + 1, n, ctx.device).c_struct()
@@ -393,45 +328,21 @@ def test_c_abi_refusals():
     assert rc == -1 and "unknown flag" in lib.scg_last_error(ctx._ctx).decode()     # scg_rollout still refuses BEGIN_AT
 
 
-def _agent(n=2048, n_opt=2, seed=1):
-    from skill_chaining_with_graphs_amd.agent import SkillChainingAgent
-    m = scg.load_map("pinball_simple")
-    kw = dict(HP)
-    kw.update(max_episode_steps=100)
-    ag = SkillChainingAgent(m, n, n_opt, seed=seed, block_envs=256, **kw)
-    ag.init_weights(std=0.05, seed=3)
-    W = ag.W.view(n_opt + 1, -1)
-    W[1:] = W[0] + 0.05 * torch.randn(W[1:].shape, generator=torch.Generator().manual_seed(7)).to(W.device)
-    ag.clf.copy_(dev(_wide_chain(m, n_opt)))
-    ag.enable_option(1)
-    ag.enable_option(2)
-    x, y, vx, vy = random_states(m, n, 7, vmax=1.0)
-    for t, v in zip(ag.state.state(), (x, y, vx, vy)):
-        t.copy_(dev(v))
-    ag.ctx.invalidate_order()
-    return ag
-
-
 def test_agent_evaluate_and_record_interrupt():
-    a = _agent()
+    a = crossing_agent()
     W0, t0 = a.W.clone(), a.t
-    st0 = {f: getattr(a.state, f).clone() for f in FIELDS}
-    calls = []
-    orig = a.ctx._call
-    a.ctx._call = lambda name, *args: (calls.append(name), orig(name, *args))[1]
-    try:
+    st0 = {f: getattr(a.state, f).clone() for f in EnvState.FIELDS}
+    with spy_calls(a.ctx) as (calls, _):
         kw = dict(n_episodes=1000, steps_per_launch=32, epsilon=0.05)      # (greedy: one start state, one episode)
         plain = a.evaluate(**kw)
         off = a.evaluate(**kw, interrupt=False)
         on = a.evaluate(**kw, interrupt=True)
         traj, rs = a.record_episodes(**kw, interrupt=True)
         _, rs_plain = a.record_episodes(**kw)
-    finally:
-        a.ctx._call = orig
     torch.cuda.synchronize()
     assert calls == [], f"evaluate(interrupt=True) called into the training context: {calls}"
     assert torch.equal(a.W, W0) and a.t == t0
-    for f in FIELDS:
+    for f in EnvState.FIELDS:
         assert torch.equal(getattr(a.state, f), st0[f]), f
     assert plain == off and "interrupts" not in plain
     assert rs_plain == plain

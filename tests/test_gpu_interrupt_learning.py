@@ -7,21 +7,20 @@ import pytest
 import torch
 
 import interrupt_learning_model as ilm
-from gpu_util import dev, make_pair, set_block_envs, state_to_device
+from gpu_util import (as_bytes, assert_same_bits, block_build, clone_state, crossing_agent, dev, make_pair, set_block_envs,
+                      spy_calls, state_to_device)
 from ref64 import env_order_layout
 from skill_chaining_with_graphs_amd import ScgError
 from skill_chaining_with_graphs_amd.core import EnvState
-from util import HP, random_states
+from util import HP
 
 pytestmark = pytest.mark.gpu
-
-FIELDS = ilm.FIELDS
 
 
 @pytest.fixture(autouse=True)
 def _default_block():
-    yield
-    set_block_envs(None)
+    with block_build(None):             # _setup picks each test's build; the default is back after the test
+        yield
 
 
 def _setup(name, n, n_opt, block=None, seed=3, run_share=0.4, gest=0, same_w=False):
@@ -39,26 +38,6 @@ def _setup(name, n, n_opt, block=None, seed=3, run_share=0.4, gest=0, same_w=Fal
     return ctx, orc, m, st, W, ilm.wide_chain(m, n_opt), mask
 
 
-def _clone(st):
-    c = object.__new__(EnvState)
-    c.n = st.n
-    for f in FIELDS:
-        setattr(c, f, getattr(st, f).clone())
-    return c
-
-
-def _bits(a):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    return np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-
-
-def _same_state(a, b, msg):
-    for f in FIELDS:
-        ga = getattr(a, f) if not isinstance(a, dict) else a[f]
-        gb = getattr(b, f) if not isinstance(b, dict) else b[f]
-        assert np.array_equal(_bits(ga), _bits(gb)), f"{msg}: {f} differs"
-
-
 @pytest.mark.parametrize("block", [64, 128, 256])
 def test_acting_outputs_equal_one_interrupting_rollout_step(block):
     n, n_opt = 3000, 5
@@ -67,11 +46,11 @@ def test_acting_outputs_equal_one_interrupting_rollout_step(block):
     W, clf = dev(W_h).view(-1), dev(clf_h).view(-1)
     intr = torch.zeros((n_opt + 1, n), dtype=torch.int32, device=ctx.device)
     for t in range(100, 106):
-        twin, W_before = _clone(st), W.clone()
+        twin, W_before = clone_state(st), W.clone()
         ctx.step(st, W, clf, mask, t, learn=True, apply=True, interrupt=True)
         ctx.rollout(twin, W_before, clf, mask, t, 1, interrupt=True, interrupts=intr)
         torch.cuda.synchronize()
-        _same_state(st, twin, f"block {block} t {t}")
+        assert_same_bits(st, twin, msg=f"block {block} t {t}")
         assert not torch.equal(W, W_before)
     assert int(intr.sum()) >= 100, f"only {int(intr.sum())} interrupts"
 
@@ -97,7 +76,7 @@ def test_G_and_counts_equal_the_emulator(case):
     post, G, n_k, info = ilm.step(orc, st_h, W_h, clf_h, 21, mask, gest=gest)
     torch.cuda.synchronize()
     assert info["interrupted"].sum() >= 5, int(info["interrupted"].sum())
-    _same_state(st, post, name)
+    assert_same_bits(st, post, msg=name)
     assert np.array_equal(n_d.cpu().numpy(), n_k)
     Gd = G_d.cpu().numpy()
     for k in range(n_opt + 1):
@@ -116,8 +95,8 @@ def test_eight_learning_steps_equal_the_emulator():
         W_h = ilm.apply(orc, W_h, G, n_k)
         cuts += int(info["interrupted"].sum())
         torch.cuda.synchronize()
-        _same_state(st, st_h, f"t {t}")
-        assert np.array_equal(_bits(W), _bits(W_h)), f"t {t}: W differs"
+        assert_same_bits(st, st_h, msg=f"t {t}")
+        assert np.array_equal(as_bytes(W), as_bytes(W_h.reshape(-1))), f"t {t}: W differs"
     assert cuts >= 40, cuts
 
 
@@ -131,14 +110,14 @@ def test_nothing_to_interrupt_is_the_plain_step():
         st, W, clf = state_to_device(st_h, ctx), dev(W_h).view(-1), dev(clf_h).view(-1)
         G_d, n_d = ctx.grad_buffers()
         ctx.step(st, W, clf, mask, 9, learn=True, apply=True, interrupt=intr)
-        first = (_clone(st), W.clone(), G_d.clone(), n_d.clone())
+        first = (clone_state(st), W.clone(), G_d.clone(), n_d.clone())
         ctx.step(st, W, clf, mask, 10, learn=True, apply=True)
         torch.cuda.synchronize()
-        out.append((first, (_clone(st), W.clone(), G_d.clone(), n_d.clone())))
+        out.append((first, (clone_state(st), W.clone(), G_d.clone(), n_d.clone())))
     for (a, b), what in zip(zip(out[0], out[1]), ("first step", "second step")):
-        _same_state(a[0], b[0], what)
+        assert_same_bits(a[0], b[0], msg=what)
         for x, y, name in zip(a[1:], b[1:], ("W", "G", "n_k")):
-            assert np.array_equal(_bits(x), _bits(y)), f"{what}: {name} differs"
+            assert np.array_equal(as_bytes(x), as_bytes(y)), f"{what}: {name} differs"
     assert int((out[0][0][0].option_id > 0).sum()) > 500
 
 
@@ -150,7 +129,7 @@ def test_folded_next_order_equals_a_fresh_sort():
         st, W, clf = state_to_device(st_h, ctx), dev(W_h).view(-1), dev(clf_h).view(-1)
         G_d, n_d = ctx.grad_buffers()
         intr = torch.zeros((n_opt + 1, n), dtype=torch.int32, device=ctx.device)
-        twin = _clone(st)
+        twin = clone_state(st)
         ctx.rollout(twin, W, clf, mask, 30, 1, interrupt=True, interrupts=intr)
         ctx.step(st, W, clf, mask, 30, learn=True, apply=True, interrupt=True)
         if fresh:
@@ -158,10 +137,10 @@ def test_folded_next_order_equals_a_fresh_sort():
         ctx.step(st, W, clf, mask, 31, learn=True, apply=True, interrupt=True)
         torch.cuda.synchronize()
         assert int(intr.sum()) > 50
-        res.append((_clone(st), W.clone(), G_d.clone(), n_d.clone()))
-    _same_state(res[0][0], res[1][0], "after the folded order")
+        res.append((clone_state(st), W.clone(), G_d.clone(), n_d.clone()))
+    assert_same_bits(res[0][0], res[1][0], msg="after the folded order")
     for x, y, name in zip(res[0][1:], res[1][1:], ("W", "G", "n_k")):
-        assert np.array_equal(_bits(x), _bits(y)), f"{name} differs"
+        assert np.array_equal(as_bytes(x), as_bytes(y)), f"{name} differs"
 
 
 def test_interrupt_without_learn_is_refused():
@@ -170,55 +149,28 @@ def test_interrupt_without_learn_is_refused():
     st, W, clf = state_to_device(st_h, ctx), dev(W_h).view(-1), dev(clf_h).view(-1)
     G_d, n_d = ctx.grad_buffers()
     G_d.fill_(7.0)
-    before = (_clone(st), W.clone(), G_d.clone(), n_d.clone())
+    before = (clone_state(st), W.clone(), G_d.clone(), n_d.clone())
     with pytest.raises(ScgError, match="SCG_STEP_INTERRUPT without SCG_STEP_LEARN"):
         ctx.step(st, W, clf, mask, 3, learn=False, interrupt=True)
     torch.cuda.synchronize()
-    _same_state(st, before[0], "refused step")
+    assert_same_bits(st, before[0], msg="refused step")
     for x, y, name in zip((W, G_d, n_d), before[1:], ("W", "G", "n_k")):
         assert torch.equal(x, y), name
     ctx.step(st, W, clf, mask, 3, learn=False)                              # the context is fine afterwards
     torch.cuda.synchronize()
 
 
-def _agent(n=2048, n_opt=2, seed=1, **kw):
-    import skill_chaining_with_graphs_amd as scg
-    from skill_chaining_with_graphs_amd.agent import SkillChainingAgent
-    m = scg.load_map("pinball_simple")
-    hp = dict(HP)
-    hp.update(max_episode_steps=100)
-    ag = SkillChainingAgent(m, n, n_opt, seed=seed, block_envs=256, **hp, **kw)
-    ag.init_weights(std=0.05, seed=3)
-    Wv = ag.W.view(n_opt + 1, -1)
-    Wv[1:] = Wv[0] + 0.05 * torch.randn(Wv[1:].shape, generator=torch.Generator().manual_seed(7)).to(Wv.device)
-    ag.clf.copy_(dev(ilm.wide_chain(m, n_opt)))
-    ag.enable_option(1)
-    ag.enable_option(2)
-    x, y, vx, vy = random_states(m, n, 7, vmax=1.0)
-    for t, v in zip(ag.state.state(), (x, y, vx, vy)):
-        t.copy_(dev(v))
-    ag.ctx.invalidate_order()
-    return ag
-
-
-def _spy(ag):
-    calls = []
-    orig = ag.ctx.step
-    ag.ctx.step = lambda *a, **kw: (calls.append((kw.get("learn"), kw.get("interrupt"))), orig(*a, **kw))[1]
-    return calls
-
-
 def test_agent_interrupt_learning():
-    plain, default, intr = _agent(interrupt_learning=False), _agent(), _agent(interrupt_learning=True)
+    plain, default, intr = crossing_agent(interrupt_learning=False), crossing_agent(), crossing_agent(interrupt_learning=True)
     assert default.interrupt_learning is False and intr.interrupt_learning is True
-    spies = [_spy(a) for a in (plain, default, intr)]
-    for a in (plain, default, intr):
-        a.rollout(6)
-        a.step_batch(learn=False)
+    with spy_calls(default.ctx) as (_, default_steps), spy_calls(intr.ctx) as (_, intr_steps):
+        for a in (plain, default, intr):
+            a.rollout(6)
+            a.step_batch(learn=False)
     torch.cuda.synchronize()
-    assert spies[1] == [(True, False)] * 6 + [(False, False)]
-    assert spies[2] == [(True, True)] * 6 + [(False, False)]               # acting-only steps never interrupt
-    for f in FIELDS:
+    assert default_steps == [(True, False)] * 6 + [(False, False)]
+    assert intr_steps == [(True, True)] * 6 + [(False, False)]             # acting-only steps never interrupt
+    for f in EnvState.FIELDS:
         assert torch.equal(getattr(plain.state, f), getattr(default.state, f)), f
     assert torch.equal(plain.W, default.W)
     assert not torch.equal(intr.W, default.W)
@@ -235,9 +187,9 @@ def test_chain_skills_with_interrupt_learning():
                             interrupt_learning=True)
     ag.enable_tracing(64)
     ag.domain.reset_random(seed=11, v_max=0.5)
-    calls = _spy(ag)
-    rep = ag.chain_skills(steps_per_option=250, min_examples=2000, max_examples=20000, start_coverage=2.0)
-    ag.rollout(50)
+    with spy_calls(ag.ctx) as (_, calls):
+        rep = ag.chain_skills(steps_per_option=250, min_examples=2000, max_examples=20000, start_coverage=2.0)
+        ag.rollout(50)
     torch.cuda.synchronize()
     assert len(rep) >= 1 and ag.enabled_mask != 0, rep
     assert calls and all(c == (True, True) for c in calls)

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import sc_oracle
-from util import HP, SCALE, chain_classifiers, random_states, random_weights
+from util import HP, SCALE, chain_classifiers, oracle_block, random_states, random_weights
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,8 +83,7 @@ def test_peer_transport_equals_the_collective_and_the_oracle(tmp_path, R, block_
         assert np.array_equal(res[r]["x"], res[r]["x_coll"]) and np.array_equal(res[r]["opt"], res[r]["opt_coll"])
     import skill_chaining_with_graphs_amd as scg
     m = scg.load_map("pinball_simple")
-    sc_oracle.use_block_envs(block_envs or 256)
-    try:
+    with oracle_block(block_envs or 256):
         x, y, vx, vy = random_states(m, R * n, 77, vmax=1.0)
         clf = chain_classifiers(m, n_opt)
         W_o = random_weights(n_opt + 1, 4, std=0.05)
@@ -106,8 +105,6 @@ def test_peer_transport_equals_the_collective_and_the_oracle(tmp_path, R, block_
             assert np.array_equal(res[0]["W"][t], W_o), f"weights differ from the oracle's {R} shards at step {t}"
         for r in range(R):
             assert np.array_equal(res[r]["x"], sts[r]["x"])
-    finally:
-        sc_oracle.use_block_envs(256)
 
 
 def _rank_main_long(rank, world, port, out_dir, steps):

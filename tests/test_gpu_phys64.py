@@ -18,7 +18,7 @@ import torch
 
 import phys64
 import sc_oracle
-from gpu_util import assert_state_equal, dev, set_block_envs, state_to_device
+from gpu_util import assert_state_equal, block_build, dev, state_to_device
 from skill_chaining_with_graphs_amd.core import ScgContext
 from test_phys64_oracle import BOUNDARY_EDGES, boundary_states
 from util import (CELL_G, HP, SCALE, edge_count_map, kernel_candidates, pair_groups, pocket_map)
@@ -32,9 +32,8 @@ KW = dict(HP, epsilon=0.0)                 # greedy on a one-hot qcache: the fus
 
 @pytest.fixture(params=[256, 128, 64], ids=lambda b: f"b{b}")
 def block(request):
-    set_block_envs(request.param)
-    yield request.param
-    set_block_envs(None)
+    with block_build(request.param) as b:
+        yield b
 
 
 def run_all(m, block, x, y, vx, vy, a, msg=""):

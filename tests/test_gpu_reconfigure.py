@@ -20,7 +20,6 @@ from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
 from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
 from skill_chaining_with_graphs_amd.trajectory import Trajectory
 from skill_chaining_with_graphs_amd.trials import TrialResult
-from test_gpu_ref64 import STATE
 from test_ref64_interrupt import seat_running_envs
 from test_ref64_oracle import assert_rarely_ambiguous, pre_state
 from util import HP, SCALE, chain_classifiers, random_states, random_weights
@@ -56,7 +55,7 @@ class Rig:
                 self.tensors()[k].copy_(v)
 
     def tensors(self):
-        d = {k: getattr(self.st, k) for k in STATE}
+        d = {k: getattr(self.st, k) for k in EnvState.FIELDS}
         d.update(W=self.W, clf=self.clf, G=self.G, n_k=self.n_k, ring_x=self.ring_x, ring_y=self.ring_y, events=self.events,
                  ev_len=self.ev_len, gest_succ=self.gs)
         return d
@@ -77,7 +76,7 @@ def warm(block, map_name="pinball_maze", hp=S1):
     pre = pre_state(a.map, N, NOPT, rng, max_ep=hp["max_episode_steps"], max_opt=hp["max_option_steps"])
     pre["opt_steps"][:] = np.minimum(pre["opt_steps"], 20)          # (the options stay clear of S1's limit during the warm-up)
     seat_running_envs(a.map, pre, clf, CHAIN, rng, share=0.8)
-    for k in STATE:
+    for k in EnvState.FIELDS:
         getattr(a.st, k).copy_(dev(pre[k]))
     a.W.copy_(dev(random_weights(NOPT + 1, 3, std=1e-3)))
     for t in (0, 1):
@@ -253,7 +252,7 @@ def test_rollouts_and_trials_after_set_hparams(block, kind):
     torch.cuda.synchronize()
     for k in ra:
         assert torch.equal(ra[k], rb[k]), f"{kind}: {k} differs"
-    assert_same(a, b, kind, names=STATE)
+    assert_same(a, b, kind, names=EnvState.FIELDS)
     if kind == "trials":
         assert (ra["outcome"] != 0).all() and int(ra["steps"].max()) <= hp2["max_option_steps"]
     else:

@@ -6,16 +6,13 @@ import pytest
 import torch
 
 import skill_chaining_with_graphs_amd as scg
-from gpu_util import dev, set_block_envs
+from gpu_util import block_envs, current_block_envs, dev, host_state, state_to_device       # noqa: F401  (block_envs: the fixture)
 from ref64 import C_G, C_PHI, U32, q_model, q_update_model
 from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
 from test_ref64_oracle import CASES, EDGES, OracleRunner, assert_rarely_ambiguous, check_step, pre_state, sweep_case
 from util import HP, SCALE, chain_classifiers, fourier_reference, random_weights
 
 pytestmark = pytest.mark.gpu
-
-STATE = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done")
-
 
 class GpuRunner(OracleRunner):
     """The system under test on the GPU: ScgContext.step (LEARN | APPLY) from a pre-state copied to the device. The oracle
@@ -28,7 +25,7 @@ class GpuRunner(OracleRunner):
         kw = dict(HP)
         kw.update(hp)
         self.ctx = ScgContext(n, n_options, self.map, device=0, seed=seed, env_id_base=env_id_base,
-                              block_envs=_BLOCK[0], **kw)
+                              block_envs=current_block_envs(), **kw)
         if parents is not None:
             self.ctx.set_option_parents(parents)
         self.gs = self.ctx.set_gestation(gest) if gest else None
@@ -36,29 +33,15 @@ class GpuRunner(OracleRunner):
         self.G, self.n_k = self.ctx.grad_buffers()
 
     def step(self, pre, W, clf, t, enabled):
-        st = EnvState(len(pre["x"]), self.ctx.device, self.map)
-        for k in STATE:
-            getattr(st, k).copy_(dev(pre[k]))
+        st = state_to_device({k: pre[k] for k in EnvState.FIELDS}, self.ctx)
         W_d, clf_d = dev(W.copy()), dev(clf)
         gs0 = self.gs.cpu().numpy().copy() if self.gs is not None else None
         self.ctx.step(st, W_d.view(-1), clf_d.view(-1), enabled, t, interrupt=self.interrupt)
         torch.cuda.synchronize()
-        out = {k: getattr(st, k).cpu().numpy() for k in STATE}
+        out = host_state(st)
         gsn = self.gs.cpu().numpy() - gs0 if self.gs is not None else np.zeros(len(W), np.int32)
         return dict(st=out, G=self.G.cpu().numpy(), n_k=self.n_k.cpu().numpy(), W=W_d.cpu().numpy(),
                     events=self.trace[2].cpu().numpy(), ev_len=self.trace[3].cpu().numpy(), gest_succ=gsn)
-
-
-_BLOCK = [256]
-
-
-@pytest.fixture
-def block_envs(request):
-    _BLOCK[0] = request.param
-    set_block_envs(request.param)
-    yield request.param
-    _BLOCK[0] = 256
-    set_block_envs(None)
 
 
 @pytest.mark.parametrize("cfg,block_envs", CASES, indirect=["block_envs"],

@@ -4,8 +4,7 @@ multiples of 2^19 and 2^20, count floors up to 2^30, weights of trained size, an
 and with SPEC §12's interruption, on the 256- and the 64-env build."""
 import pytest
 
-import test_gpu_ref64 as g64
-from gpu_util import set_block_envs
+from gpu_util import block_envs                               # noqa: F401  (the fixture)
 from test_gpu_ref64 import GpuRunner
 from test_gpu_ref64_interrupt import IntGpuRunner
 from test_ref64_hparams import CASE_IDS, HP_CASES, hparam_case
@@ -13,15 +12,6 @@ from test_ref64_hparams import CASE_IDS, HP_CASES, hparam_case
 pytestmark = pytest.mark.gpu
 
 RUNNERS = {"plain": GpuRunner, "interrupting": IntGpuRunner}
-
-
-@pytest.fixture
-def block_envs(request):
-    g64._BLOCK[0] = request.param
-    set_block_envs(request.param)
-    yield request.param
-    g64._BLOCK[0] = 256
-    set_block_envs(None)
 
 
 @pytest.mark.parametrize("mode", list(RUNNERS))

@@ -8,13 +8,12 @@ import pytest
 import torch
 
 import interrupt_learning_model as ilm
-import test_gpu_ref64 as g64
-from gpu_util import dev, set_block_envs
+from gpu_util import block_build, block_envs, dev, host_state, state_to_device       # noqa: F401  (block_envs: the fixture)
 from ref64 import U32, compare, env_order_layout
 from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
 from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
 from skill_chaining_with_graphs_amd.trajectory import Trajectory
-from test_gpu_ref64 import STATE, GpuRunner
+from test_gpu_ref64 import GpuRunner
 from test_ref64_interrupt import EDGES, INT_SWEEP, MAX_EP, MAX_OPT, case_ids, interrupt_sweep_case, seat_running_envs
 from test_ref64_oracle import OracleRunner, assert_rarely_ambiguous, check_step, pre_state
 from util import HP, chain_classifiers, random_weights
@@ -26,19 +25,6 @@ class IntGpuRunner(GpuRunner):
     """ScgContext.step(learn=True, apply=True, interrupt=True) from a pre-state copied to the device."""
 
     interrupt = True
-
-
-def _use_block(b):
-    g64._BLOCK[0] = b
-    set_block_envs(b)
-
-
-@pytest.fixture
-def block_envs(request):
-    _use_block(request.param)
-    yield request.param
-    _use_block(256)
-    set_block_envs(None)
 
 
 GPU_CASES = [(c, b) for b in (256, 128, 64) for c in INT_SWEEP if b == 256 or c[1] <= 1000]
@@ -88,10 +74,6 @@ CHAINS = [
 ]
 
 
-def _host(st):
-    return {k: getattr(st, k).cpu().numpy() for k in STATE}
-
-
 @pytest.mark.parametrize("interrupt", [True, False], ids=["interrupting", "plain"])
 @pytest.mark.parametrize("chain", CHAINS, ids=lambda c: f"n{c[1]}-b{c[3]}-{c[5]}")
 def test_chained_steps_on_one_device_state(chain, interrupt):
@@ -99,35 +81,29 @@ def test_chained_steps_on_one_device_state(chain, interrupt):
     post-state and W of the step before, read back: from the second step on, the kernel runs in the env order that the step before
     prepared (with interruption: the order it folded)."""
     name, n, nopt, block, dist, layout = chain
-    _use_block(block)
-    try:
+    with block_build(block):
         r = GpuRunner(name, n, nopt, seed=31, env_id_base=5, reoffer_period=4)
         clf = chain_classifiers(r.map, nopt)
         rng = np.random.default_rng(n + nopt)
         pre = pre_state(r.map, n, nopt, rng, max_ep=MAX_EP, max_opt=MAX_OPT, dist=dist)
         seat_running_envs(r.map, pre, clf, r.model.parents, rng, share=0.8)
         enabled = 0b111110
-        st = EnvState(n, r.ctx.device, r.map)
-        for k in STATE:
-            getattr(st, k).copy_(dev(pre[k]))
+        st = state_to_device({k: pre[k] for k in EnvState.FIELDS}, r.ctx)
         W_d = dev(ilm.crossing_weights(nopt + 1, 31))
         Wv, cv = W_d.view(-1), dev(clf).view(-1)
         n_amb = n_int = n_keep = 0
         layouts = []
         for t in range(50, 56):
-            pre, W = _host(st), W_d.cpu().numpy()
+            pre, W = host_state(st), W_d.cpu().numpy()
             layouts.append(env_order_layout(pre["option_id"], nopt + 1, block))
             r.ctx.step(st, Wv, cv, enabled, t, learn=True, apply=True, interrupt=interrupt)
             torch.cuda.synchronize()
-            got, ev, ev_len = _host(st), r.trace[2].cpu().numpy(), r.trace[3].cpu().numpy()
+            got, ev, ev_len = host_state(st), r.trace[2].cpu().numpy(), r.trace[3].cpu().numpy()
             out = r.model.step(pre, W, clf, t, enabled, 0, sut=dict(got, events=ev), interrupt=interrupt)
             n_amb += compare(out, got, r.G.cpu().numpy(), r.n_k.cpu().numpy(), W_d.cpu().numpy(), events=ev, ev_len=ev_len,
                              msg=f"t={t}")
             n_int += int(out["interrupted"].sum())
             n_keep += int(out["keep"].sum())
-    finally:
-        _use_block(256)
-        set_block_envs(None)
     print(f"\n[chain n={n} B={block} interrupt={interrupt}] layouts {layouts}, {n_keep} kept, {n_int} interrupted, {n_amb} ambiguous")
     assert_rarely_ambiguous(n_amb, 6 * n)
     assert layouts[0] == layout
@@ -198,22 +174,20 @@ def test_one_step_rollouts_match_the_float64_model(block, epw, interrupt, monkey
     pre = pre_state(r.map, n, nopt, rng, max_ep=MAX_EP, max_opt=MAX_OPT)
     seat_running_envs(r.map, pre, clf, r.model.parents, rng, share=0.7)
     W = ilm.crossing_weights(nopt + 1, 41)
-    st = EnvState(n, ctx.device, r.map)
-    for k in STATE:
-        getattr(st, k).copy_(dev(pre[k]))
+    st = state_to_device({k: pre[k] for k in EnvState.FIELDS}, ctx)
     Wv, cv = dev(W).view(-1), dev(clf).view(-1)
     stats = EpisodeStats(nopt + 1, n, ctx.device)
     intr = torch.zeros((nopt + 1, n), dtype=torch.int32, device=ctx.device) if interrupt else None
     n_amb = n_int = n_keep = n_ent = 0
     for t in range(700, 706):
         msg = f"block {block} epw {epw} t {t}:"
-        pre = _host(st)
+        pre = host_state(st)
         s0 = {f: getattr(stats, f).cpu().numpy().copy() for f in EpisodeStats.FIELDS}
         i0 = intr.cpu().numpy().copy() if interrupt else None
         tr = Trajectory(n, 1, 0, ctx.device)
         ctx.rollout(st, Wv, cv, enabled, t, 1, stats, record=tr, interrupt=interrupt, interrupts=intr)
         torch.cuda.synchronize()
-        got = _host(st)
+        got = host_state(st)
         out = r.model.step(pre, W, clf, t, enabled, gest, sut=got, learn=False, interrupt=interrupt)
         n_amb += compare(out, got, None, None, None, msg=msg)
         ok = np.ones(n, bool)

@@ -180,7 +180,7 @@ def test_a_real_handoff_give_up_voids_the_step_and_is_reported():
     for t in (T - 2, T - 1):
         ctx.step(st, W, clf, 0b10, t)
     assert ctx.async_status(synchronize=True) == 0
-    keys = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done")
+    keys = EnvState.FIELDS
     before = {k: getattr(st, k).clone() for k in keys}
     W_before = W.clone()
     ctx.step(st, W, clf, 0b10, T)                                          # launches fine; gives up on the device

@@ -8,61 +8,22 @@ import torch
 
 import sc_oracle
 import skill_chaining_with_graphs_amd as scg
-from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
+from skill_chaining_with_graphs_amd.core import EnvState
 from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
-from gpu_util import assert_state_equal, dev, make_pair, state_to_device
-from util import HP, chain_classifiers, dense_map, hub_map, random_states, random_weights
+from gpu_util import (assert_same_bits, assert_state_equal, clone_state, dev, gestating_agent, host_state, make_context,
+                      make_pair, named_map, spy_calls, state_to_device)
+from util import HP, chain_classifiers, dense_map, random_env_state, random_states, random_weights
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done")
-
-
-def _ctx(m, n, n_opt, block=None, **hp):
-    kw = dict(HP)
-    kw.update(hp)
-    return ScgContext(n, n_opt, m, device=0, block_envs=block, **kw)
-
-
 def _state(ctx, m, n, n_opt, seed):
-    """Random positions / velocities, option ids in [-n_opt - 1, n_opt + 1] (out-of-range ids included), running
-    option-step and episode-step counters, random qcache."""
-    rng = np.random.default_rng(seed)
-    st = EnvState(n, ctx.device, m)
-    x, y, vx, vy = random_states(m, n, seed, vmax=1.5)
-    st.x.copy_(dev(x)); st.y.copy_(dev(y)); st.vx.copy_(dev(vx)); st.vy.copy_(dev(vy))
-    st.option_id.copy_(dev(rng.integers(-n_opt - 1, n_opt + 2, n).astype(np.int32)))
-    st.opt_steps.copy_(dev(rng.integers(0, 20, n).astype(np.int32)))
-    st.ep_steps.copy_(dev(rng.integers(0, ctx.cfg.max_episode_steps, n).astype(np.int32)))
-    st.qcache.copy_(dev(rng.standard_normal((5, n)).astype(np.float32)))
-    return st
-
-
-def _clone(st):
-    c = object.__new__(EnvState)
-    c.n = st.n
-    for f in FIELDS:
-        setattr(c, f, getattr(st, f).clone())
-    return c
-
-
-def _host(st):
-    return {f: getattr(st, f).cpu().numpy().copy() for f in FIELDS}
-
-
-def _assert_same(a, b, msg):
-    ha, hb = _host(a), _host(b)
-    for f in FIELDS:
-        assert np.array_equal(ha[f].view(np.uint8), hb[f].view(np.uint8)), \
-            f"{msg}: field {f}: {np.sum(ha[f] != hb[f])} of {ha[f].size} differ"
+    """Option ids in [-n_opt - 1, n_opt + 1]: out-of-range ids included."""
+    return state_to_device(random_env_state(m, n, n_opt, seed, id_lo=-n_opt - 1, id_hi=n_opt + 1, opt_steps_hi=20,
+                                            max_episode_steps=ctx.cfg.max_episode_steps), ctx)
 
 
 def _setup(m, n, n_opt, block=None, parents=None, gest=0, seed=3, **hp):
-    ctx = _ctx(m, n, n_opt, block, seed=seed, **hp)
-    if parents is not None:
-        ctx.set_option_parents(parents)
-    if gest:
-        ctx.set_gestation(gest)
+    ctx = make_context(m, n, n_opt, block, parents, gest, seed, **hp)
     clf = dev(chain_classifiers(m, n_opt)).view(-1)
     W = dev(random_weights(n_opt + 1, seed, std=0.1)).view(-1)
     return ctx, W, clf
@@ -78,24 +39,20 @@ CASES = [
 ]
 
 
-def _map(name):
-    return dense_map() if name == "dense" else hub_map() if name == "hub" else scg.load_map(name)
-
-
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0]}-{c[1]}-b{c[9]}-r{c[6]}")
 def test_rollout_equals_step_loop(case):
     name, n, n_opt, mask, gest, parents, reoffer, eps, base, block = case
-    m = _map(name)
+    m = named_map(name)
     ctx, W, clf = _setup(m, n, n_opt, block, parents, gest, reoffer_period=reoffer, epsilon=eps, env_id_base=base)
     st = _state(ctx, m, n, n_opt, seed=n)
-    twin = _clone(st)
+    twin = clone_state(st)
     W0 = W.clone()
     K, t0 = 24, 1000
     ctx.rollout(st, W, clf, mask, t0, K)
     for t in range(t0, t0 + K):
         ctx.step(twin, W, clf, mask, t, learn=False)
     torch.cuda.synchronize()
-    _assert_same(st, twin, f"rollout({K}) vs {K} acting steps")
+    assert_same_bits(st, twin, msg=f"rollout({K}) vs {K} acting steps")
     assert torch.equal(W, W0), "a rollout wrote W"
     assert int((twin.done != 0).sum()) > 0, "the case ends no episode: it tests less than it should"
 
@@ -135,19 +92,19 @@ def test_rollout_every_launch_geometry(monkeypatch):
     n, n_opt, mask, gest = 5000, 3, 0b1010, 0b0100
     ctx, W, clf = _setup(m, n, n_opt, None, [0, 0, 1, 1], gest, reoffer_period=4, epsilon=0.1, env_id_base=17)
     st0 = _state(ctx, m, n, n_opt, seed=41)
-    twin = _clone(st0)
+    twin = clone_state(st0)
     K, t0 = 24, 500
     for t in range(t0, t0 + K):
         ctx.step(twin, W, clf, mask, t, learn=False)
     for epw in (2, 4, 8, 16, 32):
         monkeypatch.setenv("SCG_ROLLOUT_EPW", str(epw))
-        st = _clone(st0)
+        st = clone_state(st0)
         ctx.rollout(st, W, clf, mask, t0, K)
         torch.cuda.synchronize()
-        _assert_same(st, twin, f"epw {epw}")
+        assert_same_bits(st, twin, msg=f"epw {epw}")
     monkeypatch.setenv("SCG_ROLLOUT_EPW", "3")
     with pytest.raises(scg.ScgError):
-        ctx.rollout(_clone(st0), W, clf, mask, t0, K)
+        ctx.rollout(clone_state(st0), W, clf, mask, t0, K)
 
 
 def test_rollout_split_launches_and_block_builds():
@@ -166,10 +123,10 @@ def test_rollout_split_launches_and_block_builds():
             for i in range(3):
                 ctx.rollout(st3, W, clf, 0b1010, 5 + 21 * i, 21)
             torch.cuda.synchronize()
-            _assert_same(st3, st, "3 x 21 vs 63")
+            assert_same_bits(st3, st, msg="3 x 21 vs 63")
     torch.cuda.synchronize()
-    _assert_same(outs[0], outs[2], "block 64 vs 256")
-    _assert_same(outs[1], outs[2], "block 128 vs 256")
+    assert_same_bits(outs[0], outs[2], msg="block 64 vs 256")
+    assert_same_bits(outs[1], outs[2], msg="block 128 vs 256")
 
 
 @pytest.mark.parametrize("epw", [None, 8, 32])
@@ -232,10 +189,10 @@ def _counter_model(ctx, st, W, clf, mask, gest, t0, K):
     episodes, goals, len_sum = (np.zeros(n, np.int64) for _ in range(3))
     cols = np.arange(n)
     for t in range(t0, t0 + K):
-        before = _host(st)
+        before = host_state(st)
         entry = [getattr(st, f).clone() for f in ("x", "y", "vx", "vy")]
         ctx.step(st, W, clf, mask, t, learn=False)
-        after = _host(st)
+        after = host_state(st)
         ctx.pinball_step(entry, st.action.clone())         # s' (before the reset) from the entry state and the action taken
         sx, sy = entry[0], entry[1]
         oid_b, oid_a = before["option_id"], after["option_id"]
@@ -273,14 +230,14 @@ def test_counters_match_numpy_model(epw, monkeypatch):
     n, n_opt, mask, gest = 1000, 3, 0b1010, 0b0100
     ctx, W, clf = _setup(m, n, n_opt, None, [0, 0, 1, 1], gest, reoffer_period=4, epsilon=0.1, env_id_base=5)
     st = _state(ctx, m, n, n_opt, seed=21)
-    twin = _clone(st)
+    twin = clone_state(st)
     stats = EpisodeStats(n_opt + 1, n, ctx.device)
     t0, K = 300, 40
     ctx.rollout(st, W, clf, mask, t0, 25, stats)               # two launches add up into one set of counters
     ctx.rollout(st, W, clf, mask, t0 + 25, K - 25, stats)
     model = _counter_model(ctx, twin, W, clf, mask, gest, t0, K)
     torch.cuda.synchronize()
-    _assert_same(st, twin, "counter run")
+    assert_same_bits(st, twin, msg="counter run")
     for f in ("vf_steps", "entries", "declines", "successes"):
         got = getattr(stats, f).cpu().numpy()
         assert np.array_equal(got, model[f]), f"{f}: {np.sum(got != model[f])} entries differ"
@@ -306,10 +263,10 @@ def test_one_episode(epw, monkeypatch):
     prev = None
     for i in range(launches):
         ctx.rollout(st, W, clf, mask, 0 if i == 0 else 1 + i * spl, spl, stats, begin=(i == 0), one_episode=True)
-        cur = _host(st)
+        cur = host_state(st)
         fin = stats.finished.cpu().numpy().astype(bool)
         if prev is not None:
-            for f in FIELDS:
+            for f in EnvState.FIELDS:
                 a, b = prev[0][f], cur[f]
                 sel = prev[1]
                 assert np.array_equal(a[..., sel].view(np.uint8), b[..., sel].view(np.uint8)), f"finished env's {f} changed"
@@ -322,40 +279,15 @@ def test_one_episode(epw, monkeypatch):
     assert int(stats.vf_steps.sum()) == int(lens.sum())
 
 
-def _agent(n=2048, n_opt=2, seed=1):
-    """An agent with option 1 enabled and option 2 gestating (SPEC §4.4), its envs at random positions near the goal's
-    nested initiation sets so that the gestation success count moves."""
-    from skill_chaining_with_graphs_amd.agent import SkillChainingAgent
-    m = scg.load_map("pinball_simple")
-    kw = dict(HP)
-    kw.update(max_episode_steps=100)
-    ag = SkillChainingAgent(m, n, n_opt, seed=seed, block_envs=256, **kw)
-    ag.init_weights(std=0.05, seed=3)
-    ag.clf.copy_(dev(chain_classifiers(m, n_opt)))
-    ag.enable_option(1)
-    ag.gest_mask = 0b100
-    ag.gest_counts = ag.ctx.set_gestation(ag.gest_mask)
-    x, y, vx, vy = random_states(m, n, 7, vmax=1.0)
-    for t, v in zip(ag.state.state(), (x, y, vx, vy)):
-        t.copy_(dev(v))
-    ag.ctx.invalidate_order()
-    return ag
-
-
 def test_evaluate_leaves_training_alone():
-    a, b = _agent(), _agent()
+    a, b = gestating_agent(), gestating_agent()
     for ag in (a, b):
         ag.ctx.set_trace_buffers(64)
     calls = []                                             # every call evaluate() makes on the TRAINING context
-    orig_call, orig_step = a.ctx._call, a.ctx.step
 
     def evaluate(**kw):
-        a.ctx._call = lambda name, *args: (calls.append(name), orig_call(name, *args))[1]
-        a.ctx.step = lambda *args, **k: (calls.append("step"), orig_step(*args, **k))[1]
-        try:
+        with spy_calls(a.ctx, calls):
             return a.evaluate(**kw)
-        finally:
-            a.ctx._call, a.ctx.step = orig_call, orig_step
 
     for i in range(40):
         if i in (0, 17, 39):
@@ -365,7 +297,7 @@ def test_evaluate_leaves_training_alone():
     torch.cuda.synchronize()
     assert calls == [], f"evaluate() called into the training context: {calls}"      # (the peer exchange counter is its own)
     assert torch.equal(a.W, b.W), "evaluate() changed the training weights"
-    for f in FIELDS:
+    for f in EnvState.FIELDS:
         assert torch.equal(getattr(a.state, f), getattr(b.state, f)), f"evaluate() changed the training state ({f})"
     for x, y in zip(a.ctx._trace, b.ctx._trace):
         assert torch.equal(x, y), "evaluate() changed the trace buffers"

@@ -13,17 +13,13 @@ from skill_chaining_with_graphs_amd import _lib
 from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
 from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
 from skill_chaining_with_graphs_amd.trials import TrialResult
-from gpu_util import dev, make_pair
-from util import HP, chain_classifiers, dense_map, hub_map, random_states, random_weights
+from gpu_util import dev, gestating_agent, make_context, make_pair, named_map, spy_calls
+from util import HP, chain_classifiers, random_states, random_weights
 
 pytestmark = pytest.mark.gpu
 
 OUT = ("outcome", "steps", "ret", "disc_ret", "v0", "end_x", "end_y", "end_vx", "end_vy")
 SENTINEL = np.float32(-1234.5)
-
-
-def _map(name):
-    return dense_map() if name == "dense" else hub_map() if name == "hub" else scg.load_map(name)
 
 
 def _starts(m, n, n_opt, seed, all_valid=False):
@@ -212,14 +208,9 @@ CASES = [
 
 def _setup(case, block=None, seed=4):
     name, n, n_opt, mask, gest, parents, eps, r_succ, max_opt, max_ep, base = case
-    m = _map(name)
-    kw = dict(HP)
-    kw.update(epsilon=eps, r_option_success=r_succ, max_option_steps=max_opt, max_episode_steps=max_ep)
-    ctx = ScgContext(n, n_opt, m, device=0, seed=seed, env_id_base=base, block_envs=block, **kw)
-    if parents is not None:
-        ctx.set_option_parents(parents)
-    if gest:
-        ctx.set_gestation(gest)
+    m = named_map(name)
+    ctx = make_context(m, n, n_opt, block, parents, gest, seed, env_id_base=base, epsilon=eps, r_option_success=r_succ,
+                       max_option_steps=max_opt, max_episode_steps=max_ep)
     clf = dev(chain_classifiers(m, n_opt)).view(-1)
     W = dev(random_weights(n_opt + 1, 5, std=0.1)).view(-1)
     return ctx, m, W, clf
@@ -320,44 +311,21 @@ def test_trial_leaves_the_training_step_alone():
             ctxs[i].step(sts[i], Ws[i], clf, mask, t)
     torch.cuda.synchronize()
     assert torch.equal(Ws[0], Ws[1])
-    for f in ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done"):
+    for f in EnvState.FIELDS:
         assert torch.equal(getattr(sts[0], f), getattr(sts[1], f)), f
 
 
-def _agent(n=2048, n_opt=2, seed=1):
-    from skill_chaining_with_graphs_amd.agent import SkillChainingAgent
-    m = scg.load_map("pinball_simple")
-    kw = dict(HP)
-    kw.update(max_episode_steps=100)
-    ag = SkillChainingAgent(m, n, n_opt, seed=seed, block_envs=256, **kw)
-    ag.init_weights(std=0.05, seed=3)
-    ag.clf.copy_(dev(chain_classifiers(m, n_opt)))
-    ag.enable_option(1)
-    ag.gest_mask = 0b100
-    ag.gest_counts = ag.ctx.set_gestation(ag.gest_mask)
-    x, y, vx, vy = random_states(m, n, 7, vmax=1.0)
-    for t, v in zip(ag.state.state(), (x, y, vx, vy)):
-        t.copy_(dev(v))
-    ag.ctx.invalidate_order()
-    return ag
-
-
 def test_agent_trials_leave_training_alone():
-    a, b = _agent(), _agent()
+    a, b = gestating_agent(), gestating_agent()
     for ag in (a, b):
         ag.ctx.set_trace_buffers(64)
     calls = []
-    orig_call, orig_step = a.ctx._call, a.ctx.step
     m = a.map
     x, y, vx, vy = random_states(m, 3000, 12, vmax=0.5)
 
     def run(fn):
-        a.ctx._call = lambda name, *args: (calls.append(name), orig_call(name, *args))[1]
-        a.ctx.step = lambda *args, **k: (calls.append("step"), orig_step(*args, **k))[1]
-        try:
+        with spy_calls(a.ctx, calls):
             return fn()
-        finally:
-            a.ctx._call, a.ctx.step = orig_call, orig_step
 
     for i in range(30):
         if i in (0, 11):
@@ -371,7 +339,7 @@ def test_agent_trials_leave_training_alone():
     torch.cuda.synchronize()
     assert calls == [], f"trials called into the training context: {calls}"
     assert torch.equal(a.W, b.W)
-    for f in ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "qcache", "action", "reward", "done"):
+    for f in EnvState.FIELDS:
         assert torch.equal(getattr(a.state, f), getattr(b.state, f)), f
     for u, v in zip(a.ctx._trace, b.ctx._trace):
         assert torch.equal(u, v), "trials changed the trace buffers"
@@ -394,7 +362,7 @@ def _recount(ag, k, rep):
 
 
 def test_refine_initiation_is_a_plain_fit():
-    a, b = _agent(seed=2), _agent(seed=2)
+    a, b = gestating_agent(seed=2), gestating_agent(seed=2)
     a.enable_tracing(ring_len=64, max_examples=4096)
     xy_ex, lab_ex, cnt, _ = a._ex_buffers(1)
     rng = np.random.default_rng(4)

@@ -13,15 +13,14 @@ import torch
 import sc_oracle
 import skill_chaining_with_graphs_amd as scg
 import test_gpu_interrupt as gi
-import test_gpu_ref64 as g64
 import test_gpu_trials as gt
 from draw_model import draws_batch, grid, seven_start_map
-from gpu_util import assert_state_equal, dev, make_pair, set_block_envs, state_to_device
+from gpu_util import block_envs                               # noqa: F401  (the fixture)
+from gpu_util import assert_same_bits, assert_state_equal, clone_state, dev, host_state, make_pair, state_to_device
 from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
 from skill_chaining_with_graphs_amd.trajectory import BEGIN_ACTION, Trajectory
 from test_gpu_ref64 import GpuRunner
 from test_gpu_ref64_interrupt import IntGpuRunner
-from test_gpu_rollout import FIELDS, _assert_same, _clone
 from test_ref64_interrupt import interrupt_sweep_case
 from test_ref64_oracle import edge_reoffer_stagger_uses_global_id, sweep_case
 from test_wide_identity import (N, W_BASE, W_SEED, WIDE_STEPS, WIDE_SWEEP, SWEEP_IDS, assert_draws, draw_case_state, greedy_qcache,
@@ -29,19 +28,6 @@ from test_wide_identity import (N, W_BASE, W_SEED, WIDE_STEPS, WIDE_SWEEP, SWEEP
 from util import HP, chain_classifiers, random_states, random_weights
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture
-def block_envs(request):
-    g64._BLOCK[0] = request.param
-    set_block_envs(request.param)
-    yield request.param
-    g64._BLOCK[0] = 256
-    set_block_envs(None)
-
-
-def _host(st):
-    return {f: getattr(st, f).cpu().numpy() for f in FIELDS}
 
 
 def _draw_ctx(m, n, seed, base, eps, block=256, n_options=0, **hp):
@@ -70,7 +56,7 @@ def test_step_draws_match_the_model_over_the_grid(block, n):
         st = state_to_device(draw_case_state(m, n), ctx)
         ctx.step(st, W, clf, 0, t)
         torch.cuda.synchronize()
-        assert_draws(m, _host(st), n, seed, base, t, msg=f"B={block} {grid_id(cell)}")
+        assert_draws(m, host_state(st), n, seed, base, t, msg=f"B={block} {grid_id(cell)}")
         ctx.close()
 
 
@@ -86,7 +72,7 @@ def test_step_explore_comparison_at_wide_identities(block, eps):
         st = state_to_device(pre, ctx)
         ctx.step(st, W, clf, 0, t)
         torch.cuda.synchronize()
-        assert_draws(m, _host(st), N, seed, base, t, eps=eps, greedy=greedy, msg=f"B={block} t={t}")
+        assert_draws(m, host_state(st), N, seed, base, t, eps=eps, greedy=greedy, msg=f"B={block} t={t}")
 
 
 @pytest.mark.parametrize("block_envs", [64, 128, 256], indirect=True)
@@ -143,13 +129,13 @@ def test_step_keeps_refusing_a_bad_counter_on_the_cached_fast_path():
     ctx.step(st, W, clf, 0, 2 ** 64 - 1)                       # the second call goes through the cached arguments
     assert ctx._step_args is not None
     torch.cuda.synchronize()
-    before = _host(st)
+    before = host_state(st)
     for t in (-1, 2 ** 64):
         with pytest.raises(scg.ScgError, match="64-bit unsigned step counter"):
             ctx.step(st, W, clf, 0, t)
     torch.cuda.synchronize()
-    after = _host(st)
-    assert all(np.array_equal(before[f], after[f]) for f in FIELDS)
+    after = host_state(st)
+    assert all(np.array_equal(before[f], after[f]) for f in EnvState.FIELDS)
     with pytest.raises(scg.ScgError, match="64-bit"):
         ScgContext(64, 0, m, seed=2 ** 64)
 
@@ -179,7 +165,7 @@ def test_rollout_across_the_counter_boundary(t0, epw, monkeypatch):
     mask, K = 0b1110, 8
     ctx, orc, m, W, clf, st_o = _rollout_pair()
     st = state_to_device(st_o, ctx)
-    twin = _clone(st)
+    twin = clone_state(st)
     W_d, clf_d = dev(W).view(-1), dev(clf).view(-1)
     ctx.rollout(st, W_d, clf_d, mask, t0, K)
     for j in range(K):
@@ -187,7 +173,7 @@ def test_rollout_across_the_counter_boundary(t0, epw, monkeypatch):
         ctx.step(twin, W_d, clf_d, mask, t, learn=False)
         orc.step(st_o, W, clf, t)                              # W not applied: acting only
     torch.cuda.synchronize()
-    _assert_same(st, twin, f"rollout({K}) at t0={t0} vs {K} acting steps")
+    assert_same_bits(st, twin, msg=f"rollout({K}) at t0={t0} vs {K} acting steps")
     assert_state_equal(st, st_o, msg=f"rollout({K}) at t0={t0} vs the oracle")
     assert int((st_o["option_id"] > 0).sum()) > 0
 
@@ -203,13 +189,13 @@ def test_begin_draws_on_either_side_of_the_boundary():
     ctx.rollout(st, W, clf, 0, t0, 0, begin=True)
     torch.cuda.synchronize()
     start = draws_batch(W_BASE, N, W_SEED, t0, 7)[2]
-    h = _host(st)
+    h = host_state(st)
     assert np.array_equal(h["x"].view(np.uint32), S[start, 0].view(np.uint32)), "BEGIN's start positions (x)"
     assert np.array_equal(h["y"].view(np.uint32), S[start, 1].view(np.uint32)), "BEGIN's start positions (y)"
     st = state_to_device(draw_case_state(m, N), ctx)
     ctx.rollout(st, W, clf, 0, t0, 1, begin=True)              # max_episode_steps = 1: the step at t0 + 1 resets again
     torch.cuda.synchronize()
-    assert_draws(m, _host(st), N, W_SEED, W_BASE, t0 + 1, msg="the step after BEGIN")
+    assert_draws(m, host_state(st), N, W_SEED, W_BASE, t0 + 1, msg="the step after BEGIN")
 
 
 @pytest.mark.parametrize("begin", [False, True])
@@ -318,8 +304,8 @@ def test_two_shards_meeting_at_2_pow_32_equal_one_context():
         assert np.array_equal(total[nw:].cpu().numpy(), (n[0] + n[1]).astype(np.float32))
         for r in range(2):
             assert_state_equal(st_d[r], st_o[r], msg=f"rank {r} t={t}")
-        hf = _host(st_full)
-        for f in FIELDS:
+        hf = host_state(st_full)
+        for f in EnvState.FIELDS:
             both = np.concatenate([getattr(st_d[r], f).cpu().numpy() for r in range(2)], axis=-1)
             assert np.array_equal(hf[f].view(np.uint8), both.view(np.uint8)), f"t={t}: {f} of the two shards differs from one context"
         assert torch.equal(W_d[0], W_d[1])
@@ -361,7 +347,7 @@ def test_agent_checkpoint_across_the_counter_boundary(tmp_path):
     torch.cuda.synchronize()
     assert a.t == b.t == 2 ** 32 + 3
     assert torch.equal(a.W, b.W), "the resumed run's weights differ"
-    for f in FIELDS:
+    for f in EnvState.FIELDS:
         assert torch.equal(getattr(a.state, f), getattr(b.state, f)), f"the resumed run's state differs ({f})"
 
 

@@ -10,7 +10,8 @@ import pytest
 import sc_oracle
 import interrupt_learning_model as ilm
 from ref64 import env_order_layout
-from util import HP, SCALE
+from skill_chaining_with_graphs_amd.core import EnvState
+from util import HP, SCALE, oracle_block
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -37,7 +38,7 @@ def test_every_build_holds_the_interrupting_step_kernel():
 
 
 def _case(name, n, n_opt, block, seed, run_share, gest=0, layout=None):
-    sc_oracle.use_block_envs(block)
+    """(The caller holds the oracle on the build for `block` while it uses what this returns: oracle_block(block); 256 is the default.)"""
     import skill_chaining_with_graphs_amd as scg
     m = scg.load_map(name)
     n_vf = n_opt + 1
@@ -59,28 +60,23 @@ CASES = [
 ]
 
 
-@pytest.fixture(autouse=True)
-def _restore_block():
-    yield
-    sc_oracle.use_block_envs(256)
-
-
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0]}-n{c[1]}-o{c[2]}-b{c[3]}")
 def test_emulator_reproduces_sco_step_without_interrupts(case):
-    orc, m, st, W, clf, mask = _case(*case)
-    layout = env_order_layout(st["option_id"], orc.n_vf, case[3])
-    assert layout == case[7]
-    gest = case[6]
-    plain = ilm.copy_state(st)
-    G, n_k = orc.step(plain, W, clf, 11, mask)
-    post, Ge, nke, info = ilm.step(orc, st, W, clf, 11, mask, gest=gest, interrupt=False, recompute=True)
-    assert info["keep"].sum() > 0
-    for f in ilm.FIELDS:
-        assert np.array_equal(post[f].view(np.uint8), plain[f].view(np.uint8)), f
-    assert np.array_equal(nke, n_k)
-    for k in range(orc.n_vf):
-        assert n_k[k] > 0, k
-        assert np.array_equal(Ge[k], G[k]), f"VF {k}: {np.sum(Ge[k] != G[k])} elements differ"
+    with oracle_block(case[3]):
+        orc, m, st, W, clf, mask = _case(*case)
+        layout = env_order_layout(st["option_id"], orc.n_vf, case[3])
+        assert layout == case[7]
+        gest = case[6]
+        plain = ilm.copy_state(st)
+        G, n_k = orc.step(plain, W, clf, 11, mask)
+        post, Ge, nke, info = ilm.step(orc, st, W, clf, 11, mask, gest=gest, interrupt=False, recompute=True)
+        assert info["keep"].sum() > 0
+        for f in EnvState.FIELDS:
+            assert np.array_equal(post[f].view(np.uint8), plain[f].view(np.uint8)), f
+        assert np.array_equal(nke, n_k)
+        for k in range(orc.n_vf):
+            assert n_k[k] > 0, k
+            assert np.array_equal(Ge[k], G[k]), f"VF {k}: {np.sum(Ge[k] != G[k])} elements differ"
 
 
 def test_emulator_acting_equals_a_step_by_step_oracle_emulation_of_section_11():
@@ -109,7 +105,7 @@ def test_emulator_acting_equals_a_step_by_step_oracle_emulation_of_section_11():
         ref["opt_steps"][e] = 0
         ref["qcache"][:, e] = q0[:, cut]
         assert np.array_equal(np.nonzero(info["interrupted"])[0], e)
-        for f in ilm.FIELDS:
+        for f in EnvState.FIELDS:
             assert np.array_equal(post[f].view(np.uint8), ref[f].view(np.uint8)), f"t {t}: {f}"
         total += len(e)
         st = post

@@ -14,7 +14,7 @@ from bits import is_neg_zero, is_subnormal
 from interrupt_learning_model import env_order
 from ref64 import C_PHI, Q_FLOOR, SUB, U32, fit_model, q_model, q_update_floor, q_update_model, sigmoid_model
 from test_ref64_oracle import OracleRunner, check_step, pre_state
-from util import HP, SCALE, chain_classifiers, fourier_reference, random_states, random_weights
+from util import HP, SCALE, chain_classifiers, fourier_reference, oracle_block, random_states, random_weights
 
 FIGURES = {}
 
@@ -421,11 +421,8 @@ def test_measured_counts_of_the_subnormal_step():
 def test_step_edges_reach_both_operand_roads(block_envs):
     """With blocks of 64 envs the 257-env case has envs that keep running their block's option (W from LDS) AND envs entering
     an option that no env of their block runs (W from memory); with blocks of 256 every option has a run in the one full block."""
-    sc_oracle.use_block_envs(block_envs)
-    try:
+    with oracle_block(block_envs):
         out, got, pre = edge_subnormal_weights(OracleRunner, 257, -125)
-    finally:
-        sc_oracle.use_block_envs(256)
     n_lds, n_mem = eval_paths(pre, out, 4, block_envs)
     report(f"b{block_envs} n=257: envs on the LDS road, on the memory road", (n_lds, n_mem))
     assert n_lds > 0

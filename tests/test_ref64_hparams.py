@@ -14,11 +14,10 @@ tests/test_gpu_ref64_hparams.py runs the same cases on the HIP path."""
 import numpy as np
 import pytest
 
-import sc_oracle
 from ref64 import clf_model, env_order_layout
 from test_ref64_interrupt import EmulatorRunner, seat_running_envs
 from test_ref64_oracle import TREE, OracleRunner, assert_rarely_ambiguous, check_step, pre_state, tree_classifiers
-from util import HP, chain_classifiers, random_weights
+from util import HP, chain_classifiers, oracle_block, random_weights
 
 WIDE = 1 << 20                                # the large re-offer period: its mask 2^20 - 1 opens for one env id in 2^20
 BASES = (0, WIDE - 100)                       # env ids 0..256 (t + g = 0 at t = 0 only) and ids that cross 2^20 (one env per step)
@@ -169,11 +168,8 @@ def test_oracle_at_hyperparameter_edges(case, mode):
 @pytest.mark.parametrize("mode", list(RUNNERS))
 def test_oracle_at_hyperparameter_edges_on_the_64_env_build(mode):
     """The 1000-env case on the oracle's 64-env build (16 blocks, the last one partial)."""
-    sc_oracle.use_block_envs(64)
-    try:
+    with oracle_block(64):
         hparam_case(RUNNERS[mode], HP_CASES[-1], 64)
-    finally:
-        sc_oracle.use_block_envs(256)
 
 
 def test_cases_change_one_setting_and_cover_the_padded_layout():

@@ -11,11 +11,10 @@ import numpy as np
 import pytest
 
 import interrupt_learning_model as ilm
-import sc_oracle
 import skill_chaining_with_graphs_amd as scg
 from ref64 import clf_model, compare, env_order_layout
 from test_ref64_oracle import SWEEP, OracleRunner, assert_rarely_ambiguous, check_step, pre_state, tree_classifiers
-from util import HP, chain_classifiers, disc_weights, random_weights
+from util import HP, chain_classifiers, disc_weights, oracle_block, random_weights
 
 MAX_EP, MAX_OPT = HP["max_episode_steps"], HP["max_option_steps"]
 
@@ -91,11 +90,8 @@ CPU_CASES = [(c, b) for b in (256, 64) for c in INT_SWEEP if b == 256 or c[1] <=
 
 @pytest.mark.parametrize("cfg,block_envs", CPU_CASES, ids=case_ids(CPU_CASES))
 def test_model_matches_the_interrupt_emulator(cfg, block_envs):
-    sc_oracle.use_block_envs(block_envs)
-    try:
+    with oracle_block(block_envs):
         interrupt_sweep_case(EmulatorRunner, cfg, block_envs)
-    finally:
-        sc_oracle.use_block_envs(256)
 
 
 def test_interrupt_sweep_covers_both_env_order_layouts():
@@ -327,7 +323,7 @@ def test_mutation_d_opt_steps_not_reset(base):
 
 def test_mutation_e_one_env_given_the_plain_step(base):
     st = _state(base)
-    for f in ilm.FIELDS:
+    for f in scg.EnvState.FIELDS:
         st[f][..., base.e] = base.plain[f][..., base.e]
     _refuse(base, st=st)
 

@@ -11,7 +11,7 @@ import pytest
 import sc_oracle
 import skill_chaining_with_graphs_amd as scg
 from ref64 import StepModel, compare, env_order_layout, philox4x32_10
-from util import HP, SCALE, chain_classifiers, disc_weights, random_states, random_weights
+from util import HP, SCALE, chain_classifiers, disc_weights, oracle_block, random_states, random_weights
 
 TREE = [0, 0, 0, 1, 2, 4]                 # 1 -> goal, 2 -> goal, 3 -> 1, 4 -> 2, 5 -> 4
 
@@ -141,11 +141,8 @@ def sweep_case(make, cfg, block_envs, steps=(0, 1, 2), seed=None):
 
 @pytest.mark.parametrize("cfg,block_envs", CASES, ids=[f"b{b}-{c[0]}-{c[1]}-{c[2]}opt-{c[9]}" for c, b in CASES])
 def test_oracle_step_matches_the_float64_model(cfg, block_envs):
-    sc_oracle.use_block_envs(block_envs)
-    try:
+    with oracle_block(block_envs):
         sweep_case(OracleRunner, cfg, block_envs)
-    finally:
-        sc_oracle.use_block_envs(256)
 
 
 def test_sweep_covers_both_env_order_layouts():

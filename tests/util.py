@@ -1,4 +1,12 @@
-"""Shared helpers for the tests (host side only)."""
+"""The tests' rig, host side only (nothing here needs a device; tests/gpu_util.py holds the half that does).
+
+`oracle_block(b)` puts the oracle on its build for another SPEC §5 block size for a `with` body and back on the 256-env build
+after it. `make_oracle` is an oracle with the test hyper-parameters HP. `random_states`, `random_env_state`, `random_weights`
+and `chain_classifiers` are the seeded inputs the parity tests share: a test that needs "some running env batch" takes
+random_env_state and uploads it with gpu_util.state_to_device. The maps below (dense, hub, edge-count, pocket) and the
+restatement of the HIP physics' candidate pruning serve the physics tests."""
+import contextlib
+
 import numpy as np
 
 import sc_oracle
@@ -8,6 +16,16 @@ from skill_chaining_with_graphs_amd.core import fourier_scale_table
 SCALE = fourier_scale_table()
 HP = dict(gamma=0.99, alpha=1e-3, epsilon=0.1, r_option_success=100.0, max_episode_steps=60,
           max_option_steps=25)
+
+
+@contextlib.contextmanager
+def oracle_block(block_envs):
+    """The oracle built for `block_envs` (64 / 128 / 256) inside the body; the default 256-env build after it, also on an error."""
+    sc_oracle.use_block_envs(block_envs)
+    try:
+        yield block_envs
+    finally:
+        sc_oracle.use_block_envs(256)
 
 
 def make_oracle(map_name, n_envs=1, n_options=0, seed=0, env_id_base=0, enabled_mask=0, n_threads=4, **hp):
@@ -24,6 +42,19 @@ def random_states(m, n, seed, vmax=2.0, near_walls=True):
     pos = m.sample_free(n, rng, margin=1.05 if near_walls else 2.0)
     v = rng.uniform(-vmax, vmax, (n, 2)).astype(np.float32)
     return pos[:, 0].copy(), pos[:, 1].copy(), v[:, 0].copy(), v[:, 1].copy()
+
+
+def random_env_state(m, n, n_opt, seed, *, id_lo, id_hi, opt_steps_hi, max_episode_steps):
+    """A running env batch as a dict of arrays: random_states' positions / velocities (vmax 1.5), option ids in [id_lo, id_hi]
+    (out-of-range ids are part of some tests), option-step counters below opt_steps_hi, episode-step counters below
+    max_episode_steps, random qcache. The draws and their order are fixed: tests pin their cases on them."""
+    rng = np.random.default_rng(seed)
+    x, y, vx, vy = random_states(m, n, seed, vmax=1.5)
+    return dict(x=x, y=y, vx=vx, vy=vy,
+                option_id=rng.integers(id_lo, id_hi + 1, n).astype(np.int32),
+                opt_steps=rng.integers(0, opt_steps_hi, n).astype(np.int32),
+                ep_steps=rng.integers(0, max_episode_steps, n).astype(np.int32),
+                qcache=rng.standard_normal((5, n)).astype(np.float32))
 
 
 def disc_weights(cx, cy, radius):
