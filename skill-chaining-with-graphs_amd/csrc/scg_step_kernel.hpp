@@ -20,7 +20,16 @@
 //   groups of four: the accumulation order of SPEC §5 is reproduced exactly (null items masked to +0 on both operands).
 // Value functions with update items that are NOT that prefix (gestating options, a second option in the padded env
 // order) take a single-VF pass of their own afterwards (compacted lists, as in rounds 2-3); value functions that only
-// have envs entering them are evaluated as extra E units of pass 0 (operands from memory). MODE_TRANS / MODE_QVAL are single passes.
+// have envs entering them are evaluated as extra E units of the merged pass (operands from memory). MODE_TRANS / MODE_QVAL run the
+// merged pass's body on one value function.
+// Round 14: the pass body is written ONCE (run_pass, a generic lambda on the compile-time flag MERGED) and instantiated twice. The
+// merged pass is straight-line code of the kernel — E over position groups, kA = 0 and kBp = kB, the helper waves' U1, the
+// evaluation-only lists are facts of that copy, and it holds no code of the single passes (the saved root column, the compacted E,
+// U1 behind E). The single-VF passes run from a loop BEHIND it, in ascending order of their value function, and everything behind
+// the merged pass reads the kernel's arguments afresh from the kernel-argument segment (reread_args), so that no argument the cold
+// code needs is kept in a scalar register — or parked in a VGPR lane — across the merged pass. While both lived in one
+// `for (pass ...)` loop the kernel spilled 125 SGPRs and one VGPR (393 lane moves, 16 B of scratch per lane); now 26 and none
+// (81 lane moves, 38 of them up to the merged pass's last MFMA, no scratch): profiles/r14_pass_peel.txt.
 // Every sum has the pinned order of SPEC §3.1 / §5 (no atomics on data): the CPU oracle reproduces every bit.
 #pragma once
 
@@ -236,6 +245,15 @@ __device__ __attribute__((noinline)) void stage_w_cold(const float *Wk, float *s
 #pragma unroll
     for (int i = 0; i < 2; ++i) { const int d = tid + i * THREADS; if (d < N4) dst4[d] = v[i]; }
     if (tid < N1) s_dst[W_TAIL + tid] = tl;
+}
+
+// The kernel's arguments read again from the kernel-argument segment (StepArgs is td_kernel's one argument: offset 0), through a pointer
+// the compiler cannot trace back to the loads of the kernel's entry: scalar loads where they are used, nothing kept live up to there.
+typedef const __attribute__((address_space(4))) StepArgs *StepArgsK;
+__device__ __forceinline__ StepArgsK reread_args() {
+    StepArgsK p = (StepArgsK)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
 }
 
 template <int MODE>
@@ -789,11 +807,11 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     // candidates evaluated in pass 0 (the block's option, value functions without a pass of their own); kdec = k: option k's own
     // single pass has just run. A declined env gets option 0 in the block's flags, the mark in its result line (commit_row then takes
     // the root's Q values the root's unit left beside the line) and its share of the next order's histogram moved to key 0.
-    auto gate = [&](int kdec) {
+    auto gate = [&](const auto &A, int kdec) {
         if (!FUSED) return;
         int ln;                                             // (the thread id is re-made from the hardware lane counter: the kernel's own `tid`, kept
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));      //  live across the pass loop for this, is what the
-        const int ti = (wave << 6) | ln;                    //  register allocator spills — see the top of the pass loop)
+        const int ti = (wave << 6) | ln;                    //  register allocator spills — see the top of run_pass)
         if (ti >= nb || !(s_ia[ti] & IA_ENTERING)) return;
         const int cand = s_on[ti];
         const bool mine = kdec < 0 ? (cand >= 1 && cand < MAX_VF && !((single0 >> cand) & 1u)) : cand == kdec;
@@ -815,7 +833,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     // -c (0: no candidate), where c is the candidate P worked out as if the option had ended — with opt_steps 0, and its share of the next
     // order's histogram moves from key o to key 0. kdec < 0: the block's option kB after pass 0 (both maxima in s_maxq); kdec = k: option k's
     // own single pass has just run (its max in s_maxq's first half, the root's saved in s_qsa's second half).
-    auto interrupt_rewrite = [&](int kdec) {
+    auto interrupt_rewrite = [&](const auto &A, int kdec) {
         if constexpr (INT) {
             int ln;
             asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
@@ -841,7 +859,15 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
     // no pass, no slab, counts 0 — instead of computing on them; the step as a whole is voided by the reduce launch
     const bool blk_fail = FUSED && __builtin_amdgcn_readfirstlane(s_misc[M_FAIL]) != 0;
     if (blk_fail && tid < A.n_vf && A.cnts) A.cnts[(size_t)b * A.n_vf + tid] = 0;
-    for (int pass = 0; pass < n_pass0 + MAX_VF && !blk_fail; ++pass) {
+    // ONE pass, written once and instantiated twice on the compile-time flag MERGED (round 14). MERGED: the merged pass — value
+    // function A = the root (the caller's VF in the un-fused modes), B = the block's option, E over position groups, in a learning
+    // step the helper waves' list and U1 — as straight-line code of the kernel: at the headline size it is the only pass a block runs.
+    // !MERGED: the single-VF pass of value function kA_single, run from the loop behind the merged pass. While both lived in one
+    // `for (pass ...)` loop, everything invariant in the body was hoisted and stayed live across the whole of the merged pass, whose
+    // values were allocated together with the cold code of the later iterations: 125 spilled SGPRs and 347 lane moves up to the merged
+    // pass's last MFMA (profiles/r14_pass_peel.txt).
+    auto run_pass = [&](auto merged_c, const auto &A, int kA_single) {
+        constexpr bool MERGED = decltype(merged_c)::value;
         // Opaque copies of the thread and lane ids for the pass: every per-lane address of the pass body is loop-invariant, and
         // hoisted out of the pass loop they all stay live across it — the register allocator then spills them to scratch.
         // (Re-made from the hardware lane counter rather than copied from the kernel's tid: kept live across the loop the copy
@@ -851,19 +877,15 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_p));
         const int tid_p = (wave << 6) | lane_p;
         const int tid = tid_p, lane = lane_p;
-        int kA, kBp;                                        // value functions of this pass (kBp < 0: none)
-        bool dense;                                         // E over position groups (pass 0) or over the compacted eval list
-        if (pass == 0) {
-            if (!n_pass0) continue;
-            kA = FUSED ? 0 : A.k_lo; kBp = kB; dense = true;
-        } else {
-            if (!single) break;
-            kA = __builtin_ctz(single); single &= single - 1; kBp = -1; dense = false;
-        }
-        const bool u1_done = helpers && pass == 0;          // the helper waves ran U1 and built the list under phase P
-        if (pass > 0) block_lds_sync();                     // (pass 0 starts behind the barrier that ends phase P)
-        if (FUSED && pass > 0 && kA == __builtin_ctz(single0)) {      // first single pass: save the root's max_a Q_0(s_next, a) of pass 0
-            if (tid < nb) s_qsa[BLOCK_ENVS + tid] = s_maxq[tid];                 // before this pass's E reuses s_maxq (s_qsa's second half: B's Q(s, a), pass 0 only)
+        const int kA = MERGED ? (FUSED ? 0 : A.k_lo) : kA_single;      // value functions of this pass (kBp < 0: none)
+        const int kBp = MERGED ? kB : -1;
+        constexpr bool dense = MERGED;                      // E over position groups (merged pass) or over the compacted eval list
+        const bool u1_done = MERGED && helpers;             // the helper waves ran U1 and built the list under phase P
+        if constexpr (!MERGED) {
+            block_lds_sync();                               // (the merged pass starts behind the barrier that ends phase P)
+            if (FUSED && kA == __builtin_ctz(single0)) {    // first single pass: save the root's max_a Q_0(s_next, a) of the merged pass
+                if (tid < nb) s_qsa[BLOCK_ENVS + tid] = s_maxq[tid];             // before this pass's E reuses s_maxq (s_qsa's second half: B's Q(s, a), merged pass only)
+            }
         }
         // ---- per-env flags of the pass (SPEC §5): ev bit v = the env needs Q_v(s_next, .) (bootstrap target and/or next
         // action); update items of A (all of them in pass 0 of a fused step: the root updates on every env) with their action
@@ -899,7 +921,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         // compacted list: single passes -> the eval items of A; pass 0 -> the envs that need Q_B but lie outside B's prefix groups
         const int pg_b = (mB + 7) >> 3;                     // position groups that hold B's prefix
         const bool cmp = dense ? (evB && (ft >> 3) >= pg_b) : evA;
-        const bool eo_pass = pass == 0 && FUSED && eval_only != 0;
+        const bool eo_pass = MERGED && FUSED && eval_only != 0;
         const int on_me = (unsigned)ft < (unsigned)nb ? (int)s_on[ft] : 0;
         const bool eo = eo_pass && (unsigned)ft < (unsigned)nb && ((eval_only >> (on_me & 7)) & 1u);       // this env enters an evaluation-only value function
         uint64_t me[MAX_VF];
@@ -930,7 +952,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                 }
             }
         }
-        if (!u1_done) {                                      // (the helper waves staged W_0 / W_kB under phase P)
+        if (!u1_done) {                                      // (the helper waves staged W_0 / W_kB under phase P; merged pass: acting-only steps and the un-fused modes)
             // (kA / kBp are wave-uniform: readfirstlane keeps the pointer arithmetic on the scalar unit)
             const float *Wa = A.W + (MODE == MODE_QVAL ? 0 : (size_t)__builtin_amdgcn_readfirstlane(kA) * NACT * NF);
             stage_w_cold(Wa, s_W, tid);
@@ -1008,7 +1030,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             A.cnts[(size_t)b * A.n_vf + kA] = nupd;
             if (kBp >= 1) A.cnts[(size_t)b * A.n_vf + kBp] = nupdB;
         }
-        if (pass == 0) SCG_LITE(4);                         // E starts
+        if constexpr (MERGED) SCG_LITE(4);                  // E starts
         // ---- E: Q_v(s_next, .), one 8-item column block per wave-iteration (SPEC §3.1); the tables of a block are built
         // once and serve both value functions. Units [0, npg) are position groups (dense pass), the rest 8-item blocks of
         // the compacted list.
@@ -1016,7 +1038,7 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         const int n_own = (n_cmp + 7) >> 3;                 // units of the pass's own compacted list
         const int eo_units = eo_pass ? __builtin_amdgcn_readfirstlane(s_misc[M_EO + 6]) : 0;
         const int n_units = npg + n_own + eo_units;
-        if (n_units + nupd == 0) continue;
+        if (n_units + nupd == 0) return;
         {
         // Dealing: units are taken from a counter in LDS by whichever wave is free (a static deal left the four top waves —
         // the youngest of their SIMDs — 15k cycles behind the others). Order: the compacted units first (the pass's own list,
@@ -1026,6 +1048,10 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         // written — an LDS counter instead of the barrier above — measured 750.6 against 749.6 M env-steps/s: not kept.)
         const int n_cu = n_own + eo_units;
         for (;;) {
+            // (the lane id per unit from the hardware lane counter: the pass's copy, live across this loop, was the kernel's one spilled
+            //  VGPR — stored in front of the loop and reloaded from scratch for every unit)
+            int lane;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
             int it = 0;
             if (lane == 0) it = atomicAdd(&s_misc[M_ECTR], 1);
             it = __builtin_amdgcn_readfirstlane(it);
@@ -1107,12 +1133,15 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
             wave_lds_sync();
         }
         }
-        // ---- U1 (pass 0 of a learning step: ran under phase P on the helper waves)
-        if (MODE != MODE_QVAL && nupd > 0 && !u1_done) run_u1(wave, WAVES, n_units);   // dealt on behind E's blocks
-        if (MODE == MODE_QVAL || nupd == 0) continue;
-        if (pass == 0) SCG_LITE(5);                         // this wave's E is done
+        // ---- U1 (merged pass of a learning step: ran under phase P on the helper waves; a fused merged pass without helpers is an
+        // acting-only step and has no update item, so U1 behind E exists in the single passes and the un-fused modes only)
+        if constexpr (!(FUSED && MERGED)) {
+            if (MODE != MODE_QVAL && nupd > 0 && !u1_done) run_u1(wave, WAVES, n_units);   // dealt on behind E's blocks
+        }
+        if (MODE == MODE_QVAL || nupd == 0) return;
+        if constexpr (MERGED) SCG_LITE(5);                  // this wave's E is done
         block_lds_sync();                                   // s_maxq, s_qsa cross waves; the staging area changes hands
-        if (pass == 0) SCG_LITE(6);                         // ... everybody's: U2 starts
+        if constexpr (MERGED) SCG_LITE(6);                  // ... everybody's: U2 starts
 
         // ---- U2: the block partials (SPEC §5). Every action run of A's list is padded with null items to a multiple of 4
         // (groups of four items); run a has Ga groups, the first GBa of which also carry items of B. The groups are laid out in
@@ -1126,8 +1155,8 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
         //          Wave w < 15 owns the three output tiles (mi = w % 3, ni = 0..2) of action a = w / 3 of BOTH value functions:
         //          per group one P operand per value function and three C operands feed six (twelve) independent MFMAs;
         //          accumulators stay in registers for the whole pass and go straight to the block's slabs
-        int lane_u = lane;
-        asm volatile("" : "+v"(lane_u));                    // (lane roles derived afresh: see SCG_LANE_ROLES)
+        int lane_u;                                         // (lane roles derived afresh: see SCG_LANE_ROLES — from the hardware lane counter, so
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_u));      //  that nothing per-lane lives across E)
         const int n16 = lane_u & 15, g = lane_u >> 4;
         int Ga[NACT], GBa[NACT];
         int Gtot = 0;
@@ -1336,23 +1365,36 @@ __global__ __launch_bounds__(THREADS, 4) void td_kernel(const StepArgs A) {
                     }
                 }
             }
-        } else if (tid == 0 && A.cnts) {
+        } else if (wave == 0 && lane_u == 0 && A.cnts) {
             A.cnts[(size_t)b * A.n_vf + kA] = 0;
             if (kBp >= 1) A.cnts[(size_t)b * A.n_vf + kBp] = 0;
         }
-        if (pass == 0) SCG_LITE(7);                         // pass 0 done (slab stores issued)
-        if (pass > 0) gate(kA);
-        if constexpr (INT) { if (pass > 0 || kB >= 1) interrupt_rewrite(pass > 0 ? kA : -1); }
+        if constexpr (MERGED) SCG_LITE(7);                  // merged pass done (slab stores issued)
+        if constexpr (!MERGED) gate(A, kA);
+        if constexpr (INT) { if (!MERGED || kB >= 1) interrupt_rewrite(A, MERGED ? -1 : kA); }
+    };
+    // Passes: the merged one, then the single-VF passes in ascending order of their value function.
+    if (!blk_fail && n_pass0) run_pass(std::true_type{}, A, 0);
+    // Everything behind the merged pass is cold or short, and reads its arguments AFRESH from the kernel-argument segment (Ac): read
+    // through the kernel's own copy A, every argument this code needs — loaded at the kernel's entry — stayed live in a scalar register,
+    // or parked in a VGPR lane, across the whole of the merged pass.
+    const auto &Ac = *reread_args();
+    if (!blk_fail) {
+        while (single) {
+            const int k = __builtin_ctz(single);
+            single &= single - 1;
+            run_pass(std::false_type{}, Ac, k);
+        }
     }
     if (FUSED && n_pass0 && !blk_fail) {       // the candidates evaluated in pass 0 (their maxima are in s_maxq's second half, which
-        if (!A.learn) block_lds_sync();                     // no later pass touches; acting-only steps: pass 0 ended behind E, without a barrier)
-        gate(-1);
+        if (!Ac.learn) block_lds_sync();                    // no later pass touches; acting-only steps: pass 0 ended behind E, without a barrier)
+        gate(Ac, -1);
     }
-    if (FUSED && A.async_word) {               // a hand-off poll ran out somewhere in this block: tell the host (sticky)
+    if (FUSED && Ac.async_word) {              // a hand-off poll ran out somewhere in this block: tell the host (sticky)
         block_lds_sync();
         if (tid == 0 && s_misc[M_FAIL]) {
-            __hip_atomic_fetch_or(A.async_word, SCG_ASYNC_STEP_HANDOFF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if (A.fail_flag) __hip_atomic_store(A.fail_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_or(Ac.async_word, SCG_ASYNC_STEP_HANDOFF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (Ac.fail_flag) __hip_atomic_store(Ac.fail_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 #ifdef SCG_STAMPS_LITE
