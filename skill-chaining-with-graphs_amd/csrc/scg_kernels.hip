@@ -302,6 +302,13 @@ static std::vector<CtxAlloc> ctx_allocs(scg_ctx *c) {
     };
 }
 
+#ifdef SCG_REDUCE_STAMPS
+static size_t reduce_stamp_bytes(const scg_ctx *c) {      // the largest reduce grid of this context: the slab workgroups + one slot per row of 256 envs
+    const int nrow = (c->cfg.n_envs + 255) / 256, sy = (nrow + RED_NCOL - 1) / RED_NCOL;
+    return (size_t)RED_NCOL * (c->n_vf + sy) * RED_STAMP_SLOTS * sizeof(unsigned long long);
+}
+#endif
+
 int scg_create(scg_ctx **out, const scg_config *cfg) {
     if (!out || !cfg) return fail(nullptr, SCG_ERR_INVALID, "scg_create: null argument");
     *out = nullptr;
@@ -346,6 +353,9 @@ int scg_create(scg_ctx **out, const scg_config *cfg) {
 #ifdef SCG_STAMPS_LITE
     if (hipMalloc(&c->d_stamps, (size_t)c->nblk * STAMP_SLOTS * sizeof(unsigned long long)) == hipSuccess)
         (void)hipMemset(c->d_stamps, 0, (size_t)c->nblk * STAMP_SLOTS * sizeof(unsigned long long));
+#endif
+#ifdef SCG_REDUCE_STAMPS
+    if (hipMalloc(&c->d_stamps, reduce_stamp_bytes(c)) == hipSuccess) (void)hipMemset(c->d_stamps, 0, reduce_stamp_bytes(c));
 #endif
     c->parents = 0;
     for (int k = 1; k < MAX_VF; ++k) c->parents |= (uint32_t)(k - 1) << (3 * k);      // chain: 1 -> goal, k -> k-1
@@ -497,6 +507,9 @@ static int launch_reduce(scg_ctx *c, float *W, uint32_t apply, int nblk, hipStre
             R.c_rows = c->d_collect_rows; R.c_bits = c->arm_bits; R.c_L = c->arm_L; R.c_ring_len = c->ring_len;
         }
     }
+#ifdef SCG_REDUCE_STAMPS
+    R.stamps = c->d_stamps;
+#endif
     if (mode == COMMIT_ONLY) {
         hipLaunchKernelGGL(commit_kernel, dim3(nrow), dim3(256), 0, s, R);
         SCG_HIP(c, hipGetLastError());
@@ -801,6 +814,16 @@ extern "C" int scg_diag_stamps(scg_ctx *c, unsigned long long *host_out /*[nblk]
     if (host_out && hipMemcpy(host_out, c->d_stamps, (size_t)c->nblk * STAMP_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return SCG_ERR_HIP;
     if (reset) (void)hipMemset(c->d_stamps, 0, (size_t)c->nblk * STAMP_SLOTS * sizeof(unsigned long long));
     return SCG_OK;
+}
+#endif
+
+#ifdef SCG_REDUCE_STAMPS
+// the last reduce launch's workgroup stamps, [RED_NCOL * (n_vf + row slots)][RED_STAMP_SLOTS] in grid order (y major); returns the workgroup count
+extern "C" int scg_diag_reduce_stamps(scg_ctx *c, unsigned long long *host_out, int32_t reset) {
+    if (!c || !c->d_stamps) return -1;
+    if (host_out && hipMemcpy(host_out, c->d_stamps, reduce_stamp_bytes(c), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (reset) (void)hipMemset(c->d_stamps, 0, reduce_stamp_bytes(c));
+    return (int)(reduce_stamp_bytes(c) / (RED_STAMP_SLOTS * sizeof(unsigned long long)));
 }
 #endif
 
