@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("SCG_LIB") or os.path.join(_HERE, "csrc", "libscg_hip.
 NUM_ACTIONS = 5
 FOURIER_ORDER = 5
 NUM_FEATURES = 1296
+W_ROW = NUM_ACTIONS * NUM_FEATURES     # one value function's weights: W is [n_vf] of these, a packed operand [n_vf] of W_ROW + 1
 MAX_OPTIONS = 5
 MAX_EDGES = 256
 CLF_STRIDE = 8
@@ -112,6 +113,9 @@ class Record(C.Structure):
 
 
 _P = C.c_void_p
+# the arguments the rollout and the trial entry points start with; each appends its own tail (record, interrupt counts, stream)
+_ROLLOUT = [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(RolloutStats)]
+_TRIALS = [_P, C.c_int32] + [_P] * 7 + [C.c_uint32, C.c_uint64, C.POINTER(TrialOut)]
 _SIGS = {
     "scg_abi_version": (C.c_int, []),
     "scg_block_envs": (C.c_int, []),
@@ -122,14 +126,11 @@ _SIGS = {
     "scg_set_hparams": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "scg_set_map": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     "scg_step": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_uint32, _P]),
-    "scg_rollout": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(RolloutStats), _P]),
-    "scg_option_trials": (C.c_int, [_P, C.c_int32] + [_P] * 7 + [C.c_uint32, C.c_uint64, C.POINTER(TrialOut), _P]),
-    "scg_rollout_record": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(RolloutStats),
-                                                         C.POINTER(Record), _P]),
-    "scg_option_trials_record": (C.c_int, [_P, C.c_int32] + [_P] * 7 + [C.c_uint32, C.c_uint64, C.POINTER(TrialOut),
-                                                                       C.POINTER(Record), _P]),
-    "scg_rollout_interrupt": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(RolloutStats),
-                                                            _P, C.POINTER(Record), _P]),
+    "scg_rollout": (C.c_int, _ROLLOUT + [_P]),
+    "scg_option_trials": (C.c_int, _TRIALS + [_P]),
+    "scg_rollout_record": (C.c_int, _ROLLOUT + [C.POINTER(Record), _P]),
+    "scg_option_trials_record": (C.c_int, _TRIALS + [C.POINTER(Record), _P]),
+    "scg_rollout_interrupt": (C.c_int, _ROLLOUT + [_P, C.POINTER(Record), _P]),
     "scg_grad_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "scg_set_grad_buffers": (C.c_int, [_P, _P, _P]),
     "scg_apply_update": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -234,9 +235,8 @@ def block_envs(block_envs: int | None = None) -> int:
     return int(load(block_envs).scg_block_envs())
 
 
-def check(status: int, ctx=None, what: str = "") -> None:
-    if status == 0:
-        return
-    lib = load()
-    msg = lib.scg_last_error(ctx).decode() if True else ""
-    raise ScgError(f"{what or 'scg call'} failed ({lib.scg_strerror(status).decode()}): {msg}")
+def check(status: int, ctx, what: str, lib: C.CDLL) -> None:
+    """Raise ScgError for a failed call of `lib`. The text comes from that library: a context's own lives in the context, the
+    text of a call without one (a refused scg_create) in a thread_local of the build that refused."""
+    if status != 0:
+        raise ScgError(f"{what or 'scg call'} failed ({lib.scg_strerror(status).decode()}): {lib.scg_last_error(ctx).decode()}")

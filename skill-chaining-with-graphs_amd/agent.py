@@ -6,7 +6,7 @@ named after north_star. Per-step work is one scg_step launch pair (fused kernel 
 nothing on the per-step path synchronises with or copies to the host."""
 from __future__ import annotations
 
-import ctypes as C
+import contextlib
 import os
 from typing import List, Optional
 
@@ -17,9 +17,12 @@ from . import _lib
 from . import dist as _dist
 from ._lib import CLF_STRIDE, NUM_ACTIONS, NUM_FEATURES, ScgError, auto_block_envs
 from .core import EnvState, ScgContext
+from .evaluation import EpisodeStats
 from .maps import PinballMap, load_map
 from .option import Option
 from .pinball import PinballDomain
+from .trajectory import Trajectory
+from .trials import OUTCOMES, TrialResult
 
 
 def frontier_masks(k: int, enabled_mask: int, gest_mask: int, parents, max_children: Optional[int] = None):
@@ -85,6 +88,9 @@ class SkillChainingAgent:
         self.domain = PinballDomain(self.ctx)
         self.state: EnvState = self.domain.state
         self.options: List[Option] = [Option(self, k) for k in range(self.n_vf)]
+        self.trace, self._ex, self._ex_cap = None, {}, None     # enable_tracing(): the ring + events, the example buffers by option
+        # grow_skill_tree()'s per-node buffers (kept for inspection); evaluate()'s n_episodes -> (context, EnvState, EpisodeStats); option_trials()'s context
+        self._frontier, self._eval_ctx, self._trial_ctx = None, {}, None
 
     # ------------------------------------------------------------------ option management (outer loop)
     def enable_option(self, k: int, enabled: bool = True) -> None:
@@ -199,29 +205,43 @@ class SkillChainingAgent:
         or enable it at once, and stop once the start states are covered. The host looks at the device-side
         counters only every `poll_every` step-batches. Returns one report dict per created option."""
         report = []
-        sx = torch.as_tensor(self.map.starts[:, 0].copy(), device=self.W.device)
-        sy = torch.as_tensor(self.map.starts[:, 1].copy(), device=self.W.device)
         max_examples = min(max_examples, self._ex_cap)
         for k in range(1, self.n_options + 1):
             if ((self.enabled_mask | self.gest_mask) >> k) & 1:
                 continue
-            got = steps = 0
-            while steps < steps_per_option and got < max_examples:
-                for _ in range(min(poll_every, steps_per_option - steps)):
-                    self.step_batch()
-                    self.collect_examples(k, l_pos, l_neg)
-                    steps += 1
-                got = self.examples_held(k)
-                self.poll_gestation()
+            got, steps = self._collect_until(lambda: self.collect_examples(k, l_pos, l_neg), lambda: self.examples_held(k),
+                                             lambda got: got >= max_examples, 0, steps_per_option, poll_every)
             if got < min_examples:
                 break
             acc, gsteps = self._fit_and_gestate(k, gestation, gestation_steps, poll_every, fit)
-            cov = float(self.options[k].initiation_classifier.predict(sx, sy).float().mean())
+            cov = self._start_coverage([k])
             report.append(dict(option=k, parent=int(self.ctx.parents[k]), steps=steps, examples=got,
                                accuracy=acc, start_coverage=cov, gestation_steps=gsteps))
             if cov >= start_coverage:
                 break
         return report
+
+    def _collect_until(self, collect, held, full, counts, steps_per_option: int, poll_every: int):
+        """An option's collection in chain_skills and grow_skill_tree: step-batches with `collect()` behind each, until
+        `steps_per_option` of them have run or `full(counts)`; the host reads `held()`, the counts (from `counts` on), and
+        the gestation counters only every `poll_every` step-batches. Returns (counts, step-batches run)."""
+        steps = 0
+        while steps < steps_per_option and not full(counts):
+            for _ in range(min(poll_every, steps_per_option - steps)):
+                self.step_batch()
+                collect()
+                steps += 1
+            counts = held()
+            self.poll_gestation()
+        return counts, steps
+
+    def _start_coverage(self, options) -> float:
+        """The share of the map's start states that lie in the initiation set of one of `options`."""
+        sx, sy = (torch.as_tensor(self.map.starts[:, i].copy(), device=self.W.device) for i in (0, 1))
+        inside = torch.zeros_like(sx, dtype=torch.bool)
+        for j in options:
+            inside |= self.options[j].initiation_classifier.predict(sx, sy).bool()
+        return float(inside.float().mean())
 
     def _fit_and_gestate(self, k: int, gestation: int, gestation_steps: int, poll_every: int, fit: dict):
         """Fit option k on its example buffer (create_option) and run its gestation: step-batches until the success counters
@@ -254,31 +274,26 @@ class SkillChainingAgent:
         cap). Returns one report dict per created option."""
         if self.group is not None:
             raise ValueError("grow_skill_tree: a sharded agent (group=...) cannot grow a skill tree yet; use chain_skills")
-        if getattr(self, "trace", None) is None:
+        if self.trace is None:
             raise ScgError("grow_skill_tree: tracing is off (enable_tracing)")
-        report = []
         dev = self.W.device
-        sx = torch.as_tensor(self.map.starts[:, 0].copy(), device=dev)
-        sy = torch.as_tensor(self.map.starts[:, 1].copy(), device=dev)
         cap = min(max_examples, self._ex_cap)
         node_xy = torch.zeros((self.n_vf, cap, 2), dtype=torch.float32, device=dev)
         node_lab = torch.zeros((self.n_vf, cap), dtype=torch.uint8, device=dev)
         node_cnt = torch.zeros(self.n_vf, dtype=torch.int32, device=dev)
-        self._frontier = (node_xy, node_lab, node_cnt)      # the per-node buffers (kept for inspection)
+        self._frontier = (node_xy, node_lab, node_cnt)
+        report = []
         for k in range(1, self.n_options + 1):
             if ((self.enabled_mask | self.gest_mask) >> k) & 1:
                 continue
             target, cover = frontier_masks(k, self.enabled_mask, self.gest_mask, self.ctx.parents, max_children)
             node_cnt.zero_()
-            counts, steps = [0] * self.n_vf, 0
-            while steps < steps_per_option and max(counts[p] for p in range(self.n_vf) if (target >> p) & 1) < cap:
-                for _ in range(min(poll_every, steps_per_option - steps)):
-                    self.step_batch()
-                    self.ctx.collect_frontier(target, cover, self.clf.view(-1), l_pos, l_neg, node_xy.view(-1),
-                                              node_lab.view(-1), node_cnt)
-                    steps += 1
-                counts = [int(c) for c in node_cnt.tolist()]
-                self.poll_gestation()
+            counts, steps = self._collect_until(
+                lambda: self.ctx.collect_frontier(target, cover, self.clf.view(-1), l_pos, l_neg, node_xy.view(-1),
+                                                  node_lab.view(-1), node_cnt),
+                lambda: [int(c) for c in node_cnt.tolist()],
+                lambda counts: max(counts[p] for p in range(self.n_vf) if (target >> p) & 1) >= cap,
+                [0] * self.n_vf, steps_per_option, poll_every)
             p = choose_parent(counts, target, min_examples)
             if p is None:
                 break
@@ -291,11 +306,7 @@ class SkillChainingAgent:
             xy[:n].copy_(node_xy[p, :n]); lab[:n].copy_(node_lab[p, :n]); cnt.fill_(n)
             acc, gsteps = self._fit_and_gestate(k, gestation, gestation_steps, poll_every, fit)
             known = self.enabled_mask | self.gest_mask
-            cover_start = torch.zeros_like(sx, dtype=torch.bool)
-            for j in range(1, self.n_options + 1):
-                if (known >> j) & 1:
-                    cover_start |= self.options[j].initiation_classifier.predict(sx, sy).bool()
-            cov = float(cover_start.float().mean())
+            cov = self._start_coverage([j for j in range(1, self.n_options + 1) if (known >> j) & 1])
             report.append(dict(option=k, parent=p, steps=steps, examples=n, node_examples=counts, accuracy=acc,
                                start_coverage=cov, gestation_steps=gsteps))
             if cov >= start_coverage:
@@ -330,52 +341,46 @@ class SkillChainingAgent:
         options when `interrupt_learning` is set (SPEC §12); an acting-only one (learn=False) never does — evaluate(interrupt=True)
         is the acting counterpart."""
         shared = self.group is not None and learn
-        if shared and self.transport == "peer":
-            self._step_batch_peer()
-            return
-        if shared:
+        if shared and self.transport != "peer":
             gp = self.ctx.grad_packed()                  # G and the update counts: ONE all-reduce operand
         self.ctx.step(self.state, self.W, self.clf, self.enabled_mask, self.t, learn=learn, apply=not shared,
                       interrupt=learn and self.interrupt_learning)
-        if shared:
-            timing = self.allreduce_timing
-            sample = timing is not None and (self.t % timing["every"]) == 0
-            if sample:                                   # measurement hook (bench.py): events on the stream of use
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
+        if shared and self.transport == "peer":
+            # the step left the operand in this rank's peer region: ONE call publishes it, waits for every rank's and applies their sum
+            try:
+                with self._exchange_timed():
+                    self.ctx.peer_exchange_apply(self.W)
+            finally:
+                self.t += 1
+            return
+        if shared:                                       # (nested: an unshared step-batch pays one test here, not two)
             if self.ordered_sum:
                 if self._slots is None:
                     import torch.distributed as dist
                     self._slots = torch.zeros((dist.get_world_size(self.group), gp.numel()), dtype=torch.float32, device=gp.device)
-                _dist.allgather_packed(gp, self._slots, self.group)     # one all-gather; the sum is taken in rank order on every rank
-            else:
-                _dist.allreduce_packed(gp, self.group)      # RCCL over xGMI: one latency-bound 26 KB x n_vf message
-            if sample:
-                e1.record()
-                timing["events"].append((e0, e1))
-            if self.ordered_sum:
+                with self._exchange_timed():
+                    _dist.allgather_packed(gp, self._slots, self.group)     # one all-gather; the sum is taken in rank order on every rank
                 self.ctx.apply_update_slots(self.W, self._slots)
             else:
+                with self._exchange_timed():
+                    _dist.allreduce_packed(gp, self.group)      # RCCL over xGMI: one latency-bound 26 KB x n_vf message
                 self.ctx.apply_update_packed(self.W, gp)
         self.t += 1
 
-    def _step_batch_peer(self) -> None:
-        """A learning step-batch over the peer transport: the step leaves the operand in this rank's peer region, then ONE
-        exchange call publishes it, waits for every rank's and applies their rank-order sum (no collective, no host wait)."""
-        self.ctx.step(self.state, self.W, self.clf, self.enabled_mask, self.t, learn=True, apply=False,
-                      interrupt=self.interrupt_learning)
+    @contextlib.contextmanager
+    def _exchange_timed(self):
+        """Around a step-batch's exchange: time_allreduce()'s event pair on the stream of use, when it samples this step (bench.py)."""
         timing = self.allreduce_timing
-        sample = timing is not None and (self.t % timing["every"]) == 0
-        if sample:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        if timing is None or (self.t % timing["every"]) != 0:
+            yield
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
         try:
-            self.ctx.peer_exchange_apply(self.W)
+            yield
         finally:
-            if sample:
-                e1.record()
-                timing["events"].append((e0, e1))
-            self.t += 1
+            e1.record()
+            timing["events"].append((e0, e1))
 
     def time_allreduce(self, every: int = 0) -> Optional[dict]:
         """every > 0: bracket every `every`-th shared-weights all-reduce with an event pair on the current stream
@@ -402,7 +407,7 @@ class SkillChainingAgent:
              "enabled_mask": int(self.enabled_mask), "parents": torch.as_tensor(self.ctx.parents.copy()),
              "W": self.W.cpu(), "clf": self.clf.cpu(),
              "state": {f: getattr(self.state, f).cpu() for f in self._STATE_FIELDS}}
-        if getattr(self, "trace", None) is not None:
+        if self.trace is not None:
             ring_x, ring_y, events, ev_len = self.trace
             d["trace"] = {"ring_x": ring_x.cpu(), "ring_y": ring_y.cpu(), "events": events.cpu(), "ev_len": ev_len.cpu()}
             d["ex_cap"] = self._ex_cap
@@ -465,12 +470,7 @@ class SkillChainingAgent:
         start state (SPEC §10's BEGIN_AT), and n_episodes is the number of states.
         With `interrupt` a running option is cut short wherever the root's value at the next state is higher (SPEC §11's
         interrupting rollout); the summary then also holds interrupts per value function."""
-        ectx, st, stats, launches = self._eval_setup(n_episodes, epsilon, seed, steps_per_launch, states)
-        spl = int(steps_per_launch)
-        for i in range(launches):
-            ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
-                         begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None),
-                         interrupt=interrupt)
+        stats, _ = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt)
         out = stats.summary()
         return (out, stats.per_env()) if per_env else out
 
@@ -480,22 +480,13 @@ class SkillChainingAgent:
         of all envs that is appended to a Trajectory after the launch. Returns (Trajectory, the EpisodeStats summary, equal to
         evaluate()'s with the same arguments). Row 0 of each env is its begin row. The training run is left alone.
         `interrupt`: as for evaluate(); an interrupted step's row has term INTERRUPTED (SPEC §11)."""
-        from .trajectory import Trajectory
-        ectx, st, stats, launches = self._eval_setup(n_episodes, epsilon, seed, steps_per_launch, states)
-        spl = int(steps_per_launch)
-        traj = Trajectory(ectx.n_envs, spl + 1, 0, ectx.device, n_vf=self.n_vf)
-        for i in range(launches):
-            ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
-                         begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None),
-                         record=traj, interrupt=interrupt)
-            traj.append()
+        stats, traj = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record=True)
         return traj, stats.summary()
 
-    def _eval_setup(self, n_episodes, epsilon, seed, steps_per_launch, states):
-        """The evaluation context of evaluate() / record_episodes() for this episode count and seed, its hyper-parameters set
-        from training (epsilon aside), stats zeroed and, with `states`, the start states written into its env state. Returns
-        (context, EnvState, EpisodeStats, launches)."""
-        from .evaluation import EpisodeStats
+    def _eval_launches(self, n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record: bool = False):
+        """The launches of evaluate() / record_episodes() on the evaluation context for this episode count and seed, its settings
+        copied from training (epsilon aside), stats zeroed and, with `states`, the start states written into its env state: the
+        first begins every episode at t0 = 0, launch i > 0 goes on at t0 = 1 + i * steps_per_launch. Returns (EpisodeStats, Trajectory or None)."""
         if states is not None:
             states = self._start_states(states, 0, 0)
             n_episodes = states[0].numel()
@@ -508,7 +499,7 @@ class SkillChainingAgent:
         seed = int(c.seed) if seed is None else int(seed)
         # one evaluation context per n_episodes; the seed is a create-time setting, so another seed replaces that entry (a
         # caller sweeping seeds holds one context, not one per seed)
-        cache = self.__dict__.setdefault("_eval_ctx", {})
+        cache = self._eval_ctx
         if n not in cache or cache[n][0].cfg.seed != seed:
             if n in cache:
                 cache.pop(n)[0].close()
@@ -516,35 +507,28 @@ class SkillChainingAgent:
                               block_envs=self.ctx.block_envs)
             cache[n] = (ectx, EnvState(n, ectx.device, self.map), EpisodeStats(self.n_vf, n, ectx.device))
         ectx, st, stats = cache[n]
-        ectx.set_hparams(gamma=c.gamma, alpha=c.alpha, epsilon=float(epsilon), r_option_success=c.r_option_success,
-                         max_episode_steps=c.max_episode_steps, max_option_steps=c.max_option_steps,
-                         update_count_floor=c.update_count_floor, reoffer_period=c.reoffer_period)
-        ectx.set_option_parents([int(v) for v in self.ctx.parents])
-        ectx._call("scg_set_gestation", C.c_uint32(self.gest_mask), None)      # classifiers in use, no success counts kept
+        self._mirror_training(ectx, epsilon)
         stats.zero_()
         if states is not None:
             for dst, src in zip((st.x, st.y, st.vx, st.vy), states):
                 dst.copy_(src.to(dst.device))
-        return ectx, st, stats, -(-int(c.max_episode_steps) // spl)
+        traj = Trajectory(n, spl + 1, 0, ectx.device, n_vf=self.n_vf) if record else None
+        for i in range(-(-int(c.max_episode_steps) // spl)):
+            ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
+                         begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None),
+                         record=traj, interrupt=interrupt)
+            if record:
+                traj.append()
+        return stats, traj
+
+    def _mirror_training(self, side: ScgContext, epsilon: float) -> None:
+        """Copy the training run's settings into a side context (evaluation, trials): its hyper-parameters (epsilon aside),
+        parents and gestation mask — classifiers in use, no success counts kept; its own state, t and counters untouched."""
+        side.set_hparams(**dict({k: getattr(self.ctx.cfg, k) for k in ScgContext._HPARAMS}, epsilon=float(epsilon)))
+        side.set_option_parents([int(v) for v in self.ctx.parents])
+        side.set_gestation(self.gest_mask, counters=False)
 
     # ------------------------------------------------------------------ option trials (SPEC §9)
-    def _trial_context(self, seed: int, epsilon: float) -> ScgContext:
-        """The cached context trials run on (one, replaced when another seed is asked for): the training run's
-        hyper-parameters (epsilon aside), parents and gestation mask copied in; its own state, t and counters untouched."""
-        tc = self.__dict__.get("_trial_ctx")
-        if tc is None or tc.cfg.seed != seed:
-            if tc is not None:
-                tc.close()
-            tc = self._trial_ctx = ScgContext(1, self.n_options, self.map, device=self.ctx.device.index, seed=seed,
-                                              env_id_base=0, block_envs=self.ctx.block_envs)
-        c = self.ctx.cfg
-        tc.set_hparams(gamma=c.gamma, alpha=c.alpha, epsilon=float(epsilon), r_option_success=c.r_option_success,
-                       max_episode_steps=c.max_episode_steps, max_option_steps=c.max_option_steps,
-                       update_count_floor=c.update_count_floor, reoffer_period=c.reoffer_period)
-        tc.set_option_parents([int(v) for v in self.ctx.parents])
-        tc._call("scg_set_gestation", C.c_uint32(self.gest_mask), None)      # classifiers in use, no success counts kept
-        return tc
-
     def option_trials(self, option, x, y, vx=None, vy=None, epsilon: float = 0.0, seed: Optional[int] = None,
                       record: Optional[int] = None):
         """Run option `option` (an int, or one id per start state) from each start state (x, y, vx, vy; velocities default to
@@ -552,25 +536,31 @@ class SkillChainingAgent:
         TrialResult (outcome, steps, ret, disc_ret, v0, end state; summary() per option). Runs on a separate cached context
         at t0 = 0: W, state, t, the training context's env order, trace ring and counters are untouched. With `record` (rows
         per entry) every step is recorded (SPEC §10) into res.trajectory, a Trajectory over all entries."""
-        from .trials import TrialResult
         dev = self.W.device
-        f32 = lambda v: torch.as_tensor(v, dtype=torch.float32).to(dev).contiguous().view(-1)
-        x, y = f32(x), f32(y)
+        x, y = self._f32(x), self._f32(y)
         n = x.numel()
-        vx = torch.zeros(n, dtype=torch.float32, device=dev) if vx is None else f32(vx)
-        vy = torch.zeros(n, dtype=torch.float32, device=dev) if vy is None else f32(vy)
+        vx = torch.zeros(n, dtype=torch.float32, device=dev) if vx is None else self._f32(vx)
+        vy = torch.zeros(n, dtype=torch.float32, device=dev) if vy is None else self._f32(vy)
         opt = torch.full((n,), int(option), dtype=torch.int32, device=dev) if isinstance(option, int) \
             else torch.as_tensor(option, dtype=torch.int32).to(dev).contiguous().view(-1)
-        tc = self._trial_context(int(self.ctx.cfg.seed) if seed is None else int(seed), epsilon)
+        seed = int(self.ctx.cfg.seed) if seed is None else int(seed)
+        tc = self._trial_ctx                 # the one cached context trials run on, replaced when another seed is asked for
+        if tc is None or tc.cfg.seed != seed:
+            if tc is not None:
+                tc.close()
+            tc = self._trial_ctx = ScgContext(1, self.n_options, self.map, device=self.ctx.device.index, seed=seed,
+                                              env_id_base=0, block_envs=self.ctx.block_envs)
+        self._mirror_training(tc, epsilon)
         res = TrialResult(n, opt, dev)
-        traj = None
-        if record is not None:
-            from .trajectory import Trajectory
-            traj = Trajectory(n, int(record), 0, dev, n_vf=self.n_vf)
+        traj = None if record is None else Trajectory(n, int(record), 0, dev, n_vf=self.n_vf)
         tc.option_trials(x, y, vx, vy, res.option, self.W.view(-1), self.clf.view(-1), self.enabled_mask, 0, res, record=traj)
         if traj is not None:
             res.trajectory = traj.append()
         return res
+
+    def _f32(self, v) -> torch.Tensor:
+        """`v` as a flat, contiguous float32 tensor on the agent's device."""
+        return torch.as_tensor(v, dtype=torch.float32).to(self.W.device).contiguous().view(-1)
 
     def _start_states(self, states, n_states: int, seed: int):
         """(x, y, vx, vy) as float32 device tensors: from `states` ((x, y) or (x, y, vx, vy)), else n_states map.sample_free
@@ -578,8 +568,7 @@ class SkillChainingAgent:
         if states is None:
             pos = self.map.sample_free(int(n_states), np.random.default_rng(seed))
             states = (pos[:, 0], pos[:, 1])
-        dev = self.W.device
-        st = [torch.as_tensor(v, dtype=torch.float32).to(dev).contiguous().view(-1) for v in states]
+        st = [self._f32(v) for v in states]
         if len(st) not in (2, 4) or any(v.numel() != st[0].numel() for v in st):
             raise ValueError("states must be (x, y) or (x, y, vx, vy) of one length")
         if len(st) == 2:
@@ -592,7 +581,6 @@ class SkillChainingAgent:
         start classified by in_k(s0). Returns tp / fp / fn / tn (predicted in I_k x trial succeeded), precision, recall,
         success_in / success_out (success rate inside / outside the predicted set; NaN when empty), outcomes (count per
         outcome) and, per entry, trials (the TrialResult), predicted (uint8) and states (x, y, vx, vy)."""
-        from .trials import OUTCOMES
         if not (1 <= k <= self.n_options) or not ((self.enabled_mask | self.gest_mask) >> k) & 1:
             raise ValueError(f"option {k} is not enabled or gestating")
         xs, ys, vxs, vys = self._start_states(states, n_states, seed)
@@ -628,7 +616,7 @@ class SkillChainingAgent:
         xs, ys, vxs, vys = before["states"]
         lab = (before["trials"].outcome == _lib.TRIAL_SUCCESS).to(torch.uint8)
         xy = torch.stack((xs, ys), 1)
-        if k in getattr(self, "_ex", {}):
+        if k in self._ex:
             ex_xy, ex_lab = self.examples(k)
             xy, lab = torch.cat((ex_xy, xy)), torch.cat((ex_lab, lab))
         self.options[k].initiation_classifier.fit(xy.contiguous(), lab.contiguous(), iters=iters, lr=lr, l2=l2, warm_start=True)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (CLF_STRIDE, MAX_OPTIONS, NUM_ACTIONS, NUM_FEATURES, STEP_APPLY, STEP_INTERRUPT, STEP_LEARN, ScgConfig,
+from ._lib import (CLF_STRIDE, MAX_OPTIONS, NUM_ACTIONS, NUM_FEATURES, STEP_APPLY, STEP_INTERRUPT, STEP_LEARN, W_ROW, ScgConfig,
                    ScgError)
 from .maps import PinballMap
 
@@ -30,6 +30,18 @@ def fourier_scale_table(order: int = 5, n_vars: int = 4) -> np.ndarray:
 
 def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _chk_W(ctx, W: torch.Tensor, name: str = "W") -> torch.Tensor:      # (these three take the context: a stand-in's, too)
+    return ctx._chk(W, torch.float32, ctx.n_vf * W_ROW, name)
+
+
+def _chk_clf(ctx, clf: torch.Tensor) -> torch.Tensor:
+    return ctx._chk(clf, torch.float32, ctx.n_vf * CLF_STRIDE, "clf")
+
+
+def _chk_packed(ctx, gp: torch.Tensor, name: str, rows: int = 1) -> torch.Tensor:      # (a packed operand: G, then the counts)
+    return ctx._chk(gp, torch.float32, rows * ctx.n_vf * (W_ROW + 1), name)
 
 
 class ScgContext:
@@ -64,15 +76,20 @@ class ScgContext:
                              epsilon=epsilon, r_option_success=r_option_success,
                              max_episode_steps=max_episode_steps, max_option_steps=max_option_steps,
                              update_count_floor=update_count_floor, reoffer_period=reoffer_period)
+        # what later calls attach: the trace tensors, the announced trigger's (prev_in, count), the gradient operand in one of its two
+        # forms, SPEC §4.4's success counters; then step()'s cached call
+        self._trace = self._armed = self._gbuf = self._gpacked = self._gest_succ = None
+        self._step_args = self._step_keep = self._step_fn = self._last_state = None
+        self.gest_mask = self.peer_ranks = 0
         self._ctx = C.c_void_p()
-        _lib.check(self.lib.scg_create(C.byref(self._ctx), C.byref(self.cfg)), None, "scg_create")
+        _lib.check(self.lib.scg_create(C.byref(self._ctx), C.byref(self.cfg)), None, "scg_create", self.lib)
         self.scale = fourier_scale_table()
         self.parents = np.arange(-1, n_options, dtype=np.int32).clip(0)      # default chain k -> k-1
         self.set_map(pmap)
 
     # ------------------------------------------------------------------ plumbing
     def _call(self, name: str, *args) -> None:
-        _lib.check(getattr(self.lib, name)(self._ctx, *args), self._ctx, name)
+        _lib.check(getattr(self.lib, name)(self._ctx, *args), self._ctx, name, self.lib)
 
     def _stream(self) -> C.c_void_p:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -136,8 +153,7 @@ class ScgContext:
         self._chk(st.ep_steps, i32, N, "ep_steps"); self._chk(st.qcache, f32, NUM_ACTIONS * N, "qcache")
         self._chk(st.action, u8, N, "action"); self._chk(st.reward, f32, N, "reward")
         self._chk(st.done, u8, N, "done")
-        self._chk(W, f32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
-        self._chk(clf, f32, self.n_vf * CLF_STRIDE, "clf")
+        _chk_W(self, W); _chk_clf(self, clf)
 
     def step(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t: int,
              learn: bool = True, apply: bool = True, interrupt: bool = False) -> None:
@@ -157,7 +173,7 @@ class ScgContext:
         if cached is not None and cached[0] == key:
             flags = self._step_flags(learn, apply, interrupt)
             _lib.check(self._step_fn(self._ctx, *cached[1], C.c_uint32(enabled_mask), C.c_uint64(t), C.c_uint32(flags),
-                                     self._stream()), self._ctx, "scg_step")
+                                     self._stream()), self._ctx, "scg_step", self.lib)
             return
         self._chk_operands(st, W, clf)
         flags = self._step_flags(learn, apply, interrupt)
@@ -255,8 +271,7 @@ class ScgContext:
             raise ScgError("option_trials: need at least one start state")
         x, y, vx, vy = self._chk4((x, y, vx, vy), n, "state")
         self._chk(option, torch.int32, n, "option")
-        self._chk(W, torch.float32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
-        self._chk(clf, torch.float32, self.n_vf * CLF_STRIDE, "clf")
+        _chk_W(self, W); _chk_clf(self, clf)
         if out.n != n:
             raise ScgError(f"option_trials: out holds {out.n} entries, the call has {n}")
         self._chk(out.outcome, torch.uint8, n, "out.outcome"); self._chk(out.steps, torch.int32, n, "out.steps")
@@ -265,13 +280,13 @@ class ScgContext:
         if not (0 <= int(t0) < 2 ** 64):
             raise ScgError("option_trials: t0 must be a 64-bit unsigned step counter")
         cs = out.c_struct()
-        if record is not None:
+        head = (C.c_int32(n), _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(option), _ptr(W), _ptr(clf), C.c_uint32(enabled_mask),
+                C.c_uint64(int(t0)), C.byref(cs))
+        if record is None:
+            self._call("scg_option_trials", *head, self._stream())
+        else:
             rc = self._chk_record(record, n, 1, "option_trials")
-            self._call("scg_option_trials_record", C.c_int32(n), _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(option), _ptr(W),
-                       _ptr(clf), C.c_uint32(enabled_mask), C.c_uint64(int(t0)), C.byref(cs), C.byref(rc), self._stream())
-            return
-        self._call("scg_option_trials", C.c_int32(n), _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(option), _ptr(W), _ptr(clf),
-                   C.c_uint32(enabled_mask), C.c_uint64(int(t0)), C.byref(cs), self._stream())
+            self._call("scg_option_trials_record", *head, C.byref(rc), self._stream())
 
     def invalidate_order(self) -> None:
         """Tell the library that option ids were written outside scg_step (reset, restore): re-sort next step."""
@@ -309,7 +324,7 @@ class ScgContext:
 
     def harvest(self, sel_env: torch.Tensor, l_pos: int, l_neg: int):
         """Examples for the listed envs (int32, device) from the ring: (xy[n,L,2] f32, label[n,L] u8)."""
-        if getattr(self, "_trace", None) is None:
+        if self._trace is None:
             raise ScgError("harvest: trace buffers are not attached (set_trace_buffers)")
         ring_x, ring_y, _, ev_len = self._trace
         n = sel_env.numel()
@@ -334,7 +349,7 @@ class ScgContext:
         comes back to the host. With `rearm` the library keeps the RAW device pointers of prev_in and count and reads
         them inside every later scg_step until disarm_collect() / set_trace_buffers(): this object holds references to
         both tensors for exactly that long, so dropping yours cannot leave the step reading freed memory."""
-        if getattr(self, "_trace", None) is None:
+        if self._trace is None:
             raise ScgError("collect_examples: trace buffers are not attached (set_trace_buffers)")
         cap = ex_label.numel()
         self._chk(ex_xy, torch.float32, 2 * cap, "ex_xy"); self._chk(ex_label, torch.uint8, cap, "ex_label")
@@ -358,13 +373,13 @@ class ScgContext:
         of clf[n_vf, 8]) appends its most recent ring states to ex_xy[n_vf, cap, 2] / ex_label[n_vf, cap] behind count[p]
         (device int32[n_vf], in/out). Two small launches; stateless (no prev_in, an announced collect_examples trigger is
         left alone); nothing comes back to the host."""
-        if getattr(self, "_trace", None) is None:
+        if self._trace is None:
             raise ScgError("collect_frontier: trace buffers are not attached (set_trace_buffers)")
         cap = ex_label.numel() // self.n_vf
         if cap < 1 or ex_label.numel() != self.n_vf * cap:
             raise ScgError(f"collect_frontier: ex_label must hold n_vf = {self.n_vf} buffers of cap >= 1 examples")
         self._chk(ex_xy, torch.float32, 2 * self.n_vf * cap, "ex_xy"); self._chk(ex_label, torch.uint8, self.n_vf * cap, "ex_label")
-        self._chk(count, torch.int32, self.n_vf, "count"); self._chk(clf, torch.float32, self.n_vf * CLF_STRIDE, "clf")
+        self._chk(count, torch.int32, self.n_vf, "count"); _chk_clf(self, clf)
         nodes = (1 << self.n_vf) - 1
         if l_pos < 0 or l_neg < 0 or l_pos + l_neg < 1 or not (0 <= target_mask <= nodes) or not (0 <= cover_mask <= nodes) \
                 or cover_mask & 1 or target_mask & ~cover_mask & ~1:
@@ -376,54 +391,51 @@ class ScgContext:
         self._call("scg_arm_collect", C.c_uint32(0), None, 0, 0, None)
         self._armed = None
 
-    def set_gestation(self, gest_mask: int) -> torch.Tensor:
-        """SPEC §4.4: options in gestation (known, never selected, learning off-policy). Returns the device int32[n_vf]
-        success counters the fused step adds to (kept across calls; zero an entry when its option starts gestating)."""
-        if not hasattr(self, "_gest_succ"):
+    def set_gestation(self, gest_mask: int, counters: bool = True) -> Optional[torch.Tensor]:
+        """SPEC §4.4: options in gestation (known, never selected, learning off-policy). Returns the device int32[n_vf] success
+        counters the fused step adds to (kept across calls; zero an entry when its option starts gestating); with counters=False
+        the classifiers are in use but no counts are kept (a context that only acts) and None is returned."""
+        if counters and self._gest_succ is None:
             self._gest_succ = torch.zeros(self.n_vf, dtype=torch.int32, device=self.device)
-        self._call("scg_set_gestation", C.c_uint32(gest_mask), _ptr(self._gest_succ))
+        succ = self._gest_succ if counters else None
+        self._call("scg_set_gestation", C.c_uint32(gest_mask), _ptr(succ))
         self.gest_mask = gest_mask
-        return self._gest_succ
+        return succ
 
     def grad_buffers(self):
         """(G[n_vf,5,1296] float32, n_k[n_vf] int32): caller-owned torch tensors that scg_step(LEARN)
         fills with the rank-local gradient sum and update counts (the all-reduce operands, SPEC §5)."""
-        if not hasattr(self, "_gbuf"):
+        if self._gbuf is None:
             G = torch.zeros((self.n_vf, NUM_ACTIONS, NUM_FEATURES), dtype=torch.float32, device=self.device)
             n = torch.zeros((self.n_vf,), dtype=torch.int32, device=self.device)
             self._call("scg_set_grad_buffers", _ptr(G), _ptr(n))
-            self._gbuf = (G, n)
-            self.__dict__.pop("_gpacked", None)
+            self._gbuf, self._gpacked = (G, n), None
         return self._gbuf
 
     def grad_packed(self) -> torch.Tensor:
         """One flat float32 tensor [n_vf*5*1296 + n_vf]: G followed by the update counts as floats — the single
         all-reduce operand of a sharded run with shared weights (scg_set_grad_buffer_packed)."""
-        if not hasattr(self, "_gpacked"):
-            gp = torch.zeros(self.n_vf * NUM_ACTIONS * NUM_FEATURES + self.n_vf, dtype=torch.float32, device=self.device)
+        if self._gpacked is None:
+            gp = torch.zeros(self.n_vf * (W_ROW + 1), dtype=torch.float32, device=self.device)
             self._call("scg_set_grad_buffer_packed", _ptr(gp))
-            self._gpacked = gp
-            self.__dict__.pop("_gbuf", None)
+            self._gpacked, self._gbuf = gp, None
         return self._gpacked
 
     def apply_update_packed(self, W: torch.Tensor, gp: torch.Tensor) -> None:
-        self._chk(W, torch.float32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
-        self._chk(gp, torch.float32, self.n_vf * NUM_ACTIONS * NUM_FEATURES + self.n_vf, "G_packed")
+        _chk_W(self, W); _chk_packed(self, gp, "G_packed")
         self._call("scg_apply_update_packed", _ptr(W), _ptr(gp), self._stream())
 
     def apply_update_slots(self, W: torch.Tensor, slots: torch.Tensor) -> None:
         """The order-pinned multi-rank update (SPEC §5): `slots` [n_ranks, n_vf*5*1296 + n_vf] holds every rank's packed operand
         (an all-gather of grad_packed()); G and the counts are summed in slot order: the weights are identical on every rank of a run and reproducible by the oracle for any number of ranks (the rank count, like the block size and the seed, is part of the run's identity)."""
-        per = self.n_vf * NUM_ACTIONS * NUM_FEATURES + self.n_vf
+        per = self.n_vf * (W_ROW + 1)
         if slots.dim() != 2 or slots.shape[1] != per or not slots.is_contiguous():
             raise ScgError(f"slots must be a contiguous [n_ranks, {per}] tensor")
-        self._chk(W, torch.float32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
-        self._chk(slots, torch.float32, slots.shape[0] * per, "slots")
+        _chk_W(self, W); _chk_packed(self, slots, "slots", slots.shape[0])
         self._call("scg_apply_update_slots", _ptr(W), _ptr(slots), C.c_int32(slots.shape[0]), C.c_int64(per), self._stream())
 
     def apply_update(self, W: torch.Tensor, G: torch.Tensor, n_k: torch.Tensor) -> None:
-        self._chk(W, torch.float32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
-        self._chk(G, torch.float32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "G")
+        _chk_W(self, W); _chk_W(self, G, "G")
         self._chk(n_k, torch.int32, self.n_vf, "n_k")
         self._call("scg_apply_update", _ptr(W), _ptr(G), _ptr(n_k), self._stream())
 
@@ -468,7 +480,7 @@ class ScgContext:
         xn, yn, vxn, vyn = self._chk4(sn, n, "s_next")
         self._chk(action, torch.uint8, n, "action"); self._chk(r, torch.float32, n, "r")
         self._chk(cont, torch.float32, n, "cont")
-        self._chk(W, torch.float32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
+        _chk_W(self, W)
         if n and int(action.max()) >= NUM_ACTIONS:
             raise ScgError("action out of range [0, 5)")
         self._call("scg_q_update", n, k, _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(action), _ptr(r), _ptr(cont),
@@ -534,7 +546,7 @@ class ScgContext:
     def peer_exchange_apply(self, W: torch.Tensor) -> None:
         """After a learning step: publish this rank's operand, wait for every rank's, apply their rank-order sum to W
         (all on the device, on the current stream)."""
-        self._chk(W, torch.float32, self.n_vf * NUM_ACTIONS * NUM_FEATURES, "W")
+        _chk_W(self, W)
         self._call("scg_peer_exchange_apply", _ptr(W), self._stream())
 
     def set_peer_timeout(self, seconds: float) -> None:

@@ -379,3 +379,38 @@ def test_announced_trigger_gives_the_same_examples_in_one_launch():
     assert na == nb and na > 100
     for ta, tb in zip(a._ex_buffers(2), b._ex_buffers(2)):
         assert torch.equal(ta, tb)
+
+
+@pytest.mark.gpu
+def test_discovery_makes_its_library_calls_in_order():
+    """What chain_skills and grow_skill_tree call on the training context, in order, against the sequence their own reports
+    imply: per created option its collection step-batches (the step, then the collector behind it), the tree's parent
+    assignment, the fit (disarm, fit, status, the training-accuracy predict) and the start-coverage predicts — one for the
+    chain (option k alone), one per known option for the tree (their union); an option that fell short leaves only its
+    collection steps. scg_step and scg_invalidate_order are the step's cache behaviour and are left out. The goal disc covers
+    0.8 % of the empty map: about eight of the 1024 envs start inside it, so each loop creates at least one option."""
+    from gpu_util import spy_calls
+    from skill_chaining_with_graphs_amd import SkillChainingAgent
+    n_opt, steps_per_option = 2, 48
+    fit = ["scg_arm_collect", "scg_fit_initiation", "scg_async_status", "scg_classifier_predict"]
+
+    def discover(grow):
+        agent = SkillChainingAgent("pinball_empty", 1024, n_opt, seed=5, epsilon=1.0, alpha=1e-4, max_episode_steps=400)
+        agent.enable_tracing(64)
+        agent.domain.reset_random(seed=11, v_max=0.5)
+        with spy_calls(agent.ctx) as (calls, _):
+            report = (agent.grow_skill_tree if grow else agent.chain_skills)(
+                steps_per_option=steps_per_option, poll_every=8, l_pos=8, l_neg=8, min_examples=1, gestation=0, start_coverage=2.0)
+        return report, [c for c in calls if c not in ("scg_step", "scg_invalidate_order")]
+
+    for grow, collect in ((False, ["step", "scg_collect_examples", "scg_arm_collect"]), (True, ["step", "scg_collect_frontier"])):
+        report, calls = discover(grow)
+        assert len(report) >= 1, (grow, report)                 # a loop that created nothing would pin nothing
+        assert [r["option"] for r in report] == list(range(1, len(report) + 1))
+        want = []
+        for known, r in enumerate(report, 1):
+            want += collect * r["steps"] + (["scg_set_option_parents"] if grow else []) + fit
+            want += ["scg_classifier_predict"] * (known if grow else 1)
+        if len(report) < n_opt:                                 # the next option fell short of min_examples: collection only
+            want += collect * steps_per_option
+        assert calls == want, (grow, report)
