@@ -13,14 +13,8 @@ Prints one JSON line. Kernel times without the event overhead: run it under rocp
 """
 import argparse
 import json
-import os
-import sys
 
-import numpy as np
-import torch
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from skill_chaining_with_graphs_amd import SkillChainingAgent  # noqa: E402
+import rig  # noqa: F401  (puts the repository root on sys.path)
 
 
 def main():
@@ -30,6 +24,9 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--map", default="pinball_simple")
     a = ap.parse_args()
+    import numpy as np
+    import torch
+    from skill_chaining_with_graphs_amd import SkillChainingAgent
     ag = SkillChainingAgent(a.map, a.envs, 5, seed=1)
     ag.enable_tracing(64)
     for k, (cx, cy) in enumerate([(0.2, 0.2), (0.5, 0.5), (0.2, 0.8), (0.8, 0.8), (0.5, 0.15)], start=1):

@@ -7,58 +7,47 @@ Interruption is only guaranteed not to hurt with exact values; these are linear 
 
     python tools/interrupt_report.py [--maps pinball_simple pinball_maze] [--seeds 1 2 3] [--envs 8192] [--options 5]
 """
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
-from skill_chaining_with_graphs_amd import SkillChainingAgent  # noqa: E402
-
-ap = argparse.ArgumentParser()
-ap.add_argument("--maps", nargs="+", default=["pinball_simple", "pinball_maze"])
-ap.add_argument("--envs", type=int, default=8192); ap.add_argument("--options", type=int, default=5)
-ap.add_argument("--seeds", type=int, nargs="+", default=[1, 2, 3])
-ap.add_argument("--warm", type=int, default=3000); ap.add_argument("--after", type=int, default=1000)
-ap.add_argument("--episodes", type=int, default=4096, help="episodes of each evaluate()")
-ap.add_argument("--out-dir", default=None, help="also write one report per map: <dir>/r08_interrupt_report_<map>.txt")
-a = ap.parse_args()
-HP = dict(alpha=0.02, epsilon=0.05, gamma=0.99, max_episode_steps=2000, max_option_steps=200, r_option_success=0.0,
-          update_count_floor=a.envs // 16, reoffer_period=4)
+import argparse, os
+import rig
 
 
-def fmt(r):
-    line = (f"success {r['success_rate']:.4f} return {r['mean_return']:9.2f} length {r['mean_length']:7.1f} "
-            f"share {[round(v, 3) for v in r['steps_share']]} entries {r['entries']} declines {r['declines']}")
-    if "interrupts" in r:
-        line += f" interrupts {r['interrupts']}"
-    return line
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--maps", nargs="+", default=["pinball_simple", "pinball_maze"])
+    ap.add_argument("--envs", type=int, default=8192); ap.add_argument("--options", type=int, default=5)
+    ap.add_argument("--seeds", type=int, nargs="+", default=[1, 2, 3])
+    ap.add_argument("--warm", type=int, default=3000); ap.add_argument("--after", type=int, default=1000)
+    ap.add_argument("--episodes", type=int, default=4096, help="episodes of each evaluate()")
+    ap.add_argument("--out-dir", default=None, help="also write one report per map: <dir>/r08_interrupt_report_<map>.txt")
+    a = ap.parse_args()
+    from skill_chaining_with_graphs_amd import SkillChainingAgent
+    HP = rig.discovery_hp(a.envs)
+
+    for mp in a.maps:
+        lines = [f"# interrupt_report map {mp} envs {a.envs} options {a.options} warm {a.warm} after {a.after} "
+                 f"episodes {a.episodes} hparams {HP}"]
+        print(lines[0], flush=True)
+        for seed in a.seeds:
+            ag = SkillChainingAgent(mp, a.envs, a.options, seed=seed, **HP)
+            ag.enable_tracing(64)
+            ag.rollout(a.warm)
+            created = ag.chain_skills(steps_per_option=400, min_examples=3000, max_examples=40000, start_coverage=0.9)
+            ag.rollout(a.after)
+            plain = ag.evaluate(n_episodes=a.episodes)
+            intr = ag.evaluate(n_episodes=a.episodes, interrupt=True)
+            out = [f"seed {seed}: {len(created)} options, enabled mask {ag.enabled_mask:#x}",
+                   f"  plain       {rig.fmt_eval(plain)}",
+                   f"  interrupt   {rig.fmt_eval(intr)}",
+                   "  delta       " + rig.delta_eval(plain, intr)]
+            for ln in out:
+                print(ln, flush=True)
+            lines += out
+            del ag
+        if a.out_dir:
+            os.makedirs(a.out_dir, exist_ok=True)
+            with open(os.path.join(a.out_dir, f"r08_interrupt_report_{mp}.txt"), "w") as fh:
+                fh.write("\n".join(lines) + "\n")
 
 
-for mp in a.maps:
-    lines = [f"# interrupt_report map {mp} envs {a.envs} options {a.options} warm {a.warm} after {a.after} "
-             f"episodes {a.episodes} hparams {HP}"]
-    print(lines[0], flush=True)
-    for seed in a.seeds:
-        ag = SkillChainingAgent(mp, a.envs, a.options, seed=seed, **HP)
-        ag.enable_tracing(64)
-        ag.rollout(a.warm)
-        created = ag.chain_skills(steps_per_option=400, min_examples=3000, max_examples=40000, start_coverage=0.9)
-        ag.rollout(a.after)
-        plain = ag.evaluate(n_episodes=a.episodes)
-        intr = ag.evaluate(n_episodes=a.episodes, interrupt=True)
-        out = [f"seed {seed}: {len(created)} options, enabled mask {ag.enabled_mask:#x}",
-               f"  plain       {fmt(plain)}",
-               f"  interrupt   {fmt(intr)}",
-               "  delta       " + json.dumps({"success": round(intr["success_rate"] - plain["success_rate"], 4),
-                                             "return": round(intr["mean_return"] - plain["mean_return"], 2),
-                                             "length": round(intr["mean_length"] - plain["mean_length"], 1)})]
-        for ln in out:
-            print(ln, flush=True)
-        lines += out
-        del ag
-    if a.out_dir:
-        os.makedirs(a.out_dir, exist_ok=True)
-        with open(os.path.join(a.out_dir, f"r08_interrupt_report_{mp}.txt"), "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+if __name__ == "__main__":
+    main()

@@ -12,57 +12,23 @@ rollouts (SPEC §11, scg_rollout_interrupt) on a state of their own, timed in th
 import argparse
 import json
 import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import skill_chaining_with_graphs_amd as scg  # noqa: E402
-from skill_chaining_with_graphs_amd.core import EnvState, ScgContext  # noqa: E402
-from skill_chaining_with_graphs_amd.trajectory import Trajectory  # noqa: E402
-
-
-def chain_classifiers(m, n_options):
-    """Option k's initiation set: a disc round the goal of radius 0.18 + 0.17 (k - 1) (each holds the one before)."""
-    clf = np.zeros((n_options + 1, 8), np.float32)
-    tx, ty, _ = m.target
-    for k in range(1, n_options + 1):
-        uc, vc, r = 2 * tx - 1, 2 * ty - 1, 2 * (0.18 + 0.17 * (k - 1))
-        clf[k, :6] = [r * r - uc * uc - vc * vc, 2 * uc, 2 * vc, -1.0, 0.0, -1.0]
-    return clf
-
-
-def _state(ctx, m, n, seed=1):
-    rng = np.random.default_rng(seed)
-    st = EnvState(n, ctx.device, m)
-    pos = m.sample_free(n, rng, margin=2.0)
-    v = rng.uniform(-1.0, 1.0, (n, 2)).astype(np.float32)
-    for t, a in zip((st.x, st.y, st.vx, st.vy), (pos[:, 0], pos[:, 1], v[:, 0], v[:, 1])):
-        t.copy_(torch.as_tensor(np.ascontiguousarray(a, np.float32), device=ctx.device))
-    return st
-
-
-def _time(fn, reps):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / reps
+import rig
 
 
 def bench(n, k, rounds, n_opt=5, epw=None, record=(), interrupt=False):
+    import numpy as np
+    import torch
+    import skill_chaining_with_graphs_amd as scg
+    from skill_chaining_with_graphs_amd.core import ScgContext
+    from skill_chaining_with_graphs_amd.trajectory import Trajectory
     m = scg.load_map("pinball_simple")
     ctx = ScgContext(n, n_opt, m, device=0, seed=7, epsilon=0.05, max_episode_steps=2000)
     mask = ((1 << (n_opt + 1)) - 1) & ~1
-    clf = torch.as_tensor(chain_classifiers(m, n_opt), device=ctx.device).view(-1)
+    clf = torch.as_tensor(rig.chain_classifiers(m, n_opt), device=ctx.device).view(-1)
     g = torch.Generator().manual_seed(3)
     W = (torch.randn((n_opt + 1) * 5 * 1296, generator=g) * 1e-3).to(ctx.device)
-    st_r, st_s = _state(ctx, m, n), _state(ctx, m, n)
+    st_r, st_s = rig.state_on(ctx, m, n), rig.state_on(ctx, m, n)
     t = {"r": 0, "s": 0}
 
     def roll():
@@ -82,13 +48,13 @@ def bench(n, k, rounds, n_opt=5, epw=None, record=(), interrupt=False):
     recs = []                                             # (label, its own state and step counter, the record)
     for spec in record:
         nr = n if spec == "all" else min(int(spec), n)
-        recs.append((spec, {"st": _state(ctx, m, n), "t": 0}, Trajectory(nr, k, 0, ctx.device)))
+        recs.append((spec, {"st": rig.state_on(ctx, m, n), "t": 0}, Trajectory(nr, k, 0, ctx.device)))
 
     def roll_rec(r):
         ctx.rollout(r[1]["st"], W, clf, mask, r[1]["t"], k, record=r[2])
         r[1]["t"] += k
 
-    ist = {"st": _state(ctx, m, n), "t": 0, "intr": torch.zeros((n_opt + 1) * n, dtype=torch.int32, device=ctx.device)}
+    ist = {"st": rig.state_on(ctx, m, n), "t": 0, "intr": torch.zeros((n_opt + 1) * n, dtype=torch.int32, device=ctx.device)}
 
     def roll_int():
         ctx.rollout(ist["st"], W, clf, mask, ist["t"], k, interrupt=True, interrupts=ist["intr"])
@@ -101,12 +67,12 @@ def bench(n, k, rounds, n_opt=5, epw=None, record=(), interrupt=False):
         roll_int(); roll_int()
     r_us, s_us, rec_us, int_us = [], [], {r[0]: [] for r in recs}, []
     for _ in range(rounds):
-        r_us.append(_time(roll, 3) * 1e6 / k)
-        s_us.append(_time(loop, 3) * 1e6 / k)
+        r_us.append(rig.timed(roll, 3) * 1e6 / k)
+        s_us.append(rig.timed(loop, 3) * 1e6 / k)
         for r in recs:
-            rec_us[r[0]].append(_time(lambda: roll_rec(r), 3) * 1e6 / k)
+            rec_us[r[0]].append(rig.timed(lambda: roll_rec(r), 3) * 1e6 / k)
         if interrupt:
-            int_us.append(_time(roll_int, 3) * 1e6 / k)
+            int_us.append(rig.timed(roll_int, 3) * 1e6 / k)
     r, s = float(np.median(r_us)), float(np.median(s_us))
     out = {"n_envs": n, "k": k, "epw": epw or "auto", "options": n_opt, "rollout_us_per_step": round(r, 2), "step_loop_us_per_step": round(s, 2),
            "speedup": round(s / r, 2), "rollout_rounds_us": [round(v, 2) for v in r_us],

@@ -7,74 +7,61 @@ first), the step share and option entries.
 
     python tools/skill_tree_report.py [--maps pinball_simple pinball_maze] [--seeds 1 2] [--envs 8192] [--options 5]
 """
-import argparse
-import json
-import os
-import sys
-import time
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
-from skill_chaining_with_graphs_amd import SkillChainingAgent  # noqa: E402
-
-ap = argparse.ArgumentParser()
-ap.add_argument("--maps", nargs="+", default=["pinball_simple", "pinball_maze"])
-ap.add_argument("--envs", type=int, default=8192); ap.add_argument("--options", type=int, default=5)
-ap.add_argument("--seeds", type=int, nargs="+", default=[1, 2])
-ap.add_argument("--warm", type=int, default=3000); ap.add_argument("--after", type=int, default=1000)
-ap.add_argument("--steps-per-option", type=int, default=400)
-ap.add_argument("--episodes", type=int, default=4096, help="episodes of each evaluate()")
-ap.add_argument("--out-dir", default=None, help="also write one report per map: <dir>/r10_skill_tree_<map>.txt")
-a = ap.parse_args()
-HP = dict(alpha=0.02, epsilon=0.05, gamma=0.99, max_episode_steps=2000, max_option_steps=200, r_option_success=0.0,
-          update_count_floor=a.envs // 16, reoffer_period=4)
-TOTAL = a.warm + a.options * a.steps_per_option + a.after        # step-batches of every learner
-DISCOVERY = dict(steps_per_option=a.steps_per_option, min_examples=3000, max_examples=40000, start_coverage=0.9)
+import argparse, os, time
+import rig
 
 
-def fmt(r):
-    return (f"success {r['success_rate']:.4f} return {r['mean_return']:9.2f} length {r['mean_length']:7.1f} "
-            f"share {[round(v, 3) for v in r['steps_share']]} entries {r['entries']}")
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--maps", nargs="+", default=["pinball_simple", "pinball_maze"])
+    ap.add_argument("--envs", type=int, default=8192); ap.add_argument("--options", type=int, default=5)
+    ap.add_argument("--seeds", type=int, nargs="+", default=[1, 2])
+    ap.add_argument("--warm", type=int, default=3000); ap.add_argument("--after", type=int, default=1000)
+    ap.add_argument("--steps-per-option", type=int, default=400)
+    ap.add_argument("--episodes", type=int, default=4096, help="episodes of each evaluate()")
+    ap.add_argument("--out-dir", default=None, help="also write one report per map: <dir>/r10_skill_tree_<map>.txt")
+    a = ap.parse_args()
+    from skill_chaining_with_graphs_amd import SkillChainingAgent
+    HP = rig.discovery_hp(a.envs)
+    TOTAL = a.warm + a.options * a.steps_per_option + a.after        # step-batches of every learner
+    DISCOVERY = dict(steps_per_option=a.steps_per_option, min_examples=3000, max_examples=40000, start_coverage=0.9)
 
-
-def delta(x, y):
-    return json.dumps({"success": round(y["success_rate"] - x["success_rate"], 4),
-                       "return": round(y["mean_return"] - x["mean_return"], 2),
-                       "length": round(y["mean_length"] - x["mean_length"], 1)})
-
-
-for mp in a.maps:
-    lines = [f"# skill_tree_report map {mp} envs {a.envs} options {a.options} warm {a.warm} step-batches per learner {TOTAL} "
-             f"episodes {a.episodes} discovery {DISCOVERY} hparams {HP}"]
-    print(lines[0], flush=True)
-    for seed in a.seeds:
-        res = {}
-        for learner in ("chain", "tree"):
-            t0 = time.time()
-            ag = SkillChainingAgent(mp, a.envs, a.options, seed=seed, **HP)
-            ag.enable_tracing(64)
-            ag.rollout(a.warm)
-            grow = ag.chain_skills if learner == "chain" else ag.grow_skill_tree
-            created = grow(**DISCOVERY)
-            found_t = ag.t
-            ag.rollout(TOTAL - ag.t)
-            assert ag.t == TOTAL
-            res[learner] = ag.evaluate(n_episodes=a.episodes)
-            made = [(r["option"], r["parent"], r["examples"]) for r in created]
-            out = [f"seed {seed} {learner}: {len(created)} options (option, parent, examples) {made}, enabled mask "
-                   f"{ag.enabled_mask:#x}, parents {[int(p) for p in ag.ctx.parents]}, discovery done by step-batch {found_t}, "
-                   f"{TOTAL} step-batches in {time.time() - t0:.0f} s"]
-            if learner == "tree":
-                out.append(f"  node examples at each decision {[r['node_examples'] for r in created]}")
-            out.append(f"  acting {fmt(res[learner])}")
-            for ln in out:
-                print(ln, flush=True)
+    for mp in a.maps:
+        lines = [f"# skill_tree_report map {mp} envs {a.envs} options {a.options} warm {a.warm} step-batches per learner {TOTAL} "
+                 f"episodes {a.episodes} discovery {DISCOVERY} hparams {HP}"]
+        print(lines[0], flush=True)
+        for seed in a.seeds:
+            res = {}
+            for learner in ("chain", "tree"):
+                t0 = time.time()
+                ag = SkillChainingAgent(mp, a.envs, a.options, seed=seed, **HP)
+                ag.enable_tracing(64)
+                ag.rollout(a.warm)
+                grow = ag.chain_skills if learner == "chain" else ag.grow_skill_tree
+                created = grow(**DISCOVERY)
+                found_t = ag.t
+                ag.rollout(TOTAL - ag.t)
+                assert ag.t == TOTAL
+                res[learner] = ag.evaluate(n_episodes=a.episodes)
+                made = [(r["option"], r["parent"], r["examples"]) for r in created]
+                out = [f"seed {seed} {learner}: {len(created)} options (option, parent, examples) {made}, enabled mask "
+                       f"{ag.enabled_mask:#x}, parents {[int(p) for p in ag.ctx.parents]}, discovery done by step-batch {found_t}, "
+                       f"{TOTAL} step-batches in {time.time() - t0:.0f} s"]
+                if learner == "tree":
+                    out.append(f"  node examples at each decision {[r['node_examples'] for r in created]}")
+                out.append(f"  acting {rig.fmt_eval(res[learner], declines=False)}")
+                for ln in out:
+                    print(ln, flush=True)
+                lines += out
+                del ag
+            out = [f"seed {seed} tree - chain: {rig.delta_eval(res['chain'], res['tree'])}"]
+            print(out[0], flush=True)
             lines += out
-            del ag
-        out = [f"seed {seed} tree - chain: {delta(res['chain'], res['tree'])}"]
-        print(out[0], flush=True)
-        lines += out
-    if a.out_dir:
-        os.makedirs(a.out_dir, exist_ok=True)
-        with open(os.path.join(a.out_dir, f"r10_skill_tree_{mp}.txt"), "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+        if a.out_dir:
+            os.makedirs(a.out_dir, exist_ok=True)
+            with open(os.path.join(a.out_dir, f"r10_skill_tree_{mp}.txt"), "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

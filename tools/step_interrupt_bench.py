@@ -8,49 +8,34 @@ medians over the rounds and, per side, the share of envs running an option at th
 """
 import argparse
 import json
-import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import skill_chaining_with_graphs_amd as scg  # noqa: E402
-from skill_chaining_with_graphs_amd.core import ScgContext  # noqa: E402
-from rollout_bench import _state, chain_classifiers  # noqa: E402
+import rig
 
 
 def bench(n, k, rounds, n_opt=5):
+    import numpy as np
+    import torch
+    import skill_chaining_with_graphs_amd as scg
+    from skill_chaining_with_graphs_amd.core import ScgContext
     m = scg.load_map("pinball_simple")
     ctx = ScgContext(n, n_opt, m, device=0, seed=7, epsilon=0.05, max_episode_steps=2000)
     mask = ((1 << (n_opt + 1)) - 1) & ~1
-    clf = torch.as_tensor(chain_classifiers(m, n_opt), device=ctx.device).view(-1)
+    clf = torch.as_tensor(rig.chain_classifiers(m, n_opt), device=ctx.device).view(-1)
     g = torch.Generator().manual_seed(3)
     W0 = (torch.randn((n_opt + 1) * 5 * 1296, generator=g) * 1e-3).to(ctx.device)
-    sides = {name: {"st": _state(ctx, m, n), "W": W0.clone(), "t": 0, "int": name == "interrupt"} for name in ("plain", "interrupt")}
+    sides = {name: {"st": rig.state_on(ctx, m, n), "W": W0.clone(), "t": 0, "int": name == "interrupt"} for name in ("plain", "interrupt")}
 
     def run(s):
         for _ in range(k):
             ctx.step(s["st"], s["W"], clf, mask, s["t"], learn=True, apply=True, interrupt=s["int"])
             s["t"] += 1
 
-    def timed(s):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        run(s)
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e6 / k
-
     for s in sides.values():                              # warm-up (first launches, allocator, code objects)
         run(s); run(s)
     us = {name: [] for name in sides}
     for _ in range(rounds):
         for name, s in sides.items():
-            us[name].append(timed(s))
+            us[name].append(rig.timed(lambda: run(s), 1) * 1e6 / k)
     out = {"n_envs": n, "k": k, "options": n_opt}
     for name in sides:
         out[f"{name}_us_per_step"] = round(float(np.median(us[name])), 2)

@@ -11,37 +11,22 @@ With --record ROWS the trials are also timed with every step recorded (SPEC §10
 """
 import argparse
 import json
-import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import skill_chaining_with_graphs_amd as scg  # noqa: E402
-from skill_chaining_with_graphs_amd.core import EnvState, ScgContext  # noqa: E402
-from skill_chaining_with_graphs_amd.trajectory import Trajectory  # noqa: E402
-from skill_chaining_with_graphs_amd.trials import TrialResult  # noqa: E402
-from rollout_bench import chain_classifiers  # noqa: E402
-
-
-def _time(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return time.perf_counter() - t0
+import rig
 
 
 def bench(n, rounds, max_opt, n_opt=5, rows=0):
+    import numpy as np
+    import torch
+    import skill_chaining_with_graphs_amd as scg
+    from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
+    from skill_chaining_with_graphs_amd.trajectory import Trajectory
+    from skill_chaining_with_graphs_amd.trials import TrialResult
+    _time = lambda fn: rig.timed(fn, 1)
     m = scg.load_map("pinball_simple")
     ctx = ScgContext(n, n_opt, m, device=0, seed=7, epsilon=0.05, max_episode_steps=2000, max_option_steps=max_opt)
     mask = ((1 << (n_opt + 1)) - 1) & ~1
-    clf = torch.as_tensor(chain_classifiers(m, n_opt), device=ctx.device).view(-1)
+    clf = torch.as_tensor(rig.chain_classifiers(m, n_opt), device=ctx.device).view(-1)
     g = torch.Generator().manual_seed(3)
     W = (torch.randn((n_opt + 1) * 5 * 1296, generator=g) * 1e-3).to(ctx.device)
     rng = np.random.default_rng(1)
