@@ -229,6 +229,27 @@ int scg_rollout_interrupt(scg_ctx *ctx, float *x, float *y, float *vx, float *vy
                           uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, const scg_record *rec,
                           void *stream);
 
+/* ---- rollouts with a selection rule (SPEC §14): which of several candidate options an env is offered ----
+ * scg_rollout_select is scg_rollout_interrupt plus `rules` and `overrides`. rules = 0 is scg_rollout_record and rules =
+ * SCG_SELECT_INTERRUPT is scg_rollout_interrupt (the same kernels, the same results). With SCG_SELECT_BEST an env that is offered an
+ * option is offered the candidate of the highest value instead of the lowest-numbered one: with C = {k : enabled, s_next in k's
+ * initiation set and outside its target region} and V_k = max_a Q_k(s_next, a) (this launch's W, §5's max order), c* = the k in C
+ * with the largest V_k (ties: the lowest k; a NaN never wins; all NaN: min C), and §4.2's gate is applied to c*: option_id = c* if
+ * V_c* >= V_0, else -c* with qcache = Q_0. An env that stayed out of any member of C (option_id = -k, k in C) is offered again only on
+ * §4.2's re-offer schedule and keeps its option_id in between. Where C has at most one member every output equals rules without
+ * BEST, bit for bit. Together with SCG_SELECT_INTERRUPT, §11 is unchanged (an interrupted step writes -min C).
+ * `overrides` (DEVICE [n_vf][N] int32, in/out, may be NULL): overrides[c*][e] += 1 when env e enters c* != min C; never written
+ * without SCG_SELECT_BEST. `interrupts` is written with SCG_SELECT_INTERRUPT only. Flags, `rec`, the write set and the errors are
+ * scg_rollout_record's; SCG_ERR_INVALID also for an unknown bit in `rules` (nothing is launched). Results do not depend on the
+ * launch geometry or the block build; the kernel talks to no other workgroup, so it raises no asynchronous failure bit. */
+#define SCG_SELECT_INTERRUPT 1u   /* SPEC §11 */
+#define SCG_SELECT_BEST      2u   /* SPEC §14 */
+int scg_rollout_select(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                       int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                       const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                       uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                       const scg_record *rec, uint32_t rules, void *stream);
+
 /* Device pointers of the ctx-owned reduced gradient G[n_vf][5][1296] and counts n_k[n_vf] (int32)
  * left by the last scg_step(LEARN) — the buffers a multi-rank caller all-reduces (SPEC §5). */
 int scg_grad_buffers(scg_ctx *ctx, float **G, int32_t **n_k);

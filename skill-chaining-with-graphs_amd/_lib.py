@@ -29,6 +29,8 @@ TRIAL_LEFT_INITIATION = 3
 TRIAL_TIMEOUT = 4
 TRIAL_MAX_STEPS = ROLLOUT_MAX_STEPS
 ROLLOUT_TERM_INTERRUPTED = 5   # include/scg_abi.h SCG_ROLLOUT_TERM_INTERRUPTED: a recorded row's term where an option was interrupted
+SELECT_INTERRUPT = 1       # include/scg_abi.h SCG_SELECT_*: the rules of scg_rollout_select (SPEC §11, §14)
+SELECT_BEST = 2
 ABI_VERSION = 5            # include/scg_abi.h SCG_ABI_VERSION
 ASYNC_FIT_TIMEOUT = 0x1
 ASYNC_STEP_HANDOFF = 0x2
@@ -131,6 +133,7 @@ _SIGS = {
     "scg_rollout_record": (C.c_int, _ROLLOUT + [C.POINTER(Record), _P]),
     "scg_option_trials_record": (C.c_int, _TRIALS + [C.POINTER(Record), _P]),
     "scg_rollout_interrupt": (C.c_int, _ROLLOUT + [_P, C.POINTER(Record), _P]),
+    "scg_rollout_select": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, _P]),
     "scg_grad_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "scg_set_grad_buffers": (C.c_int, [_P, _P, _P]),
     "scg_apply_update": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -456,7 +456,7 @@ class SkillChainingAgent:
         self.ctx.q_update(k, s, action, r, cont, s_next, self.W, apply=apply)
 
     def evaluate(self, n_episodes: int = 4096, epsilon: float = 0.0, seed: Optional[int] = None, steps_per_launch: int = 64,
-                 per_env: bool = False, states=None, interrupt: bool = False):
+                 per_env: bool = False, states=None, interrupt: bool = False, choose: Optional[str] = None):
         """How good the current policy is: one episode per env on `n_episodes` envs of a separate evaluation context (cached per
         n_episodes; another seed replaces the entry), acting with `epsilon` and the current W, clf and enabled options, weights
         frozen (SPEC §8). Returns
@@ -469,24 +469,29 @@ class SkillChainingAgent:
         With `states` ((x, y) or (x, y, vx, vy); velocities default to zero) episode i starts from state i instead of a drawn
         start state (SPEC §10's BEGIN_AT), and n_episodes is the number of states.
         With `interrupt` a running option is cut short wherever the root's value at the next state is higher (SPEC §11's
-        interrupting rollout); the summary then also holds interrupts per value function."""
-        stats, _ = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt)
+        interrupting rollout); the summary then also holds interrupts per value function.
+        With `choose="value"` an env is offered the candidate option whose value at the next state is highest instead of the
+        lowest-numbered one (SPEC §14; ValueError for any other value); the summary then also holds overrides per option: the
+        entries of an option that was not the lowest-numbered candidate. It combines with `interrupt`."""
+        stats, _ = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt, choose=choose)
         out = stats.summary()
         return (out, stats.per_env()) if per_env else out
 
     def record_episodes(self, n_episodes: int = 256, states=None, epsilon: float = 0.0, seed: Optional[int] = None,
-                        steps_per_launch: int = 64, interrupt: bool = False):
+                        steps_per_launch: int = 64, interrupt: bool = False, choose: Optional[str] = None):
         """evaluate() with every step recorded (SPEC §10): the same launches on the same evaluation context, each with a record
         of all envs that is appended to a Trajectory after the launch. Returns (Trajectory, the EpisodeStats summary, equal to
         evaluate()'s with the same arguments). Row 0 of each env is its begin row. The training run is left alone.
-        `interrupt`: as for evaluate(); an interrupted step's row has term INTERRUPTED (SPEC §11)."""
-        stats, traj = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record=True)
+        `interrupt`: as for evaluate(); an interrupted step's row has term INTERRUPTED (SPEC §11). `choose`: as for evaluate()."""
+        stats, traj = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record=True, choose=choose)
         return traj, stats.summary()
 
-    def _eval_launches(self, n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record: bool = False):
+    def _eval_launches(self, n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record: bool = False, choose=None):
         """The launches of evaluate() / record_episodes() on the evaluation context for this episode count and seed, its settings
         copied from training (epsilon aside), stats zeroed and, with `states`, the start states written into its env state: the
         first begins every episode at t0 = 0, launch i > 0 goes on at t0 = 1 + i * steps_per_launch. Returns (EpisodeStats, Trajectory or None)."""
+        if choose not in (None, "value"):
+            raise ValueError(f"choose must be None or 'value', not {choose!r}")
         if states is not None:
             states = self._start_states(states, 0, 0)
             n_episodes = states[0].numel()
@@ -516,7 +521,7 @@ class SkillChainingAgent:
         for i in range(-(-int(c.max_episode_steps) // spl)):
             ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
                          begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None),
-                         record=traj, interrupt=interrupt)
+                         record=traj, interrupt=interrupt, choose=choose)
             if record:
                 traj.append()
         return stats, traj

@@ -203,7 +203,7 @@ class ScgContext:
 
     def rollout(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, n_steps: int,
                 stats=None, begin: bool = False, one_episode: bool = False, record=None, begin_at: bool = False,
-                interrupt: bool = False, interrupts=None) -> None:
+                interrupt: bool = False, interrupts=None, choose: Optional[str] = None, overrides=None) -> None:
         """SPEC §8: n_steps acting steps in ONE launch, bit for bit n_steps calls of step(learn=False) at t0 .. t0+n_steps-1
         (with `begin`: a new episode for every env at t0 first, the steps at t0+1 .. t0+n_steps). W is read, never written.
         `stats` (EpisodeStats of this context's n_vf and n_envs, on its device) receives the episode counters; `one_episode`
@@ -212,7 +212,12 @@ class ScgContext:
         state in `st` (x, y, vx, vy as given) instead of a drawn start. Neither changes any other output.
         SPEC §11: `interrupt` cuts a running option short wherever max_a Q_0(s', .) exceeds max_a Q_o(s', .) (scg_rollout_interrupt);
         `interrupts` ([n_vf][n_envs] int32, in/out) counts the interrupted steps per option, by default into `stats.interrupts`
-        (which then shows in stats.summary())."""
+        (which then shows in stats.summary()).
+        SPEC §14: `choose="value"` offers an env the candidate option of the highest value instead of the lowest-numbered one
+        (scg_rollout_select, the only path that goes through it); `overrides` ([n_vf][n_envs] int32, in/out) counts the entries
+        of an option that was not the lowest-numbered candidate, by default into `stats.overrides` (created on demand)."""
+        if choose not in (None, "value"):
+            raise ValueError(f"rollout: choose must be None or 'value', not {choose!r}")
         self._chk_operands(st, W, clf)
         N = self.n_envs
         n_steps, t0 = int(n_steps), int(t0)
@@ -244,13 +249,26 @@ class ScgContext:
                 interrupts = stats.interrupts
             if interrupts is not None:
                 self._chk(interrupts, torch.int32, self.n_vf * N, "interrupts")
+        if overrides is not None and choose is None:
+            raise ScgError("rollout: overrides without choose='value'")
+        if choose is not None:
+            if overrides is None and stats is not None:
+                overrides = stats.want_overrides()
+            if overrides is not None:
+                self._chk(overrides, torch.int32, self.n_vf * N, "overrides")
         rc = None if record is None else self._chk_record(record, N, n_steps + (1 if begin or begin_at else 0), "rollout")
         # the arguments every entry point starts with; each appends its own tail
         head = (_ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id), _ptr(st.opt_steps), _ptr(st.ep_steps),
                 _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done), _ptr(W), _ptr(clf), C.c_uint32(enabled_mask),
                 C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags), None if cs is None else C.byref(cs))
         rc_ref = None if rc is None else C.byref(rc)
-        if interrupt:
+        if choose is not None:
+            rules = _lib.SELECT_BEST | (_lib.SELECT_INTERRUPT if interrupt else 0)
+            self._call("scg_rollout_select", *head, None if interrupts is None else _ptr(interrupts),
+                       None if overrides is None else _ptr(overrides), rc_ref, C.c_uint32(rules), self._stream())
+            if stats is not None and interrupt and interrupts is stats.interrupts:
+                stats.interrupting = True
+        elif interrupt:
             self._call("scg_rollout_interrupt", *head, None if interrupts is None else _ptr(interrupts), rc_ref, self._stream())
             if stats is not None and interrupts is stats.interrupts:
                 stats.interrupting = True

@@ -432,6 +432,17 @@ __device__ __forceinline__ bool option_keep(uint32_t parents, int o, unsigned in
     const bool otime = osteps + 1 >= max_opt;
     return !((dn != 0) || succ || fail || otime);
 }
+// SPEC §14's candidate set C as a mask: bit k = option k is enabled, s_next lies in its initiation set and outside its target
+// region (select_option's `sel`, restated: that function is left as it compiles today; min C is its result)
+__device__ __forceinline__ unsigned candidate_mask(uint32_t parents, unsigned inB, unsigned enabled) {
+    unsigned tgtB = 0;
+#pragma unroll
+    for (int k = 1; k < MAX_VF; ++k) {
+        const unsigned p = target_of(parents, k);
+        if (p != 0 && ((inB >> p) & 1u)) tgtB |= 1u << k;
+    }
+    return inB & ~tgtB & enabled & ((1u << MAX_VF) - 2u);
+}
 // selection: the smallest enabled option k with s_next in its initiation set and outside its target region (0: none)
 __device__ __forceinline__ int select_option(uint32_t parents, unsigned inB, unsigned enabled) {
     unsigned tgtB = 0;                                     // bit k: s_next already lies in option k's target region

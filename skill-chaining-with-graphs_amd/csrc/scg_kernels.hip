@@ -19,6 +19,7 @@
 //                            leaves its row untouched and raises the ctx's asynchronous status word
 // scg_record_kernels.hip is the second translation unit: rollout_kernel<true> / trial_kernel<true> (SPEC §10's per-step record) and
 // rollout_kernel on RolloutIntArgs / RolloutIntRecArgs (SPEC §11's interrupting rollout, without and with the record).
+// scg_select_kernels.hip is the third: rollout_kernel on RolloutBestArgs / RolloutBestIntArgs (SPEC §14's value-ranked choice).
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -52,6 +53,9 @@ __attribute__((visibility("hidden"))) hipError_t launch_trial_record(const Trial
 // the interrupting instantiations (SPEC §11), in the same translation unit
 __attribute__((visibility("hidden"))) hipError_t launch_rollout_interrupt(const RolloutIntArgs &A, int grid, hipStream_t s);
 __attribute__((visibility("hidden"))) hipError_t launch_rollout_interrupt_record(const RolloutIntRecArgs &A, int grid, hipStream_t s);
+// the value-ranking instantiations (SPEC §14), compiled and launched in scg_select_kernels.hip
+__attribute__((visibility("hidden"))) hipError_t launch_rollout_best(const RolloutBestArgs &A, int grid, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_rollout_best_interrupt(const RolloutBestIntArgs &A, int grid, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -661,12 +665,13 @@ static Derived derived_args(const Base &base, Set set) {
 }
 
 // scg_rollout, and scg_rollout_record (`fn` names the caller in error texts) with `rec` or `at` (BEGIN_AT, passed as BEGIN in
-// `flags`): the recording instantiation; scg_rollout_interrupt (`intr`): the interrupting ones, counting into `interrupts`
+// `flags`): the recording instantiation; scg_rollout_interrupt (`intr`): the interrupting ones, counting into `interrupts`;
+// scg_rollout_select with SCG_SELECT_BEST (`best`): the value-ranking ones (SPEC §14), counting into `overrides`
 static int rollout_launch(const char *fn, scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
                           int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
                           const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
                           uint32_t flags, const scg_rollout_stats *stats, const scg_record *rec, bool at, void *stream,
-                          bool intr = false, int32_t *interrupts = nullptr) {
+                          bool intr = false, int32_t *interrupts = nullptr, bool best = false, int32_t *overrides = nullptr) {
     if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
     if (!c->have_map) return fail_in(c, SCG_ERR_STATE, fn, "scg_set_map has not been called");
     if (!x || !y || !vx || !vy || !option_id || !opt_steps || !ep_steps || !qcache || !action || !reward ||
@@ -699,7 +704,11 @@ static int rollout_launch(const char *fn, scg_ctx *c, float *x, float *y, float 
     R.epw = epw;
     const int grid = (c->cfg.n_envs + RO_WAVES * epw - 1) / (RO_WAVES * epw);
     c->order_valid = false;                               // the ids change under the step's prepared env order
-    if (intr && (rec || at)) {
+    if (best) {
+        const auto fill = [&](auto &D) { if (rec) D.rec = *rec; D.begin_at = at ? 1u : 0u; D.interrupts = interrupts; D.overrides = overrides; };
+        if (intr) SCG_HIP(c, launch_rollout_best_interrupt(derived_args<RolloutBestIntArgs>(R, fill), grid, reinterpret_cast<hipStream_t>(stream)));
+        else SCG_HIP(c, launch_rollout_best(derived_args<RolloutBestArgs>(R, fill), grid, reinterpret_cast<hipStream_t>(stream)));
+    } else if (intr && (rec || at)) {
         const auto RR = derived_args<RolloutIntRecArgs>(R, [&](auto &D) { if (rec) D.rec = *rec; D.begin_at = at ? 1u : 0u; D.interrupts = interrupts; });
         SCG_HIP(c, launch_rollout_interrupt_record(RR, grid, reinterpret_cast<hipStream_t>(stream)));
     } else if (intr) {
@@ -751,6 +760,23 @@ int scg_rollout_interrupt(scg_ctx *c, float *x, float *y, float *vx, float *vy, 
     if (const int rc = begin_at_flags(c, "scg_rollout_interrupt", flags, at)) return rc;
     return rollout_launch("scg_rollout_interrupt", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done,
                           W, clf, enabled_mask, t0, n_steps, flags, stats, rec, at, stream, true, interrupts);
+}
+
+// rules = 0: scg_rollout_record; SCG_SELECT_INTERRUPT alone: scg_rollout_interrupt (both on the kernels those launch). `overrides` is
+// passed on with SCG_SELECT_BEST only
+int scg_rollout_select(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                       int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                       const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                       uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                       const scg_record *rec, uint32_t rules, void *stream) {
+    if (c && (rules & ~(SCG_SELECT_INTERRUPT | SCG_SELECT_BEST)))
+        return fail_in(c, SCG_ERR_INVALID, "scg_rollout_select", "unknown rule");
+    const bool intr = (rules & SCG_SELECT_INTERRUPT) != 0, best = (rules & SCG_SELECT_BEST) != 0;
+    bool at;
+    if (const int rc = begin_at_flags(c, "scg_rollout_select", flags, at)) return rc;
+    return rollout_launch("scg_rollout_select", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done,
+                          W, clf, enabled_mask, t0, n_steps, flags, stats, rec, at, stream, intr, intr ? interrupts : nullptr,
+                          best, best ? overrides : nullptr);
 }
 
 static int trials_launch(const char *fn, scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,

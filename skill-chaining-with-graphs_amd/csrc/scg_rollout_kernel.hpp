@@ -38,6 +38,7 @@ struct RolloutArgs {
     uint32_t reoffer_mask;
     MapScalars ms;
     static constexpr bool INT = false;   // SPEC §11's interruption: a compile-time flag of the argument type (kernel symbols unchanged)
+    static constexpr bool BEST = false;  // SPEC §14's value-ranked choice: likewise
 };
 // the recording instantiation's arguments (SPEC §10): RolloutArgs at offset 0, so the exit's re-read holds for both
 struct RolloutRecArgs : RolloutArgs {
@@ -52,6 +53,18 @@ struct RolloutIntArgs : RolloutArgs {
 struct RolloutIntRecArgs : RolloutRecArgs {
     static constexpr bool INT = true;
     int32_t *interrupts;
+};
+// the value-ranking instantiations' arguments (SPEC §14; scg_rollout_select), without and with the interruption, always with the record
+struct RolloutBestArgs : RolloutRecArgs {
+    static constexpr bool BEST = true;
+    int32_t *interrupts;           // (not counted without INT)
+    int32_t *overrides;            // [n_vf][N] in/out, may be null
+};
+struct RolloutBestIntArgs : RolloutRecArgs {
+    static constexpr bool INT = true;
+    static constexpr bool BEST = true;
+    int32_t *interrupts;
+    int32_t *overrides;
 };
 
 // per-VF counters of one launch, six 16-bit fields in three words (a launch takes at most 1 + SCG_ROLLOUT_MAX_STEPS steps)
@@ -73,15 +86,19 @@ static_assert(SCG_ROLLOUT_MAX_STEPS + 1 < 65536, "16-bit launch counters");
 
 // <false, RolloutArgs>: scg_rollout's kernel. <true, RolloutRecArgs>: the same steps, plus SPEC §10's rows of the envs in the
 // record's window, and BEGIN_AT (scg_rollout_record). <false, RolloutIntArgs> / <true, RolloutIntRecArgs>: the same with
-// SPEC §11's interruption (scg_rollout_interrupt); INT = Args::INT
+// SPEC §11's interruption (scg_rollout_interrupt); INT = Args::INT. <true, RolloutBestArgs> / <true, RolloutBestIntArgs>: SPEC §14's
+// value-ranked choice (scg_rollout_select), BEST = Args::BEST: an offered env is evaluated under every candidate's value function
+// and the root's, the Q of VF k in slot k of s_qv (root: slot 0), and phase G enters the candidate whose value is highest
 template <bool REC, typename Args>
 __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
-    constexpr bool INT = Args::INT;
+    constexpr bool INT = Args::INT, BEST = Args::BEST;
+    constexpr int QV_SLOTS = BEST ? MAX_VF : 2;               // BEST: one slot per value function
+    constexpr int QV_ROOT = BEST ? 0 : 1;                     // the slot of the root's Q beside the running VF's
     __shared__ __attribute__((aligned(16))) float s_w0[W_FLOATS];                 // W_0 in A-operand order (stage_w_cold's layout)
     __shared__ __attribute__((aligned(16))) float s_edges[MAX_EDGES * 8];
     __shared__ __attribute__((aligned(16))) float s_wave[RO_WAVES][RO_WAVE_FLOATS];
     __shared__ __attribute__((aligned(16))) float2 s_z1[RO_MAX_ENVS][4];          // Z_d^1 of each env's s_next
-    __shared__ float s_qv[2][NACT][RO_MAX_ENVS];                                   // [0]: the VF the env runs next; [1]: the root (entering)
+    __shared__ float s_qv[QV_SLOTS][NACT][RO_MAX_ENVS];                            // [0]: the VF the env runs next; [1]: the root (entering). BEST: [k]: VF k
     __shared__ uint16_t s_list[MAX_VF][RO_MAX_ENVS];                               // env index | slot << 8
     __shared__ int s_cnt[2][MAX_VF];                                               // list lengths, by step parity
     __shared__ float s_clf[MAX_VF * CLF_STRIDE];
@@ -101,6 +118,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
     bool finished = false;
     Ctr16 c_vf = {{0u, 0u, 0u}}, c_en = {{0u, 0u, 0u}}, c_de = {{0u, 0u, 0u}}, c_su = {{0u, 0u, 0u}};
     Ctr16 c_in = {{0u, 0u, 0u}};                               // INT: interrupted steps per option
+    Ctr16 c_ov = {{0u, 0u, 0u}};                               // BEST: entries of an option that is not min C
     if (mine) {
         sx = A.x[e]; sy = A.y[e]; svx = A.vx[e]; svy = A.vy[e];
 #pragma unroll
@@ -162,6 +180,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         bool keep = false, succ = false;
         int cand = 0, on = 0, stay = 0, term = 0;
         int ic = 0;                                            // INT: §4.2's cand of a keeping env, as if its option had ended
+        unsigned cset = 0;                                     // BEST: the candidate set C of an env that is not keeping
         if (valid) {
             dn = is_begin ? 2 : episode_end(goal, eps1, A.max_ep);
             if (dn && !(REC && is_begin && kernel_args<RolloutRecArgs>()->begin_at)) restart_state(u[2], A.starts, A.ms.n_starts, nx, ny, nvx, nvy);
@@ -173,13 +192,29 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
                      : !((inA >> o) & 1u) ? (int)SCG_TRIAL_LEFT_INITIATION : (int)SCG_TRIAL_TIMEOUT;
             cand = keep ? o : select_option(A.parents, inB, A.enabled);
             if constexpr (INT) ic = keep ? select_option(A.parents, inB, A.enabled) : 0;
-            stay = reoffer_stay(keep, cand, dn, is_begin ? 0 : oid, t, gid, A.reoffer_mask);
+            if constexpr (BEST) {                              // SPEC §14: stay out of ANY member of C; cand = that member
+                cset = keep ? 0u : candidate_mask(A.parents, inB, A.enabled);
+                const int o_in = is_begin ? 0 : oid;
+                const bool out_of = o_in < 0 && o_in > -MAX_VF && ((cset >> (unsigned)(-o_in & 7)) & 1u);
+                stay = (!keep && out_of && dn == 0 && (((uint32_t)t + (uint32_t)gid) & A.reoffer_mask) != 0u) ? -o_in : 0;
+                if (stay) cand = stay;
+            } else {
+                stay = reoffer_stay(keep, cand, dn, is_begin ? 0 : oid, t, gid, A.reoffer_mask);
+            }
             on = stay ? 0 : cand;
             store_z1(s_z1[il], nx, ny, nvx, nvy);
         }
         const bool entering = valid && !keep && on >= 1;
         // compaction: slot 0 -> the list of VF `on`, slot 1 (entering; INT: keeping too) -> the root's list. An env is entering
         // or keeping, never both, and either way runs on >= 1 next: the root's list still holds at most one item per env
+        if constexpr (BEST) {
+            // slot = VF index. An offered env goes to the list of every k in C and to the root's; a keeping env to its option's
+            // (INT: and the root's); any other to the root's. Every list still holds at most one item per env
+            const unsigned want = !valid ? 0u : entering ? (cset | 1u) : keep ? ((1u << o) | (INT ? 1u : 0u)) : 1u;
+#pragma unroll
+            for (int k = 0; k < MAX_VF; ++k)
+                list_append(&s_cnt[par][k], s_list[k], (want >> k) & 1u, (uint16_t)(il | (k << 8)), lane);
+        } else
 #pragma unroll
         for (int k = 0; k < MAX_VF; ++k) {
             const bool w0 = valid && on == k, w1 = (entering || (INT && keep)) && k == 0;
@@ -236,13 +271,34 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         // ------------------------------------------------------------ G
         if (valid) {
             float qa[NACT];
+            int minc = cand;                                   // BEST: min C of an offered env
+            if constexpr (BEST) {
+                if (entering) {                                // SPEC §14: c* = the candidate of the highest value, ties to the lowest k
+                    float vbest = 0.0f;
+                    int cs = 0;
 #pragma unroll
-            for (int aa = 0; aa < NACT; ++aa) qa[aa] = s_qv[0][aa][il];
+                    for (int k = 1; k < MAX_VF; ++k) {
+                        if ((cset >> k) & 1u) {
+                            float v = s_qv[k][0][il];
+#pragma unroll
+                            for (int aa = 1; aa < NACT; ++aa) v = fmaxf(v, s_qv[k][aa][il]);      // gate_holds' order
+                            if (v == v && (cs == 0 || v > vbest)) { vbest = v; cs = k; }          // a NaN never wins
+                        }
+                    }
+                    cand = cs ? cs : minc;                     // every value a NaN: min C (the gate then declines it)
+                }
+                const int slot = entering ? cand : on;         // keeping: on = o; staying, no candidate: 0
+#pragma unroll
+                for (int aa = 0; aa < NACT; ++aa) qa[aa] = s_qv[slot][aa][il];
+            } else {
+#pragma unroll
+                for (int aa = 0; aa < NACT; ++aa) qa[aa] = s_qv[0][aa][il];
+            }
             bool declined = false;
             if (entering) {
                 float q0[NACT];
 #pragma unroll
-                for (int aa = 0; aa < NACT; ++aa) q0[aa] = s_qv[1][aa][il];
+                for (int aa = 0; aa < NACT; ++aa) q0[aa] = s_qv[QV_ROOT][aa][il];
                 declined = !gate_holds(qa, q0);
                 if (declined) {
 #pragma unroll
@@ -254,7 +310,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
                 if (keep) {
                     float q0[NACT];
 #pragma unroll
-                    for (int aa = 0; aa < NACT; ++aa) q0[aa] = s_qv[1][aa][il];
+                    for (int aa = 0; aa < NACT; ++aa) q0[aa] = s_qv[QV_ROOT][aa][il];
                     interrupted = !gate_holds(qa, q0);         // V_o against V_0 at s_next: ties keep the option
                     if (interrupted) {
 #pragma unroll
@@ -275,6 +331,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
             eps = dn ? 0 : eps1;
             c_en.add(cand, entering && !declined);
             c_de.add(cand, declined);
+            if constexpr (BEST) c_ov.add(cand, entering && !declined && cand != minc);
             if (!is_begin) {
                 last_a = a; last_r = rew; last_dn = dn;
                 c_vf.add(o, true);
@@ -341,5 +398,10 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         int32_t *const I = kernel_args<Args>()->interrupts;
         if (I)
             for (int k = 0; k < K->n_vf; ++k) I[(size_t)k * N + e] += c_in.get(k);
+    }
+    if constexpr (BEST) {
+        int32_t *const O = kernel_args<Args>()->overrides;
+        if (O)
+            for (int k = 0; k < K->n_vf; ++k) O[(size_t)k * N + e] += c_ov.get(k);
     }
 }

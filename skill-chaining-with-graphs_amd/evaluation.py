@@ -14,7 +14,8 @@ class EpisodeStats:
     """Counter tensors of SPEC §8 for `n` envs and `n_vf` value functions (root + options), zeroed. They are in/out:
     several rollout launches add up into one evaluation; `zero_()` starts a new one. `interrupts` ([n_vf][n], SPEC §11) is kept
     apart from FIELDS (the scg_rollout_stats members): an interrupting rollout counts into it and sets `interrupting`, which
-    adds it to per_env() and summary()."""
+    adds it to per_env() and summary(). `overrides` ([n_vf][n], SPEC §14) exists only once a value-ranking rollout asked for it
+    (want_overrides()), and then shows in both as well."""
 
     FIELDS = ("ep_return", "ret_sum", "episodes", "goals", "len_sum", "vf_steps", "entries", "declines", "successes",
               "finished")
@@ -31,6 +32,14 @@ class EpisodeStats:
         self.finished = z(n, torch.uint8)
         self.interrupts = z((n_vf, n), torch.int32)
         self.interrupting = False
+        self.overrides = None          # [n_vf][n] int32 (SPEC §14), created by want_overrides(): a value-ranking rollout asks
+
+    def want_overrides(self) -> torch.Tensor:
+        """The `overrides` counters of a value-ranking rollout (SPEC §14), created zeroed on first use; from then on they show in
+        per_env() and summary(), until zero_()."""
+        if self.overrides is None:
+            self.overrides = torch.zeros((self.n_vf, self.n), dtype=torch.int32, device=self.device)
+        return self.overrides
 
     @property
     def device(self) -> torch.device:
@@ -41,6 +50,7 @@ class EpisodeStats:
             getattr(self, f).zero_()
         self.interrupts.zero_()
         self.interrupting = False
+        self.overrides = None
         return self
 
     def c_struct(self) -> RolloutStats:
@@ -51,12 +61,15 @@ class EpisodeStats:
         out = {f: getattr(self, f) for f in self.FIELDS}
         if self.interrupting:
             out["interrupts"] = self.interrupts
+        if self.overrides is not None:
+            out["overrides"] = self.overrides
         return out
 
     def summary(self) -> dict:
         """Aggregate over the envs on the host in float64, in env order: episodes, success_rate, mean_return, mean_length
         (NaN with no episode recorded) and per value function k (index 0 = the root): steps_share (fraction of all steps
-        run under k), entries, declines, successes; after an interrupting rollout also interrupts (SPEC §11)."""
+        run under k), entries, declines, successes; after an interrupting rollout also interrupts (SPEC §11), after a
+        value-ranking one also overrides (SPEC §14: entries of an option that was not the lowest-numbered candidate)."""
         host = {f: getattr(self, f).detach().cpu().numpy() for f in self.FIELDS}
         eps = int(host["episodes"].astype(np.int64).sum())
         goals = int(host["goals"].astype(np.int64).sum())
@@ -78,4 +91,6 @@ class EpisodeStats:
         }
         if self.interrupting:
             out["interrupts"] = [int(v) for v in self.interrupts.detach().cpu().numpy().astype(np.int64).sum(axis=1)]
+        if self.overrides is not None:
+            out["overrides"] = [int(v) for v in self.overrides.detach().cpu().numpy().astype(np.int64).sum(axis=1)]
         return out

@@ -1,0 +1,494 @@
+"""SPEC §14 value-ranked option choice on the GPU (scg_rollout_select): rules = 0 and rules = INTERRUPT forward to scg_rollout_record
+and scg_rollout_interrupt; on chains, and with every value tied, BEST changes nothing; on the sibling layout one BEST launch (and
+one BEST | INTERRUPT launch) equals an emulator built from already-verified entry points and the same emulator on the oracle;
+every launch geometry and block build agree; NaN weights, a missing or gestating sibling and out-of-range ids; the C-ABI's
+refusals; and the agent's evaluate(choose="value") / record_episodes(choose="value") leave training alone."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import choice_model as cm
+import interrupt_learning_model as ilm
+import sc_oracle
+import skill_chaining_with_graphs_amd as scg
+from skill_chaining_with_graphs_amd import _lib
+from skill_chaining_with_graphs_amd.core import EnvState
+from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
+from skill_chaining_with_graphs_amd.trajectory import Trajectory
+from gpu_util import (as_bytes, assert_same_bits, block_envs, clone_state, crossing_agent, current_block_envs, dev,  # noqa: F401
+                      host_state, make_context, spy_calls, state_to_device)                                          # (block_envs: the fixture)
+from util import HP, SCALE, random_env_state, random_states
+
+pytestmark = pytest.mark.gpu
+
+STATS = EpisodeStats.FIELDS
+N, K, T0, N_OPT, MASK = 300, 12, 40, 5, 0b111110
+N_VF = N_OPT + 1
+MAPS = ["pinball_simple", "pinball_empty"]
+INT, BEST = _lib.SELECT_INTERRUPT, _lib.SELECT_BEST
+B, ONE, AT = _lib.ROLLOUT_BEGIN, _lib.ROLLOUT_ONE_EPISODE, _lib.ROLLOUT_BEGIN_AT
+REOFFER = 4
+
+
+def _layout(m, layout):
+    if layout == "sibling":
+        return cm.sibling_tree(m)
+    return None, ilm.wide_chain(m, N_OPT)                      # default parents: the chain k -> k-1, nested sets, |C| <= 1
+
+
+def _setup(name, n=N, layout="sibling", gest=0, seed=3, block=None, **hp):
+    m = scg.load_map(name)
+    parents, clf = _layout(m, layout)
+    ctx = make_context(m, n, N_OPT, block, parents, gest, seed, reoffer_period=REOFFER, **hp)
+    return ctx, m, dev(ilm.crossing_weights(N_VF, seed)).view(-1), dev(clf).view(-1)
+
+
+def _host_state(m, n, seed, id_lo=-N_OPT, id_hi=N_OPT):
+    return random_env_state(m, n, N_OPT, seed, id_lo=id_lo, id_hi=id_hi, opt_steps_hi=10, max_episode_steps=HP["max_episode_steps"])
+
+
+class Out:
+    """What one launch can write besides the env state: stats, the record, and the two rule counters (prefilled with `fill`)."""
+
+    def __init__(self, ctx, rows, fill=0):
+        n = ctx.n_envs
+        self.stats = EpisodeStats(ctx.n_vf, n, ctx.device)
+        self.rec = Trajectory(n, rows, 0, ctx.device)
+        self.interrupts = torch.full((ctx.n_vf, n), fill, dtype=torch.int32, device=ctx.device)
+        self.overrides = torch.full((ctx.n_vf, n), fill, dtype=torch.int32, device=ctx.device)
+
+    def record(self):
+        ln = self.rec.len.cpu().numpy()
+        return {f: getattr(self.rec, f).cpu().numpy() for f in self.rec.fields}, ln
+
+
+def _args(ctx, st, W, clf, mask, t0, n_steps, flags, stats):
+    return [C.c_void_p(getattr(st, f).data_ptr()) for f in EnvState.FIELDS] + [
+        C.c_void_p(W.data_ptr()), C.c_void_p(clf.data_ptr()), C.c_uint32(mask), C.c_uint64(t0), C.c_int32(n_steps),
+        C.c_uint32(flags), None if stats is None else C.byref(stats)]
+
+
+def _select(ctx, st, W, clf, t0, n_steps, flags, rules, out, mask=MASK, rec=True):
+    """scg_rollout_select as the C-ABI has it (ScgContext.rollout reaches it with BEST only)."""
+    cs, rc = out.stats.c_struct(), out.rec.c_struct()
+    ctx._call("scg_rollout_select", *_args(ctx, st, W, clf, mask, t0, n_steps, flags, cs), C.c_void_p(out.interrupts.data_ptr()),
+              C.c_void_p(out.overrides.data_ptr()), C.byref(rc) if rec else None, C.c_uint32(rules), ctx._stream())
+
+
+def _same_record(a, b, msg):
+    (ra, la), (rb, lb) = a.record(), b.record()
+    assert np.array_equal(la, lb), f"{msg}: len"
+    valid = np.arange(a.rec.rows)[:, None] < la[None, :]
+    for f in ra:
+        assert np.array_equal(as_bytes(ra[f][valid]), as_bytes(rb[f][valid])), f"{msg}: record field {f}"
+
+
+def _same_launch(st_a, out_a, st_b, out_b, msg, counters=("interrupts", "overrides")):
+    torch.cuda.synchronize()
+    assert_same_bits(st_a, st_b, EnvState.FIELDS, msg)
+    assert_same_bits(out_a.stats, out_b.stats, STATS, msg + " stats")
+    for f in counters:
+        assert torch.equal(getattr(out_a, f), getattr(out_b, f)), f"{msg}: {f}"
+    _same_record(out_a, out_b, msg)
+
+
+# ---------------------------------------------------------------------------------------------------- 1. forwarding
+
+LAUNCHES = {                  # mode -> the launches (flags, steps) of one run
+    "plain": [(0, K)],
+    "begin": [(B, K)],
+    "begin_at": [(AT, K)],
+    "one_episode": [(B | ONE, K), (ONE, K)],
+}
+
+
+@pytest.mark.parametrize("rules", [0, INT], ids=["record", "interrupt"])
+@pytest.mark.parametrize("mode", list(LAUNCHES))
+@pytest.mark.parametrize("name", MAPS)
+def test_rules_without_best_forward_to_the_existing_entry_points(name, mode, rules):
+    ctx, m, W, clf = _setup(name)
+    st = state_to_device(_host_state(m, N, 5), ctx)
+    twin = clone_state(st)
+    a, b = Out(ctx, K + 1), Out(ctx, K + 1, fill=77)            # b's overrides are a guard: never written without BEST
+    t = T0
+    for flags, steps in LAUNCHES[mode]:
+        kw = dict(begin=bool(flags & B), begin_at=bool(flags & AT), one_episode=bool(flags & ONE), record=a.rec)
+        if rules & INT:
+            ctx.rollout(st, W, clf, MASK, t, steps, a.stats, interrupt=True, interrupts=a.interrupts.view(-1), **kw)
+        else:
+            ctx.rollout(st, W, clf, MASK, t, steps, a.stats, **kw)
+        _select(ctx, twin, W, clf, t, steps, flags, rules, b)
+        _same_launch(twin, b, st, a, f"{name} {mode} rules {rules}", counters=())
+        t += steps + (1 if flags & (B | AT) else 0)
+    assert int((b.overrides != 77).sum()) == 0, "overrides written without BEST"
+    if rules & INT:
+        assert torch.equal(b.interrupts - 77, a.interrupts) and int(a.interrupts.sum()) > 0
+    else:
+        assert int((b.interrupts != 77).sum()) == 0, "interrupts written without INTERRUPT"
+    assert int(a.stats.entries.sum()) > 0 and int(a.stats.declines.sum()) > 0
+
+
+# ---------------------------------------------------------------------------------------------------- 2. chains unchanged
+
+@pytest.mark.parametrize("rules", [0, INT], ids=["best", "best+interrupt"])
+@pytest.mark.parametrize("name", MAPS)
+def test_best_changes_nothing_on_a_chain(name, rules):
+    ctx, m, W, clf = _setup(name, layout="chain")
+    st = state_to_device(_host_state(m, N, 6), ctx)
+    twin = clone_state(st)
+    a, b = Out(ctx, K + 1), Out(ctx, K + 1)
+    t = T0
+    for flags, steps in ((B, K), (0, K)):
+        _select(ctx, st, W, clf, t, steps, flags, rules, a)
+        _select(ctx, twin, W, clf, t, steps, flags, rules | BEST, b)
+        t += steps + 1
+    _same_launch(twin, b, st, a, f"{name} chain")
+    assert int(b.overrides.sum()) == 0
+    assert int(a.stats.entries.sum()) > 0 and int(a.stats.declines.sum()) > 0
+    assert not rules or int(a.interrupts.sum()) > 0
+
+
+@pytest.mark.parametrize("name", MAPS)
+def test_best_changes_nothing_where_every_value_ties(name):
+    """Every W_k == W_0 on the sibling layout: all values tie, the lowest wins and the gate holds."""
+    ctx, m, W, clf = _setup(name)
+    Wt = W.view(N_VF, -1)[0].repeat(N_VF).contiguous()
+    st = state_to_device(_host_state(m, N, 7), ctx)
+    twin = clone_state(st)
+    a, b = Out(ctx, K + 1), Out(ctx, K + 1)
+    _select(ctx, st, Wt, clf, T0, K, B, 0, a)
+    _select(ctx, twin, Wt, clf, T0, K, B, BEST, b)
+    _same_launch(twin, b, st, a, f"{name} ties")
+    assert int(b.overrides.sum()) == 0 and int(b.stats.declines.sum()) == 0
+    assert int(b.stats.entries[1:].sum()) > 0, "no option entered: the tie check is vacuous"
+
+
+# ---------------------------------------------------------------------------------------------------- 3. the rule
+
+class GpuEmulator(cm.Emulator):
+    """cm.Emulator on verified entry points: scg_rollout_record launches of one step (begin: BEGIN_AT with no step), scg_q_values,
+    scg_classifier_predict; the device arrays are patched after every step. Keeps the record row of every pseudo-step."""
+
+    def __init__(self, ctx, st_dev, W, clf, mask, gest=0, interrupt=False):
+        super().__init__(host_state(st_dev), ctx.n_vf, mask, gest, ctx.parents, ctx.cfg.reoffer_period, 0, interrupt)
+        self.ctx, self.dst, self.W, self.clf, self.mask = ctx, st_dev, W, clf, mask
+        self.stats = EpisodeStats(ctx.n_vf, self.n, ctx.device)
+        self.rows, self.lens = [], []
+
+    def _launch(self, t, n_steps, **kw):
+        tr = Trajectory(self.n, 1, 0, self.ctx.device)
+        self.ctx.rollout(self.dst, self.W, self.clf, self.mask, t, n_steps, self.stats, record=tr, **kw)
+        for f, v in host_state(self.dst).items():
+            self.st[f][...] = v
+        self.rows.append({f: getattr(tr, f)[0].cpu().numpy().copy() for f in tr.fields})
+        self.lens.append(tr.len.cpu().numpy().copy())
+
+    def plain_begin(self, t):
+        self._launch(t, 0, begin_at=True)
+
+    def plain_step(self, t):
+        self._launch(t, 1)
+
+    def q_values(self, k):
+        s = [getattr(self.dst, f) for f in ("x", "y", "vx", "vy")]
+        return self.ctx.q_values(s, self.W.view(self.n_vf, -1)[k].contiguous()).cpu().numpy()
+
+    def predict(self, k):
+        return self.ctx.classifier_predict(self.dst.x, self.dst.y, self.clf.view(self.n_vf, -1)[k].contiguous()).cpu().numpy()
+
+    def _push(self, cut):
+        for f in ("option_id", "opt_steps", "qcache"):
+            getattr(self.dst, f).copy_(dev(self.st[f]).view(getattr(self.dst, f).shape))
+        self.rows[-1]["option_id"] = self.st["option_id"].astype(np.int8)
+        self.rows[-1]["term"][cut] = _lib.ROLLOUT_TERM_INTERRUPTED
+
+    def begin_at(self, t):
+        ch, cut = super().begin_at(t)
+        self._push(cut)
+
+    def step(self, t):
+        ch, cut = super().step(t)
+        self._push(cut)
+
+    def record(self):
+        return {f: np.stack([r[f] for r in self.rows]) for f in self.rows[0]}, np.sum(self.lens, axis=0)
+
+
+def _oracle(name, n, seed, gest=0, parents=None):
+    m = scg.load_map(name)
+    orc = sc_oracle.Oracle(m, SCALE, n_envs=n, n_options=N_OPT, seed=seed, enabled_mask=MASK, n_threads=8,
+                           reoffer_period=REOFFER, **HP)
+    orc.set_parents(parents if parents is not None else cm.SIBLING_PARENTS)
+    if gest:
+        orc.set_gestation(gest)
+    return orc
+
+
+def _oracle_state(st_np, m, n):
+    st = sc_oracle.new_state(n, m)
+    for f, v in st_np.items():
+        st[f][...] = v
+    return st
+
+
+def _check_counters(out, emu, msg, interrupt):
+    for f in ("entries", "declines"):
+        assert np.array_equal(getattr(out.stats, f).cpu().numpy(), getattr(emu, f)), f"{msg}: {f}"
+    assert np.array_equal(out.overrides.cpu().numpy(), emu.overrides), f"{msg}: overrides"
+    assert np.array_equal(out.interrupts.cpu().numpy(), emu.interrupts), f"{msg}: interrupts"
+    assert interrupt or not emu.interrupts.any()
+
+
+@pytest.mark.parametrize("rules", [BEST, BEST | INT], ids=["best", "best+interrupt"])
+@pytest.mark.parametrize("name", MAPS)
+def test_best_equals_both_emulators(name, rules):
+    seed, interrupt = 3, bool(rules & INT)
+    ctx, m, W, clf = _setup(name, seed=seed)
+    st_np = _host_state(m, N, 7)
+    st = state_to_device(st_np, ctx)
+    twin = clone_state(st)
+    out = Out(ctx, K + 1)
+    _select(ctx, twin, W, clf, T0, K, AT, rules, out)
+    emu = GpuEmulator(ctx, st, W, clf, MASK, interrupt=interrupt)
+    emu.run(T0, K)
+    torch.cuda.synchronize()
+    msg = f"{name} rules {rules}"
+    # ---- the launch against the emulator on the library's own entry points
+    assert_same_bits(twin, st, EnvState.FIELDS, msg)
+    assert_same_bits(out.stats, emu.stats, [f for f in STATS if f not in ("entries", "declines")], msg + " stats")
+    _check_counters(out, emu, msg, interrupt)
+    rows, ln = emu.record()
+    got, got_len = out.record()
+    assert np.array_equal(got_len, ln) and (ln == K + 1).all()
+    for f in rows:
+        assert np.array_equal(as_bytes(got[f]), as_bytes(rows[f])), f"{msg}: record field {f}"
+    # ---- and against the same emulator on the oracle
+    orc = _oracle(name, N, seed)
+    oem = cm.OracleEmulator(orc, _oracle_state(st_np, m, N), W.cpu().numpy(), clf.cpu().numpy().reshape(N_VF, -1), MASK,
+                            interrupt=interrupt)
+    oem.run(T0, K)
+    for f in EnvState.FIELDS:
+        assert np.array_equal(as_bytes(getattr(twin, f)), as_bytes(oem.st[f])), f"{msg}: oracle emulator: {f} differs"
+    _check_counters(out, oem, msg + " oracle", interrupt)
+    # ---- the case exercises the rule (the emulators' own tallies)
+    for e in (emu, oem):
+        print(name, rules, e.begin_stats, e.events, int(e.overrides.sum()))
+        assert e.begin_stats["multi"] >= 0.5, "fewer than half of the envs have two candidates at the begin pseudo-step"
+        assert e.begin_stats["not_lowest"] >= 0.25, "c* is min C too often at the begin pseudo-step"
+        assert e.overrides.sum() > 0
+        assert e.events["sibling_rescues"] >= 1, "no env entered a sibling where min C would have been declined"
+        assert e.events["sibling_stays"] >= 1, "no env stayed out of an option that is not min C"
+        assert not interrupt or (e.events["interrupted"] > 0 and e.events["kept"] > e.events["interrupted"])
+
+
+# ---------------------------------------------------------------------------------------------------- 4. geometry
+
+def _two_launches(name, n, rules, block=None, seed=3):
+    ctx, m, W, clf = _setup(name, n=n, block=block, seed=seed, epsilon=0.1)
+    st = state_to_device(_host_state(m, n, 11), ctx)
+    out = Out(ctx, K + 1)
+    _select(ctx, st, W, clf, T0, K, AT, rules, out)             # (from the random states: the map's start states have one candidate)
+    _select(ctx, st, W, clf, T0 + K + 1, K, 0, rules, out, rec=False)
+    torch.cuda.synchronize()
+    return st, out
+
+
+def test_every_launch_geometry(monkeypatch):
+    ref_st, ref = _two_launches("pinball_simple", N, BEST | INT)
+    assert int(ref.overrides.sum()) > 0 and int(ref.interrupts.sum()) > 0
+    for epw in (2, 8, 32):
+        monkeypatch.setenv("SCG_ROLLOUT_EPW", str(epw))
+        st, out = _two_launches("pinball_simple", N, BEST | INT)
+        _same_launch(st, out, ref_st, ref, f"epw {epw}")
+
+
+@pytest.mark.parametrize("block_envs", [64, 256], indirect=True)
+def test_every_block_build(block_envs):
+    ref_st, ref = _two_launches("pinball_empty", N, BEST)
+    st, out = _two_launches("pinball_empty", N, BEST, block=current_block_envs())
+    assert int(ref.overrides.sum()) > 0
+    _same_launch(st, out, ref_st, ref, f"block {block_envs}")
+
+
+@pytest.mark.parametrize("n", [1, 257])
+def test_edge_launch_sizes_equal_the_oracle_emulator(n):
+    ctx, m, W, clf = _setup("pinball_simple", n=n)
+    st_np = _host_state(m, n, 13)
+    st = state_to_device(st_np, ctx)
+    out = Out(ctx, K + 1)
+    _select(ctx, st, W, clf, T0, K, AT, BEST | INT, out)
+    torch.cuda.synchronize()
+    oem = cm.OracleEmulator(_oracle("pinball_simple", n, 3), _oracle_state(st_np, m, n), W.cpu().numpy(),
+                            clf.cpu().numpy().reshape(N_VF, -1), MASK, interrupt=True)
+    oem.run(T0, K)
+    for f in EnvState.FIELDS:
+        assert np.array_equal(as_bytes(getattr(st, f)), as_bytes(oem.st[f])), f"n {n}: {f} differs"
+    _check_counters(out, oem, f"n {n}", True)
+    assert (out.rec.len.cpu().numpy() == K + 1).all()
+
+
+# ---------------------------------------------------------------------------------------------------- 5. edges
+
+def _edge_case(name, W=None, mask=MASK, gest=0, id_lo=-N_OPT, id_hi=N_OPT, rules=BEST | INT, flags=AT):
+    """One launch against the oracle emulator with the case's weights, enabled mask, gestation mask and entry ids."""
+    ctx, m, W0, clf = _setup(name, gest=gest)
+    W = W0 if W is None else W
+    st_np = _host_state(m, N, 17, id_lo=id_lo, id_hi=id_hi)
+    st = state_to_device(st_np, ctx)
+    out = Out(ctx, K + 1)
+    _select(ctx, st, W, clf, T0, K, flags, rules, out, mask=mask)
+    torch.cuda.synchronize()
+    orc = _oracle(name, N, 3, gest=gest)
+    oem = cm.OracleEmulator(orc, _oracle_state(st_np, m, N), W.cpu().numpy(), clf.cpu().numpy().reshape(N_VF, -1), mask, gest=gest,
+                            interrupt=bool(rules & INT))
+    oem.run(T0, K, begin_at=bool(flags & AT))
+    for f in EnvState.FIELDS:
+        a, b = getattr(st, f).cpu().numpy(), oem.st[f]
+        assert np.array_equal(as_bytes(a), as_bytes(b)), f"{f} differs"
+    _check_counters(out, oem, name, bool(rules & INT))
+    return out, oem
+
+
+def _nan_rows(W, ks):
+    Wn = W.clone().view(N_VF, -1)
+    for k in ks:
+        Wn[k] = float("nan")
+    return Wn.view(-1).contiguous()
+
+
+@pytest.mark.parametrize("name", MAPS)
+def test_nan_weights_of_one_candidate(name):
+    _, _, W, _ = _setup(name)
+    out, oem = _edge_case(name, W=_nan_rows(W, [1]))
+    assert int(out.stats.entries[1].sum()) == 0, "an option whose values are NaN was entered"
+    assert int(out.overrides.sum()) > 0
+
+
+def test_nan_weights_of_every_candidate():
+    _, _, W, _ = _setup("pinball_simple")
+    out, oem = _edge_case("pinball_simple", W=_nan_rows(W, range(1, N_VF)))
+    assert int(out.stats.entries.sum()) == 0 and int(out.overrides.sum()) == 0
+    dec = out.stats.declines.cpu().numpy().sum(axis=1)
+    assert dec[1:].sum() > 0 and oem.events["offers"] == dec.sum()                  # every offer is min C, declined
+
+
+@pytest.mark.parametrize("name", MAPS)
+def test_a_sibling_that_is_not_enabled(name):
+    out, _ = _edge_case(name, mask=MASK & ~0b100)
+    assert int(out.stats.entries[2].sum()) == 0 and int(out.stats.declines[2].sum()) == 0
+    assert int(out.overrides.sum()) > 0
+
+
+@pytest.mark.parametrize("name", MAPS)
+def test_a_gestating_sibling_is_known_and_never_chosen(name):
+    out, _ = _edge_case(name, mask=MASK & ~0b1000, gest=0b1000)
+    assert int(out.stats.entries[3].sum()) == 0 and int(out.stats.declines[3].sum()) == 0
+    assert int(out.overrides.sum()) > 0
+
+
+def test_out_of_range_option_ids_at_entry():
+    """Ids beyond the options on both sides, without a begin: such an env runs the root, stays out of nothing and is offered at once."""
+    out, _ = _edge_case("pinball_simple", id_lo=-9, id_hi=9, flags=0)
+    assert int(out.overrides.sum()) > 0
+
+
+# ---------------------------------------------------------------------------------------------------- 6. refusals
+
+def test_c_abi_refusals_launch_nothing():
+    n = 64
+    ctx, m, W, clf = _setup("pinball_simple", n=n)
+    st = state_to_device(_host_state(m, n, 1), ctx)
+    before = clone_state(st)
+    lib = ctx.lib
+    out = Out(ctx, 2, fill=77)
+    for f in STATS:
+        getattr(out.stats, f).fill_(77)
+    cs = out.stats.c_struct()
+    nofin = out.stats.c_struct()
+    nofin.finished = None
+    good, noln, short = out.rec.c_struct(), out.rec.c_struct(), out.rec.c_struct()
+    noln.len = None
+    short.rows = 1
+    intr, ov = C.c_void_p(out.interrupts.data_ptr()), C.c_void_p(out.overrides.data_ptr())
+
+    def call(rules, flags, n_steps, s, rec):
+        """scg_rollout_select, or with rules = None scg_rollout_record: (status, message)."""
+        head = _args(ctx, st, W, clf, 0b110, 0, n_steps, flags, s)
+        rp = None if rec is None else C.byref(rec)
+        if rules is None:
+            rc = lib.scg_rollout_record(ctx._ctx, *head, rp, None)
+        else:
+            rc = lib.scg_rollout_select(ctx._ctx, *head, intr, ov, rp, C.c_uint32(rules), None)
+        return rc, lib.scg_last_error(ctx._ctx).decode()
+
+    for rules in (0, INT, BEST, BEST | INT):
+        for flags, n_steps, s, rec in ((0x80, 1, cs, None), (B | AT, 1, cs, None), (0, _lib.ROLLOUT_MAX_STEPS + 1, cs, None),
+                                       (0, -1, cs, None), (0, 0, cs, None), (ONE, 1, nofin, None), (0, 1, cs, noln),
+                                       (B, 2, cs, short)):
+            rc_s, msg_s = call(rules, flags, n_steps, s, rec)
+            rc_r, msg_r = call(None, flags, n_steps, s, rec)
+            assert rc_s == rc_r == -1, (rules, flags, n_steps)
+            assert msg_s == msg_r.replace("scg_rollout_record", "scg_rollout_select"), (msg_s, msg_r)
+            assert msg_s.startswith("scg_rollout_select: ")
+    for rules in (4, 8 | BEST, 0x80000000 | INT, 0xfffffffc):
+        rc, msg = call(rules, B, 1, cs, good)
+        assert rc == -1 and msg == "scg_rollout_select: unknown rule", (rules, msg)
+    torch.cuda.synchronize()
+    assert_same_bits(st, before, EnvState.FIELDS, "a refused call wrote the state")
+    for f in STATS:
+        assert int((getattr(out.stats, f) != 77).sum()) == 0, f"a refused call wrote stats.{f}"
+    assert int((out.interrupts != 77).sum()) == 0 and int((out.overrides != 77).sum()) == 0
+    assert int(out.rec.len.abs().sum()) == 0 and all(int(getattr(out.rec, f).abs().sum()) == 0 for f in ("vf", "done", "action"))
+    out.stats.zero_()
+    cs = out.stats.c_struct()
+    rc, _ = call(BEST | INT, B, 1, cs, good)                                   # well-formed: it runs
+    torch.cuda.synchronize()
+    assert rc == 0 and (out.rec.len == 2).all()
+
+
+# ---------------------------------------------------------------------------------------------------- 7. the facade
+
+def test_agent_evaluate_and_record_with_choose():
+    a = crossing_agent(n_opt=N_OPT)
+    parents, clf = cm.sibling_tree(a.map)
+    a.ctx.set_option_parents(parents)
+    a.clf.copy_(dev(clf))
+    for k in range(3, N_OPT + 1):
+        a.enable_option(k)
+    W0, t0 = a.W.clone(), a.t
+    st0 = {f: getattr(a.state, f).clone() for f in EnvState.FIELDS}
+    eval_calls = []
+    x, y, _, _ = random_states(a.map, 1000, 7)                  # (the map's start states have one candidate: start anywhere)
+    kw = dict(states=(dev(x), dev(y)), steps_per_launch=32, epsilon=0.05)
+    plain0 = a.evaluate(**kw)                                   # (creates the evaluation context)
+    ectx = a._eval_ctx[1000][0]
+    with spy_calls(a.ctx) as (calls, _), spy_calls(ectx, eval_calls):
+        plain = a.evaluate(**kw)
+        n_plain = len(eval_calls)
+        # (BEGIN_AT's launch is scg_rollout_record's, the others scg_rollout's: the entry points it uses without this feature)
+        assert set(c for c in eval_calls if c.startswith("scg_rollout")) == {"scg_rollout_record", "scg_rollout"}, eval_calls
+        none = a.evaluate(**kw, choose=None)
+        assert eval_calls[n_plain:] == eval_calls[:n_plain]    # choose=None: exactly the calls it makes without it
+        on = a.evaluate(**kw, choose="value")
+        assert "scg_rollout_select" in eval_calls[2 * n_plain:]
+        traj, rs = a.record_episodes(**kw, choose="value", interrupt=True)
+        both = a.evaluate(**kw, choose="value", interrupt=True)
+        again = a.evaluate(**kw)
+        for bad in ("best", "", 0):
+            with pytest.raises(ValueError):
+                a.evaluate(**kw, choose=bad)
+            with pytest.raises(ValueError):
+                a.record_episodes(**kw, choose=bad)
+    torch.cuda.synchronize()
+    assert calls == [], f"evaluate(choose='value') called into the training context: {calls}"
+    assert torch.equal(a.W, W0) and a.t == t0
+    for f in EnvState.FIELDS:
+        assert torch.equal(getattr(a.state, f), st0[f]), f
+    assert plain0 == plain == none == again and "overrides" not in plain and "interrupts" not in plain
+    assert list(on) == list(plain) + ["overrides"] and on["episodes"] == 1000
+    assert list(both) == list(plain) + ["interrupts", "overrides"] and rs == both
+    assert sum(on["overrides"]) > 0 and on["overrides"][0] == 0 and sum(both["overrides"]) > 0
+    assert all(o <= e for o, e in zip(on["overrides"], on["entries"]))
+    assert traj.summary()["interrupted"] == both["interrupts"]

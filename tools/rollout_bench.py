@@ -4,10 +4,12 @@ Root + 5 options (chain classifiers, all enabled), bench-like weights (std 1e-3)
 warmed up and synchronised, and the two are timed alternately (rounds of rollout, step loop, rollout, ...); the line per size
 gives the median over the rounds. --record adds rollouts that record every step (SPEC §10) of all envs (`all`) or of the
 first N envs (`N`), timed in the same alternation (`none` is the plain rollout, always timed). --interrupt adds interrupting
-rollouts (SPEC §11, scg_rollout_interrupt) on a state of their own, timed in the same alternation.
+rollouts (SPEC §11, scg_rollout_interrupt) on a state of their own, timed in the same alternation. --choose times something
+else: value-ranked choice (SPEC §14, scg_rollout_select) against scg_rollout_record's kernel, on the default chain and on the
+sibling tree of tools/choice_report.py (bench_choose).
 
     python tools/rollout_bench.py [--sizes 4096 65536] [--k 64] [--rounds 7] [--epw 2 4 8 16 32] [--record none 1024 all]
-                                  [--interrupt]
+                                  [--interrupt] [--choose]
 """
 import argparse
 import json
@@ -91,6 +93,61 @@ def bench(n, k, rounds, n_opt=5, epw=None, record=(), interrupt=False):
     return out
 
 
+SIBLING_PARENTS = [0, 0, 0, 1, 1, 2]
+
+
+def bench_choose(n, k, rounds, layout, n_opt=5):
+    """µs per step of scg_rollout_select(BEST) against scg_rollout_record's kernel (a record of one env: the same recording
+    instantiation, next to nothing recorded), each on a state of its own, timed alternately. layout "chain": the default chain
+    (at most one candidate: the kernel's overhead alone); "sibling": tools/choice_report.py's hand-set tree (several candidates:
+    the extra evaluations too)."""
+    import numpy as np
+    import torch
+    import skill_chaining_with_graphs_amd as scg
+    from choice_report import disc_weights, sibling_discs
+    from skill_chaining_with_graphs_amd.core import ScgContext
+    from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
+    from skill_chaining_with_graphs_amd.trajectory import Trajectory
+    m = scg.load_map("pinball_simple")
+    ctx = ScgContext(n, n_opt, m, device=0, seed=7, epsilon=0.05, max_episode_steps=2000)
+    mask = ((1 << (n_opt + 1)) - 1) & ~1
+    if layout == "sibling":
+        ctx.set_option_parents(SIBLING_PARENTS)
+        c = np.zeros((n_opt + 1, 8), np.float32)
+        c[1:] = [disc_weights(*d) for d in sibling_discs(m)]
+    else:
+        c = rig.chain_classifiers(m, n_opt)
+    clf = torch.as_tensor(c, device=ctx.device).view(-1)
+    g = torch.Generator().manual_seed(3)
+    W = (torch.randn((n_opt + 1) * 5 * 1296, generator=g) * 1e-3).to(ctx.device)
+    side = {}
+    for name in ("record", "choose"):
+        side[name] = {"st": rig.state_on(ctx, m, n), "t": 0, "stats": EpisodeStats(n_opt + 1, n, ctx.device), "us": []}
+    rec = Trajectory(1, k, 0, ctx.device)
+
+    def roll(name):
+        s = side[name]
+        kw = {"record": rec} if name == "record" else {"choose": "value"}
+        ctx.rollout(s["st"], W, clf, mask, s["t"], k, s["stats"], **kw)
+        s["t"] += k
+
+    for name in side:
+        roll(name); roll(name)
+    for _ in range(rounds):
+        for name in side:
+            side[name]["us"].append(rig.timed(lambda: roll(name), 3) * 1e6 / k)
+    r, c_us = (float(np.median(side[x]["us"])) for x in ("record", "choose"))
+    out = {"n_envs": n, "k": k, "options": n_opt, "layout": layout, "record_kernel_us_per_step": round(r, 2),
+           "choose_us_per_step": round(c_us, 2), "choose_over_record": round(c_us / r, 4),
+           "record_rounds_us": [round(v, 2) for v in side["record"]["us"]], "choose_rounds_us": [round(v, 2) for v in side["choose"]["us"]]}
+    for name in side:
+        s = side[name]
+        out[f"{name}_offers_per_env_step"] = round(float(s["stats"].entries.sum() + s["stats"].declines.sum()) / (s["t"] * n), 4)
+    st = side["choose"]
+    out["choose_overrides_per_env_step"] = round(float(st["stats"].overrides.sum()) / (st["t"] * n), 4)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--sizes", type=int, nargs="+", default=[4096, 65536])
@@ -101,7 +158,14 @@ def main():
     ap.add_argument("--record", nargs="+", default=["none"],
                     help="also time recorded rollouts: `all` envs or the first N envs (`none`: the plain rollout only)")
     ap.add_argument("--interrupt", action="store_true", help="also time interrupting rollouts (SPEC §11)")
+    ap.add_argument("--choose", action="store_true",
+                    help="instead: value-ranked choice (SPEC §14) against the recording kernel, on the chain and on the sibling tree")
     a = ap.parse_args()
+    if a.choose:
+        for n in a.sizes:
+            for layout in ("chain", "sibling"):
+                print(json.dumps(bench_choose(n, a.k, a.rounds, layout)), flush=True)
+        return
     rec = [r for r in a.record if r != "none"]
     for r in rec:
         if r != "all" and not r.isdigit():
