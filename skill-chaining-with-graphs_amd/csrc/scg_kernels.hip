@@ -519,10 +519,11 @@ static int launch_reduce(scg_ctx *c, float *W, uint32_t apply, int nblk, hipStre
         SCG_HIP(c, hipGetLastError());
         return SCG_OK;
     }
-    const int sy = (nrow + RED_NCOL - 1) / RED_NCOL;
-    if (RED_NCOL * (c->n_vf + sy) <= c->n_cu)           // fits the chip at one workgroup per CU: all sixteen slabs of a segment in flight
+    const int sy = (nrow + RED_NCOL - 1) / RED_NCOL;            // row slots: whole lines of the grid in front of the slab workgroups' n_vf lines
+    constexpr int W64 = (RED_COLS + 63) / 64;                   // the launch's size in units of 64 columns x 16 waves (+ its rows in lines of as many)
+    if (W64 * (c->n_vf + (nrow + W64 - 1) / W64) <= c->n_cu)    // a small launch (at most one such unit per CU): all sixteen slabs of a segment in flight
         hipLaunchKernelGGL(reduce_kernel<16>, dim3(RED_NCOL, c->n_vf + sy), dim3(RED_THREADS), 0, s, R);
-    else
+    else                                                        // 64 VGPRs: eight waves per SIMD (round 18: with all of the bench size's workgroups resident either way, this form was 0.2 % ahead there)
         hipLaunchKernelGGL(reduce_kernel<8>, dim3(RED_NCOL, c->n_vf + sy), dim3(RED_THREADS), 0, s, R);
     SCG_HIP(c, hipGetLastError());
     return SCG_OK;

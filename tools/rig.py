@@ -16,8 +16,9 @@ import bench  # noqa: E402  (constants and chain_discs; bench.py imports torch o
 _TIMING = {"lite": ("SCG_LITE_LIB", "libscg_hip_lite.so"), "rstamps": ("SCG_RSTAMPS_LIB", "libscg_hip_rstamps.so")}
 STAMP_SLOTS = 48      # csrc/scg_step_kernel.hpp STAMP_SLOTS: [0..31] four waves x eight boundaries, [32] [33] the block's start / end
 #                       on the 100 MHz clock, [34..41] HW_REG_HW_ID of the 16 waves, [42] the block's pair groups
-RED_NCOL = 26         # csrc/scg_reduce_kernel.hpp RED_NCOL = (RED_COLS + 63) / 64: the reduce grid is RED_NCOL x (n_vf + row slots)
-RED_STAMP_SLOTS = 8   # csrc/scg_reduce_kernel.hpp RED_STAMP_SLOTS
+RED_NCOL = 102        # csrc/scg_reduce_kernel.hpp RED_NCOL = ceil(1620 / RED_C): the reduce grid is RED_NCOL x (row slots + n_vf)
+RED_WAVES = 4         # csrc/scg_reduce_kernel.hpp RED_WAVES: waves of a slab workgroup
+RED_STAMP_SLOTS = 24  # csrc/scg_reduce_kernel.hpp RED_STAMP_SLOTS
 
 
 def headline_agent(envs=bench.ENVS_PER_GPU, options=bench.N_OPTIONS, *, seed=0, hp=None, enabled=None, w_std=1e-3, reset_seed=1000,
@@ -70,13 +71,13 @@ def read_step_stamps(ctx, reset):
     return out
 
 
-def read_reduce_stamps(ctx, reset):
+def read_reduce_stamps(ctx, reset, ncol=RED_NCOL):
     """[workgroups, RED_STAMP_SLOTS] uint64 of the reduce timing build's last launch, in grid order (y major: the row slots, then
-    one line of RED_NCOL slab workgroups per value function)."""
+    one line of `ncol` slab workgroups per value function; another `ncol` reads a library with another grid width)."""
     import numpy as np
     fn = _diag(ctx, "scg_diag_reduce_stamps", C.c_int)
     nwg, nrow = fn(ctx._ctx, None, 0), -(-ctx.n_envs // 256)
-    assert nwg == RED_NCOL * (ctx.n_vf + -(-nrow // RED_NCOL)), "not a reduce timing build, or RED_NCOL moved"
+    assert nwg == ncol * (ctx.n_vf + -(-nrow // ncol)), "not a reduce timing build of this grid width, or RED_NCOL moved"
     out = np.zeros((nwg, RED_STAMP_SLOTS), np.uint64)
     fn(ctx._ctx, out.ctypes.data_as(C.c_void_p), int(reset))
     return out
