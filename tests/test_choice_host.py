@@ -1,4 +1,4 @@
-"""SPEC §14 value-ranked option choice, host side (no GPU): the numpy model of tests/choice_model.py on hand-made cases (ties, NaN
+"""SPEC §14 value-ranked option choice, host side (no GPU): tests/option_rules.py's `choose` on hand-made cases (ties, NaN
 values, stay, the fresh offer, the re-offer period, |C| <= 1 against §4.2), the sibling layout, the header and the binding of
 scg_rollout_select, ScgContext.rollout's own refusals and EpisodeStats' optional `overrides`."""
 import ctypes as C
@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-import choice_model as cm
-import interrupt_learning_model as ilm
+import option_rules as rules
+from util import SIBLING_PARENTS, sibling_tree
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "scg_abi.h")
@@ -26,7 +26,7 @@ def _one(cset, values, v0, keep=False, done=0, oid=0, t=1, gid=0, period=4, n_vf
     for k, v in values.items():
         V[k] = v
     V[0] = v0
-    ch = cm.choose(Cm, V, np.array([keep]), np.array([done]), np.array([oid]), t, np.array([gid], np.uint64), period)
+    ch = rules.choose(Cm, V, np.array([keep]), np.array([done]), np.array([oid]), t, np.array([gid], np.uint64), period)
     return {k: (v[0].item()) for k, v in ch.items()}
 
 
@@ -76,13 +76,13 @@ def test_reoffer_period(period):
 
 
 def _spec42(cand, V, keep, done, oid, t, gid, period):
-    """SPEC §4.2 for one step, from ilm.candidates' cand: (option_id after the step, vf, declined, stay)."""
+    """SPEC §4.2 for one step, from rules.candidates' cand: (option_id after the step, vf, declined, stay)."""
     idx = np.arange(len(cand))
     stay = ~keep & (cand >= 1) & (done == 0) & (oid == -cand) & (((t + gid) % period) != 0)
     offer = ~keep & (cand >= 1) & ~stay
     with np.errstate(invalid="ignore"):
         declined = offer & ~(V[cand, idx] >= V[0])
-    o_keep = np.where((oid >= 1) & (oid < V.shape[0]), oid, 0)
+    o_keep = rules.vf_of(oid, V.shape[0])
     new = np.where(keep, oid, np.where(declined | stay, -cand, np.where(offer, cand, 0)))
     return new, np.where(keep, o_keep, np.where(offer & ~declined, cand, 0)), declined, stay
 
@@ -95,10 +95,10 @@ def test_at_most_one_candidate_is_spec_4_2():
     in_n = np.zeros((n_vf, n), bool)
     for k in range(1, n_vf):
         in_n[k] = (depth >= 1) & (k >= depth)
-    Cm = cm.candidate_mask(in_n, enabled, parents, n_vf)
+    Cm = rules.candidate_mask(in_n, enabled, parents, n_vf)
     assert Cm.sum(axis=0).max() == 1
-    cand = ilm.candidates(in_n, enabled, parents, n_vf)
-    assert np.array_equal(cm.min_c(Cm), cand)
+    cand = rules.min_c(Cm)
+    assert np.array_equal(cand, np.where((depth >= 1) & (((enabled >> depth) & 1) == 1), depth, 0))   # in I_depth, not in I_(depth-1)
     V = rng.standard_normal((n_vf, n)).astype(np.float32)
     V[:, rng.random(n) < 0.05] = NAN
     V[1:, rng.random(n) < 0.2] = V[0, 0]
@@ -107,7 +107,7 @@ def test_at_most_one_candidate_is_spec_4_2():
     done = rng.choice([0, 0, 0, 1, 2], n)
     gid = np.arange(n, dtype=np.uint64)
     for t in (0, 1, 2, 3):
-        ch = cm.choose(Cm, V, keep, done, oid, t, gid, 4)
+        ch = rules.choose(Cm, V, keep, done, oid, t, gid, 4)
         new, vf, declined, stay = _spec42(cand, V, keep, done, oid, t, np.arange(n), 4)
         assert np.array_equal(ch["option_id"], new) and np.array_equal(ch["vf"], vf)
         assert np.array_equal(ch["declined"], declined) and np.array_equal(ch["stay"], stay)
@@ -116,15 +116,25 @@ def test_at_most_one_candidate_is_spec_4_2():
 
 
 def test_candidate_mask_generalises_ilm_candidates():
+    """candidate_mask / min_c against §4.2 written out per env: ascending k; enabled, in the set, not in the parent's region."""
     rng = np.random.default_rng(3)
     n, n_vf = 5000, 6
     in_n = rng.random((n_vf, n)) < 0.5
     in_n[0] = False
     for enabled in (0b111110, 0b101010, 0b000100):
-        Cm = cm.candidate_mask(in_n, enabled, cm.SIBLING_PARENTS, n_vf)
+        Cm = rules.candidate_mask(in_n, enabled, SIBLING_PARENTS, n_vf)
         assert not Cm[0].any()
-        assert np.array_equal(cm.min_c(Cm), ilm.candidates(in_n, enabled, cm.SIBLING_PARENTS, n_vf))
-    assert (cm.candidate_mask(in_n, 0b111110, cm.SIBLING_PARENTS, n_vf).sum(axis=0) >= 2).mean() > 0.3
+        want_c, want_C = np.zeros(n, np.int64), np.zeros((n_vf, n), bool)
+        for i in range(n):
+            for k in range(1, n_vf):
+                p = SIBLING_PARENTS[k]
+                if (enabled >> k) & 1 and in_n[k, i] and not (p != 0 and in_n[p, i]):
+                    want_C[k, i] = True
+                    if want_c[i] == 0:
+                        want_c[i] = k
+        assert np.array_equal(Cm, want_C)
+        assert np.array_equal(rules.min_c(Cm), want_c) and np.array_equal(rules.candidates(in_n, enabled, SIBLING_PARENTS, n_vf), want_c)
+    assert (rules.candidate_mask(in_n, 0b111110, SIBLING_PARENTS, n_vf).sum(axis=0) >= 2).mean() > 0.3
 
 
 @pytest.mark.parametrize("name", ["pinball_simple", "pinball_empty"])
@@ -133,13 +143,11 @@ def test_sibling_tree_gives_most_states_several_candidates(name):
     import skill_chaining_with_graphs_amd as scg
     from util import make_oracle, random_states
     orc, m = make_oracle(name, n_envs=1, n_options=5)
-    parents, clf = cm.sibling_tree(m)
+    parents, clf = sibling_tree(m)
     assert parents == [0, 0, 0, 1, 1, 2] and clf.shape == (6, 8) and not clf[0].any()
     x, y, _, _ = random_states(m, 2048, 7, vmax=1.5)
-    in_n = np.zeros((6, len(x)), bool)
-    for k in range(1, 6):
-        in_n[k] = orc.classifier_predict(x, y, clf[k]) != 0
-    Cm = cm.candidate_mask(in_n, 0b111110, parents, 6)
+    in_n = rules.membership(lambda px, py, k: orc.classifier_predict(px, py, clf[k]), x, y, 6, 0b111110)
+    Cm = rules.candidate_mask(in_n, 0b111110, parents, 6)
     assert (Cm.sum(axis=0) >= 2).mean() >= 0.5
 
 

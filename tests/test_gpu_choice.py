@@ -1,6 +1,6 @@
 """SPEC §14 value-ranked option choice on the GPU (scg_rollout_select): rules = 0 and rules = INTERRUPT forward to scg_rollout_record
 and scg_rollout_interrupt; on chains, and with every value tied, BEST changes nothing; on the sibling layout one BEST launch (and
-one BEST | INTERRUPT launch) equals an emulator built from already-verified entry points and the same emulator on the oracle;
+one BEST | INTERRUPT launch) equals tests/acting_emulator.py's emulator on already-verified entry points and the same emulator on the oracle;
 every launch geometry and block build agree; NaN weights, a missing or gestating sibling and out-of-range ids; the C-ABI's
 refusals; and the agent's evaluate(choose="value") / record_episodes(choose="value") leave training alone."""
 import ctypes as C
@@ -9,17 +9,16 @@ import numpy as np
 import pytest
 import torch
 
-import choice_model as cm
-import interrupt_learning_model as ilm
 import sc_oracle
 import skill_chaining_with_graphs_amd as scg
+from acting_emulator import oracle_emulator
 from skill_chaining_with_graphs_amd import _lib
 from skill_chaining_with_graphs_amd.core import EnvState
 from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
 from skill_chaining_with_graphs_amd.trajectory import Trajectory
 from gpu_util import (as_bytes, assert_same_bits, block_envs, clone_state, crossing_agent, current_block_envs, dev,  # noqa: F401
-                      host_state, make_context, spy_calls, state_to_device)                                          # (block_envs: the fixture)
-from util import HP, SCALE, random_env_state, random_states
+                      gpu_emulator, make_context, spy_calls, state_to_device)                                          # (block_envs: the fixture)
+from util import HP, SCALE, SIBLING_PARENTS, crossing_weights, oracle_state, random_env_state, random_states, sibling_tree, wide_chain
 
 pytestmark = pytest.mark.gpu
 
@@ -34,15 +33,15 @@ REOFFER = 4
 
 def _layout(m, layout):
     if layout == "sibling":
-        return cm.sibling_tree(m)
-    return None, ilm.wide_chain(m, N_OPT)                      # default parents: the chain k -> k-1, nested sets, |C| <= 1
+        return sibling_tree(m)
+    return None, wide_chain(m, N_OPT)                      # default parents: the chain k -> k-1, nested sets, |C| <= 1
 
 
 def _setup(name, n=N, layout="sibling", gest=0, seed=3, block=None, **hp):
     m = scg.load_map(name)
     parents, clf = _layout(m, layout)
     ctx = make_context(m, n, N_OPT, block, parents, gest, seed, reoffer_period=REOFFER, **hp)
-    return ctx, m, dev(ilm.crossing_weights(N_VF, seed)).view(-1), dev(clf).view(-1)
+    return ctx, m, dev(crossing_weights(N_VF, seed)).view(-1), dev(clf).view(-1)
 
 
 def _host_state(m, n, seed, id_lo=-N_OPT, id_hi=N_OPT):
@@ -167,70 +166,14 @@ def test_best_changes_nothing_where_every_value_ties(name):
 
 # ---------------------------------------------------------------------------------------------------- 3. the rule
 
-class GpuEmulator(cm.Emulator):
-    """cm.Emulator on verified entry points: scg_rollout_record launches of one step (begin: BEGIN_AT with no step), scg_q_values,
-    scg_classifier_predict; the device arrays are patched after every step. Keeps the record row of every pseudo-step."""
-
-    def __init__(self, ctx, st_dev, W, clf, mask, gest=0, interrupt=False):
-        super().__init__(host_state(st_dev), ctx.n_vf, mask, gest, ctx.parents, ctx.cfg.reoffer_period, 0, interrupt)
-        self.ctx, self.dst, self.W, self.clf, self.mask = ctx, st_dev, W, clf, mask
-        self.stats = EpisodeStats(ctx.n_vf, self.n, ctx.device)
-        self.rows, self.lens = [], []
-
-    def _launch(self, t, n_steps, **kw):
-        tr = Trajectory(self.n, 1, 0, self.ctx.device)
-        self.ctx.rollout(self.dst, self.W, self.clf, self.mask, t, n_steps, self.stats, record=tr, **kw)
-        for f, v in host_state(self.dst).items():
-            self.st[f][...] = v
-        self.rows.append({f: getattr(tr, f)[0].cpu().numpy().copy() for f in tr.fields})
-        self.lens.append(tr.len.cpu().numpy().copy())
-
-    def plain_begin(self, t):
-        self._launch(t, 0, begin_at=True)
-
-    def plain_step(self, t):
-        self._launch(t, 1)
-
-    def q_values(self, k):
-        s = [getattr(self.dst, f) for f in ("x", "y", "vx", "vy")]
-        return self.ctx.q_values(s, self.W.view(self.n_vf, -1)[k].contiguous()).cpu().numpy()
-
-    def predict(self, k):
-        return self.ctx.classifier_predict(self.dst.x, self.dst.y, self.clf.view(self.n_vf, -1)[k].contiguous()).cpu().numpy()
-
-    def _push(self, cut):
-        for f in ("option_id", "opt_steps", "qcache"):
-            getattr(self.dst, f).copy_(dev(self.st[f]).view(getattr(self.dst, f).shape))
-        self.rows[-1]["option_id"] = self.st["option_id"].astype(np.int8)
-        self.rows[-1]["term"][cut] = _lib.ROLLOUT_TERM_INTERRUPTED
-
-    def begin_at(self, t):
-        ch, cut = super().begin_at(t)
-        self._push(cut)
-
-    def step(self, t):
-        ch, cut = super().step(t)
-        self._push(cut)
-
-    def record(self):
-        return {f: np.stack([r[f] for r in self.rows]) for f in self.rows[0]}, np.sum(self.lens, axis=0)
-
-
 def _oracle(name, n, seed, gest=0, parents=None):
     m = scg.load_map(name)
     orc = sc_oracle.Oracle(m, SCALE, n_envs=n, n_options=N_OPT, seed=seed, enabled_mask=MASK, n_threads=8,
                            reoffer_period=REOFFER, **HP)
-    orc.set_parents(parents if parents is not None else cm.SIBLING_PARENTS)
+    orc.set_parents(parents if parents is not None else SIBLING_PARENTS)
     if gest:
         orc.set_gestation(gest)
     return orc
-
-
-def _oracle_state(st_np, m, n):
-    st = sc_oracle.new_state(n, m)
-    for f, v in st_np.items():
-        st[f][...] = v
-    return st
 
 
 def _check_counters(out, emu, msg, interrupt):
@@ -251,13 +194,13 @@ def test_best_equals_both_emulators(name, rules):
     twin = clone_state(st)
     out = Out(ctx, K + 1)
     _select(ctx, twin, W, clf, T0, K, AT, rules, out)
-    emu = GpuEmulator(ctx, st, W, clf, MASK, interrupt=interrupt)
-    emu.run(T0, K)
+    emu = gpu_emulator(ctx, st, W, clf, MASK, best=True, interrupt=interrupt)
+    emu.run(T0, K, begin_at=True)
     torch.cuda.synchronize()
     msg = f"{name} rules {rules}"
     # ---- the launch against the emulator on the library's own entry points
     assert_same_bits(twin, st, EnvState.FIELDS, msg)
-    assert_same_bits(out.stats, emu.stats, [f for f in STATS if f not in ("entries", "declines")], msg + " stats")
+    assert_same_bits(out.stats, emu.B.stats, [f for f in STATS if f not in ("entries", "declines")], msg + " stats")
     _check_counters(out, emu, msg, interrupt)
     rows, ln = emu.record()
     got, got_len = out.record()
@@ -266,21 +209,20 @@ def test_best_equals_both_emulators(name, rules):
         assert np.array_equal(as_bytes(got[f]), as_bytes(rows[f])), f"{msg}: record field {f}"
     # ---- and against the same emulator on the oracle
     orc = _oracle(name, N, seed)
-    oem = cm.OracleEmulator(orc, _oracle_state(st_np, m, N), W.cpu().numpy(), clf.cpu().numpy().reshape(N_VF, -1), MASK,
-                            interrupt=interrupt)
-    oem.run(T0, K)
+    oem = oracle_emulator(orc, oracle_state(st_np, m), W.cpu().numpy(), clf.cpu().numpy(), MASK, best=True, interrupt=interrupt)
+    oem.run(T0, K, begin_at=True)
     for f in EnvState.FIELDS:
         assert np.array_equal(as_bytes(getattr(twin, f)), as_bytes(oem.st[f])), f"{msg}: oracle emulator: {f} differs"
     _check_counters(out, oem, msg + " oracle", interrupt)
     # ---- the case exercises the rule (the emulators' own tallies)
     for e in (emu, oem):
-        print(name, rules, e.begin_stats, e.events, int(e.overrides.sum()))
+        print(name, rules, e.begin_stats, e.events, e.kept, e.interrupted, int(e.overrides.sum()))
         assert e.begin_stats["multi"] >= 0.5, "fewer than half of the envs have two candidates at the begin pseudo-step"
         assert e.begin_stats["not_lowest"] >= 0.25, "c* is min C too often at the begin pseudo-step"
         assert e.overrides.sum() > 0
         assert e.events["sibling_rescues"] >= 1, "no env entered a sibling where min C would have been declined"
         assert e.events["sibling_stays"] >= 1, "no env stayed out of an option that is not min C"
-        assert not interrupt or (e.events["interrupted"] > 0 and e.events["kept"] > e.events["interrupted"])
+        assert not interrupt or (e.interrupted > 0 and e.kept > e.interrupted)
 
 
 # ---------------------------------------------------------------------------------------------------- 4. geometry
@@ -320,9 +262,9 @@ def test_edge_launch_sizes_equal_the_oracle_emulator(n):
     out = Out(ctx, K + 1)
     _select(ctx, st, W, clf, T0, K, AT, BEST | INT, out)
     torch.cuda.synchronize()
-    oem = cm.OracleEmulator(_oracle("pinball_simple", n, 3), _oracle_state(st_np, m, n), W.cpu().numpy(),
-                            clf.cpu().numpy().reshape(N_VF, -1), MASK, interrupt=True)
-    oem.run(T0, K)
+    oem = oracle_emulator(_oracle("pinball_simple", n, 3), oracle_state(st_np, m), W.cpu().numpy(), clf.cpu().numpy(), MASK,
+                          best=True, interrupt=True)
+    oem.run(T0, K, begin_at=True)
     for f in EnvState.FIELDS:
         assert np.array_equal(as_bytes(getattr(st, f)), as_bytes(oem.st[f])), f"n {n}: {f} differs"
     _check_counters(out, oem, f"n {n}", True)
@@ -341,8 +283,8 @@ def _edge_case(name, W=None, mask=MASK, gest=0, id_lo=-N_OPT, id_hi=N_OPT, rules
     _select(ctx, st, W, clf, T0, K, flags, rules, out, mask=mask)
     torch.cuda.synchronize()
     orc = _oracle(name, N, 3, gest=gest)
-    oem = cm.OracleEmulator(orc, _oracle_state(st_np, m, N), W.cpu().numpy(), clf.cpu().numpy().reshape(N_VF, -1), mask, gest=gest,
-                            interrupt=bool(rules & INT))
+    oem = oracle_emulator(orc, oracle_state(st_np, m), W.cpu().numpy(), clf.cpu().numpy(), mask, gest=gest, best=True,
+                          interrupt=bool(rules & INT))
     oem.run(T0, K, begin_at=bool(flags & AT))
     for f in EnvState.FIELDS:
         a, b = getattr(st, f).cpu().numpy(), oem.st[f]
@@ -452,7 +394,7 @@ def test_c_abi_refusals_launch_nothing():
 
 def test_agent_evaluate_and_record_with_choose():
     a = crossing_agent(n_opt=N_OPT)
-    parents, clf = cm.sibling_tree(a.map)
+    parents, clf = sibling_tree(a.map)
     a.ctx.set_option_parents(parents)
     a.clf.copy_(dev(clf))
     for k in range(3, N_OPT + 1):

@@ -18,7 +18,7 @@ import torch
 import interrupt_learning_model as ilm
 from bits import assert_bits_equal
 from gpu_util import assert_state_equal, block_build, dev, make_pair, state_to_device
-from util import HP, chain_classifiers, make_oracle
+from util import HP, chain_classifiers, copy_state, crossing_weights, entry_state, make_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -37,14 +37,14 @@ def _reference(case):
         enabled, share = CASES[case]
         with block_build(B):
             orc, m = make_oracle("pinball_simple", N, n_options=2, seed=11, enabled_mask=enabled, n_threads=4, reoffer_period=1)
-            st0 = ilm.entry_state(m, N, 2, 72, share, HP["max_episode_steps"])
-            W0, clf = ilm.crossing_weights(3, 72), chain_classifiers(m, 2)
-            st, W, steps = ilm.copy_state(st0), W0.copy(), []
+            st0 = entry_state(m, N, 2, 72, share, HP["max_episode_steps"])
+            W0, clf = crossing_weights(3, 72), chain_classifiers(m, 2)
+            st, W, steps = copy_state(st0), W0.copy(), []
             for t in range(STEPS):
                 before = st["option_id"].copy()
                 G, n_k = orc.step(st, W, clf, 40 + t)
                 W_next = ilm.apply(orc, W, G, n_k)
-                steps.append((before, G, n_k, W_next, ilm.copy_state(st)))
+                steps.append((before, G, n_k, W_next, copy_state(st)))
                 W = W_next
         _REF[case] = (st0, W0, clf, steps)
     return _REF[case]

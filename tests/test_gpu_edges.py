@@ -13,6 +13,7 @@ import torch
 import interrupt_learning_model as ilm
 import sc_oracle
 import skill_chaining_with_graphs_amd as scg
+from acting_emulator import OracleBackend, oracle_emulator
 from bits import assert_bits_equal, is_neg_zero, is_subnormal
 from gpu_util import block_envs, current_block_envs, dev, host_state, state_to_device     # noqa: F401  (block_envs: the fixture)
 from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
@@ -315,33 +316,19 @@ def _assert_rows(tr, log, allow_nan, msg):
 @pytest.mark.parametrize("wname,make_w,free_nan", RO_WEIGHTS, ids=[w[0] for w in RO_WEIGHTS])
 def test_hip_rollout_edges_equal_the_oracle_step_loop(wname, make_w, free_nan, interrupt):
     """scg_rollout / scg_rollout_interrupt and their recording variant, 257 envs, 8 steps in one launch, with subnormal-scale and
-    overflowing weights, against the oracle's acting step loop (SPEC §11's interruption emulated from the oracle's q_values and
-    classifier_predict, as in tests/test_gpu_interrupt.py): state, qcache and the record's rows by bits."""
-    from test_gpu_interrupt import _candidates
+    overflowing weights, against the oracle's acting step loop (SPEC §11's interruption by tests/acting_emulator.py on the oracle,
+    as in tests/test_gpu_interrupt.py): state, qcache and the record's rows by bits."""
     ctx, orc, m, st_o, clf = _rollout_case()
     W = make_w()
-    n_vf, parents = 4, [0, 0, 1, 2]
+    n_vf = 4
     st_a, st_b = state_to_device(st_o, ctx), state_to_device(st_o, ctx)
     W_d, clf_d = dev(W).view(-1), dev(clf).view(-1)
-    ref_int = np.zeros((n_vf, N_RO), np.int64)
+    emu = oracle_emulator(orc, st_o, W, clf, MASK, interrupt=interrupt, v_option="qcache")   # W never applied: acting only
     log = []
     for t in range(T0_RO, T0_RO + K_RO):
-        o_b, s_b = st_o["option_id"].copy(), st_o["opt_steps"].copy()
-        orc.step(st_o, W, clf, t)                                              # W never applied: acting only
-        if interrupt:
-            kept = (o_b >= 1) & (o_b < n_vf) & (st_o["opt_steps"] == s_b + 1)
-            idx = np.nonzero(kept)[0]
-            if len(idx):
-                s = [np.ascontiguousarray(st_o[f][idx]) for f in ("x", "y", "vx", "vy")]
-                q0 = orc.q_values(*s, W[0])
-                cut = ~(ilm.vmax(st_o["qcache"][:, idx]) >= ilm.vmax(q0))
-                c = _candidates(lambda k, x, y: orc.classifier_predict(x, y, clf[k]), s[0][cut], s[1][cut], n_vf, MASK, MASK, parents)
-                e = idx[cut]
-                st_o["option_id"][e] = -c
-                st_o["opt_steps"][e] = 0
-                st_o["qcache"][:, e] = q0[:, cut]
-                np.add.at(ref_int, (o_b[e], e), 1)
+        emu.step(t)
         log.append({f: st_o[f].copy() for f in ("x", "y", "vx", "vy", "action", "reward", "done", "option_id")})
+    ref_int = emu.interrupts
     tr = Trajectory(N_RO, K_RO, 0, ctx.device)
     kw = {}
     if interrupt:
@@ -364,7 +351,7 @@ def test_hip_rollout_edges_equal_the_oracle_step_loop(wname, make_w, free_nan, i
 def test_hip_trial_edges_equal_the_oracle_step_loop(wname, make_w, free_nan):
     """scg_option_trials and its recording variant, 257 entries, options of 8 steps at the most, against the step loop on the
     oracle (tests/test_gpu_trials.py): every output by bits; the recorded launch gives the same outputs and the loop's rows."""
-    from test_gpu_trials import OUT, _OracleLoop, _loop_model, _starts
+    from test_gpu_trials import OUT, _loop_model, _starts
     m = scg.load_map("pinball_simple")
     kw = dict(HP, epsilon=0.3, max_option_steps=K_RO)
     ctx = ScgContext(N_RO, 3, m, device=0, seed=9, block_envs=256, **kw)
@@ -372,15 +359,14 @@ def test_hip_trial_edges_equal_the_oracle_step_loop(wname, make_w, free_nan):
     clf, W = chain_classifiers(m, 3), make_w()
     *s0, opt = _starts(m, N_RO, 3, seed=13)
 
-    class Logged(_OracleLoop):
+    class Logged(OracleBackend):
         def step(self, t):
-            h = super().step(t)
-            self.log.append(h)
-            return h
+            self.log.append({f: v.copy() for f, v in super().step(t).items()})
+            return self.log[-1]
 
-    loop = Logged(orc, W, clf, m, N_RO)
+    loop = Logged(orc, W, clf)
     loop.log = []
-    model, run = _loop_model(loop, s0, opt, 4, MASK, [0, 0, 1, 2], HP["r_option_success"], K_RO, HP["max_episode_steps"], T0_RO,
+    model, run = _loop_model(loop, m, s0, opt, 4, MASK, [0, 0, 1, 2], HP["r_option_success"], K_RO, HP["max_episode_steps"], T0_RO,
                              HP["gamma"])
     W_d, clf_d = dev(W).view(-1), dev(clf).view(-1)
     outs = []

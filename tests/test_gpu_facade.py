@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import option_rules as rules
 import sc_oracle
 from util import HP, SCALE, chain_classifiers, random_states, random_weights
 
@@ -71,16 +72,13 @@ def test_option_initiation_set_and_beta(agent, orc):
     done = np.where(goal == 1, 1, np.where(rng.random(N) < 0.05, 2, 0)).astype(np.uint8)
     steps = rng.integers(0, HP["max_option_steps"] + 2, N).astype(np.int32)
     clf = agent.clf.cpu().numpy()
-    inset = {k: orc.classifier_predict(x, y, clf[k]).astype(bool) for k in (1, 2)}
+    inset = rules.membership(lambda px, py, k: orc.classifier_predict(px, py, clf[k]), x, y, NOPT + 1, MASK)
     xd, yd = _dev(x), _dev(y)
     assert np.array_equal(agent.options[0].in_initiation_set(xd, yd).cpu().numpy(), np.ones(N, np.uint8))
     for k in (1, 2):
         assert np.array_equal(agent.options[k].in_initiation_set(xd, yd).cpu().numpy().astype(bool), inset[k])
-        # SPEC §4.2, restated on the oracle's classifier outputs
-        succ = goal.astype(bool) if k == 1 else inset[1]
-        fail = ~succ & ~inset[k]
-        otime = steps + 1 >= HP["max_option_steps"]
-        want = (done != 0) | succ | fail | otime
+        # SPEC §4.2 on the oracle's classifier outputs (the chain's parents: k -> k - 1)
+        want = rules.option_end(inset, goal, done, np.full(N, k), steps, [0, 0, 1], MASK, HP["max_option_steps"])["term"]
         got = agent.options[k].beta(xd, yd, goal=_dev(goal), done=_dev(done), opt_steps=_dev(steps))
         assert np.array_equal(got.cpu().numpy().astype(bool), want), k
     got0 = agent.options[0].beta(xd, yd, goal=_dev(goal), done=_dev(done))

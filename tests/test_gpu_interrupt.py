@@ -1,24 +1,23 @@
-"""SPEC §11 interrupting rollouts on the GPU: one scg_rollout_interrupt launch equals an emulator built from already-verified
-entry points (scg_rollout one step at a time, scg_q_values for V_0, scg_classifier_predict for the candidate), and the same
-emulator on the oracle; every launch geometry and block build agree; with every W_k == W_0 nothing is interrupted; the record
-marks interrupted rows INTERRUPTED; the agent's evaluate(interrupt=True) / record_episodes(interrupt=True) leave training
-alone; and the C-ABI's refusals."""
+"""SPEC §11 interrupting rollouts on the GPU: one scg_rollout_interrupt launch equals tests/acting_emulator.py's emulator on
+already-verified entry points (gpu_util.GpuBackend: scg_rollout_record one step at a time, scg_q_values for V_0,
+scg_classifier_predict for the candidate; V_o read from the option's qcache), and the same emulator on the oracle; every launch
+geometry and block build agree; with every W_k == W_0 nothing is interrupted; the record marks interrupted rows INTERRUPTED; the
+agent's evaluate(interrupt=True) / record_episodes(interrupt=True) leave training alone; and the C-ABI's refusals."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
-import interrupt_learning_model as ilm
-import sc_oracle
 import skill_chaining_with_graphs_amd as scg
+from acting_emulator import oracle_emulator
 from skill_chaining_with_graphs_amd import _lib
 from skill_chaining_with_graphs_amd.core import EnvState
 from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
 from skill_chaining_with_graphs_amd.trajectory import Trajectory
-from gpu_util import (as_bytes, assert_same_bits, clone_state, crossing_agent, dev, make_context, make_pair, spy_calls,
-                      state_to_device)
-from util import HP, chain_classifiers, random_env_state, random_states
+from gpu_util import (as_bytes, assert_same_bits, clone_state, crossing_agent, dev, gpu_emulator, make_context, make_pair,
+                      spy_calls, state_to_device)
+from util import HP, chain_classifiers, crossing_weights, oracle_state, random_env_state, wide_chain
 
 pytestmark = pytest.mark.gpu
 
@@ -28,90 +27,14 @@ STATS = EpisodeStats.FIELDS
 def _setup(name, n, n_opt, parents=None, gest=0, seed=3, block=None, **hp):
     m = scg.load_map(name)
     ctx = make_context(m, n, n_opt, block, parents, gest, seed, **hp)
-    clf = dev(ilm.wide_chain(m, n_opt)).view(-1)
-    W = dev(ilm.crossing_weights(n_opt + 1, seed)).view(-1)
+    clf = dev(wide_chain(m, n_opt)).view(-1)
+    W = dev(crossing_weights(n_opt + 1, seed)).view(-1)
     return ctx, m, W, clf
 
 
 def _state(ctx, m, n, n_opt, seed):
     return state_to_device(random_env_state(m, n, n_opt, seed, id_lo=-n_opt, id_hi=n_opt, opt_steps_hi=10,
                                             max_episode_steps=ctx.cfg.max_episode_steps), ctx)
-
-
-def _candidates(predict, x, y, n_vf, known, enabled, parents):
-    """SPEC §4.2's cand at s' = (x, y), by ilm.candidates from the known options' membership bits (no bit for the others)."""
-    in_n = np.zeros((n_vf, len(x)), bool)
-    for k in range(1, n_vf):
-        if (known >> k) & 1:
-            in_n[k] = predict(k, x, y) != 0
-    return ilm.candidates(in_n, enabled, parents, n_vf)
-
-
-class Emulator:
-    """SPEC §11 from scg_rollout_record launches of ONE step each (begin: a launch of 0 steps), patched after every step."""
-
-    def __init__(self, ctx, W, clf, mask, gest):
-        self.ctx, self.W, self.clf, self.mask = ctx, W, clf, mask
-        self.known = mask | gest
-        self.n, self.n_vf = ctx.n_envs, ctx.n_vf
-        self.parents = [int(p) for p in ctx.parents]
-        self.W0 = W.view(self.n_vf, -1)[0].contiguous()
-        self.W8 = clf.view(self.n_vf, -1)
-        self.kept = self.interrupted = 0
-        self.rows, self.lens = [], []              # per pseudo-step: the record's row (host) and len
-
-    def _predict(self, k, x, y):
-        return self.ctx.classifier_predict(dev(x), dev(y), self.W8[k].contiguous()).cpu().numpy()
-
-    def _launch(self, st, t, n_steps, stats, **kw):
-        tr = Trajectory(self.n, 1, 0, self.ctx.device)
-        self.ctx.rollout(st, self.W, self.clf, self.mask, t, n_steps, stats, record=tr, **kw)
-        return tr
-
-    def _keep_row(self, tr):
-        self.rows.append({f: getattr(tr, f)[0].cpu().numpy().copy() for f in tr.fields})
-        self.lens.append(tr.len.cpu().numpy().copy())
-
-    def run(self, st, t0, K, stats, interrupts, begin=False, begin_at=False, one_episode=False):
-        t = t0
-        if begin or begin_at:
-            self._keep_row(self._launch(st, t0, 0, stats, begin=begin, begin_at=begin_at, one_episode=one_episode))
-            t = t0 + 1
-        n_vf = self.n_vf
-        for j in range(K):
-            o_b, s_b = st.option_id.cpu().numpy(), st.opt_steps.cpu().numpy()
-            tr = self._launch(st, t + j, 1, stats, one_episode=one_episode)
-            row = {f: getattr(tr, f)[0].cpu().numpy().copy() for f in tr.fields}
-            s_a = st.opt_steps.cpu().numpy()
-            kept = (o_b >= 1) & (o_b < n_vf) & (s_a == s_b + 1)
-            idx = np.nonzero(kept)[0]
-            self.kept += len(idx)
-            if len(idx):
-                it = torch.as_tensor(idx, device=self.ctx.device)
-                s = [getattr(st, f)[it].contiguous() for f in ("x", "y", "vx", "vy")]
-                q0 = self.ctx.q_values(s, self.W0).cpu().numpy()
-                qo = st.qcache.view(5, self.n)[:, it].cpu().numpy()
-                cut = ~(ilm.vmax(qo) >= ilm.vmax(q0))
-                if cut.any():
-                    xs, ys = s[0].cpu().numpy(), s[1].cpu().numpy()
-                    c = _candidates(self._predict, xs[cut], ys[cut], n_vf, self.known, self.mask, self.parents)
-                    e = idx[cut]
-                    et = torch.as_tensor(e, device=self.ctx.device)
-                    st.option_id[et] = torch.as_tensor(-c.astype(np.int32), device=self.ctx.device)
-                    st.opt_steps[et] = 0
-                    qc = st.qcache.view(5, self.n)
-                    qc[:, et] = torch.as_tensor(q0[:, cut], device=self.ctx.device)
-                    np.add.at(interrupts, (o_b[e], e), 1)
-                    row["option_id"][e] = -c.astype(np.int8)
-                    row["term"][e] = _lib.ROLLOUT_TERM_INTERRUPTED
-                    self.interrupted += len(e)
-            self.rows.append(row)
-            self.lens.append(tr.len.cpu().numpy().copy())
-
-    def record(self):
-        """The rows a recorded launch of all these pseudo-steps holds: [rows][n] per field, and len."""
-        ln = np.sum(self.lens, axis=0)
-        return {f: np.stack([r[f] for r in self.rows]) for f in self.rows[0]}, ln
 
 
 CASES = [
@@ -132,20 +55,19 @@ def _run_case(name, n, n_opt, mask, gest, parents, eps, splits, mode, seed=3, t0
     twin = clone_state(st)
     n_vf = n_opt + 1
     s_ref, s_int = EpisodeStats(n_vf, n, ctx.device), EpisodeStats(n_vf, n, ctx.device)
-    ref_int = np.zeros((n_vf, n), np.int64)
-    emu = Emulator(ctx, W, clf, mask, gest)
     begin, at, one = mode == "begin", mode == "begin_at", mode in ("begin", "begin_at", "one_episode")
+    emu = gpu_emulator(ctx, st, W, clf, mask, gest, stats=s_ref, one_episode=one, interrupt=True, v_option="qcache")
     t = t0
     for i, K in enumerate(splits):
         first = i == 0
-        emu.run(st, t, K, s_ref, ref_int, begin=begin and first, begin_at=at and first, one_episode=one)
+        emu.run(t, K, begin=begin and first, begin_at=at and first)
         ctx.rollout(twin, W, clf, mask, t, K, s_int, begin=begin and first, begin_at=at and first, one_episode=one,
                     interrupt=True)
         t += K + (1 if (begin or at) and first else 0)
     torch.cuda.synchronize()
     assert_same_bits(twin, st, EnvState.FIELDS, f"{name} {mode}")
     assert_same_bits(s_int, s_ref, STATS, f"{name} {mode} stats")
-    assert np.array_equal(s_int.interrupts.cpu().numpy(), ref_int), f"{name} {mode}: interrupts differ"
+    assert np.array_equal(s_int.interrupts.cpu().numpy(), emu.interrupts), f"{name} {mode}: interrupts differ"
     assert emu.interrupted > 0 and emu.kept > emu.interrupted, \
         f"the case never interrupts, or never keeps an option (kept {emu.kept}, interrupted {emu.interrupted})"
     assert int(s_ref.entries.sum()) > 0, "the case never enters an option"
@@ -167,43 +89,21 @@ def test_interrupt_equals_oracle_emulator():
     n, n_opt, mask = 1000, 3, 0b1110
     ctx, orc, m = make_pair("pinball_simple", n, n_options=n_opt, seed=9, enabled_mask=mask, reoffer_period=4)
     clf = chain_classifiers(m, n_opt)
-    W = ilm.crossing_weights(n_opt + 1, 4)
+    W = crossing_weights(n_opt + 1, 4)
     n_vf = n_opt + 1
-    st_o = sc_oracle.new_state(n, m)
-    rng = np.random.default_rng(5)
-    st_o["x"][:], st_o["y"][:], st_o["vx"][:], st_o["vy"][:] = random_states(m, n, 5, vmax=1.5)
-    st_o["option_id"][:] = rng.integers(-n_opt, n_opt + 1, n)
-    st_o["opt_steps"][:] = rng.integers(0, 10, n)
-    st_o["ep_steps"][:] = rng.integers(0, HP["max_episode_steps"], n)
-    st_o["qcache"][:] = rng.standard_normal((5, n)).astype(np.float32)
+    st_o = oracle_state(random_env_state(m, n, n_opt, 5, id_lo=-n_opt, id_hi=n_opt, opt_steps_hi=10,
+                                         max_episode_steps=HP["max_episode_steps"]), m)
     st_d = state_to_device(st_o, ctx)
-    parents = [int(p) for p in ctx.parents]
-    ref_int = np.zeros((n_vf, n), np.int64)
-    K, t0, cuts = 20, 77, 0
-    for t in range(t0, t0 + K):
-        o_b, s_b = st_o["option_id"].copy(), st_o["opt_steps"].copy()
-        orc.step(st_o, W, clf, t)                          # W not applied: acting only
-        kept = (o_b >= 1) & (o_b < n_vf) & (st_o["opt_steps"] == s_b + 1)
-        idx = np.nonzero(kept)[0]
-        if not len(idx):
-            continue
-        s = [np.ascontiguousarray(st_o[f][idx]) for f in ("x", "y", "vx", "vy")]
-        q0 = orc.q_values(*s, W[0])
-        cut = ~(ilm.vmax(st_o["qcache"][:, idx]) >= ilm.vmax(q0))
-        c = _candidates(lambda k, x, y: orc.classifier_predict(x, y, clf[k]), s[0][cut], s[1][cut], n_vf, mask, mask, parents)
-        e = idx[cut]
-        st_o["option_id"][e] = -c
-        st_o["opt_steps"][e] = 0
-        st_o["qcache"][:, e] = q0[:, cut]
-        np.add.at(ref_int, (o_b[e], e), 1)
-        cuts += len(e)
+    K, t0 = 20, 77
+    emu = oracle_emulator(orc, st_o, W, clf, mask, interrupt=True, v_option="qcache")     # W not applied: acting only
+    emu.run(t0, K)
     intr = torch.zeros((n_vf, n), dtype=torch.int32, device=ctx.device)
     ctx.rollout(st_d, dev(W).view(-1), dev(clf).view(-1), mask, t0, K, interrupt=True, interrupts=intr)
     torch.cuda.synchronize()
-    assert cuts > 0
+    assert emu.interrupted > 0
     for f in EnvState.FIELDS:
         assert np.array_equal(as_bytes(getattr(st_d, f)), as_bytes(st_o[f])), f"oracle emulator: {f} differs"
-    assert np.array_equal(intr.cpu().numpy(), ref_int)
+    assert np.array_equal(intr.cpu().numpy(), emu.interrupts)
 
 
 def _interrupt_launch(name, n, n_opt, mask, block=None, W=None, seed=3, rec=False):
@@ -241,12 +141,16 @@ def test_ties_never_interrupt():
     ctx, m, W, clf = _setup("pinball_simple", n, n_opt, epsilon=0.1)
     Wt = W.view(n_opt + 1, -1)[0].repeat(n_opt + 1).contiguous()
     st = _state(ctx, m, n, n_opt, seed=21)
-    twin = clone_state(st)
+    twin, third = clone_state(st), clone_state(st)
     a, b = EpisodeStats(n_opt + 1, n, ctx.device), EpisodeStats(n_opt + 1, n, ctx.device)
     ctx.rollout(st, Wt, clf, mask, 40, 48, a, begin=True)
     ctx.rollout(twin, Wt, clf, mask, 40, 48, b, begin=True, interrupt=True)
+    emu = gpu_emulator(ctx, third, Wt, clf, mask, interrupt=True, v_option="qcache")    # the host rule holds a tie as well
+    emu.run(40, 48, begin=True)
     torch.cuda.synchronize()
     assert_same_bits(twin, st, EnvState.FIELDS, "ties")
+    assert_same_bits(third, st, EnvState.FIELDS, "ties, emulated")
+    assert emu.interrupted == 0 and emu.kept > 0
     assert_same_bits(b, a, STATS, "ties stats")
     assert int(b.interrupts.sum()) == 0 and b.summary()["interrupts"] == [0] * (n_opt + 1)
     assert int(a.vf_steps[1:].sum()) > 0, "no option ran: the tie check is vacuous"
@@ -258,12 +162,11 @@ def test_record_rows_equal_emulator(mode):
     ctx, m, W, clf = _setup("pinball_simple", n, n_opt, epsilon=0.1, reoffer_period=4, max_episode_steps=30)
     st = _state(ctx, m, n, n_opt, seed=31)
     twin, plain = clone_state(st), clone_state(st)
-    emu = Emulator(ctx, W, clf, mask, 0)
     s_ref, s_int, s_plain = (EpisodeStats(n_opt + 1, n, ctx.device) for _ in range(3))
-    ref_int = np.zeros((n_opt + 1, n), np.int64)
     one = mode == "one_episode"
     K = 40
-    emu.run(st, 9, K, s_ref, ref_int, begin=True, one_episode=one)
+    emu = gpu_emulator(ctx, st, W, clf, mask, stats=s_ref, one_episode=one, interrupt=True, v_option="qcache")
+    emu.run(9, K, begin=True)
     tr = Trajectory(n, K + 1, 0, ctx.device)
     ctx.rollout(twin, W, clf, mask, 9, K, s_int, begin=True, one_episode=one, interrupt=True, record=tr)
     ctx.rollout(plain, W, clf, mask, 9, K, s_plain, begin=True, one_episode=one, interrupt=True)
@@ -271,7 +174,7 @@ def test_record_rows_equal_emulator(mode):
     assert_same_bits(twin, st, EnvState.FIELDS, "recorded")
     assert_same_bits(plain, twin, EnvState.FIELDS, "recording changed the outputs")
     assert_same_bits(s_plain, s_int, STATS + ("interrupts",), "recording changed the counters")
-    assert np.array_equal(s_int.interrupts.cpu().numpy(), ref_int)
+    assert np.array_equal(s_int.interrupts.cpu().numpy(), emu.interrupts)
     rows, ln = emu.record()
     got_len = tr.len.cpu().numpy()
     assert np.array_equal(got_len, ln), "len"

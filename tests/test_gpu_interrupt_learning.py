@@ -12,7 +12,7 @@ from gpu_util import (as_bytes, assert_same_bits, block_build, clone_state, cros
 from ref64 import env_order_layout
 from skill_chaining_with_graphs_amd import ScgError
 from skill_chaining_with_graphs_amd.core import EnvState
-from util import HP
+from util import HP, crossing_weights, entry_state, wide_chain
 
 pytestmark = pytest.mark.gpu
 
@@ -31,11 +31,11 @@ def _setup(name, n, n_opt, block=None, seed=3, run_share=0.4, gest=0, same_w=Fal
     if gest:
         ctx.set_gestation(gest)
         orc.set_gestation(gest)
-    st = ilm.entry_state(m, n, n_opt, seed, run_share, HP["max_episode_steps"])
-    W = ilm.crossing_weights(n_vf, seed)
+    st = entry_state(m, n, n_opt, seed, run_share, HP["max_episode_steps"])
+    W = crossing_weights(n_vf, seed)
     if same_w:
         W[1:] = W[0]
-    return ctx, orc, m, st, W, ilm.wide_chain(m, n_opt), mask
+    return ctx, orc, m, st, W, wide_chain(m, n_opt), mask
 
 
 @pytest.mark.parametrize("block", [64, 128, 256])

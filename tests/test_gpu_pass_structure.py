@@ -14,11 +14,12 @@ import pytest
 import torch
 
 import interrupt_learning_model as ilm
+import option_rules as rules
 import sc_oracle
 from bits import assert_bits_equal
 from gpu_util import as_bytes, assert_same_bits, block_envs, dev, make_pair, state_to_device      # noqa: F401 (block_envs: a fixture)
 from ref64 import env_order_layout
-from util import disc_weights, random_states, random_weights
+from util import copy_state, crossing_weights, disc_weights, random_states, random_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -90,9 +91,9 @@ def _passes(pre, clf, orc, n_vf, B, gest, learn):
     not gestate and its envs are the block's position prefix (it shares the merged pass with the root); every other option with
     an update item in the block — an env running it, or (gestating) an env whose s lies in its set — takes a single pass."""
     oid = pre["option_id"].astype(np.int64)
-    o = np.where((oid >= 1) & (oid < n_vf), oid, 0)
-    perm = ilm.env_order(oid, n_vf, B)
-    in_s = {k: orc.classifier_predict(pre["x"], pre["y"], clf[k]) != 0 for k in range(1, n_vf)}
+    o = rules.vf_of(oid, n_vf)
+    perm = rules.env_order(oid, n_vf, B)
+    in_s = rules.membership(lambda x, y, k: orc.classifier_predict(x, y, clf[k]), pre["x"], pre["y"], n_vf, gest)   # (read where k gestates)
     blocks, block_of = [], np.zeros(len(o), np.int64)
     for b in range(0, len(perm), B):
         pos = perm[b:b + B]
@@ -117,11 +118,11 @@ def _reference(case, orc, m, n, B, interrupt=False, learn=True):
     n_vf = c["n_opt"] + 1
     clf = _clf(m, c["n_opt"])
     st = _seat(case, m, orc, n)
-    W = ilm.crossing_weights(n_vf, c["seed"])
+    W = crossing_weights(n_vf, c["seed"])
     orc.set_gestation(c["gest"])
     seen = dict(merged_only=0, kB_blocks=0, no_kB_blocks=0, one_single=0, two_singles=0, two_running=0, off_policy=0, accepted=0,
                 declined=0, accepted_single=0, declined_single=0, interrupted=0, interrupted_single=0, first=None)
-    out = [(ilm.copy_state(st), None, None, W)]
+    out = [(copy_state(st), None, None, W)]
     for t in range(STEPS):
         blocks, block_of = _passes(st, clf, orc, n_vf, B, c["gest"], learn)
         post, G, n_k, info = ilm.step(orc, st, W, clf, 50 + t, c["enabled"], gest=c["gest"], interrupt=interrupt, recompute=interrupt)

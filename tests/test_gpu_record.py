@@ -8,33 +8,21 @@ import numpy as np
 import pytest
 import torch
 
-import sc_oracle
+import option_rules as rules
 import skill_chaining_with_graphs_amd as scg
 from skill_chaining_with_graphs_amd import _lib
 from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
 from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
 from skill_chaining_with_graphs_amd.trajectory import Trajectory
 from skill_chaining_with_graphs_amd.trials import TrialResult
-from gpu_util import (as_bytes, assert_same_bits, clone_state, dev, gestating_agent, make_context, make_pair, named_map,
-                      spy_calls, state_to_device)
-from util import HP, chain_classifiers, random_env_state, random_states, random_weights
+from gpu_util import GpuBackend, as_bytes, assert_same_bits, clone_state, dev, gestating_agent, named_map, spy_calls
+from test_gpu_rollout import _oracle_case, _setup, _state
+from util import HP, chain_classifiers, random_states, random_weights
 
 pytestmark = pytest.mark.gpu
 
 STATS = EpisodeStats.FIELDS
 GUARD = 64
-
-
-def _setup(m, n, n_opt, block=None, parents=None, gest=0, seed=3, **hp):
-    ctx = make_context(m, n, n_opt, block, parents, gest, seed, **hp)
-    clf = dev(chain_classifiers(m, n_opt)).view(-1)
-    W = dev(random_weights(n_opt + 1, seed, std=0.1)).view(-1)
-    return ctx, W, clf
-
-
-def _state(ctx, m, n, n_opt, seed):
-    return state_to_device(random_env_state(m, n, n_opt, seed, id_lo=-n_opt - 1, id_hi=n_opt + 1, opt_steps_hi=20,
-                                            max_episode_steps=ctx.cfg.max_episode_steps), ctx)
 
 
 def _guarded(n, rows, first=0, sentinel=77):
@@ -77,24 +65,6 @@ CASES = [
 ]
 
 
-def _term_model(ctx, clf, known, parents, sp, goal, done, o, osteps):
-    """SPEC §4.2 / §9 on the host: the term of a step of value function o (numpy arrays over envs) into s' = sp."""
-    n_vf = ctx.n_vf
-    W8 = clf.view(n_vf, -1)
-    inA = np.zeros(len(o), np.int64)
-    for k in range(1, n_vf):
-        if (known >> k) & 1:
-            inA |= ctx.classifier_predict(sp[0], sp[1], W8[k].contiguous()).cpu().numpy().astype(np.int64) << k
-    p = np.asarray(parents, np.int64)[np.clip(o, 0, n_vf - 1)]
-    succ = np.where(p == 0, goal != 0, (inA >> p) & 1 == 1)
-    fail = ~succ & ((inA >> o) & 1 == 0)
-    otime = osteps + 1 >= ctx.cfg.max_option_steps
-    keep = ~((done != 0) | succ | fail | otime)
-    term = np.where(succ, 1, np.where(done != 0, 2, np.where(fail, 3, 4)))
-    term = np.where((o >= 1) & ~keep, term, 0)
-    return term, keep
-
-
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0]}-{c[1]}-o{c[2]}-b{c[9]}")
 def test_rows_equal_step_loop(case):
     name, n, n_opt, mask, gest, parents, reoffer, eps, base, block = case
@@ -106,30 +76,30 @@ def test_rows_equal_step_loop(case):
     tr = Trajectory(n, K, 0, ctx.device)
     ctx.rollout(st, W, clf, mask, t0, K, record=tr)
     known, par = mask | gest, [int(v) for v in ctx.parents]
+    B = GpuBackend(ctx, W, clf, mask)                          # (its physics and classifiers only: the loop is ctx.step's)
     rows = {f: getattr(tr, f).cpu().numpy() for f in tr.fields}
     assert np.array_equal(tr.len.cpu().numpy(), np.full(n, K, np.int32))
     ends = 0
     for j, t in enumerate(range(t0, t0 + K)):
-        s_before = [getattr(twin, f).clone() for f in ("x", "y", "vx", "vy")]
+        entry = [getattr(twin, f).cpu().numpy() for f in ("x", "y", "vx", "vy")]
         oid = twin.option_id.cpu().numpy()
-        osteps = twin.opt_steps.cpu().numpy().astype(np.int64)
-        o = np.where((oid >= 1) & (oid < ctx.n_vf), oid, 0).astype(np.int64)
+        osteps = twin.opt_steps.cpu().numpy()
         ctx.step(twin, W, clf, mask, t, learn=False)
-        act = twin.action.clone()
-        _, goal = ctx.pinball_step(s_before, act)          # s' of step j, before the reset
+        sp, _, goal = B.pinball(entry, twin.action.cpu().numpy())           # s' of step j, before the reset
         done = twin.done.cpu().numpy()
         ends += int((done != 0).sum())
-        for f, want in (("action", act), ("reward", twin.reward), ("done", twin.done), ("option_id", twin.option_id)):
+        for f, want in (("action", twin.action), ("reward", twin.reward), ("done", twin.done), ("option_id", twin.option_id)):
             got = rows[f][j]
             want = want.cpu().numpy().astype(got.dtype)
             assert np.array_equal(as_bytes(got), as_bytes(want)), f"row {j}: {f}"
-        for f, want in zip(("x", "y", "vx", "vy"), s_before):
+        for f, want in zip(("x", "y", "vx", "vy"), sp):
             assert np.array_equal(as_bytes(rows[f][j]), as_bytes(want)), f"row {j}: {f} is not s'"
-        assert np.array_equal(rows["vf"][j], o.astype(np.uint8)), f"row {j}: vf"
-        term, keep = _term_model(ctx, clf, known, par, s_before, goal.cpu().numpy(), done, o, osteps)
-        assert np.array_equal(rows["term"][j], term.astype(np.uint8)), f"row {j}: term"
-        on = o >= 1
-        assert np.array_equal(rows["term"][j][on] == 0, keep[on])
+        end = rules.option_end(rules.membership(B.predict, sp[0], sp[1], ctx.n_vf, known), goal, done, oid, osteps, par, known,
+                               ctx.cfg.max_option_steps)                    # SPEC §4.2 / §9: the term of a step into s'
+        assert np.array_equal(rows["vf"][j], end["o"].astype(np.uint8)), f"row {j}: vf"
+        assert np.array_equal(rows["term"][j], end["code"].astype(np.uint8)), f"row {j}: term"
+        on = end["o"] >= 1
+        assert np.array_equal(rows["term"][j][on] == 0, end["keep"][on])
     torch.cuda.synchronize()
     assert_same_bits(st, twin, EnvState.FIELDS, "recorded rollout vs step loop")
     assert ends > 0, "the case ends no episode"
@@ -138,17 +108,7 @@ def test_rows_equal_step_loop(case):
 
 
 def test_rows_equal_oracle_step_loop():
-    n, n_opt, mask = 257, 2, 0b110
-    ctx, orc, m = make_pair("pinball_simple", n, n_options=n_opt, seed=9, enabled_mask=mask)
-    clf = chain_classifiers(m, n_opt)
-    W = random_weights(n_opt + 1, 4, std=0.1)
-    st_o = sc_oracle.new_state(n, m)
-    rng = np.random.default_rng(5)
-    st_o["x"][:], st_o["y"][:], st_o["vx"][:], st_o["vy"][:] = random_states(m, n, 5, vmax=1.5)
-    st_o["option_id"][:] = rng.integers(-n_opt, n_opt + 1, n)
-    st_o["ep_steps"][:] = rng.integers(0, HP["max_episode_steps"], n)
-    st_o["qcache"][:] = rng.standard_normal((5, n)).astype(np.float32)
-    st_d = state_to_device(st_o, ctx)
+    ctx, orc, n, mask, clf, W, st_o, st_d = _oracle_case()
     K, t0 = 12, 77
     tr = Trajectory(n, K, 0, ctx.device)
     ctx.rollout(st_d, dev(W).view(-1), dev(clf).view(-1), mask, t0, K, record=tr)
@@ -273,21 +233,10 @@ def test_begin_at_selection_and_steps():
     sv = [getattr(st0, f) for f in ("x", "y", "vx", "vy")]
     Wv = W.view(ctx.n_vf, -1)
     q = [ctx.q_values(sv, Wv[k].contiguous()).cpu().numpy() for k in range(ctx.n_vf)]
-    W8 = clf.view(ctx.n_vf, -1)
-    inB = np.zeros(n, np.int64)
-    for k in range(1, ctx.n_vf):
-        if not (mask | gest) >> k & 1:
-            continue
-        inB |= ctx.classifier_predict(sv[0], sv[1], W8[k].contiguous()).cpu().numpy().astype(np.int64) << k
     par = [int(v) for v in ctx.parents]
-    cand = np.zeros(n, np.int64)
-    for i in range(n):
-        tgt = 0
-        for k in range(1, ctx.n_vf):
-            if par[k] != 0 and (inB[i] >> par[k]) & 1:
-                tgt |= 1 << k
-        sel = int(inB[i]) & ~tgt & mask
-        cand[i] = (sel & -sel).bit_length() - 1 if sel else 0
+    B = GpuBackend(ctx, W, clf, mask)
+    in_n = rules.membership(B.predict, sv[0].cpu().numpy(), sv[1].cpu().numpy(), ctx.n_vf, mask | gest)
+    cand = rules.candidates(in_n, mask, par, ctx.n_vf)
     mc = np.array([q[c][:, i].max() for i, c in enumerate(cand)], np.float32)
     m0 = q[0].max(axis=0)
     declined = (cand >= 1) & ~(mc >= m0)

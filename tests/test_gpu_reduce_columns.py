@@ -24,7 +24,7 @@ import interrupt_learning_model as ilm
 import test_gpu_reduce_sum as rs
 from bits import assert_bits_equal
 from gpu_util import assert_state_equal, block_build, dev, make_pair, state_to_device
-from util import chain_classifiers, make_oracle
+from util import chain_classifiers, copy_state, make_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -52,14 +52,14 @@ def _reference(case):
             orc, m = make_oracle("pinball_simple", n, n_options=n_opt, seed=7, enabled_mask=enabled, n_threads=8)
             st0 = make_state(m)
             W, clf = make_w(), chain_classifiers(m, n_opt)
-            st, steps = ilm.copy_state(st0), []
+            st, steps = copy_state(st0), []
             for t in range(STEPS):
                 cnt = rs._block_counts(st["option_id"], n_opt + 1)
                 with np.errstate(all="ignore"):
                     G, n_k = orc.step(st, W, clf, 20 + t)
                     W_next = ilm.apply(orc, W, G, n_k)
                 assert np.array_equal(cnt.sum(0), n_k), (case, t, cnt.sum(0), n_k)
-                steps.append((G, n_k, W_next, cnt, ilm.copy_state(st)))
+                steps.append((G, n_k, W_next, cnt, copy_state(st)))
                 W = W_next
         _REF[case] = (st0, make_w(), clf, steps)
     return _REF[case]

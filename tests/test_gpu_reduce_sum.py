@@ -17,9 +17,10 @@ import pytest
 import torch
 
 import interrupt_learning_model as ilm
+import option_rules as rules
 from bits import assert_bits_equal
 from gpu_util import block_build, dev, make_pair, state_to_device
-from util import HP, chain_classifiers, make_oracle, random_weights
+from util import HP, chain_classifiers, copy_state, crossing_weights, entry_state, make_oracle, random_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -35,8 +36,8 @@ def _n(nblk):
 def _block_counts(option_id, n_vf):
     """[nblk][n_vf] update items per block and value function, for the option ids at entry."""
     oid = np.asarray(option_id, np.int64)
-    perm = ilm.env_order(oid, n_vf, B)
-    o = np.where((oid >= 1) & (oid < n_vf), oid, 0)[perm]
+    perm = rules.env_order(oid, n_vf, B)
+    o = rules.vf_of(oid, n_vf)[perm]
     nblk = -(-len(o) // B)
     cnt = np.zeros((nblk, n_vf), np.int64)
     for b in range(nblk):
@@ -54,14 +55,14 @@ def _segments(cnt_k):
 
 def _mixed_ids(n, n_opt, seed):
     def make(m):
-        return ilm.entry_state(m, n, n_opt, seed, 0.4, HP["max_episode_steps"])
+        return entry_state(m, n, n_opt, seed, 0.4, HP["max_episode_steps"])
     return make
 
 
 def _seated_ids(n, n_opt, seed, runs):
     """`runs` = {option: envs running it}; every other env runs none. Env ids are shuffled over the seats."""
     def make(m):
-        st = ilm.entry_state(m, n, n_opt, seed, 0.0, HP["max_episode_steps"])
+        st = entry_state(m, n, n_opt, seed, 0.0, HP["max_episode_steps"])
         envs = np.random.default_rng(seed).permutation(n)
         st["option_id"][:] = 0
         lo = 0
@@ -74,7 +75,7 @@ def _seated_ids(n, n_opt, seed, runs):
 
 # name -> (n, n_options, enabled mask, entry state, weights)
 def _weights(n_vf, seed):
-    return lambda: ilm.crossing_weights(n_vf, seed)
+    return lambda: crossing_weights(n_vf, seed)
 
 
 def _overflow_weights():
@@ -104,7 +105,7 @@ def _reference(case):
             orc, m = make_oracle("pinball_simple", n, n_options=n_opt, seed=7, enabled_mask=enabled, n_threads=8)
             st0 = make_state(m)
             W, clf = make_w(), chain_classifiers(m, n_opt)
-            st, steps = ilm.copy_state(st0), []
+            st, steps = copy_state(st0), []
             for t in range(STEPS):
                 cnt = _block_counts(st["option_id"], n_opt + 1)
                 with np.errstate(all="ignore"):

@@ -7,7 +7,6 @@ import numpy as np
 import pytest
 import torch
 
-import interrupt_learning_model as ilm
 from gpu_util import block_build, block_envs, dev, host_state, state_to_device       # noqa: F401  (block_envs: the fixture)
 from ref64 import U32, compare, env_order_layout
 from skill_chaining_with_graphs_amd.core import EnvState, ScgContext
@@ -16,7 +15,7 @@ from skill_chaining_with_graphs_amd.trajectory import Trajectory
 from test_gpu_ref64 import GpuRunner
 from test_ref64_interrupt import EDGES, INT_SWEEP, MAX_EP, MAX_OPT, case_ids, interrupt_sweep_case, seat_running_envs
 from test_ref64_oracle import OracleRunner, assert_rarely_ambiguous, check_step, pre_state
-from util import HP, chain_classifiers, random_weights
+from util import HP, chain_classifiers, crossing_weights, random_weights, wide_chain
 
 pytestmark = pytest.mark.gpu
 
@@ -89,7 +88,7 @@ def test_chained_steps_on_one_device_state(chain, interrupt):
         seat_running_envs(r.map, pre, clf, r.model.parents, rng, share=0.8)
         enabled = 0b111110
         st = state_to_device({k: pre[k] for k in EnvState.FIELDS}, r.ctx)
-        W_d = dev(ilm.crossing_weights(nopt + 1, 31))
+        W_d = dev(crossing_weights(nopt + 1, 31))
         Wv, cv = W_d.view(-1), dev(clf).view(-1)
         n_amb = n_int = n_keep = 0
         layouts = []
@@ -169,11 +168,11 @@ def test_one_step_rollouts_match_the_float64_model(block, epw, interrupt, monkey
     r = OracleRunner("pinball_simple", n, nopt, seed=41, env_id_base=9, gest=gest, **hp)   # the model and its borrowed physics
     ctx = ScgContext(n, nopt, r.map, device=0, seed=41, env_id_base=9, block_envs=block, **hp)
     ctx.set_gestation(gest)
-    clf = ilm.wide_chain(r.map, nopt)
+    clf = wide_chain(r.map, nopt)
     rng = np.random.default_rng(block + epw)
     pre = pre_state(r.map, n, nopt, rng, max_ep=MAX_EP, max_opt=MAX_OPT)
     seat_running_envs(r.map, pre, clf, r.model.parents, rng, share=0.7)
-    W = ilm.crossing_weights(nopt + 1, 41)
+    W = crossing_weights(nopt + 1, 41)
     st = state_to_device({k: pre[k] for k in EnvState.FIELDS}, ctx)
     Wv, cv = dev(W).view(-1), dev(clf).view(-1)
     stats = EpisodeStats(nopt + 1, n, ctx.device)

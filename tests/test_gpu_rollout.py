@@ -6,11 +6,12 @@ import numpy as np
 import pytest
 import torch
 
+import option_rules as rules
 import sc_oracle
 import skill_chaining_with_graphs_amd as scg
 from skill_chaining_with_graphs_amd.core import EnvState
 from skill_chaining_with_graphs_amd.evaluation import EpisodeStats
-from gpu_util import (assert_same_bits, assert_state_equal, clone_state, dev, gestating_agent, host_state, make_context,
+from gpu_util import (GpuBackend, assert_same_bits, assert_state_equal, clone_state, dev, gestating_agent, host_state, make_context,
                       make_pair, named_map, spy_calls, state_to_device)
 from util import HP, chain_classifiers, dense_map, random_env_state, random_states, random_weights
 
@@ -129,21 +130,24 @@ def test_rollout_split_launches_and_block_builds():
     assert_same_bits(outs[1], outs[2], msg="block 128 vs 256")
 
 
-@pytest.mark.parametrize("epw", [None, 8, 32])
-def test_rollout_equals_oracle(epw, monkeypatch):
-    if epw:
-        monkeypatch.setenv("SCG_ROLLOUT_EPW", str(epw))
+def _oracle_case():
+    """257 envs on a context / oracle pair, two chain options, one running state on both sides."""
     n, n_opt, mask = 257, 2, 0b110
     ctx, orc, m = make_pair("pinball_simple", n, n_options=n_opt, seed=9, enabled_mask=mask)
-    clf = chain_classifiers(m, n_opt)
-    W = random_weights(n_opt + 1, 4, std=0.1)
     st_o = sc_oracle.new_state(n, m)
     rng = np.random.default_rng(5)
     st_o["x"][:], st_o["y"][:], st_o["vx"][:], st_o["vy"][:] = random_states(m, n, 5, vmax=1.5)
     st_o["option_id"][:] = rng.integers(-n_opt, n_opt + 1, n)
     st_o["ep_steps"][:] = rng.integers(0, HP["max_episode_steps"], n)
     st_o["qcache"][:] = rng.standard_normal((5, n)).astype(np.float32)
-    st_d = state_to_device(st_o, ctx)
+    return ctx, orc, n, mask, chain_classifiers(m, n_opt), random_weights(n_opt + 1, 4, std=0.1), st_o, state_to_device(st_o, ctx)
+
+
+@pytest.mark.parametrize("epw", [None, 8, 32])
+def test_rollout_equals_oracle(epw, monkeypatch):
+    if epw:
+        monkeypatch.setenv("SCG_ROLLOUT_EPW", str(epw))
+    ctx, orc, n, mask, clf, W, st_o, st_d = _oracle_case()
     K, t0 = 12, 77
     for t in range(t0, t0 + K):
         orc.step(st_o, W, clf, t)                          # W not applied: acting only
@@ -188,6 +192,7 @@ def _counter_model(ctx, st, W, clf, mask, gest, t0, K):
     ret_sum = np.zeros(n, np.float64)
     episodes, goals, len_sum = (np.zeros(n, np.int64) for _ in range(3))
     cols = np.arange(n)
+    B = GpuBackend(ctx, W, clf, mask)                          # (its classifiers only: the loop is ctx.step's)
     for t in range(t0, t0 + K):
         before = host_state(st)
         entry = [getattr(st, f).clone() for f in ("x", "y", "vx", "vy")]
@@ -196,7 +201,7 @@ def _counter_model(ctx, st, W, clf, mask, gest, t0, K):
         ctx.pinball_step(entry, st.action.clone())         # s' (before the reset) from the entry state and the action taken
         sx, sy = entry[0], entry[1]
         oid_b, oid_a = before["option_id"], after["option_id"]
-        o = np.where((oid_b >= 1) & (oid_b < n_vf), oid_b, 0)
+        o = rules.vf_of(oid_b, n_vf)
         np.add.at(c["vf_steps"], (o, cols), 1)
         dn = after["done"]
         ent = (oid_a >= 1) & (after["opt_steps"] == 0)
@@ -205,15 +210,9 @@ def _counter_model(ctx, st, W, clf, mask, gest, t0, K):
         decl = (oid_a < 0) & ~stay
         np.add.at(c["declines"], (np.maximum(-oid_a, 0), cols), decl.astype(np.int64))
         goal = dn == 1
-        for k in range(1, n_vf):
-            p = parents[k]
-            if p == 0:
-                succ = goal
-            elif (known >> p) & 1:
-                succ = ctx.classifier_predict(sx, sy, clf.view(n_vf, 8)[p].contiguous()).cpu().numpy().astype(bool)
-            else:
-                succ = np.zeros(n, bool)
-            c["successes"][k] += ((o == k) & succ).astype(np.int64)
+        end = rules.option_end(rules.membership(B.predict, sx.cpu().numpy(), sy.cpu().numpy(), n_vf, known), goal, dn, oid_b,
+                               before["opt_steps"], parents, known, ctx.cfg.max_option_steps)
+        np.add.at(c["successes"], (o, cols), (end["succ"] & (o >= 1)).astype(np.int64))
         r = ep_ret + after["reward"]
         rec = dn != 0
         episodes += rec; goals += goal; len_sum += np.where(rec, before["ep_steps"] + 1, 0)

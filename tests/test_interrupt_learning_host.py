@@ -9,9 +9,10 @@ import pytest
 
 import sc_oracle
 import interrupt_learning_model as ilm
+from acting_emulator import oracle_emulator
 from ref64 import env_order_layout
 from skill_chaining_with_graphs_amd.core import EnvState
-from util import HP, SCALE, oracle_block
+from util import HP, SCALE, copy_state, crossing_weights, entry_state, oracle_block, wide_chain
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -46,8 +47,8 @@ def _case(name, n, n_opt, block, seed, run_share, gest=0, layout=None):
     orc = sc_oracle.Oracle(m, SCALE, n_envs=n, n_options=n_opt, seed=seed, enabled_mask=mask, n_threads=4, reoffer_period=4, **HP)
     if gest:
         orc.set_gestation(gest)
-    st = ilm.entry_state(m, n, n_opt, seed, run_share, HP["max_episode_steps"])
-    return orc, m, st, ilm.crossing_weights(n_vf, seed), ilm.wide_chain(m, n_opt), mask
+    st = entry_state(m, n, n_opt, seed, run_share, HP["max_episode_steps"])
+    return orc, m, st, crossing_weights(n_vf, seed), wide_chain(m, n_opt), mask
 
 
 CASES = [
@@ -67,7 +68,7 @@ def test_emulator_reproduces_sco_step_without_interrupts(case):
         layout = env_order_layout(st["option_id"], orc.n_vf, case[3])
         assert layout == case[7]
         gest = case[6]
-        plain = ilm.copy_state(st)
+        plain = copy_state(st)
         G, n_k = orc.step(plain, W, clf, 11, mask)
         post, Ge, nke, info = ilm.step(orc, st, W, clf, 11, mask, gest=gest, interrupt=False, recompute=True)
         assert info["keep"].sum() > 0
@@ -81,35 +82,23 @@ def test_emulator_reproduces_sco_step_without_interrupts(case):
 
 def test_emulator_acting_equals_a_step_by_step_oracle_emulation_of_section_11():
     """The emulator's interrupted envs, found from the physics and the classifiers, against §11's rule applied to sco_step's outputs
-    the way the §11 tests do it: kept = opt_steps went up, V_o from the option's qcache, V_0 from q_values, c from the classifiers."""
+    the way the §11 tests do it (acting_emulator, v_option="qcache"): two derivations of each input of the rule.
+      keep   option_rules.option_end on s' (ilm.step)       against  option_rules.kept_by_counters: opt_steps went up;
+      V_o    sco_q_values of W_o at s_next (ilm.step)       against  the option's qcache as the plain step left it."""
     n, n_opt = 1500, 4
     orc, m, st, W, clf, mask = _case("pinball_simple", n, n_opt, 256, 7, 0.5)
-    n_vf = n_opt + 1
-    parents = [int(orc.p.parents[k]) for k in range(8)]
     total = 0
     for t in range(30, 34):
         post, G, n_k, info = ilm.step(orc, st, W, clf, t, mask, interrupt=True, recompute=False)
-        ref = ilm.copy_state(st)
-        orc.step(ref, W, clf, t, mask)
-        kept = (st["option_id"] >= 1) & (st["option_id"] < n_vf) & (ref["opt_steps"] == st["opt_steps"] + 1)
-        idx = np.nonzero(kept)[0]
-        s = [np.ascontiguousarray(ref[f][idx]) for f in ("x", "y", "vx", "vy")]
-        q0 = orc.q_values(*s, W[0])
-        cut = ~(ilm.vmax(ref["qcache"][:, idx]) >= ilm.vmax(q0))
-        in_n = np.zeros((8, len(idx)), bool)
-        for k in range(1, n_vf):
-            in_n[k] = orc.classifier_predict(s[0], s[1], clf[k]) != 0
-        c = ilm.candidates(in_n, mask, parents, n_vf)
-        e = idx[cut]
-        ref["option_id"][e] = -c[cut]
-        ref["opt_steps"][e] = 0
-        ref["qcache"][:, e] = q0[:, cut]
-        assert np.array_equal(np.nonzero(info["interrupted"])[0], e)
+        emu = oracle_emulator(orc, copy_state(st), W, clf, mask, interrupt=True, v_option="qcache")
+        _, cut = emu.step(t)
+        assert np.array_equal(info["keep"], emu.keep), f"t {t}: keep from the option's end and from the counters differ"
+        assert np.array_equal(info["interrupted"], cut)
         for f in EnvState.FIELDS:
-            assert np.array_equal(post[f].view(np.uint8), ref[f].view(np.uint8)), f"t {t}: {f}"
-        total += len(e)
+            assert np.array_equal(post[f].view(np.uint8), emu.st[f].view(np.uint8)), f"t {t}: {f}"
+        total += int(cut.sum())
         st = post
-    assert total > 0
+    assert total > 0 and emu.kept > emu.interrupted > 0
 
 
 def test_fmaf_is_fused():

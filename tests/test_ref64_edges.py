@@ -11,7 +11,7 @@ import pytest
 import sc_oracle
 import skill_chaining_with_graphs_amd as scg
 from bits import is_neg_zero, is_subnormal
-from interrupt_learning_model import env_order
+from option_rules import env_order
 from ref64 import C_PHI, Q_FLOOR, SUB, U32, fit_model, q_model, q_update_floor, q_update_model, sigmoid_model
 from test_ref64_oracle import OracleRunner, check_step, pre_state
 from util import HP, SCALE, chain_classifiers, fourier_reference, oracle_block, random_states, random_weights

@@ -14,7 +14,7 @@ import interrupt_learning_model as ilm
 import skill_chaining_with_graphs_amd as scg
 from ref64 import clf_model, compare, env_order_layout
 from test_ref64_oracle import SWEEP, OracleRunner, assert_rarely_ambiguous, check_step, pre_state, tree_classifiers
-from util import HP, chain_classifiers, disc_weights, oracle_block, random_weights
+from util import HP, chain_classifiers, crossing_weights, disc_weights, oracle_block, random_weights
 
 MAX_EP, MAX_OPT = HP["max_episode_steps"], HP["max_option_steps"]
 
@@ -134,7 +134,7 @@ def _check(r, pre, W, clf, enabled, n):
 def edge_ties_never_interrupt(make, n=512):
     """Every W_k == W_0: V_o and V_0 are the same sum in the same order, an exact tie, which keeps the option."""
     r, clf, pre = _edge(make, n, 3, 21)
-    W = ilm.crossing_weights(4, 21)
+    W = crossing_weights(4, 21)
     W[1:] = W[0]
     out, got, _ = _check(r, pre, W, clf, 0b1110, n)
     keep = out["keep"]
@@ -146,7 +146,7 @@ def edge_nan_option_weights_interrupt(make, n=512):
     """NaN in all of W_2: V_2 is NaN, so every env whose option 2 goes on is interrupted and takes the root's finite values; the
     other options' kept envs are decided by value."""
     r, clf, pre = _edge(make, n, 3, 22)
-    W = ilm.crossing_weights(4, 22)
+    W = crossing_weights(4, 22)
     W[2] = np.nan
     out, got, _ = _check(r, pre, W, clf, 0b1110, n)
     k2 = out["keep"] & (out["vf"] == 2)
@@ -159,7 +159,7 @@ def edge_nan_option_weights_interrupt(make, n=512):
 def edge_nan_root_weights_interrupt(make, n=512):
     """NaN in all of W_0: V_0 is NaN, so every option that goes on is interrupted (its qcache: the root's NaN values)."""
     r, clf, pre = _edge(make, n, 3, 23)
-    W = ilm.crossing_weights(4, 23)
+    W = crossing_weights(4, 23)
     W[0] = np.nan
     out, got, _ = _check(r, pre, W, clf, 0b1110, n)
     keep = out["keep"]
@@ -171,7 +171,7 @@ def edge_nan_root_action_is_passed_over(make, n=512):
     """NaN in one action row of W_0: Q_0(., 3) is NaN everywhere and V_0 is the maxNum of the other four, so kept envs are still
     decided by value; an interrupted env's qcache holds the root's NaN for action 3 only."""
     r, clf, pre = _edge(make, n, 3, 24)
-    W = ilm.crossing_weights(4, 24)
+    W = crossing_weights(4, 24)
     W[0, 3, 100] = np.nan
     out, got, _ = _check(r, pre, W, clf, 0b1110, n)
     cut = out["interrupted"]
@@ -192,7 +192,7 @@ def edge_candidate_kinds(make, n=768):
     clf[3] = disc_weights(cx, cy, 0.32)
     r, clf, pre = _edge(make, n, 3, 25, map_name="pinball_empty", clf=clf, ids=1 + np.arange(n) % 3, parents=[0, 0, 0, 0],
                         gest=0b1000)
-    W = ilm.crossing_weights(4, 25)
+    W = crossing_weights(4, 25)
     out, got, ok = _check(r, pre, W, clf, 0b0110, n)
     cut = out["interrupted"] & ok
     c, o = out["c"], out["vf"]
@@ -208,7 +208,7 @@ def edge_option_time_limit(make, n=512):
     r, clf, pre = _edge(make, n, 3, 26)
     last = np.arange(n) % 2 == 0
     pre["opt_steps"][:] = np.where(last, MAX_OPT - 1, MAX_OPT - 2)
-    W = ilm.crossing_weights(4, 26)
+    W = crossing_weights(4, 26)
     out, got, _ = _check(r, pre, W, clf, 0b1110, n)
     cut, keep = out["interrupted"], out["keep"]
     assert (last & (out["vf"] >= 1)).sum() >= 30 and not keep[last].any() and not cut[last].any()
@@ -222,7 +222,7 @@ def edge_disabled_and_gestating_ids(make, n=768):
     selected), so such envs write 0 or -1."""
     ids = np.array([1, 2, 3, -3, 0])[np.arange(n) % 5]
     r, clf, pre = _edge(make, n, 3, 27, ids=ids, gest=0b0100)
-    W = ilm.crossing_weights(4, 27)
+    W = crossing_weights(4, 27)
     out, got, _ = _check(r, pre, W, clf, 0b0010, n)
     cut, keep = out["interrupted"], out["keep"]
     o3, o2 = ids == 3, ids == 2
@@ -238,7 +238,7 @@ def edge_out_of_range_ids_never_interrupt(make, n=768):
     wild = np.array([33, 257, nopt + 1, -(nopt + 1), -40])
     ids = np.where(np.arange(n) % 3 == 0, wild[np.arange(n) % 5], 1 + np.arange(n) % 2)
     r, clf, pre = _edge(make, n, nopt, 28, ids=ids)
-    W = ilm.crossing_weights(nopt + 1, 28)
+    W = crossing_weights(nopt + 1, 28)
     out, got, _ = _check(r, pre, W, clf, 0b110, n)
     w = np.isin(ids, wild)
     assert not out["keep"][w].any() and not out["interrupted"][w].any() and (got["st"]["opt_steps"][w] == 0).all()
@@ -249,7 +249,7 @@ def edge_reoffer_every_step(make, n=512):
     """reoffer_period = 1: every step is a re-offer step and no env stays out, yet an interrupted env writes -c; the offer of c
     waits for its next step."""
     r, clf, pre = _edge(make, n, 3, 29, reoffer_period=1)
-    W = ilm.crossing_weights(4, 29)
+    W = crossing_weights(4, 29)
     out, got, ok = _check(r, pre, W, clf, 0b1110, n)
     cut = out["interrupted"] & ok & (out["c"] >= 1)
     assert cut.sum() >= 5 and not out["stay"].any()

@@ -1,8 +1,9 @@
 """The tests' rig, host side only (nothing here needs a device; tests/gpu_util.py holds the half that does).
 
 `oracle_block(b)` puts the oracle on its build for another SPEC §5 block size for a `with` body and back on the 256-env build
-after it. `make_oracle` is an oracle with the test hyper-parameters HP. `random_states`, `random_env_state`, `random_weights`
-and `chain_classifiers` are the seeded inputs the parity tests share: a test that needs "some running env batch" takes
+after it. `make_oracle` is an oracle with the test hyper-parameters HP. `random_states`, `random_env_state`, `entry_state`,
+`random_weights`, `crossing_weights` and the classifier layouts (`chain_classifiers`, `wide_chain`, `sibling_tree`) are the
+seeded inputs the parity tests share: a test that needs "some running env batch" takes
 random_env_state and uploads it with gpu_util.state_to_device. The maps below (dense, hub, edge-count, pocket) and the
 restatement of the HIP physics' candidate pruning serve the physics tests."""
 import contextlib
@@ -11,7 +12,7 @@ import numpy as np
 
 import sc_oracle
 import skill_chaining_with_graphs_amd as scg
-from skill_chaining_with_graphs_amd.core import fourier_scale_table
+from skill_chaining_with_graphs_amd.core import EnvState, fourier_scale_table
 
 SCALE = fourier_scale_table()
 HP = dict(gamma=0.99, alpha=1e-3, epsilon=0.1, r_option_success=100.0, max_episode_steps=60,
@@ -74,9 +75,67 @@ def chain_classifiers(m, n_options):
     return clf
 
 
+def wide_chain(m, n_opt):
+    """Nested discs round the goal, of radius 0.3 (option 1) up to 1.05 (the last option): options are entered everywhere."""
+    clf = np.zeros((n_opt + 1, 8), np.float32)
+    tx, ty, _ = m.target
+    for k in range(1, n_opt + 1):
+        clf[k] = disc_weights(tx, ty, 0.3 + 0.75 * (k - 1) / max(n_opt - 1, 1))
+    return clf
+
+
+SIBLING_PARENTS = [0, 0, 0, 1, 1, 2]
+
+
+def sibling_tree(m):
+    """(parents, clf [6][8]) of the sibling layout on map `m`: five discs whose initiation sets overlap, so that most states
+    have several candidates (SPEC §14). Options 1 and 2 lead to the goal, 3 and 4 into option 1, 5 into option 2; (tx, ty) the
+    target, s = +-1 pointing from it towards the map centre."""
+    tx, ty = float(m.target[0]), float(m.target[1])
+    sx, sy = (1.0 if tx < 0.5 else -1.0), (1.0 if ty < 0.5 else -1.0)
+    clf = np.zeros((6, 8), np.float32)
+    for k, (cx, cy, r) in enumerate([(tx, ty, 0.30), (tx + 0.10 * sx, ty + 0.10 * sy, 0.35), (0.5, 0.5, 0.45), (tx, 0.5, 0.50),
+                                     (0.5, 0.5, 0.75)], start=1):
+        clf[k] = disc_weights(cx, cy, r)
+    return list(SIBLING_PARENTS), clf
+
+
 def random_weights(n_vf, seed, std=1e-2):
     rng = np.random.default_rng(seed)
     return (rng.standard_normal((n_vf, 5, 1296)) * std).astype(np.float32)
+
+
+def crossing_weights(n_vf, seed, noise=0.05):
+    """Option weights of the root's scale plus noise: V_o and V_0 cross both ways."""
+    W = random_weights(n_vf, seed, std=0.1)
+    rng = np.random.default_rng(seed + 1000)
+    W[1:] = W[0] + (rng.standard_normal(W[1:].shape) * noise).astype(np.float32)
+    return W
+
+
+def entry_state(m, n, n_opt, seed, run_share, max_episode_steps):
+    """Random states; a share of the envs runs a random option, the others none or stay out of one (-k)."""
+    rng = np.random.default_rng(seed)
+    st = sc_oracle.new_state(n, m)
+    st["x"][:], st["y"][:], st["vx"][:], st["vy"][:] = random_states(m, n, seed, vmax=1.5)
+    run = rng.random(n) < run_share
+    st["option_id"][:] = np.where(run, rng.integers(1, n_opt + 1, n), -rng.integers(0, n_opt + 1, n))
+    st["opt_steps"][:] = rng.integers(0, 10, n)
+    st["ep_steps"][:] = rng.integers(0, max_episode_steps, n)
+    st["qcache"][:] = rng.standard_normal((5, n)).astype(np.float32)
+    return st
+
+
+def oracle_state(st_np, m):
+    """sc_oracle.new_state seated with a dict of arrays (random_env_state's)."""
+    st = sc_oracle.new_state(len(st_np["x"]), m)
+    for f, v in st_np.items():
+        st[f][...] = v
+    return st
+
+
+def copy_state(st):
+    return {f: np.array(st[f], copy=True) for f in EnvState.FIELDS}
 
 
 def fourier_reference(x, y, vx, vy):

@@ -36,9 +36,13 @@ def offer_shares(ag, traj):
     """(offers, those with |C| >= 2) over a recorded choose="value" evaluation. A row holds s' of its step (the begin row: the
     start state) and the ids written after it; a choice is made on every row that does not keep an option and does not end the
     episode (the begin row always), at that row's position. An offer is a choice with a candidate that is not a stay (§14)."""
+    import sys
     import numpy as np
     import torch
+    sys.path.append(os.path.join(rig.ROOT, "tests"))
+    from option_rules import candidate_mask, membership     # tests/: SPEC §4.2's membership bits and §14's candidate set on the host
     n_vf, mask, parents = ag.n_vf, ag.enabled_mask, [int(p) for p in ag.ctx.parents]
+    predict = lambda x, y, k: ag.ctx.classifier_predict(x, y, ag.clf[k].contiguous()).cpu().numpy()
     known = mask | ag.gest_mask
     period = int(ag.ctx.cfg.reoffer_period)
     offers = multi = 0
@@ -48,14 +52,8 @@ def offer_shares(ag, traj):
         if n == 0:
             continue
         x, y = (torch.as_tensor(r[f], device=ag.W.device) for f in ("x", "y"))
-        in_n = np.zeros((n_vf, n), bool)
-        for k in range(1, n_vf):
-            if (known >> k) & 1:
-                in_n[k] = ag.ctx.classifier_predict(x, y, ag.clf[k].contiguous()).cpu().numpy() != 0
-        C = np.zeros((n_vf, n), bool)
-        for k in range(1, n_vf):
-            if (mask >> k) & 1:
-                C[k] = in_n[k] & ~(in_n[parents[k]] if parents[k] else False)
+        in_n = membership(predict, x, y, n_vf, known)
+        C = candidate_mask(in_n, mask, parents, n_vf)
         j = np.arange(n)
         begin = j == 0
         choice = begin | (((r["vf"] == 0) | (r["term"] != 0)) & (r["done"] == 0))

@@ -5,7 +5,7 @@ import rig
 
 def main():
     import numpy as np
-    from interrupt_learning_model import env_order     # tests/: SPEC §5's env order on the host, perm[position] = env
+    from option_rules import env_order     # tests/: SPEC §5's env order on the host, perm[position] = env
     n=65536; nopt=5
     ag=rig.headline_agent(n,nopt,warm=200)
     key=lambda ids: np.where(ids>0,ids,0)               # SPEC §5: an env staying out of an option (a negative id) is keyed as the root's

@@ -12,7 +12,7 @@ def main():
     ap.add_argument("--options", type=int, default=5); ap.add_argument("--seed", type=int, default=1000)
     args = ap.parse_args()
     import numpy as np, torch
-    from interrupt_learning_model import env_order     # tests/: SPEC §5's env order on the host, order[position] = env
+    from option_rules import env_order     # tests/: SPEC §5's env order on the host, order[position] = env
     n, nopt = 65536, args.options
     _pad = torch.empty(args.pad_kb * 1024, dtype=torch.uint8, device="cuda") if args.pad_kb else None
     agent = rig.headline_agent(n, nopt, reset_seed=args.seed, warm=300, library=rig.timing_library("lite"))
