@@ -250,6 +250,41 @@ int scg_rollout_select(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, i
                        uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
                        const scg_record *rec, uint32_t rules, void *stream);
 
+/* ---- audited rollouts (SPEC §15): a forced first choice and the discounted TASK return, to check the value gate against ----
+ * scg_rollout_audit is scg_rollout_select (any `rules`) plus `audit`, a HOST struct of DEVICE pointers, each [N], any may be NULL.
+ * audit = NULL, or every member NULL, is scg_rollout_select: the same kernels, the same results.
+ * The begin pseudo-step (BEGIN or BEGIN_AT) only: with C the candidate set of the start state s0 (scg_rollout_select's C, for every
+ * `rules`) and f = force[e]: f = +k, k in C: env e is offered k and enters it whatever the gate says (option_id = k, qcache =
+ * Q_k(s0, .); entries[k] += 1; with SCG_SELECT_BEST overrides[k] += 1 when k != min C). f = -k, k in C: env e is offered k and declines
+ * it (option_id = -k, qcache = Q_0(s0, .); declines[k] += 1; k is offered again on §4.2's re-offer schedule). f = 0, |f| outside
+ * 1..n_options or |f| not in C (not enabled, gestating, s0 outside its set or inside its target): the unaudited choice. Every later
+ * step is scg_rollout_select's.
+ *   applied [N] uint8   1 where the force decided the begin choice, else 0           (written at the begin pseudo-step)
+ *   cand    [N] int8    the option offered at the begin pseudo-step after the force, 0: none          (likewise)
+ *   v_root  [N] float   max_a Q_0(s0, a), this launch's W, §5's max order                             (likewise)
+ *   v_cand  [N] float   max_a Q_cand(s0, a); written where cand >= 1 only
+ *   disc_ret, disc_g [N] float, in/out: the discounted task return d of the running episode and its discount g. BEGIN / BEGIN_AT
+ *           set d = 0, g = 1 (what the arrays hold is not read); every real step does d = d + g * reward, then g = g * gamma, each
+ *           product and sum rounded to binary32, no fma; reward is the env's reward (the record's `reward`), gamma the context's.
+ *   disc_final [N] float: on a step with done != 0, disc_final[e] = d, then d = 0, g = 1 (the last episode ended in the launch;
+ *           not written for an env no episode of which ended).
+ * An env skipped under ONE_EPISODE writes none of these. The write set is scg_rollout_select's plus the members given. Errors:
+ * scg_rollout_select's, and SCG_ERR_INVALID (nothing launched) for `force` without BEGIN or BEGIN_AT, and for disc_ret without
+ * disc_g or the reverse. Results do not depend on the launch geometry or the block build; the kernel talks to no other workgroup,
+ * so it raises no asynchronous failure bit. */
+typedef struct {
+    const int8_t *force;
+    uint8_t *applied;
+    int8_t *cand;
+    float *v_root, *v_cand;
+    float *disc_ret, *disc_g, *disc_final;
+} scg_audit;
+int scg_rollout_audit(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                      int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                      const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                      uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                      const scg_record *rec, uint32_t rules, const scg_audit *audit, void *stream);
+
 /* Device pointers of the ctx-owned reduced gradient G[n_vf][5][1296] and counts n_k[n_vf] (int32)
  * left by the last scg_step(LEARN) — the buffers a multi-rank caller all-reduces (SPEC §5). */
 int scg_grad_buffers(scg_ctx *ctx, float **G, int32_t **n_k);

@@ -23,9 +23,9 @@ def __getattr__(name):
     if name == "TrialResult":
         from .trials import TrialResult
         return TrialResult
-    if name == "EpisodeStats":
-        from .evaluation import EpisodeStats
-        return EpisodeStats
+    if name in ("EpisodeStats", "GateAudit"):
+        from . import evaluation
+        return getattr(evaluation, name)
     if name == "FourierBasis":
         from .fourier import FourierBasis
         return FourierBasis

@@ -114,6 +114,20 @@ class Record(C.Structure):
     ]
 
 
+class Audit(C.Structure):
+    """scg_audit: device pointers of SPEC §15's per-env audit arrays, each [N] (any NULL = not given / not written)."""
+    _fields_ = [
+        ("force", C.c_void_p),
+        ("applied", C.c_void_p),
+        ("cand", C.c_void_p),
+        ("v_root", C.c_void_p),
+        ("v_cand", C.c_void_p),
+        ("disc_ret", C.c_void_p),
+        ("disc_g", C.c_void_p),
+        ("disc_final", C.c_void_p),
+    ]
+
+
 _P = C.c_void_p
 # the arguments the rollout and the trial entry points start with; each appends its own tail (record, interrupt counts, stream)
 _ROLLOUT = [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(RolloutStats)]
@@ -134,6 +148,7 @@ _SIGS = {
     "scg_option_trials_record": (C.c_int, _TRIALS + [C.POINTER(Record), _P]),
     "scg_rollout_interrupt": (C.c_int, _ROLLOUT + [_P, C.POINTER(Record), _P]),
     "scg_rollout_select": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, _P]),
+    "scg_rollout_audit": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, C.POINTER(Audit), _P]),
     "scg_grad_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "scg_set_grad_buffers": (C.c_int, [_P, _P, _P]),
     "scg_apply_update": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -17,7 +17,7 @@ from . import _lib
 from . import dist as _dist
 from ._lib import CLF_STRIDE, NUM_ACTIONS, NUM_FEATURES, ScgError, auto_block_envs
 from .core import EnvState, ScgContext
-from .evaluation import EpisodeStats
+from .evaluation import EpisodeStats, GateAudit
 from .maps import PinballMap, load_map
 from .option import Option
 from .pinball import PinballDomain
@@ -456,7 +456,8 @@ class SkillChainingAgent:
         self.ctx.q_update(k, s, action, r, cont, s_next, self.W, apply=apply)
 
     def evaluate(self, n_episodes: int = 4096, epsilon: float = 0.0, seed: Optional[int] = None, steps_per_launch: int = 64,
-                 per_env: bool = False, states=None, interrupt: bool = False, choose: Optional[str] = None):
+                 per_env: bool = False, states=None, interrupt: bool = False, choose: Optional[str] = None,
+                 discounted: bool = False):
         """How good the current policy is: one episode per env on `n_episodes` envs of a separate evaluation context (cached per
         n_episodes; another seed replaces the entry), acting with `epsilon` and the current W, clf and enabled options, weights
         frozen (SPEC §8). Returns
@@ -472,8 +473,11 @@ class SkillChainingAgent:
         interrupting rollout); the summary then also holds interrupts per value function.
         With `choose="value"` an env is offered the candidate option whose value at the next state is highest instead of the
         lowest-numbered one (SPEC §14; ValueError for any other value); the summary then also holds overrides per option: the
-        entries of an option that was not the lowest-numbered candidate. It combines with `interrupt`."""
-        stats, _ = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt, choose=choose)
+        entries of an option that was not the lowest-numbered candidate. It combines with `interrupt`.
+        With `discounted` the launches also keep each episode's discounted task return (SPEC §15's audited rollout, nothing
+        forced): the summary then holds mean_discounted_return and the per-env dict disc_final. No other result changes."""
+        stats, _ = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt, choose=choose,
+                                       audit=True if discounted else None)
         out = stats.summary()
         return (out, stats.per_env()) if per_env else out
 
@@ -486,10 +490,13 @@ class SkillChainingAgent:
         stats, traj = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record=True, choose=choose)
         return traj, stats.summary()
 
-    def _eval_launches(self, n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record: bool = False, choose=None):
+    def _eval_launches(self, n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record: bool = False, choose=None,
+                       audit=None):
         """The launches of evaluate() / record_episodes() on the evaluation context for this episode count and seed, its settings
         copied from training (epsilon aside), stats zeroed and, with `states`, the start states written into its env state: the
-        first begins every episode at t0 = 0, launch i > 0 goes on at t0 = 1 + i * steps_per_launch. Returns (EpisodeStats, Trajectory or None)."""
+        first begins every episode at t0 = 0, launch i > 0 goes on at t0 = 1 + i * steps_per_launch. Returns (EpisodeStats, Trajectory or None).
+        `audit` (True: a new GateAudit without a force; or a force vector, one int8 per episode) makes every launch an audited one
+        (SPEC §15); the force acts in the first launch, and the GateAudit is left in stats.audit."""
         if choose not in (None, "value"):
             raise ValueError(f"choose must be None or 'value', not {choose!r}")
         if states is not None:
@@ -501,7 +508,26 @@ class SkillChainingAgent:
         if not (1 <= spl <= _lib.ROLLOUT_MAX_STEPS):
             raise ValueError(f"steps_per_launch must be in [1, {_lib.ROLLOUT_MAX_STEPS}]")
         c = self.ctx.cfg
-        seed = int(c.seed) if seed is None else int(seed)
+        ectx, st, stats = self._eval_context(n, epsilon, seed, states)
+        traj = Trajectory(n, spl + 1, 0, ectx.device, n_vf=self.n_vf) if record else None
+        kw = {}
+        if audit is not None:
+            stats.audit = GateAudit(n, ectx.device, force=None if audit is True else audit)
+            kw["audit"] = stats.audit
+        for i in range(-(-int(c.max_episode_steps) // spl)):
+            ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
+                         begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None),
+                         record=traj, interrupt=interrupt, choose=choose, **kw)
+            if audit is not None:
+                stats.audit.force = None                       # the force is the begin pseudo-step's alone
+            if record:
+                traj.append()
+        return stats, traj
+
+    def _eval_context(self, n: int, epsilon: float, seed: Optional[int], states):
+        """The evaluation context for `n` episodes and `seed` (None: training's), its settings copied from training (epsilon
+        aside), its stats zeroed and, with `states`, the start states written into its env state: (context, EnvState, EpisodeStats)."""
+        seed = int(self.ctx.cfg.seed) if seed is None else int(seed)
         # one evaluation context per n_episodes; the seed is a create-time setting, so another seed replaces that entry (a
         # caller sweeping seeds holds one context, not one per seed)
         cache = self._eval_ctx
@@ -517,14 +543,43 @@ class SkillChainingAgent:
         if states is not None:
             for dst, src in zip((st.x, st.y, st.vx, st.vy), states):
                 dst.copy_(src.to(dst.device))
-        traj = Trajectory(n, spl + 1, 0, ectx.device, n_vf=self.n_vf) if record else None
-        for i in range(-(-int(c.max_episode_steps) // spl)):
-            ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
-                         begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None),
-                         record=traj, interrupt=interrupt, choose=choose)
-            if record:
-                traj.append()
-        return stats, traj
+        return ectx, st, stats
+
+    def gate_audit(self, k: Optional[int] = None, states=None, n_states: int = 4096, epsilon: float = 0.0,
+                   seed: Optional[int] = None, interrupt: bool = False, choose: Optional[str] = None) -> dict:
+        """Does the value gate decide right (SPEC §15)? From every start state (`states` as for evaluate(); default: n_states
+        map.sample_free positions at rest) two episodes are run on the evaluation context, one FORCED to enter option k at the
+        start and one forced to decline it, with the same seed and step counters, so the same random numbers afterwards; with
+        epsilon = 0 the pair is deterministic. `k = None`: each state's own lowest-numbered candidate. States where k is no
+        candidate are left out. Returns GateAudit.pair_summary()'s dict ("overall", "options") plus "per_state": the kept
+        states' index, option, v_k, v_0, g_enter, g_decline, goal_enter, goal_decline (host arrays, state order). W, the
+        training state and t are untouched. `interrupt`, `choose`: the rules of every later step, as for evaluate()."""
+        if k is not None and not (1 <= int(k) <= self.n_options):
+            raise ValueError(f"k must be None or an option 1..{self.n_options}")
+        states = self._start_states(states, n_states, 0 if seed is None else int(seed))
+        n = states[0].numel()
+        run = lambda force, **kw: self._eval_launches(n, epsilon, seed, 64, states, interrupt, choose=choose, audit=force, **kw)[0]
+        if k is None:                                          # min C of each state: the option an unforced begin offers (§4.2)
+            ectx, st, _ = self._eval_context(n, epsilon, seed, states)
+            probe = GateAudit(n, ectx.device)
+            ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0, 0, None, begin_at=True, audit=probe)      # a 0-step begin launch
+            ks = probe.cand
+        else:
+            ks = torch.full((n,), int(k), dtype=torch.int8, device=self.W.device)
+        res = []
+        for sign in (1, -1):
+            stats = run(sign * ks)
+            res.append(dict(stats.audit.host(), goals=stats.goals.cpu().numpy().copy()))
+        ent, dec = res
+        keep = (ent["applied"] == 1) & (dec["applied"] == 1)
+        per = {"index": np.nonzero(keep)[0], "option": ent["cand"][keep].astype(np.int64),
+               "v_k": ent["v_cand"][keep], "v_0": ent["v_root"][keep],
+               "g_enter": ent["disc_final"][keep], "g_decline": dec["disc_final"][keep],
+               "goal_enter": ent["goals"][keep] > 0, "goal_decline": dec["goals"][keep] > 0}
+        out = GateAudit.pair_summary(per["option"], per["v_k"], per["v_0"], per["g_enter"], per["g_decline"],
+                                     per["goal_enter"], per["goal_decline"])
+        out["per_state"] = per
+        return out
 
     def _mirror_training(self, side: ScgContext, epsilon: float) -> None:
         """Copy the training run's settings into a side context (evaluation, trials): its hyper-parameters (epsilon aside),

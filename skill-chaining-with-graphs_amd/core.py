@@ -203,7 +203,7 @@ class ScgContext:
 
     def rollout(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, n_steps: int,
                 stats=None, begin: bool = False, one_episode: bool = False, record=None, begin_at: bool = False,
-                interrupt: bool = False, interrupts=None, choose: Optional[str] = None, overrides=None) -> None:
+                interrupt: bool = False, interrupts=None, choose: Optional[str] = None, overrides=None, audit=None) -> None:
         """SPEC §8: n_steps acting steps in ONE launch, bit for bit n_steps calls of step(learn=False) at t0 .. t0+n_steps-1
         (with `begin`: a new episode for every env at t0 first, the steps at t0+1 .. t0+n_steps). W is read, never written.
         `stats` (EpisodeStats of this context's n_vf and n_envs, on its device) receives the episode counters; `one_episode`
@@ -215,7 +215,10 @@ class ScgContext:
         (which then shows in stats.summary()).
         SPEC §14: `choose="value"` offers an env the candidate option of the highest value instead of the lowest-numbered one
         (scg_rollout_select, the only path that goes through it); `overrides` ([n_vf][n_envs] int32, in/out) counts the entries
-        of an option that was not the lowest-numbered candidate, by default into `stats.overrides` (created on demand)."""
+        of an option that was not the lowest-numbered candidate, by default into `stats.overrides` (created on demand).
+        SPEC §15: `audit` (a GateAudit of n_envs envs on this device) makes the launch an audited one (scg_rollout_audit, with the
+        rules `interrupt` and `choose` name): its `force`, where set, decides the begin pseudo-step's choice (begin or begin_at
+        only), and its arrays receive the begin choice, the values it compared and the discounted task return."""
         if choose not in (None, "value"):
             raise ValueError(f"rollout: choose must be None or 'value', not {choose!r}")
         self._chk_operands(st, W, clf)
@@ -262,7 +265,21 @@ class ScgContext:
                 _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done), _ptr(W), _ptr(clf), C.c_uint32(enabled_mask),
                 C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags), None if cs is None else C.byref(cs))
         rc_ref = None if rc is None else C.byref(rc)
-        if choose is not None:
+        if audit is not None:
+            if audit.n != N or audit.device != self.device:
+                raise ScgError(f"rollout: the audit is for {audit.n} envs on {audit.device}, the context has {N} on {self.device}")
+            if audit.force is not None and not (begin or begin_at):
+                raise ScgError("rollout: audit.force without begin or begin_at")
+            for f, dt in audit.DTYPES.items():
+                if getattr(audit, f) is not None:
+                    self._chk(getattr(audit, f), dt, N, "audit." + f)
+            au = audit.c_struct()
+            rules = (_lib.SELECT_BEST if choose is not None else 0) | (_lib.SELECT_INTERRUPT if interrupt else 0)
+            self._call("scg_rollout_audit", *head, None if interrupts is None else _ptr(interrupts),
+                       None if overrides is None else _ptr(overrides), rc_ref, C.c_uint32(rules), C.byref(au), self._stream())
+            if stats is not None and interrupt and interrupts is stats.interrupts:
+                stats.interrupting = True
+        elif choose is not None:
             rules = _lib.SELECT_BEST | (_lib.SELECT_INTERRUPT if interrupt else 0)
             self._call("scg_rollout_select", *head, None if interrupts is None else _ptr(interrupts),
                        None if overrides is None else _ptr(overrides), rc_ref, C.c_uint32(rules), self._stream())

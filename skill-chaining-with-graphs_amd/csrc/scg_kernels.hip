@@ -20,6 +20,7 @@
 // scg_record_kernels.hip is the second translation unit: rollout_kernel<true> / trial_kernel<true> (SPEC §10's per-step record) and
 // rollout_kernel on RolloutIntArgs / RolloutIntRecArgs (SPEC §11's interrupting rollout, without and with the record).
 // scg_select_kernels.hip is the third: rollout_kernel on RolloutBestArgs / RolloutBestIntArgs (SPEC §14's value-ranked choice).
+// scg_audit_kernels.hip is the fourth: rollout_kernel on RolloutAuditArgs<I, B> (SPEC §15's audited rollout).
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -56,6 +57,11 @@ __attribute__((visibility("hidden"))) hipError_t launch_rollout_interrupt_record
 // the value-ranking instantiations (SPEC §14), compiled and launched in scg_select_kernels.hip
 __attribute__((visibility("hidden"))) hipError_t launch_rollout_best(const RolloutBestArgs &A, int grid, hipStream_t s);
 __attribute__((visibility("hidden"))) hipError_t launch_rollout_best_interrupt(const RolloutBestIntArgs &A, int grid, hipStream_t s);
+// the audited instantiations (SPEC §15), compiled and launched in scg_audit_kernels.hip
+__attribute__((visibility("hidden"))) hipError_t launch_rollout_audit(const RolloutAuditArgs<false, false> &A, int grid, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_rollout_audit(const RolloutAuditArgs<true, false> &A, int grid, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_rollout_audit(const RolloutAuditArgs<false, true> &A, int grid, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_rollout_audit(const RolloutAuditArgs<true, true> &A, int grid, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -667,12 +673,14 @@ static Derived derived_args(const Base &base, Set set) {
 
 // scg_rollout, and scg_rollout_record (`fn` names the caller in error texts) with `rec` or `at` (BEGIN_AT, passed as BEGIN in
 // `flags`): the recording instantiation; scg_rollout_interrupt (`intr`): the interrupting ones, counting into `interrupts`;
-// scg_rollout_select with SCG_SELECT_BEST (`best`): the value-ranking ones (SPEC §14), counting into `overrides`
+// scg_rollout_select with SCG_SELECT_BEST (`best`): the value-ranking ones (SPEC §14), counting into `overrides`;
+// scg_rollout_audit with a member of `audit` given: the audited ones (SPEC §15), one per (intr, best)
 static int rollout_launch(const char *fn, scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
                           int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
                           const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
                           uint32_t flags, const scg_rollout_stats *stats, const scg_record *rec, bool at, void *stream,
-                          bool intr = false, int32_t *interrupts = nullptr, bool best = false, int32_t *overrides = nullptr) {
+                          bool intr = false, int32_t *interrupts = nullptr, bool best = false, int32_t *overrides = nullptr,
+                          const scg_audit *audit = nullptr) {
     if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
     if (!c->have_map) return fail_in(c, SCG_ERR_STATE, fn, "scg_set_map has not been called");
     if (!x || !y || !vx || !vy || !option_id || !opt_steps || !ep_steps || !qcache || !action || !reward ||
@@ -689,6 +697,10 @@ static int rollout_launch(const char *fn, scg_ctx *c, float *x, float *y, float 
         const int rc = check_record(c, fn, rec, c->cfg.n_envs, (long long)n_steps + ((flags & SCG_ROLLOUT_BEGIN) ? 1 : 0));
         if (rc != SCG_OK) return rc;
     }
+    if (audit && audit->force && !(flags & SCG_ROLLOUT_BEGIN))
+        return fail_in(c, SCG_ERR_INVALID, fn, "audit->force without SCG_ROLLOUT_BEGIN or _BEGIN_AT");
+    if (audit && !audit->disc_ret != !audit->disc_g)
+        return fail_in(c, SCG_ERR_INVALID, fn, "audit->disc_ret and audit->disc_g go together");
     SCG_CHECK_ASYNC(c);
     DeviceGuard dev_guard_(c->cfg.device);
     if (!dev_guard_.ok) return fail_in(c, SCG_ERR_HIP, fn, "cannot make the context's device current");
@@ -705,7 +717,17 @@ static int rollout_launch(const char *fn, scg_ctx *c, float *x, float *y, float 
     R.epw = epw;
     const int grid = (c->cfg.n_envs + RO_WAVES * epw - 1) / (RO_WAVES * epw);
     c->order_valid = false;                               // the ids change under the step's prepared env order
-    if (best) {
+    if (audit) {
+        const auto fill = [&](auto &D) {
+            if (rec) D.rec = *rec;
+            D.begin_at = at ? 1u : 0u; D.interrupts = interrupts; D.overrides = overrides; D.au = *audit; D.gamma = c->cfg.gamma;
+        };
+        const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        if (best && intr) SCG_HIP(c, launch_rollout_audit(derived_args<RolloutAuditArgs<true, true>>(R, fill), grid, s));
+        else if (best) SCG_HIP(c, launch_rollout_audit(derived_args<RolloutAuditArgs<false, true>>(R, fill), grid, s));
+        else if (intr) SCG_HIP(c, launch_rollout_audit(derived_args<RolloutAuditArgs<true, false>>(R, fill), grid, s));
+        else SCG_HIP(c, launch_rollout_audit(derived_args<RolloutAuditArgs<false, false>>(R, fill), grid, s));
+    } else if (best) {
         const auto fill = [&](auto &D) { if (rec) D.rec = *rec; D.begin_at = at ? 1u : 0u; D.interrupts = interrupts; D.overrides = overrides; };
         if (intr) SCG_HIP(c, launch_rollout_best_interrupt(derived_args<RolloutBestIntArgs>(R, fill), grid, reinterpret_cast<hipStream_t>(stream)));
         else SCG_HIP(c, launch_rollout_best(derived_args<RolloutBestArgs>(R, fill), grid, reinterpret_cast<hipStream_t>(stream)));
@@ -778,6 +800,25 @@ int scg_rollout_select(scg_ctx *c, float *x, float *y, float *vx, float *vy, int
     return rollout_launch("scg_rollout_select", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done,
                           W, clf, enabled_mask, t0, n_steps, flags, stats, rec, at, stream, intr, intr ? interrupts : nullptr,
                           best, best ? overrides : nullptr);
+}
+
+// audit = NULL, or every member NULL: scg_rollout_select's launch, under this entry point's name in error texts
+int scg_rollout_audit(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                      int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                      const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                      uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                      const scg_record *rec, uint32_t rules, const scg_audit *audit, void *stream) {
+    if (c && (rules & ~(SCG_SELECT_INTERRUPT | SCG_SELECT_BEST)))
+        return fail_in(c, SCG_ERR_INVALID, "scg_rollout_audit", "unknown rule");
+    const bool intr = (rules & SCG_SELECT_INTERRUPT) != 0, best = (rules & SCG_SELECT_BEST) != 0;
+    if (audit && !audit->force && !audit->applied && !audit->cand && !audit->v_root && !audit->v_cand && !audit->disc_ret &&
+        !audit->disc_g && !audit->disc_final)
+        audit = nullptr;
+    bool at;
+    if (const int rc = begin_at_flags(c, "scg_rollout_audit", flags, at)) return rc;
+    return rollout_launch("scg_rollout_audit", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done,
+                          W, clf, enabled_mask, t0, n_steps, flags, stats, rec, at, stream, intr, intr ? interrupts : nullptr,
+                          best, best ? overrides : nullptr, audit);
 }
 
 static int trials_launch(const char *fn, scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,

@@ -39,6 +39,7 @@ struct RolloutArgs {
     MapScalars ms;
     static constexpr bool INT = false;   // SPEC §11's interruption: a compile-time flag of the argument type (kernel symbols unchanged)
     static constexpr bool BEST = false;  // SPEC §14's value-ranked choice: likewise
+    static constexpr bool AUDIT = false; // SPEC §15's forced first choice and discounted return: likewise
 };
 // the recording instantiation's arguments (SPEC §10): RolloutArgs at offset 0, so the exit's re-read holds for both
 struct RolloutRecArgs : RolloutArgs {
@@ -66,6 +67,17 @@ struct RolloutBestIntArgs : RolloutRecArgs {
     int32_t *interrupts;
     int32_t *overrides;
 };
+// the audited instantiations' arguments (SPEC §15; scg_rollout_audit), one per `rules` of scg_rollout_select, always with the record
+template <bool I, bool B>
+struct RolloutAuditArgs : RolloutRecArgs {
+    static constexpr bool INT = I;
+    static constexpr bool BEST = B;
+    static constexpr bool AUDIT = true;
+    int32_t *interrupts;           // (not counted without INT)
+    int32_t *overrides;            // (not counted without BEST)
+    scg_audit au;                  // device pointers, any may be null
+    float gamma;
+};
 
 // per-VF counters of one launch, six 16-bit fields in three words (a launch takes at most 1 + SCG_ROLLOUT_MAX_STEPS steps)
 struct Ctr16 {
@@ -88,10 +100,12 @@ static_assert(SCG_ROLLOUT_MAX_STEPS + 1 < 65536, "16-bit launch counters");
 // record's window, and BEGIN_AT (scg_rollout_record). <false, RolloutIntArgs> / <true, RolloutIntRecArgs>: the same with
 // SPEC §11's interruption (scg_rollout_interrupt); INT = Args::INT. <true, RolloutBestArgs> / <true, RolloutBestIntArgs>: SPEC §14's
 // value-ranked choice (scg_rollout_select), BEST = Args::BEST: an offered env is evaluated under every candidate's value function
-// and the root's, the Q of VF k in slot k of s_qv (root: slot 0), and phase G enters the candidate whose value is highest
+// and the root's, the Q of VF k in slot k of s_qv (root: slot 0), and phase G enters the candidate whose value is highest.
+// <true, RolloutAuditArgs<I, B>>: SPEC §15's audited rollout (scg_rollout_audit), AUDIT = Args::AUDIT: the begin pseudo-step's
+// choice may be forced per env, and the discounted task return is kept in two more registers across the steps
 template <bool REC, typename Args>
 __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
-    constexpr bool INT = Args::INT, BEST = Args::BEST;
+    constexpr bool INT = Args::INT, BEST = Args::BEST, AUDIT = Args::AUDIT;
     constexpr int QV_SLOTS = BEST ? MAX_VF : 2;               // BEST: one slot per value function
     constexpr int QV_ROOT = BEST ? 0 : 1;                     // the slot of the root's Q beside the running VF's
     __shared__ __attribute__((aligned(16))) float s_w0[W_FLOATS];                 // W_0 in A-operand order (stage_w_cold's layout)
@@ -119,6 +133,11 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
     Ctr16 c_vf = {{0u, 0u, 0u}}, c_en = {{0u, 0u, 0u}}, c_de = {{0u, 0u, 0u}}, c_su = {{0u, 0u, 0u}};
     Ctr16 c_in = {{0u, 0u, 0u}};                               // INT: interrupted steps per option
     Ctr16 c_ov = {{0u, 0u, 0u}};                               // BEST: entries of an option that is not min C
+    float dsc = 0.0f, dg = 1.0f, dfin = 0.0f;                  // AUDIT: §15's d and g of the running episode; d of the last ended one
+    bool have_fin = false;
+    if constexpr (AUDIT) {
+        if (mine && !A.begin && A.au.disc_ret) { dsc = A.au.disc_ret[e]; dg = A.au.disc_g[e]; }
+    }
     if (mine) {
         sx = A.x[e]; sy = A.y[e]; svx = A.vx[e]; svy = A.vy[e];
 #pragma unroll
@@ -181,6 +200,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         int cand = 0, on = 0, stay = 0, term = 0;
         int ic = 0;                                            // INT: §4.2's cand of a keeping env, as if its option had ended
         unsigned cset = 0;                                     // BEST: the candidate set C of an env that is not keeping
+        int fk = 0, amin = 0;                                  // AUDIT: the force that applies (+k / -k, 0: none) and min C beside it
         if (valid) {
             dn = is_begin ? 2 : episode_end(goal, eps1, A.max_ep);
             if (dn && !(REC && is_begin && kernel_args<RolloutRecArgs>()->begin_at)) restart_state(u[2], A.starts, A.ms.n_starts, nx, ny, nvx, nvy);
@@ -200,6 +220,16 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
                 if (stay) cand = stay;
             } else {
                 stay = reoffer_stay(keep, cand, dn, is_begin ? 0 : oid, t, gid, A.reoffer_mask);
+            }
+            if constexpr (AUDIT) {                             // SPEC §15: the begin choice forced to a member of C (begin: stay = 0)
+                if (is_begin && A.au.force) {
+                    const int f = A.au.force[e], k = f < 0 ? -f : f;
+                    const unsigned C = BEST ? cset : candidate_mask(A.parents, inB, A.enabled);
+                    if (k >= 1 && k < A.n_vf && ((C >> k) & 1u)) {
+                        fk = f; amin = cand; cand = k;
+                        if constexpr (BEST) cset = 1u << k;    // phase E's lists: Q_k and Q_0 of this env, no other
+                    }
+                }
             }
             on = stay ? 0 : cand;
             store_z1(s_z1[il], nx, ny, nvx, nvy);
@@ -300,6 +330,16 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
 #pragma unroll
                 for (int aa = 0; aa < NACT; ++aa) q0[aa] = s_qv[QV_ROOT][aa][il];
                 declined = !gate_holds(qa, q0);
+                if constexpr (AUDIT) {
+                    if (is_begin) {                            // SPEC §15's begin outputs, from the values the gate reads
+                        const scg_audit U = kernel_args<Args>()->au;
+                        float v = qa[0];
+#pragma unroll
+                        for (int aa = 1; aa < NACT; ++aa) v = fmaxf(v, qa[aa]);
+                        if (U.v_cand) U.v_cand[e] = v;
+                    }
+                    if (fk) declined = fk < 0;                 // the force replaces the gate's result
+                }
                 if (declined) {
 #pragma unroll
                     for (int aa = 0; aa < NACT; ++aa) qa[aa] = q0[aa];
@@ -331,11 +371,28 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
             eps = dn ? 0 : eps1;
             c_en.add(cand, entering && !declined);
             c_de.add(cand, declined);
+            if constexpr (AUDIT) {
+                if (fk) minc = amin;                           // a forced entry overrides where k != min C
+                if (is_begin) {
+                    const scg_audit U = kernel_args<Args>()->au;
+                    float v = s_qv[entering ? QV_ROOT : 0][0][il];
+#pragma unroll
+                    for (int aa = 1; aa < NACT; ++aa) v = fmaxf(v, s_qv[entering ? QV_ROOT : 0][aa][il]);
+                    if (U.v_root) U.v_root[e] = v;
+                    if (U.cand) U.cand[e] = (int8_t)(entering ? cand : 0);
+                    if (U.applied) U.applied[e] = fk ? 1 : 0;
+                }
+            }
             if constexpr (BEST) c_ov.add(cand, entering && !declined && cand != minc);
             if (!is_begin) {
                 last_a = a; last_r = rew; last_dn = dn;
                 c_vf.add(o, true);
                 c_su.add(o, o >= 1 && succ);
+                if constexpr (AUDIT) {                         // SPEC §15: d += g * reward, g *= gamma, each rounded, no fma
+                    dsc = __fadd_rn(dsc, __fmul_rn(dg, rew));
+                    dg = __fmul_rn(dg, A.gamma);
+                    if (dn) { dfin = dsc; have_fin = true; dsc = 0.0f; dg = 1.0f; }
+                }
                 const float r = ep_ret + rew;
                 if (dn) {
                     episodes += 1; goals += dn == 1 ? 1 : 0; len_sum += eps1;
@@ -349,6 +406,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
             } else {
                 ep_ret = 0.0f;
                 finished = false;
+                if constexpr (AUDIT) { dsc = 0.0f; dg = 1.0f; }
             }
             if constexpr (REC) {                                 // SPEC §10's row j of this env
                 if (rr >= 0) {
@@ -398,6 +456,11 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         int32_t *const I = kernel_args<Args>()->interrupts;
         if (I)
             for (int k = 0; k < K->n_vf; ++k) I[(size_t)k * N + e] += c_in.get(k);
+    }
+    if constexpr (AUDIT) {
+        const scg_audit U = kernel_args<Args>()->au;
+        if (U.disc_ret) { U.disc_ret[e] = dsc; U.disc_g[e] = dg; }
+        if (U.disc_final && have_fin) U.disc_final[e] = dfin;
     }
     if constexpr (BEST) {
         int32_t *const O = kernel_args<Args>()->overrides;

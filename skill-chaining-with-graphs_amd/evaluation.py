@@ -1,5 +1,6 @@
 """EpisodeStats — the per-env counters of an acting rollout (SPEC §8, scg_rollout; §11, scg_rollout_interrupt) and their
-host-side summary."""
+host-side summary; GateAudit — the per-env arrays of an audited rollout (SPEC §15, scg_rollout_audit) and the summary of an
+enter / decline pair of them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -7,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import RolloutStats
+from ._lib import Audit, RolloutStats
 
 
 class EpisodeStats:
@@ -33,6 +34,7 @@ class EpisodeStats:
         self.interrupts = z((n_vf, n), torch.int32)
         self.interrupting = False
         self.overrides = None          # [n_vf][n] int32 (SPEC §14), created by want_overrides(): a value-ranking rollout asks
+        self.audit = None              # the GateAudit of an audited evaluation (SPEC §15): its disc_final shows in per_env()
 
     def want_overrides(self) -> torch.Tensor:
         """The `overrides` counters of a value-ranking rollout (SPEC §14), created zeroed on first use; from then on they show in
@@ -51,6 +53,7 @@ class EpisodeStats:
         self.interrupts.zero_()
         self.interrupting = False
         self.overrides = None
+        self.audit = None
         return self
 
     def c_struct(self) -> RolloutStats:
@@ -63,6 +66,8 @@ class EpisodeStats:
             out["interrupts"] = self.interrupts
         if self.overrides is not None:
             out["overrides"] = self.overrides
+        if self.audit is not None:
+            out["disc_final"] = self.audit.disc_final
         return out
 
     def summary(self) -> dict:
@@ -93,4 +98,78 @@ class EpisodeStats:
             out["interrupts"] = [int(v) for v in self.interrupts.detach().cpu().numpy().astype(np.int64).sum(axis=1)]
         if self.overrides is not None:
             out["overrides"] = [int(v) for v in self.overrides.detach().cpu().numpy().astype(np.int64).sum(axis=1)]
+        if self.audit is not None:
+            d = self.audit.disc_final.detach().cpu().numpy().astype(np.float64)[host["episodes"] > 0]
+            out["mean_discounted_return"] = float(np.cumsum(d)[-1]) / d.size if d.size else nan
         return out
+
+
+def _mean(v) -> float:
+    """The float64 mean of `v` summed in order (NaN for none)."""
+    v = np.asarray(v, np.float64)
+    return float(np.cumsum(v)[-1]) / v.size if v.size else float("nan")
+
+
+class GateAudit:
+    """The per-env arrays of an audited rollout (SPEC §15) for `n` envs: `force` (int8; +k: enter option k at the begin
+    pseudo-step, -k: decline it, 0: the gate's own choice; None: not given), and the outputs applied (uint8), cand (int8), v_root,
+    v_cand, disc_ret, disc_g, disc_final (float32; v_cand and disc_final start as NaN: written only where a candidate was offered /
+    an episode ended). disc_ret and disc_g are in/out across the launches of one evaluation."""
+
+    DTYPES = {"force": torch.int8, "applied": torch.uint8, "cand": torch.int8, "v_root": torch.float32, "v_cand": torch.float32,
+              "disc_ret": torch.float32, "disc_g": torch.float32, "disc_final": torch.float32}
+
+    def __init__(self, n: int, device="cpu", force=None):
+        self.n = int(n)
+        dev = torch.device(device)
+        self.force = None if force is None else torch.as_tensor(force, dtype=torch.int8).to(dev).contiguous().view(-1)
+        if self.force is not None and self.force.numel() != self.n:
+            raise ValueError(f"force has {self.force.numel()} entries for {self.n} envs")
+        self.applied = torch.zeros(self.n, dtype=torch.uint8, device=dev)
+        self.cand = torch.zeros(self.n, dtype=torch.int8, device=dev)
+        self.v_root = torch.zeros(self.n, dtype=torch.float32, device=dev)
+        self.v_cand = torch.full((self.n,), float("nan"), dtype=torch.float32, device=dev)
+        self.disc_ret = torch.zeros(self.n, dtype=torch.float32, device=dev)
+        self.disc_g = torch.ones(self.n, dtype=torch.float32, device=dev)
+        self.disc_final = torch.full((self.n,), float("nan"), dtype=torch.float32, device=dev)
+
+    @property
+    def device(self) -> torch.device:
+        return self.applied.device
+
+    def c_struct(self) -> Audit:
+        """The scg_audit of these tensors (device pointers; the tensors must stay alive while it is in use)."""
+        return Audit(**{f: None if getattr(self, f) is None else C.c_void_p(getattr(self, f).data_ptr()) for f in self.DTYPES})
+
+    def host(self) -> dict:
+        return {f: getattr(self, f).detach().cpu().numpy() for f in self.DTYPES if getattr(self, f) is not None}
+
+    @staticmethod
+    def pair_summary(option, v_k, v_0, g_enter, g_decline, goal_enter, goal_decline) -> dict:
+        """The gate against the two branches it chooses between, over the audited states (host arrays of one length, in state
+        order; float64 arithmetic): `option` the option offered, v_k / v_0 the values the gate compared, g_enter / g_decline the
+        realised discounted task returns of the episode that entered / declined, goal_* whether that episode reached the goal.
+        Returns {"overall": row, "options": {k: row}}; a row holds n, enter_rate (V_k >= V_0; a NaN declines), mean_v_k,
+        mean_v_0, mean_g_enter, mean_g_decline, mean_advantage (G_enter - G_decline), agreement (the share of states where the
+        gate's decision equals G_enter >= G_decline), regret (mean of max(G_enter, G_decline) - G of the branch the gate chose),
+        calib_enter (mean V_k - G_enter), calib_decline (mean V_0 - G_decline), goal_rate_enter and goal_rate_decline. Means
+        of no state are NaN."""
+        option = np.asarray(option, np.int64)
+        v_k, v_0, ge, gd = (np.asarray(v, np.float64) for v in (v_k, v_0, g_enter, g_decline))
+        goal_e, goal_d = np.asarray(goal_enter, np.float64), np.asarray(goal_decline, np.float64)
+        with np.errstate(invalid="ignore"):
+            gate = v_k >= v_0
+            better = ge >= gd
+        chosen = np.where(gate, ge, gd)
+
+        def row(m):
+            return {
+                "n": int(m.sum()),
+                "enter_rate": _mean(gate[m]), "mean_v_k": _mean(v_k[m]), "mean_v_0": _mean(v_0[m]),
+                "mean_g_enter": _mean(ge[m]), "mean_g_decline": _mean(gd[m]), "mean_advantage": _mean((ge - gd)[m]),
+                "agreement": _mean((gate == better)[m]), "regret": _mean((np.maximum(ge, gd) - chosen)[m]),
+                "calib_enter": _mean((v_k - ge)[m]), "calib_decline": _mean((v_0 - gd)[m]),
+                "goal_rate_enter": _mean(goal_e[m]), "goal_rate_decline": _mean(goal_d[m]),
+            }
+        return {"overall": row(np.ones(option.shape, bool)),
+                "options": {int(k): row(option == k) for k in sorted(set(option.tolist()))}}

@@ -6,10 +6,11 @@ gives the median over the rounds. --record adds rollouts that record every step 
 first N envs (`N`), timed in the same alternation (`none` is the plain rollout, always timed). --interrupt adds interrupting
 rollouts (SPEC §11, scg_rollout_interrupt) on a state of their own, timed in the same alternation. --choose times something
 else: value-ranked choice (SPEC §14, scg_rollout_select) against scg_rollout_record's kernel, on the default chain and on the
-sibling tree of tools/choice_report.py (bench_choose).
+sibling tree of tools/choice_report.py (bench_choose). --audit times the audited rollout (SPEC §15, scg_rollout_audit, keeping the
+discounted return) against scg_rollout_select with the same rules, record and launches (bench_audit).
 
     python tools/rollout_bench.py [--sizes 4096 65536] [--k 64] [--rounds 7] [--epw 2 4 8 16 32] [--record none 1024 all]
-                                  [--interrupt] [--choose]
+                                  [--interrupt] [--choose] [--audit]
 """
 import argparse
 import json
@@ -148,6 +149,50 @@ def bench_choose(n, k, rounds, layout, n_opt=5):
     return out
 
 
+def bench_audit(n, k, rounds, rules, n_opt=5):
+    """µs per step of scg_rollout_audit (disc_ret, disc_g and disc_final kept; no begin, so no force) against scg_rollout_select
+    with the same `rules` ("" / "interrupt" / "best" / "best+interrupt"), both with a record of one env, each on a state of its own, on
+    tools/choice_report.py's sibling tree, timed alternately."""
+    import numpy as np
+    import torch
+    import skill_chaining_with_graphs_amd as scg
+    from choice_report import disc_weights, sibling_discs
+    from skill_chaining_with_graphs_amd.core import ScgContext
+    from skill_chaining_with_graphs_amd.evaluation import EpisodeStats, GateAudit
+    from skill_chaining_with_graphs_amd.trajectory import Trajectory
+    m = scg.load_map("pinball_simple")
+    ctx = ScgContext(n, n_opt, m, device=0, seed=7, epsilon=0.05, max_episode_steps=2000)
+    mask = ((1 << (n_opt + 1)) - 1) & ~1
+    ctx.set_option_parents(SIBLING_PARENTS)
+    c = np.zeros((n_opt + 1, 8), np.float32)
+    c[1:] = [disc_weights(*d) for d in sibling_discs(m)]
+    clf = torch.as_tensor(c, device=ctx.device).view(-1)
+    g = torch.Generator().manual_seed(3)
+    W = (torch.randn((n_opt + 1) * 5 * 1296, generator=g) * 1e-3).to(ctx.device)
+    kw = {"interrupt": "interrupt" in rules, "choose": "value" if "best" in rules else None}
+    if kw["choose"] is None:                                   # rules without BEST: scg_rollout_select's kernels, reached by their own names
+        del kw["choose"]
+    side = {}
+    for name in ("select", "audit"):
+        side[name] = {"st": rig.state_on(ctx, m, n), "t": 0, "stats": EpisodeStats(n_opt + 1, n, ctx.device), "us": []}
+    rec, ga = Trajectory(1, k, 0, ctx.device), GateAudit(n, ctx.device)
+
+    def roll(name):
+        s = side[name]
+        ctx.rollout(s["st"], W, clf, mask, s["t"], k, s["stats"], record=rec, **kw, **({"audit": ga} if name == "audit" else {}))
+        s["t"] += k
+
+    for name in side:
+        roll(name); roll(name)
+    for _ in range(rounds):
+        for name in side:
+            side[name]["us"].append(rig.timed(lambda: roll(name), 3) * 1e6 / k)
+    sel, aud = (float(np.median(side[x]["us"])) for x in ("select", "audit"))
+    return {"n_envs": n, "k": k, "options": n_opt, "rules": rules or "none", "select_us_per_step": round(sel, 2),
+            "audit_us_per_step": round(aud, 2), "audit_over_select": round(aud / sel, 4),
+            "select_rounds_us": [round(v, 2) for v in side["select"]["us"]], "audit_rounds_us": [round(v, 2) for v in side["audit"]["us"]]}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--sizes", type=int, nargs="+", default=[4096, 65536])
@@ -160,7 +205,14 @@ def main():
     ap.add_argument("--interrupt", action="store_true", help="also time interrupting rollouts (SPEC §11)")
     ap.add_argument("--choose", action="store_true",
                     help="instead: value-ranked choice (SPEC §14) against the recording kernel, on the chain and on the sibling tree")
+    ap.add_argument("--audit", action="store_true",
+                    help="instead: the audited rollout (SPEC §15) against scg_rollout_select, for the four rules, on the sibling tree")
     a = ap.parse_args()
+    if a.audit:
+        for n in a.sizes:
+            for rules in ("", "interrupt", "best", "best+interrupt"):
+                print(json.dumps(bench_audit(n, a.k, a.rounds, rules)), flush=True)
+        return
     if a.choose:
         for n in a.sizes:
             for layout in ("chain", "sibling"):
