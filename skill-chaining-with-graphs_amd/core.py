@@ -260,11 +260,7 @@ class ScgContext:
             if overrides is not None:
                 self._chk(overrides, torch.int32, self.n_vf * N, "overrides")
         rc = None if record is None else self._chk_record(record, N, n_steps + (1 if begin or begin_at else 0), "rollout")
-        # the arguments every entry point starts with; each appends its own tail
-        head = (_ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id), _ptr(st.opt_steps), _ptr(st.ep_steps),
-                _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done), _ptr(W), _ptr(clf), C.c_uint32(enabled_mask),
-                C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags), None if cs is None else C.byref(cs))
-        rc_ref = None if rc is None else C.byref(rc)
+        au = None
         if audit is not None:
             if audit.n != N or audit.device != self.device:
                 raise ScgError(f"rollout: the audit is for {audit.n} envs on {audit.device}, the context has {N} on {self.device}")
@@ -274,25 +270,25 @@ class ScgContext:
                 if getattr(audit, f) is not None:
                     self._chk(getattr(audit, f), dt, N, "audit." + f)
             au = audit.c_struct()
-            rules = (_lib.SELECT_BEST if choose is not None else 0) | (_lib.SELECT_INTERRUPT if interrupt else 0)
-            self._call("scg_rollout_audit", *head, None if interrupts is None else _ptr(interrupts),
-                       None if overrides is None else _ptr(overrides), rc_ref, C.c_uint32(rules), C.byref(au), self._stream())
-            if stats is not None and interrupt and interrupts is stats.interrupts:
-                stats.interrupting = True
+        # the narrowest entry point that takes what was asked for, and its tail behind the arguments all five start with
+        rules = (_lib.SELECT_BEST if choose is not None else 0) | (_lib.SELECT_INTERRUPT if interrupt else 0)
+        ints, ovr = (None if a is None else _ptr(a) for a in (interrupts, overrides))
+        rc_ref = None if rc is None else C.byref(rc)
+        if au is not None:
+            name, tail = "scg_rollout_audit", (ints, ovr, rc_ref, C.c_uint32(rules), C.byref(au))
         elif choose is not None:
-            rules = _lib.SELECT_BEST | (_lib.SELECT_INTERRUPT if interrupt else 0)
-            self._call("scg_rollout_select", *head, None if interrupts is None else _ptr(interrupts),
-                       None if overrides is None else _ptr(overrides), rc_ref, C.c_uint32(rules), self._stream())
-            if stats is not None and interrupt and interrupts is stats.interrupts:
-                stats.interrupting = True
+            name, tail = "scg_rollout_select", (ints, ovr, rc_ref, C.c_uint32(rules))
         elif interrupt:
-            self._call("scg_rollout_interrupt", *head, None if interrupts is None else _ptr(interrupts), rc_ref, self._stream())
-            if stats is not None and interrupts is stats.interrupts:
-                stats.interrupting = True
+            name, tail = "scg_rollout_interrupt", (ints, rc_ref)
         elif record is not None or begin_at:
-            self._call("scg_rollout_record", *head, rc_ref, self._stream())
+            name, tail = "scg_rollout_record", (rc_ref,)
         else:
-            self._call("scg_rollout", *head, self._stream())
+            name, tail = "scg_rollout", ()
+        self._call(name, _ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id), _ptr(st.opt_steps), _ptr(st.ep_steps),
+                   _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done), _ptr(W), _ptr(clf), C.c_uint32(enabled_mask),
+                   C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags), None if cs is None else C.byref(cs), *tail, self._stream())
+        if stats is not None and interrupt and interrupts is stats.interrupts:
+            stats.interrupting = True
 
     def option_trials(self, x: torch.Tensor, y: torch.Tensor, vx: torch.Tensor, vy: torch.Tensor, option: torch.Tensor,
                       W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, out, record=None) -> None:

@@ -17,10 +17,9 @@
 //   scg_aux_kernels.hpp      pinball / features / predict, and fit_kernel: SPEC §6 on 8 workgroups x 1024 chains per option behind
 //                            tagged-word exchanges; a fit whose workgroups cannot run together gives up after a wall-clock wait,
 //                            leaves its row untouched and raises the ctx's asynchronous status word
-// scg_record_kernels.hip is the second translation unit: rollout_kernel<true> / trial_kernel<true> (SPEC §10's per-step record) and
-// rollout_kernel on RolloutIntArgs / RolloutIntRecArgs (SPEC §11's interrupting rollout, without and with the record).
-// scg_select_kernels.hip is the third: rollout_kernel on RolloutBestArgs / RolloutBestIntArgs (SPEC §14's value-ranked choice).
-// scg_audit_kernels.hip is the fourth: rollout_kernel on RolloutAuditArgs<I, B> (SPEC §15's audited rollout).
+// scg_rollout_variants.hip is the second translation unit: every other instantiation of rollout_kernel (SPEC §10's record, §11's
+// interruption, §14's value-ranked choice, §15's audit: the table in scg_rollout_kernel.hpp) and trial_kernel<true>, reached through
+// launch_rollout<REC, Args> / launch_trial_record, which the two kernel headers declare.
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -47,21 +46,6 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 #include "scg_reduce_kernel.hpp"
 #include "scg_apply_kernels.hpp"
 #include "scg_aux_kernels.hpp"
-
-// the recording instantiations (SPEC §10), compiled and launched in scg_record_kernels.hip
-__attribute__((visibility("hidden"))) hipError_t launch_rollout_record(const RolloutRecArgs &A, int grid, hipStream_t s);
-__attribute__((visibility("hidden"))) hipError_t launch_trial_record(const TrialRecArgs &A, int grid, hipStream_t s);
-// the interrupting instantiations (SPEC §11), in the same translation unit
-__attribute__((visibility("hidden"))) hipError_t launch_rollout_interrupt(const RolloutIntArgs &A, int grid, hipStream_t s);
-__attribute__((visibility("hidden"))) hipError_t launch_rollout_interrupt_record(const RolloutIntRecArgs &A, int grid, hipStream_t s);
-// the value-ranking instantiations (SPEC §14), compiled and launched in scg_select_kernels.hip
-__attribute__((visibility("hidden"))) hipError_t launch_rollout_best(const RolloutBestArgs &A, int grid, hipStream_t s);
-__attribute__((visibility("hidden"))) hipError_t launch_rollout_best_interrupt(const RolloutBestIntArgs &A, int grid, hipStream_t s);
-// the audited instantiations (SPEC §15), compiled and launched in scg_audit_kernels.hip
-__attribute__((visibility("hidden"))) hipError_t launch_rollout_audit(const RolloutAuditArgs<false, false> &A, int grid, hipStream_t s);
-__attribute__((visibility("hidden"))) hipError_t launch_rollout_audit(const RolloutAuditArgs<true, false> &A, int grid, hipStream_t s);
-__attribute__((visibility("hidden"))) hipError_t launch_rollout_audit(const RolloutAuditArgs<false, true> &A, int grid, hipStream_t s);
-__attribute__((visibility("hidden"))) hipError_t launch_rollout_audit(const RolloutAuditArgs<true, true> &A, int grid, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -661,40 +645,67 @@ static int check_record(scg_ctx *c, const char *fn, const scg_record *rec, int N
     return why ? fail_in(c, SCG_ERR_INVALID, fn, why) : SCG_OK;
 }
 
-// a derived argument struct (record, interrupt): all zero but its base (the launch's plain arguments) and what `set` fills in
-extern "C++" template <typename Derived, typename Base, typename Set>
-static Derived derived_args(const Base &base, Set set) {
+// a derived argument struct (record, interrupt, ...): its base (the launch's plain arguments), every member of its own zero
+extern "C++" template <typename Derived, typename Base>
+static Derived derived_args(const Base &base) {
     Derived D;
     memset(&D, 0, sizeof(D));
     static_cast<Base &>(D) = base;
-    set(D);
     return D;
 }
 
-// scg_rollout, and scg_rollout_record (`fn` names the caller in error texts) with `rec` or `at` (BEGIN_AT, passed as BEGIN in
-// `flags`): the recording instantiation; scg_rollout_interrupt (`intr`): the interrupting ones, counting into `interrupts`;
-// scg_rollout_select with SCG_SELECT_BEST (`best`): the value-ranking ones (SPEC §14), counting into `overrides`;
-// scg_rollout_audit with a member of `audit` given: the audited ones (SPEC §15), one per (intr, best)
-static int rollout_launch(const char *fn, scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
-                          int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
-                          const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
-                          uint32_t flags, const scg_rollout_stats *stats, const scg_record *rec, bool at, void *stream,
-                          bool intr = false, int32_t *interrupts = nullptr, bool best = false, int32_t *overrides = nullptr,
-                          const scg_audit *audit = nullptr) {
+// one call of a rollout entry point: each of the five fills in what it takes, the members behind `stream` stay null / zero otherwise
+struct RolloutCall {
+    float *x, *y, *vx, *vy;
+    int32_t *option_id, *opt_steps, *ep_steps;
+    float *qcache;
+    uint8_t *action;
+    float *reward;
+    uint8_t *done;
+    const float *W, *clf;
+    uint32_t enabled_mask;
+    uint64_t t0;
+    int32_t n_steps;
+    uint32_t flags;
+    const scg_rollout_stats *stats;
+    void *stream;
+    bool takes_begin_at;           // every entry point but scg_rollout knows SCG_ROLLOUT_BEGIN_AT
+    const scg_record *rec;
+    int32_t *interrupts, *overrides;
+    uint32_t rules;                // SCG_SELECT_*; scg_rollout_interrupt: SCG_SELECT_INTERRUPT
+    const scg_audit *audit;
+};
+
+// the five rollout entry points (`fn` names the caller in error texts). The kernel follows from what the call asks for:
+//   audit      a member of `audit` given (SPEC §15; every member NULL counts as no audit)
+//   best, intr SCG_SELECT_BEST / SCG_SELECT_INTERRUPT in `rules` (SPEC §14 / §11), counting into `overrides` / `interrupts`
+//   rec, at    a record (SPEC §10) / SCG_ROLLOUT_BEGIN_AT, from here on BEGIN in `flags` plus `at`
+// Neither audit, best, rec nor at: the plain kernel, or with intr the non-recording interrupting one; otherwise a RolloutVar by (intr, best, audit)
+static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
     if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
+    if (a.rules & ~(SCG_SELECT_INTERRUPT | SCG_SELECT_BEST)) return fail_in(c, SCG_ERR_INVALID, fn, "unknown rule");
+    const bool intr = (a.rules & SCG_SELECT_INTERRUPT) != 0, best = (a.rules & SCG_SELECT_BEST) != 0;
+    const scg_audit *audit = a.audit;
+    if (audit && !audit->force && !audit->applied && !audit->cand && !audit->v_root && !audit->v_cand && !audit->disc_ret &&
+        !audit->disc_g && !audit->disc_final)
+        audit = nullptr;
+    uint32_t flags = a.flags;
+    const bool at = a.takes_begin_at && (flags & SCG_ROLLOUT_BEGIN_AT);
+    if (at && (flags & SCG_ROLLOUT_BEGIN)) return fail_in(c, SCG_ERR_INVALID, fn, "SCG_ROLLOUT_BEGIN and SCG_ROLLOUT_BEGIN_AT together");
+    if (at) flags = (flags & ~SCG_ROLLOUT_BEGIN_AT) | SCG_ROLLOUT_BEGIN;
     if (!c->have_map) return fail_in(c, SCG_ERR_STATE, fn, "scg_set_map has not been called");
-    if (!x || !y || !vx || !vy || !option_id || !opt_steps || !ep_steps || !qcache || !action || !reward ||
-        !done || !W || !clf)
+    if (!a.x || !a.y || !a.vx || !a.vy || !a.option_id || !a.opt_steps || !a.ep_steps || !a.qcache || !a.action || !a.reward ||
+        !a.done || !a.W || !a.clf)
         return fail_in(c, SCG_ERR_INVALID, fn, "null array argument");
     if (flags & ~(SCG_ROLLOUT_BEGIN | SCG_ROLLOUT_ONE_EPISODE)) return fail_in(c, SCG_ERR_INVALID, fn, "unknown flag");
-    if (n_steps < 0 || n_steps > SCG_ROLLOUT_MAX_STEPS)
+    if (a.n_steps < 0 || a.n_steps > SCG_ROLLOUT_MAX_STEPS)
         return fail_in(c, SCG_ERR_INVALID, fn, "n_steps out of range [0, SCG_ROLLOUT_MAX_STEPS]");
-    if (n_steps == 0 && !(flags & SCG_ROLLOUT_BEGIN))
+    if (a.n_steps == 0 && !(flags & SCG_ROLLOUT_BEGIN))
         return fail_in(c, SCG_ERR_INVALID, fn, "n_steps == 0 without SCG_ROLLOUT_BEGIN (or _BEGIN_AT)");
-    if ((flags & SCG_ROLLOUT_ONE_EPISODE) && !(stats && stats->finished))
+    if ((flags & SCG_ROLLOUT_ONE_EPISODE) && !(a.stats && a.stats->finished))
         return fail_in(c, SCG_ERR_INVALID, fn, "SCG_ROLLOUT_ONE_EPISODE needs stats->finished");
-    if (rec) {
-        const int rc = check_record(c, fn, rec, c->cfg.n_envs, (long long)n_steps + ((flags & SCG_ROLLOUT_BEGIN) ? 1 : 0));
+    if (a.rec) {
+        const int rc = check_record(c, fn, a.rec, c->cfg.n_envs, (long long)a.n_steps + ((flags & SCG_ROLLOUT_BEGIN) ? 1 : 0));
         if (rc != SCG_OK) return rc;
     }
     if (audit && audit->force && !(flags & SCG_ROLLOUT_BEGIN))
@@ -706,44 +717,44 @@ static int rollout_launch(const char *fn, scg_ctx *c, float *x, float *y, float 
     if (!dev_guard_.ok) return fail_in(c, SCG_ERR_HIP, fn, "cannot make the context's device current");
     RolloutArgs R;
     fill_shared(c, R);
-    R.x = x; R.y = y; R.vx = vx; R.vy = vy; R.option_id = option_id; R.opt_steps = opt_steps; R.ep_steps = ep_steps;
-    R.qcache = qcache; R.action = action; R.reward = reward; R.done = done; R.W = W; R.clf = clf;
-    if (stats) R.st = *stats;
-    R.n_steps = n_steps;
+    R.x = a.x; R.y = a.y; R.vx = a.vx; R.vy = a.vy; R.option_id = a.option_id; R.opt_steps = a.opt_steps; R.ep_steps = a.ep_steps;
+    R.qcache = a.qcache; R.action = a.action; R.reward = a.reward; R.done = a.done; R.W = a.W; R.clf = a.clf;
+    if (a.stats) R.st = *a.stats;
+    R.n_steps = a.n_steps;
     R.begin = (flags & SCG_ROLLOUT_BEGIN) ? 1u : 0u; R.one_episode = (flags & SCG_ROLLOUT_ONE_EPISODE) ? 1u : 0u;
-    R.enabled = enabled_mask; R.t0 = t0;
+    R.enabled = a.enabled_mask; R.t0 = a.t0;
     int epw;
     if (!rollout_epw(c, c->cfg.n_envs, epw)) return fail_in(c, SCG_ERR_INVALID, fn, "SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
     R.epw = epw;
     const int grid = (c->cfg.n_envs + RO_WAVES * epw - 1) / (RO_WAVES * epw);
+    const hipStream_t s = reinterpret_cast<hipStream_t>(a.stream);
     c->order_valid = false;                               // the ids change under the step's prepared env order
-    if (audit) {
-        const auto fill = [&](auto &D) {
-            if (rec) D.rec = *rec;
-            D.begin_at = at ? 1u : 0u; D.interrupts = interrupts; D.overrides = overrides; D.au = *audit; D.gamma = c->cfg.gamma;
-        };
-        const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        if (best && intr) SCG_HIP(c, launch_rollout_audit(derived_args<RolloutAuditArgs<true, true>>(R, fill), grid, s));
-        else if (best) SCG_HIP(c, launch_rollout_audit(derived_args<RolloutAuditArgs<false, true>>(R, fill), grid, s));
-        else if (intr) SCG_HIP(c, launch_rollout_audit(derived_args<RolloutAuditArgs<true, false>>(R, fill), grid, s));
-        else SCG_HIP(c, launch_rollout_audit(derived_args<RolloutAuditArgs<false, false>>(R, fill), grid, s));
-    } else if (best) {
-        const auto fill = [&](auto &D) { if (rec) D.rec = *rec; D.begin_at = at ? 1u : 0u; D.interrupts = interrupts; D.overrides = overrides; };
-        if (intr) SCG_HIP(c, launch_rollout_best_interrupt(derived_args<RolloutBestIntArgs>(R, fill), grid, reinterpret_cast<hipStream_t>(stream)));
-        else SCG_HIP(c, launch_rollout_best(derived_args<RolloutBestArgs>(R, fill), grid, reinterpret_cast<hipStream_t>(stream)));
-    } else if (intr && (rec || at)) {
-        const auto RR = derived_args<RolloutIntRecArgs>(R, [&](auto &D) { if (rec) D.rec = *rec; D.begin_at = at ? 1u : 0u; D.interrupts = interrupts; });
-        SCG_HIP(c, launch_rollout_interrupt_record(RR, grid, reinterpret_cast<hipStream_t>(stream)));
-    } else if (intr) {
-        const auto RI = derived_args<RolloutIntArgs>(R, [&](auto &D) { D.interrupts = interrupts; });
-        SCG_HIP(c, launch_rollout_interrupt(RI, grid, reinterpret_cast<hipStream_t>(stream)));
-    } else if (rec || at) {
-        const auto RR = derived_args<RolloutRecArgs>(R, [&](auto &D) { if (rec) D.rec = *rec; D.begin_at = at ? 1u : 0u; });     // (no rec: n = 0, nothing recorded)
-        SCG_HIP(c, launch_rollout_record(RR, grid, reinterpret_cast<hipStream_t>(stream)));
-    } else {
-        hipLaunchKernelGGL((rollout_kernel<false, RolloutArgs>), dim3(grid), dim3(RO_THREADS), 0, reinterpret_cast<hipStream_t>(stream), R);
-        SCG_HIP(c, hipGetLastError());
+    auto I = derived_args<RolloutIntArgs>(R);
+    I.interrupts = a.interrupts;
+    auto V = derived_args<RolloutVarArgs>(R);
+    if (a.rec) V.rec = *a.rec;                            // (no rec: n = 0, nothing recorded)
+    V.begin_at = at ? 1u : 0u;
+    if (intr) V.interrupts = a.interrupts;
+    if (best) V.overrides = a.overrides;
+    if (audit) { V.au = *audit; V.gamma = c->cfg.gamma; }
+    const bool var = audit || best || a.rec || at;        // what only the RolloutVar kernels take
+    hipError_t rollout_kernel_launch = hipSuccess;
+    switch ((var ? 8 : 0) | (audit ? 4 : 0) | (best ? 2 : 0) | (intr ? 1 : 0)) {                    // INT    BEST   AUDIT
+    case 0:
+        hipLaunchKernelGGL((rollout_kernel<false, RolloutArgs>), dim3(grid), dim3(RO_THREADS), 0, s, R);
+        rollout_kernel_launch = hipGetLastError();
+        break;
+    case 1: rollout_kernel_launch = launch_rollout<false, RolloutIntArgs>(I, grid, s); break;
+    case 8: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutVar<false, false, false>>(V), grid, s); break;
+    case 9: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutVar<true, false, false>>(V), grid, s); break;
+    case 10: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutVar<false, true, false>>(V), grid, s); break;
+    case 11: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutVar<true, true, false>>(V), grid, s); break;
+    case 12: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutVar<false, false, true>>(V), grid, s); break;
+    case 13: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutVar<true, false, true>>(V), grid, s); break;
+    case 14: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutVar<false, true, true>>(V), grid, s); break;
+    case 15: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutVar<true, true, true>>(V), grid, s); break;
     }
+    SCG_HIP(c, rollout_kernel_launch);
     return SCG_OK;
 }
 
@@ -751,27 +762,16 @@ int scg_rollout(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *o
                 int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
                 const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
                 uint32_t flags, const scg_rollout_stats *stats, void *stream) {
-    return rollout_launch("scg_rollout", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
-                          enabled_mask, t0, n_steps, flags, stats, nullptr, false, stream);
-}
-
-// SCG_ROLLOUT_BEGIN_AT is passed on as `at` plus SCG_ROLLOUT_BEGIN in `flags` (a null ctx is rollout_launch's to refuse)
-static int begin_at_flags(scg_ctx *c, const char *fn, uint32_t &flags, bool &at) {
-    at = (flags & SCG_ROLLOUT_BEGIN_AT) != 0;
-    if (c && at && (flags & SCG_ROLLOUT_BEGIN))
-        return fail_in(c, SCG_ERR_INVALID, fn, "SCG_ROLLOUT_BEGIN and SCG_ROLLOUT_BEGIN_AT together");
-    if (at) flags = (flags & ~SCG_ROLLOUT_BEGIN_AT) | SCG_ROLLOUT_BEGIN;
-    return SCG_OK;
+    return rollout_launch("scg_rollout", c, {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
+                                             enabled_mask, t0, n_steps, flags, stats, stream});
 }
 
 int scg_rollout_record(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
                        int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
                        const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
                        uint32_t flags, const scg_rollout_stats *stats, const scg_record *rec, void *stream) {
-    bool at;
-    if (const int rc = begin_at_flags(c, "scg_rollout_record", flags, at)) return rc;
-    return rollout_launch("scg_rollout_record", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done,
-                          W, clf, enabled_mask, t0, n_steps, flags, stats, rec, at, stream);
+    return rollout_launch("scg_rollout_record", c, {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
+                                                    enabled_mask, t0, n_steps, flags, stats, stream, true, rec});
 }
 
 int scg_rollout_interrupt(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
@@ -779,27 +779,20 @@ int scg_rollout_interrupt(scg_ctx *c, float *x, float *y, float *vx, float *vy, 
                           const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
                           uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, const scg_record *rec,
                           void *stream) {
-    bool at;
-    if (const int rc = begin_at_flags(c, "scg_rollout_interrupt", flags, at)) return rc;
-    return rollout_launch("scg_rollout_interrupt", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done,
-                          W, clf, enabled_mask, t0, n_steps, flags, stats, rec, at, stream, true, interrupts);
+    return rollout_launch("scg_rollout_interrupt", c, {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
+                                                       enabled_mask, t0, n_steps, flags, stats, stream, true, rec, interrupts, nullptr,
+                                                       SCG_SELECT_INTERRUPT});
 }
 
-// rules = 0: scg_rollout_record; SCG_SELECT_INTERRUPT alone: scg_rollout_interrupt (both on the kernels those launch). `overrides` is
-// passed on with SCG_SELECT_BEST only
+// rules = 0: scg_rollout_record's kernel; SCG_SELECT_INTERRUPT alone: scg_rollout_interrupt's
 int scg_rollout_select(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
                        int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
                        const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
                        uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
                        const scg_record *rec, uint32_t rules, void *stream) {
-    if (c && (rules & ~(SCG_SELECT_INTERRUPT | SCG_SELECT_BEST)))
-        return fail_in(c, SCG_ERR_INVALID, "scg_rollout_select", "unknown rule");
-    const bool intr = (rules & SCG_SELECT_INTERRUPT) != 0, best = (rules & SCG_SELECT_BEST) != 0;
-    bool at;
-    if (const int rc = begin_at_flags(c, "scg_rollout_select", flags, at)) return rc;
-    return rollout_launch("scg_rollout_select", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done,
-                          W, clf, enabled_mask, t0, n_steps, flags, stats, rec, at, stream, intr, intr ? interrupts : nullptr,
-                          best, best ? overrides : nullptr);
+    return rollout_launch("scg_rollout_select", c, {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
+                                                    enabled_mask, t0, n_steps, flags, stats, stream, true, rec, interrupts, overrides,
+                                                    rules});
 }
 
 // audit = NULL, or every member NULL: scg_rollout_select's launch, under this entry point's name in error texts
@@ -808,17 +801,9 @@ int scg_rollout_audit(scg_ctx *c, float *x, float *y, float *vx, float *vy, int3
                       const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
                       uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
                       const scg_record *rec, uint32_t rules, const scg_audit *audit, void *stream) {
-    if (c && (rules & ~(SCG_SELECT_INTERRUPT | SCG_SELECT_BEST)))
-        return fail_in(c, SCG_ERR_INVALID, "scg_rollout_audit", "unknown rule");
-    const bool intr = (rules & SCG_SELECT_INTERRUPT) != 0, best = (rules & SCG_SELECT_BEST) != 0;
-    if (audit && !audit->force && !audit->applied && !audit->cand && !audit->v_root && !audit->v_cand && !audit->disc_ret &&
-        !audit->disc_g && !audit->disc_final)
-        audit = nullptr;
-    bool at;
-    if (const int rc = begin_at_flags(c, "scg_rollout_audit", flags, at)) return rc;
-    return rollout_launch("scg_rollout_audit", c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done,
-                          W, clf, enabled_mask, t0, n_steps, flags, stats, rec, at, stream, intr, intr ? interrupts : nullptr,
-                          best, best ? overrides : nullptr, audit);
+    return rollout_launch("scg_rollout_audit", c, {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
+                                                   enabled_mask, t0, n_steps, flags, stats, stream, true, rec, interrupts, overrides,
+                                                   rules, audit});
 }
 
 static int trials_launch(const char *fn, scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,
@@ -849,7 +834,8 @@ static int trials_launch(const char *fn, scg_ctx *c, int32_t n, const float *x, 
     T.epw = epw;
     const int grid = (int)(((long long)n + RO_WAVES * epw - 1) / (RO_WAVES * epw));
     if (rec) {
-        const auto TR = derived_args<TrialRecArgs>(T, [&](auto &D) { D.rec = *rec; });
+        auto TR = derived_args<TrialRecArgs>(T);
+        TR.rec = *rec;
         SCG_HIP(c, launch_trial_record(TR, grid, reinterpret_cast<hipStream_t>(stream)));
     } else {
         hipLaunchKernelGGL((trial_kernel<false, TrialArgs>), dim3(grid), dim3(RO_THREADS), 0, reinterpret_cast<hipStream_t>(stream), T);

@@ -41,42 +41,36 @@ struct RolloutArgs {
     static constexpr bool BEST = false;  // SPEC §14's value-ranked choice: likewise
     static constexpr bool AUDIT = false; // SPEC §15's forced first choice and discounted return: likewise
 };
-// the recording instantiation's arguments (SPEC §10): RolloutArgs at offset 0, so the exit's re-read holds for both
-struct RolloutRecArgs : RolloutArgs {
-    scg_record rec;                // device pointers; n = 0: nothing recorded
-    uint32_t begin_at;             // BEGIN's reset replaced by the state given
-};
-// the interrupting instantiations' arguments (SPEC §11), without and with the record; the base at offset 0 as above
+// The ten instantiations, the narrowest entry point that launches each (rollout_launch in scg_kernels.hip has the whole mapping), and
+// what each adds to <false, RolloutArgs>. INT, BEST and AUDIT are compile-time flags of the argument type. Every argument type has
+// RolloutArgs at offset 0, so the exit's re-read holds for all.
+//   REC    Args                               launched by                    adds
+//   false  RolloutArgs                        scg_rollout                    -
+//   false  RolloutIntArgs                     scg_rollout_interrupt          SPEC §11's interruption, counted into `interrupts` (no rec, no BEGIN_AT)
+//   true   RolloutVar<false, false, false>    scg_rollout_record             SPEC §10's rows of the envs in the record's window, and BEGIN_AT
+//   true   RolloutVar<true,  false, false>    scg_rollout_interrupt          both of the above
+//   true   RolloutVar<false, true,  false>    scg_rollout_select, BEST       SPEC §14's value-ranked choice: an offered env is evaluated under
+//   true   RolloutVar<true,  true,  false>    ... BEST | INTERRUPT           every candidate's value function and the root's, the Q of VF k in slot k
+//                                                                            of s_qv (root: 0); phase G enters the candidate whose value is highest
+//   true   RolloutVar<I,     B,     true>     scg_rollout_audit, by `rules`  SPEC §15: the begin pseudo-step's choice may be forced per env, and the
+//          (all four I, B)                                                   discounted task return is kept in two more registers across the steps
+// Every REC instantiation shares ONE argument layout, RolloutVarArgs; the non-recording interrupting kernel keeps
+// its own, because `interrupts` at another offset changes its code.
 struct RolloutIntArgs : RolloutArgs {
     static constexpr bool INT = true;
     int32_t *interrupts;           // [n_vf][N] in/out, may be null
 };
-struct RolloutIntRecArgs : RolloutRecArgs {
-    static constexpr bool INT = true;
-    int32_t *interrupts;
-};
-// the value-ranking instantiations' arguments (SPEC §14; scg_rollout_select), without and with the interruption, always with the record
-struct RolloutBestArgs : RolloutRecArgs {
-    static constexpr bool BEST = true;
-    int32_t *interrupts;           // (not counted without INT)
-    int32_t *overrides;            // [n_vf][N] in/out, may be null
-};
-struct RolloutBestIntArgs : RolloutRecArgs {
-    static constexpr bool INT = true;
-    static constexpr bool BEST = true;
-    int32_t *interrupts;
-    int32_t *overrides;
-};
-// the audited instantiations' arguments (SPEC §15; scg_rollout_audit), one per `rules` of scg_rollout_select, always with the record
-template <bool I, bool B>
-struct RolloutAuditArgs : RolloutRecArgs {
-    static constexpr bool INT = I;
-    static constexpr bool BEST = B;
-    static constexpr bool AUDIT = true;
-    int32_t *interrupts;           // (not counted without INT)
-    int32_t *overrides;            // (not counted without BEST)
-    scg_audit au;                  // device pointers, any may be null
+struct RolloutVarArgs : RolloutArgs {
+    scg_record rec;                // device pointers; n = 0: nothing recorded
+    uint32_t begin_at;             // BEGIN's reset replaced by the state given
+    int32_t *interrupts;           // [n_vf][N] in/out, may be null (read with INT only)
+    int32_t *overrides;            // [n_vf][N] in/out, may be null (read with BEST only)
+    scg_audit au;                  // device pointers, any may be null (read with AUDIT only)
     float gamma;
+};
+template <bool I, bool B, bool AU>
+struct RolloutVar : RolloutVarArgs {
+    static constexpr bool INT = I, BEST = B, AUDIT = AU;
 };
 
 // per-VF counters of one launch, six 16-bit fields in three words (a launch takes at most 1 + SCG_ROLLOUT_MAX_STEPS steps)
@@ -96,13 +90,7 @@ struct Ctr16 {
 };
 static_assert(SCG_ROLLOUT_MAX_STEPS + 1 < 65536, "16-bit launch counters");
 
-// <false, RolloutArgs>: scg_rollout's kernel. <true, RolloutRecArgs>: the same steps, plus SPEC §10's rows of the envs in the
-// record's window, and BEGIN_AT (scg_rollout_record). <false, RolloutIntArgs> / <true, RolloutIntRecArgs>: the same with
-// SPEC §11's interruption (scg_rollout_interrupt); INT = Args::INT. <true, RolloutBestArgs> / <true, RolloutBestIntArgs>: SPEC §14's
-// value-ranked choice (scg_rollout_select), BEST = Args::BEST: an offered env is evaluated under every candidate's value function
-// and the root's, the Q of VF k in slot k of s_qv (root: slot 0), and phase G enters the candidate whose value is highest.
-// <true, RolloutAuditArgs<I, B>>: SPEC §15's audited rollout (scg_rollout_audit), AUDIT = Args::AUDIT: the begin pseudo-step's
-// choice may be forced per env, and the discounted task return is kept in two more registers across the steps
+// (the instantiations: the table at the argument types)
 template <bool REC, typename Args>
 __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
     constexpr bool INT = Args::INT, BEST = Args::BEST, AUDIT = Args::AUDIT;
@@ -152,14 +140,14 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
     }
     const bool skip = !mine || (A.one_episode && finished);   // not stepped at all in this launch: nothing of it is written
     if (!__syncthreads_or(!skip)) {                           // (workgroup-uniform) every env of the workgroup is finished
-        if constexpr (REC) record_len(kernel_args<RolloutRecArgs>()->rec, e, mine, 0);
+        if constexpr (REC) record_len(kernel_args<RolloutVarArgs>()->rec, e, mine, 0);
         return;
     }
     bool alive = !skip;
     int nrow = 0;                                             // REC: rows recorded
     int rr = -1;                                              // REC: this env's column in the record, -1: outside its window
     if constexpr (REC) {
-        const scg_record R = kernel_args<RolloutRecArgs>()->rec;
+        const scg_record R = kernel_args<RolloutVarArgs>()->rec;
         if (e - R.first >= 0 && e - R.first < R.n) rr = e - R.first;
     }
 
@@ -203,7 +191,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         int fk = 0, amin = 0;                                  // AUDIT: the force that applies (+k / -k, 0: none) and min C beside it
         if (valid) {
             dn = is_begin ? 2 : episode_end(goal, eps1, A.max_ep);
-            if (dn && !(REC && is_begin && kernel_args<RolloutRecArgs>()->begin_at)) restart_state(u[2], A.starts, A.ms.n_starts, nx, ny, nvx, nvy);
+            if (dn && !(REC && is_begin && kernel_args<RolloutVarArgs>()->begin_at)) restart_state(u[2], A.starts, A.ms.n_starts, nx, ny, nvx, nvy);
             unsigned inA, inB;
             member_masks(s_clf, A.n_vf, known, px, py, nx, ny, inA, inB);
             if (!is_begin && o >= 1) keep = option_keep(A.parents, o, inA, goal, dn, osteps, A.max_opt, succ);
@@ -410,7 +398,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
             }
             if constexpr (REC) {                                 // SPEC §10's row j of this env
                 if (rr >= 0) {
-                    const scg_record R = kernel_args<RolloutRecArgs>()->rec;  // by value: see record_len
+                    const scg_record R = kernel_args<RolloutVarArgs>()->rec;  // by value: see record_len
                     const size_t at = (size_t)j * R.n + rr;
                     if (R.x) R.x[at] = is_begin ? sx : px;
                     if (R.y) R.y[at] = is_begin ? sy : py;
@@ -430,7 +418,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
 
     // ---- exit: the stepped envs' results, once. The output pointers are fetched from the kernel arguments again here (kernel_args):
     // otherwise the compiler keeps the 21 pointers it loaded at entry live in scalar registers across the whole step loop
-    if constexpr (REC) record_len(kernel_args<RolloutRecArgs>()->rec, e, mine, nrow);     // (skipped: 0)
+    if constexpr (REC) record_len(kernel_args<RolloutVarArgs>()->rec, e, mine, nrow);     // (skipped: 0)
     if (skip) return;
     const RolloutArgs *K = kernel_args<RolloutArgs>();
     K->x[e] = sx; K->y[e] = sy; K->vx[e] = svx; K->vy[e] = svy;
@@ -468,3 +456,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
             for (int k = 0; k < K->n_vf; ++k) O[(size_t)k * N + e] += c_ov.get(k);
     }
 }
+
+// the launch of rollout_kernel<REC, Args>: defined and instantiated in scg_rollout_variants.hip for every Args but RolloutArgs
+template <bool REC, typename Args>
+__attribute__((visibility("hidden"))) hipError_t launch_rollout(const Args &A, int grid, hipStream_t s);

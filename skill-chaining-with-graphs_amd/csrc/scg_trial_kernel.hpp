@@ -205,3 +205,6 @@ __global__ __launch_bounds__(RO_THREADS) void trial_kernel(const Args A) {
     if (O.end_vx) O.end_vx[i] = svx;
     if (O.end_vy) O.end_vy[i] = svy;
 }
+
+// the launch of trial_kernel<true, TrialRecArgs>, defined in scg_rollout_variants.hip
+__attribute__((visibility("hidden"))) hipError_t launch_trial_record(const TrialRecArgs &A, int grid, hipStream_t s);
