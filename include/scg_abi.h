@@ -343,6 +343,22 @@ int scg_pinball_step(scg_ctx *ctx, int32_t n, float *x, float *y, float *vx, flo
 /* FourierBasis.features (SPEC §3): phi[n][1296]. */
 int scg_fourier_features(scg_ctx *ctx, int32_t n, const float *x, const float *y, const float *vx,
                          const float *vy, float *phi, void *stream);
+/* Feature Gram (SPEC §16.1): for each of n_seg segments of the n recorded states — segment g = samples offsets[g] .. offsets[g+1]-1;
+ * offsets HOST int64[n_seg+1], non-decreasing, inside [0, n]; empty segments allowed, samples outside every segment ignored —
+ *   A[g][1296][1296] = sum_n phi(s_n) phi(s_n)^T   and, with yv[n] / b given (both or neither),   b[g][1296] = sum_n phi(s_n) yv[n]
+ * in SPEC §16.1's pinned order: per entry an fma chain over each slab of SCG_GRAM_SLAB consecutive samples of the segment, the slab
+ * sums added in order. phi is never materialised (f32 MFMA operands are built from the state). A and b are fully overwritten (an
+ * empty segment: +0), A exactly symmetric; the same bits from every block build. Needs no map (no SCG_ERR_STATE before scg_set_map)
+ * and writes A and b only: nothing of the training state. SCG_ERR_INVALID, nothing launched: a null x / y / vx / vy / A / offsets,
+ * n < 0, n_seg outside [1, SCG_GRAM_MAX_SEGMENTS], offsets that decrease or leave [0, n], yv without b or b without yv. */
+#define SCG_GRAM_SLAB 1024
+#define SCG_GRAM_MAX_SEGMENTS 64
+#ifndef SCG_GRAM_MACRO_TILE
+#define SCG_GRAM_MACRO_TILE 96     /* features a side of one workgroup's block of A (not part of the arithmetic: a test's edge list) */
+#endif
+int scg_feature_gram(scg_ctx *ctx, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                     const float *yv /* may be NULL */, int32_t n_seg, const int64_t *offsets /* HOST */,
+                     float *A, float *b /* NULL iff yv is NULL */, void *stream);
 /* Option.policy value part (SPEC §3.1): q[5][n] = Q_k(s, .) for one VF Wk[5][1296]. */
 int scg_q_values(scg_ctx *ctx, int32_t n, const float *x, const float *y, const float *vx,
                  const float *vy, const float *Wk, float *q, void *stream);

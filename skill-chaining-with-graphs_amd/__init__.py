@@ -35,6 +35,9 @@ def __getattr__(name):
     if name in ("Option", "InitiationClassifier"):
         from . import option
         return getattr(option, name)
+    if name in ("returns_to_go", "ridge_solve"):
+        from . import valuefit
+        return getattr(valuefit, name)
     if name == "SkillChainingAgent":
         from .agent import SkillChainingAgent
         return SkillChainingAgent

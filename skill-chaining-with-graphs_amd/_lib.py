@@ -37,6 +37,9 @@ ASYNC_STEP_HANDOFF = 0x2
 ASYNC_PEER_TIMEOUT = 0x4
 PEER_HANDLE_BYTES = 64      # hipIpcMemHandle_t
 PEER_MAX_RANKS = 8
+GRAM_SLAB = 1024            # include/scg_abi.h SCG_GRAM_*: SPEC §16.1's slab, the segment cap, one workgroup's block of A (features a side)
+GRAM_MAX_SEGMENTS = 64
+GRAM_MACRO_TILE = 96
 
 
 class ScgError(RuntimeError):
@@ -157,6 +160,7 @@ _SIGS = {
     "scg_apply_update_slots": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, _P]),
     "scg_pinball_step": (C.c_int, [_P, C.c_int32] + [_P] * 7 + [_P]),
     "scg_fourier_features": (C.c_int, [_P, C.c_int32] + [_P] * 5 + [_P]),
+    "scg_feature_gram": (C.c_int, [_P, C.c_int64] + [_P] * 5 + [C.c_int32, _P, _P, _P, _P]),
     "scg_q_values": (C.c_int, [_P, C.c_int32] + [_P] * 6 + [_P]),
     "scg_q_update": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 12 + [C.c_uint32, _P]),
     "scg_classifier_predict": (C.c_int, [_P, C.c_int32] + [_P] * 4 + [_P]),

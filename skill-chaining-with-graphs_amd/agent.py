@@ -581,6 +581,83 @@ class SkillChainingAgent:
         out["per_state"] = per
         return out
 
+    def fit_values_to_returns(self, n_episodes: int = 4096, epsilon: float = 0.1, seed: Optional[int] = None, vfs=None,
+                              ridge: float = 1e-3, apply: bool = False, interrupt: bool = False, choose: Optional[str] = None,
+                              keep: bool = False):
+        """The best linear fit of each Q_k to the returns its own policy realises (SPEC §16): record_episodes() with the current
+        policy, Monte-Carlo targets by valuefit.returns_to_go, then per value function k of `vfs` (default: all) and action a the
+        ridge regression of the residual y - Q_k^old on the 1296 features over the rows with vf = k, action = a of the EVEN envs
+        (the odd envs are held out): A, b by ScgContext.feature_gram with the action as segment, Delta by valuefit.ridge_solve,
+        W_k[a] <- float32(W_k^old[a] + Delta). An action without samples keeps its row bit for bit.
+        Returns (report, W_new): W_new a copy of W with the fitted rows; report["vf"][k] holds n (fit samples per action),
+        delta_norm and, for "fit" and "held_out", old / new: n, rmse, mean_error of Q^old / Q^new against y. The held-out numbers
+        are the ones that count. `keep` adds the operands (report["vf"][k]["operands"]: states, action, y, d, offsets, A, b) and
+        report["targets"] (returns_to_go's dict) and report["trajectory"].
+        apply=False leaves the agent as evaluate() does: W, training state, t, env order, trace ring, gestation counts and peer
+        counter untouched. apply=True copies the fitted rows of `vfs` into W; refused with shared weights (a sharded agent would
+        fit its own rank's copy only, and the ranks' W would part)."""
+        from .valuefit import error_stats, returns_to_go, ridge_solve
+        if apply and self.group is not None:
+            raise ScgError("fit_values_to_returns(apply=True) with shared weights: each rank would fit its own copy of W and the "
+                           "ranks would part; fit with apply=False and load one rank's result on all of them")
+        vfs = list(range(self.n_vf)) if vfs is None else [int(k) for k in vfs]
+        if any(not (0 <= k < self.n_vf) for k in vfs):
+            raise ValueError(f"vfs must name value functions 0..{self.n_vf - 1}")
+        c = self.ctx.cfg
+        traj, summary = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose)
+        ectx = self._eval_ctx[int(n_episodes)][0]
+        flat = traj.to_numpy()
+        tg = returns_to_go(flat, float(c.gamma), float(c.r_option_success))
+        off = flat["offsets"]
+        env = np.repeat(np.arange(traj.n), np.diff(off))
+        smp = np.nonzero(tg["sample"])[0]                      # the rows that are steps, in (env, row) order; their s is the row before
+        dev = self.W.device
+        W_new = self.W.clone()
+        report = {"episodes": summary, "ridge": float(ridge), "vf": {}}
+
+        def q_of(states, Wk, act):                             # Q_k(s_n, a_n) of a sample list, float32 as the kernel gives it
+            out = np.zeros(len(act), np.float32)
+            for i in range(0, len(act), ectx.n_envs):
+                sl = slice(i, i + ectx.n_envs)
+                q = ectx.q_values([t[sl].contiguous() for t in states], Wk.contiguous().view(-1)).cpu().numpy()
+                out[sl] = q[act[sl], np.arange(q.shape[1])]
+            return out
+
+        for k in vfs:
+            rows = smp[flat["vf"][smp] == k]
+            rows = np.concatenate([rows[env[rows] % 2 == 0], rows[env[rows] % 2 == 1]])      # the fit half, then the held-out half
+            n_fit = int(np.sum(env[rows] % 2 == 0))
+            order = np.argsort(flat["action"][rows[:n_fit]], kind="stable")
+            rows[:n_fit] = rows[:n_fit][order]                 # the fit samples by action, (env, row) order within one
+            act = flat["action"][rows].astype(np.int64)
+            y = tg["y"][rows]
+            states = [torch.from_numpy(np.ascontiguousarray(flat[f][rows - 1])).to(dev) for f in ("x", "y", "vx", "vy")]
+            q_old = q_of(states, self.W[k], act)
+            d = (y - q_old.astype(np.float64)).astype(np.float32)
+            n_a = np.bincount(act[:n_fit], minlength=NUM_ACTIONS).astype(np.int64)
+            offsets = np.concatenate([[0], np.cumsum(n_a)]).astype(np.int64)
+            A, b = ectx.feature_gram(states, offsets, torch.from_numpy(d).to(dev))
+            delta = ridge_solve(A.cpu().numpy(), b.cpu().numpy(), n_a, ridge, self.ctx.scale)
+            w_old = self.W[k].cpu().numpy()
+            w_new = (w_old.astype(np.float64) + delta).astype(np.float32)
+            w_new[n_a == 0] = w_old[n_a == 0]
+            W_new[k] = torch.from_numpy(w_new).to(dev)
+            q_new = q_of(states, W_new[k], act)
+            half = {"fit": slice(0, n_fit), "held_out": slice(n_fit, None)}
+            rep = {"n": [int(v) for v in n_a], "delta_norm": float(np.sqrt(np.sum(delta * delta)))}
+            for name, sl in half.items():
+                rep[name] = {"old": error_stats(q_old[sl], y[sl]), "new": error_stats(q_new[sl], y[sl])}
+            if keep:
+                rep["operands"] = {"states": states, "action": act, "y": y, "d": d, "offsets": offsets, "n_fit": n_fit, "A": A, "b": b,
+                                   "rows": rows, "delta": delta}
+            report["vf"][k] = rep
+        if keep:
+            report["targets"], report["trajectory"] = tg, traj
+        if apply:
+            for k in vfs:
+                self.W[k].copy_(W_new[k])
+        return report, W_new
+
     def _mirror_training(self, side: ScgContext, epsilon: float) -> None:
         """Copy the training run's settings into a side context (evaluation, trials): its hyper-parameters (epsilon aside),
         parents and gestation mask — classifiers in use, no success counts kept; its own state, t and counters untouched."""

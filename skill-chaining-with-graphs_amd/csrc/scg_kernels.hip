@@ -17,6 +17,7 @@
 //   scg_aux_kernels.hpp      pinball / features / predict, and fit_kernel: SPEC §6 on 8 workgroups x 1024 chains per option behind
 //                            tagged-word exchanges; a fit whose workgroups cannot run together gives up after a wall-clock wait,
 //                            leaves its row untouched and raises the ctx's asynchronous status word
+//   scg_gram_kernel.hpp      SPEC §16.1's feature Gram: here only its arguments and launch (the kernel is compiled in scg_gram.hip)
 // scg_rollout_variants.hip is the second translation unit: every other instantiation of rollout_kernel (SPEC §10's record, §11's
 // interruption, §14's value-ranked choice, §15's audit: the table in scg_rollout_kernel.hpp) and trial_kernel<true>, reached through
 // launch_rollout<REC, Args> / launch_trial_record, which the two kernel headers declare.
@@ -46,6 +47,7 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 #include "scg_reduce_kernel.hpp"
 #include "scg_apply_kernels.hpp"
 #include "scg_aux_kernels.hpp"
+#include "scg_gram_kernel.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -1214,6 +1216,38 @@ int scg_fourier_features(scg_ctx *c, int32_t n, const float *x, const float *y, 
     hipLaunchKernelGGL(features_kernel, dim3(grid), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), n, x, y,
                        vx, vy, phi);
     SCG_HIP(c, hipGetLastError());
+    return SCG_OK;
+}
+
+int scg_feature_gram(scg_ctx *c, int64_t n, const float *x, const float *y, const float *vx, const float *vy, const float *yv,
+                     int32_t n_seg, const int64_t *offsets, float *A, float *b, void *stream) {
+    const char *fn = "scg_feature_gram";
+    if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
+    if (!x || !y || !vx || !vy || !A || !offsets) return fail_in(c, SCG_ERR_INVALID, fn, "null array argument");
+    if (n < 0) return fail_in(c, SCG_ERR_INVALID, fn, "n must be >= 0");
+    if (n_seg < 1 || n_seg > SCG_GRAM_MAX_SEGMENTS) return fail_in(c, SCG_ERR_INVALID, fn, "n_seg out of range [1, SCG_GRAM_MAX_SEGMENTS]");
+    if ((yv == nullptr) != (b == nullptr)) return fail_in(c, SCG_ERR_INVALID, fn, "yv and b go together");
+    if (offsets[0] < 0 || offsets[n_seg] > n) return fail_in(c, SCG_ERR_INVALID, fn, "offsets leave [0, n]");
+    for (int g = 0; g < n_seg; ++g)
+        if (offsets[g + 1] < offsets[g]) return fail_in(c, SCG_ERR_INVALID, fn, "offsets decrease");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_feature_gram");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    GramArgs G;
+    G.x = x; G.y = y; G.vx = vx; G.vy = vy; G.yv = yv; G.A = A; G.b = b;
+    int n_active = 0;
+    for (int g = 0; g < n_seg; ++g) {
+        const int64_t cnt = offsets[g + 1] - offsets[g];
+        if (cnt > 0) {
+            G.seg[n_active] = g; G.start[n_active] = offsets[g]; G.count[n_active] = cnt;
+            ++n_active;
+        } else {                                          // an empty segment: all +0 (the kernel writes every entry of the others)
+            SCG_HIP(c, hipMemsetAsync(A + (size_t)g * NF * NF, 0, (size_t)NF * NF * sizeof(float), s));
+            if (b) SCG_HIP(c, hipMemsetAsync(b + (size_t)g * NF, 0, (size_t)NF * sizeof(float), s));
+        }
+    }
+    for (int g = n_active; g < GRAM_MAX_SEG; ++g) { G.seg[g] = 0; G.start[g] = 0; G.count[g] = 0; }
+    if (n_active) SCG_HIP(c, launch_feature_gram(G, n_active, s));
     return SCG_OK;
 }
 

@@ -1,0 +1,85 @@
+"""What scg_feature_gram costs (SPEC §16.1): the Gram of recorded states at --sizes samples per segment and --segs
+segments, against the materialising path (ScgContext.features in chunks of --chunk samples, then phi.T @ phi per chunk and
+segment). The two are timed interleaved, round by round, as tools/ab_bench.py does; one JSON line per case with the median
+times, the TFLOP/s counted on the triangle (n 1296 1297 flops) and its share of the 157.3 TF f32 matrix peak.
+The states are snapshots of the headline workload's env states, one per step-batch.
+--lib NAME=PATH times further builds of the library (another tiling: make's DEFS) in the same rounds.
+
+    python tools/gram_bench.py [--sizes 65536 1048576] [--segs 1 5] [--rounds 5] [--lib r3=path/to/libscg_hip_r3.so] [--out file.jsonl]
+"""
+import argparse
+import json
+import statistics
+
+import rig
+
+PEAK_TF = 157.3
+NF = 1296
+
+
+def recorded_states(n, envs):
+    """n states (x, y, vx, vy) on the device: the env states of the headline workload after each of ceil(n / envs) step-batches."""
+    import torch
+    ag = rig.headline_agent(envs=envs)
+    parts = []
+    for _ in range(-(-n // envs)):
+        ag.step_batch()
+        parts.append([t.clone() for t in ag.state.state()])
+    s = [torch.cat([p[d] for p in parts])[:n].contiguous() for d in range(4)]
+    torch.cuda.synchronize()
+    return ag, s
+
+
+def materialised(ctx, s, offsets, chunk):
+    import torch
+    out = torch.zeros((len(offsets) - 1, NF, NF), dtype=torch.float32, device=s[0].device)
+    for g in range(len(offsets) - 1):
+        for lo in range(offsets[g], offsets[g + 1], chunk):
+            hi = min(lo + chunk, offsets[g + 1])
+            phi = ctx.features([t[lo:hi] for t in s])
+            out[g].addmm_(phi.T, phi)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[65536, 1048576]); ap.add_argument("--segs", type=int, nargs="+", default=[1, 5])
+    ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--chunk", type=int, default=65536)
+    ap.add_argument("--envs", type=int, default=65536); ap.add_argument("--lib", nargs="*", default=[])
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    from skill_chaining_with_graphs_amd.core import ScgContext
+    ag, s = recorded_states(max(a.sizes) * max(a.segs), a.envs)
+    ctxs = {"shipped": ag.ctx}
+    for spec in a.lib:
+        name, path = spec.split("=", 1)
+        ctxs[name] = ScgContext(64, 0, ag.map, device=0, library=path)
+    lines = []
+    for n in a.sizes:
+        for k in a.segs:
+            off = [i * n for i in range(k + 1)]
+            sub = [t[: n * k] for t in s]
+            runs = {name: (lambda c=c: c.feature_gram(sub, off)) for name, c in ctxs.items()}
+            runs["materialised"] = lambda: materialised(ag.ctx, sub, off, a.chunk)
+            ref = runs["shipped"]()
+            err = float((runs["materialised"]() - ref).abs().max() / ref.abs().max())
+            times = {name: [] for name in runs}
+            for _ in range(a.rounds):
+                for name, fn in runs.items():
+                    times[name].append(rig.timed(fn, 1) * 1e3)
+            flops = n * k * NF * (NF + 1)
+            row = {"samples_per_segment": n, "segments": k, "rounds": a.rounds, "materialised_max_rel_diff": err}
+            for name, t in times.items():
+                ms = statistics.median(t)
+                row[name] = {"ms": round(ms, 3), "min_ms": round(min(t), 3), "tflops_triangle": round(flops / ms / 1e9, 2),
+                             "peak_fraction": round(flops / ms / 1e9 / PEAK_TF, 4)}
+            lines.append(json.dumps(row))
+            print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
