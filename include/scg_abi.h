@@ -359,6 +359,20 @@ int scg_fourier_features(scg_ctx *ctx, int32_t n, const float *x, const float *y
 int scg_feature_gram(scg_ctx *ctx, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
                      const float *yv /* may be NULL */, int32_t n_seg, const int64_t *offsets /* HOST */,
                      float *A, float *b /* NULL iff yv is NULL */, void *stream);
+/* Cross-feature Gram (SPEC §17.1): for each of n_seg segments (offsets as in scg_feature_gram) of n recorded samples with two states
+ * each, s_n = (x, y, vx, vy)[n] and s2_n = (x2, y2, vx2, vy2)[n],
+ *   C[g][1296][1296] = sum_n phi(s_n) phi(s2_n)^T   (rows: features of s, columns: features of s2; not symmetric)
+ * in scg_feature_gram's pinned order: per entry an fma chain over each slab of SCG_GRAM_SLAB consecutive samples of the segment, the
+ * slab sums added in order. C is fully overwritten (an empty segment: +0); C(s, s2) = C(s2, s)^T and C(s, s) = scg_feature_gram's A,
+ * both by bits; the same bits from every block build; the s2 arrays may alias the s arrays. Needs no map and writes C only.
+ * SCG_ERR_INVALID, nothing launched: a null array argument, n < 0, n_seg outside [1, SCG_GRAM_MAX_SEGMENTS], offsets that decrease or
+ * leave [0, n]. */
+#ifndef SCG_CROSS_GRAM_MACRO_TILE
+#define SCG_CROSS_GRAM_MACRO_TILE 96   /* features a side (rows and columns alike) of one workgroup's block of C: a test's edge list */
+#endif
+int scg_feature_cross_gram(scg_ctx *ctx, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                           const float *x2, const float *y2, const float *vx2, const float *vy2,
+                           int32_t n_seg, const int64_t *offsets /* HOST */, float *C, void *stream);
 /* Option.policy value part (SPEC §3.1): q[5][n] = Q_k(s, .) for one VF Wk[5][1296]. */
 int scg_q_values(scg_ctx *ctx, int32_t n, const float *x, const float *y, const float *vx,
                  const float *vy, const float *Wk, float *q, void *stream);

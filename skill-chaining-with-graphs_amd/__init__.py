@@ -35,7 +35,7 @@ def __getattr__(name):
     if name in ("Option", "InitiationClassifier"):
         from . import option
         return getattr(option, name)
-    if name in ("returns_to_go", "ridge_solve"):
+    if name in ("returns_to_go", "ridge_solve", "td_samples", "lstdq_solve"):
         from . import valuefit
         return getattr(valuefit, name)
     if name == "SkillChainingAgent":

@@ -40,6 +40,7 @@ PEER_MAX_RANKS = 8
 GRAM_SLAB = 1024            # include/scg_abi.h SCG_GRAM_*: SPEC §16.1's slab, the segment cap, one workgroup's block of A (features a side)
 GRAM_MAX_SEGMENTS = 64
 GRAM_MACRO_TILE = 96
+CROSS_GRAM_MACRO_TILE = 96  # include/scg_abi.h SCG_CROSS_GRAM_MACRO_TILE: one workgroup's block of SPEC §17.1's C (rows and columns alike)
 
 
 class ScgError(RuntimeError):
@@ -161,6 +162,7 @@ _SIGS = {
     "scg_pinball_step": (C.c_int, [_P, C.c_int32] + [_P] * 7 + [_P]),
     "scg_fourier_features": (C.c_int, [_P, C.c_int32] + [_P] * 5 + [_P]),
     "scg_feature_gram": (C.c_int, [_P, C.c_int64] + [_P] * 5 + [C.c_int32, _P, _P, _P, _P]),
+    "scg_feature_cross_gram": (C.c_int, [_P, C.c_int64] + [_P] * 8 + [C.c_int32, _P, _P, _P]),
     "scg_q_values": (C.c_int, [_P, C.c_int32] + [_P] * 6 + [_P]),
     "scg_q_update": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 12 + [C.c_uint32, _P]),
     "scg_classifier_predict": (C.c_int, [_P, C.c_int32] + [_P] * 4 + [_P]),

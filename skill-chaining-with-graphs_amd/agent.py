@@ -658,6 +658,129 @@ class SkillChainingAgent:
                 self.W[k].copy_(W_new[k])
         return report, W_new
 
+    def fit_values_lstdq(self, n_episodes: int = 4096, epsilon: float = 0.1, seed: Optional[int] = None, vfs=None,
+                         ridge: float = 1e-3, rounds: int = 1, apply: bool = False, keep: bool = False, interrupt: bool = False,
+                         choose: Optional[str] = None, trajectory=None, weights: Optional[torch.Tensor] = None):
+        """Least-squares policy evaluation of the GREEDY policy of the current weights, off-policy from recorded episodes (SPEC §17,
+        LSTD-Q): record_episodes() with the current policy, then per value function k of `vfs` (default: all) the items of
+        valuefit.td_samples, their greedy next actions a' and TD residuals delta under W^o = W, on the EVEN envs (the odd envs are
+        held out) A, b by ScgContext.feature_gram with the action as segment and yv = delta, C by ScgContext.feature_cross_gram on
+        the CONT samples with (a, a') as segment, Delta by valuefit.lstdq_solve (a float64 LU of 6480^2, on the device), W_k[a] <-
+        float32(W^o_k[a] + Delta_a). Every value function of a round is solved from the same W^o (an option's BOOT samples use the
+        root's W^o row). `rounds` = R repeats this on the same samples with W^o <- W^new: least-squares policy iteration.
+        Returns (report, W_new): report["rounds"][r]["vf"][k] holds n (fit samples per action), kinds (CONT / BOOT / END counts),
+        delta_norm, solve_residual, a_changed (share of samples whose a' differs from the round before; None in round 0) and, for
+        "fit" and "held_out", "td" and "mc", each old / new: n, rmse, mean_error of the frozen-policy TD residual and of Q against
+        §16.2's Monte-Carlo targets; report["rounds"][r]["W"] is the weights after round r and report["solve_seconds"] lists the
+        solves' wall times. `keep` adds per round and k "operands" (rows, kind, r, action, a2, delta, offsets, n_fit, c_index,
+        c_offsets, states, next_states, A, b, C, Delta), and report["targets"], report["trajectory"].
+        `trajectory`: a kept record to evaluate on instead of recording; `weights`: W^o of the first round instead of W.
+        apply=False leaves the agent as evaluate() does; apply=True copies the fitted rows of `vfs` into W and is refused with
+        shared weights. Non-finite rows of W^o are refused; a solve that fails raises ScgError and leaves the agent untouched."""
+        import time
+        from .valuefit import (TD_BOOT, TD_CONT, TD_END, error_stats, greedy_max, lstdq_residual, lstdq_solve, returns_to_go,
+                               td_residual, td_samples)
+        if apply and self.group is not None:
+            raise ScgError("fit_values_lstdq(apply=True) with shared weights: each rank would fit its own copy of W and the "
+                           "ranks would part; fit with apply=False and load one rank's result on all of them")
+        vfs = list(range(self.n_vf)) if vfs is None else [int(k) for k in vfs]
+        if any(not (0 <= k < self.n_vf) for k in vfs):
+            raise ValueError(f"vfs must name value functions 0..{self.n_vf - 1}")
+        if int(rounds) < 1:
+            raise ValueError("rounds must be >= 1")
+        W_cur = (self.W if weights is None else weights.to(self.W.device).view_as(self.W)).clone()
+        if not bool(torch.isfinite(W_cur[sorted(set(vfs) | {0})]).all()):
+            raise ScgError("fit_values_lstdq: the weights to evaluate hold non-finite values")
+        c = self.ctx.cfg
+        gamma, r_succ = float(c.gamma), float(c.r_option_success)
+        if trajectory is None:
+            traj, summary = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose)
+        else:
+            traj, summary = trajectory, None
+        ectx = self._eval_context(int(traj.n), epsilon, seed, None)[0]
+        flat = traj.to_numpy()
+        tg = returns_to_go(flat, gamma, r_succ)
+        dev = self.W.device
+        report = {"episodes": summary, "ridge": float(ridge), "gamma": gamma, "rounds": [], "solve_seconds": []}
+
+        def q_all(states, Wk):                                 # Q_k(s_n, .) [5][n] of a sample list, float32 as the kernel gives it
+            n = states[0].numel()
+            out = np.zeros((NUM_ACTIONS, n), np.float32)
+            for i in range(0, n, ectx.n_envs):
+                sl = slice(i, i + ectx.n_envs)
+                out[:, sl] = ectx.q_values([t[sl].contiguous() for t in states], Wk.contiguous().view(-1)).cpu().numpy()
+            return out
+
+        items = {}
+        for k in vfs:                                          # what does not change from round to round
+            it = td_samples(flat, k, r_succ)
+            fit = np.nonzero(it["env"] % 2 == 0)[0]
+            fit = fit[np.argsort(flat["action"][it["rows"][fit]], kind="stable")]      # the fit samples by action, (env, row) order within one
+            order = np.concatenate([fit, np.nonzero(it["env"] % 2 == 1)[0]])          # ... then the held-out half
+            rows = it["rows"][order]
+            act = flat["action"][rows].astype(np.int64)
+            n_a = np.bincount(act[:len(fit)], minlength=NUM_ACTIONS).astype(np.int64)
+            up = lambda at: [torch.from_numpy(np.ascontiguousarray(flat[f][at])).to(dev) for f in ("x", "y", "vx", "vy")]
+            items[k] = dict(rows=rows, kind=it["kind"][order], r=it["r"][order], act=act, n_fit=len(fit), n_a=n_a,
+                            offsets=np.concatenate([[0], np.cumsum(n_a)]).astype(np.int64), s=up(rows - 1), s2=up(rows),
+                            y=tg["y"][rows], A=None, a2=None)
+
+        for rnd in range(int(rounds)):
+            W_next = W_cur.clone()
+            out = {"vf": {}}
+            for k in vfs:
+                it = items[k]
+                kind, act, n_fit, idx = it["kind"], it["act"], it["n_fit"], np.arange(len(it["rows"]))
+                q_sa = q_all(it["s"], W_cur[k])[act, idx]
+                qn = q_all(it["s2"], W_cur[k])
+                m_k, a2 = greedy_max(qn)
+                m_0 = greedy_max(q_all(it["s2"], W_cur[0]))[0] if np.any(kind == TD_BOOT) else np.zeros_like(m_k)
+                delta = td_residual(it["r"], kind, gamma, q_sa, m_k, m_0)
+                A, b = ectx.feature_gram(it["s"], it["offsets"], torch.from_numpy(delta).to(dev))
+                if it["A"] is None:                            # sum phi phi^T does not change: the first round's is kept
+                    it["A"] = A
+                cont = np.nonzero(kind[:n_fit] == TD_CONT)[0]
+                key = NUM_ACTIONS * act[cont] + a2[cont]
+                c_index = cont[np.argsort(key, kind="stable")]  # the CONT fit samples by (a, a'), (env, row) order within a pair
+                c_off = np.concatenate([[0], np.cumsum(np.bincount(key, minlength=NUM_ACTIONS ** 2))]).astype(np.int64)
+                at = torch.from_numpy(c_index).to(dev)
+                Cm = ectx.feature_cross_gram([t[at].contiguous() for t in it["s"]], [t[at].contiguous() for t in it["s2"]], c_off)
+                Ah, bh = it["A"].cpu().numpy(), b.cpu().numpy()
+                Ch = Cm.cpu().numpy().reshape(NUM_ACTIONS, NUM_ACTIONS, NUM_FEATURES, NUM_FEATURES)
+                t0 = time.perf_counter()
+                Delta = lstdq_solve(Ah, Ch, bh, it["n_a"], gamma, ridge, self.ctx.scale, device=dev)
+                report["solve_seconds"].append(time.perf_counter() - t0)
+                w_old = W_cur[k].cpu().numpy()
+                w_new = (w_old.astype(np.float64) + Delta).astype(np.float32)
+                w_new[it["n_a"] == 0] = w_old[it["n_a"] == 0]
+                W_next[k] = torch.from_numpy(w_new).to(dev)
+                # the same frozen policy under the new weights: a' and the root's m_0 stay W^o's
+                q_sa_new = q_all(it["s"], W_next[k])[act, idx]
+                delta_new = td_residual(it["r"], kind, gamma, q_sa_new, q_all(it["s2"], W_next[k])[a2, idx], m_0)
+                rep = {"n": [int(v) for v in it["n_a"]], "delta_norm": float(np.sqrt(np.sum(Delta * Delta))),
+                       "kinds": {name: int(np.sum(kind == v)) for name, v in (("CONT", TD_CONT), ("BOOT", TD_BOOT), ("END", TD_END))},
+                       "solve_residual": lstdq_residual(Ah, Ch, bh, it["n_a"], gamma, ridge, self.ctx.scale, Delta),
+                       "a_changed": None if it["a2"] is None else (float(np.mean(a2 != it["a2"])) if len(a2) else 0.0)}
+                zero = np.zeros(len(idx))
+                for name, sl in (("fit", slice(0, n_fit)), ("held_out", slice(n_fit, None))):
+                    rep[name] = {"td": {"old": error_stats(delta[sl], zero[sl]), "new": error_stats(delta_new[sl], zero[sl])},
+                                 "mc": {"old": error_stats(q_sa[sl], it["y"][sl]), "new": error_stats(q_sa_new[sl], it["y"][sl])}}
+                if keep:
+                    rep["operands"] = {"rows": it["rows"], "kind": kind, "r": it["r"], "action": act, "a2": a2, "delta": delta,
+                                       "offsets": it["offsets"], "n_fit": n_fit, "c_index": c_index, "c_offsets": c_off,
+                                       "states": it["s"], "next_states": it["s2"], "A": it["A"], "b": b, "C": Cm, "Delta": Delta}
+                it["a2"] = a2
+                out["vf"][k] = rep
+            W_cur = W_next
+            out["W"] = W_cur.clone()
+            report["rounds"].append(out)
+        if keep:
+            report["targets"], report["trajectory"] = tg, traj
+        if apply:
+            for k in vfs:
+                self.W[k].copy_(W_cur[k])
+        return report, W_cur
+
     def _mirror_training(self, side: ScgContext, epsilon: float) -> None:
         """Copy the training run's settings into a side context (evaluation, trials): its hyper-parameters (epsilon aside),
         parents and gestation mask — classifiers in use, no success counts kept; its own state, t and counters untouched."""

@@ -518,6 +518,26 @@ class ScgContext:
                    off.ctypes.data_as(C.c_void_p), _ptr(A), _ptr(b), self._stream())
         return A if b is None else (A, b)
 
+    def feature_cross_gram(self, s, s2, offsets):
+        """SPEC §17.1: C[g] = sum phi(s_n) phi(s2_n)^T over segment g = samples offsets[g] .. offsets[g+1]-1 of the state pairs
+        (`s`, `s2`: four [n] tensors each, which may be the same tensors; `offsets` as for feature_gram). Returns C
+        [n_seg][1296][1296]: rows the features of s, columns those of s2. phi is not materialised; the sums have §16.1's pinned order."""
+        n = s[0].numel()
+        a = self._chk4(s, n, "state")
+        b = self._chk4(s2, n, "successor state")
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        n_seg = len(off) - 1
+        if not (1 <= n_seg <= _lib.GRAM_MAX_SEGMENTS):
+            raise ScgError(f"feature_cross_gram: offsets must name 1 .. {_lib.GRAM_MAX_SEGMENTS} segments")
+        if off[0] < 0 or off[-1] > n or np.any(np.diff(off) < 0):
+            raise ScgError("feature_cross_gram: offsets must be non-decreasing and inside [0, n]")
+        if n == 0:                                           # (an empty tensor has no address: the entry point refuses a null array)
+            a = b = (torch.zeros(1, dtype=torch.float32, device=self.device),) * 4
+        Cm = torch.empty((n_seg, NUM_FEATURES, NUM_FEATURES), dtype=torch.float32, device=self.device)
+        self._call("scg_feature_cross_gram", C.c_int64(n), *[_ptr(t) for t in a], *[_ptr(t) for t in b], n_seg,
+                   off.ctypes.data_as(C.c_void_p), _ptr(Cm), self._stream())
+        return Cm
+
     def q_values(self, s, Wk: torch.Tensor) -> torch.Tensor:
         n = s[0].numel()
         x, y, vx, vy = self._chk4(s, n, "state")

@@ -18,6 +18,7 @@
 //                            tagged-word exchanges; a fit whose workgroups cannot run together gives up after a wall-clock wait,
 //                            leaves its row untouched and raises the ctx's asynchronous status word
 //   scg_gram_kernel.hpp      SPEC §16.1's feature Gram: here only its arguments and launch (the kernel is compiled in scg_gram.hip)
+//   scg_cross_gram_kernel.hpp  SPEC §17.1's cross-feature Gram: likewise (the kernel is compiled in scg_cross_gram.hip)
 // scg_rollout_variants.hip is the second translation unit: every other instantiation of rollout_kernel (SPEC §10's record, §11's
 // interruption, §14's value-ranked choice, §15's audit: the table in scg_rollout_kernel.hpp) and trial_kernel<true>, reached through
 // launch_rollout<REC, Args> / launch_trial_record, which the two kernel headers declare.
@@ -48,6 +49,7 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 #include "scg_apply_kernels.hpp"
 #include "scg_aux_kernels.hpp"
 #include "scg_gram_kernel.hpp"
+#include "scg_cross_gram_kernel.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -1248,6 +1250,41 @@ int scg_feature_gram(scg_ctx *c, int64_t n, const float *x, const float *y, cons
     }
     for (int g = n_active; g < GRAM_MAX_SEG; ++g) { G.seg[g] = 0; G.start[g] = 0; G.count[g] = 0; }
     if (n_active) SCG_HIP(c, launch_feature_gram(G, n_active, s));
+    return SCG_OK;
+}
+
+int scg_feature_cross_gram(scg_ctx *c, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                           const float *x2, const float *y2, const float *vx2, const float *vy2,
+                           int32_t n_seg, const int64_t *offsets, float *Cm, void *stream) {
+    const char *fn = "scg_feature_cross_gram";
+    if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
+    if (!x || !y || !vx || !vy || !x2 || !y2 || !vx2 || !vy2 || !Cm || !offsets) return fail_in(c, SCG_ERR_INVALID, fn, "null array argument");
+    if (n < 0) return fail_in(c, SCG_ERR_INVALID, fn, "n must be >= 0");
+    if (n_seg < 1 || n_seg > SCG_GRAM_MAX_SEGMENTS) return fail_in(c, SCG_ERR_INVALID, fn, "n_seg out of range [1, SCG_GRAM_MAX_SEGMENTS]");
+    if (offsets[0] < 0 || offsets[n_seg] > n) return fail_in(c, SCG_ERR_INVALID, fn, "offsets leave [0, n]");
+    for (int g = 0; g < n_seg; ++g)
+        if (offsets[g + 1] < offsets[g]) return fail_in(c, SCG_ERR_INVALID, fn, "offsets decrease");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_feature_cross_gram");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    CrossGramArgs G;
+    const float *src[2][4] = {{x, y, vx, vy}, {x2, y2, vx2, vy2}};
+    for (int h = 0; h < 2; ++h)
+        for (int d = 0; d < 4; ++d) G.s[h][d] = src[h][d];
+    G.C = Cm;
+    int n_active = 0;
+    for (int g = 0; g < n_seg; ++g) {
+        const int64_t cnt = offsets[g + 1] - offsets[g];
+        if (cnt > 0) {                                    // kept longest first (ties: as listed): the longest chains are dispatched first
+            int at = n_active++;
+            for (; at > 0 && G.count[at - 1] < cnt; --at) { G.seg[at] = G.seg[at - 1]; G.start[at] = G.start[at - 1]; G.count[at] = G.count[at - 1]; }
+            G.seg[at] = g; G.start[at] = offsets[g]; G.count[at] = cnt;
+        } else {                                          // an empty segment: all +0 (the kernel writes every entry of the others)
+            SCG_HIP(c, hipMemsetAsync(Cm + (size_t)g * NF * NF, 0, (size_t)NF * NF * sizeof(float), s));
+        }
+    }
+    for (int g = n_active; g < SCG_GRAM_MAX_SEGMENTS; ++g) { G.seg[g] = 0; G.start[g] = 0; G.count[g] = 0; }
+    if (n_active) SCG_HIP(c, launch_feature_cross_gram(G, n_active, s));
     return SCG_OK;
 }
 

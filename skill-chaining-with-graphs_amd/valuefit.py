@@ -1,11 +1,13 @@
-"""Least-squares value fit on realised returns (SPEC §16): the Monte-Carlo targets of recorded episodes and the ridge solve of
-the normal equations whose matrix scg_feature_gram forms. Host code, float64; the hot part is ScgContext.feature_gram."""
+"""Least-squares value fits on recorded episodes. SPEC §16: the Monte-Carlo targets and the ridge solve of the normal equations
+whose matrix scg_feature_gram forms. SPEC §17: the items of the least-squares TD fixed point (LSTD-Q) and the solve of its
+block system, whose off-diagonal part scg_feature_cross_gram forms. Host code, float64; the hot parts are
+ScgContext.feature_gram and ScgContext.feature_cross_gram."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from ._lib import TRIAL_SUCCESS
+from ._lib import TRIAL_SUCCESS, ScgError
 from .trajectory import Trajectory
 
 
@@ -73,3 +75,107 @@ def error_stats(q, y) -> dict:
     e = q - y
     return {"n": int(len(y)), "rmse": float(np.sqrt(np.mean(e * e))), "mean_error": float(np.mean(e))}
 
+
+TD_CONT, TD_BOOT, TD_END = 0, 1, 2      # SPEC §17.2's kinds: bootstrap from Q_k(s'), from the root's value of s' (§5's exit rule), from nothing
+
+
+def td_samples(traj, k: int, r_option_success: float = 0.0) -> dict:
+    """SPEC §17.2's items of value function k on a Trajectory of one-episode rollouts (or its to_numpy() dict), in (env, row)
+    order: `rows` (int64 indices into the flattened record: s' is that row's state, s the state of the row before), `env`,
+    `kind` (uint8: TD_CONT / TD_BOOT / TD_END) and `r` (float64: the row's reward, plus r_option_success on an option's
+    SUCCESS row). The root (k = 0) takes every step row of every env, kind CONT unless done (a time limit is terminal); option k
+    the rows with vf = k, kind CONT while term = 0, BOOT where the option ends and the episode goes on, END where both end.
+    There are no gestation items."""
+    flat = traj.to_numpy() if isinstance(traj, Trajectory) else traj
+    off = np.asarray(flat["offsets"], np.int64)
+    L = np.diff(off)
+    env = np.repeat(np.arange(len(L)), L)
+    step = (np.arange(int(off[-1])) - off[:-1][env]) >= 1
+    done, term = np.asarray(flat["done"]) != 0, np.asarray(flat["term"])
+    if int(k) == 0:
+        rows = np.nonzero(step)[0]
+        kind = np.where(done[rows], TD_END, TD_CONT)
+        r = np.asarray(flat["reward"], np.float64)[rows]
+    else:
+        rows = np.nonzero(step & (np.asarray(flat["vf"]) == int(k)))[0]
+        kind = np.where(term[rows] == 0, TD_CONT, np.where(done[rows], TD_END, TD_BOOT))
+        r = np.asarray(flat["reward"], np.float64)[rows] + np.where(term[rows] == TRIAL_SUCCESS, float(r_option_success), 0.0)
+    return {"rows": rows.astype(np.int64), "env": env[rows], "kind": kind.astype(np.uint8), "r": r}
+
+
+def greedy_max(q):
+    """§5's max and its lowest index for q [5][n] (binary32 as scg_q_values gives it): m = q[0]; m = max(m, q[1]); ...;
+    a' = the lowest a with q[a] = m. Returns (m float32 [n], a' int64 [n])."""
+    q = np.asarray(q, np.float32)
+    m = q[0].copy()
+    for a in range(1, q.shape[0]):
+        m = np.maximum(m, q[a])
+    return m, np.argmax(q == m[None, :], axis=0).astype(np.int64)
+
+
+def td_residual(r, kind, gamma: float, q_sa, m_k, m_0) -> np.ndarray:
+    """SPEC §17.2: delta = r + gamma [CONT] m_k + gamma [BOOT] m_0 - Q_k(s, a), as (r + gamma m) - q in float64 (m the one
+    maximum the sample's kind names, no term for END), rounded to binary32 once."""
+    kind = np.asarray(kind)
+    m = np.where(kind == TD_CONT, np.asarray(m_k, np.float64), np.where(kind == TD_BOOT, np.asarray(m_0, np.float64), 0.0))
+    t = np.where(kind == TD_END, np.asarray(r, np.float64), np.asarray(r, np.float64) + float(gamma) * m)
+    return (t - np.asarray(q_sa, np.float64)).astype(np.float32)
+
+
+def lstdq_matrix(A, C, n, gamma: float, ridge: float, scale):
+    """SPEC §17.3's matrix over the actions that have samples: (M float64 [m F][m F], act) with block (i, j) of M =
+    [i = j] (A[a_i] + Lambda_{a_i}) - gamma C[a_i][a_j], a = act[.], Lambda_a = diag(ridge max(n[a], 1) / scale_f^2). A's lower
+    triangle is read, as by ridge_solve."""
+    A, C = np.asarray(A), np.asarray(C)
+    n = np.asarray(n, np.int64).reshape(-1)
+    F = A.shape[-1]
+    act = [a for a in range(A.shape[0]) if n[a] > 0]
+    lam = 1.0 / np.asarray(scale, np.float64) ** 2
+    M = np.empty((len(act) * F, len(act) * F), np.float64)
+    for i, a in enumerate(act):
+        for j, a2 in enumerate(act):
+            blk = M[i * F:(i + 1) * F, j * F:(j + 1) * F]
+            blk[...] = C[a][a2]                             # (to float64 first: the product is not to be rounded to C's binary32)
+            blk *= -float(gamma)
+            if i == j:
+                T = np.tril(A[a]).astype(np.float64)
+                blk += T + np.tril(T, -1).T
+                blk[np.diag_indices(F)] += float(ridge) * max(int(n[a]), 1) * lam
+    return M, act
+
+
+def lstdq_solve(A, C, b, n, gamma: float, ridge: float, scale, device=None) -> np.ndarray:
+    """SPEC §17.3: Delta [n_act][F] float64 with M Delta = b, M as lstdq_matrix builds it from A [n_act][F][F], C
+    [n_act][n_act][F][F], the counts n [n_act] and `scale` [F]; b [n_act][F]. A dense LU in float64, on the host (LAPACK) or, with
+    `device` a torch device, there. Any F. An action with n[a] = 0 is taken out of the system and gets Delta = 0 exactly. A solve
+    that fails or gives a non-finite value raises ScgError."""
+    b = np.asarray(b, np.float64)
+    M, act = lstdq_matrix(A, C, n, gamma, ridge, scale)
+    out = np.zeros_like(b)
+    if not act:
+        return out
+    rhs = np.concatenate([b[a] for a in act])
+    try:
+        if device is None:
+            x = np.linalg.solve(M, rhs)
+        else:
+            x = torch.linalg.solve(torch.from_numpy(M).to(device), torch.from_numpy(rhs).to(device)).cpu().numpy()
+    except (np.linalg.LinAlgError, RuntimeError) as e:
+        raise ScgError(f"lstdq_solve: the {M.shape[0]} x {M.shape[0]} system could not be solved: {e}") from None
+    if not np.isfinite(x).all():
+        raise ScgError("lstdq_solve: the solution holds non-finite values")
+    F = b.shape[1]
+    for i, a in enumerate(act):
+        out[a] = x[i * F:(i + 1) * F]
+    return out
+
+
+def lstdq_residual(A, C, b, n, gamma: float, ridge: float, scale, delta) -> float:
+    """||M Delta - b|| / (||M|| ||Delta|| + ||b||) of a solution of SPEC §17.3's system (Frobenius / 2-norms, float64)."""
+    M, act = lstdq_matrix(A, C, n, gamma, ridge, scale)
+    if not act:
+        return 0.0
+    rhs = np.concatenate([np.asarray(b, np.float64)[a] for a in act])
+    x = np.concatenate([np.asarray(delta, np.float64)[a] for a in act])
+    den = np.linalg.norm(M) * np.linalg.norm(x) + np.linalg.norm(rhs)
+    return float(np.linalg.norm(M @ x - rhs) / den) if den > 0 else 0.0
