@@ -47,7 +47,9 @@ __device__ __forceinline__ float2 sincospi_cs(float t) {   // returns (cos, sin)
     float sp = fmaf(z, S4, S3); sp = fmaf(z, sp, S2); sp = fmaf(z, sp, S1); sp = fmaf(z, sp, S0); sp = sp * r;
     float cp = fmaf(z, C4, C3); cp = fmaf(z, cp, C2); cp = fmaf(z, cp, C1); cp = fmaf(z, cp, C0);
     cp = fmaf(z, cp, 1.0f);
-    const int q = (int)n & 3;
+    // n >= 2^26 is a multiple of 4: q = 0. The conversion saturates at INT_MAX (low bits 3) from 2^31 on, so n is capped first;
+    // below -2^31 it saturates at INT_MIN, whose low bits are 0 already
+    const int q = (int)fminf(n, 0x1p30f) & 3;
     float c = cp, s = sp;
     if (q == 1) { c = -sp; s = cp; }
     else if (q == 2) { c = -cp; s = -sp; }

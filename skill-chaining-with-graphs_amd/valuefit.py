@@ -15,8 +15,9 @@ def returns_to_go(traj, gamma: float, r_option_success: float, device="cpu") -> 
     """SPEC §16.2 on a Trajectory of one-episode rollouts (or its to_numpy() dict): for every row, in (env, row) order as
     to_numpy() lays them out, float64
       g       the discounted task return-to-go  g_j = reward[j] + gamma g_{j+1},  g_L = 0  (a time limit is terminal)
-      y       the target: g_j, plus gamma^(tau - j) r_option_success on a row of option o >= 1 whose run of rows with vf = o ends,
-              at row tau, in SUCCESS
+      y       the target: g_j, plus gamma^(tau - j) r_option_success on a row of option o >= 1 whose execution ends, at row tau,
+              in SUCCESS; tau is the first row >= j of the run of rows with vf = o whose term is not 0 (Trajectory.segments'
+              cut), or the run's last row: a TIMEOUT followed at once by a new entry of the same option earns no bonus
       sample  False on every env's row 0 (the begin row: no step), True elsewhere
     and `offsets` [n + 1]. Vectorised over the envs, a loop over the rows, on `device` (torch, float64)."""
     flat = traj.to_numpy() if isinstance(traj, Trajectory) else traj
@@ -33,16 +34,18 @@ def returns_to_go(traj, gamma: float, r_option_success: float, device="cpu") -> 
     Lt = torch.from_numpy(L).to(dev)
     g = torch.zeros((n, rows + 1), dtype=torch.float64, device=dev)
     y = torch.zeros_like(g)
-    tau = torch.zeros(n, dtype=torch.int64, device=dev)            # the last row of the run the row below belongs to ...
+    tau = torch.zeros(n, dtype=torch.int64, device=dev)            # the last row of the execution the row below belongs to ...
     succ = torch.zeros(n, dtype=torch.bool, device=dev)            # ... and whether that row's term is SUCCESS
+    disc = torch.tensor([float(gamma) ** k * float(r_option_success) for k in range(rows + 1)], dtype=torch.float64, device=dev)
     for j in range(rows - 1, 0, -1):
         live = j < Lt
         g[:, j] = torch.where(live, reward[:, j] + gamma * g[:, j + 1], g[:, j])
-        new_run = (j + 1 >= Lt) | (vf[:, j + 1] != vf[:, j])
+        # an execution ends with the env's last row, before a row of another vf, and on a row whose option ended (term != 0):
+        # an option that timed out and was entered again at once is two executions under one vf
+        new_run = (j + 1 >= Lt) | (vf[:, j + 1] != vf[:, j]) | (term[:, j] != 0)
         tau = torch.where(new_run, torch.full_like(tau, j), tau)
         succ = torch.where(new_run, term[:, j] == TRIAL_SUCCESS, succ)
-        bonus = torch.where(succ & (vf[:, j] >= 1), float(r_option_success) * torch.pow(
-            torch.full((n,), float(gamma), dtype=torch.float64, device=dev), (tau - j).to(torch.float64)), torch.zeros_like(g[:, j]))
+        bonus = torch.where(succ & (vf[:, j] >= 1), disc[tau - j], torch.zeros_like(g[:, j]))
         y[:, j] = torch.where(live, g[:, j] + bonus, y[:, j])
     e, r = torch.from_numpy(env).to(dev), torch.from_numpy(row).to(dev)
     return {"offsets": off, "g": g[e, r].cpu().numpy(), "y": y[e, r].cpu().numpy(), "sample": row >= 1}

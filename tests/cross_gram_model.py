@@ -3,12 +3,13 @@
 `cross(phi, phi2, offsets, rows, cols)` is §17.1 on index lists: §16.1's two-level chains (tests/gram_model.py) with phi_i(s_n)
 and phi_j(s2_n) as the operands, rows of the result the features of s, columns those of s2. `cross_chain_bound` is
 gram_model.chain_bound's formula with sum |phi_i(s) phi_j(s2)| and the float64 product it bounds the distance to.
+`lattice_cross` is the whole-matrix form through gram_model.chain (lattice prefix exact, real tail by the fma32 chain).
 
 `scalar_items` and `scalar_residual` are §17.2 for one env and one sample as plain loops, the yardsticks of valuefit.td_samples
 and of the residuals SkillChainingAgent.fit_values_lstdq forms."""
 import numpy as np
 
-from gram_model import SLAB, fma32, slabs
+from gram_model import SLAB, chain, fma32, slabs
 
 CONT, BOOT, END = 0, 1, 2
 SUCCESS = 1                                                  # SCG_TRIAL_SUCCESS
@@ -26,6 +27,13 @@ def cross(phi, phi2, offsets, rows, cols):
                 P = fma32(phi[n, rows][:, None], phi2[n, cols][None, :], P)
             out[g] = out[g] + P
     return out
+
+
+def lattice_cross(phi, phi2, offsets, lattice=None, rows=None, cols=None):
+    """C_g by gram_model.chain: whole (rows / cols None) or on index lists; `lattice` marks the samples both of whose states are
+    lattice states, a prefix of every slab."""
+    phi, phi2 = np.asarray(phi, np.float32), np.asarray(phi2, np.float32)
+    return chain(phi if rows is None else phi[:, rows], phi2 if cols is None else phi2[:, cols], offsets, lattice)
 
 
 def cross_chain_bound(phi, phi2, offsets):

@@ -1,5 +1,6 @@
 """SkillChainingAgent.fit_values_to_returns (SPEC §16) on a 256-env agent with one enabled option on the rig's dense map:
-its targets against the scalar model of §16.2, each (A, b) it formed against the host model of §16.1, its weights against the
+its targets against the scalar model of §16.2 (also with an option step limit of 3, where option 2 times out inside its initiation
+set and is entered again: several executions in one run of a vf), each (A, b) it formed against the host model of §16.1, its weights against the
 normal equations, the objective's inequality, rows without samples, apply=False / apply=True, and the report tool at toy size."""
 import numpy as np
 import pytest
@@ -23,14 +24,13 @@ RUN, IDLE = (0, 2), 1            # the value functions that run in the record, a
 IDX = GM.index_set(_lib.GRAM_MACRO_TILE)
 
 
-@pytest.fixture(scope="module")
-def fitted():
+def fit_agent(**hp):
     """The agent and one fit with everything kept. Option 2 (enabled) is offered everywhere outside its target, option 1's set:
     everything but a small disc round the start, so it is offered at the start and succeeds when the ball leaves the disc.
     Option 1 gestates (known, never selected): value function 1 never runs. W is random at a scale that has nothing to do
     with the returns; half the actions are random (every episode has the one start)."""
     m = dense_map()
-    ag = SkillChainingAgent(m, 256, 2, seed=5, block_envs=256, **dict(HP, max_episode_steps=63))
+    ag = SkillChainingAgent(m, 256, 2, seed=5, block_envs=256, **dict(HP, max_episode_steps=63, **hp))
     ag.init_weights(std=0.05, seed=3)
     sx, sy = (float(v) for v in m.starts[0])
     clf = np.zeros((3, 8), np.float32)
@@ -43,8 +43,26 @@ def fitted():
     report, W_new = ag.fit_values_to_returns(n_episodes=N_EPISODES, epsilon=EPS, seed=9, ridge=RIDGE, keep=True)
     torch.cuda.synchronize()
     orc, _ = make_oracle("pinball_simple")
-    yield dict(ag=ag, W0=W0, report=report, W_new=W_new, orc=orc)
-    ag.ctx.close()
+    return dict(ag=ag, W0=W0, report=report, W_new=W_new, orc=orc)
+
+
+@pytest.fixture(scope="module")
+def fitted():
+    f = fit_agent()
+    yield f
+    f["ag"].ctx.close()
+
+
+SHORT_OPTION_STEPS = 3           # option 2 needs more steps than this to leave the start's disc: it times out inside its own initiation set
+
+
+@pytest.fixture(scope="module")
+def fitted_short():
+    """The same agent with max_option_steps = 3: option 2 ends by TIMEOUT while the ball is still inside its initiation set, is the
+    candidate again on the next step (SPEC §4.2) and is entered again: several executions in one run of vf = 2."""
+    f = fit_agent(max_option_steps=SHORT_OPTION_STEPS)
+    yield f
+    f["ag"].ctx.close()
 
 
 def test_the_record_is_what_the_test_needs(fitted):
@@ -77,6 +95,40 @@ def test_targets_equal_the_scalar_model(fitted):
         for a in range(5):
             seg = fit[op["offsets"][a]: op["offsets"][a + 1]]
             assert np.all(flat["action"][seg] == a) and np.all(np.diff(seg) > 0)
+
+
+def test_targets_follow_executions_when_an_option_times_out_and_is_entered_again(fitted_short):
+    """SPEC §16.2's tau on a record in which one run of vf = 2 holds several executions: targets["y"] against the scalar model
+    bit for bit, and the rows that carry a bonus are exactly the rows of Trajectory.segments' runs of an option that end in SUCCESS."""
+    rep, ag = fitted_short["report"], fitted_short["ag"]
+    traj, tg = rep["trajectory"], rep["targets"]
+    flat = traj.to_numpy()
+    off, vf, term = flat["offsets"], flat["vf"], flat["term"]
+    gamma, r_succ = float(ag.ctx.cfg.gamma), float(ag.ctx.cfg.r_option_success)
+    assert ag.ctx.cfg.max_option_steps == SHORT_OPTION_STEPS and r_succ == 100.0
+    reentered = then_success = 0
+    for e in range(N_EPISODES):
+        sl = slice(off[e], off[e + 1])
+        v, t = vf[sl], term[sl]
+        for j in range(len(v) - 1):
+            if t[j] == _lib.TRIAL_TIMEOUT and v[j + 1] == v[j]:
+                reentered += 1
+                k = j + 1
+                while k + 1 < len(v) and v[k + 1] == v[j] and t[k] != _lib.TRIAL_SUCCESS:
+                    k += 1
+                then_success += int(t[k] == _lib.TRIAL_SUCCESS)
+        g, y = GM.scalar_targets(flat["reward"][sl], v, t, gamma, r_succ)
+        assert np.array_equal(tg["g"][sl], g) and np.array_equal(tg["y"][sl], y), e
+        paid = np.zeros(len(v), bool)                                # ... and by the record's own segments
+        for s in traj.segments(e):
+            if s["vf"] >= 1 and s["term"] == _lib.TRIAL_SUCCESS:
+                paid[max(s["start"], 1): s["end"] + 1] = True
+                rows = np.arange(max(s["start"], 1), s["end"] + 1)
+                want = tg["g"][sl][rows] + np.array([gamma ** int(s["end"] - j) * r_succ for j in rows])
+                assert np.array_equal(tg["y"][sl][rows], want), (e, s)
+        assert np.array_equal(tg["y"][sl] != tg["g"][sl], paid), e
+    print(f"TIMEOUT rows followed by the same vf: {reentered}, of them followed by a SUCCESS in the same vf run: {then_success}")
+    assert reentered >= 50 and then_success >= 20
 
 
 @pytest.mark.parametrize("k", RUN)

@@ -1,5 +1,6 @@
 """SPEC §16 on the host: the yardsticks of tests/test_gpu_gram.py and test_gpu_value_fit.py are themselves held to something —
-gram_model.fma32 to libm's fmaf, valuefit.returns_to_go to a scalar loop, valuefit.ridge_solve to its normal equations."""
+gram_model.fma32 to libm's fmaf, the lattice shortcut of whole matrices (gram_model.chain) to the plain chains, valuefit.returns_to_go
+to a scalar loop and to hand-made records whose bonus is known exactly, valuefit.ridge_solve to its normal equations."""
 import ctypes
 import ctypes.util
 
@@ -112,6 +113,57 @@ def test_model_rhs_chain(phi_small):
     assert b[0][0] == want0
 
 
+# ---------------------------------------------------------------------------------------------------- the lattice shortcut
+
+def test_lattice_features_are_exactly_minus_one_zero_or_one():
+    orc, _ = make_oracle("pinball_simple")
+    pos, vel = np.array(GM.LATTICE_POS, np.float32), np.array(GM.LATTICE_VEL, np.float32)
+    g = np.stack(np.meshgrid(pos, pos, vel, vel, indexing="ij"), -1).reshape(-1, 4)      # all 81 lattice states
+    phi = orc.features(*(np.ascontiguousarray(g[:, d]) for d in range(4)))
+    assert phi.shape == (81, NF) and np.isin(phi, [-1.0, 0.0, 1.0]).all()
+    assert np.all(phi[:, 0] == 1) and {-1.0, 0.0, 1.0} == set(np.unique(phi))
+    drawn = orc.features(*GM.lattice_states(500, 4))
+    assert np.isin(drawn, [-1.0, 0.0, 1.0]).all() and len(np.unique(drawn, axis=0)) > 70           # the draw reaches most of the 81
+
+
+# a segment of two slabs whose real-valued samples lie on both sides of the slab edge (950 lattice + 74 real | 40 real: gram's
+# chunk edge at 960 and the slab edge at 1024 are inside real samples), an empty one, and 28 lattice + 9 real samples (the cross
+# kernel's chunk edge at 32 inside the tail); the first two samples belong to no segment
+MIXED_RUNS = [(2, False), (950, True), (114, False), (28, True), (9, False), (3, True)]
+MIXED_OFF = [2, 1066, 1066, 1103]
+
+
+def test_lattice_shortcut_equals_the_plain_chains_on_the_index_set():
+    orc, _ = make_oracle("pinball_simple")
+    s, lat = GM.mixed_states(MIXED_RUNS, 40)
+    assert len(lat) == 1106 and lat.sum() == 981 and not lat[1100:1103].any()
+    phi = orc.features(*s)
+    idx = GM.index_set()
+    yv = np.random.default_rng(41).standard_normal(len(lat)).astype(np.float32)
+    yv[lat] = np.random.default_rng(42).integers(-3, 4, int(lat.sum())).astype(np.float32)
+    assert_bits_equal(GM.lattice_gram(phi, MIXED_OFF, lat, idx, idx), GM.gram(phi, MIXED_OFF, idx, idx), msg="A by the shortcut:")
+    assert_bits_equal(GM.lattice_rhs(phi, yv, MIXED_OFF, lat), GM.rhs(phi, yv, MIXED_OFF), msg="b by the shortcut:")
+    assert_bits_equal(GM.lattice_gram(phi, MIXED_OFF, None, idx, idx), GM.gram(phi, MIXED_OFF, idx, idx), msg="A without a mask:")
+    with pytest.raises(AssertionError):                              # a lattice sample behind a real one in its slab
+        GM.lattice_gram(phi, [0, 1103], lat, idx[:2], idx[:2])
+    with pytest.raises(AssertionError):                              # a real sample marked as a lattice one
+        GM.lattice_gram(phi, [0, 2], np.ones(len(lat), bool), idx[:2], idx[:2])
+
+
+def test_whole_matrix_of_one_sample_is_the_rounded_product():
+    """One sample a segment: the chain from +0 is one fma, float32(float64(phi_i) float64(phi_j)) with -0 turned into +0."""
+    orc, _ = make_oracle("pinball_simple")
+    s = GM.gram_states(3, 6)
+    s[2][1], s[3][1] = 0.0, 2.0                                      # a corner velocity: features that are exactly +-0 and +-1
+    phi = orc.features(*s)
+    A = GM.lattice_gram(phi, [0, 1, 2, 3])
+    p = phi.astype(np.float64)
+    want = (p[:, :, None] * p[:, None, :]).astype(np.float32) + np.float32(0)
+    assert A.shape == (3, NF, NF) and (phi[1] == 0).any()
+    assert_bits_equal(A, want, msg="one-sample A:")
+    assert_bits_equal(A[:, 0, :], phi + np.float32(0), msg="row 0 of a one-sample A:")
+
+
 # ---------------------------------------------------------------------------------------------------- §16.2: returns_to_go
 
 SUCCESS, EPISODE_END, LEFT, TIMEOUT = 1, 2, 3, 4
@@ -155,6 +207,65 @@ def test_returns_to_go_equals_the_scalar_loop(gamma, r_succ):
     assert y[1] - g[1] == pytest.approx(99.0) and y[2] - g[2] == 100.0 and y[4] == g[4] and y[5] == g[5]
     g, y = scalar_targets(*zip(*HAND["left initiation"]), 0.99, 100.0)
     assert y == g
+
+
+# Executions inside one run of a vf (SPEC §16.2's tau): (vf, term) per step and the bonus each row must get at gamma = 0.5,
+# r_option_success = 100, the begin row in front. A power of 0.5 times 100 is exact, so with rewards of 0 y IS the bonus.
+INTERRUPTED = 5
+EXECUTIONS = {
+    "a timeout inside the initiation set, entered again at once, then success":
+        ([(0, 0), (1, 0), (1, TIMEOUT), (1, 0), (1, SUCCESS), (0, 0), (0, 0)], [0, 0, 0, 0, 50, 100, 0, 0]),
+    "timeout, timeout, success":
+        ([(2, 0), (2, TIMEOUT), (2, TIMEOUT), (2, 0), (2, 0), (2, SUCCESS)], [0, 0, 0, 0, 25, 50, 100]),
+    "an interrupted run that is entered again":
+        ([(1, 0), (1, INTERRUPTED), (1, 0), (1, SUCCESS), (0, 0)], [0, 0, 0, 50, 100, 0]),
+    "option 1 followed directly by option 2":
+        ([(1, 0), (1, SUCCESS), (2, 0), (2, 0), (2, SUCCESS), (1, 0), (1, LEFT)], [0, 50, 100, 25, 50, 100, 0, 0]),
+    "a success followed by a run that the record's end cuts":
+        ([(1, SUCCESS), (1, 0), (1, 0)], [0, 100, 0, 0]),
+    "the episode ends inside an execution":
+        ([(0, 0), (2, 0), (2, TIMEOUT), (2, 0), (2, EPISODE_END)], [0, 0, 0, 0, 0, 0]),
+    "a begin row only": ([], [0]),
+}
+
+
+def exec_flat(rewards=None):
+    envs = [[(0, 0)] + steps for steps, _ in EXECUTIONS.values()]
+    off = np.concatenate([[0], np.cumsum([len(e) for e in envs])]).astype(np.int64)
+    flat = {"offsets": off, "vf": np.array([v for e in envs for v, _ in e], np.uint8), "term": np.array([t for e in envs for _, t in e], np.uint8)}
+    flat["reward"] = np.zeros(int(off[-1]), np.float32) if rewards is None else rewards(int(off[-1]))
+    return flat
+
+
+def test_the_bonus_goes_to_the_execution_that_succeeded():
+    flat = exec_flat()
+    got = valuefit.returns_to_go(flat, 0.5, 100.0)
+    off = flat["offsets"]
+    for i, (name, (steps, bonus)) in enumerate(EXECUTIONS.items()):
+        sl = slice(off[i], off[i + 1])
+        assert got["y"][sl].tolist() == [float(v) for v in bonus], name
+        assert not got["g"][sl].any(), name
+        g, y = scalar_targets(flat["reward"][sl], flat["vf"][sl], flat["term"][sl], 0.5, 100.0)
+        assert y == [float(v) for v in bonus] and not any(g), name
+    # the issue's record by itself, and no envs at all
+    one = {"offsets": np.array([0, 7]), "reward": np.zeros(7, np.float32), "vf": np.array([0, 1, 1, 1, 1, 0, 0], np.uint8),
+           "term": np.array([0, 0, 4, 0, 1, 0, 0], np.uint8)}
+    assert valuefit.returns_to_go(one, 0.5, 100.0)["y"].tolist() == [0, 0, 0, 50, 100, 0, 0]
+    none = valuefit.returns_to_go({"offsets": np.zeros(1, np.int64), "reward": np.zeros(0, np.float32), "vf": np.zeros(0, np.uint8),
+                                   "term": np.zeros(0, np.uint8)}, 0.5, 100.0)
+    assert all(len(none[k]) == 0 for k in ("g", "y", "sample")) and none["y"].dtype == np.float64 and none["offsets"].tolist() == [0]
+
+
+@pytest.mark.parametrize("gamma,r_succ", [(0.99, 100.0), (float(np.float32(0.99)), 100.0), (1.0, -7.5)])
+def test_executions_with_rewards_equal_the_scalar_loop_by_bits(gamma, r_succ):
+    flat = exec_flat(lambda n: np.random.default_rng(7).choice(np.array([-1, -5, 10000], np.float32), n))
+    got = valuefit.returns_to_go(flat, gamma, r_succ)
+    off = flat["offsets"]
+    for i, name in enumerate(EXECUTIONS):
+        sl = slice(off[i], off[i + 1])
+        g, y = scalar_targets(flat["reward"][sl], flat["vf"][sl], flat["term"][sl], gamma, r_succ)
+        assert np.array_equal(got["g"][sl], g) and np.array_equal(got["y"][sl], y), name
+        assert (np.asarray(y) != np.asarray(g)).sum() == np.count_nonzero(EXECUTIONS[name][1]), name
 
 
 # ---------------------------------------------------------------------------------------------------- §16.3: ridge_solve

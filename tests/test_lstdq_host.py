@@ -250,3 +250,20 @@ def test_cross_model_inside_the_chain_bound_and_its_identities():
     rows, cols = idx[:5], idx[7:20]                                  # rows and columns are the features of s and of s2
     part = CM.cross(phi, phi2, off, rows, cols)
     assert_bits_equal(part, Cm[:, :5, 7:20].copy(), msg="another index pair:")
+
+
+def test_lattice_shortcut_equals_the_plain_cross_chain_on_the_index_set():
+    """tests/test_gram_host.py's layout (a slab edge and both kernels' chunk edges inside real-valued samples), s2 drawn apart from s
+    on the same lattice mask."""
+    from test_gram_host import MIXED_OFF, MIXED_RUNS
+    orc, _ = make_oracle("pinball_simple")
+    (s, lat), (s2, lat2) = GM.mixed_states(MIXED_RUNS, 40), GM.mixed_states(MIXED_RUNS, 50)
+    assert np.array_equal(lat, lat2) and not all(np.array_equal(a, b) for a, b in zip(s, s2))
+    phi, phi2 = orc.features(*s), orc.features(*s2)
+    idx = GM.index_set()
+    got = CM.lattice_cross(phi, phi2, MIXED_OFF, lat, idx, idx)
+    assert_bits_equal(got, CM.cross(phi, phi2, MIXED_OFF, idx, idx), msg="C by the shortcut:")
+    assert not np.array_equal(got[0], got[0].T) and got[0][0, 0] == 1064 and got[2][0, 0] == 37
+    one = CM.lattice_cross(phi[:2], phi2[:2], [0, 1, 2])             # whole matrices of one real-valued sample each
+    want = (phi[:2].astype(np.float64)[:, :, None] * phi2[:2].astype(np.float64)[:, None, :]).astype(np.float32) + np.float32(0)
+    assert_bits_equal(one, want, msg="one-sample C:")
