@@ -495,26 +495,32 @@ class ScgContext:
         self._call("scg_fourier_features", n, _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(phi), self._stream())
         return phi
 
+    def _gram_setup(self, fn: str, offsets, *states):
+        """What feature_gram and feature_cross_gram (`fn`) share: the checked state tensors of each of `states` (placeholders when
+        n = 0), n, the offsets as a host int64 array, n_seg and the uninitialised output [n_seg][1296][1296]."""
+        n = states[0][0].numel()
+        sv = [self._chk4(s, n, name) for s, name in zip(states, ("state", "successor state"))]
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        n_seg = len(off) - 1
+        if not (1 <= n_seg <= _lib.GRAM_MAX_SEGMENTS):
+            raise ScgError(f"{fn}: offsets must name 1 .. {_lib.GRAM_MAX_SEGMENTS} segments")
+        if off[0] < 0 or off[-1] > n or np.any(np.diff(off) < 0):
+            raise ScgError(f"{fn}: offsets must be non-decreasing and inside [0, n]")
+        if n == 0:                                           # (an empty tensor has no address: the entry point refuses a null array)
+            sv = [[torch.zeros(1, dtype=torch.float32, device=self.device)] * 4] * len(sv)
+        out = torch.empty((n_seg, NUM_FEATURES, NUM_FEATURES), dtype=torch.float32, device=self.device)
+        return sv, n, off, n_seg, out
+
     def feature_gram(self, s, offsets, yv: Optional[torch.Tensor] = None):
         """SPEC §16.1: A[g] = sum phi(s_n) phi(s_n)^T over segment g = samples offsets[g] .. offsets[g+1]-1 of the states `s`
         (`offsets`: host integers, non-decreasing, inside [0, n]); with `yv` [n] also b[g] = sum phi(s_n) yv[n]. Returns A
         [n_seg][1296][1296], or (A, b [n_seg][1296]). phi is not materialised; the sums have §16.1's pinned order."""
-        n = s[0].numel()
-        x, y, vx, vy = self._chk4(s, n, "state")
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
-        n_seg = len(off) - 1
-        if not (1 <= n_seg <= _lib.GRAM_MAX_SEGMENTS):
-            raise ScgError(f"feature_gram: offsets must name 1 .. {_lib.GRAM_MAX_SEGMENTS} segments")
-        if off[0] < 0 or off[-1] > n or np.any(np.diff(off) < 0):
-            raise ScgError("feature_gram: offsets must be non-decreasing and inside [0, n]")
+        (a,), n, off, n_seg, A = self._gram_setup("feature_gram", offsets, s)
         if yv is not None:
             self._chk(yv, torch.float32, n, "yv")
-        if n == 0:                                           # (an empty tensor has no address: the entry point refuses a null array)
-            x = y = vx = vy = torch.zeros(1, dtype=torch.float32, device=self.device)
-            yv = None if yv is None else x
-        A = torch.empty((n_seg, NUM_FEATURES, NUM_FEATURES), dtype=torch.float32, device=self.device)
+            yv = yv if n else a[0]
         b = None if yv is None else torch.empty((n_seg, NUM_FEATURES), dtype=torch.float32, device=self.device)
-        self._call("scg_feature_gram", C.c_int64(n), _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(yv), n_seg,
+        self._call("scg_feature_gram", C.c_int64(n), *[_ptr(t) for t in a], _ptr(yv), n_seg,
                    off.ctypes.data_as(C.c_void_p), _ptr(A), _ptr(b), self._stream())
         return A if b is None else (A, b)
 
@@ -522,18 +528,7 @@ class ScgContext:
         """SPEC §17.1: C[g] = sum phi(s_n) phi(s2_n)^T over segment g = samples offsets[g] .. offsets[g+1]-1 of the state pairs
         (`s`, `s2`: four [n] tensors each, which may be the same tensors; `offsets` as for feature_gram). Returns C
         [n_seg][1296][1296]: rows the features of s, columns those of s2. phi is not materialised; the sums have §16.1's pinned order."""
-        n = s[0].numel()
-        a = self._chk4(s, n, "state")
-        b = self._chk4(s2, n, "successor state")
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
-        n_seg = len(off) - 1
-        if not (1 <= n_seg <= _lib.GRAM_MAX_SEGMENTS):
-            raise ScgError(f"feature_cross_gram: offsets must name 1 .. {_lib.GRAM_MAX_SEGMENTS} segments")
-        if off[0] < 0 or off[-1] > n or np.any(np.diff(off) < 0):
-            raise ScgError("feature_cross_gram: offsets must be non-decreasing and inside [0, n]")
-        if n == 0:                                           # (an empty tensor has no address: the entry point refuses a null array)
-            a = b = (torch.zeros(1, dtype=torch.float32, device=self.device),) * 4
-        Cm = torch.empty((n_seg, NUM_FEATURES, NUM_FEATURES), dtype=torch.float32, device=self.device)
+        (a, b), n, off, n_seg, Cm = self._gram_setup("feature_cross_gram", offsets, s, s2)
         self._call("scg_feature_cross_gram", C.c_int64(n), *[_ptr(t) for t in a], *[_ptr(t) for t in b], n_seg,
                    off.ctypes.data_as(C.c_void_p), _ptr(Cm), self._stream())
         return Cm

@@ -17,8 +17,8 @@
 //   scg_aux_kernels.hpp      pinball / features / predict, and fit_kernel: SPEC §6 on 8 workgroups x 1024 chains per option behind
 //                            tagged-word exchanges; a fit whose workgroups cannot run together gives up after a wall-clock wait,
 //                            leaves its row untouched and raises the ctx's asynchronous status word
-//   scg_gram_kernel.hpp      SPEC §16.1's feature Gram: here only its arguments and launch (the kernel is compiled in scg_gram.hip)
-//   scg_cross_gram_kernel.hpp  SPEC §17.1's cross-feature Gram: likewise (the kernel is compiled in scg_cross_gram.hip)
+//   scg_gram_kernel.hpp      SPEC §16.1's feature Gram and §17.1's cross-feature Gram, one kernel template: here only its arguments and
+//                            the two launches (its instantiations are compiled in scg_gram.hip)
 // scg_rollout_variants.hip is the second translation unit: every other instantiation of rollout_kernel (SPEC §10's record, §11's
 // interruption, §14's value-ranked choice, §15's audit: the table in scg_rollout_kernel.hpp) and trial_kernel<true>, reached through
 // launch_rollout<REC, Args> / launch_trial_record, which the two kernel headers declare.
@@ -49,7 +49,6 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 #include "scg_apply_kernels.hpp"
 #include "scg_aux_kernels.hpp"
 #include "scg_gram_kernel.hpp"
-#include "scg_cross_gram_kernel.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -1221,71 +1220,53 @@ int scg_fourier_features(scg_ctx *c, int32_t n, const float *x, const float *y, 
     return SCG_OK;
 }
 
-int scg_feature_gram(scg_ctx *c, int64_t n, const float *x, const float *y, const float *vx, const float *vy, const float *yv,
-                     int32_t n_seg, const int64_t *offsets, float *A, float *b, void *stream) {
-    const char *fn = "scg_feature_gram";
+// What scg_feature_gram and scg_feature_cross_gram share behind their null checks: the other argument checks, an empty segment's +0
+// fill, the non-empty segments listed into G — as listed, or longest first (ties as listed: blockIdx.y is dispatched slowest, so the
+// longest chains start first) — and the launch. G's pointers are the caller's.
+static int gram_call(scg_ctx *c, const char *fn, bool null_array, bool yv_without_b, int64_t n, int32_t n_seg, const int64_t *offsets,
+                     GramArgs &G, bool longest_first, hipError_t (*launch)(const GramArgs &, int, hipStream_t), void *stream) {
     if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
-    if (!x || !y || !vx || !vy || !A || !offsets) return fail_in(c, SCG_ERR_INVALID, fn, "null array argument");
+    if (null_array) return fail_in(c, SCG_ERR_INVALID, fn, "null array argument");
     if (n < 0) return fail_in(c, SCG_ERR_INVALID, fn, "n must be >= 0");
     if (n_seg < 1 || n_seg > SCG_GRAM_MAX_SEGMENTS) return fail_in(c, SCG_ERR_INVALID, fn, "n_seg out of range [1, SCG_GRAM_MAX_SEGMENTS]");
-    if ((yv == nullptr) != (b == nullptr)) return fail_in(c, SCG_ERR_INVALID, fn, "yv and b go together");
+    if (yv_without_b) return fail_in(c, SCG_ERR_INVALID, fn, "yv and b go together");
     if (offsets[0] < 0 || offsets[n_seg] > n) return fail_in(c, SCG_ERR_INVALID, fn, "offsets leave [0, n]");
     for (int g = 0; g < n_seg; ++g)
         if (offsets[g + 1] < offsets[g]) return fail_in(c, SCG_ERR_INVALID, fn, "offsets decrease");
     SCG_CHECK_ASYNC(c);
-    SCG_ON_DEVICE(c, "scg_feature_gram");
+    DeviceGuard dev_guard(c->cfg.device);
+    if (!dev_guard.ok) return fail_in(c, SCG_ERR_HIP, fn, "cannot make the context's device current");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    GramArgs G;
-    G.x = x; G.y = y; G.vx = vx; G.vy = vy; G.yv = yv; G.A = A; G.b = b;
     int n_active = 0;
     for (int g = 0; g < n_seg; ++g) {
         const int64_t cnt = offsets[g + 1] - offsets[g];
         if (cnt > 0) {
-            G.seg[n_active] = g; G.start[n_active] = offsets[g]; G.count[n_active] = cnt;
-            ++n_active;
+            int at = n_active++;
+            for (; longest_first && at > 0 && G.count[at - 1] < cnt; --at) { G.seg[at] = G.seg[at - 1]; G.start[at] = G.start[at - 1]; G.count[at] = G.count[at - 1]; }
+            G.seg[at] = g; G.start[at] = offsets[g]; G.count[at] = cnt;
         } else {                                          // an empty segment: all +0 (the kernel writes every entry of the others)
-            SCG_HIP(c, hipMemsetAsync(A + (size_t)g * NF * NF, 0, (size_t)NF * NF * sizeof(float), s));
-            if (b) SCG_HIP(c, hipMemsetAsync(b + (size_t)g * NF, 0, (size_t)NF * sizeof(float), s));
+            SCG_HIP(c, hipMemsetAsync(G.out + (size_t)g * NF * NF, 0, (size_t)NF * NF * sizeof(float), s));
+            if (G.b) SCG_HIP(c, hipMemsetAsync(G.b + (size_t)g * NF, 0, (size_t)NF * sizeof(float), s));
         }
     }
     for (int g = n_active; g < GRAM_MAX_SEG; ++g) { G.seg[g] = 0; G.start[g] = 0; G.count[g] = 0; }
-    if (n_active) SCG_HIP(c, launch_feature_gram(G, n_active, s));
+    if (n_active) SCG_HIP(c, launch(G, n_active, s));
     return SCG_OK;
+}
+
+int scg_feature_gram(scg_ctx *c, int64_t n, const float *x, const float *y, const float *vx, const float *vy, const float *yv,
+                     int32_t n_seg, const int64_t *offsets, float *A, float *b, void *stream) {
+    GramArgs G = {{{x, y, vx, vy}, {x, y, vx, vy}}, yv, A, b};
+    return gram_call(c, "scg_feature_gram", !x || !y || !vx || !vy || !A || !offsets, (yv == nullptr) != (b == nullptr), n, n_seg, offsets,
+                     G, false, launch_feature_gram, stream);
 }
 
 int scg_feature_cross_gram(scg_ctx *c, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
                            const float *x2, const float *y2, const float *vx2, const float *vy2,
                            int32_t n_seg, const int64_t *offsets, float *Cm, void *stream) {
-    const char *fn = "scg_feature_cross_gram";
-    if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
-    if (!x || !y || !vx || !vy || !x2 || !y2 || !vx2 || !vy2 || !Cm || !offsets) return fail_in(c, SCG_ERR_INVALID, fn, "null array argument");
-    if (n < 0) return fail_in(c, SCG_ERR_INVALID, fn, "n must be >= 0");
-    if (n_seg < 1 || n_seg > SCG_GRAM_MAX_SEGMENTS) return fail_in(c, SCG_ERR_INVALID, fn, "n_seg out of range [1, SCG_GRAM_MAX_SEGMENTS]");
-    if (offsets[0] < 0 || offsets[n_seg] > n) return fail_in(c, SCG_ERR_INVALID, fn, "offsets leave [0, n]");
-    for (int g = 0; g < n_seg; ++g)
-        if (offsets[g + 1] < offsets[g]) return fail_in(c, SCG_ERR_INVALID, fn, "offsets decrease");
-    SCG_CHECK_ASYNC(c);
-    SCG_ON_DEVICE(c, "scg_feature_cross_gram");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    CrossGramArgs G;
-    const float *src[2][4] = {{x, y, vx, vy}, {x2, y2, vx2, vy2}};
-    for (int h = 0; h < 2; ++h)
-        for (int d = 0; d < 4; ++d) G.s[h][d] = src[h][d];
-    G.C = Cm;
-    int n_active = 0;
-    for (int g = 0; g < n_seg; ++g) {
-        const int64_t cnt = offsets[g + 1] - offsets[g];
-        if (cnt > 0) {                                    // kept longest first (ties: as listed): the longest chains are dispatched first
-            int at = n_active++;
-            for (; at > 0 && G.count[at - 1] < cnt; --at) { G.seg[at] = G.seg[at - 1]; G.start[at] = G.start[at - 1]; G.count[at] = G.count[at - 1]; }
-            G.seg[at] = g; G.start[at] = offsets[g]; G.count[at] = cnt;
-        } else {                                          // an empty segment: all +0 (the kernel writes every entry of the others)
-            SCG_HIP(c, hipMemsetAsync(Cm + (size_t)g * NF * NF, 0, (size_t)NF * NF * sizeof(float), s));
-        }
-    }
-    for (int g = n_active; g < SCG_GRAM_MAX_SEGMENTS; ++g) { G.seg[g] = 0; G.start[g] = 0; G.count[g] = 0; }
-    if (n_active) SCG_HIP(c, launch_feature_cross_gram(G, n_active, s));
-    return SCG_OK;
+    GramArgs G = {{{x, y, vx, vy}, {x2, y2, vx2, vy2}}, nullptr, Cm, nullptr};
+    return gram_call(c, "scg_feature_cross_gram", !x || !y || !vx || !vy || !x2 || !y2 || !vx2 || !vy2 || !Cm || !offsets, false, n, n_seg,
+                     offsets, G, true, launch_feature_cross_gram, stream);
 }
 
 int scg_q_values(scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,
