@@ -373,6 +373,26 @@ int scg_feature_gram(scg_ctx *ctx, int64_t n, const float *x, const float *y, co
 int scg_feature_cross_gram(scg_ctx *ctx, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
                            const float *x2, const float *y2, const float *vx2, const float *vy2,
                            int32_t n_seg, const int64_t *offsets /* HOST */, float *C, void *stream);
+/* ---- the basis-order probe (SPEC §18): the Fourier basis of order p in {3, 5, 7}, F = (p + 1)^4 = 256, 1296, 4096 features, feature
+ * ((c1 (p+1) + c2) (p+1) + c3) (p+1) + c4, formed by SPEC §3's operations with 6 replaced by p + 1: at order 5 SPEC §3's bits, and
+ * a feature with every c <= q < p has, at order p, the bits it has at order q. Reporting instruments: nothing acts or learns at an
+ * order other than 5. All three need no map, raise no asynchronous status and write their output only. SCG_ERR_INVALID, nothing
+ * launched, nothing written: a null ctx, then an order outside {3, 5, 7}, then the checks each comment names. */
+#define SCG_BASIS_VALUES_MAX_ROWS 8
+/* phi[n][F] of order p; at order 5 scg_fourier_features' bits (n < 2^31 there). Then: n < 0, a null array. */
+int scg_basis_features(scg_ctx *ctx, int32_t order, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                       float *phi, void *stream);
+/* scg_feature_gram with 1296 -> F: A[n_seg][F][F] and b[n_seg][F], the same slabs, chains, symmetry, +0 for an empty segment, and the
+ * same checks in the same sequence; at order 5 scg_feature_gram's bits. For q < p, order q's A and b are the sub-block of order p's
+ * at the embedded indices, by bits. */
+int scg_basis_gram(scg_ctx *ctx, int32_t order, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                   const float *yv /* may be NULL */, int32_t n_seg, const int64_t *offsets /* HOST */,
+                   float *A, float *b /* NULL iff yv is NULL */, void *stream);
+/* out[m][n], out[r][n] = sum_f V[r][f] phi_f(s_n) for the m rows of V[m][F], 1 <= m <= SCG_BASIS_VALUES_MAX_ROWS, in SPEC §18.3's pinned
+ * order (per c12 = f / (p+1)^2 an fma chain over c34 from +0, those sums added in c12 order from +0): NOT SPEC §3.1's order, also at
+ * order 5. Then: n < 0, a null array, m out of range. */
+int scg_basis_values(scg_ctx *ctx, int32_t order, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                     const float *V, int32_t m, float *out, void *stream);
 /* Option.policy value part (SPEC §3.1): q[5][n] = Q_k(s, .) for one VF Wk[5][1296]. */
 int scg_q_values(scg_ctx *ctx, int32_t n, const float *x, const float *y, const float *vx,
                  const float *vy, const float *Wk, float *q, void *stream);

@@ -41,6 +41,15 @@ GRAM_SLAB = 1024            # include/scg_abi.h SCG_GRAM_*: SPEC §16.1's slab, 
 GRAM_MAX_SEGMENTS = 64
 GRAM_MACRO_TILE = 96
 CROSS_GRAM_MACRO_TILE = 96  # include/scg_abi.h SCG_CROSS_GRAM_MACRO_TILE: one workgroup's block of SPEC §17.1's C (rows and columns alike)
+BASIS_ORDERS = (3, 5, 7)    # SPEC §18: the orders of the basis-order probe (F = (order + 1)^4 = 256, 1296, 4096 features)
+BASIS_VALUES_MAX_ROWS = 8   # include/scg_abi.h SCG_BASIS_VALUES_MAX_ROWS
+
+
+def basis_features(order: int) -> int:
+    """F of SPEC §18's basis of order `order`."""
+    if order not in BASIS_ORDERS:
+        raise ScgError(f"the basis order must be one of {BASIS_ORDERS}")
+    return (int(order) + 1) ** 4
 
 
 class ScgError(RuntimeError):
@@ -163,6 +172,9 @@ _SIGS = {
     "scg_fourier_features": (C.c_int, [_P, C.c_int32] + [_P] * 5 + [_P]),
     "scg_feature_gram": (C.c_int, [_P, C.c_int64] + [_P] * 5 + [C.c_int32, _P, _P, _P, _P]),
     "scg_feature_cross_gram": (C.c_int, [_P, C.c_int64] + [_P] * 8 + [C.c_int32, _P, _P, _P]),
+    "scg_basis_features": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 5 + [_P]),
+    "scg_basis_gram": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 5 + [C.c_int32, _P, _P, _P, _P]),
+    "scg_basis_values": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 5 + [C.c_int32, _P, _P]),
     "scg_q_values": (C.c_int, [_P, C.c_int32] + [_P] * 6 + [_P]),
     "scg_q_update": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 12 + [C.c_uint32, _P]),
     "scg_classifier_predict": (C.c_int, [_P, C.c_int32] + [_P] * 4 + [_P]),

@@ -583,7 +583,7 @@ class SkillChainingAgent:
 
     def fit_values_to_returns(self, n_episodes: int = 4096, epsilon: float = 0.1, seed: Optional[int] = None, vfs=None,
                               ridge: float = 1e-3, apply: bool = False, interrupt: bool = False, choose: Optional[str] = None,
-                              keep: bool = False):
+                              keep: bool = False, order: Optional[int] = None, trajectory=None):
         """The best linear fit of each Q_k to the returns its own policy realises (SPEC §16): record_episodes() with the current
         policy, Monte-Carlo targets by valuefit.returns_to_go, then per value function k of `vfs` (default: all) and action a the
         ridge regression of the residual y - Q_k^old on the 1296 features over the rows with vf = k, action = a of the EVEN envs
@@ -595,8 +595,22 @@ class SkillChainingAgent:
         report["targets"] (returns_to_go's dict) and report["trajectory"].
         apply=False leaves the agent as evaluate() does: W, training state, t, env order, trace ring, gestation counts and peer
         counter untouched. apply=True copies the fitted rows of `vfs` into W; refused with shared weights (a sharded agent would
-        fit its own rank's copy only, and the ranks' W would part)."""
+        fit its own rank's copy only, and the ranks' W would part).
+        `order` = p in (3, 5, 7) is SPEC §18's basis-order probe: the same samples, targets and split, the residual regressed on the
+        (p + 1)^4 features of order p (A, b by ScgContext.basis_gram, Lambda from order p's scale table) while Q^old stays the
+        agent's order-5 value: Q^new(s, a) = float32(Q^old + v), v = ScgContext.basis_values(float32(Delta))[a], the sum in float64.
+        The report adds "order" and "features" and, per value function, "delta" (float64 [5][F]); W_new is a plain copy of W, and
+        apply=True is refused (no kernel acts on F != 1296 weights). order=None is the path above, untouched.
+        `trajectory`: a kept record (report["trajectory"] of an earlier call) to fit on instead of recording, as fit_values_lstdq
+        takes one: several orders are then fitted to one record; report["episodes"] is None."""
+        from .core import fourier_scale_table
         from .valuefit import error_stats, returns_to_go, ridge_solve
+        if order is not None:
+            if order not in _lib.BASIS_ORDERS:
+                raise ScgError(f"fit_values_to_returns: order must be None or one of {_lib.BASIS_ORDERS}")
+            if apply:
+                raise ScgError(f"fit_values_to_returns(order={order}, apply=True): the fit at a basis order is a report; no kernel acts "
+                               f"on weights of {_lib.basis_features(order)} features")
         if apply and self.group is not None:
             raise ScgError("fit_values_to_returns(apply=True) with shared weights: each rank would fit its own copy of W and the "
                            "ranks would part; fit with apply=False and load one rank's result on all of them")
@@ -604,8 +618,12 @@ class SkillChainingAgent:
         if any(not (0 <= k < self.n_vf) for k in vfs):
             raise ValueError(f"vfs must name value functions 0..{self.n_vf - 1}")
         c = self.ctx.cfg
-        traj, summary = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose)
-        ectx = self._eval_ctx[int(n_episodes)][0]
+        if trajectory is None:
+            traj, summary = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose)
+            ectx = self._eval_ctx[int(n_episodes)][0]
+        else:
+            traj, summary = trajectory, None
+            ectx = self._eval_context(int(traj.n), epsilon, seed, None)[0]
         flat = traj.to_numpy()
         tg = returns_to_go(flat, float(c.gamma), float(c.r_option_success))
         off = flat["offsets"]
@@ -614,6 +632,11 @@ class SkillChainingAgent:
         dev = self.W.device
         W_new = self.W.clone()
         report = {"episodes": summary, "ridge": float(ridge), "vf": {}}
+        # the regression basis: the Gram of the fit samples and the scale table of the ridge term
+        gram = ectx.feature_gram if order is None else (lambda st, offs, yv: ectx.basis_gram(order, st, offs, yv))
+        scale = self.ctx.scale if order is None else fourier_scale_table(order)
+        if order is not None:
+            report["order"], report["features"] = int(order), _lib.basis_features(order)
 
         def q_of(states, Wk, act):                             # Q_k(s_n, a_n) of a sample list, float32 as the kernel gives it
             out = np.zeros(len(act), np.float32)
@@ -627,8 +650,8 @@ class SkillChainingAgent:
             rows = smp[flat["vf"][smp] == k]
             rows = np.concatenate([rows[env[rows] % 2 == 0], rows[env[rows] % 2 == 1]])      # the fit half, then the held-out half
             n_fit = int(np.sum(env[rows] % 2 == 0))
-            order = np.argsort(flat["action"][rows[:n_fit]], kind="stable")
-            rows[:n_fit] = rows[:n_fit][order]                 # the fit samples by action, (env, row) order within one
+            by_action = np.argsort(flat["action"][rows[:n_fit]], kind="stable")
+            rows[:n_fit] = rows[:n_fit][by_action]                 # the fit samples by action, (env, row) order within one
             act = flat["action"][rows].astype(np.int64)
             y = tg["y"][rows]
             states = [torch.from_numpy(np.ascontiguousarray(flat[f][rows - 1])).to(dev) for f in ("x", "y", "vx", "vy")]
@@ -636,15 +659,26 @@ class SkillChainingAgent:
             d = (y - q_old.astype(np.float64)).astype(np.float32)
             n_a = np.bincount(act[:n_fit], minlength=NUM_ACTIONS).astype(np.int64)
             offsets = np.concatenate([[0], np.cumsum(n_a)]).astype(np.int64)
-            A, b = ectx.feature_gram(states, offsets, torch.from_numpy(d).to(dev))
-            delta = ridge_solve(A.cpu().numpy(), b.cpu().numpy(), n_a, ridge, self.ctx.scale)
-            w_old = self.W[k].cpu().numpy()
-            w_new = (w_old.astype(np.float64) + delta).astype(np.float32)
-            w_new[n_a == 0] = w_old[n_a == 0]
-            W_new[k] = torch.from_numpy(w_new).to(dev)
-            q_new = q_of(states, W_new[k], act)
+            A, b = gram(states, offsets, torch.from_numpy(d).to(dev))
+            if order is None:
+                delta = ridge_solve(A.cpu().numpy(), b.cpu().numpy(), n_a, ridge, scale)
+            else:                                              # (F up to 4096: factored on the device)
+                delta = ridge_solve(A, b, n_a, ridge, scale, device=dev)
+            if order is None:
+                w_old = self.W[k].cpu().numpy()
+                w_new = (w_old.astype(np.float64) + delta).astype(np.float32)
+                w_new[n_a == 0] = w_old[n_a == 0]
+                W_new[k] = torch.from_numpy(w_new).to(dev)
+                q_new = q_of(states, W_new[k], act)
+            else:                                              # the correction lives at order p: Q^new = Q^old + Delta . phi^p
+                q_new = q_old.copy()
+                if len(act):
+                    v = ectx.basis_values(order, states, torch.from_numpy(delta.astype(np.float32)).to(dev)).cpu().numpy()
+                    q_new = (q_old.astype(np.float64) + v[act, np.arange(len(act))].astype(np.float64)).astype(np.float32)
             half = {"fit": slice(0, n_fit), "held_out": slice(n_fit, None)}
             rep = {"n": [int(v) for v in n_a], "delta_norm": float(np.sqrt(np.sum(delta * delta)))}
+            if order is not None:
+                rep["delta"] = delta
             for name, sl in half.items():
                 rep[name] = {"old": error_stats(q_old[sl], y[sl]), "new": error_stats(q_new[sl], y[sl])}
             if keep:

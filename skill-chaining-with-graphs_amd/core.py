@@ -495,9 +495,10 @@ class ScgContext:
         self._call("scg_fourier_features", n, _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(phi), self._stream())
         return phi
 
-    def _gram_setup(self, fn: str, offsets, *states):
-        """What feature_gram and feature_cross_gram (`fn`) share: the checked state tensors of each of `states` (placeholders when
-        n = 0), n, the offsets as a host int64 array, n_seg and the uninitialised output [n_seg][1296][1296]."""
+    def _gram_setup(self, fn: str, offsets, *states, features: int = NUM_FEATURES):
+        """What feature_gram, feature_cross_gram and basis_gram (`fn`) share: the checked state tensors of each of `states`
+        (placeholders when n = 0), n, the offsets as a host int64 array, n_seg and the uninitialised output [n_seg][F][F], F =
+        `features` (1296 but for basis_gram)."""
         n = states[0][0].numel()
         sv = [self._chk4(s, n, name) for s, name in zip(states, ("state", "successor state"))]
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
@@ -508,7 +509,7 @@ class ScgContext:
             raise ScgError(f"{fn}: offsets must be non-decreasing and inside [0, n]")
         if n == 0:                                           # (an empty tensor has no address: the entry point refuses a null array)
             sv = [[torch.zeros(1, dtype=torch.float32, device=self.device)] * 4] * len(sv)
-        out = torch.empty((n_seg, NUM_FEATURES, NUM_FEATURES), dtype=torch.float32, device=self.device)
+        out = torch.empty((n_seg, features, features), dtype=torch.float32, device=self.device)
         return sv, n, off, n_seg, out
 
     def feature_gram(self, s, offsets, yv: Optional[torch.Tensor] = None):
@@ -532,6 +533,44 @@ class ScgContext:
         self._call("scg_feature_cross_gram", C.c_int64(n), *[_ptr(t) for t in a], *[_ptr(t) for t in b], n_seg,
                    off.ctypes.data_as(C.c_void_p), _ptr(Cm), self._stream())
         return Cm
+
+    # SPEC §18, the basis-order probe: the basis of order p in _lib.BASIS_ORDERS, F = (p + 1)^4 features
+    def basis_features(self, order: int, s) -> torch.Tensor:
+        """phi [n][F] of order `order`; at order 5 features()' bits."""
+        F = _lib.basis_features(order)
+        n = s[0].numel()
+        x, y, vx, vy = self._chk4(s, n, "state")
+        phi = torch.empty((n, F), dtype=torch.float32, device=self.device)
+        self._call("scg_basis_features", int(order), C.c_int64(n), _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(phi), self._stream())
+        return phi
+
+    def basis_gram(self, order: int, s, offsets, yv: Optional[torch.Tensor] = None):
+        """feature_gram at order `order`: A [n_seg][F][F], or (A, b [n_seg][F]) with `yv`; SPEC §16.1's pinned order with 1296 -> F.
+        At order 5 feature_gram's bits; the A and b of a lower order are the sub-block at the embedded indices, by bits."""
+        F = _lib.basis_features(order)
+        (a,), n, off, n_seg, A = self._gram_setup("basis_gram", offsets, s, features=F)
+        if yv is not None:
+            self._chk(yv, torch.float32, n, "yv")
+            yv = yv if n else a[0]
+        b = None if yv is None else torch.empty((n_seg, F), dtype=torch.float32, device=self.device)
+        self._call("scg_basis_gram", int(order), C.c_int64(n), *[_ptr(t) for t in a], _ptr(yv), n_seg,
+                   off.ctypes.data_as(C.c_void_p), _ptr(A), _ptr(b), self._stream())
+        return A if b is None else (A, b)
+
+    def basis_values(self, order: int, s, V: torch.Tensor) -> torch.Tensor:
+        """out [m][n] = sum_f V[r][f] phi_f(s_n) for the rows of V [m][F], 1 <= m <= 8, in SPEC §18.3's pinned order (not q_values'
+        order, also at order 5)."""
+        F = _lib.basis_features(order)
+        n = s[0].numel()
+        x, y, vx, vy = self._chk4(s, n, "state")
+        if not isinstance(V, torch.Tensor) or V.dim() != 2 or not (1 <= V.shape[0] <= _lib.BASIS_VALUES_MAX_ROWS):
+            raise ScgError(f"basis_values: V must be [m][{F}] with 1 <= m <= {_lib.BASIS_VALUES_MAX_ROWS}")
+        m = int(V.shape[0])
+        self._chk(V, torch.float32, m * F, "V")
+        out = torch.empty((m, n), dtype=torch.float32, device=self.device)
+        self._call("scg_basis_values", int(order), C.c_int64(n), _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(V), m, _ptr(out),
+                   self._stream())
+        return out
 
     def q_values(self, s, Wk: torch.Tensor) -> torch.Tensor:
         n = s[0].numel()

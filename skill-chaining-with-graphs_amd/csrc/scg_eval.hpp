@@ -40,24 +40,27 @@ __device__ __forceinline__ bool w_a_src(int t, int kb, int ln, int &src) {
 // ------------------------------------------------------------------ SPEC §3 tables of one item
 // AB[c2] = Z_1^c2, AB[c1*6 + c2] = cmul(AB[(c1-1)*6 + c2], Z_0^1) (CD likewise from Z_3, Z_2), Z^0 = (1, 0), Z^k = cmul(Z^(k-1), Z^1):
 // five chained products per table column instead of a power chain plus a product per entry.
+// (P1 = order + 1 entries a table row: 6 everywhere but in SPEC §18's basis-order probe, whose Gram kernel builds rows of 4 and 8)
+template <int P1>
 __device__ __forceinline__ float2 zpow_sel(float2 z, int c) {
     float2 cur = z, out = make_float2(1.0f, 0.0f);
 #pragma unroll
-    for (int j = 1; j <= 5; ++j) {
+    for (int j = 1; j <= P1 - 1; ++j) {
         if (c == j) out = cur;
-        if (j < 5) cur = cmul(cur, z);
+        if (j < P1 - 1) cur = cmul(cur, z);
     }
     return out;
 }
 // from the item's four Z_d^1 (z1p: 4 float2 in LDS) the lane with second index `cp` (c2 of AB, c4 of CD; cp < 6) gets, for the
-// first index c = 0..5, AB[6c + cp] and CD[6c + cp]
-__device__ __forceinline__ void item_entries(const float2 *z1p, int cp, float2 (&ab)[6], float2 (&cd)[6]) {
+// first index c = 0..5, AB[6c + cp] and CD[6c + cp] (P1 is deduced from the arrays: 6 here)
+template <int P1>
+__device__ __forceinline__ void item_entries(const float2 *z1p, int cp, float2 (&ab)[P1], float2 (&cd)[P1]) {
     const float4 za = *reinterpret_cast<const float4 *>(z1p), zc = *reinterpret_cast<const float4 *>(z1p + 2);
     const float2 z0 = make_float2(za.x, za.y), z1 = make_float2(za.z, za.w);
     const float2 z2 = make_float2(zc.x, zc.y), z3 = make_float2(zc.z, zc.w);
-    ab[0] = zpow_sel(z1, cp); cd[0] = zpow_sel(z3, cp);
+    ab[0] = zpow_sel<P1>(z1, cp); cd[0] = zpow_sel<P1>(z3, cp);
 #pragma unroll
-    for (int c = 1; c < 6; ++c) {
+    for (int c = 1; c < P1; ++c) {
         ab[c] = cmul(ab[c - 1], z0);
         cd[c] = cmul(cd[c - 1], z2);
     }

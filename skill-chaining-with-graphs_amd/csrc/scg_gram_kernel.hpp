@@ -1,15 +1,18 @@
-// scg_gram_kernel.hpp — SPEC §16.1 and §17.1: gram_kernel, the feature Gram of segments of recorded states as an f32 rank-k update on
+// scg_gram_kernel.hpp — SPEC §16.1, §17.1 and §18: gram_kernel, the feature Gram of segments of recorded states as an f32 rank-k update on
 // v_mfma_f32_16x16x4_f32 whose operands are built on the fly from the 16-byte state: phi is never materialised. One template, two shapes:
 //   symmetric (GramSym)   A_g = sum_n phi(s_n) phi(s_n)^T, and with RHS b_g = sum_n phi(s_n) yv[n]: the macro-tiles on or above the
 //                         diagonal are computed and every block is stored with its mirror image; one table set of 64 samples in LDS
 //   cross (GramCross)     C_g = sum_n phi(s_n) phi(s2_n)^T between a state and its successor: every macro-tile of the square, no mirror
 //                         store, no diagonal case; TWO table sets of 32 samples, s's for the row operands and s2's for the column operands
-// Both are instantiated in scg_gram.hip only, a translation unit of its own (what shares a module with the hot kernels changes their
-// code: DESIGN §3.10); scg_kernels.hip includes this header for GramArgs and the launches' declarations and instantiates nothing.
+// and, for the symmetric shape, the basis order p of SPEC §18 (GramBasis<p>: 3 or 7 next to GramSym's 5; GramOrder<p> holds what follows
+// from p). The order-5 shapes are instantiated in scg_gram.hip only, a translation unit of its own (what shares a module with the hot
+// kernels changes their code: DESIGN §3.10), the other orders in scg_basis.hip; scg_kernels.hip includes this header for
+// GramArgs and the launches' declarations and instantiates nothing.
 //
-// Geometry. The 1296 features are 81 tiles of 16. A wave owns R x R tiles, a workgroup WG x WG waves = one
-// macro-tile of MT tiles a side; the grid is (macro-tiles) x (non-empty segments). The last macro-tile of a side is short
-// (81 = 13 x 6 + 3): waves past tile 80 only help to build tables. A workgroup walks its segment slab by slab (SCG_GRAM_SLAB samples) and
+// Geometry. The F features are F / 16 tiles of 16 (order 5: 81). A wave owns R x R tiles, a workgroup
+// WG x WG waves = one macro-tile of MT tiles a side; the grid is (macro-tiles) x (non-empty segments). The last macro-tile of a side
+// is short (81 = 13 x 6 + 3; 16 = 2 x 6 + 4; 256 = 42 x 6 + 4): waves past the last tile only help to build tables. A workgroup walks
+// its segment slab by slab (SCG_GRAM_SLAB samples) and
 // a slab in chunks of CHUNK samples: all waves build the chunk's AB / CD tables (SPEC §3) into LDS once, then every wave, per four
 // samples, turns them into its 2 R operand registers — lane (i, k) holds phi_{16 t + i}(sample k) — and issues R^2 MFMAs into the slab's
 // accumulators P. At the end of a slab the wave adds P to its second set, the segment totals, in registers. Nothing is exchanged
@@ -39,6 +42,9 @@
 #ifndef SCG_CROSS_GRAM_CP_FAST
 #define SCG_CROSS_GRAM_CP_FAST 1                     // how the table build is dealt to the lanes (GramShape::FAST_DEAL)
 #endif
+#ifndef SCG_BASIS_GRAM_CHUNK
+#define SCG_BASIS_GRAM_CHUNK 64                      // (build parameter of tools/gram_bench.py --order: the chunk of the orders 3 and 7)
+#endif
 
 constexpr int GRAM_SLAB = SCG_GRAM_SLAB;
 constexpr int GRAM_MAX_SEG = SCG_GRAM_MAX_SEGMENTS;
@@ -47,26 +53,48 @@ constexpr int GRAM_TS = 80;                          // float2 per sample row of
                                                      // rows of two neighbouring samples, read at once, start on opposite bank halves
 static_assert(NF % 16 == 0, "gram geometry");
 
-// everything the two shapes differ in
-template <bool CROSS_, int R_, int WG_, int WPE_, int CHUNK_, bool FAST_DEAL_>
-struct GramShape {
+// what follows from the basis order p (SPEC §18): P1 = p + 1 entries a table row, P2 = P1^2 AB (and CD) entries a sample, F = P2^2
+// features; the table row of a sample — 2 P2 float2 used of TS, TS = 16 mod 32 float2 at every order, so that the rows of two
+// neighbouring samples start on opposite halves of the 64 banks a ds_read_b64 sees —; and the row's swizzle. A power
+// of two P1 makes a row's length a multiple of the 32 banks a ds_write_b64 sees, and the lanes of a 16-lane write group, (sample,
+// entry column) = (lane / P1, lane mod P1), would meet 16 / P1 deep on 2 P1 banks: the sample with index s (mod 16 / P1) keeps its
+// entry e at e ^ (P1 s) instead — its rows of P1 entries permuted —, which spreads a group over all 32 banks. A reader lane always
+// reads the samples 4 ks + kk, so its s is a constant it folds into its places once. Order 5 (P1 = 6) has no such swizzle.
+template <int ORDER_>
+struct GramOrder {
+    static_assert(ORDER_ == 3 || ORDER_ == 5 || ORDER_ == 7, "SPEC §18's orders");
+    static constexpr int ORDER = ORDER_, P1 = ORDER_ + 1, P2 = P1 * P1, F = P2 * P2, TILES = F / 16;
+    static constexpr int TS = ORDER_ == 5 ? GRAM_TS : 2 * P2 + 16;
+    static constexpr int SWZ_MASK = ORDER_ == 5 ? 0 : 16 / P1 - 1;
+    static_assert(F % 16 == 0 && TS % 32 == 16 && TS >= 2 * P2, "gram geometry");
+};
+static_assert(GramOrder<5>::F == NF && GramOrder<5>::TILES == GRAM_TILES && GramOrder<5>::P2 == 36, "order 5 is SPEC §3");
+
+// everything the shapes differ in
+template <bool CROSS_, int R_, int WG_, int WPE_, int CHUNK_, bool FAST_DEAL_, int ORDER_ = 5>
+struct GramShape : GramOrder<ORDER_> {
+    using O = GramOrder<ORDER_>;
     static constexpr bool CROSS = CROSS_;            // the whole square from two table sets, or the upper triangle and its mirror from one
     static constexpr int R = R_;                     // tiles a side per wave: R^2 accumulators of 4 registers, twice (P and the totals)
     static constexpr int WG = WG_;                   // waves a side per workgroup (1: every wave builds its own tables)
     static constexpr int WPE = WPE_;                 // waves per SIMD of the launch bounds
     static constexpr int CHUNK = CHUNK_;             // samples whose tables the workgroup holds in LDS
-    // the table build's deal: (entry column = lane mod 6, sample = lane / 6), or (sample = lane, entry column uniform per wave), whose
+    // the table build's deal: (entry column = lane mod P1, sample = lane / P1), or (sample = lane, entry column uniform per wave), whose
     // writes all meet on one LDS bank (rows are 160 floats apart): 1.5 - 1.7 x slower in the cross shape
     static constexpr bool FAST_DEAL = FAST_DEAL_;
     static constexpr int SETS = CROSS ? 2 : 1;
     static constexpr int MT = R * WG;                // tiles a side per macro-tile
-    static constexpr int ME = (GRAM_TILES + MT - 1) / MT;
+    static constexpr int ME = (O::TILES + MT - 1) / MT;
     static constexpr int MACROS = CROSS ? ME * ME : ME * (ME + 1) / 2;
     static constexpr int THREADS = 64 * WG * WG;
     static_assert(GRAM_SLAB % CHUNK == 0 && CHUNK % 4 == 0, "gram geometry");
+    static_assert(O::SWZ_MASK == 0 || FAST_DEAL_, "the swizzle belongs to the deal by entry column");
 };
 using GramSym = GramShape<false, SCG_GRAM_R, SCG_GRAM_WG, SCG_GRAM_WPE, 64, false>;
 using GramCross = GramShape<true, SCG_CROSS_GRAM_R, SCG_CROSS_GRAM_WG, 2, SCG_CROSS_GRAM_CHUNK, SCG_CROSS_GRAM_CP_FAST != 0>;
+// SPEC §18's symmetric shape of order 3 or 7: GramSym's tiling, the deal by entry column (scg_basis.hip)
+template <int ORDER_>
+using GramBasis = GramShape<false, SCG_GRAM_R, SCG_GRAM_WG, SCG_GRAM_WPE, SCG_BASIS_GRAM_CHUNK, true, ORDER_>;
 static_assert(GramSym::MT * 16 == SCG_GRAM_MACRO_TILE, "gram geometry");
 static_assert(GramCross::MT * 16 == SCG_CROSS_GRAM_MACRO_TILE, "cross gram geometry");
 
@@ -74,17 +102,19 @@ struct GramArgs {
     const float *s[2][4];                            // x, y, vx, vy of the row operands' states and of the column operands' (the same, or s2)
     const float *yv;                                 // yv and b: both or neither
     float *out, *b;                                  // A or C
-    int32_t seg[GRAM_MAX_SEG];                       // the non-empty segments: index (A_g = out + seg * 1296^2), first sample, samples
+    int32_t seg[GRAM_MAX_SEG];                       // the non-empty segments: index (A_g = out + seg * F^2), first sample, samples
     int64_t start[GRAM_MAX_SEG], count[GRAM_MAX_SEG];
 };
 // grid = MACROS x n_active workgroups of THREADS on stream s (defined in scg_gram.hip); the first reads s[0] only
 hipError_t launch_feature_gram(const GramArgs &G, int n_active, hipStream_t s);
 hipError_t launch_feature_cross_gram(const GramArgs &G, int n_active, hipStream_t s);
 
-// the table places of feature f (clamped: the tiles of a short macro-tile read a valid place and are never stored): AB at f / 36, CD behind them
-__device__ __forceinline__ void gram_places(int f, int &ab, int &cd) {
-    f = min(f, NF - 1);
-    ab = f / 36; cd = 36 + f % 36;
+// the table places of feature f (clamped: the tiles of a short macro-tile read a valid place and are never stored): AB at f / P2, CD
+// behind them; `swz` is the reader lane's P1 s of GramOrder's swizzle (0 at order 5)
+template <class O>
+__device__ __forceinline__ void gram_places(int f, int swz, int &ab, int &cd) {
+    f = min(f, O::F - 1);
+    ab = (f / O::P2) ^ swz; cd = O::P2 + ((f % O::P2) ^ swz);
 }
 // phi_f of the sample whose table row is `row`, exactly as features_kernel forms it
 __device__ __forceinline__ float gram_phi(const float2 *row, int ab_at, int cd_at) {
@@ -96,9 +126,10 @@ template <class S, bool RHS>
 __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs G) {
     constexpr bool CROSS = S::CROSS;
     constexpr int R = S::R, WG = S::WG, MT = S::MT, ME = S::ME, CHUNK = S::CHUNK, SETS = S::SETS, THREADS = S::THREADS;
+    constexpr int P1 = S::P1, P2 = S::P2, F = S::F, TILES = S::TILES, TS = S::TS;
     static_assert(!(CROSS && RHS), "b belongs to the symmetric shape");
     __shared__ __attribute__((aligned(16))) float2 s_z1[SETS][CHUNK][4];
-    __shared__ float2 s_tab[SETS][CHUNK * GRAM_TS];
+    __shared__ float2 s_tab[SETS][CHUNK * TS];
     __shared__ float s_yv[CHUNK];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n16 = lane & 15, kk = lane >> 4;                 // MFMA operand lane: row / column n16 of the tile, k index (A, B) or row group (C, D)
@@ -112,13 +143,13 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
     const int r0 = MT * I + R * (wave / WG), c0 = MT * J + R * (wave % WG);      // the wave's first row / column tile
     const bool diag = !CROSS && r0 == c0;                      // the block is its own mirror image
     // (the last macro-tile of a side is short; a block below the diagonal of the symmetric shape is the mirror image of one that is computed)
-    const bool active = c0 < GRAM_TILES && (CROSS ? r0 < GRAM_TILES : r0 <= c0);
+    const bool active = c0 < TILES && (CROSS ? r0 < TILES : r0 <= c0);
     const bool rhs = RHS && diag;                              // b's rows 16 r0 .. are this wave's
     int ra[R], rc[R], ca[R], cc[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        gram_places(16 * (r0 + r) + n16, ra[r], rc[r]);
-        gram_places(16 * (c0 + r) + n16, ca[r], cc[r]);
+        gram_places<S>(16 * (r0 + r) + n16, P1 * (kk & S::SWZ_MASK), ra[r], rc[r]);
+        gram_places<S>(16 * (c0 + r) + n16, P1 * (kk & S::SWZ_MASK), ca[r], cc[r]);
     }
     const f4v zero4 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
     f4v tot[R][R], acc[R][R], btot[R], bacc[R];
@@ -148,31 +179,32 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
                 for (int t = tid; t < CHUNK; t += THREADS) s_yv[t] = t < m ? G.yv[base + t] : 0.0f;
             }
             __syncthreads();
-            for (int t = tid; t < SETS * CHUNK * 6; t += THREADS) {
-                const int set = CROSS ? t / (CHUNK * 6) : 0, u = CROSS ? t % (CHUNK * 6) : t;
-                const int smp = S::FAST_DEAL ? u / 6 : u % CHUNK, cp = S::FAST_DEAL ? u % 6 : u / CHUNK;      // (slow deal: cp is wave-uniform)
-                float2 *row = s_tab[set] + smp * GRAM_TS;
+            for (int t = tid; t < SETS * CHUNK * P1; t += THREADS) {
+                const int set = CROSS ? t / (CHUNK * P1) : 0, u = CROSS ? t % (CHUNK * P1) : t;
+                const int smp = S::FAST_DEAL ? u / P1 : u % CHUNK, cp = S::FAST_DEAL ? u % P1 : u / CHUNK;    // (slow deal: cp is wave-uniform)
+                float2 *row = s_tab[set] + smp * TS;
                 if (smp < m) {
-                    float2 ab[6], cd[6];
+                    float2 ab[P1], cd[P1];
                     item_entries(&s_z1[set][smp][0], cp, ab, cd);
+                    const int wz = P1 * (smp & S::SWZ_MASK);   // (0 at order 5)
 #pragma unroll
-                    for (int c = 0; c < 6; ++c) { row[6 * c + cp] = ab[c]; row[36 + 6 * c + cp] = cd[c]; }
+                    for (int c = 0; c < P1; ++c) { row[(P1 * c + cp) ^ wz] = ab[c]; row[P2 + ((P1 * c + cp) ^ wz)] = cd[c]; }
                 } else if (smp < ((m + 3) & ~3)) {
 #pragma unroll
-                    for (int c = 0; c < 6; ++c) { row[6 * c + cp] = make_float2(0.0f, 0.0f); row[36 + 6 * c + cp] = make_float2(0.0f, 0.0f); }
+                    for (int c = 0; c < P1; ++c) { row[P1 * c + cp] = make_float2(0.0f, 0.0f); row[P2 + P1 * c + cp] = make_float2(0.0f, 0.0f); }
                 }
             }
             __syncthreads();
             if (active) {
                 // per four samples: the operands of the NEXT four are read and formed before this four's products are issued (one wave per
                 // SIMD: nothing else hides the LDS round trip); a full chunk's loop is unrolled, a short one runs the same steps
-                const float2 *rowa = s_tab[0] + kk * GRAM_TS, *rowb = s_tab[SETS - 1] + kk * GRAM_TS;
+                const float2 *rowa = s_tab[0] + kk * TS, *rowb = s_tab[SETS - 1] + kk * TS;
                 float a[R], bo[R], an[R], bn[R];
                 auto operands = [&](int ks, float (&pa)[R], float (&pb)[R]) {
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
-                        pa[r] = gram_phi(rowa + 4 * ks * GRAM_TS, ra[r], rc[r]);
-                        pb[r] = gram_phi(rowb + 4 * ks * GRAM_TS, ca[r], cc[r]);
+                        pa[r] = gram_phi(rowa + 4 * ks * TS, ra[r], rc[r]);
+                        pb[r] = gram_phi(rowb + 4 * ks * TS, ca[r], cc[r]);
                     }
                 };
                 auto step = [&](int ks, bool more) {
@@ -209,25 +241,25 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
     }
     if (!active) return;
     // accumulator lane (n16, kk), register v = entry (row 4 kk + v, column n16) of the tile
-    float *Og = G.out + (size_t)G.seg[blockIdx.y] * NF * NF;
+    float *Og = G.out + (size_t)G.seg[blockIdx.y] * F * F;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        if (r0 + r >= GRAM_TILES) continue;
+        if (r0 + r >= TILES) continue;
         const int row = 16 * (r0 + r) + 4 * kk;
 #pragma unroll
         for (int c = 0; c < R; ++c) {
-            if (c0 + c >= GRAM_TILES) continue;
+            if (c0 + c >= TILES) continue;
             const int col = 16 * (c0 + c) + n16;
 #pragma unroll
-            for (int v = 0; v < 4; ++v) Og[(size_t)(row + v) * NF + col] = tot[r][c][v];
+            for (int v = 0; v < 4; ++v) Og[(size_t)(row + v) * F + col] = tot[r][c][v];
             if (!CROSS && !diag) {                             // the mirror image (a diagonal block holds its own)
 #pragma unroll
-                for (int v = 0; v < 4; ++v) Og[(size_t)col * NF + row + v] = tot[r][c][v];
+                for (int v = 0; v < 4; ++v) Og[(size_t)col * F + row + v] = tot[r][c][v];
             }
         }
         if (rhs && n16 == 0) {
 #pragma unroll
-            for (int v = 0; v < 4; ++v) G.b[(size_t)G.seg[blockIdx.y] * NF + row + v] = btot[r][v];
+            for (int v = 0; v < 4; ++v) G.b[(size_t)G.seg[blockIdx.y] * F + row + v] = btot[r][v];
         }
     }
 }

@@ -19,6 +19,7 @@
 //                            leaves its row untouched and raises the ctx's asynchronous status word
 //   scg_gram_kernel.hpp      SPEC §16.1's feature Gram and §17.1's cross-feature Gram, one kernel template: here only its arguments and
 //                            the two launches (its instantiations are compiled in scg_gram.hip)
+//   scg_basis_kernels.hpp    SPEC §18's basis-order probe: here only the launches of the orders 3 and 7 (compiled in scg_basis.hip)
 // scg_rollout_variants.hip is the second translation unit: every other instantiation of rollout_kernel (SPEC §10's record, §11's
 // interruption, §14's value-ranked choice, §15's audit: the table in scg_rollout_kernel.hpp) and trial_kernel<true>, reached through
 // launch_rollout<REC, Args> / launch_trial_record, which the two kernel headers declare.
@@ -49,6 +50,7 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 #include "scg_apply_kernels.hpp"
 #include "scg_aux_kernels.hpp"
 #include "scg_gram_kernel.hpp"
+#include "scg_basis_kernels.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -1222,9 +1224,9 @@ int scg_fourier_features(scg_ctx *c, int32_t n, const float *x, const float *y, 
 
 // What scg_feature_gram and scg_feature_cross_gram share behind their null checks: the other argument checks, an empty segment's +0
 // fill, the non-empty segments listed into G — as listed, or longest first (ties as listed: blockIdx.y is dispatched slowest, so the
-// longest chains start first) — and the launch. G's pointers are the caller's.
+// longest chains start first) — and the launch. G's pointers are the caller's; F is the feature count of the launch's order (§18).
 static int gram_call(scg_ctx *c, const char *fn, bool null_array, bool yv_without_b, int64_t n, int32_t n_seg, const int64_t *offsets,
-                     GramArgs &G, bool longest_first, hipError_t (*launch)(const GramArgs &, int, hipStream_t), void *stream) {
+                     int F, GramArgs &G, bool longest_first, hipError_t (*launch)(const GramArgs &, int, hipStream_t), void *stream) {
     if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
     if (null_array) return fail_in(c, SCG_ERR_INVALID, fn, "null array argument");
     if (n < 0) return fail_in(c, SCG_ERR_INVALID, fn, "n must be >= 0");
@@ -1245,8 +1247,8 @@ static int gram_call(scg_ctx *c, const char *fn, bool null_array, bool yv_withou
             for (; longest_first && at > 0 && G.count[at - 1] < cnt; --at) { G.seg[at] = G.seg[at - 1]; G.start[at] = G.start[at - 1]; G.count[at] = G.count[at - 1]; }
             G.seg[at] = g; G.start[at] = offsets[g]; G.count[at] = cnt;
         } else {                                          // an empty segment: all +0 (the kernel writes every entry of the others)
-            SCG_HIP(c, hipMemsetAsync(G.out + (size_t)g * NF * NF, 0, (size_t)NF * NF * sizeof(float), s));
-            if (G.b) SCG_HIP(c, hipMemsetAsync(G.b + (size_t)g * NF, 0, (size_t)NF * sizeof(float), s));
+            SCG_HIP(c, hipMemsetAsync(G.out + (size_t)g * F * F, 0, (size_t)F * F * sizeof(float), s));
+            if (G.b) SCG_HIP(c, hipMemsetAsync(G.b + (size_t)g * F, 0, (size_t)F * sizeof(float), s));
         }
     }
     for (int g = n_active; g < GRAM_MAX_SEG; ++g) { G.seg[g] = 0; G.start[g] = 0; G.count[g] = 0; }
@@ -1258,7 +1260,7 @@ int scg_feature_gram(scg_ctx *c, int64_t n, const float *x, const float *y, cons
                      int32_t n_seg, const int64_t *offsets, float *A, float *b, void *stream) {
     GramArgs G = {{{x, y, vx, vy}, {x, y, vx, vy}}, yv, A, b};
     return gram_call(c, "scg_feature_gram", !x || !y || !vx || !vy || !A || !offsets, (yv == nullptr) != (b == nullptr), n, n_seg, offsets,
-                     G, false, launch_feature_gram, stream);
+                     NF, G, false, launch_feature_gram, stream);
 }
 
 int scg_feature_cross_gram(scg_ctx *c, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
@@ -1266,7 +1268,54 @@ int scg_feature_cross_gram(scg_ctx *c, int64_t n, const float *x, const float *y
                            int32_t n_seg, const int64_t *offsets, float *Cm, void *stream) {
     GramArgs G = {{{x, y, vx, vy}, {x2, y2, vx2, vy2}}, nullptr, Cm, nullptr};
     return gram_call(c, "scg_feature_cross_gram", !x || !y || !vx || !vy || !x2 || !y2 || !vx2 || !vy2 || !Cm || !offsets, false, n, n_seg,
-                     offsets, G, true, launch_feature_cross_gram, stream);
+                     offsets, NF, G, true, launch_feature_cross_gram, stream);
+}
+
+// ---- SPEC §18: the basis-order probe. A null ctx is refused first, then an order outside {3, 5, 7}; order 5 goes to the kernels above.
+static int basis_order_features(int32_t order) { return order == 3 ? 256 : (order == 5 ? NF : (order == 7 ? 4096 : 0)); }
+
+int scg_basis_features(scg_ctx *c, int32_t order, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                       float *phi, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_basis_features: null ctx");
+    if (!basis_order_features(order)) return fail(c, SCG_ERR_INVALID, "scg_basis_features: order must be 3, 5 or 7");
+    if (n < 0 || !x || !y || !vx || !vy || !phi) return fail(c, SCG_ERR_INVALID, "scg_basis_features: bad argument");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_basis_features");
+    if (n == 0) return SCG_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (order == 5) {
+        if (n > INT32_MAX) return fail(c, SCG_ERR_INVALID, "scg_basis_features: n must fit 32 bits at order 5");
+        hipLaunchKernelGGL(features_kernel, dim3(n < 8192 ? (int)n : 8192), dim3(64), 0, s, (int)n, x, y, vx, vy, phi);
+        SCG_HIP(c, hipGetLastError());
+    } else {
+        const float *st[4] = {x, y, vx, vy};
+        SCG_HIP(c, launch_basis_features(order, n, st, phi, s));
+    }
+    return SCG_OK;
+}
+
+int scg_basis_gram(scg_ctx *c, int32_t order, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                   const float *yv, int32_t n_seg, const int64_t *offsets, float *A, float *b, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_basis_gram: null ctx");
+    const int F = basis_order_features(order);
+    if (!F) return fail(c, SCG_ERR_INVALID, "scg_basis_gram: order must be 3, 5 or 7");
+    GramArgs G = {{{x, y, vx, vy}, {x, y, vx, vy}}, yv, A, b};
+    return gram_call(c, "scg_basis_gram", !x || !y || !vx || !vy || !A || !offsets, (yv == nullptr) != (b == nullptr), n, n_seg, offsets,
+                     F, G, false, order == 3 ? launch_basis_gram_3 : (order == 5 ? launch_feature_gram : launch_basis_gram_7), stream);
+}
+
+int scg_basis_values(scg_ctx *c, int32_t order, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                     const float *V, int32_t m, float *out, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_basis_values: null ctx");
+    if (!basis_order_features(order)) return fail(c, SCG_ERR_INVALID, "scg_basis_values: order must be 3, 5 or 7");
+    if (n < 0 || !x || !y || !vx || !vy || !V || !out) return fail(c, SCG_ERR_INVALID, "scg_basis_values: bad argument");
+    if (m < 1 || m > SCG_BASIS_VALUES_MAX_ROWS) return fail(c, SCG_ERR_INVALID, "scg_basis_values: m out of range [1, SCG_BASIS_VALUES_MAX_ROWS]");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_basis_values");
+    if (n == 0) return SCG_OK;
+    const float *st[4] = {x, y, vx, vy};
+    SCG_HIP(c, launch_basis_values(order, n, st, V, m, out, reinterpret_cast<hipStream_t>(stream)));
+    return SCG_OK;
 }
 
 int scg_q_values(scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,

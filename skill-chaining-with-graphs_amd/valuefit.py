@@ -51,13 +51,30 @@ def returns_to_go(traj, gamma: float, r_option_success: float, device="cpu") -> 
     return {"offsets": off, "g": g[e, r].cpu().numpy(), "y": y[e, r].cpu().numpy(), "sample": row >= 1}
 
 
-def ridge_solve(A, b, n, ridge: float, scale) -> np.ndarray:
+def ridge_solve(A, b, n, ridge: float, scale, device=None) -> np.ndarray:
     """SPEC §16.3: Delta[a] = (A[a] + Lambda_a)^-1 b[a] with Lambda_a = diag(ridge max(n[a], 1) / scale_f^2), by a float64 Cholesky
     per action. A [n_act][F][F] symmetric (its lower triangle is read), b [n_act][F], n [n_act] sample counts, `scale` §3's
-    table [F]. An action with n[a] = 0 gets Delta = 0 exactly. Returns float64 [n_act][F]."""
-    A, b = np.asarray(A, np.float64), np.asarray(b, np.float64)
+    table [F]. An action with n[a] = 0 gets Delta = 0 exactly. Returns float64 [n_act][F].
+    With `device` a torch device the same system is factored there (A and b may be tensors on it): SPEC §18's fit at order 7 is
+    five factorisations of 4096^2 per value function. The host path is the default and what §16's fit uses."""
     n = np.asarray(n, np.int64).reshape(-1)
     lam = 1.0 / np.asarray(scale, np.float64) ** 2
+    if device is not None:
+        At, bt = torch.as_tensor(A).to(device), torch.as_tensor(b).to(device)
+        lam_t = torch.from_numpy(lam).to(device)
+        out = np.zeros(tuple(bt.shape), np.float64)
+        for a in range(At.shape[0]):
+            if n[a] == 0:
+                continue
+            M = torch.tril(At[a].to(torch.float64))
+            M = M + torch.tril(M, -1).T
+            M.diagonal().add_(float(ridge) * max(int(n[a]), 1) * lam_t)
+            Lc, info = torch.linalg.cholesky_ex(M)
+            if int(info) != 0:
+                raise ScgError(f"ridge_solve: the matrix of action {a} is not positive definite (leading minor {int(info)})")
+            out[a] = torch.cholesky_solve(bt[a].to(torch.float64)[:, None], Lc)[:, 0].cpu().numpy()
+        return out
+    A, b = np.asarray(A, np.float64), np.asarray(b, np.float64)
     out = np.zeros_like(b)
     for a in range(A.shape[0]):
         if n[a] == 0:

@@ -4,8 +4,10 @@ segment). The two are timed interleaved, round by round, as tools/ab_bench.py do
 times, the TFLOP/s counted on the triangle (n 1296 1297 flops) and its share of the 157.3 TF f32 matrix peak.
 The states are snapshots of the headline workload's env states, one per step-batch.
 --lib NAME=PATH times further builds of the library (another tiling: make's DEFS) in the same rounds.
+--order P (3, 5 or 7; SPEC §18) times scg_basis_gram at that order against ScgContext.basis_features + phi.T @ phi,
+flops counted on the triangle of F = (P + 1)^4 features; without it the tool is scg_feature_gram's, as it was.
 
-    python tools/gram_bench.py [--sizes 65536 1048576] [--segs 1 5] [--rounds 5] [--lib r3=path/to/libscg_hip_r3.so] [--out file.jsonl]
+    python tools/gram_bench.py [--sizes 65536 1048576] [--segs 1 5] [--rounds 5] [--lib r3=path/to/libscg_hip_r3.so] [--order 7] [--out file.jsonl]
 """
 import argparse
 import json
@@ -30,13 +32,14 @@ def recorded_states(n, envs):
     return ag, s
 
 
-def materialised(ctx, s, offsets, chunk):
+def materialised(ctx, s, offsets, chunk, order=None):
     import torch
-    out = torch.zeros((len(offsets) - 1, NF, NF), dtype=torch.float32, device=s[0].device)
+    F = NF if order is None else (order + 1) ** 4
+    out = torch.zeros((len(offsets) - 1, F, F), dtype=torch.float32, device=s[0].device)
     for g in range(len(offsets) - 1):
         for lo in range(offsets[g], offsets[g + 1], chunk):
             hi = min(lo + chunk, offsets[g + 1])
-            phi = ctx.features([t[lo:hi] for t in s])
+            phi = ctx.features([t[lo:hi] for t in s]) if order is None else ctx.basis_features(order, [t[lo:hi] for t in s])
             out[g].addmm_(phi.T, phi)
     return out
 
@@ -46,8 +49,9 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[65536, 1048576]); ap.add_argument("--segs", type=int, nargs="+", default=[1, 5])
     ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--chunk", type=int, default=65536)
     ap.add_argument("--envs", type=int, default=65536); ap.add_argument("--lib", nargs="*", default=[])
-    ap.add_argument("--out", default=None)
+    ap.add_argument("--order", type=int, default=None, choices=(3, 5, 7)); ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    F = NF if a.order is None else (a.order + 1) ** 4
     import torch
     from skill_chaining_with_graphs_amd.core import ScgContext
     ag, s = recorded_states(max(a.sizes) * max(a.segs), a.envs)
@@ -60,16 +64,21 @@ def main():
         for k in a.segs:
             off = [i * n for i in range(k + 1)]
             sub = [t[: n * k] for t in s]
-            runs = {name: (lambda c=c: c.feature_gram(sub, off)) for name, c in ctxs.items()}
-            runs["materialised"] = lambda: materialised(ag.ctx, sub, off, a.chunk)
+            if a.order is None:
+                runs = {name: (lambda c=c: c.feature_gram(sub, off)) for name, c in ctxs.items()}
+            else:
+                runs = {name: (lambda c=c: c.basis_gram(a.order, sub, off)) for name, c in ctxs.items()}
+            runs["materialised"] = lambda: materialised(ag.ctx, sub, off, a.chunk, a.order)
             ref = runs["shipped"]()
             err = float((runs["materialised"]() - ref).abs().max() / ref.abs().max())
             times = {name: [] for name in runs}
             for _ in range(a.rounds):
                 for name, fn in runs.items():
                     times[name].append(rig.timed(fn, 1) * 1e3)
-            flops = n * k * NF * (NF + 1)
+            flops = n * k * F * (F + 1)
             row = {"samples_per_segment": n, "segments": k, "rounds": a.rounds, "materialised_max_rel_diff": err}
+            if a.order is not None:
+                row["order"] = a.order
             for name, t in times.items():
                 ms = statistics.median(t)
                 row[name] = {"ms": round(ms, 3), "min_ms": round(min(t), 3), "tflops_triangle": round(flops / ms / 1e9, 2),
