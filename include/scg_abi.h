@@ -285,6 +285,25 @@ int scg_rollout_audit(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, in
                       uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
                       const scg_record *rec, uint32_t rules, const scg_audit *audit, void *stream);
 
+/* ---- branch rollouts (SPEC §19): resume a given state with the first action forced ----
+ * scg_rollout_branch is scg_rollout_audit (any `rules`; `rec` and `audit` may be NULL) plus `first_action`, a DEVICE array [N] of
+ * uint8, read only. first_action = NULL, or every entry >= SCG_NUM_ACTIONS, is scg_rollout_audit: the same kernels, the same results.
+ * The forced step is the launch's first real step: the step at t0 without a begin flag, at t0 + 1 with BEGIN or BEGIN_AT (with
+ * BEGIN_AT an exploring start: the caller's state, then the forced action). For every env that is stepped, first_action[e] <
+ * SCG_NUM_ACTIONS replaces §4.3's choice of that step's action; any other value means not forced (255 is the canonical one). The
+ * step's RNG draw is made as ever (draws are keyed by (seed, global env id, t): a force shifts no later draw), and everything else
+ * of the step is unchanged: physics, done, §4.2, the record row (its `action` is the forced one), the counters, §15's d and g.
+ * Every later step is scg_rollout_audit's. An env skipped under ONE_EPISODE ignores its entry and writes nothing.
+ * Errors: scg_rollout_audit's, and SCG_ERR_INVALID (nothing launched) for a non-NULL first_action with n_steps == 0: there is no
+ * real step to force. The write set is scg_rollout_audit's; first_action is never written. Results do not depend on the launch
+ * geometry or the block build; no asynchronous failure bit is raised. */
+int scg_rollout_branch(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                       int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                       const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                       uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                       const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action,
+                       void *stream);
+
 /* Device pointers of the ctx-owned reduced gradient G[n_vf][5][1296] and counts n_k[n_vf] (int32)
  * left by the last scg_step(LEARN) — the buffers a multi-rank caller all-reduces (SPEC §5). */
 int scg_grad_buffers(scg_ctx *ctx, float **G, int32_t **n_k);

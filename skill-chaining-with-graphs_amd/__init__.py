@@ -23,7 +23,7 @@ def __getattr__(name):
     if name == "TrialResult":
         from .trials import TrialResult
         return TrialResult
-    if name in ("EpisodeStats", "GateAudit"):
+    if name in ("EpisodeStats", "GateAudit", "BranchResult"):
         from . import evaluation
         return getattr(evaluation, name)
     if name == "FourierBasis":

@@ -31,6 +31,8 @@ TRIAL_MAX_STEPS = ROLLOUT_MAX_STEPS
 ROLLOUT_TERM_INTERRUPTED = 5   # include/scg_abi.h SCG_ROLLOUT_TERM_INTERRUPTED: a recorded row's term where an option was interrupted
 SELECT_INTERRUPT = 1       # include/scg_abi.h SCG_SELECT_*: the rules of scg_rollout_select (SPEC §11, §14)
 SELECT_BEST = 2
+NO_FIRST_ACTION = 255      # SPEC §19: scg_rollout_branch's first_action entry of an env that is not forced (any value >= NUM_ACTIONS)
+BRANCH_ID_BASE = 2 ** 40   # the global env ids of branch rollouts start here: no stream of a record (env_id_base = 0) is reused
 ABI_VERSION = 5            # include/scg_abi.h SCG_ABI_VERSION
 ASYNC_FIT_TIMEOUT = 0x1
 ASYNC_STEP_HANDOFF = 0x2
@@ -162,6 +164,7 @@ _SIGS = {
     "scg_rollout_interrupt": (C.c_int, _ROLLOUT + [_P, C.POINTER(Record), _P]),
     "scg_rollout_select": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, _P]),
     "scg_rollout_audit": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, C.POINTER(Audit), _P]),
+    "scg_rollout_branch": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, C.POINTER(Audit), _P, _P]),
     "scg_grad_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "scg_set_grad_buffers": (C.c_int, [_P, _P, _P]),
     "scg_apply_update": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -17,7 +17,7 @@ from . import _lib
 from . import dist as _dist
 from ._lib import CLF_STRIDE, NUM_ACTIONS, NUM_FEATURES, ScgError, auto_block_envs
 from .core import EnvState, ScgContext
-from .evaluation import EpisodeStats, GateAudit
+from .evaluation import BranchResult, EpisodeStats, GateAudit
 from .maps import PinballMap, load_map
 from .option import Option
 from .pinball import PinballDomain
@@ -90,7 +90,7 @@ class SkillChainingAgent:
         self.options: List[Option] = [Option(self, k) for k in range(self.n_vf)]
         self.trace, self._ex, self._ex_cap = None, {}, None     # enable_tracing(): the ring + events, the example buffers by option
         # grow_skill_tree()'s per-node buffers (kept for inspection); evaluate()'s n_episodes -> (context, EnvState, EpisodeStats); option_trials()'s context
-        self._frontier, self._eval_ctx, self._trial_ctx = None, {}, None
+        self._frontier, self._eval_ctx, self._trial_ctx, self._branch_ctx = None, {}, None, {}
 
     # ------------------------------------------------------------------ option management (outer loop)
     def enable_option(self, k: int, enabled: bool = True) -> None:
@@ -814,6 +814,131 @@ class SkillChainingAgent:
             for k in vfs:
                 self.W[k].copy_(W_cur[k])
         return report, W_cur
+
+    # ------------------------------------------------------------------ branch rollouts (SPEC §19)
+    def branch_returns(self, sources: dict, actions, replicates: int = 8, epsilon: float = 0.1, seed: Optional[int] = None,
+                       interrupt: bool = False, choose: Optional[str] = None, steps_per_launch: int = 64) -> BranchResult:
+        """Monte-Carlo returns of forced first actions from recorded states (SPEC §19). `sources`: Trajectory.resume_state's dict
+        for M states (x, y, vx, vy, option_id, opt_steps, ep_steps, vf_next); `actions` [M][A] uint8, A = 1 .. 5: the first actions
+        to force per state; `replicates` = R runs of each. Env (i * A + a) * R + r of a cached context of M A R envs, its global
+        env ids from _lib.BRANCH_ID_BASE on (no random stream of a record, whose ids start at 0, is reused), starts in source i's
+        whole env state with qcache = Q_vf_next(s, .), takes actions[i][a] on its first step (scg_rollout_branch) and goes on under
+        the current policy (W, clf, enabled options, `epsilon`, `interrupt`, `choose`) to the end of the episode: one-episode
+        launches without a begin at t0 = 0, spl, 2 spl, ... Returns a BranchResult (g, ret, goal, steps: [M][A][R], from the
+        branch step on; g carries no completion bonus). The training run is left alone exactly as evaluate() leaves it."""
+        if choose not in (None, "value"):
+            raise ValueError(f"choose must be None or 'value', not {choose!r}")
+        acts = np.ascontiguousarray(np.asarray(actions, np.uint8))
+        if acts.ndim != 2 or not (1 <= acts.shape[1] <= NUM_ACTIONS) or acts.shape[0] < 1 or int(acts.max()) >= NUM_ACTIONS:
+            raise ValueError(f"actions must be [M][A] with 1 <= A <= {NUM_ACTIONS} and entries below {NUM_ACTIONS}")
+        M, A = (int(v) for v in acts.shape)
+        R, spl = int(replicates), int(steps_per_launch)
+        if R < 1:
+            raise ValueError("replicates must be >= 1")
+        if not (1 <= spl <= _lib.ROLLOUT_MAX_STEPS):
+            raise ValueError(f"steps_per_launch must be in [1, {_lib.ROLLOUT_MAX_STEPS}]")
+        need = ("x", "y", "vx", "vy", "option_id", "opt_steps", "ep_steps", "vf_next")
+        src = {f: np.asarray(sources[f]).reshape(-1) for f in need}
+        if any(len(v) != M for v in src.values()):
+            raise ValueError(f"sources must hold {M} states, one per row of actions")
+        vf_next = src["vf_next"].astype(np.int64)
+        if np.any(vf_next < 0) or np.any(vf_next >= self.n_vf):
+            raise ValueError(f"sources['vf_next'] must name value functions 0..{self.n_vf - 1}")
+        n, per = M * A * R, A * R
+        seed = int(self.ctx.cfg.seed) if seed is None else int(seed)
+        cache = self._branch_ctx                               # one branch context per env count, as the evaluation contexts
+        if n not in cache or cache[n][0].cfg.seed != seed:
+            if n in cache:
+                cache.pop(n)[0].close()
+            bctx = ScgContext(n, self.n_options, self.map, device=self.ctx.device.index, seed=seed,
+                              env_id_base=_lib.BRANCH_ID_BASE, block_envs=self.ctx.block_envs)
+            cache[n] = (bctx, EnvState(n, bctx.device, self.map), EpisodeStats(self.n_vf, n, bctx.device))
+        bctx, st, stats = cache[n]
+        self._mirror_training(bctx, epsilon)
+        stats.zero_()
+        dev = bctx.device
+        up = lambda v, dt: torch.from_numpy(np.ascontiguousarray(v)).to(dev).to(dt).contiguous()
+        s_src = [up(src[f], torch.float32) for f in ("x", "y", "vx", "vy")]
+        q_src = torch.zeros((NUM_ACTIONS, M), dtype=torch.float32, device=dev)
+        for k in sorted(set(vf_next.tolist())):                # qcache = Q_vf_next(s, .), as the step before left it
+            at = torch.from_numpy(np.nonzero(vf_next == k)[0]).to(dev)
+            q_src[:, at] = bctx.q_values([t[at].contiguous() for t in s_src], self.W[k].contiguous().view(-1))
+        for dst, v in zip((st.x, st.y, st.vx, st.vy), s_src):
+            dst.copy_(v.repeat_interleave(per))
+        for f in ("option_id", "opt_steps", "ep_steps"):
+            getattr(st, f).copy_(up(src[f], torch.int32).repeat_interleave(per))
+        st.qcache.copy_(q_src.repeat_interleave(per, dim=1))
+        st.action.zero_(); st.reward.zero_(); st.done.zero_()
+        audit = GateAudit(n, dev)                              # disc_ret = 0, disc_g = 1, disc_final = NaN until the episode ends
+        first = up(acts.reshape(-1), torch.uint8).repeat_interleave(R).contiguous()
+        for i in range(-(-int(self.ctx.cfg.max_episode_steps) // spl)):
+            bctx.rollout(st, self.W, self.clf, self.enabled_mask, i * spl, spl, stats, one_episode=True, interrupt=interrupt,
+                         choose=choose, audit=audit, first_action=first if i == 0 else None)
+        shape = (M, A, R)
+        ep0 = np.repeat(src["ep_steps"].astype(np.int64), per).reshape(shape)
+        res = BranchResult(acts, audit.disc_final.cpu().numpy().reshape(shape), stats.ret_sum.cpu().numpy().reshape(shape),
+                           stats.goals.cpu().numpy().reshape(shape) > 0,
+                           stats.len_sum.cpu().numpy().astype(np.int64).reshape(shape) - ep0)
+        res.qcache = q_src.cpu().numpy().T.copy()              # [M][5]: what the source's policy saw
+        res.finished = stats.finished.cpu().numpy().reshape(shape) != 0
+        return res
+
+    def branch_audit(self, trajectory=None, n_states: int = 1024, replicates: int = 8, actions: str = "all", vfs=None,
+                     epsilon: float = 0.1, seed: Optional[int] = None, n_episodes: int = 4096, interrupt: bool = False,
+                     choose: Optional[str] = None, steps_per_launch: int = 64) -> dict:
+        """How much of a value function's error is noise, and is its greedy action the best one (SPEC §19)? Records episodes as
+        fit_values_to_returns does (or takes its `trajectory`), then per value function k of `vfs` (default: all) draws `n_states`
+        rows (fewer where there are fewer) uniformly, with a generator seeded by `seed`, from the held-out (odd) envs' rows with
+        vf = k — the state distribution §16's held-out RMSE is over — rebuilds each row's env state (Trajectory.resume_state) and
+        runs branch_returns from it: `actions` = "taken": the recorded action only; "all": all five. `replicates` must be even, >= 2.
+        Returns {"trajectory", "vf": {k: {"n", "rows", "taken", "g_recorded", "spread", "actions" (with "all"), "result"}}}:
+        "spread" is BranchResult.spread of the recorded action against the record's own return-to-go (§16.2's g, "g_recorded"),
+        "actions" BranchResult.action_table of a_W = the first maximum of the source's qcache, "result" the BranchResult, "rows"
+        the sampled rows' (env, row), "taken" their recorded actions; "trajectory" is the record. A branch's g carries no
+        completion bonus, so with r_option_success != 0 a report for k >= 1 is refused. All arithmetic is host float64, in state
+        order. The training run is left alone exactly as evaluate() leaves it."""
+        from .valuefit import returns_to_go
+        if actions not in ("all", "taken"):
+            raise ValueError(f"actions must be 'all' or 'taken', not {actions!r}")
+        R = int(replicates)
+        if R < 2 or R % 2:
+            raise ValueError(f"replicates must be even and >= 2, not {replicates}")
+        if int(n_states) < 1:
+            raise ValueError("n_states must be >= 1")
+        vfs = list(range(self.n_vf)) if vfs is None else [int(k) for k in vfs]
+        if any(not (0 <= k < self.n_vf) for k in vfs):
+            raise ValueError(f"vfs must name value functions 0..{self.n_vf - 1}")
+        c = self.ctx.cfg
+        if float(c.r_option_success) != 0.0 and any(k >= 1 for k in vfs):
+            raise ScgError("branch_audit: r_option_success != 0: a branch's return carries no completion bonus, so it is not "
+                           "SPEC §16.2's target of an option's value function; report vfs=[0] only")
+        if trajectory is None:
+            traj, _ = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose)
+        else:
+            traj = trajectory
+        flat = traj.to_numpy()
+        tg = returns_to_go(flat, float(c.gamma), float(c.r_option_success))
+        off = flat["offsets"]
+        env = np.repeat(np.arange(traj.n), np.diff(off))
+        row = np.arange(int(off[-1])) - off[:-1][env]
+        rng = np.random.default_rng(int(c.seed) if seed is None else int(seed))
+        report = {"replicates": R, "actions": actions, "trajectory": traj, "vf": {}}
+        for k in vfs:
+            rows = np.nonzero(tg["sample"] & (flat["vf"] == k) & (env % 2 == 1))[0]
+            if len(rows) > int(n_states):
+                rows = np.sort(rng.choice(rows, int(n_states), replace=False))
+            taken = flat["action"][rows].astype(np.uint8)
+            rep = {"n": int(len(rows)), "rows": (env[rows], row[rows]), "taken": taken.astype(np.int64), "g_recorded": tg["g"][rows]}
+            if len(rows):
+                acts = np.tile(np.arange(NUM_ACTIONS, dtype=np.uint8), (len(rows), 1)) if actions == "all" else taken[:, None]
+                res = self.branch_returns(traj.resume_state(env[rows], row[rows]), acts, R, epsilon, seed, interrupt, choose,
+                                          steps_per_launch)
+                rep["spread"] = res.spread(tg["g"][rows], column=taken.astype(np.int64) if actions == "all" else 0)
+                if actions == "all":
+                    rep["actions"] = res.action_table(np.argmax(res.qcache, axis=1))
+                rep["result"] = res
+            report["vf"][k] = rep
+        return report
 
     def _mirror_training(self, side: ScgContext, epsilon: float) -> None:
         """Copy the training run's settings into a side context (evaluation, trials): its hyper-parameters (epsilon aside),

@@ -203,7 +203,8 @@ class ScgContext:
 
     def rollout(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, n_steps: int,
                 stats=None, begin: bool = False, one_episode: bool = False, record=None, begin_at: bool = False,
-                interrupt: bool = False, interrupts=None, choose: Optional[str] = None, overrides=None, audit=None) -> None:
+                interrupt: bool = False, interrupts=None, choose: Optional[str] = None, overrides=None, audit=None,
+                first_action: Optional[torch.Tensor] = None) -> None:
         """SPEC §8: n_steps acting steps in ONE launch, bit for bit n_steps calls of step(learn=False) at t0 .. t0+n_steps-1
         (with `begin`: a new episode for every env at t0 first, the steps at t0+1 .. t0+n_steps). W is read, never written.
         `stats` (EpisodeStats of this context's n_vf and n_envs, on its device) receives the episode counters; `one_episode`
@@ -218,7 +219,10 @@ class ScgContext:
         of an option that was not the lowest-numbered candidate, by default into `stats.overrides` (created on demand).
         SPEC §15: `audit` (a GateAudit of n_envs envs on this device) makes the launch an audited one (scg_rollout_audit, with the
         rules `interrupt` and `choose` name): its `force`, where set, decides the begin pseudo-step's choice (begin or begin_at
-        only), and its arrays receive the begin choice, the values it compared and the discounted task return."""
+        only), and its arrays receive the begin choice, the values it compared and the discounted task return.
+        SPEC §19: `first_action` (uint8 [n_envs] on this device, read only) makes the launch a branch rollout (scg_rollout_branch, with
+        whatever else was asked for): on the launch's first real step an env whose entry is below 5 takes that action instead of
+        §4.3's choice, the step's draw made as ever; 255 (_lib.NO_FIRST_ACTION) leaves an env alone. It needs n_steps >= 1."""
         if choose not in (None, "value"):
             raise ValueError(f"rollout: choose must be None or 'value', not {choose!r}")
         self._chk_operands(st, W, clf)
@@ -270,11 +274,18 @@ class ScgContext:
                 if getattr(audit, f) is not None:
                     self._chk(getattr(audit, f), dt, N, "audit." + f)
             au = audit.c_struct()
+        if first_action is not None:
+            self._chk(first_action, torch.uint8, N, "first_action")
+            if n_steps == 0:
+                raise ScgError("rollout: first_action with n_steps = 0: there is no real step to force")
         # the narrowest entry point that takes what was asked for, and its tail behind the arguments all five start with
         rules = (_lib.SELECT_BEST if choose is not None else 0) | (_lib.SELECT_INTERRUPT if interrupt else 0)
         ints, ovr = (None if a is None else _ptr(a) for a in (interrupts, overrides))
         rc_ref = None if rc is None else C.byref(rc)
-        if au is not None:
+        if first_action is not None:
+            name, tail = "scg_rollout_branch", (ints, ovr, rc_ref, C.c_uint32(rules), None if au is None else C.byref(au),
+                                                _ptr(first_action))
+        elif au is not None:
             name, tail = "scg_rollout_audit", (ints, ovr, rc_ref, C.c_uint32(rules), C.byref(au))
         elif choose is not None:
             name, tail = "scg_rollout_select", (ints, ovr, rc_ref, C.c_uint32(rules))

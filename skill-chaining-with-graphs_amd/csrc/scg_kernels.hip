@@ -679,10 +679,12 @@ struct RolloutCall {
     int32_t *interrupts, *overrides;
     uint32_t rules;                // SCG_SELECT_*; scg_rollout_interrupt: SCG_SELECT_INTERRUPT
     const scg_audit *audit;
+    const uint8_t *first_action;   // scg_rollout_branch (SPEC §19)
 };
 
-// the five rollout entry points (`fn` names the caller in error texts). The kernel follows from what the call asks for:
-//   audit      a member of `audit` given (SPEC §15; every member NULL counts as no audit)
+// the six rollout entry points (`fn` names the caller in error texts). The kernel follows from what the call asks for:
+//   audit      a member of `audit` given (SPEC §15; every member NULL counts as no audit), or a first_action (SPEC §19: the AUDIT
+//              kernels are the ones that read it; with no audit member they write nothing of the audit's)
 //   best, intr SCG_SELECT_BEST / SCG_SELECT_INTERRUPT in `rules` (SPEC §14 / §11), counting into `overrides` / `interrupts`
 //   rec, at    a record (SPEC §10) / SCG_ROLLOUT_BEGIN_AT, from here on BEGIN in `flags` plus `at`
 // Neither audit, best, rec nor at: the plain kernel, or with intr the non-recording interrupting one; otherwise a RolloutVar by (intr, best, audit)
@@ -717,6 +719,7 @@ static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
         return fail_in(c, SCG_ERR_INVALID, fn, "audit->force without SCG_ROLLOUT_BEGIN or _BEGIN_AT");
     if (audit && !audit->disc_ret != !audit->disc_g)
         return fail_in(c, SCG_ERR_INVALID, fn, "audit->disc_ret and audit->disc_g go together");
+    if (a.first_action && a.n_steps == 0) return fail_in(c, SCG_ERR_INVALID, fn, "first_action with n_steps == 0: no real step to force");
     SCG_CHECK_ASYNC(c);
     DeviceGuard dev_guard_(c->cfg.device);
     if (!dev_guard_.ok) return fail_in(c, SCG_ERR_HIP, fn, "cannot make the context's device current");
@@ -742,9 +745,11 @@ static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
     if (intr) V.interrupts = a.interrupts;
     if (best) V.overrides = a.overrides;
     if (audit) { V.au = *audit; V.gamma = c->cfg.gamma; }
-    const bool var = audit || best || a.rec || at;        // what only the RolloutVar kernels take
+    V.first_action = a.first_action;
+    const bool aud = audit || a.first_action;             // the AUDIT kernels: they alone read first_action
+    const bool var = aud || best || a.rec || at;          // what only the RolloutVar kernels take
     hipError_t rollout_kernel_launch = hipSuccess;
-    switch ((var ? 8 : 0) | (audit ? 4 : 0) | (best ? 2 : 0) | (intr ? 1 : 0)) {                    // INT    BEST   AUDIT
+    switch ((var ? 8 : 0) | (aud ? 4 : 0) | (best ? 2 : 0) | (intr ? 1 : 0)) {                      // INT    BEST   AUDIT
     case 0:
         hipLaunchKernelGGL((rollout_kernel<false, RolloutArgs>), dim3(grid), dim3(RO_THREADS), 0, s, R);
         rollout_kernel_launch = hipGetLastError();
@@ -809,6 +814,17 @@ int scg_rollout_audit(scg_ctx *c, float *x, float *y, float *vx, float *vy, int3
     return rollout_launch("scg_rollout_audit", c, {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
                                                    enabled_mask, t0, n_steps, flags, stats, stream, true, rec, interrupts, overrides,
                                                    rules, audit});
+}
+
+// first_action = NULL: scg_rollout_audit's launch, under this entry point's name in error texts
+int scg_rollout_branch(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                       int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                       const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                       uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                       const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action, void *stream) {
+    return rollout_launch("scg_rollout_branch", c, {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
+                                                    enabled_mask, t0, n_steps, flags, stats, stream, true, rec, interrupts, overrides,
+                                                    rules, audit, first_action});
 }
 
 static int trials_launch(const char *fn, scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,

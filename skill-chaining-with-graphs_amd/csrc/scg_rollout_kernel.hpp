@@ -54,6 +54,8 @@ struct RolloutArgs {
 //                                                                            of s_qv (root: 0); phase G enters the candidate whose value is highest
 //   true   RolloutVar<I,     B,     true>     scg_rollout_audit, by `rules`  SPEC §15: the begin pseudo-step's choice may be forced per env, and the
 //          (all four I, B)                                                   discounted task return is kept in two more registers across the steps
+//                                             scg_rollout_branch             SPEC §19: the same four kernels; the first real step's action may be
+//                                                                            given per env (first_action, read on that step only)
 // Every REC instantiation shares ONE argument layout, RolloutVarArgs; the non-recording interrupting kernel keeps
 // its own, because `interrupts` at another offset changes its code.
 struct RolloutIntArgs : RolloutArgs {
@@ -67,6 +69,7 @@ struct RolloutVarArgs : RolloutArgs {
     int32_t *overrides;            // [n_vf][N] in/out, may be null (read with BEST only)
     scg_audit au;                  // device pointers, any may be null (read with AUDIT only)
     float gamma;
+    const uint8_t *first_action;   // [n], may be null (read with AUDIT only): SPEC §19's forced action of the first real step
 };
 template <bool I, bool B, bool AU>
 struct RolloutVar : RolloutVarArgs {
@@ -177,6 +180,15 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         if (valid) env_draw(gid, t, A.seed, u);
         int a = NACT - 1;
         if (valid && !is_begin) a = act_spec(u, qc, A.epsilon);
+        if constexpr (AUDIT) {                                 // SPEC §19: the launch's first real step takes the caller's action
+            if (valid && j == (A.begin ? 1 : 0)) {             // (the draw above is made as ever; fetched here, once: see the exit)
+                const uint8_t *const fa = kernel_args<Args>()->first_action;
+                if (fa) {
+                    const int f = fa[e];
+                    if (f < NACT) a = f;
+                }
+            }
+        }
         float px = sx, py = sy, pvx = svx, pvy = svy, rew = 0.0f;
         bool goal = false;
         if (!is_begin) rew = wave_physics(s_edges, A.cellmask, A.ms, sw, valid, px, py, pvx, pvy, a, goal);      // (wave-uniform)

@@ -1,5 +1,6 @@
 // scg_rollout_variants.hip — every instantiation of rollout_kernel but scg_rollout's plain one (the table in scg_rollout_kernel.hpp:
-// SPEC §10's record, §11's interruption, §14's value-ranked choice, §15's audit), trial_kernel<true> (SPEC §10), and their launches.
+// SPEC §10's record, §11's interruption, §14's value-ranked choice, §15's audit with §19's forced first action), trial_kernel<true>
+// (SPEC §10), and their launches.
 //
 // They are apart from scg_kernels.hip because what shares a module with rollout_kernel<false, RolloutArgs> and trial_kernel<false>
 // changes the gfx950 code of those two (two shifts of a known non-negative value came out signed). Among themselves

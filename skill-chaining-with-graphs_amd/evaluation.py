@@ -1,6 +1,6 @@
 """EpisodeStats — the per-env counters of an acting rollout (SPEC §8, scg_rollout; §11, scg_rollout_interrupt) and their
 host-side summary; GateAudit — the per-env arrays of an audited rollout (SPEC §15, scg_rollout_audit) and the summary of an
-enter / decline pair of them."""
+enter / decline pair of them; BranchResult — the returns of branch rollouts (SPEC §19, scg_rollout_branch) and their statistics."""
 from __future__ import annotations
 
 import ctypes as C
@@ -173,3 +173,91 @@ class GateAudit:
             }
         return {"overall": row(np.ones(option.shape, bool)),
                 "options": {int(k): row(option == k) for k in sorted(set(option.tolist()))}}
+
+
+class BranchResult:
+    """The returns of branch rollouts (SPEC §19): M source states, A first actions per state, R replicates of each, every
+    replicate resumed from the source's whole env state with that first action forced and continued under the current policy on
+    a random stream of its own. Host arrays:
+      actions [M][A] uint8   the forced first action of column a
+      g       [M][A][R]      the discounted TASK return from the branch step on (SPEC §15's d of the episode's end, binary32)
+      ret     [M][A][R]      the undiscounted return from the branch step on;  goal [M][A][R] bool;  steps [M][A][R] steps taken
+    The statistics are host float64, in state order. They condition on the WHOLE env state (position, velocity, ep_steps,
+    opt_steps, a declined id), not on (x, y, vx, vy) alone: spread() is the floor under a function of the whole state."""
+
+    def __init__(self, actions, g, ret, goal, steps):
+        self.actions = np.asarray(actions, np.uint8)
+        self.g, self.ret = np.asarray(g, np.float32), np.asarray(ret, np.float64)
+        self.goal, self.steps = np.asarray(goal, bool), np.asarray(steps, np.int64)
+        if self.actions.ndim != 2 or self.g.ndim != 3 or self.g.shape[:2] != self.actions.shape:
+            raise ValueError("BranchResult: actions must be [M][A] and g [M][A][R]")
+        self.M, self.A, self.R = (int(v) for v in self.g.shape)
+
+    def _moments(self):
+        """(mean [M][A], unbiased variance [M][A]) of g over the replicates, float64, summed in replicate order."""
+        if self.R < 2:
+            raise ValueError("BranchResult: the within-state variance needs at least 2 replicates")
+        g = self.g.astype(np.float64)
+        mean = np.cumsum(g, axis=2)[:, :, -1] / self.R
+        var = np.cumsum((g - mean[:, :, None]) ** 2, axis=2)[:, :, -1] / (self.R - 1)
+        return mean, var
+
+    def spread(self, g_recorded=None, column=0) -> dict:
+        """The within-state spread of the return-to-go under action column `column` (the recorded action's; one for all states, or
+        one per state [M]): n, spread_rmse =
+        sqrt(mean_i s_i^2) with s_i^2 the unbiased variance over the R replicates (the noise floor under ANY function of the
+        whole env state, whatever its basis), zero_variance (the share of states with s_i^2 = 0) and, with `g_recorded` [M] (the
+        record's own return-to-go of each state), recorded_z2: the mean over the states with s_i^2 > 0 of (g_recorded - mean_i)^2
+        / (s_i^2 (1 + 1/R)), near 1 where the record's continuation is one more draw from the replicates' distribution (NaN
+        without such a state), and recorded_z2_median, the median of the same ratios. With s_i^2 estimated from R replicates the
+        ratio is heavy-tailed: for normal returns it is F(1, R - 1), whose mean is (R - 1) / (R - 3) (1.4 at R = 8) and whose
+        median is near 0.5, and a state whose replicates almost agree while the record took an exploring step can carry the
+        whole mean. Read the median beside the mean."""
+        mean, var = self._moments()
+        col = np.broadcast_to(np.asarray(column, np.int64), (self.M,))
+        mean, var = mean[np.arange(self.M), col], var[np.arange(self.M), col]
+        out = {"n": self.M, "spread_rmse": float(np.sqrt(_mean(var))) if self.M else float("nan"),
+               "zero_variance": _mean(var == 0)}
+        if g_recorded is not None:
+            gr = np.asarray(g_recorded, np.float64).reshape(-1)
+            if gr.shape != (self.M,):
+                raise ValueError(f"g_recorded must hold {self.M} entries")
+            pos = var > 0
+            z2 = (gr[pos] - mean[pos]) ** 2 / (var[pos] * (1.0 + 1.0 / self.R))
+            out["recorded_z2"] = _mean(z2)
+            out["recorded_z2_median"] = float(np.median(z2)) if z2.size else float("nan")
+        return out
+
+    def action_table(self, a_w) -> dict:
+        """Is the action a value function prefers the best one? `a_w` [M]: the action to judge per state (the first maximum of
+        the source's qcache), which must be one of the state's columns. With mean_i[a] the replicate mean of column a:
+          greedy_agreement  mean(a_w == the action of argmax_a mean_i[a])  (first maximum)
+          gap               mean(max_a mean_i[a] - mean_i[a_w]): BIASED UPWARDS by the noise, since the maximum of noisy means
+                            exceeds the mean of the best action; it is >= 0 by construction even where every action is equal
+          gap_holdout       the best action chosen on the even-indexed replicates, its mean minus a_w's evaluated on the
+                            odd-indexed ones: the unbiased one-step improvement available (R must be even and >= 2)
+          significant       the share of states whose gap_i exceeds twice its standard error sqrt((s_i^2[best] + s_i^2[a_w]) / R)
+        and per_state: a_w, best (action ids), mean [M][A], var [M][A], gap, gap_holdout."""
+        if self.R < 2 or self.R % 2:
+            raise ValueError(f"BranchResult.action_table: replicates must be even and >= 2, not {self.R}")
+        a_w = np.asarray(a_w, np.int64).reshape(-1)
+        if a_w.shape != (self.M,):
+            raise ValueError(f"a_w must hold {self.M} entries")
+        hit = self.actions.astype(np.int64) == a_w[:, None]
+        if not hit.any(axis=1).all():
+            raise ValueError("a_w names an action that is not among a state's columns")
+        cw, idx = np.argmax(hit, axis=1), np.arange(self.M)
+        mean, var = self._moments()
+        best = np.argmax(mean, axis=1)
+        gap = mean[idx, best] - mean[idx, cw]
+        g = self.g.astype(np.float64)
+        half = self.R // 2
+        even = np.cumsum(g[:, :, 0::2], axis=2)[:, :, -1] / half
+        odd = np.cumsum(g[:, :, 1::2], axis=2)[:, :, -1] / half
+        pick = np.argmax(even, axis=1)
+        gap_h = odd[idx, pick] - odd[idx, cw]
+        se = np.sqrt((var[idx, best] + var[idx, cw]) / self.R)
+        return {"n": self.M, "greedy_agreement": _mean(best == cw), "gap": _mean(gap), "gap_holdout": _mean(gap_h),
+                "significant": _mean(gap > 2.0 * se),
+                "per_state": {"a_w": a_w, "best": self.actions[idx, best].astype(np.int64), "mean": mean, "var": var, "gap": gap,
+                              "gap_holdout": gap_h}}

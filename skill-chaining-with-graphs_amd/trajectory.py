@@ -147,6 +147,48 @@ class Trajectory:
             out["interrupted"] = [int(v) for v in intr]
         return out
 
+    def resume_state(self, env, row) -> dict:
+        """SPEC §19.2: the env state a one-episode record's env `env[i]` was in BEFORE step `row[i]` (row 0 is its begin row, so
+        row >= 1), exactly as the kernel held it — what a branch rollout resumes. Host arrays, one entry per (env, row):
+          x, y, vx, vy, option_id   of row - 1 (the begin row holds the start state; a row that ends no episode has no reset)
+          ep_steps                  row - 1
+          opt_steps                 the recurrence the kernel runs over rows 0 .. row - 1: 0 after the begin row, prev + 1 after a
+                                    row with vf >= 1 and term == 0 (the option goes on), otherwise 0 (an interrupted row has term 5)
+          vf_next                   the value function that runs step `row`: option_id if 1 <= option_id < n_vf, else 0
+        plus env and row as given. Needs the state fields, vf, term, done, action and option_id, and n_vf (given at construction).
+        Raises ValueError for a row < 1 or at or beyond the env's length, and where row - 1 ended the episode (done != 0 on a row
+        that is not the begin row): the state after that row is the next episode's drawn start, which the record does not hold."""
+        need = ("x", "y", "vx", "vy", "vf", "term", "done", "action", "option_id")
+        if any(f not in self.fields for f in need) or self.n_vf is None:
+            raise ValueError(f"resume_state needs the record fields {need} and n_vf")
+        env, row = np.asarray(env, np.int64).reshape(-1), np.asarray(row, np.int64).reshape(-1)
+        if env.shape != row.shape:
+            raise ValueError("env and row must have one length")
+        if np.any(env < 0) or np.any(env >= self.n):
+            raise ValueError(f"env outside the record's {self.n} envs")
+        out = {"x": np.zeros(len(env), np.float32), "y": np.zeros(len(env), np.float32), "vx": np.zeros(len(env), np.float32),
+               "vy": np.zeros(len(env), np.float32), "option_id": np.zeros(len(env), np.int32), "opt_steps": np.zeros(len(env), np.int32),
+               "ep_steps": (row - 1).astype(np.int32), "env": env, "row": row}
+        for e in np.unique(env):
+            at = np.nonzero(env == e)[0]
+            rec, r = self.per_env(e), row[at]
+            n = len(rec["vf"])
+            if np.any(r < 1) or np.any(r >= n):
+                raise ValueError(f"env {int(e)}: row outside 1 .. {n - 1} (the record holds {n} rows of it)")
+            ended = (rec["done"][r - 1] != 0) & (rec["action"][r - 1] != BEGIN_ACTION)
+            if np.any(ended):
+                raise ValueError(f"env {int(e)}: row {int(r[ended][0]) - 1} ended the episode: there is no state to resume behind it")
+            goes_on = (rec["vf"] >= 1) & (rec["term"] == 0)       # (the begin row: vf = 0)
+            j = np.arange(n)
+            last_reset = np.maximum.accumulate(np.where(goes_on, -1, j))      # the last row <= j that left opt_steps at 0
+            for f in ("x", "y", "vx", "vy"):
+                out[f][at] = rec[f][r - 1]
+            out["option_id"][at] = rec["option_id"][r - 1]
+            out["opt_steps"][at] = (j - last_reset)[r - 1]
+        oid = out["option_id"].astype(np.int64)
+        out["vf_next"] = np.where((oid >= 1) & (oid < self.n_vf), oid, 0)
+        return out
+
     def to_numpy(self) -> dict:
         """Every env's rows flattened for saving: `offsets` [n + 1] into the concatenated fields, plus `first`."""
         per = [self.per_env(i) for i in range(self.n)]
