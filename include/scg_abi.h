@@ -378,6 +378,19 @@ int scg_fourier_features(scg_ctx *ctx, int32_t n, const float *x, const float *y
 int scg_feature_gram(scg_ctx *ctx, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
                      const float *yv /* may be NULL */, int32_t n_seg, const int64_t *offsets /* HOST */,
                      float *A, float *b /* NULL iff yv is NULL */, void *stream);
+/* Feature Gram with several right-hand sides (SPEC §20.1): scg_feature_gram's A[g][1296][1296] and, for the n_tgt targets per sample
+ * Y[n_tgt][n] (target c of sample n at Y[c * n + n]),   B[g][c][1296] = sum_n phi(s_n) Y[c][n],   1 <= n_tgt <= SCG_GRAM_MAX_TARGETS:
+ * the targets are the columns of the one MFMA operand that carries scg_feature_gram's yv, so up to 16 right-hand sides cost what one
+ * does. A is by bits scg_feature_gram's A and B[g][c] by bits the b[g] it gives for yv = Y[c], for every n_tgt, whether c is
+ * computed alone or among 16, and from every block build. A target that holds NaN or +-inf leaves its own B[.][c] unspecified and
+ * every other target and A untouched. A and the n_seg * n_tgt * 1296 floats of B are fully overwritten (an empty segment: +0) and
+ * nothing else is written; needs no map; raises no asynchronous status. SCG_ERR_INVALID, nothing launched, in this sequence: a null
+ * x / y / vx / vy / Y / A / B / offsets, n < 0, n_seg outside [1, SCG_GRAM_MAX_SEGMENTS], offsets that decrease or leave [0, n],
+ * n_tgt outside [1, SCG_GRAM_MAX_TARGETS]. */
+#define SCG_GRAM_MAX_TARGETS 16
+int scg_feature_gram_targets(scg_ctx *ctx, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                             const float *Y /* [n_tgt][n] */, int32_t n_tgt, int32_t n_seg, const int64_t *offsets /* HOST */,
+                             float *A /* [n_seg][1296][1296] */, float *B /* [n_seg][n_tgt][1296] */, void *stream);
 /* Cross-feature Gram (SPEC §17.1): for each of n_seg segments (offsets as in scg_feature_gram) of n recorded samples with two states
  * each, s_n = (x, y, vx, vy)[n] and s2_n = (x2, y2, vx2, vy2)[n],
  *   C[g][1296][1296] = sum_n phi(s_n) phi(s2_n)^T   (rows: features of s, columns: features of s2; not symmetric)

@@ -42,6 +42,7 @@ PEER_MAX_RANKS = 8
 GRAM_SLAB = 1024            # include/scg_abi.h SCG_GRAM_*: SPEC §16.1's slab, the segment cap, one workgroup's block of A (features a side)
 GRAM_MAX_SEGMENTS = 64
 GRAM_MACRO_TILE = 96
+GRAM_MAX_TARGETS = 16       # include/scg_abi.h SCG_GRAM_MAX_TARGETS: SPEC §20.1's right-hand sides per call (the columns of one MFMA operand)
 CROSS_GRAM_MACRO_TILE = 96  # include/scg_abi.h SCG_CROSS_GRAM_MACRO_TILE: one workgroup's block of SPEC §17.1's C (rows and columns alike)
 BASIS_ORDERS = (3, 5, 7)    # SPEC §18: the orders of the basis-order probe (F = (order + 1)^4 = 256, 1296, 4096 features)
 BASIS_VALUES_MAX_ROWS = 8   # include/scg_abi.h SCG_BASIS_VALUES_MAX_ROWS
@@ -174,6 +175,7 @@ _SIGS = {
     "scg_pinball_step": (C.c_int, [_P, C.c_int32] + [_P] * 7 + [_P]),
     "scg_fourier_features": (C.c_int, [_P, C.c_int32] + [_P] * 5 + [_P]),
     "scg_feature_gram": (C.c_int, [_P, C.c_int64] + [_P] * 5 + [C.c_int32, _P, _P, _P, _P]),
+    "scg_feature_gram_targets": (C.c_int, [_P, C.c_int64] + [_P] * 5 + [C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "scg_feature_cross_gram": (C.c_int, [_P, C.c_int64] + [_P] * 8 + [C.c_int32, _P, _P, _P]),
     "scg_basis_features": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 5 + [_P]),
     "scg_basis_gram": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 5 + [C.c_int32, _P, _P, _P, _P]),

@@ -940,6 +940,107 @@ class SkillChainingAgent:
             report["vf"][k] = rep
         return report
 
+    def fit_values_to_branches(self, trajectory=None, n_states: int = 8192, n_held: int = 2048, replicates: int = 8, vfs=None,
+                               ridge: float = 1e-3, epsilon: float = 0.1, seed: Optional[int] = None, n_episodes: int = 4096,
+                               apply: bool = False, keep: bool = False, interrupt: bool = False, choose: Optional[str] = None,
+                               steps_per_launch: int = 64):
+        """Fit every action's Q_k to fresh Monte-Carlo branch returns of ALL five actions from the same states (SPEC §20): one Gram,
+        a right-hand side per action. Records episodes as branch_audit does (or takes its `trajectory`), then per value function k
+        of `vfs` (default: all), with a generator seeded by `seed`, draws `n_states` rows of the EVEN envs' step rows with vf = k
+        (the fit half) and then `n_held` of the ODD envs' (the held-out half), fewer where there are fewer, each in (env, row)
+        order; rebuilds the rows' env states (Trajectory.resume_state) and runs branch_returns from them with all five first
+        actions, `replicates` each. With gbar the replicate means and Q^old the result's qcache (valuefit.branch_targets): on the
+        fit half (A, B) = ScgContext.feature_gram_targets(states, [0, n_fit], D), D[a] = float32(gbar[:, a] - Q^old[:, a]); Delta =
+        valuefit.ridge_solve_shared; W_new[k][a] = float32(W_k^old[a] + Delta[a]). A value function without fit states keeps its
+        rows bit for bit. This fits Q of the epsilon-greedy policy that ran the branches; acting greedily on W_new is a step of
+        policy improvement.
+        Returns (report, W_new): W_new a copy of W with the fitted rows; report["vf"][k] holds n_fit, n_held, delta_norm and, for
+        "fit" and "held_out": old / new (valuefit.error_stats of Q(s_i, a) against gbar[i][a] over all (i, a)), per_action (the
+        same per action), target_se = sqrt(mean se2) (the RMSE a perfect Q^pi would still show against these means) and greedy
+        (valuefit.greedy_table: agreement_old / _new, changed, one_step_gain and its standard error; unbiased on the held-out
+        half, whose replicates W_new never saw). `keep` adds report["vf"][k]["operands"] (states, D, A, B, delta, rows, n_fit,
+        gbar, se2, q_old, q_new, result) and report["trajectory"].
+        Refused: r_option_success != 0 with any k >= 1 (as branch_audit), apply=True with shared weights (as
+        fit_values_to_returns), replicates < 1, n_states < 1, n_held < 0. apply=False leaves the agent as evaluate() does;
+        apply=True copies the fitted rows of `vfs` into W."""
+        from .valuefit import branch_targets, error_stats, greedy_table, returns_to_go, ridge_solve_shared
+        if int(replicates) < 1:
+            raise ValueError("replicates must be >= 1")
+        if int(n_states) < 1:
+            raise ValueError("n_states must be >= 1")
+        if int(n_held) < 0:
+            raise ValueError("n_held must be >= 0")
+        if apply and self.group is not None:
+            raise ScgError("fit_values_to_branches(apply=True) with shared weights: each rank would fit its own copy of W and the "
+                           "ranks would part; fit with apply=False and load one rank's result on all of them")
+        vfs = list(range(self.n_vf)) if vfs is None else [int(k) for k in vfs]
+        if any(not (0 <= k < self.n_vf) for k in vfs):
+            raise ValueError(f"vfs must name value functions 0..{self.n_vf - 1}")
+        c = self.ctx.cfg
+        if float(c.r_option_success) != 0.0 and any(k >= 1 for k in vfs):
+            raise ScgError("fit_values_to_branches: r_option_success != 0: a branch's return carries no completion bonus, so it is "
+                           "not SPEC §16.2's target of an option's value function; fit vfs=[0] only")
+        if trajectory is None:
+            traj, _ = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose)
+        else:
+            traj = trajectory
+        flat = traj.to_numpy()
+        tg = returns_to_go(flat, float(c.gamma), float(c.r_option_success))
+        off = flat["offsets"]
+        env = np.repeat(np.arange(traj.n), np.diff(off))
+        row = np.arange(int(off[-1])) - off[:-1][env]
+        rng = np.random.default_rng(int(c.seed) if seed is None else int(seed))
+        dev = self.W.device
+        W_new = self.W.clone()
+        report = {"replicates": int(replicates), "ridge": float(ridge), "vf": {}}
+        if keep:
+            report["trajectory"] = traj
+        for k in vfs:
+            halves = []
+            for parity, want in ((0, int(n_states)), (1, int(n_held))):
+                rows = np.nonzero(tg["sample"] & (flat["vf"] == k) & (env % 2 == parity))[0]
+                if len(rows) > want:
+                    rows = np.sort(rng.choice(rows, want, replace=False)) if want else rows[:0]
+                halves.append(rows)
+            n_fit, n_hld = len(halves[0]), len(halves[1])
+            rows = np.concatenate(halves)
+            rep = {"n_fit": int(n_fit), "n_held": int(n_hld), "delta_norm": 0.0}
+            report["vf"][k] = rep
+            if n_fit == 0:                                     # nothing to fit: the rows of W_k stay, and there is no Q^new to judge
+                continue
+            # the fit half's states first: its branch envs, and so its returns, do not depend on n_held
+            res = self.branch_returns(traj.resume_state(env[rows], row[rows]), np.tile(np.arange(NUM_ACTIONS, dtype=np.uint8), (len(rows), 1)),
+                                      int(replicates), epsilon, seed, interrupt, choose, steps_per_launch)
+            gbar, se2, D = branch_targets(res.g, res.qcache)
+            ectx = self._branch_ctx[res.g.size][0]               # the side context the branches ran on: 5 R envs per state
+            states = [torch.from_numpy(np.ascontiguousarray(flat[f][rows - 1])).to(dev) for f in ("x", "y", "vx", "vy")]
+            fit_states = [t[:n_fit].contiguous() for t in states]
+            D_fit = torch.from_numpy(np.ascontiguousarray(D[:, :n_fit])).to(dev)
+            A, B = ectx.feature_gram_targets(fit_states, [0, n_fit], D_fit)
+            delta = ridge_solve_shared(A[0].cpu().numpy(), B[0].cpu().numpy(), n_fit, ridge, self.ctx.scale)
+            w_old = self.W[k].cpu().numpy()
+            W_new[k] = torch.from_numpy((w_old.astype(np.float64) + delta).astype(np.float32)).to(dev)
+            q_old = res.qcache
+            q_new = np.zeros_like(q_old)
+            for i in range(0, len(rows), ectx.n_envs):         # (a branch context holds 5 R envs per state: one pass)
+                sl = slice(i, i + ectx.n_envs)
+                q_new[sl] = ectx.q_values([t[sl].contiguous() for t in states], W_new[k].contiguous().view(-1)).cpu().numpy().T
+            rep["delta_norm"] = float(np.sqrt(np.sum(delta * delta)))
+            for name, sl in (("fit", slice(0, n_fit)), ("held_out", slice(n_fit, None))):
+                rep[name] = {"old": error_stats(q_old[sl].reshape(-1), gbar[sl].reshape(-1)),
+                             "new": error_stats(q_new[sl].reshape(-1), gbar[sl].reshape(-1)),
+                             "per_action": [{"old": error_stats(q_old[sl, a], gbar[sl, a]), "new": error_stats(q_new[sl, a], gbar[sl, a])}
+                                            for a in range(NUM_ACTIONS)],
+                             "target_se": float(np.sqrt(np.mean(se2[sl]))) if se2[sl].size else float("nan"),
+                             "greedy": greedy_table(gbar[sl], q_old[sl], q_new[sl])}
+            if keep:
+                rep["operands"] = {"states": states, "D": D, "A": A, "B": B, "delta": delta, "rows": (env[rows], row[rows]), "n_fit": n_fit,
+                                   "gbar": gbar, "se2": se2, "q_old": q_old, "q_new": q_new, "result": res}
+        if apply:
+            for k in vfs:
+                self.W[k].copy_(W_new[k])
+        return report, W_new
+
     def _mirror_training(self, side: ScgContext, epsilon: float) -> None:
         """Copy the training run's settings into a side context (evaluation, trials): its hyper-parameters (epsilon aside),
         parents and gestation mask — classifiers in use, no success counts kept; its own state, t and counters untouched."""

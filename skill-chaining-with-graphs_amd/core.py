@@ -536,6 +536,21 @@ class ScgContext:
                    off.ctypes.data_as(C.c_void_p), _ptr(A), _ptr(b), self._stream())
         return A if b is None else (A, b)
 
+    def feature_gram_targets(self, s, offsets, Y: torch.Tensor):
+        """SPEC §20.1: feature_gram's A and, for the targets `Y` (a contiguous float32 [n_tgt][n], 1 <= n_tgt <= 16), B[g][c] = sum
+        phi(s_n) Y[c][n] over segment g: one Gram, a right-hand side per target, for the MFMAs one right-hand side costs. Returns
+        (A [n_seg][1296][1296], B [n_seg][n_tgt][1296]); A and every B[g][c] have the bits feature_gram gives for yv = Y[c]."""
+        (a,), n, off, n_seg, A = self._gram_setup("feature_gram_targets", offsets, s)
+        if not isinstance(Y, torch.Tensor) or Y.dim() != 2 or not (1 <= Y.shape[0] <= _lib.GRAM_MAX_TARGETS) or Y.shape[1] != n:
+            raise ScgError(f"feature_gram_targets: Y must be [n_tgt][{n}] with 1 <= n_tgt <= {_lib.GRAM_MAX_TARGETS}")
+        n_tgt = int(Y.shape[0])
+        self._chk(Y, torch.float32, n_tgt * n, "Y")
+        Y = Y if n else a[0]
+        B = torch.empty((n_seg, n_tgt, NUM_FEATURES), dtype=torch.float32, device=self.device)
+        self._call("scg_feature_gram_targets", C.c_int64(n), *[_ptr(t) for t in a], _ptr(Y), n_tgt, n_seg,
+                   off.ctypes.data_as(C.c_void_p), _ptr(A), _ptr(B), self._stream())
+        return A, B
+
     def feature_cross_gram(self, s, s2, offsets):
         """SPEC §17.1: C[g] = sum phi(s_n) phi(s2_n)^T over segment g = samples offsets[g] .. offsets[g+1]-1 of the state pairs
         (`s`, `s2`: four [n] tensors each, which may be the same tensors; `offsets` as for feature_gram). Returns C

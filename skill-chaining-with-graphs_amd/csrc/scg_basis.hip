@@ -15,8 +15,8 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 
 template <class S>
 static hipError_t launch_gram_order(const GramArgs &G, int n_active, hipStream_t s) {
-    if (G.yv) hipLaunchKernelGGL((gram_kernel<S, true>), dim3(S::MACROS, n_active), dim3(S::THREADS), 0, s, G);
-    else hipLaunchKernelGGL((gram_kernel<S, false>), dim3(S::MACROS, n_active), dim3(S::THREADS), 0, s, G);
+    if (G.yv) hipLaunchKernelGGL((gram_kernel<S, GRAM_RHS_ONE>), dim3(S::MACROS, n_active), dim3(S::THREADS), 0, s, G);
+    else hipLaunchKernelGGL((gram_kernel<S, GRAM_RHS_NONE>), dim3(S::MACROS, n_active), dim3(S::THREADS), 0, s, G);
     return hipGetLastError();
 }
 hipError_t launch_basis_gram_3(const GramArgs &G, int n_active, hipStream_t s) { return launch_gram_order<GramBasis<3>>(G, n_active, s); }

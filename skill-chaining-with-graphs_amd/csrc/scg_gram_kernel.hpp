@@ -1,7 +1,8 @@
 // scg_gram_kernel.hpp — SPEC §16.1, §17.1 and §18: gram_kernel, the feature Gram of segments of recorded states as an f32 rank-k update on
 // v_mfma_f32_16x16x4_f32 whose operands are built on the fly from the 16-byte state: phi is never materialised. One template, two shapes:
 //   symmetric (GramSym)   A_g = sum_n phi(s_n) phi(s_n)^T, and with RHS b_g = sum_n phi(s_n) yv[n]: the macro-tiles on or above the
-//                         diagonal are computed and every block is stored with its mirror image; one table set of 64 samples in LDS
+//                         diagonal are computed and every block is stored with its mirror image; one table set of 64 samples in LDS;
+//                         or, SPEC §20.1, B_g[c] = sum_n phi(s_n) Y[c][n] for up to 16 targets c: the columns of the MFMA that forms b
 //   cross (GramCross)     C_g = sum_n phi(s_n) phi(s2_n)^T between a state and its successor: every macro-tile of the square, no mirror
 //                         store, no diagonal case; TWO table sets of 32 samples, s's for the row operands and s2's for the column operands
 // and, for the symmetric shape, the basis order p of SPEC §18 (GramBasis<p>: 3 or 7 next to GramSym's 5; GramOrder<p> holds what follows
@@ -98,15 +99,25 @@ using GramBasis = GramShape<false, SCG_GRAM_R, SCG_GRAM_WG, SCG_GRAM_WPE, SCG_BA
 static_assert(GramSym::MT * 16 == SCG_GRAM_MACRO_TILE, "gram geometry");
 static_assert(GramCross::MT * 16 == SCG_CROSS_GRAM_MACRO_TILE, "cross gram geometry");
 
+// what the kernel forms next to A (its second template argument): nothing; b from one yv per sample, as column 0 of one more B operand;
+// or SPEC §20.1's B from n_tgt <= GRAM_MAX_TGT targets per sample, which fill the 16 columns of that same operand
+constexpr int GRAM_RHS_NONE = 0, GRAM_RHS_ONE = 1, GRAM_RHS_TARGETS = 2;
+constexpr int GRAM_MAX_TGT = SCG_GRAM_MAX_TARGETS;
+static_assert(GRAM_MAX_TGT == 16, "the targets are the columns of one 16-wide MFMA operand");
+
 struct GramArgs {
     const float *s[2][4];                            // x, y, vx, vy of the row operands' states and of the column operands' (the same, or s2)
-    const float *yv;                                 // yv and b: both or neither
+    const float *yv;                                 // yv and b: both or neither (GRAM_RHS_TARGETS: Y[n_tgt][y_stride] and B[seg][n_tgt][F])
     float *out, *b;                                  // A or C
     int32_t seg[GRAM_MAX_SEG];                       // the non-empty segments: index (A_g = out + seg * F^2), first sample, samples
     int64_t start[GRAM_MAX_SEG], count[GRAM_MAX_SEG];
+    // GRAM_RHS_TARGETS only, and behind everything the other instantiations read: their code keeps its argument offsets
+    int64_t y_stride;                                // floats between two targets' rows of Y (the entry point's n)
+    int32_t n_tgt;
 };
-// grid = MACROS x n_active workgroups of THREADS on stream s (defined in scg_gram.hip); the first reads s[0] only
+// grid = MACROS x n_active workgroups of THREADS on stream s (defined in scg_gram.hip); the first two read s[0] only
 hipError_t launch_feature_gram(const GramArgs &G, int n_active, hipStream_t s);
+hipError_t launch_feature_gram_targets(const GramArgs &G, int n_active, hipStream_t s);
 hipError_t launch_feature_cross_gram(const GramArgs &G, int n_active, hipStream_t s);
 
 // the table places of feature f (clamped: the tiles of a short macro-tile read a valid place and are never stored): AB at f / P2, CD
@@ -122,15 +133,20 @@ __device__ __forceinline__ float gram_phi(const float2 *row, int ab_at, int cd_a
     return fmaf(-ab.y, cd.y, ab.x * cd.x);
 }
 
-template <class S, bool RHS>
+template <class S, int RHS>
 __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs G) {
     constexpr bool CROSS = S::CROSS;
     constexpr int R = S::R, WG = S::WG, MT = S::MT, ME = S::ME, CHUNK = S::CHUNK, SETS = S::SETS, THREADS = S::THREADS;
     constexpr int P1 = S::P1, P2 = S::P2, F = S::F, TILES = S::TILES, TS = S::TS;
+    constexpr bool TARGETS = RHS == GRAM_RHS_TARGETS;
+    static_assert(RHS == GRAM_RHS_NONE || RHS == GRAM_RHS_ONE || TARGETS, "the three modes");
     static_assert(!(CROSS && RHS), "b belongs to the symmetric shape");
+    static_assert(!TARGETS || (CHUNK % 16 == 0 && THREADS % 64 == 0), "the deal of the targets' fill");
     __shared__ __attribute__((aligned(16))) float2 s_z1[SETS][CHUNK][4];
     __shared__ float2 s_tab[SETS][CHUNK * TS];
-    __shared__ float s_yv[CHUNK];
+    // yv of the chunk; with TARGETS the chunk's targets sample-major, [CHUNK][16]: the B operand of four samples is 64 consecutive floats,
+    // lane (n16, kk) reads its own bank (target-major rows of 64 floats would put the 16 lanes of a sample on one bank)
+    __shared__ float s_yv[TARGETS ? CHUNK * GRAM_MAX_TGT : CHUNK];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n16 = lane & 15, kk = lane >> 4;                 // MFMA operand lane: row / column n16 of the tile, k index (A, B) or row group (C, D)
     int I, J;                                                  // macro-tile (I, J)
@@ -175,7 +191,14 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
                     s_z1[set][smp][d] = sincospi_cs(d < 2 ? v : fmaf(v, 0.25f, 0.5f));     // state_powers' Z_d^1
                 }
             }
-            if (RHS) {
+            if (TARGETS) {
+                // 16 consecutive samples of 4 targets per wave and pass: 64-byte runs of Y's rows from global memory, and the writes of a
+                // wave meet 4 deep on 16 banks (one target per wave and pass: 16 deep on 4). +0 for a target >= n_tgt and a sample >= m
+                for (int t = tid; t < CHUNK * GRAM_MAX_TGT; t += THREADS) {
+                    const int smp = (t & 15) + 16 * (t >> 8), c = (t >> 4) & 15;
+                    s_yv[smp * GRAM_MAX_TGT + c] = c < G.n_tgt && smp < m ? G.yv[(int64_t)c * G.y_stride + base + smp] : 0.0f;
+                }
+            } else if (RHS) {
                 for (int t = tid; t < CHUNK; t += THREADS) s_yv[t] = t < m ? G.yv[base + t] : 0.0f;
             }
             __syncthreads();
@@ -215,7 +238,8 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
                         for (int c = 0; c < R; ++c) acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], bo[c], acc[r][c], 0, 0, 0);
                     }
                     if (rhs) {                                 // yv as column 0 of a B operand: column 0 of the product is b's chain
-                        const float yb = n16 == 0 ? s_yv[4 * ks + kk] : 0.0f;
+                        // (TARGETS: target c as column c; a column of the product depends on that column of the operand only)
+                        const float yb = TARGETS ? s_yv[(4 * ks + kk) * GRAM_MAX_TGT + n16] : (n16 == 0 ? s_yv[4 * ks + kk] : 0.0f);
 #pragma unroll
                         for (int r = 0; r < R; ++r) bacc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], yb, bacc[r], 0, 0, 0);
                     }
@@ -257,7 +281,12 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
                 for (int v = 0; v < 4; ++v) Og[(size_t)col * F + row + v] = tot[r][c][v];
             }
         }
-        if (rhs && n16 == 0) {
+        if (TARGETS) {
+            if (rhs && n16 < G.n_tgt) {                        // column n16 is target n16's; the lanes of the zero columns store nothing
+#pragma unroll
+                for (int v = 0; v < 4; ++v) G.b[((size_t)G.seg[blockIdx.y] * G.n_tgt + n16) * F + row + v] = btot[r][v];
+            }
+        } else if (rhs && n16 == 0) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) G.b[(size_t)G.seg[blockIdx.y] * F + row + v] = btot[r][v];
         }

@@ -1,7 +1,8 @@
 """Least-squares value fits on recorded episodes. SPEC §16: the Monte-Carlo targets and the ridge solve of the normal equations
 whose matrix scg_feature_gram forms. SPEC §17: the items of the least-squares TD fixed point (LSTD-Q) and the solve of its
-block system, whose off-diagonal part scg_feature_cross_gram forms. Host code, float64; the hot parts are
-ScgContext.feature_gram and ScgContext.feature_cross_gram."""
+block system, whose off-diagonal part scg_feature_cross_gram forms. SPEC §20: the targets of a fit to all-action branch returns, the
+solve of one matrix against a right-hand side per action (scg_feature_gram_targets forms both) and the greedy-action table of its
+report. Host code, float64; the hot parts are ScgContext.feature_gram, feature_gram_targets and feature_cross_gram."""
 from __future__ import annotations
 
 import numpy as np
@@ -85,6 +86,67 @@ def ridge_solve(A, b, n, ridge: float, scale, device=None) -> np.ndarray:
         Lc = np.linalg.cholesky(M)
         out[a] = np.linalg.solve(Lc.T, np.linalg.solve(Lc, b[a]))
     return out
+
+
+def ridge_solve_shared(A, B, n, ridge: float, scale) -> np.ndarray:
+    """SPEC §20.2: Delta[c] = (A + Lambda)^-1 B[c] for C right-hand sides B [C][F] of ONE matrix A [F][F] over n samples, Lambda =
+    diag(ridge max(n, 1) / scale_f^2): one float64 Cholesky, then a solve per right-hand side with the calls ridge_solve makes, so
+    that the result is by bits ridge_solve(repeat(A, C), B, [n] * C, ridge, scale). n = 0 gives zeros exactly. Returns float64 [C][F]."""
+    B = np.asarray(B, np.float64)
+    out = np.zeros_like(B)
+    if int(n) == 0:
+        return out
+    lam = 1.0 / np.asarray(scale, np.float64) ** 2
+    M = np.tril(np.asarray(A, np.float64))
+    M = M + np.tril(M, -1).T
+    M[np.diag_indices_from(M)] += float(ridge) * max(int(n), 1) * lam
+    Lc = np.linalg.cholesky(M)
+    for c in range(B.shape[0]):
+        out[c] = np.linalg.solve(Lc.T, np.linalg.solve(Lc, B[c]))
+    return out
+
+
+def branch_targets(g, q_old):
+    """SPEC §20.2: what a fit of Q to all-action branch returns regresses. g [M][A][R] (BranchResult.g: binary32), q_old [M][A]
+    float32 (Q^old(s_i, a): the result's qcache). Returns
+      gbar [M][A] float64   the mean of g over the replicates, summed in replicate order (BranchResult._moments)
+      se2  [M][A] float64   s^2 / R with s^2 the unbiased variance: the squared standard error of gbar; 0 at R = 1
+      D    [A][M] float32   float32(gbar - float64(q_old)) transposed: the residual, rounded once, a target per action as
+                            ScgContext.feature_gram_targets takes them."""
+    g = np.asarray(g, np.float32)
+    q_old = np.asarray(q_old, np.float32)
+    if g.ndim != 3 or g.shape[2] < 1 or q_old.shape != g.shape[:2]:
+        raise ValueError("branch_targets: g must be [M][A][R] with R >= 1 and q_old [M][A]")
+    R = g.shape[2]
+    if R == 1:
+        gbar, se2 = g[:, :, 0].astype(np.float64), np.zeros(g.shape[:2], np.float64)
+    else:
+        from .evaluation import BranchResult
+        z = np.zeros(g.shape)
+        gbar, var = BranchResult(np.zeros(g.shape[:2], np.uint8), g, z, z, z)._moments()
+        se2 = var / R
+    D = np.ascontiguousarray((gbar - q_old.astype(np.float64)).astype(np.float32).T)
+    return gbar, se2, D
+
+
+def greedy_table(gbar, q_old, q_new) -> dict:
+    """SPEC §20.4: does acting greedily on Q^new pick better actions than on Q^old, judged by the branch means gbar [M][A]? With
+    a_old, a_new, a* the FIRST maxima of q_old, q_new, gbar (each [M][A]):
+      agreement_old, agreement_new   the share of states with a_old = a*, a_new = a*
+      changed                        the share with a_new != a_old
+      one_step_gain, one_step_gain_se   the mean over the states of gbar_i[a_new] - gbar_i[a_old] (exactly 0 where nothing changed)
+                                     and its standard error (the unbiased standard deviation / sqrt(M); 0 with fewer than 2 states)
+    Unbiased where gbar's replicates are not the ones q_new was fitted to (the held-out half). NaN without a state."""
+    gbar = np.asarray(gbar, np.float64)
+    M = gbar.shape[0]
+    if M == 0:
+        return {"n": 0, **{f: float("nan") for f in ("agreement_old", "agreement_new", "changed", "one_step_gain", "one_step_gain_se")}}
+    idx = np.arange(M)
+    a_old, a_new, a_star = (np.argmax(np.asarray(v), axis=1) for v in (q_old, q_new, gbar))
+    gain = gbar[idx, a_new] - gbar[idx, a_old]
+    se = float(np.sqrt(np.sum((gain - gain.mean()) ** 2) / (M - 1) / M)) if M >= 2 else 0.0
+    return {"n": int(M), "agreement_old": float(np.mean(a_old == a_star)), "agreement_new": float(np.mean(a_new == a_star)),
+            "changed": float(np.mean(a_new != a_old)), "one_step_gain": float(np.mean(gain)), "one_step_gain_se": se}
 
 
 def error_stats(q, y) -> dict:

@@ -6,8 +6,14 @@ The states are snapshots of the headline workload's env states, one per step-bat
 --lib NAME=PATH times further builds of the library (another tiling: make's DEFS) in the same rounds.
 --order P (3, 5 or 7; SPEC §18) times scg_basis_gram at that order against ScgContext.basis_features + phi.T @ phi,
 flops counted on the triangle of F = (P + 1)^4 features; without it the tool is scg_feature_gram's, as it was.
+--targets C (1 .. 16; SPEC §20.1) times, at each of --sizes samples, three ways to the C right-hand sides of one set of
+states, interleaved round by round: "targets" = scg_feature_gram_targets, one segment, C targets; "one_rhs" = scg_feature_gram, one
+segment with yv (it issues the same number of MFMAs: the floor); "repeated" = scg_feature_gram on C segments of the same states
+repeated, target c as segment c's yv (what a fit of C actions would otherwise call). One JSON line per size: per arm the median,
+the fastest and the slowest round in ms (the tool's own round-to-round spread), and the ratios of the medians. --segs is not used.
 
     python tools/gram_bench.py [--sizes 65536 1048576] [--segs 1 5] [--rounds 5] [--lib r3=path/to/libscg_hip_r3.so] [--order 7] [--out file.jsonl]
+    python tools/gram_bench.py --targets 5 [--sizes 8192 65536 1048576] [--rounds 9] [--out file.jsonl]
 """
 import argparse
 import json
@@ -44,13 +50,51 @@ def materialised(ctx, s, offsets, chunk, order=None):
     return out
 
 
+def targets_bench(a):
+    """--targets C: the three arms at each size; returns the JSON lines."""
+    import torch
+    C = a.targets
+    ag, s = recorded_states(max(a.sizes), a.envs)
+    ctx, lines = ag.ctx, []
+    for n in a.sizes:
+        sub = [t[:n].contiguous() for t in s]
+        Y = torch.randn((C, n), dtype=torch.float32, device=sub[0].device, generator=torch.Generator(sub[0].device).manual_seed(n))
+        tiled, yv = [t.repeat(C) for t in sub], Y.reshape(-1)
+        runs = {"targets": lambda: ctx.feature_gram_targets(sub, [0, n], Y),
+                "one_rhs": lambda: ctx.feature_gram(sub, [0, n], Y[0]),
+                "repeated": lambda: ctx.feature_gram(tiled, [i * n for i in range(C + 1)], yv)}
+        (A, B), (A1, _), (_, bC) = runs["targets"](), runs["one_rhs"](), runs["repeated"]()
+        same = bool(torch.equal(A, A1) and torch.equal(B[0], bC))      # (the bits the three ways must share)
+        times = {name: [] for name in runs}
+        for _ in range(a.rounds):
+            for name, fn in runs.items():
+                times[name].append(rig.timed(fn, 1) * 1e3)
+        med = {name: statistics.median(t) for name, t in times.items()}
+        row = {"samples": n, "n_targets": C, "rounds": a.rounds, "same_bits": same}
+        for name, t in times.items():
+            row[name] = {"ms": round(med[name], 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3)}
+        row["targets_over_one_rhs"] = round(med["targets"] / med["one_rhs"], 4)
+        row["repeated_over_one_rhs"] = round(med["repeated"] / med["one_rhs"], 4)
+        row["repeated_over_targets"] = round(med["repeated"] / med["targets"], 4)
+        lines.append(json.dumps(row))
+        print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[65536, 1048576]); ap.add_argument("--segs", type=int, nargs="+", default=[1, 5])
     ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--chunk", type=int, default=65536)
     ap.add_argument("--envs", type=int, default=65536); ap.add_argument("--lib", nargs="*", default=[])
     ap.add_argument("--order", type=int, default=None, choices=(3, 5, 7)); ap.add_argument("--out", default=None)
+    ap.add_argument("--targets", type=int, default=None, choices=range(1, 17), metavar="C")
     a = ap.parse_args()
+    if a.targets is not None:
+        lines = targets_bench(a)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     F = NF if a.order is None else (a.order + 1) ** 4
     import torch
     from skill_chaining_with_graphs_amd.core import ScgContext
