@@ -304,6 +304,34 @@ int scg_rollout_branch(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, i
                        const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action,
                        void *stream);
 
+/* ---- population rollouts (SPEC §21): several policies in one launch, on common random numbers ----
+ * scg_rollout_population is scg_rollout_branch plus `pop`. pop = NULL is scg_rollout_branch: the same kernels, the same results.
+ * With pop the context's N envs are C = n_policies ranges of n_per consecutive envs; the envs c * n_per .. (c + 1) * n_per - 1 act
+ * under policy c: the weights W[c] (W is then a DEVICE array [C][n_vf][5][1296]), the exploration rate epsilon[c] and the enabled
+ * mask enabled[c]. Classifiers, gestation, parents, map and hyper-parameters are the context's for every policy. The draws of env
+ * c * n_per + i are those of global env id env_id_base + i for every c (§4.2's re-offer schedule likewise): the policies see the
+ * same start states and the same draws. Every array is indexed by the env's position among the N as ever.
+ * The contract: for every c the outputs of range c equal BY BITS what scg_rollout_branch writes on a context of n_per envs with the
+ * same seed, env_id_base, map, hyper-parameters, classifiers, t0, n_steps, flags and rules, with W[c], epsilon[c], enabled[c], and
+ * that range of every input (a record window clipped to the range).
+ * Errors: scg_rollout_branch's, in its sequence; after them SCG_ERR_INVALID (nothing launched, nothing written), in this order:
+ * n_policies outside [1, SCG_POP_MAX]; n_per < 1; n_policies * n_per != the context's n_envs. The write set is
+ * scg_rollout_branch's; W, epsilon and enabled are never written. Results do not depend on the launch geometry or the block
+ * build; no asynchronous failure bit is raised. */
+#define SCG_POP_MAX 64
+typedef struct {            /* HOST struct of DEVICE pointers */
+    int32_t n_policies;     /* C in [1, SCG_POP_MAX] */
+    int32_t n_per;          /* envs per policy, >= 1; C * n_per == cfg.n_envs */
+    const float *epsilon;   /* [C], or NULL: cfg's epsilon for every policy */
+    const uint32_t *enabled;/* [C], or NULL: the enabled_mask argument for every policy */
+} scg_population;
+int scg_rollout_population(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                           int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                           const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                           uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                           const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action,
+                           void *stream, const scg_population *pop);
+
 /* Device pointers of the ctx-owned reduced gradient G[n_vf][5][1296] and counts n_k[n_vf] (int32)
  * left by the last scg_step(LEARN) — the buffers a multi-rank caller all-reduces (SPEC §5). */
 int scg_grad_buffers(scg_ctx *ctx, float **G, int32_t **n_k);

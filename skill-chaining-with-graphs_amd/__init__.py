@@ -23,7 +23,7 @@ def __getattr__(name):
     if name == "TrialResult":
         from .trials import TrialResult
         return TrialResult
-    if name in ("EpisodeStats", "GateAudit", "BranchResult"):
+    if name in ("EpisodeStats", "GateAudit", "BranchResult", "paired_differences"):
         from . import evaluation
         return getattr(evaluation, name)
     if name == "FourierBasis":
@@ -35,7 +35,7 @@ def __getattr__(name):
     if name in ("Option", "InitiationClassifier"):
         from . import option
         return getattr(option, name)
-    if name in ("returns_to_go", "ridge_solve", "td_samples", "lstdq_solve"):
+    if name in ("returns_to_go", "ridge_solve", "td_samples", "lstdq_solve", "damped_tables", "choose_candidate"):
         from . import valuefit
         return getattr(valuefit, name)
     if name == "SkillChainingAgent":

@@ -31,6 +31,7 @@ TRIAL_MAX_STEPS = ROLLOUT_MAX_STEPS
 ROLLOUT_TERM_INTERRUPTED = 5   # include/scg_abi.h SCG_ROLLOUT_TERM_INTERRUPTED: a recorded row's term where an option was interrupted
 SELECT_INTERRUPT = 1       # include/scg_abi.h SCG_SELECT_*: the rules of scg_rollout_select (SPEC §11, §14)
 SELECT_BEST = 2
+POP_MAX = 64               # SCG_POP_MAX: the policies of one population rollout (SPEC §21)
 NO_FIRST_ACTION = 255      # SPEC §19: scg_rollout_branch's first_action entry of an env that is not forced (any value >= NUM_ACTIONS)
 BRANCH_ID_BASE = 2 ** 40   # the global env ids of branch rollouts start here: no stream of a record (env_id_base = 0) is reused
 ABI_VERSION = 5            # include/scg_abi.h SCG_ABI_VERSION
@@ -144,6 +145,17 @@ class Audit(C.Structure):
     ]
 
 
+class Population(C.Structure):
+    """scg_population: SPEC §21's C policies over n_per envs each; device pointers of the [C] epsilon (float32) and enabled mask
+    (uint32) arrays (NULL = the context's epsilon / the call's enabled_mask for every policy)."""
+    _fields_ = [
+        ("n_policies", C.c_int32),
+        ("n_per", C.c_int32),
+        ("epsilon", C.c_void_p),
+        ("enabled", C.c_void_p),
+    ]
+
+
 _P = C.c_void_p
 # the arguments the rollout and the trial entry points start with; each appends its own tail (record, interrupt counts, stream)
 _ROLLOUT = [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(RolloutStats)]
@@ -166,6 +178,8 @@ _SIGS = {
     "scg_rollout_select": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, _P]),
     "scg_rollout_audit": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, C.POINTER(Audit), _P]),
     "scg_rollout_branch": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, C.POINTER(Audit), _P, _P]),
+    "scg_rollout_population": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, C.POINTER(Audit), _P, _P,
+                                            C.POINTER(Population)]),
     "scg_grad_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "scg_set_grad_buffers": (C.c_int, [_P, _P, _P]),
     "scg_apply_update": (C.c_int, [_P, _P, _P, _P, _P]),

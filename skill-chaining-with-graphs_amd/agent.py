@@ -17,7 +17,7 @@ from . import _lib
 from . import dist as _dist
 from ._lib import CLF_STRIDE, NUM_ACTIONS, NUM_FEATURES, ScgError, auto_block_envs
 from .core import EnvState, ScgContext
-from .evaluation import BranchResult, EpisodeStats, GateAudit
+from .evaluation import BranchResult, EpisodeStats, GateAudit, paired_differences
 from .maps import PinballMap, load_map
 from .option import Option
 from .pinball import PinballDomain
@@ -491,12 +491,15 @@ class SkillChainingAgent:
         return traj, stats.summary()
 
     def _eval_launches(self, n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record: bool = False, choose=None,
-                       audit=None):
+                       audit=None, population=None):
         """The launches of evaluate() / record_episodes() on the evaluation context for this episode count and seed, its settings
         copied from training (epsilon aside), stats zeroed and, with `states`, the start states written into its env state: the
         first begins every episode at t0 = 0, launch i > 0 goes on at t0 = 1 + i * steps_per_launch. Returns (EpisodeStats, Trajectory or None).
         `audit` (True: a new GateAudit without a force; or a force vector, one int8 per episode) makes every launch an audited one
-        (SPEC §15); the force acts in the first launch, and the GateAudit is left in stats.audit."""
+        (SPEC §15); the force acts in the first launch, and the GateAudit is left in stats.audit.
+        `population` = (W [C, n_vf, 5, 1296], epsilon [C] or None, enabled [C] or None) on the device makes every launch a
+        population rollout (SPEC §21) of C policies over n_episodes envs each: the context has C * n_episodes envs, the `states`
+        are repeated for every policy, and `epsilon` is the context's own (no policy's, where the population gives one)."""
         if choose not in (None, "value"):
             raise ValueError(f"choose must be None or 'value', not {choose!r}")
         if states is not None:
@@ -508,14 +511,22 @@ class SkillChainingAgent:
         if not (1 <= spl <= _lib.ROLLOUT_MAX_STEPS):
             raise ValueError(f"steps_per_launch must be in [1, {_lib.ROLLOUT_MAX_STEPS}]")
         c = self.ctx.cfg
+        W, kw = self.W, {}
+        if population is not None:
+            W, pol_eps, pol_enabled = population
+            n_pol = int(W.shape[0])
+            if n * n_pol > 2 ** 31 - 1:
+                raise ValueError(f"{n_pol} policies x {n} episodes are more envs than a context holds")
+            if states is not None:
+                states = [s.repeat(n_pol) for s in states]
+            n, kw["population"] = n * n_pol, (pol_eps, pol_enabled)
         ectx, st, stats = self._eval_context(n, epsilon, seed, states)
         traj = Trajectory(n, spl + 1, 0, ectx.device, n_vf=self.n_vf) if record else None
-        kw = {}
         if audit is not None:
             stats.audit = GateAudit(n, ectx.device, force=None if audit is True else audit)
             kw["audit"] = stats.audit
         for i in range(-(-int(c.max_episode_steps) // spl)):
-            ectx.rollout(st, self.W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
+            ectx.rollout(st, W, self.clf, self.enabled_mask, 0 if i == 0 else 1 + i * spl, spl, stats,
                          begin=(i == 0 and states is None), one_episode=True, begin_at=(i == 0 and states is not None),
                          record=traj, interrupt=interrupt, choose=choose, **kw)
             if audit is not None:
@@ -523,6 +534,94 @@ class SkillChainingAgent:
             if record:
                 traj.append()
         return stats, traj
+
+    def evaluate_policies(self, W, epsilons=None, enabled=None, n_episodes: int = 4096, seed: Optional[int] = None,
+                          steps_per_launch: int = 64, states=None, interrupt: bool = False, choose: Optional[str] = None,
+                          per_env: bool = False, baseline: int = 0):
+        """Several policies in one set of launches, on common random numbers (SPEC §21): `W` is [C, n_vf, 5, 1296] or a list of C
+        [n_vf, 5, 1296] tables, `epsilons` and `enabled` scalars or one per policy (defaults: 0.0 and the agent's enabled mask).
+        evaluate(discounted=True)'s launches run ONCE, on an evaluation context of C * n_episodes envs of which the envs c *
+        n_episodes .. (c + 1) * n_episodes - 1 act under policy c; env i of every policy sees the same start state (`states`, as for
+        evaluate(), are repeated for every policy) and the same draws. Returns (summaries, paired): summaries[c] is what
+        evaluate(n_episodes, epsilon=epsilons[c], discounted=True, ...) returns with W[c] and enabled[c] in place, field for field;
+        paired[c] is evaluation.paired_differences of policy c against policy `baseline` (exact zeros for the baseline itself and
+        for any policy equal to it). With per_env=True also the list of the policies' per-env dicts, as (summaries, paired,
+        per_envs). The training run is left alone exactly as by evaluate(). ValueError for C outside 1 .. 64, for more than 2^31 - 1
+        envs in all, and for `epsilons` / `enabled` of another length."""
+        dev = self.W.device
+        table = (self.n_vf, NUM_ACTIONS, NUM_FEATURES)
+        if isinstance(W, (list, tuple)):
+            W = [torch.as_tensor(w, dtype=torch.float32).to(dev) for w in W]
+            if not W or any(w.numel() != self.W.numel() for w in W):
+                raise ValueError(f"every table of W must be {list(table)}")
+            W = torch.stack([w.reshape(table) for w in W])
+        W = torch.as_tensor(W, dtype=torch.float32).to(dev)
+        if W.dim() != 4 or tuple(W.shape[1:]) != table:
+            raise ValueError(f"W must be [C, {self.n_vf}, {NUM_ACTIONS}, {NUM_FEATURES}], not {tuple(W.shape)}")
+        n_pol = int(W.shape[0])
+        if not (1 <= n_pol <= _lib.POP_MAX):
+            raise ValueError(f"evaluate_policies takes 1 .. {_lib.POP_MAX} policies, not {n_pol}")
+        if not (0 <= int(baseline) < n_pol):
+            raise ValueError(f"baseline must name a policy 0 .. {n_pol - 1}")
+
+        def per_policy(v, default, dtype, what):
+            v = np.asarray(default if v is None else v)
+            if v.ndim == 0:
+                v = np.full(n_pol, v)
+            if v.shape != (n_pol,):
+                raise ValueError(f"{what} must be a scalar or hold one entry per policy ({n_pol}), not {v.shape}")
+            return torch.from_numpy(np.ascontiguousarray(v.astype(dtype))).to(dev)
+
+        pol_eps = per_policy(epsilons, 0.0, np.float32, "epsilons")
+        pol_enabled = per_policy(enabled, self.enabled_mask, np.int32, "enabled")
+        # (the context's own epsilon is read by no policy: every one has its entry)
+        stats, _ = self._eval_launches(n_episodes, 0.0, seed, steps_per_launch, states, interrupt, choose=choose, audit=True,
+                                       population=(W.contiguous(), pol_eps, pol_enabled))
+        n = stats.n // n_pol
+        summaries = [stats.summary(c * n, (c + 1) * n) for c in range(n_pol)]
+        envs = [{f: v.detach().cpu() for f, v in stats.per_env(c * n, (c + 1) * n).items()} for c in range(n_pol)]
+        paired = [paired_differences(envs[c], envs[int(baseline)]) for c in range(n_pol)]
+        return (summaries, paired, envs) if per_env else (summaries, paired)
+
+    def improve_policy(self, lambdas=(0.25, 0.5, 1.0), eval_epsilons=(0.0,), criterion: str = "discounted", z: float = 2.0,
+                       n_eval: int = 4096, apply: bool = False, **fit):
+        """A safeguarded policy-improvement step (SPEC §21.4): fit_values_to_branches(apply=False, **fit) gives W_new; the
+        candidates W and valuefit.damped_tables(W, W_new, lambdas) at each of `eval_epsilons` are evaluated in ONE
+        evaluate_policies run of n_eval episodes each (common random numbers; the baseline of a candidate is W at the same
+        epsilon); the decision is taken at eval_epsilons[0] by valuefit.choose_candidate: the candidate with the highest mean of `criterion`,
+        ties to the smallest lambda, accepted only where its paired mean difference against W exceeds z standard errors (z = 2:
+        §19.4's "beyond two standard errors" convention, a parameter). Returns (report, W_chosen): report["fit"] the fit's
+        report, report["candidates"] rows of {"lambda", "epsilon", "summary", "paired"} (lambda = 0: W itself), "chosen_lambda" (0.0
+        when W is kept), "accepted", "criterion", "z"; W_chosen a copy of the chosen table (of W when kept). apply=True copies
+        W_chosen into W when accepted. Refusals: fit_values_to_branches's; ValueError for no lambda, a lambda of 0, no epsilon or
+        an unknown criterion. With apply=False the agent is left as evaluate() leaves it."""
+        from .valuefit import choose_candidate, damped_tables
+        lam = [float(v) for v in lambdas]
+        eps = [float(v) for v in eval_epsilons]
+        if not lam or not eps or any(v == 0.0 for v in lam):
+            raise ValueError("improve_policy needs at least one lambda, none of them 0, and at least one epsilon")
+        if criterion not in ("discounted", "return", "success"):
+            raise ValueError(f"criterion must be 'discounted', 'return' or 'success', not {criterion!r}")
+        if apply and self.group is not None:
+            raise ScgError("improve_policy(apply=True) with shared weights: each rank would choose its own table and the ranks would part")
+        fit_report, W_new = self.fit_values_to_branches(apply=False, **fit)
+        shape = (self.n_vf, NUM_ACTIONS, -1)
+        tables = torch.cat([self.W.reshape(1, *shape), damped_tables(self.W.reshape(shape), W_new.reshape(shape), lam)])
+        lam0, n_tab = [0.0] + lam, 1 + len(lam)
+        per_eps = len(eps)
+        # policy e * n_tab + i: table i at epsilon e; its baseline W at that epsilon is policy e * n_tab. One run per baseline would
+        # pair against one policy only, so the paired rows are taken here from the per-env dicts of the single run.
+        summaries, _, envs = self.evaluate_policies(tables.repeat(per_eps, 1, 1, 1), np.repeat(np.asarray(eps, np.float32), n_tab),
+                                                    None, n_episodes=int(n_eval), seed=fit.get("seed"),
+                                                    interrupt=bool(fit.get("interrupt", False)), choose=fit.get("choose"), per_env=True)
+        rows = [{"lambda": lam0[i], "epsilon": eps[e], "summary": summaries[e * n_tab + i],
+                 "paired": paired_differences(envs[e * n_tab + i], envs[e * n_tab])} for e in range(per_eps) for i in range(n_tab)]
+        pick = choose_candidate(rows[:n_tab], criterion, z)
+        W_chosen = (tables[pick["index"]] if pick["accepted"] else tables[0]).reshape(self.W.shape).clone()
+        if apply and pick["accepted"]:
+            self.W.copy_(W_chosen)
+        return {"fit": fit_report, "candidates": rows, "chosen_lambda": pick["chosen_lambda"], "accepted": pick["accepted"],
+                "criterion": criterion, "z": float(z)}, W_chosen
 
     def _eval_context(self, n: int, epsilon: float, seed: Optional[int], states):
         """The evaluation context for `n` episodes and `seed` (None: training's), its settings copied from training (epsilon

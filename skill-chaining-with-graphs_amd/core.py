@@ -143,8 +143,9 @@ class ScgContext:
         # (interrupt is passed on as given: without learn the library refuses it, SPEC §12)
         return (STEP_LEARN if learn else 0) | (STEP_APPLY if (learn and apply) else 0) | (STEP_INTERRUPT if interrupt else 0)
 
-    def _chk_operands(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor) -> None:
-        """The env state, weight and classifier tensors step() and rollout() hand to the library."""
+    def _chk_operands(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, n_tables: int = 1) -> None:
+        """The env state, weight and classifier tensors step() and rollout() hand to the library (n_tables: SPEC §21's weight
+        tables, one per policy)."""
         N = self.n_envs
         f32, i32, u8 = torch.float32, torch.int32, torch.uint8
         self._chk(st.x, f32, N, "x"); self._chk(st.y, f32, N, "y")
@@ -153,7 +154,7 @@ class ScgContext:
         self._chk(st.ep_steps, i32, N, "ep_steps"); self._chk(st.qcache, f32, NUM_ACTIONS * N, "qcache")
         self._chk(st.action, u8, N, "action"); self._chk(st.reward, f32, N, "reward")
         self._chk(st.done, u8, N, "done")
-        _chk_W(self, W); _chk_clf(self, clf)
+        self._chk(W, f32, n_tables * self.n_vf * W_ROW, "W"); _chk_clf(self, clf)
 
     def step(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t: int,
              learn: bool = True, apply: bool = True, interrupt: bool = False) -> None:
@@ -201,10 +202,32 @@ class ScgContext:
             self._chk(getattr(record, f), record.DTYPES[f], record.rows * record.n, "record." + f)
         return record.c_struct()
 
+    def _chk_population(self, W: torch.Tensor, population) -> "_lib.Population":
+        """The scg_population of rollout(population=(epsilon, enabled)) (SPEC §21): C from W's leading dimension, n_per = n_envs // C."""
+        try:
+            eps, enabled = population
+        except (TypeError, ValueError):
+            raise ScgError("rollout: population must be a pair (epsilon, enabled) of [C] tensors, either may be None") from None
+        if not isinstance(W, torch.Tensor) or W.dim() != 4 or tuple(W.shape[1:]) != (self.n_vf, NUM_ACTIONS, NUM_FEATURES):
+            raise ScgError(f"rollout: with a population W must be [C, {self.n_vf}, {NUM_ACTIONS}, {NUM_FEATURES}], "
+                           f"got {tuple(getattr(W, 'shape', ()))}")
+        n_pol = int(W.shape[0])
+        if not (1 <= n_pol <= _lib.POP_MAX):
+            raise ScgError(f"rollout: a population holds 1 .. {_lib.POP_MAX} policies, W has {n_pol}")
+        if self.n_envs % n_pol:
+            raise ScgError(f"rollout: {self.n_envs} envs do not divide into {n_pol} policies")
+        if eps is not None:
+            self._chk(eps, torch.float32, n_pol, "population epsilon")
+        if enabled is not None:
+            # (the masks fit in a few bits: int32 holds the same words and is what most torch builds can fill and index)
+            self._chk(enabled, torch.uint32 if getattr(enabled, "dtype", None) == getattr(torch, "uint32", None) else torch.int32,
+                      n_pol, "population enabled")
+        return _lib.Population(n_pol, self.n_envs // n_pol, _ptr(eps), _ptr(enabled))
+
     def rollout(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, n_steps: int,
                 stats=None, begin: bool = False, one_episode: bool = False, record=None, begin_at: bool = False,
                 interrupt: bool = False, interrupts=None, choose: Optional[str] = None, overrides=None, audit=None,
-                first_action: Optional[torch.Tensor] = None) -> None:
+                first_action: Optional[torch.Tensor] = None, population=None) -> None:
         """SPEC §8: n_steps acting steps in ONE launch, bit for bit n_steps calls of step(learn=False) at t0 .. t0+n_steps-1
         (with `begin`: a new episode for every env at t0 first, the steps at t0+1 .. t0+n_steps). W is read, never written.
         `stats` (EpisodeStats of this context's n_vf and n_envs, on its device) receives the episode counters; `one_episode`
@@ -222,11 +245,19 @@ class ScgContext:
         only), and its arrays receive the begin choice, the values it compared and the discounted task return.
         SPEC §19: `first_action` (uint8 [n_envs] on this device, read only) makes the launch a branch rollout (scg_rollout_branch, with
         whatever else was asked for): on the launch's first real step an env whose entry is below 5 takes that action instead of
-        §4.3's choice, the step's draw made as ever; 255 (_lib.NO_FIRST_ACTION) leaves an env alone. It needs n_steps >= 1."""
+        §4.3's choice, the step's draw made as ever; 255 (_lib.NO_FIRST_ACTION) leaves an env alone. It needs n_steps >= 1.
+        SPEC §21: `population` = (epsilon, enabled), float32 / int32 (or uint32) [C] tensors on this device, either None (the context's epsilon /
+        `enabled_mask` for every policy), makes the launch a population rollout (scg_rollout_population, with whatever else was
+        asked for): W is [C, n_vf, 5, 1296], and the envs c * n_per .. (c + 1) * n_per - 1, n_per = n_envs // C, act under W[c],
+        epsilon[c] and enabled[c], their draws keyed by the env's index within its range: every policy sees the same start
+        states and the same draws, and its range equals by bits a rollout of n_per envs under that policy alone."""
         if choose not in (None, "value"):
             raise ValueError(f"rollout: choose must be None or 'value', not {choose!r}")
-        self._chk_operands(st, W, clf)
         N = self.n_envs
+        pop = None
+        if population is not None:
+            pop = self._chk_population(W, population)
+        self._chk_operands(st, W, clf, 1 if pop is None else pop.n_policies)
         n_steps, t0 = int(n_steps), int(t0)
         if begin and begin_at:
             raise ScgError("rollout: begin and begin_at together")
@@ -282,7 +313,10 @@ class ScgContext:
         rules = (_lib.SELECT_BEST if choose is not None else 0) | (_lib.SELECT_INTERRUPT if interrupt else 0)
         ints, ovr = (None if a is None else _ptr(a) for a in (interrupts, overrides))
         rc_ref = None if rc is None else C.byref(rc)
-        if first_action is not None:
+        if pop is not None:
+            name, tail = "scg_rollout_population", (ints, ovr, rc_ref, C.c_uint32(rules), None if au is None else C.byref(au),
+                                                    _ptr(first_action))
+        elif first_action is not None:
             name, tail = "scg_rollout_branch", (ints, ovr, rc_ref, C.c_uint32(rules), None if au is None else C.byref(au),
                                                 _ptr(first_action))
         elif au is not None:
@@ -297,7 +331,8 @@ class ScgContext:
             name, tail = "scg_rollout", ()
         self._call(name, _ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id), _ptr(st.opt_steps), _ptr(st.ep_steps),
                    _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done), _ptr(W), _ptr(clf), C.c_uint32(enabled_mask),
-                   C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags), None if cs is None else C.byref(cs), *tail, self._stream())
+                   C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags), None if cs is None else C.byref(cs), *tail, self._stream(),
+                   *(() if pop is None else (C.byref(pop),)))
         if stats is not None and interrupt and interrupts is stats.interrupts:
             stats.interrupting = True
 

@@ -23,6 +23,8 @@
 // scg_rollout_variants.hip is the second translation unit: every other instantiation of rollout_kernel (SPEC §10's record, §11's
 // interruption, §14's value-ranked choice, §15's audit: the table in scg_rollout_kernel.hpp) and trial_kernel<true>, reached through
 // launch_rollout<REC, Args> / launch_trial_record, which the two kernel headers declare.
+// scg_rollout_population.hip is a unit of the same kind: SPEC §21's four population instantiations of rollout_kernel,
+// reached through the same launch_rollout<REC, Args>.
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -680,14 +682,18 @@ struct RolloutCall {
     uint32_t rules;                // SCG_SELECT_*; scg_rollout_interrupt: SCG_SELECT_INTERRUPT
     const scg_audit *audit;
     const uint8_t *first_action;   // scg_rollout_branch (SPEC §19)
+    const scg_population *pop;     // scg_rollout_population (SPEC §21)
 };
 
-// the six rollout entry points (`fn` names the caller in error texts). The kernel follows from what the call asks for:
+// the seven rollout entry points (`fn` names the caller in error texts). The kernel follows from what the call asks for:
 //   audit      a member of `audit` given (SPEC §15; every member NULL counts as no audit), or a first_action (SPEC §19: the AUDIT
 //              kernels are the ones that read it; with no audit member they write nothing of the audit's)
 //   best, intr SCG_SELECT_BEST / SCG_SELECT_INTERRUPT in `rules` (SPEC §14 / §11), counting into `overrides` / `interrupts`
 //   rec, at    a record (SPEC §10) / SCG_ROLLOUT_BEGIN_AT, from here on BEGIN in `flags` plus `at`
-// Neither audit, best, rec nor at: the plain kernel, or with intr the non-recording interrupting one; otherwise a RolloutVar by (intr, best, audit)
+//   pop        a population (SPEC §21): a RolloutPop by (intr, best), whatever else the call asks for (they are AUDIT kernels, and with
+//              no audit member and no first_action they write nothing of either), on a grid of whole workgroups per policy
+// Neither audit, best, rec, at nor pop: the plain kernel, or with intr the non-recording interrupting one; otherwise a RolloutVar by
+// (intr, best, audit)
 static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
     if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
     if (a.rules & ~(SCG_SELECT_INTERRUPT | SCG_SELECT_BEST)) return fail_in(c, SCG_ERR_INVALID, fn, "unknown rule");
@@ -720,6 +726,13 @@ static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
     if (audit && !audit->disc_ret != !audit->disc_g)
         return fail_in(c, SCG_ERR_INVALID, fn, "audit->disc_ret and audit->disc_g go together");
     if (a.first_action && a.n_steps == 0) return fail_in(c, SCG_ERR_INVALID, fn, "first_action with n_steps == 0: no real step to force");
+    if (a.pop) {
+        if (a.pop->n_policies < 1 || a.pop->n_policies > SCG_POP_MAX)
+            return fail_in(c, SCG_ERR_INVALID, fn, "pop->n_policies out of range [1, SCG_POP_MAX]");
+        if (a.pop->n_per < 1) return fail_in(c, SCG_ERR_INVALID, fn, "pop->n_per must be >= 1");
+        if ((long long)a.pop->n_policies * (long long)a.pop->n_per != (long long)c->cfg.n_envs)
+            return fail_in(c, SCG_ERR_INVALID, fn, "pop->n_policies * pop->n_per is not the context's n_envs");
+    }
     SCG_CHECK_ASYNC(c);
     DeviceGuard dev_guard_(c->cfg.device);
     if (!dev_guard_.ok) return fail_in(c, SCG_ERR_HIP, fn, "cannot make the context's device current");
@@ -734,7 +747,8 @@ static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
     int epw;
     if (!rollout_epw(c, c->cfg.n_envs, epw)) return fail_in(c, SCG_ERR_INVALID, fn, "SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
     R.epw = epw;
-    const int grid = (c->cfg.n_envs + RO_WAVES * epw - 1) / (RO_WAVES * epw);
+    const int wgs_per_pol = a.pop ? (a.pop->n_per + RO_WAVES * epw - 1) / (RO_WAVES * epw) : 0;
+    const int grid = a.pop ? a.pop->n_policies * wgs_per_pol : (c->cfg.n_envs + RO_WAVES * epw - 1) / (RO_WAVES * epw);
     const hipStream_t s = reinterpret_cast<hipStream_t>(a.stream);
     c->order_valid = false;                               // the ids change under the step's prepared env order
     auto I = derived_args<RolloutIntArgs>(R);
@@ -749,6 +763,17 @@ static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
     const bool aud = audit || a.first_action;             // the AUDIT kernels: they alone read first_action
     const bool var = aud || best || a.rec || at;          // what only the RolloutVar kernels take
     hipError_t rollout_kernel_launch = hipSuccess;
+    if (a.pop) {
+        auto P = derived_args<RolloutPopArgs>(V);
+        P.n_pol = a.pop->n_policies; P.n_per = a.pop->n_per; P.wgs_per_pol = wgs_per_pol;
+        P.pol_eps = a.pop->epsilon; P.pol_enabled = a.pop->enabled;
+        switch ((best ? 2 : 0) | (intr ? 1 : 0)) {
+        case 0: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutPop<false, false>>(P), grid, s); break;
+        case 1: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutPop<true, false>>(P), grid, s); break;
+        case 2: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutPop<false, true>>(P), grid, s); break;
+        case 3: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutPop<true, true>>(P), grid, s); break;
+        }
+    } else
     switch ((var ? 8 : 0) | (aud ? 4 : 0) | (best ? 2 : 0) | (intr ? 1 : 0)) {                      // INT    BEST   AUDIT
     case 0:
         hipLaunchKernelGGL((rollout_kernel<false, RolloutArgs>), dim3(grid), dim3(RO_THREADS), 0, s, R);
@@ -825,6 +850,18 @@ int scg_rollout_branch(scg_ctx *c, float *x, float *y, float *vx, float *vy, int
     return rollout_launch("scg_rollout_branch", c, {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
                                                     enabled_mask, t0, n_steps, flags, stats, stream, true, rec, interrupts, overrides,
                                                     rules, audit, first_action});
+}
+
+// pop = NULL: scg_rollout_branch's launch, under this entry point's name in error texts
+int scg_rollout_population(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                           int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                           const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                           uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                           const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action, void *stream,
+                           const scg_population *pop) {
+    return rollout_launch("scg_rollout_population", c, {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
+                                                        enabled_mask, t0, n_steps, flags, stats, stream, true, rec, interrupts, overrides,
+                                                        rules, audit, first_action, pop});
 }
 
 static int trials_launch(const char *fn, scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,

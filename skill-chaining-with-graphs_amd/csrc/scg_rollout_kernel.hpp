@@ -40,9 +40,10 @@ struct RolloutArgs {
     static constexpr bool INT = false;   // SPEC §11's interruption: a compile-time flag of the argument type (kernel symbols unchanged)
     static constexpr bool BEST = false;  // SPEC §14's value-ranked choice: likewise
     static constexpr bool AUDIT = false; // SPEC §15's forced first choice and discounted return: likewise
+    static constexpr bool POP = false;   // SPEC §21's population: a weight table, an epsilon and an enabled mask per env range: likewise
 };
-// The ten instantiations, the narrowest entry point that launches each (rollout_launch in scg_kernels.hip has the whole mapping), and
-// what each adds to <false, RolloutArgs>. INT, BEST and AUDIT are compile-time flags of the argument type. Every argument type has
+// The fourteen instantiations, the narrowest entry point that launches each (rollout_launch in scg_kernels.hip has the whole mapping), and
+// what each adds to <false, RolloutArgs>. INT, BEST, AUDIT and POP are compile-time flags of the argument type. Every argument type has
 // RolloutArgs at offset 0, so the exit's re-read holds for all.
 //   REC    Args                               launched by                    adds
 //   false  RolloutArgs                        scg_rollout                    -
@@ -56,8 +57,11 @@ struct RolloutArgs {
 //          (all four I, B)                                                   discounted task return is kept in two more registers across the steps
 //                                             scg_rollout_branch             SPEC §19: the same four kernels; the first real step's action may be
 //                                                                            given per env (first_action, read on that step only)
-// Every REC instantiation shares ONE argument layout, RolloutVarArgs; the non-recording interrupting kernel keeps
-// its own, because `interrupts` at another offset changes its code.
+//   true   RolloutPop<I, B>                   scg_rollout_population         SPEC §21: the AUDIT kernels over C env ranges of n_per envs, each with
+//          (all four I, B; AUDIT)             (pop given)                    its own W, epsilon and enabled mask; a workgroup serves one range, and
+//                                                                            the draws are keyed by the env's index within its range
+// Every REC instantiation shares ONE argument layout, RolloutVarArgs (the population's members lie behind it); the
+// non-recording interrupting kernel keeps its own, because `interrupts` at another offset changes its code.
 struct RolloutIntArgs : RolloutArgs {
     static constexpr bool INT = true;
     int32_t *interrupts;           // [n_vf][N] in/out, may be null
@@ -74,6 +78,18 @@ struct RolloutVarArgs : RolloutArgs {
 template <bool I, bool B, bool AU>
 struct RolloutVar : RolloutVarArgs {
     static constexpr bool INT = I, BEST = B, AUDIT = AU;
+};
+
+// SPEC §21: policy c = workgroup / wgs_per_pol acts in the envs c * n_per .. (c + 1) * n_per - 1
+struct RolloutPopArgs : RolloutVarArgs {
+    int32_t n_pol, n_per;          // n_pol * n_per = n
+    int32_t wgs_per_pol;           // ceil(n_per / (RO_WAVES * epw)): a workgroup never straddles two policies
+    const float *pol_eps;          // [n_pol], null: epsilon for every policy
+    const uint32_t *pol_enabled;   // [n_pol], null: enabled for every policy
+};                                 // (W: [n_pol][n_vf][5][1296])
+template <bool I, bool B>
+struct RolloutPop : RolloutPopArgs {
+    static constexpr bool INT = I, BEST = B, AUDIT = true, POP = true;
 };
 
 // per-VF counters of one launch, six 16-bit fields in three words (a launch takes at most 1 + SCG_ROLLOUT_MAX_STEPS steps)
@@ -96,7 +112,7 @@ static_assert(SCG_ROLLOUT_MAX_STEPS + 1 < 65536, "16-bit launch counters");
 // (the instantiations: the table at the argument types)
 template <bool REC, typename Args>
 __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
-    constexpr bool INT = Args::INT, BEST = Args::BEST, AUDIT = Args::AUDIT;
+    constexpr bool INT = Args::INT, BEST = Args::BEST, AUDIT = Args::AUDIT, POP = Args::POP;
     constexpr int QV_SLOTS = BEST ? MAX_VF : 2;               // BEST: one slot per value function
     constexpr int QV_ROOT = BEST ? 0 : 1;                     // the slot of the root's Q beside the running VF's
     __shared__ __attribute__((aligned(16))) float s_w0[W_FLOATS];                 // W_0 in A-operand order (stage_w_cold's layout)
@@ -111,8 +127,23 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int epw = A.epw, N = A.n;
     const int il = wave * epw + lane;                          // this lane's env within the workgroup (lanes < epw)
-    const int e = blockIdx.x * RO_WAVES * epw + il;
-    const bool mine = lane < epw && e < N;
+    // POP (SPEC §21): the workgroup's policy, its weights, epsilon and mask (workgroup-uniform); el: the env's index within the
+    // policy's range, which keys its draws; e stays the index of everything in memory
+    int pol = 0, el = 0;
+    const float *Wp = A.W;
+    float epsilon = A.epsilon;
+    unsigned enabled = A.enabled;
+    if constexpr (POP) {
+        pol = (int)(blockIdx.x / (unsigned)A.wgs_per_pol);
+        el = ((int)blockIdx.x - pol * A.wgs_per_pol) * RO_WAVES * epw + il;
+        Wp = A.W + (size_t)pol * A.n_vf * NACT * NF;
+        if (A.pol_eps) epsilon = A.pol_eps[pol];
+        if (A.pol_enabled) enabled = A.pol_enabled[pol];
+    }
+    int n_own = N;                                             // the envs of this workgroup's range
+    if constexpr (POP) n_own = A.n_per;
+    const int e = POP ? pol * n_own + el : blockIdx.x * RO_WAVES * epw + il;
+    const bool mine = lane < epw && (POP ? el : e) < n_own;
 
     // ---- entry: the env's state into registers
     float sx = 0.5f, sy = 0.5f, svx = 0.0f, svy = 0.0f, qc[NACT] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -159,14 +190,14 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         const int z = i - W_TAIL;
         int src;
         const bool in = i < W_TAIL ? w_a_src(i >> 9, 4 * ((i >> 8) & 1) + (i & 3), (i >> 2) & 63, src) : w_a_src(z >> 6, 8, z & 63, src);
-        s_w0[i] = in ? A.W[src] : 0.0f;
+        s_w0[i] = in ? Wp[src] : 0.0f;
     }
     for (int i = tid; i < A.ms.n_edges * 8; i += RO_THREADS) s_edges[i] = A.edges[i];
     if (tid < A.n_vf * CLF_STRIDE) s_clf[tid] = A.clf[tid];
     if (tid < 2 * MAX_VF) (&s_cnt[0][0])[tid] = 0;
     __syncthreads();
 
-    const unsigned known = A.enabled | A.gest;
+    const unsigned known = enabled | A.gest;
     const int total = A.n_steps + (A.begin ? 1 : 0);
     float *sw = s_wave[wave];
     for (int j = 0; j < total; ++j) {
@@ -175,11 +206,11 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         const int par = j & 1;
         // ------------------------------------------------------------ P
         bool valid = alive;
-        const uint64_t gid = (uint64_t)(A.env_base + e);
+        const uint64_t gid = (uint64_t)(A.env_base + (POP ? el : e));
         uint32_t u[4] = {0u, 0u, 0u, 0u};
         if (valid) env_draw(gid, t, A.seed, u);
         int a = NACT - 1;
-        if (valid && !is_begin) a = act_spec(u, qc, A.epsilon);
+        if (valid && !is_begin) a = act_spec(u, qc, epsilon);
         if constexpr (AUDIT) {                                 // SPEC §19: the launch's first real step takes the caller's action
             if (valid && j == (A.begin ? 1 : 0)) {             // (the draw above is made as ever; fetched here, once: see the exit)
                 const uint8_t *const fa = kernel_args<Args>()->first_action;
@@ -210,10 +241,10 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
             if (REC && !is_begin && o >= 1 && !keep)          // SPEC §9's outcome code, first match wins
                 term = succ ? (int)SCG_TRIAL_SUCCESS : dn ? (int)SCG_TRIAL_EPISODE_END
                      : !((inA >> o) & 1u) ? (int)SCG_TRIAL_LEFT_INITIATION : (int)SCG_TRIAL_TIMEOUT;
-            cand = keep ? o : select_option(A.parents, inB, A.enabled);
-            if constexpr (INT) ic = keep ? select_option(A.parents, inB, A.enabled) : 0;
+            cand = keep ? o : select_option(A.parents, inB, enabled);
+            if constexpr (INT) ic = keep ? select_option(A.parents, inB, enabled) : 0;
             if constexpr (BEST) {                              // SPEC §14: stay out of ANY member of C; cand = that member
-                cset = keep ? 0u : candidate_mask(A.parents, inB, A.enabled);
+                cset = keep ? 0u : candidate_mask(A.parents, inB, enabled);
                 const int o_in = is_begin ? 0 : oid;
                 const bool out_of = o_in < 0 && o_in > -MAX_VF && ((cset >> (unsigned)(-o_in & 7)) & 1u);
                 stay = (!keep && out_of && dn == 0 && (((uint32_t)t + (uint32_t)gid) & A.reoffer_mask) != 0u) ? -o_in : 0;
@@ -224,7 +255,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
             if constexpr (AUDIT) {                             // SPEC §15: the begin choice forced to a member of C (begin: stay = 0)
                 if (is_begin && A.au.force) {
                     const int f = A.au.force[e], k = f < 0 ? -f : f;
-                    const unsigned C = BEST ? cset : candidate_mask(A.parents, inB, A.enabled);
+                    const unsigned C = BEST ? cset : candidate_mask(A.parents, inB, enabled);
                     if (k >= 1 && k < A.n_vf && ((C >> k) & 1u)) {
                         fk = f; amin = cand; cand = k;
                         if constexpr (BEST) cset = 1u << k;    // phase E's lists: Q_k and Q_0 of this env, no other
@@ -287,7 +318,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
                 float B[9], q[NACT];
                 load_b(cdk, n16, g, B);
                 if (k == 0) contract_lds<E_TG>(0, B, q, g, w4, w8, ab_lane);      // W_0 from LDS
-                else contract_mem<EO_TG>(A.W + (size_t)k * NACT * NF, B, q, n16, g, ab_lane);      // W_k straight from memory (L2-resident: 26 KB per VF)
+                else contract_mem<EO_TG>(Wp + (size_t)k * NACT * NF, B, q, n16, g, ab_lane);      // W_k straight from memory (L2-resident: 26 KB per VF)
                 if (out_lane && ocol_item < nk) {
                     const int ent = lst[ocol_item];
 #pragma unroll

@@ -1,6 +1,7 @@
 """EpisodeStats — the per-env counters of an acting rollout (SPEC §8, scg_rollout; §11, scg_rollout_interrupt) and their
 host-side summary; GateAudit — the per-env arrays of an audited rollout (SPEC §15, scg_rollout_audit) and the summary of an
-enter / decline pair of them; BranchResult — the returns of branch rollouts (SPEC §19, scg_rollout_branch) and their statistics."""
+enter / decline pair of them; BranchResult — the returns of branch rollouts (SPEC §19, scg_rollout_branch) and their statistics;
+paired_differences — the per-env differences of two policies evaluated on common random numbers (SPEC §21)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -60,7 +61,15 @@ class EpisodeStats:
         """The scg_rollout_stats of these tensors (device pointers; the tensors must stay alive while it is in use)."""
         return RolloutStats(**{f: C.c_void_p(getattr(self, f).data_ptr()) for f in self.FIELDS})
 
-    def per_env(self) -> dict:
+    def _range(self, lo, hi):
+        """The env range lo .. hi - 1 as a slice of the last axis (None, None: every env)."""
+        lo, hi = 0 if lo is None else int(lo), self.n if hi is None else int(hi)
+        if not (0 <= lo <= hi <= self.n):
+            raise ValueError(f"env range {lo}..{hi} outside the {self.n} envs")
+        return slice(lo, hi)
+
+    def per_env(self, lo=None, hi=None) -> dict:
+        """The per-env counter tensors; with `lo`, `hi` those of the envs lo .. hi - 1 (SPEC §21: one policy's range)."""
         out = {f: getattr(self, f) for f in self.FIELDS}
         if self.interrupting:
             out["interrupts"] = self.interrupts
@@ -68,14 +77,19 @@ class EpisodeStats:
             out["overrides"] = self.overrides
         if self.audit is not None:
             out["disc_final"] = self.audit.disc_final
-        return out
+        if lo is None and hi is None:
+            return out
+        r = self._range(lo, hi)
+        return {f: v[..., r] for f, v in out.items()}
 
-    def summary(self) -> dict:
+    def summary(self, lo=None, hi=None) -> dict:
         """Aggregate over the envs on the host in float64, in env order: episodes, success_rate, mean_return, mean_length
         (NaN with no episode recorded) and per value function k (index 0 = the root): steps_share (fraction of all steps
         run under k), entries, declines, successes; after an interrupting rollout also interrupts (SPEC §11), after a
-        value-ranking one also overrides (SPEC §14: entries of an option that was not the lowest-numbered candidate)."""
-        host = {f: getattr(self, f).detach().cpu().numpy() for f in self.FIELDS}
+        value-ranking one also overrides (SPEC §14: entries of an option that was not the lowest-numbered candidate).
+        With `lo`, `hi`: over the envs lo .. hi - 1 only (SPEC §21: one policy's range of a population rollout)."""
+        r = self._range(lo, hi)
+        host = {f: getattr(self, f).detach().cpu().numpy()[..., r] for f in self.FIELDS}
         eps = int(host["episodes"].astype(np.int64).sum())
         goals = int(host["goals"].astype(np.int64).sum())
         lens = int(host["len_sum"].astype(np.int64).sum())
@@ -95,11 +109,11 @@ class EpisodeStats:
             "successes": [int(v) for v in host["successes"].astype(np.int64).sum(axis=1)],
         }
         if self.interrupting:
-            out["interrupts"] = [int(v) for v in self.interrupts.detach().cpu().numpy().astype(np.int64).sum(axis=1)]
+            out["interrupts"] = [int(v) for v in self.interrupts.detach().cpu().numpy()[..., r].astype(np.int64).sum(axis=1)]
         if self.overrides is not None:
-            out["overrides"] = [int(v) for v in self.overrides.detach().cpu().numpy().astype(np.int64).sum(axis=1)]
+            out["overrides"] = [int(v) for v in self.overrides.detach().cpu().numpy()[..., r].astype(np.int64).sum(axis=1)]
         if self.audit is not None:
-            d = self.audit.disc_final.detach().cpu().numpy().astype(np.float64)[host["episodes"] > 0]
+            d = self.audit.disc_final.detach().cpu().numpy()[r].astype(np.float64)[host["episodes"] > 0]
             out["mean_discounted_return"] = float(np.cumsum(d)[-1]) / d.size if d.size else nan
         return out
 
@@ -108,6 +122,29 @@ def _mean(v) -> float:
     """The float64 mean of `v` summed in order (NaN for none)."""
     v = np.asarray(v, np.float64)
     return float(np.cumsum(v)[-1]) / v.size if v.size else float("nan")
+
+
+PAIRED_FIELDS = {"ret": "ret_sum", "disc_final": "disc_final", "goal": "goals", "steps": "len_sum"}
+
+
+def paired_differences(per_env_a, per_env_b) -> dict:
+    """Policy a against policy b on common random numbers (SPEC §21): `per_env_*` are two EpisodeStats.per_env() dicts of one
+    length (tensors or arrays) of one-episode evaluations with the discounted return kept. For ret (ret_sum), disc_final, goal
+    (goals) and steps (len_sum) returns {"mean_diff", "se", "n"} of the per-env differences a - b: host float64, summed in env
+    order; se is their unbiased standard deviation / sqrt(n), 0 below two envs. Equal inputs give exact zeros."""
+    out = {}
+    for name, f in PAIRED_FIELDS.items():
+        if f not in per_env_a or f not in per_env_b:
+            raise ValueError(f"paired_differences: both per-env dicts need {f!r} (evaluate(discounted=True, per_env=True))")
+        a, b = (np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v).astype(np.float64).reshape(-1)
+                for v in (per_env_a[f], per_env_b[f]))
+        if a.shape != b.shape:
+            raise ValueError(f"paired_differences: {f} holds {a.size} and {b.size} envs")
+        d, n = a - b, a.size
+        mean = float(np.cumsum(d)[-1]) / n if n else float("nan")
+        se = float(np.sqrt(np.cumsum((d - mean) ** 2)[-1] / (n - 1) / n)) if n >= 2 else 0.0
+        out[name] = {"mean_diff": mean, "se": se, "n": int(n)}
+    return out
 
 
 class GateAudit:

@@ -129,6 +129,47 @@ def branch_targets(g, q_old):
     return gbar, se2, D
 
 
+def damped_tables(W, W_new, lambdas):
+    """The candidates of a damped policy-improvement step (SPEC §21.4): row i is float32(float64(W) + lambdas[i] * (float64(W_new) -
+    float64(W))), of W's shape behind the leading [len(lambdas)]; the rows of lambda = 0 and lambda = 1 are W and W_new themselves,
+    by bits (the float64 difference is inexact where the two differ widely in magnitude). Tensors give a tensor on W's device,
+    arrays an array."""
+    as_np = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    w, wn = as_np(W).astype(np.float32), as_np(W_new).astype(np.float32)
+    if w.shape != wn.shape:
+        raise ValueError(f"damped_tables: W is {w.shape}, W_new {wn.shape}")
+    lam = [float(v) for v in lambdas]
+    d = wn.astype(np.float64) - w.astype(np.float64)
+    out = np.stack([w if v == 0.0 else wn if v == 1.0 else (w.astype(np.float64) + v * d).astype(np.float32) for v in lam]) \
+        if lam else np.zeros((0,) + w.shape, np.float32)
+    return torch.from_numpy(out).to(W.device) if isinstance(W, torch.Tensor) else out
+
+
+def choose_candidate(candidates, criterion: str = "discounted", z: float = 2.0) -> dict:
+    """The decision rule of improve_policy (SPEC §21.4), a pure function: `candidates` is a list of {"lambda", "summary",
+    "paired"} (paired: paired_differences against the current policy at the same epsilon). The candidate with the highest
+    mean of `criterion` ("discounted": mean_discounted_return / paired disc_final; "return": mean_return / ret; "success":
+    success_rate / goal) is picked, ties to the smallest lambda, a NaN mean never; it is accepted only where its paired
+    mean_diff exceeds z * se (se = 0, fewer than two envs or every env the same difference: where it exceeds 0). Returns
+    {"index" (the picked candidate's), "chosen_lambda" (0.0 when the current policy is kept), "accepted"}."""
+    keys = {"discounted": ("mean_discounted_return", "disc_final"), "return": ("mean_return", "ret"), "success": ("success_rate", "goal")}
+    if criterion not in keys:
+        raise ValueError(f"criterion must be one of {sorted(keys)}, not {criterion!r}")
+    mean_key, pair_key = keys[criterion]
+    best = None
+    for i, cand in enumerate(candidates):
+        m, lam = float(cand["summary"][mean_key]), float(cand["lambda"])
+        if m != m:
+            continue
+        if best is None or m > best[0] or (m == best[0] and lam < best[1]):
+            best = (m, lam, i)
+    if best is None:
+        return {"index": None, "chosen_lambda": 0.0, "accepted": False}
+    p = candidates[best[2]]["paired"][pair_key]
+    accepted = bool(best[1] != 0.0 and p["mean_diff"] > (float(z) * p["se"] if p["se"] > 0.0 else 0.0))
+    return {"index": best[2], "chosen_lambda": best[1] if accepted else 0.0, "accepted": accepted}
+
+
 def greedy_table(gbar, q_old, q_new) -> dict:
     """SPEC §20.4: does acting greedily on Q^new pick better actions than on Q^old, judged by the branch means gbar [M][A]? With
     a_old, a_new, a* the FIRST maxima of q_old, q_new, gbar (each [M][A]):

@@ -7,10 +7,12 @@ first N envs (`N`), timed in the same alternation (`none` is the plain rollout, 
 rollouts (SPEC §11, scg_rollout_interrupt) on a state of their own, timed in the same alternation. --choose times something
 else: value-ranked choice (SPEC §14, scg_rollout_select) against scg_rollout_record's kernel, on the default chain and on the
 sibling tree of tools/choice_report.py (bench_choose). --audit times the audited rollout (SPEC §15, scg_rollout_audit, keeping the
-discounted return) against scg_rollout_select with the same rules, record and launches (bench_audit).
+discounted return) against scg_rollout_select with the same rules, record and launches (bench_audit). --population C times a
+population rollout (SPEC §21, scg_rollout_population) of C policies x 4096 envs against C sequential audited rollouts of 4096 envs
+and against one audited rollout of C x 4096 envs under a single weight table (bench_population).
 
     python tools/rollout_bench.py [--sizes 4096 65536] [--k 64] [--rounds 7] [--epw 2 4 8 16 32] [--record none 1024 all]
-                                  [--interrupt] [--choose] [--audit]
+                                  [--interrupt] [--choose] [--audit] [--population 1 4 8 16]
 """
 import argparse
 import json
@@ -193,6 +195,55 @@ def bench_audit(n, k, rounds, rules, n_opt=5):
             "select_rounds_us": [round(v, 2) for v in side["select"]["us"]], "audit_rounds_us": [round(v, 2) for v in side["audit"]["us"]]}
 
 
+def bench_population(n_pol, k, rounds, n_per=4096, n_opt=5):
+    """µs per step of ONE population rollout of n_pol policies x n_per envs (distinct weight tables, the bench's epsilon and mask
+    for all) against (a) n_pol audited rollouts of n_per envs one after the other, one per table, and (b) one audited rollout of
+    n_pol * n_per envs under a single table: what per-policy tables cost. bench()'s workload, each side on states of its own,
+    the discounted return kept on all three, timed alternately."""
+    import numpy as np
+    import torch
+    import skill_chaining_with_graphs_amd as scg
+    from skill_chaining_with_graphs_amd.core import ScgContext
+    from skill_chaining_with_graphs_amd.evaluation import GateAudit
+    m = scg.load_map("pinball_simple")
+    n = n_pol * n_per
+    small, big = (ScgContext(v, n_opt, m, device=0, seed=7, epsilon=0.05, max_episode_steps=2000) for v in (n_per, n))
+    mask = ((1 << (n_opt + 1)) - 1) & ~1
+    clf = torch.as_tensor(rig.chain_classifiers(m, n_opt), device=big.device).view(-1)
+    g = torch.Generator().manual_seed(3)
+    W = (torch.randn((n_pol, n_opt + 1, 5, 1296), generator=g) * 1e-3).to(big.device)
+    eps = torch.full((n_pol,), 0.05, dtype=torch.float32, device=big.device)
+    enabled = torch.full((n_pol,), mask, dtype=torch.int32, device=big.device)
+    side = {"pop": {"st": rig.state_on(big, m, n), "au": GateAudit(n, big.device)},
+            "one": {"st": rig.state_on(big, m, n), "au": GateAudit(n, big.device)},
+            "seq": {"st": [rig.state_on(small, m, n_per, seed=1 + c) for c in range(n_pol)], "au": [GateAudit(n_per, small.device) for _ in range(n_pol)]}}
+    for s in side.values():
+        s["t"], s["us"] = 0, []
+
+    def roll(name):
+        s = side[name]
+        if name == "pop":
+            big.rollout(s["st"], W, clf, mask, s["t"], k, audit=s["au"], population=(eps, enabled))
+        elif name == "one":
+            big.rollout(s["st"], W[0].view(-1), clf, mask, s["t"], k, audit=s["au"])
+        else:
+            for c in range(n_pol):
+                small.rollout(s["st"][c], W[c].view(-1), clf, mask, s["t"], k, audit=s["au"][c])
+        s["t"] += k
+
+    for name in side:
+        roll(name); roll(name)
+    for _ in range(rounds):
+        for name in side:
+            side[name]["us"].append(rig.timed(lambda: roll(name), 3) * 1e6 / k)
+    pop, one, seq = (float(np.median(side[x]["us"])) for x in ("pop", "one", "seq"))
+    return {"policies": n_pol, "n_per": n_per, "k": k, "options": n_opt, "population_us_per_step": round(pop, 2),
+            "sequential_us_per_step": round(seq, 2), "single_table_us_per_step": round(one, 2),
+            "population_over_sequential": round(pop / seq, 4), "population_over_single_table": round(pop / one, 4),
+            "population_rounds_us": [round(v, 2) for v in side["pop"]["us"]], "sequential_rounds_us": [round(v, 2) for v in side["seq"]["us"]],
+            "single_table_rounds_us": [round(v, 2) for v in side["one"]["us"]]}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--sizes", type=int, nargs="+", default=[4096, 65536])
@@ -207,7 +258,13 @@ def main():
                     help="instead: value-ranked choice (SPEC §14) against the recording kernel, on the chain and on the sibling tree")
     ap.add_argument("--audit", action="store_true",
                     help="instead: the audited rollout (SPEC §15) against scg_rollout_select, for the four rules, on the sibling tree")
+    ap.add_argument("--population", type=int, nargs="+", default=None,
+                    help="instead: a population rollout (SPEC §21) of C policies x 4096 envs against C sequential audited rollouts and one of C x 4096 envs")
     a = ap.parse_args()
+    if a.population:
+        for c in a.population:
+            print(json.dumps(bench_population(c, a.k, a.rounds)), flush=True)
+        return
     if a.audit:
         for n in a.sizes:
             for rules in ("", "interrupt", "best", "best+interrupt"):
