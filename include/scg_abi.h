@@ -419,6 +419,25 @@ int scg_feature_gram(scg_ctx *ctx, int64_t n, const float *x, const float *y, co
 int scg_feature_gram_targets(scg_ctx *ctx, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
                              const float *Y /* [n_tgt][n] */, int32_t n_tgt, int32_t n_seg, const int64_t *offsets /* HOST */,
                              float *A /* [n_seg][1296][1296] */, float *B /* [n_seg][n_tgt][1296] */, void *stream);
+/* Weighted feature Gram (SPEC §22.1): scg_feature_gram_targets with a ROOT weight rw[n] per sample on every operand; the least-squares
+ * weight is w_n = rw[n]^2, so no square root is taken. With u_f(n) = fl32(rw[n] * phi_f(s_n)) and t_c(n) = fl32(rw[n] * Y[c][n]) — one
+ * IEEE binary32 multiply each, round to nearest, subnormals kept, fused with nothing; phi as scg_fourier_features forms it —
+ *   A[g][1296][1296] = sum_n u(n) u(n)^T   and   B[g][c][1296] = sum_n u(n) t_c(n),   0 <= n_tgt <= SCG_GRAM_MAX_TARGETS,
+ * on SPEC §16.1's chains: P = fma(u_i(n), u_j(n), P) from +0 over each slab of SCG_GRAM_SLAB samples counted from the segment's first
+ * sample, the slab sums added in order. A is exactly symmetric. By bits: rw = 1 everywhere gives scg_feature_gram_targets' A and B (and,
+ * with n_tgt = 0, scg_feature_gram's A); rw = 2 everywhere 4 A and 4 B where no partial sum is subnormal; a segment whose last m samples
+ * have rw = 0 the unweighted result of the segment shortened by m. A zero weight masks no non-finite value (0 * NaN is NaN): a non-finite
+ * rw[n] or state leaves the segment's outputs unspecified, a non-finite Y[c][n] its own B[.][c] and nothing else. A and the
+ * n_seg * n_tgt * 1296 floats of B are fully overwritten (an empty segment, n = 0: +0) and nothing else is written; needs no map; raises
+ * no asynchronous status; the same bits from every block build. SCG_ERR_INVALID, nothing launched, nothing written, in this sequence: a
+ * null x / y / vx / vy / rw / A / offsets, n < 0, n_seg outside [1, SCG_GRAM_MAX_SEGMENTS], offsets that decrease or leave [0, n], n_tgt
+ * outside [0, SCG_GRAM_MAX_TARGETS], n_tgt = 0 with a Y or a B, n_tgt >= 1 without Y or without B.
+ * Not offered weighted: the cross shape (scg_feature_cross_gram), the orders 3 and 7 (scg_basis_gram); nothing of LSTD-Q, of the fit to
+ * realised returns or of the learner uses weights. */
+int scg_feature_gram_weighted(scg_ctx *ctx, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                              const float *rw /* [n] root weights */, const float *Y /* [n_tgt][n], NULL iff n_tgt == 0 */,
+                              int32_t n_tgt /* 0 .. SCG_GRAM_MAX_TARGETS */, int32_t n_seg, const int64_t *offsets /* HOST */,
+                              float *A /* [n_seg][1296][1296] */, float *B /* [n_seg][n_tgt][1296], NULL iff n_tgt == 0 */, void *stream);
 /* Cross-feature Gram (SPEC §17.1): for each of n_seg segments (offsets as in scg_feature_gram) of n recorded samples with two states
  * each, s_n = (x, y, vx, vy)[n] and s2_n = (x2, y2, vx2, vy2)[n],
  *   C[g][1296][1296] = sum_n phi(s_n) phi(s2_n)^T   (rows: features of s, columns: features of s2; not symmetric)

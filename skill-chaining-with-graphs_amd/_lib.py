@@ -190,6 +190,7 @@ _SIGS = {
     "scg_fourier_features": (C.c_int, [_P, C.c_int32] + [_P] * 5 + [_P]),
     "scg_feature_gram": (C.c_int, [_P, C.c_int64] + [_P] * 5 + [C.c_int32, _P, _P, _P, _P]),
     "scg_feature_gram_targets": (C.c_int, [_P, C.c_int64] + [_P] * 5 + [C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "scg_feature_gram_weighted": (C.c_int, [_P, C.c_int64] + [_P] * 6 + [C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "scg_feature_cross_gram": (C.c_int, [_P, C.c_int64] + [_P] * 8 + [C.c_int32, _P, _P, _P]),
     "scg_basis_features": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 5 + [_P]),
     "scg_basis_gram": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 5 + [C.c_int32, _P, _P, _P, _P]),

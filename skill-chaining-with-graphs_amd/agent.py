@@ -1042,7 +1042,7 @@ class SkillChainingAgent:
     def fit_values_to_branches(self, trajectory=None, n_states: int = 8192, n_held: int = 2048, replicates: int = 8, vfs=None,
                                ridge: float = 1e-3, epsilon: float = 0.1, seed: Optional[int] = None, n_episodes: int = 4096,
                                apply: bool = False, keep: bool = False, interrupt: bool = False, choose: Optional[str] = None,
-                               steps_per_launch: int = 64):
+                               steps_per_launch: int = 64, weighting=None, tau2: Optional[float] = None, branches: Optional[dict] = None):
         """Fit every action's Q_k to fresh Monte-Carlo branch returns of ALL five actions from the same states (SPEC §20): one Gram,
         a right-hand side per action. Records episodes as branch_audit does (or takes its `trajectory`), then per value function k
         of `vfs` (default: all), with a generator seeded by `seed`, draws `n_states` rows of the EVEN envs' step rows with vf = k
@@ -1059,10 +1059,24 @@ class SkillChainingAgent:
         (valuefit.greedy_table: agreement_old / _new, changed, one_step_gain and its standard error; unbiased on the held-out
         half, whose replicates W_new never saw). `keep` adds report["vf"][k]["operands"] (states, D, A, B, delta, rows, n_fit,
         gbar, se2, q_old, q_new, result) and report["trajectory"].
+        `weighting` (SPEC §22): None is the fit above, untouched. "precision" weights every fit state by the precision of its
+        targets, w = valuefit.precision_weights(se2 of the fit half, tau2), and forms (A, B) = ScgContext.feature_gram_weighted(states,
+        [0, n_fit], valuefit.root_weights(w), D): one Gram, five targets, ridge_solve_shared as above. "precision_per_action" gives
+        every action its own weights (per_action=True): the fit states five times over as five segments with one target, the
+        segment of action a under column a of the weights, and valuefit.ridge_solve per action. An array [n_fit] or [n_fit][5] is
+        taken as w itself (valuefit.normalise_weights: mean 1 per column). With w = 1 everywhere (replicates = 1: se2 = 0) W_new has
+        the unweighted fit's bits. The report gains "weighting" ("given" for an array) and "tau2" (the argument) and, per weighted
+        value function, "tau2" (the value used) and "effective_n" = (sum w)^2 / sum w^2 (a list of five per action); old / new / per_action / greedy stay
+        UNWEIGHTED statistics against gbar on both halves: one yardstick for every weighting. `keep` adds w and rw to the operands.
+        `branches`: an earlier keep=True report; its trajectory, rows, states and BranchResults are reused and no rollout runs, so
+        that only the regression differs between two calls: several weightings on the SAME returns.
         Refused: r_option_success != 0 with any k >= 1 (as branch_audit), apply=True with shared weights (as
-        fit_values_to_returns), replicates < 1, n_states < 1, n_held < 0. apply=False leaves the agent as evaluate() does;
-        apply=True copies the fitted rows of `vfs` into W."""
-        from .valuefit import branch_targets, error_stats, greedy_table, returns_to_go, ridge_solve_shared
+        fit_values_to_returns), replicates < 1, n_states < 1, n_held < 0; ValueError for an unknown `weighting` string, weights of
+        a wrong shape, negative or non-finite, and a `branches` report without a trajectory or without the operands of a value
+        function of `vfs`. apply=False leaves the agent as evaluate() does; apply=True copies the fitted rows of `vfs` into W."""
+        from .valuefit import returns_to_go
+        if isinstance(weighting, str) and weighting not in ("precision", "precision_per_action"):
+            raise ValueError(f"weighting must be None, 'precision', 'precision_per_action' or an array of weights, not {weighting!r}")
         if int(replicates) < 1:
             raise ValueError("replicates must be >= 1")
         if int(n_states) < 1:
@@ -1079,49 +1093,98 @@ class SkillChainingAgent:
         if float(c.r_option_success) != 0.0 and any(k >= 1 for k in vfs):
             raise ScgError("fit_values_to_branches: r_option_success != 0: a branch's return carries no completion bonus, so it is "
                            "not SPEC §16.2's target of an option's value function; fit vfs=[0] only")
+        if branches is not None:                               # an earlier report's record and returns: only the regression runs
+            if not isinstance(branches, dict) or "trajectory" not in branches or any(
+                    k not in branches.get("vf", {}) or (branches["vf"][k]["n_fit"] and "operands" not in branches["vf"][k]) for k in vfs):
+                raise ValueError("branches must be a fit_values_to_branches(keep=True) report that holds every value function of vfs")
+            return self._fit_branches(branches["trajectory"], None, None, vfs, branches, n_states, n_held, replicates, ridge, epsilon, seed,
+                                      apply, keep, interrupt, choose, steps_per_launch, weighting, tau2)
         if trajectory is None:
             traj, _ = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose)
         else:
             traj = trajectory
         flat = traj.to_numpy()
         tg = returns_to_go(flat, float(c.gamma), float(c.r_option_success))
-        off = flat["offsets"]
-        env = np.repeat(np.arange(traj.n), np.diff(off))
-        row = np.arange(int(off[-1])) - off[:-1][env]
-        rng = np.random.default_rng(int(c.seed) if seed is None else int(seed))
+        return self._fit_branches(traj, flat, tg, vfs, None, n_states, n_held, replicates, ridge, epsilon, seed, apply, keep, interrupt,
+                                  choose, steps_per_launch, weighting, tau2)
+
+    def _fit_branches(self, traj, flat, tg, vfs, branches, n_states, n_held, replicates, ridge, epsilon, seed, apply, keep, interrupt,
+                      choose, steps_per_launch, weighting, tau2):
+        """fit_values_to_branches behind its checks: per value function the rows, the branch returns (or `branches`' kept ones), the
+        Gram under `weighting`, the solve and the report."""
+        from .valuefit import (branch_targets, error_stats, greedy_table, normalise_weights, precision_weights, ridge_solve,
+                               ridge_solve_shared, root_weights)
+        c = self.ctx.cfg
+        if branches is None:
+            off = flat["offsets"]
+            env = np.repeat(np.arange(traj.n), np.diff(off))
+            row = np.arange(int(off[-1])) - off[:-1][env]
+            rng = np.random.default_rng(int(c.seed) if seed is None else int(seed))
         dev = self.W.device
         W_new = self.W.clone()
-        report = {"replicates": int(replicates), "ridge": float(ridge), "vf": {}}
+        report = {"replicates": int(replicates), "ridge": float(ridge), "vf": {},
+                  "weighting": weighting if weighting is None or isinstance(weighting, str) else "given",
+                  "tau2": None if tau2 is None else float(tau2)}
         if keep:
             report["trajectory"] = traj
         for k in vfs:
-            halves = []
-            for parity, want in ((0, int(n_states)), (1, int(n_held))):
-                rows = np.nonzero(tg["sample"] & (flat["vf"] == k) & (env % 2 == parity))[0]
-                if len(rows) > want:
-                    rows = np.sort(rng.choice(rows, want, replace=False)) if want else rows[:0]
-                halves.append(rows)
-            n_fit, n_hld = len(halves[0]), len(halves[1])
-            rows = np.concatenate(halves)
+            if branches is not None:
+                n_fit, n_hld = int(branches["vf"][k]["n_fit"]), int(branches["vf"][k]["n_held"])
+            else:
+                halves = []
+                for parity, want in ((0, int(n_states)), (1, int(n_held))):
+                    rows = np.nonzero(tg["sample"] & (flat["vf"] == k) & (env % 2 == parity))[0]
+                    if len(rows) > want:
+                        rows = np.sort(rng.choice(rows, want, replace=False)) if want else rows[:0]
+                    halves.append(rows)
+                n_fit, n_hld = len(halves[0]), len(halves[1])
+                rows = np.concatenate(halves)
             rep = {"n_fit": int(n_fit), "n_held": int(n_hld), "delta_norm": 0.0}
             report["vf"][k] = rep
             if n_fit == 0:                                     # nothing to fit: the rows of W_k stay, and there is no Q^new to judge
                 continue
-            # the fit half's states first: its branch envs, and so its returns, do not depend on n_held
-            res = self.branch_returns(traj.resume_state(env[rows], row[rows]), np.tile(np.arange(NUM_ACTIONS, dtype=np.uint8), (len(rows), 1)),
-                                      int(replicates), epsilon, seed, interrupt, choose, steps_per_launch)
+            if branches is not None:
+                op = branches["vf"][k]["operands"]
+                res, states, kept_rows = op["result"], op["states"], op["rows"]
+                # the side context the branches ran on where the agent still holds it; the Gram and q_values need no particular one
+                ectx = self._branch_ctx[res.g.size][0] if res.g.size in self._branch_ctx else self.ctx
+            else:
+                # the fit half's states first: its branch envs, and so its returns, do not depend on n_held
+                res = self.branch_returns(traj.resume_state(env[rows], row[rows]), np.tile(np.arange(NUM_ACTIONS, dtype=np.uint8), (len(rows), 1)),
+                                          int(replicates), epsilon, seed, interrupt, choose, steps_per_launch)
+                ectx = self._branch_ctx[res.g.size][0]           # the side context the branches ran on: 5 R envs per state
+                states = [torch.from_numpy(np.ascontiguousarray(flat[f][rows - 1])).to(dev) for f in ("x", "y", "vx", "vy")]
+                kept_rows = (env[rows], row[rows])
             gbar, se2, D = branch_targets(res.g, res.qcache)
-            ectx = self._branch_ctx[res.g.size][0]               # the side context the branches ran on: 5 R envs per state
-            states = [torch.from_numpy(np.ascontiguousarray(flat[f][rows - 1])).to(dev) for f in ("x", "y", "vx", "vy")]
             fit_states = [t[:n_fit].contiguous() for t in states]
             D_fit = torch.from_numpy(np.ascontiguousarray(D[:, :n_fit])).to(dev)
-            A, B = ectx.feature_gram_targets(fit_states, [0, n_fit], D_fit)
-            delta = ridge_solve_shared(A[0].cpu().numpy(), B[0].cpu().numpy(), n_fit, ridge, self.ctx.scale)
+            w = rw = None
+            if weighting is None:
+                A, B = ectx.feature_gram_targets(fit_states, [0, n_fit], D_fit)
+                delta = ridge_solve_shared(A[0].cpu().numpy(), B[0].cpu().numpy(), n_fit, ridge, self.ctx.scale)
+            else:
+                if isinstance(weighting, str):
+                    w, rep["tau2"] = precision_weights(se2[:n_fit], tau2, per_action=weighting == "precision_per_action")
+                else:
+                    w = np.asarray(weighting, np.float64)
+                    if w.shape not in ((n_fit,), (n_fit, NUM_ACTIONS)):
+                        raise ValueError(f"weighting must be [{n_fit}] or [{n_fit}][{NUM_ACTIONS}] for value function {k}, not {w.shape}")
+                    w = normalise_weights(w)
+                rw = torch.from_numpy(root_weights(w)).to(dev)
+                sw, sw2 = np.cumsum(w, axis=0)[-1], np.cumsum(w * w, axis=0)[-1]
+                rep["effective_n"] = (sw * sw / sw2).tolist() if w.ndim == 2 else float(sw * sw / sw2)
+                if w.ndim == 1:                                # one Gram under the states' weights, a target per action
+                    A, B = ectx.feature_gram_weighted(fit_states, [0, n_fit], rw, D_fit)
+                    delta = ridge_solve_shared(A[0].cpu().numpy(), B[0].cpu().numpy(), n_fit, ridge, self.ctx.scale)
+                else:                                          # segment a: the fit states under action a's weights, D[a] its one target
+                    A, B = ectx.feature_gram_weighted([t.repeat(NUM_ACTIONS) for t in fit_states], n_fit * np.arange(NUM_ACTIONS + 1),
+                                                      rw.T.contiguous().view(-1), D_fit.view(1, -1))
+                    delta = ridge_solve(A.cpu().numpy(), B[:, 0].cpu().numpy(), [n_fit] * NUM_ACTIONS, ridge, self.ctx.scale)
             w_old = self.W[k].cpu().numpy()
             W_new[k] = torch.from_numpy((w_old.astype(np.float64) + delta).astype(np.float32)).to(dev)
             q_old = res.qcache
             q_new = np.zeros_like(q_old)
-            for i in range(0, len(rows), ectx.n_envs):         # (a branch context holds 5 R envs per state: one pass)
+            for i in range(0, n_fit + n_hld, ectx.n_envs):     # (a branch context holds 5 R envs per state: one pass)
                 sl = slice(i, i + ectx.n_envs)
                 q_new[sl] = ectx.q_values([t[sl].contiguous() for t in states], W_new[k].contiguous().view(-1)).cpu().numpy().T
             rep["delta_norm"] = float(np.sqrt(np.sum(delta * delta)))
@@ -1133,8 +1196,10 @@ class SkillChainingAgent:
                              "target_se": float(np.sqrt(np.mean(se2[sl]))) if se2[sl].size else float("nan"),
                              "greedy": greedy_table(gbar[sl], q_old[sl], q_new[sl])}
             if keep:
-                rep["operands"] = {"states": states, "D": D, "A": A, "B": B, "delta": delta, "rows": (env[rows], row[rows]), "n_fit": n_fit,
+                rep["operands"] = {"states": states, "D": D, "A": A, "B": B, "delta": delta, "rows": kept_rows, "n_fit": n_fit,
                                    "gbar": gbar, "se2": se2, "q_old": q_old, "q_new": q_new, "result": res}
+                if w is not None:
+                    rep["operands"].update(w=w, rw=rw)
         if apply:
             for k in vfs:
                 self.W[k].copy_(W_new[k])

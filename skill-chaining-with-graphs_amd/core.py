@@ -586,6 +586,27 @@ class ScgContext:
                    off.ctypes.data_as(C.c_void_p), _ptr(A), _ptr(B), self._stream())
         return A, B
 
+    def feature_gram_weighted(self, s, offsets, root_weights: torch.Tensor, Y: Optional[torch.Tensor] = None):
+        """SPEC §22.1: feature_gram_targets with a root weight per sample on every operand: A[g] = sum u(n) u(n)^T and B[g][c] = sum
+        u(n) t_c(n) over segment g, u(n) = root_weights[n] * phi(s_n) and t_c(n) = root_weights[n] * Y[c][n], one binary32 multiply
+        each: the weighted normal equations with the weights root_weights^2 (valuefit.root_weights gives the roots). `root_weights`
+        a contiguous float32 [n]; `Y` a contiguous float32 [n_tgt][n], 1 <= n_tgt <= 16, or None. Returns (A [n_seg][1296][1296],
+        B [n_seg][n_tgt][1296] or None); unit weights give feature_gram_targets' bits."""
+        (a,), n, off, n_seg, A = self._gram_setup("feature_gram_weighted", offsets, s)
+        self._chk(root_weights, torch.float32, n, "root_weights")
+        rw = root_weights if n else a[0]
+        n_tgt, B = 0, None
+        if Y is not None:
+            if not isinstance(Y, torch.Tensor) or Y.dim() != 2 or not (1 <= Y.shape[0] <= _lib.GRAM_MAX_TARGETS) or Y.shape[1] != n:
+                raise ScgError(f"feature_gram_weighted: Y must be [n_tgt][{n}] with 1 <= n_tgt <= {_lib.GRAM_MAX_TARGETS}")
+            n_tgt = int(Y.shape[0])
+            self._chk(Y, torch.float32, n_tgt * n, "Y")
+            Y = Y if n else a[0]
+            B = torch.empty((n_seg, n_tgt, NUM_FEATURES), dtype=torch.float32, device=self.device)
+        self._call("scg_feature_gram_weighted", C.c_int64(n), *[_ptr(t) for t in a], _ptr(rw), _ptr(Y), n_tgt, n_seg,
+                   off.ctypes.data_as(C.c_void_p), _ptr(A), _ptr(B), self._stream())
+        return A, B
+
     def feature_cross_gram(self, s, s2, offsets):
         """SPEC §17.1: C[g] = sum phi(s_n) phi(s2_n)^T over segment g = samples offsets[g] .. offsets[g+1]-1 of the state pairs
         (`s`, `s2`: four [n] tensors each, which may be the same tensors; `offsets` as for feature_gram). Returns C

@@ -2,7 +2,8 @@
 // v_mfma_f32_16x16x4_f32 whose operands are built on the fly from the 16-byte state: phi is never materialised. One template, two shapes:
 //   symmetric (GramSym)   A_g = sum_n phi(s_n) phi(s_n)^T, and with RHS b_g = sum_n phi(s_n) yv[n]: the macro-tiles on or above the
 //                         diagonal are computed and every block is stored with its mirror image; one table set of 64 samples in LDS;
-//                         or, SPEC §20.1, B_g[c] = sum_n phi(s_n) Y[c][n] for up to 16 targets c: the columns of the MFMA that forms b
+//                         or, SPEC §20.1, B_g[c] = sum_n phi(s_n) Y[c][n] for up to 16 targets c: the columns of the MFMA that forms b;
+//                         or, SPEC §22.1 (WEIGHTED), A and that B with a root weight per sample on every operand: sum_n rw_n^2 phi phi^T
 //   cross (GramCross)     C_g = sum_n phi(s_n) phi(s2_n)^T between a state and its successor: every macro-tile of the square, no mirror
 //                         store, no diagonal case; TWO table sets of 32 samples, s's for the row operands and s2's for the column operands
 // and, for the symmetric shape, the basis order p of SPEC §18 (GramBasis<p>: 3 or 7 next to GramSym's 5; GramOrder<p> holds what follows
@@ -114,10 +115,13 @@ struct GramArgs {
     // GRAM_RHS_TARGETS only, and behind everything the other instantiations read: their code keeps its argument offsets
     int64_t y_stride;                                // floats between two targets' rows of Y (the entry point's n)
     int32_t n_tgt;
+    // WEIGHTED only (SPEC §22.1), and behind everything else for the same reason
+    const float *rw;                                 // the root weight of every sample
 };
-// grid = MACROS x n_active workgroups of THREADS on stream s (defined in scg_gram.hip); the first two read s[0] only
+// grid = MACROS x n_active workgroups of THREADS on stream s (defined in scg_gram.hip); the first three read s[0] only
 hipError_t launch_feature_gram(const GramArgs &G, int n_active, hipStream_t s);
 hipError_t launch_feature_gram_targets(const GramArgs &G, int n_active, hipStream_t s);
+hipError_t launch_feature_gram_weighted(const GramArgs &G, int n_active, hipStream_t s);      // G.n_tgt = 0: A only
 hipError_t launch_feature_cross_gram(const GramArgs &G, int n_active, hipStream_t s);
 
 // the table places of feature f (clamped: the tiles of a short macro-tile read a valid place and are never stored): AB at f / P2, CD
@@ -133,7 +137,10 @@ __device__ __forceinline__ float gram_phi(const float2 *row, int ab_at, int cd_a
     return fmaf(-ab.y, cd.y, ab.x * cd.x);
 }
 
-template <class S, int RHS>
+// WEIGHTED (SPEC §22.1): every operand carries the sample's root weight, u_f(n) = rw[n] * phi_f(s_n) and t_c(n) = rw[n] * Y[c][n], one
+// binary32 multiply each, so that A = sum rw^2 phi phi^T and B = sum rw^2 phi Y on §16.1's chains; both operands of a diagonal block
+// carry it, so the block stays its own mirror image
+template <class S, int RHS, bool WEIGHTED = false>
 __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs G) {
     constexpr bool CROSS = S::CROSS;
     constexpr int R = S::R, WG = S::WG, MT = S::MT, ME = S::ME, CHUNK = S::CHUNK, SETS = S::SETS, THREADS = S::THREADS;
@@ -142,11 +149,13 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
     static_assert(RHS == GRAM_RHS_NONE || RHS == GRAM_RHS_ONE || TARGETS, "the three modes");
     static_assert(!(CROSS && RHS), "b belongs to the symmetric shape");
     static_assert(!TARGETS || (CHUNK % 16 == 0 && THREADS % 64 == 0), "the deal of the targets' fill");
+    static_assert(!WEIGHTED || (!CROSS && S::ORDER == 5 && RHS != GRAM_RHS_ONE), "the weighted shapes: order 5, symmetric, A alone or targets");
     __shared__ __attribute__((aligned(16))) float2 s_z1[SETS][CHUNK][4];
     __shared__ float2 s_tab[SETS][CHUNK * TS];
     // yv of the chunk; with TARGETS the chunk's targets sample-major, [CHUNK][16]: the B operand of four samples is 64 consecutive floats,
     // lane (n16, kk) reads its own bank (target-major rows of 64 floats would put the 16 lanes of a sample on one bank)
     __shared__ float s_yv[TARGETS ? CHUNK * GRAM_MAX_TGT : CHUNK];
+    __shared__ float s_rw[WEIGHTED ? CHUNK : 1];               // WEIGHTED: the chunk's root weights, +0 for a null sample (else: never touched)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n16 = lane & 15, kk = lane >> 4;                 // MFMA operand lane: row / column n16 of the tile, k index (A, B) or row group (C, D)
     int I, J;                                                  // macro-tile (I, J)
@@ -196,10 +205,15 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
                 // wave meet 4 deep on 16 banks (one target per wave and pass: 16 deep on 4). +0 for a target >= n_tgt and a sample >= m
                 for (int t = tid; t < CHUNK * GRAM_MAX_TGT; t += THREADS) {
                     const int smp = (t & 15) + 16 * (t >> 8), c = (t >> 4) & 15;
-                    s_yv[smp * GRAM_MAX_TGT + c] = c < G.n_tgt && smp < m ? G.yv[(int64_t)c * G.y_stride + base + smp] : 0.0f;
+                    float v = c < G.n_tgt && smp < m ? G.yv[(int64_t)c * G.y_stride + base + smp] : 0.0f;
+                    if constexpr (WEIGHTED) v = smp < m ? G.rw[base + smp] * v : 0.0f;       // t_c(n), rounded once
+                    s_yv[smp * GRAM_MAX_TGT + c] = v;
                 }
             } else if (RHS) {
                 for (int t = tid; t < CHUNK; t += THREADS) s_yv[t] = t < m ? G.yv[base + t] : 0.0f;
+            }
+            if constexpr (WEIGHTED) {
+                for (int t = tid; t < CHUNK; t += THREADS) s_rw[t] = t < m ? G.rw[base + t] : 0.0f;
             }
             __syncthreads();
             for (int t = tid; t < SETS * CHUNK * P1; t += THREADS) {
@@ -228,6 +242,11 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
                     for (int r = 0; r < R; ++r) {
                         pa[r] = gram_phi(rowa + 4 * ks * TS, ra[r], rc[r]);
                         pb[r] = gram_phi(rowb + 4 * ks * TS, ca[r], cc[r]);
+                    }
+                    if constexpr (WEIGHTED) {                         // u = rw * phi: a multiply of its own behind gram_phi's fma, 2 R per R^2 MFMAs
+                        const float w = s_rw[4 * ks + kk];
+#pragma unroll
+                        for (int r = 0; r < R; ++r) { pa[r] = w * pa[r]; pb[r] = w * pb[r]; }
                     }
                 };
                 auto step = [&](int ks, bool more) {

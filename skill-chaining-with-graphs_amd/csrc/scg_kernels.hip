@@ -17,8 +17,8 @@
 //   scg_aux_kernels.hpp      pinball / features / predict, and fit_kernel: SPEC §6 on 8 workgroups x 1024 chains per option behind
 //                            tagged-word exchanges; a fit whose workgroups cannot run together gives up after a wall-clock wait,
 //                            leaves its row untouched and raises the ctx's asynchronous status word
-//   scg_gram_kernel.hpp      SPEC §16.1's feature Gram, §20.1's with up to 16 right-hand sides and §17.1's cross-feature Gram, one kernel
-//                            template: here only its arguments and the three launches (its instantiations are compiled in scg_gram.hip)
+//   scg_gram_kernel.hpp      SPEC §16.1's feature Gram, §20.1's with up to 16 right-hand sides, §22.1's weighted one and §17.1's cross-feature Gram, one kernel
+//                            template: here only its arguments and the four launches (its instantiations are compiled in scg_gram.hip)
 //   scg_basis_kernels.hpp    SPEC §18's basis-order probe: here only the launches of the orders 3 and 7 (compiled in scg_basis.hip)
 // scg_rollout_variants.hip is the second translation unit: every other instantiation of rollout_kernel (SPEC §10's record, §11's
 // interruption, §14's value-ranked choice, §15's audit: the table in scg_rollout_kernel.hpp) and trial_kernel<true>, reached through
@@ -1278,10 +1278,11 @@ int scg_fourier_features(scg_ctx *c, int32_t n, const float *x, const float *y, 
 // What scg_feature_gram, scg_feature_gram_targets and scg_feature_cross_gram share behind their null checks: the other argument
 // checks, an empty segment's +0 fill, the non-empty segments listed into G — as listed, or longest first (ties as listed: blockIdx.y is dispatched slowest, so the
 // longest chains start first) — and the launch. G's pointers are the caller's; F is the feature count of the launch's order (§18);
-// n_tgt the right-hand sides a segment has in G.b (1 but for scg_feature_gram_targets, whose range check is the last one).
+// n_tgt the right-hand sides a segment has in G.b (1 but for scg_feature_gram_targets, whose range check is the last one, and for
+// scg_feature_gram_weighted — `weighted` —, whose range starts at 0 and whose Y and B, given or not as n_tgt says, are checked behind it).
 static int gram_call(scg_ctx *c, const char *fn, bool null_array, bool yv_without_b, int64_t n, int32_t n_seg, const int64_t *offsets,
                      int F, GramArgs &G, bool longest_first, hipError_t (*launch)(const GramArgs &, int, hipStream_t), void *stream,
-                     int32_t n_tgt = 1) {
+                     int32_t n_tgt = 1, bool weighted = false) {
     if (!c) return fail_in(nullptr, SCG_ERR_INVALID, fn, "null ctx");
     if (null_array) return fail_in(c, SCG_ERR_INVALID, fn, "null array argument");
     if (n < 0) return fail_in(c, SCG_ERR_INVALID, fn, "n must be >= 0");
@@ -1290,7 +1291,11 @@ static int gram_call(scg_ctx *c, const char *fn, bool null_array, bool yv_withou
     if (offsets[0] < 0 || offsets[n_seg] > n) return fail_in(c, SCG_ERR_INVALID, fn, "offsets leave [0, n]");
     for (int g = 0; g < n_seg; ++g)
         if (offsets[g + 1] < offsets[g]) return fail_in(c, SCG_ERR_INVALID, fn, "offsets decrease");
-    if (n_tgt < 1 || n_tgt > SCG_GRAM_MAX_TARGETS) return fail_in(c, SCG_ERR_INVALID, fn, "n_tgt out of range [1, SCG_GRAM_MAX_TARGETS]");
+    if (weighted) {
+        if (n_tgt < 0 || n_tgt > SCG_GRAM_MAX_TARGETS) return fail_in(c, SCG_ERR_INVALID, fn, "n_tgt out of range [0, SCG_GRAM_MAX_TARGETS]");
+        if (n_tgt == 0 && (G.yv || G.b)) return fail_in(c, SCG_ERR_INVALID, fn, "n_tgt = 0 goes with a null Y and a null B");
+        if (n_tgt >= 1 && (!G.yv || !G.b)) return fail_in(c, SCG_ERR_INVALID, fn, "n_tgt >= 1 needs Y and B");
+    } else if (n_tgt < 1 || n_tgt > SCG_GRAM_MAX_TARGETS) return fail_in(c, SCG_ERR_INVALID, fn, "n_tgt out of range [1, SCG_GRAM_MAX_TARGETS]");
     SCG_CHECK_ASYNC(c);
     DeviceGuard dev_guard(c->cfg.device);
     if (!dev_guard.ok) return fail_in(c, SCG_ERR_HIP, fn, "cannot make the context's device current");
@@ -1326,6 +1331,15 @@ int scg_feature_gram_targets(scg_ctx *c, int64_t n, const float *x, const float 
     G.y_stride = n; G.n_tgt = n_tgt;
     return gram_call(c, "scg_feature_gram_targets", !x || !y || !vx || !vy || !Y || !A || !B || !offsets, false, n, n_seg, offsets,
                      NF, G, false, launch_feature_gram_targets, stream, n_tgt);
+}
+
+// SPEC §22.1: every operand of scg_feature_gram_targets' kernel times the sample's root weight
+int scg_feature_gram_weighted(scg_ctx *c, int64_t n, const float *x, const float *y, const float *vx, const float *vy, const float *rw,
+                              const float *Y, int32_t n_tgt, int32_t n_seg, const int64_t *offsets, float *A, float *B, void *stream) {
+    GramArgs G = {{{x, y, vx, vy}, {x, y, vx, vy}}, Y, A, B};
+    G.y_stride = n; G.n_tgt = n_tgt; G.rw = rw;
+    return gram_call(c, "scg_feature_gram_weighted", !x || !y || !vx || !vy || !rw || !A || !offsets, false, n, n_seg, offsets,
+                     NF, G, false, launch_feature_gram_weighted, stream, n_tgt, true);
 }
 
 int scg_feature_cross_gram(scg_ctx *c, int64_t n, const float *x, const float *y, const float *vx, const float *vy,

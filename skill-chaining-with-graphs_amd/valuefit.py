@@ -2,7 +2,8 @@
 whose matrix scg_feature_gram forms. SPEC §17: the items of the least-squares TD fixed point (LSTD-Q) and the solve of its
 block system, whose off-diagonal part scg_feature_cross_gram forms. SPEC §20: the targets of a fit to all-action branch returns, the
 solve of one matrix against a right-hand side per action (scg_feature_gram_targets forms both) and the greedy-action table of its
-report. Host code, float64; the hot parts are ScgContext.feature_gram, feature_gram_targets and feature_cross_gram."""
+report. SPEC §22: the precision weights of that fit, their normalisation and the root weights scg_feature_gram_weighted takes. Host
+code, float64; the hot parts are ScgContext.feature_gram, feature_gram_targets, feature_gram_weighted and feature_cross_gram."""
 from __future__ import annotations
 
 import numpy as np
@@ -127,6 +128,55 @@ def branch_targets(g, q_old):
         se2 = var / R
     D = np.ascontiguousarray((gbar - q_old.astype(np.float64)).astype(np.float32).T)
     return gbar, se2, D
+
+
+def normalise_weights(w) -> np.ndarray:
+    """SPEC §22.2: w n / sum w, float64, the sum a plain chain in state order (per column of a [n][A] array): the weights of n
+    samples with mean 1, so that §16.3's ridge term ridge max(n, 1) / scale^2 keeps its meaning. ValueError for an array that is
+    not [n] or [n][A], for a negative or non-finite weight and for weights that sum to 0; weights that are all exactly 1 stay so."""
+    w = np.array(w, np.float64)
+    if w.ndim not in (1, 2) or not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError("weights must be a [n] or [n][A] array of finite values >= 0")
+    if len(w) == 0:
+        return w
+    total = np.cumsum(w, axis=0)[-1]                           # (cumsum adds in index order; sum() adds pairwise)
+    if np.any(total <= 0) or not np.isfinite(total).all():
+        raise ValueError("weights must have a finite sum > 0")
+    return w * len(w) / total
+
+
+def precision_weights(se2, tau2=None, per_action: bool = False):
+    """SPEC §22.2: the weights of a fit to branch means with the squared standard errors se2 [n][A] (branch_targets'): with
+    v_i = mean_a se2[i][a] ([n]; per_action: v = se2 itself, a column of weights per action), w = 1 / (v + tau2), then
+    normalise_weights. tau2 — the variance a target has beyond its replicates' spread; a parameter, not a constant of the method —
+    defaults to the median of v, to the mean of v where that is 0, and where that is 0 too every weight is exactly 1. Returns
+    (w float64, the tau2 used). ValueError for an se2 that is not [n][A], negative or non-finite, a tau2 that is negative or
+    non-finite, and a tau2 of 0 given with some v of 0."""
+    se2 = np.asarray(se2, np.float64)
+    if se2.ndim != 2 or not np.isfinite(se2).all() or (se2 < 0).any():
+        raise ValueError("se2 must be a [n][A] array of finite values >= 0")
+    v = se2.copy() if per_action else (se2.mean(axis=1) if se2.shape[1] else np.zeros(len(se2)))
+    if tau2 is None:
+        tau2 = float(np.median(v)) if v.size else 0.0
+        if tau2 == 0.0:
+            tau2 = float(np.mean(v)) if v.size else 0.0
+        if tau2 == 0.0:
+            return np.ones(v.shape, np.float64), 0.0
+    tau2 = float(tau2)
+    if not np.isfinite(tau2) or tau2 < 0:
+        raise ValueError("tau2 must be finite and >= 0")
+    if tau2 == 0.0 and (v == 0).any():
+        raise ValueError("tau2 = 0 with a target of variance 0: its weight would be infinite")
+    return normalise_weights(1.0 / (v + tau2)), tau2
+
+
+def root_weights(w) -> np.ndarray:
+    """SPEC §22.2: what scg_feature_gram_weighted takes, float32(sqrt(float64 w)), rounded once. ValueError for a negative or
+    non-finite weight."""
+    w = np.asarray(w, np.float64)
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError("weights must be finite and >= 0")
+    return np.sqrt(w).astype(np.float32)
 
 
 def damped_tables(W, W_new, lambdas):

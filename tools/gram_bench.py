@@ -11,9 +11,15 @@ states, interleaved round by round: "targets" = scg_feature_gram_targets, one se
 segment with yv (it issues the same number of MFMAs: the floor); "repeated" = scg_feature_gram on C segments of the same states
 repeated, target c as segment c's yv (what a fit of C actions would otherwise call). One JSON line per size: per arm the median,
 the fastest and the slowest round in ms (the tool's own round-to-round spread), and the ratios of the medians. --segs is not used.
+With --lib NAME=PATH a fourth arm "targets@NAME" is that build's scg_feature_gram_targets on the same operands in the same rounds.
+--weighted C (0 .. 16; SPEC §22.1) times, at each of --sizes samples and interleaved round by round, "weighted" =
+scg_feature_gram_weighted with C targets under seeded root weights in [0.25, 4] against "targets" = the unweighted call on the same
+operands (scg_feature_gram_targets; C = 0: scg_feature_gram without yv): per arm the median, the fastest and the slowest round, the
+ratio of the medians, and same_bits = does the weighted call under unit weights give the unweighted call's A and B by bits.
 
     python tools/gram_bench.py [--sizes 65536 1048576] [--segs 1 5] [--rounds 5] [--lib r3=path/to/libscg_hip_r3.so] [--order 7] [--out file.jsonl]
-    python tools/gram_bench.py --targets 5 [--sizes 8192 65536 1048576] [--rounds 9] [--out file.jsonl]
+    python tools/gram_bench.py --targets 5 [--sizes 8192 65536 1048576] [--rounds 9] [--lib parent=path/to/libscg_hip.so] [--out file.jsonl]
+    python tools/gram_bench.py --weighted 5 [--sizes 8192 65536 1048576] [--rounds 9] [--out file.jsonl]
 """
 import argparse
 import json
@@ -50,12 +56,56 @@ def materialised(ctx, s, offsets, chunk, order=None):
     return out
 
 
+def other_builds(a, ag):
+    """{NAME: a context on the library at PATH} for every --lib NAME=PATH."""
+    from skill_chaining_with_graphs_amd.core import ScgContext
+    return {name: ScgContext(64, 0, ag.map, device=0, library=path) for name, path in (spec.split("=", 1) for spec in a.lib)}
+
+
+def interleaved(runs, rounds):
+    """Every arm once per round, round by round: {arm: [ms per round]}."""
+    times = {name: [] for name in runs}
+    for _ in range(rounds):
+        for name, fn in runs.items():
+            times[name].append(rig.timed(fn, 1) * 1e3)
+    return times
+
+
+def spread(t):
+    return {"ms": round(statistics.median(t), 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3)}
+
+
+def weighted_bench(a):
+    """--weighted C: the two arms at each size; returns the JSON lines."""
+    import torch
+    C = a.weighted
+    ag, s = recorded_states(max(a.sizes), a.envs)
+    ctx, lines = ag.ctx, []
+    for n in a.sizes:
+        sub = [t[:n].contiguous() for t in s]
+        gen = torch.Generator(sub[0].device).manual_seed(n)
+        Y = torch.randn((C, n), dtype=torch.float32, device=sub[0].device, generator=gen) if C else None
+        rw = torch.rand(n, dtype=torch.float32, device=sub[0].device, generator=gen) * 3.75 + 0.25
+        plain = (lambda: ctx.feature_gram_targets(sub, [0, n], Y)) if C else (lambda: (ctx.feature_gram(sub, [0, n]), None))
+        runs = {"weighted": lambda: ctx.feature_gram_weighted(sub, [0, n], rw, Y), "targets": plain}
+        (A1, B1), (A0, B0) = ctx.feature_gram_weighted(sub, [0, n], torch.ones_like(rw), Y), plain()
+        same = bool(torch.equal(A1.view(torch.int32), A0.view(torch.int32)) and (C == 0 or torch.equal(B1.view(torch.int32), B0.view(torch.int32))))
+        times = interleaved(runs, a.rounds)
+        row = {"samples": n, "n_targets": C, "rounds": a.rounds, "same_bits": same}
+        row.update({name: spread(t) for name, t in times.items()})
+        row["weighted_over_targets"] = round(statistics.median(times["weighted"]) / statistics.median(times["targets"]), 4)
+        lines.append(json.dumps(row))
+        print(lines[-1], flush=True)
+    return lines
+
+
 def targets_bench(a):
-    """--targets C: the three arms at each size; returns the JSON lines."""
+    """--targets C: the three arms at each size (and one per --lib build); returns the JSON lines."""
     import torch
     C = a.targets
     ag, s = recorded_states(max(a.sizes), a.envs)
     ctx, lines = ag.ctx, []
+    others = other_builds(a, ag)
     for n in a.sizes:
         sub = [t[:n].contiguous() for t in s]
         Y = torch.randn((C, n), dtype=torch.float32, device=sub[0].device, generator=torch.Generator(sub[0].device).manual_seed(n))
@@ -63,16 +113,16 @@ def targets_bench(a):
         runs = {"targets": lambda: ctx.feature_gram_targets(sub, [0, n], Y),
                 "one_rhs": lambda: ctx.feature_gram(sub, [0, n], Y[0]),
                 "repeated": lambda: ctx.feature_gram(tiled, [i * n for i in range(C + 1)], yv)}
+        runs.update({f"targets@{name}": (lambda c=c: c.feature_gram_targets(sub, [0, n], Y)) for name, c in others.items()})
         (A, B), (A1, _), (_, bC) = runs["targets"](), runs["one_rhs"](), runs["repeated"]()
         same = bool(torch.equal(A, A1) and torch.equal(B[0], bC))      # (the bits the three ways must share)
-        times = {name: [] for name in runs}
-        for _ in range(a.rounds):
-            for name, fn in runs.items():
-                times[name].append(rig.timed(fn, 1) * 1e3)
+        for name in others:
+            Ao, Bo = runs[f"targets@{name}"]()
+            same = same and bool(torch.equal(A, Ao) and torch.equal(B, Bo))
+        times = interleaved(runs, a.rounds)
         med = {name: statistics.median(t) for name, t in times.items()}
         row = {"samples": n, "n_targets": C, "rounds": a.rounds, "same_bits": same}
-        for name, t in times.items():
-            row[name] = {"ms": round(med[name], 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3)}
+        row.update({name: spread(t) for name, t in times.items()})
         row["targets_over_one_rhs"] = round(med["targets"] / med["one_rhs"], 4)
         row["repeated_over_one_rhs"] = round(med["repeated"] / med["one_rhs"], 4)
         row["repeated_over_targets"] = round(med["repeated"] / med["targets"], 4)
@@ -88,21 +138,18 @@ def main():
     ap.add_argument("--envs", type=int, default=65536); ap.add_argument("--lib", nargs="*", default=[])
     ap.add_argument("--order", type=int, default=None, choices=(3, 5, 7)); ap.add_argument("--out", default=None)
     ap.add_argument("--targets", type=int, default=None, choices=range(1, 17), metavar="C")
+    ap.add_argument("--weighted", type=int, default=None, choices=range(0, 17), metavar="C")
     a = ap.parse_args()
-    if a.targets is not None:
-        lines = targets_bench(a)
+    if a.targets is not None or a.weighted is not None:
+        lines = targets_bench(a) if a.weighted is None else weighted_bench(a)
         if a.out:
             with open(a.out, "w") as fh:
                 fh.write("\n".join(lines) + "\n")
         return
     F = NF if a.order is None else (a.order + 1) ** 4
     import torch
-    from skill_chaining_with_graphs_amd.core import ScgContext
     ag, s = recorded_states(max(a.sizes) * max(a.segs), a.envs)
-    ctxs = {"shipped": ag.ctx}
-    for spec in a.lib:
-        name, path = spec.split("=", 1)
-        ctxs[name] = ScgContext(64, 0, ag.map, device=0, library=path)
+    ctxs = dict({"shipped": ag.ctx}, **other_builds(a, ag))
     lines = []
     for n in a.sizes:
         for k in a.segs:
@@ -115,17 +162,14 @@ def main():
             runs["materialised"] = lambda: materialised(ag.ctx, sub, off, a.chunk, a.order)
             ref = runs["shipped"]()
             err = float((runs["materialised"]() - ref).abs().max() / ref.abs().max())
-            times = {name: [] for name in runs}
-            for _ in range(a.rounds):
-                for name, fn in runs.items():
-                    times[name].append(rig.timed(fn, 1) * 1e3)
+            times = interleaved(runs, a.rounds)
             flops = n * k * F * (F + 1)
             row = {"samples_per_segment": n, "segments": k, "rounds": a.rounds, "materialised_max_rel_diff": err}
             if a.order is not None:
                 row["order"] = a.order
             for name, t in times.items():
                 ms = statistics.median(t)
-                row[name] = {"ms": round(ms, 3), "min_ms": round(min(t), 3), "tflops_triangle": round(flops / ms / 1e9, 2),
+                row[name] = {"ms": round(ms, 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3), "tflops_triangle": round(flops / ms / 1e9, 2),
                              "peak_fraction": round(flops / ms / 1e9 / PEAK_TF, 4)}
             lines.append(json.dumps(row))
             print(lines[-1], flush=True)
