@@ -432,8 +432,8 @@ int scg_feature_gram_targets(scg_ctx *ctx, int64_t n, const float *x, const floa
  * no asynchronous status; the same bits from every block build. SCG_ERR_INVALID, nothing launched, nothing written, in this sequence: a
  * null x / y / vx / vy / rw / A / offsets, n < 0, n_seg outside [1, SCG_GRAM_MAX_SEGMENTS], offsets that decrease or leave [0, n], n_tgt
  * outside [0, SCG_GRAM_MAX_TARGETS], n_tgt = 0 with a Y or a B, n_tgt >= 1 without Y or without B.
- * Not offered weighted: the cross shape (scg_feature_cross_gram), the orders 3 and 7 (scg_basis_gram); nothing of LSTD-Q, of the fit to
- * realised returns or of the learner uses weights. */
+ * Not offered weighted: the cross shape (scg_feature_cross_gram), the orders 3 and 7 of this entry point (scg_basis_gram_irls below has
+ * the weighted A at every order); nothing of LSTD-Q, of the fit to realised returns or of the learner uses weights. */
 int scg_feature_gram_weighted(scg_ctx *ctx, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
                               const float *rw /* [n] root weights */, const float *Y /* [n_tgt][n], NULL iff n_tgt == 0 */,
                               int32_t n_tgt /* 0 .. SCG_GRAM_MAX_TARGETS */, int32_t n_seg, const int64_t *offsets /* HOST */,
@@ -472,6 +472,28 @@ int scg_basis_gram(scg_ctx *ctx, int32_t order, int64_t n, const float *x, const
  * order 5. Then: n < 0, a null array, m out of range. */
 int scg_basis_values(scg_ctx *ctx, int32_t order, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
                      const float *V, int32_t m, float *out, void *stream);
+/* ---- the instruments of the Fourier initiation classifier's fit (SPEC §23): logistic regression on the basis of order p by IRLS.
+ * Reporting instruments as the probe above: nothing acts or learns with them. Both need no map, raise no asynchronous status and
+ * write their outputs only. */
+/* Logistic terms (SPEC §23.1). Per sample, from a logit z[n] and a label[n] (u8, non-zero is 1): p = sigmoid(z) by SPEC §6's formula
+ * operation by operation (a NaN and every z <= -87 give 0x1.666d0ep-126, z >= 87 gives 1), l = label != 0 ? 1 : 0, e = l - p,
+ * q = 1 - p, s = p * q, rw = sqrt(s): one binary32 operation each, fused with nothing, the square root correctly rounded (+0 for
+ * s = +0). Outputs p[n], rw[n] and e[n]. SCG_ERR_INVALID, nothing launched, nothing written, in this sequence: a null ctx, n < 0, a
+ * null array. n = 0 succeeds and writes nothing. */
+int scg_logistic_terms(scg_ctx *ctx, int64_t n, const float *z, const uint8_t *label, float *p, float *rw, float *e, void *stream);
+/* IRLS Gram (SPEC §23.2): for the order p in {3, 5, 7}, F = (p + 1)^4, and the segments of scg_feature_gram,
+ *   H[g][F][F] = sum_n u(n) u(n)^T,  u_f(n) = fl32(rw[n] * phi_f(s_n))   (scg_feature_gram_weighted's operands at the order's phi)
+ *   grad[g][F] = sum_n phi(s_n) e[n]                                      (the UNWEIGHTED phi: scg_basis_gram's b for yv = e)
+ * both on SPEC §16.1's chains. By bits: at order 5 H is scg_feature_gram_weighted's A (n_tgt = 0); at every order grad is
+ * scg_basis_gram's b for yv = e whatever rw holds, and H does not depend on e; rw = 1 everywhere gives scg_basis_gram's A; order q's H
+ * and grad are the sub-block of order p's at the embedded indices (q < p); H is exactly symmetric; the same bits from every block
+ * build. A non-finite rw[n] or state leaves the segment's H and grad unspecified, a non-finite e[n] its grad only; a zero weight masks
+ * no NaN. H and grad are fully overwritten (an empty segment, n = 0: +0) and nothing else is written. SCG_ERR_INVALID, nothing
+ * launched, nothing written, in this sequence: a null ctx, an order outside {3, 5, 7}, a null x / y / vx / vy / rw / e / H / grad /
+ * offsets, n < 0, n_seg outside [1, SCG_GRAM_MAX_SEGMENTS], offsets that decrease or leave [0, n]. */
+int scg_basis_gram_irls(scg_ctx *ctx, int32_t order, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                        const float *rw, const float *e, int32_t n_seg, const int64_t *offsets /* HOST */,
+                        float *H /* [n_seg][F][F] */, float *grad /* [n_seg][F] */, void *stream);
 /* Option.policy value part (SPEC §3.1): q[5][n] = Q_k(s, .) for one VF Wk[5][1296]. */
 int scg_q_values(scg_ctx *ctx, int32_t n, const float *x, const float *y, const float *vx,
                  const float *vy, const float *Wk, float *q, void *stream);

@@ -38,6 +38,9 @@ def __getattr__(name):
     if name in ("returns_to_go", "ridge_solve", "td_samples", "lstdq_solve", "damped_tables", "choose_candidate"):
         from . import valuefit
         return getattr(valuefit, name)
+    if name in ("irls_fit", "FourierClassifier", "classification_stats"):
+        from . import initfit
+        return getattr(initfit, name)
     if name == "SkillChainingAgent":
         from .agent import SkillChainingAgent
         return SkillChainingAgent

@@ -195,6 +195,8 @@ _SIGS = {
     "scg_basis_features": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 5 + [_P]),
     "scg_basis_gram": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 5 + [C.c_int32, _P, _P, _P, _P]),
     "scg_basis_values": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 5 + [C.c_int32, _P, _P]),
+    "scg_logistic_terms": (C.c_int, [_P, C.c_int64] + [_P] * 5 + [_P]),
+    "scg_basis_gram_irls": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 6 + [C.c_int32, _P, _P, _P, _P]),
     "scg_q_values": (C.c_int, [_P, C.c_int32] + [_P] * 6 + [_P]),
     "scg_q_update": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 12 + [C.c_uint32, _P]),
     "scg_classifier_predict": (C.c_int, [_P, C.c_int32] + [_P] * 4 + [_P]),

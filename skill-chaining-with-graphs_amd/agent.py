@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from . import dist as _dist
+from . import initfit
 from ._lib import CLF_STRIDE, NUM_ACTIONS, NUM_FEATURES, ScgError, auto_block_envs
 from .core import EnvState, ScgContext
 from .evaluation import BranchResult, EpisodeStats, GateAudit, paired_differences
@@ -1259,33 +1260,77 @@ class SkillChainingAgent:
             st += [torch.zeros_like(st[0]), torch.zeros_like(st[0])]
         return st
 
-    def initiation_report(self, k: int, states=None, n_states: int = 8192, seed: int = 0) -> dict:
+    def initiation_report(self, k: int, states=None, n_states: int = 8192, seed: int = 0, classifier=None) -> dict:
         """Does initiation set k hold exactly the states from which option k reaches its target? Trials of option k (greedy)
         from `states` ((x, y) or (x, y, vx, vy); default: n_states map.sample_free positions at rest, drawn with `seed`), each
-        start classified by in_k(s0). Returns tp / fp / fn / tn (predicted in I_k x trial succeeded), precision, recall,
-        success_in / success_out (success rate inside / outside the predicted set; NaN when empty), outcomes (count per
-        outcome) and, per entry, trials (the TrialResult), predicted (uint8) and states (x, y, vx, vy)."""
+        start classified by in_k(s0) — or, with `classifier` (an initfit.FourierClassifier, SPEC §23.3), by it: a reporting
+        instrument, the trials themselves run with in_k as ever. Returns tp / fp / fn / tn (predicted in I_k x trial
+        succeeded), precision, recall, success_in / success_out (success rate inside / outside the predicted set; NaN when
+        empty), outcomes (count per outcome) and, per entry, trials (the TrialResult), predicted (uint8) and states (x, y, vx, vy)."""
         if not (1 <= k <= self.n_options) or not ((self.enabled_mask | self.gest_mask) >> k) & 1:
             raise ValueError(f"option {k} is not enabled or gestating")
         xs, ys, vxs, vys = self._start_states(states, n_states, seed)
         res = self.option_trials(k, xs, ys, vxs, vys)
-        pred = self._trial_ctx.classifier_predict(xs, ys, self.clf[k].contiguous())
-        p = pred.cpu().numpy().astype(bool)
+        if classifier is None:
+            pred = self._trial_ctx.classifier_predict(xs, ys, self.clf[k].contiguous())
+        else:
+            pred = classifier.predict(self._trial_ctx, (xs, ys, vxs, vys))
         oc = res.outcome.cpu().numpy()
-        s = oc == _lib.TRIAL_SUCCESS
-        tp, fp, fn, tn = (int(v) for v in (np.sum(p & s), np.sum(p & ~s), np.sum(~p & s), np.sum(~p & ~s)))
+        st = initfit.classification_stats(pred.cpu().numpy(), oc == _lib.TRIAL_SUCCESS)
+        tp, fp, fn, tn = st["tp"], st["fp"], st["fn"], st["tn"]
         nan = float("nan")
         return {
             "option": int(k), "n": int(oc.size),
             "tp": tp, "fp": fp, "fn": fn, "tn": tn,
-            "precision": tp / (tp + fp) if tp + fp else nan,
-            "recall": tp / (tp + fn) if tp + fn else nan,
+            "precision": st["precision"],
+            "recall": st["recall"],
             "success_in": tp / (tp + fp) if tp + fp else nan,
             "success_out": fn / (fn + tn) if fn + tn else nan,
             "outcomes": {name: int(np.sum(oc == code)) for code, name in OUTCOMES.items()},
             "trials": res, "predicted": pred,
             "states": (xs, ys, vxs, vys),
         }
+
+    def fit_initiation_fourier(self, k: int, states=None, n_states: int = 8192, order: int = 3, features: str = "state",
+                               ridge: float = 1e-3, held_out: float = 0.5, seed: int = 0, trials: Optional[dict] = None):
+        """SPEC §23.3: fit a Fourier-basis classifier of order `order` on the `features` ("state": all of the basis, "position":
+        the features without velocity) to "option k started here reaches its target". Greedy trials of option k from `states`
+        as initiation_report draws or takes them (`trials`: an earlier report of this method or of initiation_report for option k,
+        whose states and outcomes are taken over, no trial run); the fit (initfit.irls_fit) on the even-indexed states
+        (held_out = 0.5; 0: on all of them). Returns (FourierClassifier, report): report["fit"] and report["held_out"] hold, for
+        their half, "n", "fourier" and "shipped" — initfit.classification_stats of the new classifier (with its log-loss) and of
+        SPEC §4.1's in_k on the same states —; "history" / "reason" are the fit's, "trials" / "states" / "predicted" /
+        "shipped_predicted" per entry. A reporting instrument: runs on the trial context, writes nothing to W, clf, the env state
+        or the training context's order."""
+        if held_out not in (0, 0.0, 0.5):
+            raise ValueError("held_out must be 0.5 (fit on the even-indexed states) or 0 (fit on all)")
+        if trials is None:
+            trials = self.initiation_report(k, states, n_states, seed)
+        elif int(trials["option"]) != int(k):
+            raise ValueError(f"trials= is a report of option {trials['option']}, not of option {k}")
+        st = tuple(trials["states"])
+        ok = (trials["trials"].outcome == _lib.TRIAL_SUCCESS)
+        tc = self._trial_ctx
+        n = st[0].numel()
+        fit_rows = torch.arange(0, n, 2 if held_out else 1, device=ok.device)
+        held_rows = torch.arange(1, n, 2, device=ok.device) if held_out else fit_rows
+        take = lambda rows: [t[rows].contiguous() for t in st]
+        w, history, reason = initfit.irls_fit(tc, order, take(fit_rows), ok[fit_rows], mask=features, ridge=ridge)
+        clf = initfit.FourierClassifier(order, features, w)
+        z = clf.logits(tc, st)
+        pred = (z > 0).to(torch.uint8)
+        shipped = trials.get("shipped_predicted")
+        if shipped is None:
+            shipped = tc.classifier_predict(st[0], st[1], self.clf[k].contiguous())
+        z_h, pred_h, ship_h, ok_h = z.cpu().numpy(), pred.cpu().numpy(), shipped.cpu().numpy(), ok.cpu().numpy()
+        report = {"option": int(k), "n": int(n), "order": int(order), "features": str(features), "ridge": float(ridge),
+                  "held_out": float(held_out), "history": history, "reason": reason, "iterations": len(history) - 1,
+                  "trials": trials["trials"], "states": st, "predicted": pred, "shipped_predicted": shipped}
+        for name, rows in (("fit", fit_rows), ("held_out", held_rows)):
+            r = rows.cpu().numpy()
+            report[name] = {"n": int(r.size), "fourier": initfit.classification_stats(pred_h[r], ok_h[r], z_h[r]),
+                            "shipped": initfit.classification_stats(ship_h[r], ok_h[r])}
+        return clf, report
 
     def refine_initiation(self, k: int, states=None, n_states: int = 8192, iters: int = 400, lr: float = 3.0,
                           l2: float = 1e-4, seed: int = 0):

@@ -654,6 +654,34 @@ class ScgContext:
                    self._stream())
         return out
 
+    # SPEC §23, the instruments of initfit.irls_fit
+    def logistic_terms(self, z: torch.Tensor, label: torch.Tensor):
+        """SPEC §23.1: (p, rw, e) float32 [n] from the logits `z` (float32 [n]) and the labels `label` (uint8 [n], non-zero is 1):
+        p = SPEC §6's sigmoid, e = l - p, rw = sqrt(p (1 - p)), one binary32 operation each."""
+        if not isinstance(z, torch.Tensor) or z.dim() != 1:
+            raise ScgError("logistic_terms: z must be a float32 [n] tensor")
+        n = z.numel()
+        self._chk(z, torch.float32, n, "z")
+        self._chk(label, torch.uint8, n, "label")
+        p, rw, e = (torch.empty(n, dtype=torch.float32, device=self.device) for _ in range(3))
+        if n:                                                # (an empty tensor has no address; n = 0 writes nothing)
+            self._call("scg_logistic_terms", C.c_int64(n), _ptr(z), _ptr(label), _ptr(p), _ptr(rw), _ptr(e), self._stream())
+        return p, rw, e
+
+    def basis_gram_irls(self, order: int, s, offsets, rw: torch.Tensor, e: torch.Tensor):
+        """SPEC §23.2: (H [n_seg][F][F], grad [n_seg][F]) at order `order`: H[g] = sum u(n) u(n)^T with u(n) = rw[n] * phi(s_n), the
+        weighted Gram of feature_gram_weighted at the order's phi, and grad[g] = sum phi(s_n) e[n] with the UNWEIGHTED phi,
+        basis_gram's b for yv = e. `rw`, `e`: contiguous float32 [n] (logistic_terms gives both)."""
+        F = _lib.basis_features(order)
+        (a,), n, off, n_seg, H = self._gram_setup("basis_gram_irls", offsets, s, features=F)
+        self._chk(rw, torch.float32, n, "rw")
+        self._chk(e, torch.float32, n, "e")
+        rw, e = (rw, e) if n else (a[0], a[0])
+        grad = torch.empty((n_seg, F), dtype=torch.float32, device=self.device)
+        self._call("scg_basis_gram_irls", int(order), C.c_int64(n), *[_ptr(t) for t in a], _ptr(rw), _ptr(e), n_seg,
+                   off.ctypes.data_as(C.c_void_p), _ptr(H), _ptr(grad), self._stream())
+        return H, grad
+
     def q_values(self, s, Wk: torch.Tensor) -> torch.Tensor:
         n = s[0].numel()
         x, y, vx, vy = self._chk4(s, n, "state")

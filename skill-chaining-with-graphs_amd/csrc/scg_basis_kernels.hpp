@@ -4,6 +4,7 @@
 //                           point launches features_kernel itself there)
 //   basis_values_kernel     out[r][n] = sum_f V[r][f] phi_f(s_n) for r < m <= 8 in §18.3's order: per c12 an fma chain T over c34 from +0,
 //                           the T added in c12 order from +0. phi is formed in registers, never stored.
+//   logistic_terms_kernel   SPEC §23.1: p = sigmoid_spec(z), e = l - p, rw = sqrt(p (1 - p)) per sample, every step one binary32 operation
 #pragma once
 
 // grid-stride launches on stream s (scg_basis.hip); st = {x, y, vx, vy}. The Gram launches read G.s[0] only.
@@ -11,6 +12,9 @@ hipError_t launch_basis_gram_3(const GramArgs &G, int n_active, hipStream_t s);
 hipError_t launch_basis_gram_7(const GramArgs &G, int n_active, hipStream_t s);
 hipError_t launch_basis_features(int order, int64_t n, const float *const *st, float *phi, hipStream_t s);      // order 3 or 7
 hipError_t launch_basis_values(int order, int64_t n, const float *const *st, const float *V, int m, float *out, hipStream_t s);
+hipError_t launch_basis_gram_irls_3(const GramArgs &G, int n_active, hipStream_t s);      // SPEC §23.2: G.rw, G.yv = e, G.b = grad
+hipError_t launch_basis_gram_irls_7(const GramArgs &G, int n_active, hipStream_t s);
+hipError_t launch_logistic_terms(int64_t n, const float *z, const uint8_t *label, float *p, float *rw, float *e, hipStream_t s);
 
 constexpr int BASIS_VALUES_SAMPLES = 8;              // samples a wavefront of basis_values_kernel takes at once: a weight is loaded once for all of them
 
@@ -99,5 +103,23 @@ __global__ __launch_bounds__(64) void basis_values_kernel(int64_t n, const float
             }
             wave_lds_sync();
         }
+    }
+}
+
+// SPEC §23.1. The build has -ffp-contract=off, so 1 - p and p q stay one subtraction and one multiply; sqrtf is the correctly rounded
+// binary32 root (no fast-math anywhere in this library). p (1 - p) is +0 or normal: p >= 0x1.666d0ep-126, and 1 - p >= 2^-24 unless p = 1.
+// (A template as the two above, so that scg_basis.hip alone holds its code.)
+constexpr int LOGISTIC_THREADS = 256;
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void logistic_terms_kernel(int64_t n, const float *z, const uint8_t *label, float *p, float *rw,
+                                                                 float *e) {
+    for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * THREADS) {
+        const float pv = sigmoid_spec(z[i]);
+        const float l = label[i] != 0 ? 1.0f : 0.0f;
+        const float q = 1.0f - pv;
+        const float sv = pv * q;
+        p[i] = pv;
+        rw[i] = sqrtf(sv);
+        e[i] = l - pv;
     }
 }

@@ -4,6 +4,7 @@
 //                         diagonal are computed and every block is stored with its mirror image; one table set of 64 samples in LDS;
 //                         or, SPEC §20.1, B_g[c] = sum_n phi(s_n) Y[c][n] for up to 16 targets c: the columns of the MFMA that forms b;
 //                         or, SPEC §22.1 (WEIGHTED), A and that B with a root weight per sample on every operand: sum_n rw_n^2 phi phi^T
+//                         or, SPEC §23.2 (IRLS), that weighted A as the Hessian H and, beside it, the UNWEIGHTED b for yv = e as grad
 //   cross (GramCross)     C_g = sum_n phi(s_n) phi(s2_n)^T between a state and its successor: every macro-tile of the square, no mirror
 //                         store, no diagonal case; TWO table sets of 32 samples, s's for the row operands and s2's for the column operands
 // and, for the symmetric shape, the basis order p of SPEC §18 (GramBasis<p>: 3 or 7 next to GramSym's 5; GramOrder<p> holds what follows
@@ -122,6 +123,7 @@ struct GramArgs {
 hipError_t launch_feature_gram(const GramArgs &G, int n_active, hipStream_t s);
 hipError_t launch_feature_gram_targets(const GramArgs &G, int n_active, hipStream_t s);
 hipError_t launch_feature_gram_weighted(const GramArgs &G, int n_active, hipStream_t s);      // G.n_tgt = 0: A only
+hipError_t launch_feature_gram_irls(const GramArgs &G, int n_active, hipStream_t s);          // SPEC §23.2 at order 5: G.rw, G.yv = e, G.b = grad
 hipError_t launch_feature_cross_gram(const GramArgs &G, int n_active, hipStream_t s);
 
 // the table places of feature f (clamped: the tiles of a short macro-tile read a valid place and are never stored): AB at f / P2, CD
@@ -139,8 +141,11 @@ __device__ __forceinline__ float gram_phi(const float2 *row, int ab_at, int cd_a
 
 // WEIGHTED (SPEC §22.1): every operand carries the sample's root weight, u_f(n) = rw[n] * phi_f(s_n) and t_c(n) = rw[n] * Y[c][n], one
 // binary32 multiply each, so that A = sum rw^2 phi phi^T and B = sum rw^2 phi Y on §16.1's chains; both operands of a diagonal block
-// carry it, so the block stays its own mirror image
-template <class S, int RHS, bool WEIGHTED = false>
+// carry it, so the block stays its own mirror image.
+// IRLS (SPEC §23.2; with WEIGHTED and GRAM_RHS_ONE): A as WEIGHTED forms it, at any order, and b from the UNWEIGHTED phi against yv = e:
+// the row operand's phi is kept beside its weighted copy, R more live registers per operand set, and only the b
+// product reads it. yv carries no weight.
+template <class S, int RHS, bool WEIGHTED = false, bool IRLS = false>
 __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs G) {
     constexpr bool CROSS = S::CROSS;
     constexpr int R = S::R, WG = S::WG, MT = S::MT, ME = S::ME, CHUNK = S::CHUNK, SETS = S::SETS, THREADS = S::THREADS;
@@ -149,7 +154,9 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
     static_assert(RHS == GRAM_RHS_NONE || RHS == GRAM_RHS_ONE || TARGETS, "the three modes");
     static_assert(!(CROSS && RHS), "b belongs to the symmetric shape");
     static_assert(!TARGETS || (CHUNK % 16 == 0 && THREADS % 64 == 0), "the deal of the targets' fill");
-    static_assert(!WEIGHTED || (!CROSS && S::ORDER == 5 && RHS != GRAM_RHS_ONE), "the weighted shapes: order 5, symmetric, A alone or targets");
+    static_assert(!WEIGHTED || (!CROSS && (IRLS ? RHS == GRAM_RHS_ONE : (S::ORDER == 5 && RHS != GRAM_RHS_ONE))),
+                  "the weighted shapes: symmetric; A alone or targets at order 5, or IRLS' one unweighted right-hand side at any order");
+    static_assert(!IRLS || WEIGHTED, "IRLS is a weighted mode");
     __shared__ __attribute__((aligned(16))) float2 s_z1[SETS][CHUNK][4];
     __shared__ float2 s_tab[SETS][CHUNK * TS];
     // yv of the chunk; with TARGETS the chunk's targets sample-major, [CHUNK][16]: the B operand of four samples is 64 consecutive floats,
@@ -236,8 +243,9 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
                 // per four samples: the operands of the NEXT four are read and formed before this four's products are issued (one wave per
                 // SIMD: nothing else hides the LDS round trip); a full chunk's loop is unrolled, a short one runs the same steps
                 const float2 *rowa = s_tab[0] + kk * TS, *rowb = s_tab[SETS - 1] + kk * TS;
-                float a[R], bo[R], an[R], bn[R];
-                auto operands = [&](int ks, float (&pa)[R], float (&pb)[R]) {
+                constexpr int RU = IRLS ? R : 1;                 // IRLS: the row operands' unweighted phi, for b
+                float a[R], bo[R], an[R], bn[R], au[RU], aun[RU];
+                auto operands = [&](int ks, float (&pa)[R], float (&pb)[R], float (&pu)[RU]) {
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         pa[r] = gram_phi(rowa + 4 * ks * TS, ra[r], rc[r]);
@@ -246,11 +254,14 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
                     if constexpr (WEIGHTED) {                         // u = rw * phi: a multiply of its own behind gram_phi's fma, 2 R per R^2 MFMAs
                         const float w = s_rw[4 * ks + kk];
 #pragma unroll
-                        for (int r = 0; r < R; ++r) { pa[r] = w * pa[r]; pb[r] = w * pb[r]; }
+                        for (int r = 0; r < R; ++r) {
+                            if constexpr (IRLS) pu[r] = pa[r];
+                            pa[r] = w * pa[r]; pb[r] = w * pb[r];
+                        }
                     }
                 };
                 auto step = [&](int ks, bool more) {
-                    if (more) operands(ks + 1, an, bn);
+                    if (more) operands(ks + 1, an, bn, aun);
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
 #pragma unroll
@@ -260,12 +271,12 @@ __global__ __launch_bounds__(S::THREADS, S::WPE) void gram_kernel(const GramArgs
                         // (TARGETS: target c as column c; a column of the product depends on that column of the operand only)
                         const float yb = TARGETS ? s_yv[(4 * ks + kk) * GRAM_MAX_TGT + n16] : (n16 == 0 ? s_yv[4 * ks + kk] : 0.0f);
 #pragma unroll
-                        for (int r = 0; r < R; ++r) bacc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], yb, bacc[r], 0, 0, 0);
+                        for (int r = 0; r < R; ++r) bacc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(IRLS ? au[r] : a[r], yb, bacc[r], 0, 0, 0);
                     }
 #pragma unroll
-                    for (int r = 0; r < R; ++r) { a[r] = an[r]; bo[r] = bn[r]; }
+                    for (int r = 0; r < R; ++r) { a[r] = an[r]; bo[r] = bn[r]; if constexpr (IRLS) au[r] = aun[r]; }
                 };
-                operands(0, a, bo);
+                operands(0, a, bo, au);
                 if (m == CHUNK) {
 #pragma unroll
                     for (int ks = 0; ks < CHUNK / 4; ++ks) step(ks, ks + 1 < CHUNK / 4);

@@ -18,8 +18,10 @@
 //                            tagged-word exchanges; a fit whose workgroups cannot run together gives up after a wall-clock wait,
 //                            leaves its row untouched and raises the ctx's asynchronous status word
 //   scg_gram_kernel.hpp      SPEC §16.1's feature Gram, §20.1's with up to 16 right-hand sides, §22.1's weighted one and §17.1's cross-feature Gram, one kernel
-//                            template: here only its arguments and the four launches (its instantiations are compiled in scg_gram.hip)
-//   scg_basis_kernels.hpp    SPEC §18's basis-order probe: here only the launches of the orders 3 and 7 (compiled in scg_basis.hip)
+//                            template (and §23.2's IRLS mode of it): here only its arguments and the five launches (its instantiations are
+//                            compiled in scg_gram.hip)
+//   scg_basis_kernels.hpp    SPEC §18's basis-order probe and §23's logistic terms and IRLS Gram at the orders 3 and 7: here only the
+//                            launches (compiled in scg_basis.hip)
 // scg_rollout_variants.hip is the second translation unit: every other instantiation of rollout_kernel (SPEC §10's record, §11's
 // interruption, §14's value-ranked choice, §15's audit: the table in scg_rollout_kernel.hpp) and trial_kernel<true>, reached through
 // launch_rollout<REC, Args> / launch_trial_record, which the two kernel headers declare.
@@ -1381,6 +1383,32 @@ int scg_basis_gram(scg_ctx *c, int32_t order, int64_t n, const float *x, const f
     GramArgs G = {{{x, y, vx, vy}, {x, y, vx, vy}}, yv, A, b};
     return gram_call(c, "scg_basis_gram", !x || !y || !vx || !vy || !A || !offsets, (yv == nullptr) != (b == nullptr), n, n_seg, offsets,
                      F, G, false, order == 3 ? launch_basis_gram_3 : (order == 5 ? launch_feature_gram : launch_basis_gram_7), stream);
+}
+
+// ---- SPEC §23: the instruments of the Fourier initiation classifier's IRLS fit
+int scg_logistic_terms(scg_ctx *c, int64_t n, const float *z, const uint8_t *label, float *p, float *rw, float *e, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_logistic_terms: null ctx");
+    if (n < 0) return fail(c, SCG_ERR_INVALID, "scg_logistic_terms: n must be >= 0");
+    if (!z || !label || !p || !rw || !e) return fail(c, SCG_ERR_INVALID, "scg_logistic_terms: null array argument");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_logistic_terms");
+    if (n == 0) return SCG_OK;
+    SCG_HIP(c, launch_logistic_terms(n, z, label, p, rw, e, reinterpret_cast<hipStream_t>(stream)));
+    return SCG_OK;
+}
+
+// H is the weighted A of SPEC §22.1 at the order's phi, grad the unweighted b of §16.1 / §18.2 for yv = e: gram_call's checks, in
+// gram_call's sequence, behind the order's
+int scg_basis_gram_irls(scg_ctx *c, int32_t order, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                        const float *rw, const float *e, int32_t n_seg, const int64_t *offsets, float *H, float *grad, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_basis_gram_irls: null ctx");
+    const int F = basis_order_features(order);
+    if (!F) return fail(c, SCG_ERR_INVALID, "scg_basis_gram_irls: order must be 3, 5 or 7");
+    GramArgs G = {{{x, y, vx, vy}, {x, y, vx, vy}}, e, H, grad};
+    G.y_stride = 0; G.n_tgt = 1; G.rw = rw;
+    return gram_call(c, "scg_basis_gram_irls", !x || !y || !vx || !vy || !rw || !e || !H || !grad || !offsets, false, n, n_seg, offsets,
+                     F, G, false, order == 3 ? launch_basis_gram_irls_3 : (order == 5 ? launch_feature_gram_irls : launch_basis_gram_irls_7),
+                     stream);
 }
 
 int scg_basis_values(scg_ctx *c, int32_t order, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
