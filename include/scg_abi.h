@@ -332,6 +332,25 @@ int scg_rollout_population(scg_ctx *ctx, float *x, float *y, float *vx, float *v
                            const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action,
                            void *stream, const scg_population *pop);
 
+/* ---- population rollouts with a classifier table per policy (SPEC §24.1) ----
+ * scg_rollout_population_clf is scg_rollout_population plus `pop_clf` (scg_population itself is unchanged: callers compiled against
+ * it keep working). pop_clf = NULL is scg_rollout_population, which forwards here: the same kernels, the same results.
+ * With pop_clf, a DEVICE array [C][n_vf][SCG_CLF_STRIDE], the envs of policy c use the rows pop_clf[c] wherever the rollout reads a
+ * classifier: §4.2's membership masks of s' and s_next and all that follows from them (keep / success / left-initiation, the
+ * candidate set, the selection, §14's choice, §15's force check, §9's term code in the record). `clf` is then no policy's (as
+ * cfg's epsilon is no policy's with pop->epsilon) but is checked as before. Gestation, parents, map and hyper-parameters stay the
+ * context's.
+ * The contract is scg_rollout_population's with clf = pop_clf[c] on the n_per-env context of range c.
+ * Errors: scg_rollout_population's, in its sequence; after them SCG_ERR_INVALID (nothing launched, nothing written) for a
+ * non-NULL pop_clf with pop == NULL. The write set is scg_rollout_population's; pop_clf is never written. Results do not depend on
+ * the launch geometry or the block build; no asynchronous failure bit is raised. */
+int scg_rollout_population_clf(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                               int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                               const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                               uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                               const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action,
+                               void *stream, const scg_population *pop, const float *pop_clf);
+
 /* Device pointers of the ctx-owned reduced gradient G[n_vf][5][1296] and counts n_k[n_vf] (int32)
  * left by the last scg_step(LEARN) — the buffers a multi-rank caller all-reduces (SPEC §5). */
 int scg_grad_buffers(scg_ctx *ctx, float **G, int32_t **n_k);
@@ -506,6 +525,11 @@ int scg_q_update(scg_ctx *ctx, int32_t n, int32_t k, const float *x, const float
 /* Option.initiation_classifier.predict (SPEC §4.1): out[n] u8 = w.psi(x,y) > 0 for one row w8[8]. */
 int scg_classifier_predict(scg_ctx *ctx, int32_t n, const float *x, const float *y, const float *w8,
                            uint8_t *out, void *stream);
+/* The value whose sign scg_classifier_predict tests (SPEC §24.2): z[n] f32 = w.psi(x,y) by the same device function, so
+ * (z > 0) == out for every input, NaN included. scg_classifier_predict's checks in its sequence; n = 0 writes nothing;
+ * needs no map; writes z only. */
+int scg_classifier_logits(scg_ctx *ctx, int32_t n, const float *x, const float *y, const float *w8,
+                          float *z, void *stream);
 /* Option.initiation_classifier.fit (SPEC §6), batched over n_fit options: xy[M_total][2],
  * label[M_total] u8, offsets[n_fit+1] int32 (device), w[n_fit][8] in/out. */
 int scg_fit_initiation(scg_ctx *ctx, int32_t n_fit, const float *xy, const uint8_t *label,

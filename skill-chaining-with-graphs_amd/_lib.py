@@ -180,6 +180,8 @@ _SIGS = {
     "scg_rollout_branch": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, C.POINTER(Audit), _P, _P]),
     "scg_rollout_population": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, C.POINTER(Audit), _P, _P,
                                             C.POINTER(Population)]),
+    "scg_rollout_population_clf": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, C.POINTER(Audit), _P, _P,
+                                                C.POINTER(Population), _P]),
     "scg_grad_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "scg_set_grad_buffers": (C.c_int, [_P, _P, _P]),
     "scg_apply_update": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -200,6 +202,7 @@ _SIGS = {
     "scg_q_values": (C.c_int, [_P, C.c_int32] + [_P] * 6 + [_P]),
     "scg_q_update": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 12 + [C.c_uint32, _P]),
     "scg_classifier_predict": (C.c_int, [_P, C.c_int32] + [_P] * 4 + [_P]),
+    "scg_classifier_logits": (C.c_int, [_P, C.c_int32] + [_P] * 4 + [_P]),
     "scg_set_option_parents": (C.c_int, [_P, _P]),
     "scg_invalidate_order": (C.c_int, [_P]),
     "scg_set_trace_buffers": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),

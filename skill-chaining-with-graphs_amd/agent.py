@@ -500,7 +500,8 @@ class SkillChainingAgent:
         (SPEC §15); the force acts in the first launch, and the GateAudit is left in stats.audit.
         `population` = (W [C, n_vf, 5, 1296], epsilon [C] or None, enabled [C] or None) on the device makes every launch a
         population rollout (SPEC §21) of C policies over n_episodes envs each: the context has C * n_episodes envs, the `states`
-        are repeated for every policy, and `epsilon` is the context's own (no policy's, where the population gives one)."""
+        are repeated for every policy, and `epsilon` is the context's own (no policy's, where the population gives one). A fourth
+        element, a [C, n_vf, 8] classifier table (or None), gives every policy its own classifiers (SPEC §24.1)."""
         if choose not in (None, "value"):
             raise ValueError(f"choose must be None or 'value', not {choose!r}")
         if states is not None:
@@ -514,13 +515,13 @@ class SkillChainingAgent:
         c = self.ctx.cfg
         W, kw = self.W, {}
         if population is not None:
-            W, pol_eps, pol_enabled = population
+            W, pol_eps, pol_enabled, *pol_clf = population
             n_pol = int(W.shape[0])
             if n * n_pol > 2 ** 31 - 1:
                 raise ValueError(f"{n_pol} policies x {n} episodes are more envs than a context holds")
             if states is not None:
                 states = [s.repeat(n_pol) for s in states]
-            n, kw["population"] = n * n_pol, (pol_eps, pol_enabled)
+            n, kw["population"] = n * n_pol, (pol_eps, pol_enabled, *pol_clf)
         ectx, st, stats = self._eval_context(n, epsilon, seed, states)
         traj = Trajectory(n, spl + 1, 0, ectx.device, n_vf=self.n_vf) if record else None
         if audit is not None:
@@ -538,7 +539,7 @@ class SkillChainingAgent:
 
     def evaluate_policies(self, W, epsilons=None, enabled=None, n_episodes: int = 4096, seed: Optional[int] = None,
                           steps_per_launch: int = 64, states=None, interrupt: bool = False, choose: Optional[str] = None,
-                          per_env: bool = False, baseline: int = 0):
+                          per_env: bool = False, baseline: int = 0, clf=None):
         """Several policies in one set of launches, on common random numbers (SPEC §21): `W` is [C, n_vf, 5, 1296] or a list of C
         [n_vf, 5, 1296] tables, `epsilons` and `enabled` scalars or one per policy (defaults: 0.0 and the agent's enabled mask).
         evaluate(discounted=True)'s launches run ONCE, on an evaluation context of C * n_episodes envs of which the envs c *
@@ -548,9 +549,26 @@ class SkillChainingAgent:
         paired[c] is evaluation.paired_differences of policy c against policy `baseline` (exact zeros for the baseline itself and
         for any policy equal to it). With per_env=True also the list of the policies' per-env dicts, as (summaries, paired,
         per_envs). The training run is left alone exactly as by evaluate(). ValueError for C outside 1 .. 64, for more than 2^31 - 1
-        envs in all, and for `epsilons` / `enabled` of another length."""
+        envs in all, and for `epsilons` / `enabled` of another length.
+        `clf` (SPEC §24.3): None (the agent's classifier table for every policy), one [n_vf, 8] table for all of them, or [C, n_vf, 8]
+        / a list of C tables, one per policy: summaries[c] is then evaluate()'s with clf[c] in place too. With `clf` given, `W` may
+        also be a single [n_vf, 5, 1296] table, repeated for every policy of clf (comparing classifiers under one W)."""
         dev = self.W.device
         table = (self.n_vf, NUM_ACTIONS, NUM_FEATURES)
+        row = (self.n_vf, _lib.CLF_STRIDE)
+        if clf is not None:
+            if isinstance(clf, (list, tuple)):
+                clf = [torch.as_tensor(t, dtype=torch.float32).to(dev) for t in clf]
+                if not clf or any(tuple(t.shape) != row for t in clf):
+                    raise ValueError(f"every table of clf must be {list(row)}")
+                clf = torch.stack(clf)
+            clf = torch.as_tensor(clf, dtype=torch.float32).to(dev)
+            if clf.dim() not in (2, 3) or tuple(clf.shape[-2:]) != row:
+                raise ValueError(f"clf must be {list(row)} or [C, {row[0]}, {row[1]}], not {tuple(clf.shape)}")
+            if not isinstance(W, (list, tuple)):
+                W = torch.as_tensor(W, dtype=torch.float32).to(dev)
+                if W.dim() != 4 and W.numel() == self.W.numel():       # one W for every policy of clf
+                    W = W.reshape(1, *table).repeat(int(clf.shape[0]) if clf.dim() == 3 else 1, 1, 1, 1)
         if isinstance(W, (list, tuple)):
             W = [torch.as_tensor(w, dtype=torch.float32).to(dev) for w in W]
             if not W or any(w.numel() != self.W.numel() for w in W):
@@ -575,9 +593,16 @@ class SkillChainingAgent:
 
         pol_eps = per_policy(epsilons, 0.0, np.float32, "epsilons")
         pol_enabled = per_policy(enabled, self.enabled_mask, np.int32, "enabled")
-        # (the context's own epsilon is read by no policy: every one has its entry)
+        pol_clf = ()
+        if clf is not None:
+            if clf.dim() == 2:
+                clf = clf.reshape(1, *row).repeat(n_pol, 1, 1)
+            if int(clf.shape[0]) != n_pol:
+                raise ValueError(f"clf must hold one table per policy ({n_pol}), not {int(clf.shape[0])}")
+            pol_clf = (clf.contiguous(),)
+        # (the context's own epsilon is read by no policy: every one has its entry; with clf the agent's table likewise)
         stats, _ = self._eval_launches(n_episodes, 0.0, seed, steps_per_launch, states, interrupt, choose=choose, audit=True,
-                                       population=(W.contiguous(), pol_eps, pol_enabled))
+                                       population=(W.contiguous(), pol_eps, pol_enabled, *pol_clf))
         n = stats.n // n_pol
         summaries = [stats.summary(c * n, (c + 1) * n) for c in range(n_pol)]
         envs = [{f: v.detach().cpu() for f, v in stats.per_env(c * n, (c + 1) * n).items()} for c in range(n_pol)]
@@ -1215,12 +1240,13 @@ class SkillChainingAgent:
 
     # ------------------------------------------------------------------ option trials (SPEC §9)
     def option_trials(self, option, x, y, vx=None, vy=None, epsilon: float = 0.0, seed: Optional[int] = None,
-                      record: Optional[int] = None):
+                      record: Optional[int] = None, clf=None):
         """Run option `option` (an int, or one id per start state) from each start state (x, y, vx, vy; velocities default to
         zero) until it terminates, with the current W, clf and enabled / gestating options, weights frozen (SPEC §9). Returns a
         TrialResult (outcome, steps, ret, disc_ret, v0, end state; summary() per option). Runs on a separate cached context
         at t0 = 0: W, state, t, the training context's env order, trace ring and counters are untouched. With `record` (rows
-        per entry) every step is recorded (SPEC §10) into res.trajectory, a Trajectory over all entries."""
+        per entry) every step is recorded (SPEC §10) into res.trajectory, a Trajectory over all entries. `clf`: a classifier table
+        [n_vf, 8] to run the trials under instead of the agent's (SPEC §24.3's fixed-point lines); it is read only."""
         dev = self.W.device
         x, y = self._f32(x), self._f32(y)
         n = x.numel()
@@ -1238,7 +1264,10 @@ class SkillChainingAgent:
         self._mirror_training(tc, epsilon)
         res = TrialResult(n, opt, dev)
         traj = None if record is None else Trajectory(n, int(record), 0, dev, n_vf=self.n_vf)
-        tc.option_trials(x, y, vx, vy, res.option, self.W.view(-1), self.clf.view(-1), self.enabled_mask, 0, res, record=traj)
+        table = self.clf if clf is None else torch.as_tensor(clf, dtype=torch.float32).to(dev).contiguous()
+        if tuple(table.shape) != tuple(self.clf.shape):
+            raise ValueError(f"clf must be {list(self.clf.shape)}, not {tuple(table.shape)}")
+        tc.option_trials(x, y, vx, vy, res.option, self.W.view(-1), table.view(-1), self.enabled_mask, 0, res, record=traj)
         if traj is not None:
             res.trajectory = traj.append()
         return res
@@ -1265,7 +1294,8 @@ class SkillChainingAgent:
         from `states` ((x, y) or (x, y, vx, vy); default: n_states map.sample_free positions at rest, drawn with `seed`), each
         start classified by in_k(s0) — or, with `classifier` (an initfit.FourierClassifier, SPEC §23.3), by it: a reporting
         instrument, the trials themselves run with in_k as ever. Returns tp / fp / fn / tn (predicted in I_k x trial
-        succeeded), precision, recall, success_in / success_out (success rate inside / outside the predicted set; NaN when
+        succeeded), precision, recall, log_loss (the mean log-loss of the classifier's logits against the outcomes: in_k's from
+        ScgContext.classifier_logits, SPEC §24.2), success_in / success_out (success rate inside / outside the predicted set; NaN when
         empty), outcomes (count per outcome) and, per entry, trials (the TrialResult), predicted (uint8) and states (x, y, vx, vy)."""
         if not (1 <= k <= self.n_options) or not ((self.enabled_mask | self.gest_mask) >> k) & 1:
             raise ValueError(f"option {k} is not enabled or gestating")
@@ -1273,10 +1303,12 @@ class SkillChainingAgent:
         res = self.option_trials(k, xs, ys, vxs, vys)
         if classifier is None:
             pred = self._trial_ctx.classifier_predict(xs, ys, self.clf[k].contiguous())
+            z = self._trial_ctx.classifier_logits(xs, ys, self.clf[k].contiguous())
         else:
             pred = classifier.predict(self._trial_ctx, (xs, ys, vxs, vys))
+            z = classifier.logits(self._trial_ctx, (xs, ys, vxs, vys))
         oc = res.outcome.cpu().numpy()
-        st = initfit.classification_stats(pred.cpu().numpy(), oc == _lib.TRIAL_SUCCESS)
+        st = initfit.classification_stats(pred.cpu().numpy(), oc == _lib.TRIAL_SUCCESS, z.cpu().numpy())
         tp, fp, fn, tn = st["tp"], st["fp"], st["fn"], st["tn"]
         nan = float("nan")
         return {
@@ -1284,6 +1316,7 @@ class SkillChainingAgent:
             "tp": tp, "fp": fp, "fn": fn, "tn": tn,
             "precision": st["precision"],
             "recall": st["recall"],
+            "log_loss": st["log_loss"],
             "success_in": tp / (tp + fp) if tp + fp else nan,
             "success_out": fn / (fn + tn) if fn + tn else nan,
             "outcomes": {name: int(np.sum(oc == code)) for code, name in OUTCOMES.items()},
@@ -1351,6 +1384,89 @@ class SkillChainingAgent:
         self.options[k].initiation_classifier.fit(xy.contiguous(), lab.contiguous(), iters=iters, lr=lr, l2=l2, warm_start=True)
         after = self.initiation_report(k, (xs, ys, vxs, vys))
         return before, after
+
+    def improve_initiation(self, options=None, states=None, n_states: int = 8192, iters: int = 400, lr: float = 3.0,
+                           l2: float = 1e-4, eval_epsilons=(0.0,), criterion: str = "discounted", z: float = 2.0, n_eval: int = 4096,
+                           seed: Optional[int] = None, interrupt: bool = False, choose: Optional[str] = None, apply: bool = False):
+        """A safeguarded refit of the initiation classifiers (SPEC §24.3), improve_policy's counterpart for in_k. (1) ONE
+        option_trials launch runs each of `options` (default: every enabled one) from `states` (as initiation_report draws or takes
+        them) under the shipped table; a trial that ends in SUCCESS labels its start positive. (2) Each row k is refitted on the
+        even-indexed states by initfit.refit_quadratic (iters, lr, l2); an option whose fit half holds one class only is skipped.
+        report["options"][i] holds "option", "n", "successes", "skipped" (None or the reason) and, on the odd-indexed states,
+        "shipped" and "refitted": initfit.classification_stats with the log-loss of the row's logits. (3) initfit.candidate_tables'
+        tables at each of `eval_epsilons` are evaluated in ONE evaluate_policies run of n_eval episodes each under the agent's W
+        (common start states and draws; `interrupt`, `choose` as for evaluate()). (4) initfit.choose_table decides at
+        eval_epsilons[0]. (5) One more trial launch on the same states under the table of every refitted row reports, in
+        report["fixed_point"], each option's success rate and outcomes next to those under the shipped table (a replaced row k
+        moves the target of k's children and the states k is tried from); no second refit. Returns (report, clf_chosen):
+        report["candidates"] rows of {"label", "epsilon", "summary", "paired"} (paired: against "shipped" at the same epsilon),
+        "chosen" (a label; "shipped" when nothing is accepted), "accepted", "criterion", "z"; clf_chosen a copy of the chosen
+        table. apply=True copies it into clf when accepted; refused on a sharded agent. ValueError for an option that is not
+        enabled, no epsilon, an unknown criterion, or more candidates x epsilons than a population holds. With apply=False the
+        agent is left as evaluate() leaves it."""
+        if apply and self.group is not None:
+            raise ValueError("improve_initiation(apply=True) is not available on a sharded agent")
+        if criterion not in ("discounted", "return", "success"):
+            raise ValueError(f"criterion must be 'discounted', 'return' or 'success', not {criterion!r}")
+        eps = [float(v) for v in eval_epsilons]
+        if not eps:
+            raise ValueError("improve_initiation needs at least one epsilon")
+        enabled = [k for k in range(1, self.n_options + 1) if (self.enabled_mask >> k) & 1]
+        opts = enabled if options is None else sorted({int(k) for k in options})
+        if not opts or any(k not in enabled for k in opts):
+            raise ValueError(f"options must name enabled options (enabled: {enabled}), not {opts}")
+        n_max = 1 + len(opts) + (1 if len(opts) >= 2 else 0)
+        if n_max * len(eps) > _lib.POP_MAX:
+            raise ValueError(f"{n_max} candidate tables x {len(eps)} epsilons are more than the {_lib.POP_MAX} policies of one population")
+        xs, ys, vxs, vys = self._start_states(states, n_states, 0 if seed is None else int(seed))
+        n, K = xs.numel(), len(opts)
+        opt_ids = torch.tensor(opts, dtype=torch.int32, device=xs.device).repeat_interleave(n)
+
+        def trial_outcomes(table):
+            """outcome [K][n] (host) of ONE launch: option opts[i] from every state, under `table`."""
+            res = self.option_trials(opt_ids, xs.repeat(K), ys.repeat(K), vxs.repeat(K), vys.repeat(K), seed=seed, clf=table)
+            return res.outcome.cpu().numpy().reshape(K, n)
+
+        oc = trial_outcomes(None)
+        tc = self._trial_ctx
+        rows, opt_rows = {}, []
+        for i, k in enumerate(opts):
+            ok = oc[i] == _lib.TRIAL_SUCCESS
+            rep = {"option": int(k), "n": int(n), "successes": int(ok.sum()), "skipped": None,
+                   "outcomes": {name: int(np.sum(oc[i] == code)) for code, name in OUTCOMES.items()}}
+            opt_rows.append(rep)
+            if ok[0::2].size == 0 or ok[0::2].all() or not ok[0::2].any():
+                rep["skipped"] = "the fit half holds one class only"
+                continue
+            w = initfit.refit_quadratic(tc, self.clf[k], torch.stack((xs[0::2], ys[0::2]), 1), torch.from_numpy(ok[0::2].copy()),
+                                        iters, lr, l2)
+            rows[k] = w
+            xh, yh = xs[1::2].contiguous(), ys[1::2].contiguous()
+            for name, w8 in (("shipped", self.clf[k].contiguous()), ("refitted", w)):
+                rep[name] = initfit.classification_stats(tc.classifier_predict(xh, yh, w8).cpu().numpy(), ok[1::2],
+                                                         tc.classifier_logits(xh, yh, w8).cpu().numpy())
+        tables = initfit.candidate_tables(self.clf, rows)
+        n_tab, per_eps = len(tables), len(eps)
+        stack = torch.stack([t for _, t in tables])
+        summaries, _, envs = self.evaluate_policies(self.W, np.repeat(np.asarray(eps, np.float32), n_tab), None, n_episodes=int(n_eval),
+                                                    seed=seed, interrupt=bool(interrupt), choose=choose, per_env=True,
+                                                    clf=stack.repeat(per_eps, 1, 1))
+        cands = [{"label": tables[i][0], "epsilon": eps[e], "summary": summaries[e * n_tab + i],
+                  "paired": paired_differences(envs[e * n_tab + i], envs[e * n_tab])} for e in range(per_eps) for i in range(n_tab)]
+        pick = initfit.choose_table(cands[:n_tab], criterion, z)
+        clf_chosen = dict(tables)[pick["chosen"]].clone()
+        fixed = None
+        if rows:                                               # the table of every refitted row: "all", or the one fitted k
+            oc2 = trial_outcomes(tables[-1][1])
+            fixed = [{"option": int(k), "table": tables[-1][0],
+                      "shipped": {"success_rate": float(np.mean(oc[i] == _lib.TRIAL_SUCCESS)), "outcomes": opt_rows[i]["outcomes"]},
+                      "refitted": {"success_rate": float(np.mean(oc2[i] == _lib.TRIAL_SUCCESS)),
+                                   "outcomes": {name: int(np.sum(oc2[i] == code)) for code, name in OUTCOMES.items()}}}
+                     for i, k in enumerate(opts)]
+        if apply and pick["accepted"]:
+            self.clf.copy_(clf_chosen)
+        return {"options": opt_rows, "candidates": cands, "chosen": pick["chosen"], "accepted": pick["accepted"],
+                "criterion": criterion, "z": float(z), "fixed_point": fixed}, clf_chosen
 
     def rollout(self, steps: int, learn: bool = True) -> None:
         for _ in range(steps):

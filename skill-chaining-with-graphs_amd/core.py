@@ -203,11 +203,14 @@ class ScgContext:
         return record.c_struct()
 
     def _chk_population(self, W: torch.Tensor, population) -> "_lib.Population":
-        """The scg_population of rollout(population=(epsilon, enabled)) (SPEC §21): C from W's leading dimension, n_per = n_envs // C."""
+        """The scg_population of rollout(population=(epsilon, enabled[, clf])) (SPEC §21): C from W's leading dimension, n_per = n_envs // C.
+        (§24.1's clf, checked here against that C, is no member of the struct: rollout passes it behind it.)"""
         try:
-            eps, enabled = population
+            eps, enabled, *rest = population
+            (pop_clf,) = rest or (None,)
         except (TypeError, ValueError):
-            raise ScgError("rollout: population must be a pair (epsilon, enabled) of [C] tensors, either may be None") from None
+            raise ScgError("rollout: population must be (epsilon, enabled) of [C] tensors, either may be None, optionally followed by "
+                           "a [C, n_vf, 8] classifier table") from None
         if not isinstance(W, torch.Tensor) or W.dim() != 4 or tuple(W.shape[1:]) != (self.n_vf, NUM_ACTIONS, NUM_FEATURES):
             raise ScgError(f"rollout: with a population W must be [C, {self.n_vf}, {NUM_ACTIONS}, {NUM_FEATURES}], "
                            f"got {tuple(getattr(W, 'shape', ()))}")
@@ -222,6 +225,11 @@ class ScgContext:
             # (the masks fit in a few bits: int32 holds the same words and is what most torch builds can fill and index)
             self._chk(enabled, torch.uint32 if getattr(enabled, "dtype", None) == getattr(torch, "uint32", None) else torch.int32,
                       n_pol, "population enabled")
+        if pop_clf is not None:
+            if not isinstance(pop_clf, torch.Tensor) or tuple(pop_clf.shape) != (n_pol, self.n_vf, CLF_STRIDE):
+                raise ScgError(f"rollout: the population's clf must be [{n_pol}, {self.n_vf}, {CLF_STRIDE}], "
+                               f"got {tuple(getattr(pop_clf, 'shape', ()))}")
+            self._chk(pop_clf, torch.float32, n_pol * self.n_vf * CLF_STRIDE, "population clf")
         return _lib.Population(n_pol, self.n_envs // n_pol, _ptr(eps), _ptr(enabled))
 
     def rollout(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, n_steps: int,
@@ -250,13 +258,17 @@ class ScgContext:
         `enabled_mask` for every policy), makes the launch a population rollout (scg_rollout_population, with whatever else was
         asked for): W is [C, n_vf, 5, 1296], and the envs c * n_per .. (c + 1) * n_per - 1, n_per = n_envs // C, act under W[c],
         epsilon[c] and enabled[c], their draws keyed by the env's index within its range: every policy sees the same start
-        states and the same draws, and its range equals by bits a rollout of n_per envs under that policy alone."""
+        states and the same draws, and its range equals by bits a rollout of n_per envs under that policy alone.
+        SPEC §24.1: `population` = (epsilon, enabled, clf) with clf a float32 [C, n_vf, 8] tensor on this device (or None) gives
+        every policy its own classifier table too (scg_rollout_population_clf): policy c reads clf[c] wherever the rollout reads
+        a classifier, and the `clf` argument is then no policy's."""
         if choose not in (None, "value"):
             raise ValueError(f"rollout: choose must be None or 'value', not {choose!r}")
         N = self.n_envs
-        pop = None
+        pop = pop_clf = None
         if population is not None:
             pop = self._chk_population(W, population)
+            pop_clf = population[2] if len(population) == 3 else None
         self._chk_operands(st, W, clf, 1 if pop is None else pop.n_policies)
         n_steps, t0 = int(n_steps), int(t0)
         if begin and begin_at:
@@ -314,8 +326,9 @@ class ScgContext:
         ints, ovr = (None if a is None else _ptr(a) for a in (interrupts, overrides))
         rc_ref = None if rc is None else C.byref(rc)
         if pop is not None:
-            name, tail = "scg_rollout_population", (ints, ovr, rc_ref, C.c_uint32(rules), None if au is None else C.byref(au),
-                                                    _ptr(first_action))
+            name = "scg_rollout_population" if pop_clf is None else "scg_rollout_population_clf"
+            tail = (ints, ovr, rc_ref, C.c_uint32(rules), None if au is None else C.byref(au),
+                    _ptr(first_action))
         elif first_action is not None:
             name, tail = "scg_rollout_branch", (ints, ovr, rc_ref, C.c_uint32(rules), None if au is None else C.byref(au),
                                                 _ptr(first_action))
@@ -332,7 +345,7 @@ class ScgContext:
         self._call(name, _ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id), _ptr(st.opt_steps), _ptr(st.ep_steps),
                    _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done), _ptr(W), _ptr(clf), C.c_uint32(enabled_mask),
                    C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags), None if cs is None else C.byref(cs), *tail, self._stream(),
-                   *(() if pop is None else (C.byref(pop),)))
+                   *(() if pop is None else (C.byref(pop),)), *(() if pop_clf is None else (_ptr(pop_clf),)))
         if stats is not None and interrupt and interrupts is stats.interrupts:
             stats.interrupting = True
 
@@ -712,6 +725,17 @@ class ScgContext:
         out = torch.empty(n, dtype=torch.uint8, device=self.device)
         self._call("scg_classifier_predict", n, _ptr(x), _ptr(y), _ptr(w8), _ptr(out), self._stream())
         return out
+
+    def classifier_logits(self, x: torch.Tensor, y: torch.Tensor, w8: torch.Tensor) -> torch.Tensor:
+        """SPEC §24.2: the float32 value whose sign classifier_predict tests, by the same device function."""
+        n = x.numel()
+        self._chk(x, torch.float32, n, "x"); self._chk(y, torch.float32, n, "y")
+        self._chk(w8, torch.float32, CLF_STRIDE, "w8")
+        z = torch.empty(n, dtype=torch.float32, device=self.device)
+        if n == 0:                                             # (an empty tensor has no address to pass)
+            return z
+        self._call("scg_classifier_logits", n, _ptr(x), _ptr(y), _ptr(w8), _ptr(z), self._stream())
+        return z
 
     def fit_initiation(self, xy: torch.Tensor, label: torch.Tensor, offsets: torch.Tensor, w: torch.Tensor,
                        iters: int = 200, lr: float = 1.0, l2: float = 1e-4) -> None:

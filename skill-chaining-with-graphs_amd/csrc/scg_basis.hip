@@ -59,3 +59,9 @@ hipError_t launch_basis_values(int order, int64_t n, const float *const *st, con
     return order == 3 ? launch_values_order<3>(n, st, V, m, out, s)
          : order == 5 ? launch_values_order<5>(n, st, V, m, out, s) : launch_values_order<7>(n, st, V, m, out, s);
 }
+
+// SPEC §24.2
+hipError_t launch_classifier_logits(int n, const float *x, const float *y, const float *w8, float *z, hipStream_t s) {
+    hipLaunchKernelGGL((classifier_logits_kernel<LOGISTIC_THREADS>), dim3((n + LOGISTIC_THREADS - 1) / LOGISTIC_THREADS), dim3(LOGISTIC_THREADS), 0, s, n, x, y, w8, z);
+    return hipGetLastError();
+}

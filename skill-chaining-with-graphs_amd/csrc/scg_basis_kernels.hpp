@@ -5,6 +5,7 @@
 //   basis_values_kernel     out[r][n] = sum_f V[r][f] phi_f(s_n) for r < m <= 8 in §18.3's order: per c12 an fma chain T over c34 from +0,
 //                           the T added in c12 order from +0. phi is formed in registers, never stored.
 //   logistic_terms_kernel   SPEC §23.1: p = sigmoid_spec(z), e = l - p, rw = sqrt(p (1 - p)) per sample, every step one binary32 operation
+//   classifier_logits_kernel  SPEC §24.2: z = clf_z(w8, x, y) per point, the value whose sign predict_kernel (scg_aux_kernels.hpp) tests
 #pragma once
 
 // grid-stride launches on stream s (scg_basis.hip); st = {x, y, vx, vy}. The Gram launches read G.s[0] only.
@@ -15,6 +16,7 @@ hipError_t launch_basis_values(int order, int64_t n, const float *const *st, con
 hipError_t launch_basis_gram_irls_3(const GramArgs &G, int n_active, hipStream_t s);      // SPEC §23.2: G.rw, G.yv = e, G.b = grad
 hipError_t launch_basis_gram_irls_7(const GramArgs &G, int n_active, hipStream_t s);
 hipError_t launch_logistic_terms(int64_t n, const float *z, const uint8_t *label, float *p, float *rw, float *e, hipStream_t s);
+hipError_t launch_classifier_logits(int n, const float *x, const float *y, const float *w8, float *z, hipStream_t s);      // n >= 1
 
 constexpr int BASIS_VALUES_SAMPLES = 8;              // samples a wavefront of basis_values_kernel takes at once: a weight is loaded once for all of them
 
@@ -122,4 +124,12 @@ __global__ __launch_bounds__(THREADS) void logistic_terms_kernel(int64_t n, cons
         rw[i] = sqrtf(sv);
         e[i] = l - pv;
     }
+}
+
+// SPEC §24.2: predict_kernel's launch shape and its one call of clf_z (SPEC §4.1's chain), stored before the comparison. (A template as
+// the one above, so that scg_basis.hip alone holds its code.)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void classifier_logits_kernel(int n, const float *x, const float *y, const float *w8, float *z) {
+    const int e = blockIdx.x * THREADS + threadIdx.x;
+    if (e < n) z[e] = clf_z(w8, x[e], y[e]);
 }

@@ -20,13 +20,14 @@
 //   scg_gram_kernel.hpp      SPEC §16.1's feature Gram, §20.1's with up to 16 right-hand sides, §22.1's weighted one and §17.1's cross-feature Gram, one kernel
 //                            template (and §23.2's IRLS mode of it): here only its arguments and the five launches (its instantiations are
 //                            compiled in scg_gram.hip)
-//   scg_basis_kernels.hpp    SPEC §18's basis-order probe and §23's logistic terms and IRLS Gram at the orders 3 and 7: here only the
-//                            launches (compiled in scg_basis.hip)
+//   scg_basis_kernels.hpp    SPEC §18's basis-order probe, §23's logistic terms and IRLS Gram at the orders 3 and 7 and §24.2's
+//                            classifier logits: here only the launches (compiled in scg_basis.hip)
 // scg_rollout_variants.hip is the second translation unit: every other instantiation of rollout_kernel (SPEC §10's record, §11's
 // interruption, §14's value-ranked choice, §15's audit: the table in scg_rollout_kernel.hpp) and trial_kernel<true>, reached through
 // launch_rollout<REC, Args> / launch_trial_record, which the two kernel headers declare.
 // scg_rollout_population.hip is a unit of the same kind: SPEC §21's four population instantiations of rollout_kernel,
-// reached through the same launch_rollout<REC, Args>.
+// reached through the same launch_rollout<REC, Args>; with SPEC §24.1's pop_clf the same four stage a classifier table per policy
+// (DESIGN §3.29).
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -685,15 +686,18 @@ struct RolloutCall {
     const scg_audit *audit;
     const uint8_t *first_action;   // scg_rollout_branch (SPEC §19)
     const scg_population *pop;     // scg_rollout_population (SPEC §21)
+    const float *pop_clf;          // scg_rollout_population_clf (SPEC §24.1): [C][n_vf][8], a classifier table per policy
 };
 
-// the seven rollout entry points (`fn` names the caller in error texts). The kernel follows from what the call asks for:
+// the eight rollout entry points (`fn` names the caller in error texts). The kernel follows from what the call asks for:
 //   audit      a member of `audit` given (SPEC §15; every member NULL counts as no audit), or a first_action (SPEC §19: the AUDIT
 //              kernels are the ones that read it; with no audit member they write nothing of the audit's)
 //   best, intr SCG_SELECT_BEST / SCG_SELECT_INTERRUPT in `rules` (SPEC §14 / §11), counting into `overrides` / `interrupts`
 //   rec, at    a record (SPEC §10) / SCG_ROLLOUT_BEGIN_AT, from here on BEGIN in `flags` plus `at`
 //   pop        a population (SPEC §21): a RolloutPop by (intr, best), whatever else the call asks for (they are AUDIT kernels, and with
 //              no audit member and no first_action they write nothing of either), on a grid of whole workgroups per policy
+//   pop_clf    a classifier table per policy (SPEC §24.1): the same RolloutPop kernels, which then stage pop_clf[c] where they staged
+//              `clf`; refused without pop, behind every other refusal
 // Neither audit, best, rec, at nor pop: the plain kernel, or with intr the non-recording interrupting one; otherwise a RolloutVar by
 // (intr, best, audit)
 static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
@@ -749,6 +753,7 @@ static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
     int epw;
     if (!rollout_epw(c, c->cfg.n_envs, epw)) return fail_in(c, SCG_ERR_INVALID, fn, "SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
     R.epw = epw;
+    if (a.pop_clf && !a.pop) return fail_in(c, SCG_ERR_INVALID, fn, "pop_clf without pop");      // SPEC §24.1: the last refusal
     const int wgs_per_pol = a.pop ? (a.pop->n_per + RO_WAVES * epw - 1) / (RO_WAVES * epw) : 0;
     const int grid = a.pop ? a.pop->n_policies * wgs_per_pol : (c->cfg.n_envs + RO_WAVES * epw - 1) / (RO_WAVES * epw);
     const hipStream_t s = reinterpret_cast<hipStream_t>(a.stream);
@@ -768,7 +773,7 @@ static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
     if (a.pop) {
         auto P = derived_args<RolloutPopArgs>(V);
         P.n_pol = a.pop->n_policies; P.n_per = a.pop->n_per; P.wgs_per_pol = wgs_per_pol;
-        P.pol_eps = a.pop->epsilon; P.pol_enabled = a.pop->enabled;
+        P.pol_eps = a.pop->epsilon; P.pol_enabled = a.pop->enabled; P.pol_clf = a.pop_clf;
         switch ((best ? 2 : 0) | (intr ? 1 : 0)) {
         case 0: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutPop<false, false>>(P), grid, s); break;
         case 1: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutPop<true, false>>(P), grid, s); break;
@@ -861,9 +866,21 @@ int scg_rollout_population(scg_ctx *c, float *x, float *y, float *vx, float *vy,
                            uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
                            const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action, void *stream,
                            const scg_population *pop) {
-    return rollout_launch("scg_rollout_population", c, {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf,
-                                                        enabled_mask, t0, n_steps, flags, stats, stream, true, rec, interrupts, overrides,
-                                                        rules, audit, first_action, pop});
+    return scg_rollout_population_clf(c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf, enabled_mask,
+                                      t0, n_steps, flags, stats, interrupts, overrides, rec, rules, audit, first_action, stream, pop,
+                                      nullptr);
+}
+
+// pop_clf = NULL: scg_rollout_population's launch (and its name in error texts: they are one entry point with and without the table)
+int scg_rollout_population_clf(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                               int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                               const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                               uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                               const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action, void *stream,
+                               const scg_population *pop, const float *pop_clf) {
+    return rollout_launch(pop_clf ? "scg_rollout_population_clf" : "scg_rollout_population", c,
+                          {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf, enabled_mask, t0, n_steps, flags,
+                           stats, stream, true, rec, interrupts, overrides, rules, audit, first_action, pop, pop_clf});
 }
 
 static int trials_launch(const char *fn, scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,
@@ -1481,6 +1498,17 @@ int scg_classifier_predict(scg_ctx *c, int32_t n, const float *x, const float *y
     hipLaunchKernelGGL(predict_kernel, dim3((n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        n, x, y, w8, out);
     SCG_HIP(c, hipGetLastError());
+    return SCG_OK;
+}
+
+// SPEC §24.2: predict_kernel's clf_z before the comparison (the kernel: scg_basis_kernels.hpp); scg_classifier_predict's checks in its sequence
+int scg_classifier_logits(scg_ctx *c, int32_t n, const float *x, const float *y, const float *w8, float *z, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_classifier_logits: null ctx");
+    if (n < 0 || !x || !y || !w8 || !z) return fail(c, SCG_ERR_INVALID, "scg_classifier_logits: bad argument");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_classifier_logits");
+    if (n == 0) return SCG_OK;
+    SCG_HIP(c, launch_classifier_logits(n, x, y, w8, z, reinterpret_cast<hipStream_t>(stream)));
     return SCG_OK;
 }
 

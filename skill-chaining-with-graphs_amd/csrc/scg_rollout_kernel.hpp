@@ -60,6 +60,8 @@ struct RolloutArgs {
 //   true   RolloutPop<I, B>                   scg_rollout_population         SPEC §21: the AUDIT kernels over C env ranges of n_per envs, each with
 //          (all four I, B; AUDIT)             (pop given)                    its own W, epsilon and enabled mask; a workgroup serves one range, and
 //                                                                            the draws are keyed by the env's index within its range
+//                                             scg_rollout_population_clf     SPEC §24.1: the same four kernels; with pop_clf a classifier table per
+//                                             (pop given)                    range too, staged once per launch in place of `clf`
 // Every REC instantiation shares ONE argument layout, RolloutVarArgs (the population's members lie behind it); the
 // non-recording interrupting kernel keeps its own, because `interrupts` at another offset changes its code.
 struct RolloutIntArgs : RolloutArgs {
@@ -86,6 +88,7 @@ struct RolloutPopArgs : RolloutVarArgs {
     int32_t wgs_per_pol;           // ceil(n_per / (RO_WAVES * epw)): a workgroup never straddles two policies
     const float *pol_eps;          // [n_pol], null: epsilon for every policy
     const uint32_t *pol_enabled;   // [n_pol], null: enabled for every policy
+    const float *pol_clf;          // [n_pol][n_vf][8], null: clf for every policy (SPEC §24.1; the LAST member: every offset above holds)
 };                                 // (W: [n_pol][n_vf][5][1296])
 template <bool I, bool B>
 struct RolloutPop : RolloutPopArgs {
@@ -193,7 +196,11 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
         s_w0[i] = in ? Wp[src] : 0.0f;
     }
     for (int i = tid; i < A.ms.n_edges * 8; i += RO_THREADS) s_edges[i] = A.edges[i];
-    if (tid < A.n_vf * CLF_STRIDE) s_clf[tid] = A.clf[tid];
+    const float *clfp = A.clf;                                 // POP (SPEC §24.1): the workgroup's policy's table (workgroup-uniform)
+    if constexpr (POP) {
+        if (A.pol_clf) clfp = A.pol_clf + (size_t)pol * A.n_vf * CLF_STRIDE;
+    }
+    if (tid < A.n_vf * CLF_STRIDE) s_clf[tid] = clfp[tid];
     if (tid < 2 * MAX_VF) (&s_cnt[0][0])[tid] = 0;
     __syncthreads();
 

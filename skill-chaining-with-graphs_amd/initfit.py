@@ -1,7 +1,9 @@
 """SPEC §23.3: a Fourier-basis initiation classifier fitted by IRLS — logistic regression on the basis of order p, a Newton iteration
 whose Hessian is the weighted feature Gram and whose gradient is the unweighted moment of the same samples (ScgContext.
 basis_gram_irls, on the terms of ScgContext.logistic_terms). Host code, float64; the hot parts are those two calls and
-ScgContext.basis_values. A reporting instrument (SPEC §18's sense): nothing acts or learns with such a classifier."""
+ScgContext.basis_values. A reporting instrument (SPEC §18's sense): nothing acts or learns with such a classifier.
+SPEC §24.3, at the end: the parts of SkillChainingAgent.improve_initiation — §6's quadratic refitted on trial labels
+(refit_quadratic), the candidate classifier tables (candidate_tables) and §21.4's rule over them (choose_table)."""
 from typing import Optional
 
 import numpy as np
@@ -166,3 +168,53 @@ def classification_stats(pred, outcome, z=None) -> dict:
         z = np.asarray(z).astype(np.float64).reshape(-1)
         out["log_loss"] = float(np.mean(np.logaddexp(0.0, z) - np.where(s, z, 0.0)))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- SPEC §24.3: the safeguarded refit step
+
+def refit_quadratic(ctx, w8, xy, label, iters: int = 400, lr: float = 3.0, l2: float = 1e-4) -> torch.Tensor:
+    """SPEC §6's fit (scg_fit_initiation) of ONE row, started from a copy of `w8`, on the examples xy [M][2] with `label` [M]
+    (non-zero: positive), on `ctx`. Returns the new row (float32 [8] on ctx's device); `w8` itself is never written."""
+    w = torch.as_tensor(w8, dtype=torch.float32).to(ctx.device).reshape(-1).clone().contiguous()
+    xy = torch.as_tensor(xy, dtype=torch.float32).to(ctx.device).contiguous().view(-1)
+    lab = (torch.as_tensor(label).to(ctx.device).view(-1) != 0).to(torch.uint8).contiguous()
+    off = torch.tensor([0, lab.numel()], dtype=torch.int32, device=ctx.device)
+    ctx.fit_initiation(xy, lab, off, w, iters, lr, l2)
+    return w
+
+
+def candidate_tables(clf, rows: dict) -> list:
+    """The candidate classifier tables of improve_initiation, a pure function: `clf` the shipped table [n_vf][8], `rows` {k: w8} the
+    refitted rows. Returns [(label, table)]: "shipped" first (a copy of clf), then "k" for each fitted k, ascending, with row k alone
+    replaced, then "all" (every fitted row replaced) when two or more rows were fitted. Neither input is written."""
+    clf = torch.as_tensor(clf)
+    ks = sorted(int(k) for k in rows)
+    if any(not (0 <= k < clf.shape[0]) for k in ks):
+        raise ValueError(f"candidate_tables: a fitted row is outside the table's {clf.shape[0]} rows")
+
+    def with_rows(which):
+        t = clf.clone()
+        for k in which:
+            t[k] = torch.as_tensor(rows[k], dtype=clf.dtype).to(clf.device).reshape(clf.shape[1:])
+        return t
+
+    out = [("shipped", with_rows(()))] + [(str(k), with_rows((k,))) for k in ks]
+    if len(ks) >= 2:
+        out.append(("all", with_rows(ks)))
+    return out
+
+
+def choose_table(candidates, criterion: str = "discounted", z: float = 2.0) -> dict:
+    """SPEC §21.4's rule over labelled candidates [{"label", "summary", "paired"}], "shipped" first and `paired` against it: the
+    candidate with the highest mean of `criterion`, ties to the earlier, a NaN mean never; accepted only where its paired mean
+    difference against "shipped" exceeds z standard errors (se = 0: where it exceeds 0). valuefit.choose_candidate decides: a
+    candidate's position stands in for its lambda, so "shipped" (position 0) is the table that is kept. Returns {"index", "label"
+    (of the pick; None when every mean is a NaN), "chosen" ("shipped" unless accepted), "accepted"}."""
+    from .valuefit import choose_candidate
+    cands = list(candidates)
+    if not cands or cands[0]["label"] != "shipped":
+        raise ValueError("choose_table: the first candidate must be 'shipped'")
+    pick = choose_candidate([{"lambda": float(i), "summary": c["summary"], "paired": c["paired"]} for i, c in enumerate(cands)],
+                            criterion, z)
+    label = None if pick["index"] is None else cands[pick["index"]]["label"]
+    return {"index": pick["index"], "label": label, "chosen": label if pick["accepted"] else "shipped", "accepted": pick["accepted"]}

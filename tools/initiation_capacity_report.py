@@ -4,8 +4,8 @@ states — (a) free positions at rest, (b) full states with their velocities, dr
 which the episode went on — and on each set these classifiers are fitted on the even-indexed states and judged on the odd-indexed
 ones: the shipped in_k (SPEC §4.1, as discovered: not refitted), SPEC §6's quadratic refitted on the same labels from the shipped row
 (scg_fit_initiation), and SkillChainingAgent.fit_initiation_fourier with "position" features at the orders 3 / 5 / 7 and "state"
-features at the orders 3 / 5. One line per classifier: held-out accuracy, precision, recall, log-loss (Fourier classifiers only: the
-quadratic's logits are not read back), the fit half's accuracy, and the fit's iterations and reason. Nothing acts with a fitted
+features at the orders 3 / 5. One line per classifier: held-out accuracy, precision, recall, log-loss (the quadratics' from
+ScgContext.classifier_logits, SPEC §24.2), the fit half's accuracy, and the fit's iterations and reason. Nothing acts with a fitted
 classifier: every trial ran with the shipped in_k.
 
     python tools/initiation_capacity_report.py [--maps pinball_simple pinball_maze] [--seeds 1 2] [--envs 8192] [--options 5] [--states 8192]
@@ -36,21 +36,24 @@ def fmt_row(name, held, fit, extra=""):
 
 
 def quadratic_refit(ag, k, rep, iters, lr, l2):
-    """SPEC §6's fit of one row on the even-indexed states' labels, from the shipped row, on the trial context: (held-out, fit-half)
-    classification_stats of the refitted quadratic. clf is not written."""
+    """SPEC §6's fit of one row on the even-indexed states' labels, from the shipped row, on the trial context
+    (initfit.refit_quadratic): (held-out, fit-half) classification_stats of the refitted quadratic. clf is not written."""
     import torch
     from skill_chaining_with_graphs_amd import _lib, initfit
-    tc = ag._trial_ctx
     xs, ys = rep["states"][0], rep["states"][1]
     ok = (rep["trials"].outcome == _lib.TRIAL_SUCCESS)
-    xy = torch.stack((xs[0::2], ys[0::2]), 1).contiguous()
-    lab = ok[0::2].to(torch.uint8).contiguous()
-    w = ag.clf[k].clone().contiguous()
-    off = torch.tensor([0, lab.numel()], dtype=torch.int32, device=w.device)
-    tc.fit_initiation(xy.view(-1), lab, off, w, iters, lr, l2)
-    pred = tc.classifier_predict(xs, ys, w).cpu().numpy()
-    okh = ok.cpu().numpy()
-    return initfit.classification_stats(pred[1::2], okh[1::2]), initfit.classification_stats(pred[0::2], okh[0::2])
+    w = initfit.refit_quadratic(ag._trial_ctx, ag.clf[k], torch.stack((xs[0::2], ys[0::2]), 1), ok[0::2], iters, lr, l2)
+    return quadratic_stats(ag, w, xs, ys, ok.cpu().numpy())
+
+
+def quadratic_stats(ag, w8, xs, ys, ok):
+    """(held-out, fit-half) classification_stats of the row w8 on the states (xs, ys), its log-loss from its logits (SPEC §24.2)."""
+    from skill_chaining_with_graphs_amd import initfit
+    tc = ag._trial_ctx
+    w8 = w8.contiguous()
+    pred = tc.classifier_predict(xs, ys, w8).cpu().numpy()
+    z = tc.classifier_logits(xs, ys, w8).cpu().numpy()
+    return initfit.classification_stats(pred[1::2], ok[1::2], z[1::2]), initfit.classification_stats(pred[0::2], ok[0::2], z[0::2])
 
 
 def option_lines(ag, k, states, a):
@@ -60,8 +63,7 @@ def option_lines(ag, k, states, a):
     out = [f"    option {k}: {rep['n']} states, {int(ok.sum())} successes ({ok.mean():.4f}); outcomes {rep['outcomes']}"]
     if ok[0::2].all() or not ok[0::2].any():
         return out + ["      the fit half holds one class only: nothing to fit"]
-    pred = rep["predicted"].cpu().numpy()
-    out.append(fmt_row("shipped in_k", initfit.classification_stats(pred[1::2], ok[1::2]), initfit.classification_stats(pred[0::2], ok[0::2])))
+    out.append(fmt_row("shipped in_k", *quadratic_stats(ag, ag.clf[k], rep["states"][0], rep["states"][1], ok)))
     held, fit = quadratic_refit(ag, k, rep, a.iters, a.lr, a.l2)
     out.append(fmt_row("quadratic refitted", held, fit, f"({a.iters} iterations of scg_fit_initiation)"))
     for features, order in FOURIER:

@@ -9,10 +9,13 @@ else: value-ranked choice (SPEC §14, scg_rollout_select) against scg_rollout_re
 sibling tree of tools/choice_report.py (bench_choose). --audit times the audited rollout (SPEC §15, scg_rollout_audit, keeping the
 discounted return) against scg_rollout_select with the same rules, record and launches (bench_audit). --population C times a
 population rollout (SPEC §21, scg_rollout_population) of C policies x 4096 envs against C sequential audited rollouts of 4096 envs
-and against one audited rollout of C x 4096 envs under a single weight table (bench_population).
+and against one audited rollout of C x 4096 envs under a single weight table (bench_population). --population-clf C times the same
+population launch with a classifier table per policy (SPEC §24.1, scg_rollout_population_clf) against the launch without one
+(bench_population_clf), and --logits scg_classifier_logits against scg_classifier_predict at 65 536 points (bench_logits); both
+print each arm's min - max over the rounds beside the ratio.
 
     python tools/rollout_bench.py [--sizes 4096 65536] [--k 64] [--rounds 7] [--epw 2 4 8 16 32] [--record none 1024 all]
-                                  [--interrupt] [--choose] [--audit] [--population 1 4 8 16]
+                                  [--interrupt] [--choose] [--audit] [--population 1 4 8 16] [--population-clf 1 4 8 16] [--logits]
 """
 import argparse
 import json
@@ -244,6 +247,76 @@ def bench_population(n_pol, k, rounds, n_per=4096, n_opt=5):
             "single_table_rounds_us": [round(v, 2) for v in side["one"]["us"]]}
 
 
+def _arm(us):
+    """median and [min, max] of an arm's rounds."""
+    import numpy as np
+    return round(float(np.median(us)), 2), [round(float(min(us)), 2), round(float(max(us)), 2)]
+
+
+def bench_population_clf(n_pol, k, rounds, n_per=4096, n_opt=5):
+    """µs per step of the population rollout of bench_population with a classifier table per policy (the chain's discs, their radii
+    scaled by 1 - 0.02 c for policy c) against the same launch without one (every policy reads `clf`, the chain's discs), each on a
+    state of its own, timed alternately. What the per-workgroup staging of pop_clf[c] costs."""
+    import torch
+    import skill_chaining_with_graphs_amd as scg
+    from skill_chaining_with_graphs_amd.core import ScgContext
+    from skill_chaining_with_graphs_amd.evaluation import GateAudit
+    m = scg.load_map("pinball_simple")
+    n = n_pol * n_per
+    ctx = ScgContext(n, n_opt, m, device=0, seed=7, epsilon=0.05, max_episode_steps=2000)
+    mask = ((1 << (n_opt + 1)) - 1) & ~1
+    clf = torch.as_tensor(rig.chain_classifiers(m, n_opt), device=ctx.device)
+    tabs = clf.reshape(1, n_opt + 1, 8).repeat(n_pol, 1, 1)
+    shrink = (1.0 - 0.02 * torch.arange(n_pol, dtype=torch.float32, device=ctx.device)) ** 2
+    # a disc's row is [r^2 - |c|^2, 2 cu, 2 cv, -1, 0, -1] in (u, v) = 2 (x, y) - 1: scaling r changes its constant alone
+    r2 = tabs[:, 1:, 0] + (tabs[:, 1:, 1] ** 2 + tabs[:, 1:, 2] ** 2) / 4
+    tabs[:, 1:, 0] += r2 * (shrink[:, None] - 1.0)
+    tabs = tabs.contiguous()
+    g = torch.Generator().manual_seed(3)
+    W = (torch.randn((n_pol, n_opt + 1, 5, 1296), generator=g) * 1e-3).to(ctx.device)
+    eps = torch.full((n_pol,), 0.05, dtype=torch.float32, device=ctx.device)
+    enabled = torch.full((n_pol,), mask, dtype=torch.int32, device=ctx.device)
+    side = {name: {"st": rig.state_on(ctx, m, n), "au": GateAudit(n, ctx.device), "t": 0, "us": []} for name in ("pop", "clf")}
+
+    def roll(name):
+        s = side[name]
+        ctx.rollout(s["st"], W, clf.view(-1), mask, s["t"], k, audit=s["au"], population=(eps, enabled) + ((tabs,) if name == "clf" else ()))
+        s["t"] += k
+
+    for name in side:
+        roll(name); roll(name)
+    for _ in range(rounds):
+        for name in side:
+            side[name]["us"].append(rig.timed(lambda: roll(name), 3) * 1e6 / k)
+    (pop, pop_mm), (pc, pc_mm) = _arm(side["pop"]["us"]), _arm(side["clf"]["us"])
+    return {"policies": n_pol, "n_per": n_per, "k": k, "options": n_opt, "population_us_per_step": pop, "population_min_max_us": pop_mm,
+            "population_clf_us_per_step": pc, "population_clf_min_max_us": pc_mm, "clf_over_population": round(pc / pop, 4),
+            "population_rounds_us": [round(v, 2) for v in side["pop"]["us"]], "population_clf_rounds_us": [round(v, 2) for v in side["clf"]["us"]]}
+
+
+def bench_logits(rounds, n=65536):
+    """µs per call of scg_classifier_logits against scg_classifier_predict on n points and one row, timed alternately (100 calls a round)."""
+    import torch
+    import skill_chaining_with_graphs_amd as scg
+    from skill_chaining_with_graphs_amd.core import ScgContext
+    m = scg.load_map("pinball_simple")
+    ctx = ScgContext(n, 1, m, device=0, seed=7)
+    g = torch.Generator().manual_seed(3)
+    x, y = (torch.rand(n, generator=g).to(ctx.device) for _ in range(2))
+    w8 = torch.as_tensor(rig.chain_classifiers(m, 1)[1], device=ctx.device).contiguous()
+    arms = {"predict": lambda: ctx.classifier_predict(x, y, w8), "logits": lambda: ctx.classifier_logits(x, y, w8)}
+    us = {name: [] for name in arms}
+    for fn in arms.values():
+        rig.timed(fn, 20)
+    for _ in range(rounds):
+        for name, fn in arms.items():
+            us[name].append(rig.timed(fn, 100) * 1e6)
+    (p, p_mm), (l, l_mm) = _arm(us["predict"]), _arm(us["logits"])
+    return {"points": n, "predict_us_per_call": p, "predict_min_max_us": p_mm, "logits_us_per_call": l, "logits_min_max_us": l_mm,
+            "logits_over_predict": round(l / p, 4), "predict_rounds_us": [round(v, 2) for v in us["predict"]],
+            "logits_rounds_us": [round(v, 2) for v in us["logits"]]}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--sizes", type=int, nargs="+", default=[4096, 65536])
@@ -260,7 +333,16 @@ def main():
                     help="instead: the audited rollout (SPEC §15) against scg_rollout_select, for the four rules, on the sibling tree")
     ap.add_argument("--population", type=int, nargs="+", default=None,
                     help="instead: a population rollout (SPEC §21) of C policies x 4096 envs against C sequential audited rollouts and one of C x 4096 envs")
+    ap.add_argument("--population-clf", type=int, nargs="+", default=None,
+                    help="instead: the population rollout with a classifier table per policy (SPEC §24.1) against the same launch without one")
+    ap.add_argument("--logits", action="store_true", help="instead (or after --population-clf): scg_classifier_logits against scg_classifier_predict at 65 536 points")
     a = ap.parse_args()
+    if a.population_clf or a.logits:
+        for c in a.population_clf or []:
+            print(json.dumps(bench_population_clf(c, a.k, a.rounds)), flush=True)
+        if a.logits:
+            print(json.dumps(bench_logits(a.rounds)), flush=True)
+        return
     if a.population:
         for c in a.population:
             print(json.dumps(bench_population(c, a.k, a.rounds)), flush=True)
