@@ -351,6 +351,30 @@ int scg_rollout_population_clf(scg_ctx *ctx, float *x, float *y, float *vx, floa
                                const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action,
                                void *stream, const scg_population *pop, const float *pop_clf);
 
+/* ---- population rollouts with a gate table per policy (SPEC §25.1) ----
+ * scg_rollout_population_gate is scg_rollout_population_clf plus `pop_gate`. pop_gate = NULL is scg_rollout_population_clf, which
+ * forwards here: the same kernels, the same results.
+ * pop_gate is a DEVICE array [C][n_vf][2][5][1296]. For option k >= 1, pop_gate[c][k][0] is the OPTION side and pop_gate[c][k][1]
+ * the ROOT side of policy c's value gate for k; row k = 0 is never read. With it §4.2's line reads
+ *     declined = entering && !(Vg_opt >= Vg_root),   Vg_opt = max_a Q(s_next, a) under pop_gate[c][cand][0],
+ *                                                     Vg_root = the same under pop_gate[c][cand][1],
+ * both in §3.1's evaluation order and §5's max order; a NaN side declines. NOTHING else changes: an entered env's qcache is
+ * Q_cand(s_next, .) under W[c], a declined env's Q_0(s_next, .) under W[c]; candidate selection, stay / re-offer, keep / success /
+ * termination and the actions are as before; §15's force still replaces the gate's result, and §15's begin outputs v_cand / v_root
+ * of an offered env, "the values the gate reads", are Vg_opt / Vg_root.
+ * The identity: with pop_gate[c][k][0] = W[c][k] and pop_gate[c][k][1] = W[c][0] every output equals scg_rollout_population_clf's by
+ * bits.
+ * Errors: scg_rollout_population_clf's, in its sequence; after them SCG_ERR_INVALID (nothing launched, nothing written), in this
+ * order: a non-NULL pop_gate with pop == NULL; a non-NULL pop_gate with SCG_SELECT_INTERRUPT or SCG_SELECT_BEST in `rules` (a
+ * gated interruption and a gated value-ranked choice are out of scope). The write set is scg_rollout_population's; pop_gate is
+ * never written. Results do not depend on the launch geometry or the block build; no asynchronous failure bit is raised. */
+int scg_rollout_population_gate(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                                int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                                const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                                uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                                const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action,
+                                void *stream, const scg_population *pop, const float *pop_clf, const float *pop_gate);
+
 /* Device pointers of the ctx-owned reduced gradient G[n_vf][5][1296] and counts n_k[n_vf] (int32)
  * left by the last scg_step(LEARN) — the buffers a multi-rank caller all-reduces (SPEC §5). */
 int scg_grad_buffers(scg_ctx *ctx, float **G, int32_t **n_k);

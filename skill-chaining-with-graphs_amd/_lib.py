@@ -182,6 +182,8 @@ _SIGS = {
                                             C.POINTER(Population)]),
     "scg_rollout_population_clf": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, C.POINTER(Audit), _P, _P,
                                                 C.POINTER(Population), _P]),
+    "scg_rollout_population_gate": (C.c_int, _ROLLOUT + [_P, _P, C.POINTER(Record), C.c_uint32, C.POINTER(Audit), _P, _P,
+                                                 C.POINTER(Population), _P, _P]),
     "scg_grad_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "scg_set_grad_buffers": (C.c_int, [_P, _P, _P]),
     "scg_apply_update": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -73,6 +73,9 @@ class SkillChainingAgent:
         self.W = torch.zeros((self.n_vf, NUM_ACTIONS, NUM_FEATURES), dtype=torch.float32, device=dev)
         self.clf = torch.zeros((self.n_vf, CLF_STRIDE), dtype=torch.float32, device=dev)
         self.enabled_mask = 0
+        # SPEC §25.3: the gate table evaluate() / evaluate_policies() act under by default ([n_vf, 2, 5, 1296], gatefit), or None for
+        # §4.2's own comparison; stored by improve_gate(apply=True). The learner and every other kernel ignore it; not in state_dict()
+        self.gate = None
         self.gest_mask = 0            # SPEC §4.4: options in gestation
         self._gest_need = {}
         self.t = 0
@@ -458,7 +461,7 @@ class SkillChainingAgent:
 
     def evaluate(self, n_episodes: int = 4096, epsilon: float = 0.0, seed: Optional[int] = None, steps_per_launch: int = 64,
                  per_env: bool = False, states=None, interrupt: bool = False, choose: Optional[str] = None,
-                 discounted: bool = False):
+                 discounted: bool = False, gate="agent"):
         """How good the current policy is: one episode per env on `n_episodes` envs of a separate evaluation context (cached per
         n_episodes; another seed replaces the entry), acting with `epsilon` and the current W, clf and enabled options, weights
         frozen (SPEC §8). Returns
@@ -476,9 +479,19 @@ class SkillChainingAgent:
         lowest-numbered one (SPEC §14; ValueError for any other value); the summary then also holds overrides per option: the
         entries of an option that was not the lowest-numbered candidate. It combines with `interrupt`.
         With `discounted` the launches also keep each episode's discounted task return (SPEC §15's audited rollout, nothing
-        forced): the summary then holds mean_discounted_return and the per-env dict disc_final. No other result changes."""
+        forced): the summary then holds mean_discounted_return and the per-env dict disc_final. No other result changes.
+        `gate` (SPEC §25.3): a gate table [n_vf, 2, 5, 1296] (gatefit) under which the value gate compares, None for SPEC §4.2's own
+        comparison, default the agent's `gate` (None unless improve_gate(apply=True) stored one). With a table the launches are
+        population rollouts of ONE policy (scg_rollout_population_gate), whose range is the plain rollout's by bits but for the
+        gate's decisions; ScgError with `interrupt` or `choose`."""
+        gate = self._gate_tables(gate, 1)
+        pop = None
+        if gate is not None:
+            dev = self.W.device
+            pop = (self.W.reshape(1, self.n_vf, NUM_ACTIONS, NUM_FEATURES), torch.tensor([float(epsilon)], dtype=torch.float32, device=dev),
+                   torch.tensor([int(self.enabled_mask)], dtype=torch.int32, device=dev), None, gate)
         stats, _ = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt, choose=choose,
-                                       audit=True if discounted else None)
+                                       audit=True if discounted else None, population=pop)
         out = stats.summary()
         return (out, stats.per_env()) if per_env else out
 
@@ -501,7 +514,8 @@ class SkillChainingAgent:
         `population` = (W [C, n_vf, 5, 1296], epsilon [C] or None, enabled [C] or None) on the device makes every launch a
         population rollout (SPEC §21) of C policies over n_episodes envs each: the context has C * n_episodes envs, the `states`
         are repeated for every policy, and `epsilon` is the context's own (no policy's, where the population gives one). A fourth
-        element, a [C, n_vf, 8] classifier table (or None), gives every policy its own classifiers (SPEC §24.1)."""
+        element, a [C, n_vf, 8] classifier table (or None), gives every policy its own classifiers (SPEC §24.1), a fifth, a
+        [C, n_vf, 2, 5, 1296] gate table (or None), its own value gate (SPEC §25.1)."""
         if choose not in (None, "value"):
             raise ValueError(f"choose must be None or 'value', not {choose!r}")
         if states is not None:
@@ -539,7 +553,7 @@ class SkillChainingAgent:
 
     def evaluate_policies(self, W, epsilons=None, enabled=None, n_episodes: int = 4096, seed: Optional[int] = None,
                           steps_per_launch: int = 64, states=None, interrupt: bool = False, choose: Optional[str] = None,
-                          per_env: bool = False, baseline: int = 0, clf=None):
+                          per_env: bool = False, baseline: int = 0, clf=None, gate="agent"):
         """Several policies in one set of launches, on common random numbers (SPEC §21): `W` is [C, n_vf, 5, 1296] or a list of C
         [n_vf, 5, 1296] tables, `epsilons` and `enabled` scalars or one per policy (defaults: 0.0 and the agent's enabled mask).
         evaluate(discounted=True)'s launches run ONCE, on an evaluation context of C * n_episodes envs of which the envs c *
@@ -552,10 +566,18 @@ class SkillChainingAgent:
         envs in all, and for `epsilons` / `enabled` of another length.
         `clf` (SPEC §24.3): None (the agent's classifier table for every policy), one [n_vf, 8] table for all of them, or [C, n_vf, 8]
         / a list of C tables, one per policy: summaries[c] is then evaluate()'s with clf[c] in place too. With `clf` given, `W` may
-        also be a single [n_vf, 5, 1296] table, repeated for every policy of clf (comparing classifiers under one W)."""
+        also be a single [n_vf, 5, 1296] table, repeated for every policy of clf (comparing classifiers under one W).
+        `gate` (SPEC §25.3): None (SPEC §4.2's comparison for every policy), one [n_vf, 2, 5, 1296] gate table for all of them, or
+        [C, n_vf, 2, 5, 1296] / a list of C tables, one per policy; default the agent's `gate`. summaries[c] is then evaluate()'s
+        with gate[c] too. With C tables given, `W` may be a single table as with `clf`. ScgError with `interrupt` or `choose`."""
         dev = self.W.device
         table = (self.n_vf, NUM_ACTIONS, NUM_FEATURES)
         row = (self.n_vf, _lib.CLF_STRIDE)
+        gate = self._gate_tables(gate, None)
+        if gate is not None and clf is None and not isinstance(W, (list, tuple)):
+            W = torch.as_tensor(W, dtype=torch.float32).to(dev)
+            if W.dim() != 4 and W.numel() == self.W.numel():           # one W for every policy of gate
+                W = W.reshape(1, *table).repeat(int(gate.shape[0]), 1, 1, 1)
         if clf is not None:
             if isinstance(clf, (list, tuple)):
                 clf = [torch.as_tensor(t, dtype=torch.float32).to(dev) for t in clf]
@@ -600,6 +622,12 @@ class SkillChainingAgent:
             if int(clf.shape[0]) != n_pol:
                 raise ValueError(f"clf must hold one table per policy ({n_pol}), not {int(clf.shape[0])}")
             pol_clf = (clf.contiguous(),)
+        if gate is not None:
+            if int(gate.shape[0]) == 1:
+                gate = gate.repeat(n_pol, 1, 1, 1, 1)
+            if int(gate.shape[0]) != n_pol:
+                raise ValueError(f"gate must hold one table per policy ({n_pol}), not {int(gate.shape[0])}")
+            pol_clf = (pol_clf[0] if pol_clf else None, gate.contiguous())
         # (the context's own epsilon is read by no policy: every one has its entry; with clf the agent's table likewise)
         stats, _ = self._eval_launches(n_episodes, 0.0, seed, steps_per_launch, states, interrupt, choose=choose, audit=True,
                                        population=(W.contiguous(), pol_eps, pol_enabled, *pol_clf))
@@ -608,6 +636,29 @@ class SkillChainingAgent:
         envs = [{f: v.detach().cpu() for f, v in stats.per_env(c * n, (c + 1) * n).items()} for c in range(n_pol)]
         paired = [paired_differences(envs[c], envs[int(baseline)]) for c in range(n_pol)]
         return (summaries, paired, envs) if per_env else (summaries, paired)
+
+    def _gate_tables(self, gate, n_pol: Optional[int]):
+        """`gate` of evaluate() / evaluate_policies() as a float32 [C, n_vf, 2, 5, 1296] device tensor, or None: "agent" is the
+        agent's own; one table is C = 1; a list is stacked. n_pol = 1 takes one table only."""
+        if isinstance(gate, str):
+            if gate != "agent":
+                raise ValueError(f"gate must be a table, None or 'agent', not {gate!r}")
+            gate = getattr(self, "gate", None)                 # (a stand-in agent without the attribute: no table)
+        if gate is None:
+            return None
+        shape = (self.n_vf, 2, NUM_ACTIONS, NUM_FEATURES)
+        if isinstance(gate, (list, tuple)):
+            gate = [torch.as_tensor(t, dtype=torch.float32).to(self.W.device) for t in gate]
+            if not gate or any(tuple(t.shape) != shape for t in gate):
+                raise ValueError(f"every table of gate must be {list(shape)}")
+            gate = torch.stack(gate)
+        gate = torch.as_tensor(gate, dtype=torch.float32).to(self.W.device)
+        if gate.dim() == 4:
+            gate = gate[None]
+        if gate.dim() != 5 or tuple(gate.shape[1:]) != shape or (n_pol is not None and int(gate.shape[0]) != n_pol):
+            raise ValueError(f"gate must be {list(shape)}" + (" or [C, ...] / a list of such tables" if n_pol is None else "")
+                             + f", not {tuple(gate.shape)}")
+        return gate.contiguous()
 
     def improve_policy(self, lambdas=(0.25, 0.5, 1.0), eval_epsilons=(0.0,), criterion: str = "discounted", z: float = 2.0,
                        n_eval: int = 4096, apply: bool = False, **fit):
@@ -1467,6 +1518,120 @@ class SkillChainingAgent:
             self.clf.copy_(clf_chosen)
         return {"options": opt_rows, "candidates": cands, "chosen": pick["chosen"], "accepted": pick["accepted"],
                 "criterion": criterion, "z": float(z), "fixed_point": fixed}, clf_chosen
+
+    def fit_gate(self, n_record: int = 256, n_states: int = 4096, replicates: int = 4, epsilon: float = 0.1, ridge: float = 1e-3,
+                 min_offers: int = 256, seed: Optional[int] = None):
+        """What is entering worth, as a function of the state (SPEC §25.3)? record_episodes(n_record, epsilon, seed) gives the
+        states at which offers happen (Trajectory.offer_states, at most n_states); from each, for its own lowest-numbered
+        candidate, gate_audit runs `replicates` pairs of a forced-enter and a forced-decline episode, replicate r with the seed
+        `seed` + r (so with its own draws); the target is Delta(s) = mean G_enter - mean G_decline over the replicates (float64). Per
+        option k with at least `min_offers` fit states, u_k is the ridge regression of Delta on the 1296 features: the audited
+        states of even position are the fit half, the odd ones are held out; ONE ScgContext.feature_gram call with the option as
+        the segment, then valuefit.ridge_solve. Returns (report, u): u {k: float64 [1296]}; report["options"] one row per offered
+        option with "option", "n" (its audited states), "n_fit", "n_held", "fitted" and, on the held-out half, "rmse" (of float32
+        u_k . phi against Delta, NaN where not fitted), "agreement_fitted" (sign(u_k . phi) >= 0 against Delta >= 0),
+        "agreement_shipped" (V_k >= V_0 against the same), "mean_delta"; report["n_states"], "replicates", "epsilon", "ridge". The
+        later steps of every branch act under the agent's W and SPEC §4.2's own gate. The agent is left as evaluate() leaves it."""
+        from .valuefit import ridge_solve
+        R = int(replicates)
+        if R < 1 or int(min_offers) < 1:
+            raise ValueError("fit_gate needs replicates >= 1 and min_offers >= 1")
+        base_seed = int(self.ctx.cfg.seed) if seed is None else int(seed)
+        traj, _ = self.record_episodes(int(n_record), epsilon=epsilon, seed=seed)
+        states = traj.offer_states(int(n_states))
+        report = {"n_states": int(len(states[0])), "replicates": R, "epsilon": float(epsilon), "ridge": float(ridge), "options": []}
+        if not len(states[0]):
+            return report, {}
+        per0, ge, gd = None, 0.0, 0.0
+        for r in range(R):
+            per = self.gate_audit(states=states, epsilon=epsilon, seed=base_seed + r)["per_state"]
+            if per0 is None:
+                per0 = per
+            elif not np.array_equal(per["index"], per0["index"]) or not np.array_equal(per["option"], per0["option"]):
+                raise ScgError("fit_gate: two replicates audited different states")       # (the candidate is the state's alone)
+            ge, gd = ge + per["g_enter"].astype(np.float64), gd + per["g_decline"].astype(np.float64)
+        delta = (ge - gd) / R
+        idx, opt = per0["index"], per0["option"]
+        ships = per0["v_k"] >= per0["v_0"]                     # §4.2's decision at these states (a NaN side declines)
+        fit = np.arange(len(idx)) % 2 == 0
+        dev = self.W.device
+        ectx = self._eval_ctx[len(states[0])][0]
+        st = [torch.from_numpy(np.ascontiguousarray(v[idx])).to(dev) for v in states]
+        ks = [int(k) for k in np.unique(opt)]
+        if not ks:                                             # no offer state has a candidate now
+            return report, {}
+        order = np.concatenate([np.nonzero(fit & (opt == k))[0] for k in ks])           # the fit half by option, state order within one
+        n_k = np.asarray([int(np.sum(fit & (opt == k))) for k in ks], np.int64)
+        u = {}
+        if len(order):
+            at = torch.from_numpy(order).to(dev)
+            A, b = ectx.feature_gram([t[at].contiguous() for t in st], np.concatenate([[0], np.cumsum(n_k)]).astype(np.int64),
+                                     torch.from_numpy(delta[order].astype(np.float32)).to(dev))
+            use = [i for i, k in enumerate(ks) if n_k[i] >= int(min_offers)]
+            if use:
+                sol = ridge_solve(A[use].cpu().numpy(), b[use].cpu().numpy(), n_k[use], ridge, self.ctx.scale)
+                u = {ks[i]: sol[j] for j, i in enumerate(use)}
+        nan = float("nan")
+        for i, k in enumerate(ks):
+            held = np.nonzero(~fit & (opt == k))[0]
+            row = {"option": k, "n": int(np.sum(opt == k)), "n_fit": int(n_k[i]), "n_held": int(len(held)), "fitted": k in u,
+                   "rmse": nan, "agreement_fitted": nan, "agreement_shipped": nan, "mean_delta": nan}
+            if len(held):
+                want = delta[held] >= 0.0
+                row["agreement_shipped"] = float(np.mean(ships[held] == want))
+                row["mean_delta"] = float(np.mean(delta[held]))
+                if k in u:
+                    Wk = torch.from_numpy(np.tile(u[k].astype(np.float32), (NUM_ACTIONS, 1))).to(dev).contiguous().view(-1)
+                    pred = np.zeros(len(held), np.float32)
+                    for j in range(0, len(held), ectx.n_envs):
+                        sl = torch.from_numpy(held[j:j + ectx.n_envs]).to(dev)
+                        pred[j:j + ectx.n_envs] = ectx.q_values([t[sl].contiguous() for t in st], Wk)[0].cpu().numpy()
+                    row["rmse"] = float(np.sqrt(np.mean((pred.astype(np.float64) - delta[held]) ** 2)))
+                    row["agreement_fitted"] = float(np.mean((pred >= 0.0) == want))
+            report["options"].append(row)
+        return report, u
+
+    def improve_gate(self, eval_epsilons=(0.0,), criterion: str = "discounted", z: float = 2.0, n_eval: int = 4096,
+                     apply: bool = False, **fit):
+        """A safeguarded step on the value gate itself (SPEC §25.3), the counterpart of improve_policy for W and of
+        improve_initiation for in_k. fit_gate(**fit) gives u; gatefit.candidate_gates(W, u) — SPEC §4.2's own comparison
+        ("shipped"), "always", "never", each fitted option's row alone, and "all" — at each of `eval_epsilons` are evaluated in ONE
+        evaluate_policies run of n_eval episodes each under the agent's W and clf (common start states and draws);
+        initfit.choose_table decides at eval_epsilons[0] against "shipped" (SPEC §21.4's rule). Returns (report, gate_chosen):
+        report["fit"] the fit's report, report["candidates"] rows of {"label", "epsilon", "summary", "paired"} (paired: against
+        "shipped" at the same epsilon; the summary holds SPEC §8's per-option entries, declines and steps_share), "chosen" (a
+        label; "shipped" when nothing is accepted), "accepted", "criterion", "z"; gate_chosen a copy of the chosen table.
+        apply=True stores it as the agent's `gate`, under which evaluate() and evaluate_policies() then act by default (a copy:
+        the "shipped" table is W's comparison as W was then; set `gate = None` to follow W again). ONLY those two read it: the learner (step_batch), option trials, branch and audit
+        rollouts, the recorded evaluation and every other kernel keep SPEC §4.2's comparison under W. apply=True is refused on a
+        sharded agent. ValueError for no epsilon, an unknown criterion, or more candidates x epsilons than a population holds.
+        With apply=False the agent is left as evaluate() leaves it."""
+        from . import gatefit
+        if apply and self.group is not None:
+            raise ValueError("improve_gate(apply=True) is not available on a sharded agent")
+        if criterion not in ("discounted", "return", "success"):
+            raise ValueError(f"criterion must be 'discounted', 'return' or 'success', not {criterion!r}")
+        eps = [float(v) for v in eval_epsilons]
+        if not eps:
+            raise ValueError("improve_gate needs at least one epsilon")
+        n_opt = bin(self.enabled_mask >> 1).count("1")
+        if (3 + n_opt + (1 if n_opt >= 2 else 0)) * len(eps) > _lib.POP_MAX:          # before anything runs: the most the fit can give
+            raise ValueError(f"{3 + n_opt + (1 if n_opt >= 2 else 0)} candidate gates x {len(eps)} epsilons are more than the "
+                             f"{_lib.POP_MAX} policies of one population")
+        fit_report, u = self.fit_gate(**fit)
+        tables = gatefit.candidate_gates(self.W, u)
+        n_tab, per_eps = len(tables), len(eps)
+        stack = torch.stack([t for _, t in tables])
+        summaries, _, envs = self.evaluate_policies(self.W, np.repeat(np.asarray(eps, np.float32), n_tab), None, n_episodes=int(n_eval),
+                                                    seed=fit.get("seed"), per_env=True, gate=stack.repeat(per_eps, 1, 1, 1, 1))
+        cands = [{"label": tables[i][0], "epsilon": eps[e], "summary": summaries[e * n_tab + i],
+                  "paired": paired_differences(envs[e * n_tab + i], envs[e * n_tab])} for e in range(per_eps) for i in range(n_tab)]
+        pick = initfit.choose_table(cands[:n_tab], criterion, z)
+        gate_chosen = dict(tables)[pick["chosen"]].clone()
+        if apply:
+            self.gate = gate_chosen
+        return {"fit": fit_report, "candidates": cands, "chosen": pick["chosen"], "accepted": pick["accepted"],
+                "criterion": criterion, "z": float(z)}, gate_chosen
 
     def rollout(self, steps: int, learn: bool = True) -> None:
         for _ in range(steps):

@@ -203,14 +203,17 @@ class ScgContext:
         return record.c_struct()
 
     def _chk_population(self, W: torch.Tensor, population) -> "_lib.Population":
-        """The scg_population of rollout(population=(epsilon, enabled[, clf])) (SPEC §21): C from W's leading dimension, n_per = n_envs // C.
-        (§24.1's clf, checked here against that C, is no member of the struct: rollout passes it behind it.)"""
+        """The scg_population of rollout(population=(epsilon, enabled[, clf[, gate]])) (SPEC §21): C from W's leading dimension, n_per =
+        n_envs // C. (§24.1's clf and §25.1's gate, checked here against that C, are no members of the struct: rollout passes them
+        behind it.)"""
         try:
             eps, enabled, *rest = population
-            (pop_clf,) = rest or (None,)
+            pop_clf, pop_gate = (tuple(rest) + (None, None))[:2] if len(rest) <= 2 else ()
+            if len(rest) == 2 and pop_gate is None:            # (the four-element form is for a gate table; three elements say "none")
+                raise ValueError
         except (TypeError, ValueError):
             raise ScgError("rollout: population must be (epsilon, enabled) of [C] tensors, either may be None, optionally followed by "
-                           "a [C, n_vf, 8] classifier table") from None
+                           "a [C, n_vf, 8] classifier table (or None) and then a [C, n_vf, 2, 5, 1296] gate table") from None
         if not isinstance(W, torch.Tensor) or W.dim() != 4 or tuple(W.shape[1:]) != (self.n_vf, NUM_ACTIONS, NUM_FEATURES):
             raise ScgError(f"rollout: with a population W must be [C, {self.n_vf}, {NUM_ACTIONS}, {NUM_FEATURES}], "
                            f"got {tuple(getattr(W, 'shape', ()))}")
@@ -230,6 +233,11 @@ class ScgContext:
                 raise ScgError(f"rollout: the population's clf must be [{n_pol}, {self.n_vf}, {CLF_STRIDE}], "
                                f"got {tuple(getattr(pop_clf, 'shape', ()))}")
             self._chk(pop_clf, torch.float32, n_pol * self.n_vf * CLF_STRIDE, "population clf")
+        if pop_gate is not None:
+            shape = (n_pol, self.n_vf, 2, NUM_ACTIONS, NUM_FEATURES)
+            if not isinstance(pop_gate, torch.Tensor) or tuple(pop_gate.shape) != shape:
+                raise ScgError(f"rollout: the population's gate must be {list(shape)}, got {tuple(getattr(pop_gate, 'shape', ()))}")
+            self._chk(pop_gate, torch.float32, pop_gate.numel(), "population gate")
         return _lib.Population(n_pol, self.n_envs // n_pol, _ptr(eps), _ptr(enabled))
 
     def rollout(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t0: int, n_steps: int,
@@ -261,14 +269,21 @@ class ScgContext:
         states and the same draws, and its range equals by bits a rollout of n_per envs under that policy alone.
         SPEC §24.1: `population` = (epsilon, enabled, clf) with clf a float32 [C, n_vf, 8] tensor on this device (or None) gives
         every policy its own classifier table too (scg_rollout_population_clf): policy c reads clf[c] wherever the rollout reads
-        a classifier, and the `clf` argument is then no policy's."""
+        a classifier, and the `clf` argument is then no policy's.
+        SPEC §25.1: `population` = (epsilon, enabled, clf, gate) with gate a float32 [C, n_vf, 2, 5, 1296] tensor on this device (no
+        gate table: the three-element form) gives every policy a gate table (scg_rollout_population_gate): the value gate of option k compares max_a Q(s_next, .)
+        under gate[c][k][0] against the same under gate[c][k][1] and nothing else reads the table; not with `interrupt` or
+        `choose="value"`."""
         if choose not in (None, "value"):
             raise ValueError(f"rollout: choose must be None or 'value', not {choose!r}")
         N = self.n_envs
-        pop = pop_clf = None
+        pop = pop_clf = pop_gate = None
         if population is not None:
             pop = self._chk_population(W, population)
-            pop_clf = population[2] if len(population) == 3 else None
+            pop_clf = population[2] if len(population) >= 3 else None
+            pop_gate = population[3] if len(population) >= 4 else None
+            if pop_gate is not None and (interrupt or choose is not None):
+                raise ScgError("rollout: a gate table goes with neither interrupt nor choose='value' (SPEC §25.1)")
         self._chk_operands(st, W, clf, 1 if pop is None else pop.n_policies)
         n_steps, t0 = int(n_steps), int(t0)
         if begin and begin_at:
@@ -326,7 +341,8 @@ class ScgContext:
         ints, ovr = (None if a is None else _ptr(a) for a in (interrupts, overrides))
         rc_ref = None if rc is None else C.byref(rc)
         if pop is not None:
-            name = "scg_rollout_population" if pop_clf is None else "scg_rollout_population_clf"
+            name = ("scg_rollout_population_gate" if pop_gate is not None
+                    else "scg_rollout_population" if pop_clf is None else "scg_rollout_population_clf")
             tail = (ints, ovr, rc_ref, C.c_uint32(rules), None if au is None else C.byref(au),
                     _ptr(first_action))
         elif first_action is not None:
@@ -345,7 +361,8 @@ class ScgContext:
         self._call(name, _ptr(st.x), _ptr(st.y), _ptr(st.vx), _ptr(st.vy), _ptr(st.option_id), _ptr(st.opt_steps), _ptr(st.ep_steps),
                    _ptr(st.qcache), _ptr(st.action), _ptr(st.reward), _ptr(st.done), _ptr(W), _ptr(clf), C.c_uint32(enabled_mask),
                    C.c_uint64(t0), C.c_int32(n_steps), C.c_uint32(flags), None if cs is None else C.byref(cs), *tail, self._stream(),
-                   *(() if pop is None else (C.byref(pop),)), *(() if pop_clf is None else (_ptr(pop_clf),)))
+                   *(() if pop is None else (C.byref(pop),)),
+                   *(() if pop_clf is None and pop_gate is None else (_ptr(pop_clf),)), *(() if pop_gate is None else (_ptr(pop_gate),)))
         if stats is not None and interrupt and interrupts is stats.interrupts:
             stats.interrupting = True
 

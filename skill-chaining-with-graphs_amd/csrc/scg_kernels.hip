@@ -27,7 +27,7 @@
 // launch_rollout<REC, Args> / launch_trial_record, which the two kernel headers declare.
 // scg_rollout_population.hip is a unit of the same kind: SPEC §21's four population instantiations of rollout_kernel,
 // reached through the same launch_rollout<REC, Args>; with SPEC §24.1's pop_clf the same four stage a classifier table per policy
-// (DESIGN §3.29).
+// (DESIGN §3.29); SPEC §25.1's pop_gate takes a fifth one, whose value gate compares under a gate table per policy.
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -687,9 +687,10 @@ struct RolloutCall {
     const uint8_t *first_action;   // scg_rollout_branch (SPEC §19)
     const scg_population *pop;     // scg_rollout_population (SPEC §21)
     const float *pop_clf;          // scg_rollout_population_clf (SPEC §24.1): [C][n_vf][8], a classifier table per policy
+    const float *pop_gate;         // scg_rollout_population_gate (SPEC §25.1): [C][n_vf][2][5][1296], a gate table per policy
 };
 
-// the eight rollout entry points (`fn` names the caller in error texts). The kernel follows from what the call asks for:
+// the nine rollout entry points (`fn` names the caller in error texts). The kernel follows from what the call asks for:
 //   audit      a member of `audit` given (SPEC §15; every member NULL counts as no audit), or a first_action (SPEC §19: the AUDIT
 //              kernels are the ones that read it; with no audit member they write nothing of the audit's)
 //   best, intr SCG_SELECT_BEST / SCG_SELECT_INTERRUPT in `rules` (SPEC §14 / §11), counting into `overrides` / `interrupts`
@@ -698,6 +699,8 @@ struct RolloutCall {
 //              no audit member and no first_action they write nothing of either), on a grid of whole workgroups per policy
 //   pop_clf    a classifier table per policy (SPEC §24.1): the same RolloutPop kernels, which then stage pop_clf[c] where they staged
 //              `clf`; refused without pop, behind every other refusal
+//   pop_gate   a gate table per policy (SPEC §25.1): RolloutPopGateArgs' kernel, the fifth POP one; refused without pop and with
+//              intr or best, behind pop_clf's refusal
 // Neither audit, best, rec, at nor pop: the plain kernel, or with intr the non-recording interrupting one; otherwise a RolloutVar by
 // (intr, best, audit)
 static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
@@ -754,6 +757,9 @@ static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
     if (!rollout_epw(c, c->cfg.n_envs, epw)) return fail_in(c, SCG_ERR_INVALID, fn, "SCG_ROLLOUT_EPW must be 2, 4, 8, 16 or 32");
     R.epw = epw;
     if (a.pop_clf && !a.pop) return fail_in(c, SCG_ERR_INVALID, fn, "pop_clf without pop");      // SPEC §24.1: the last refusal
+    if (a.pop_gate && !a.pop) return fail_in(c, SCG_ERR_INVALID, fn, "pop_gate without pop");     // SPEC §25.1: the last two refusals
+    if (a.pop_gate && (intr || best))
+        return fail_in(c, SCG_ERR_INVALID, fn, "pop_gate with SCG_SELECT_INTERRUPT or SCG_SELECT_BEST: the gate table is for the plain rules");
     const int wgs_per_pol = a.pop ? (a.pop->n_per + RO_WAVES * epw - 1) / (RO_WAVES * epw) : 0;
     const int grid = a.pop ? a.pop->n_policies * wgs_per_pol : (c->cfg.n_envs + RO_WAVES * epw - 1) / (RO_WAVES * epw);
     const hipStream_t s = reinterpret_cast<hipStream_t>(a.stream);
@@ -774,6 +780,11 @@ static int rollout_launch(const char *fn, scg_ctx *c, RolloutCall a) {
         auto P = derived_args<RolloutPopArgs>(V);
         P.n_pol = a.pop->n_policies; P.n_per = a.pop->n_per; P.wgs_per_pol = wgs_per_pol;
         P.pol_eps = a.pop->epsilon; P.pol_enabled = a.pop->enabled; P.pol_clf = a.pop_clf;
+        if (a.pop_gate) {
+            auto G = derived_args<RolloutPopGateArgs>(P);
+            G.pol_gate = a.pop_gate;
+            rollout_kernel_launch = launch_rollout<true>(G, grid, s);
+        } else
         switch ((best ? 2 : 0) | (intr ? 1 : 0)) {
         case 0: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutPop<false, false>>(P), grid, s); break;
         case 1: rollout_kernel_launch = launch_rollout<true>(derived_args<RolloutPop<true, false>>(P), grid, s); break;
@@ -878,9 +889,21 @@ int scg_rollout_population_clf(scg_ctx *c, float *x, float *y, float *vx, float 
                                uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
                                const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action, void *stream,
                                const scg_population *pop, const float *pop_clf) {
-    return rollout_launch(pop_clf ? "scg_rollout_population_clf" : "scg_rollout_population", c,
+    return scg_rollout_population_gate(c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf, enabled_mask,
+                                       t0, n_steps, flags, stats, interrupts, overrides, rec, rules, audit, first_action, stream, pop,
+                                       pop_clf, nullptr);
+}
+
+// pop_gate = NULL: scg_rollout_population_clf's launch, under the name that entry point gives in error texts
+int scg_rollout_population_gate(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                                int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done,
+                                const float *W, const float *clf, uint32_t enabled_mask, uint64_t t0, int32_t n_steps,
+                                uint32_t flags, const scg_rollout_stats *stats, int32_t *interrupts, int32_t *overrides,
+                                const scg_record *rec, uint32_t rules, const scg_audit *audit, const uint8_t *first_action, void *stream,
+                                const scg_population *pop, const float *pop_clf, const float *pop_gate) {
+    return rollout_launch(pop_gate ? "scg_rollout_population_gate" : pop_clf ? "scg_rollout_population_clf" : "scg_rollout_population", c,
                           {x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf, enabled_mask, t0, n_steps, flags,
-                           stats, stream, true, rec, interrupts, overrides, rules, audit, first_action, pop, pop_clf});
+                           stats, stream, true, rec, interrupts, overrides, rules, audit, first_action, pop, pop_clf, pop_gate});
 }
 
 static int trials_launch(const char *fn, scg_ctx *c, int32_t n, const float *x, const float *y, const float *vx, const float *vy,

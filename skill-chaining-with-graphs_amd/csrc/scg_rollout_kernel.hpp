@@ -41,8 +41,9 @@ struct RolloutArgs {
     static constexpr bool BEST = false;  // SPEC §14's value-ranked choice: likewise
     static constexpr bool AUDIT = false; // SPEC §15's forced first choice and discounted return: likewise
     static constexpr bool POP = false;   // SPEC §21's population: a weight table, an epsilon and an enabled mask per env range: likewise
+    static constexpr bool GATE = false;  // SPEC §25's gate table: the value gate compares under a table of its own: likewise
 };
-// The fourteen instantiations, the narrowest entry point that launches each (rollout_launch in scg_kernels.hip has the whole mapping), and
+// The fifteen instantiations, the narrowest entry point that launches each (rollout_launch in scg_kernels.hip has the whole mapping), and
 // what each adds to <false, RolloutArgs>. INT, BEST, AUDIT and POP are compile-time flags of the argument type. Every argument type has
 // RolloutArgs at offset 0, so the exit's re-read holds for all.
 //   REC    Args                               launched by                    adds
@@ -62,6 +63,8 @@ struct RolloutArgs {
 //                                                                            the draws are keyed by the env's index within its range
 //                                             scg_rollout_population_clf     SPEC §24.1: the same four kernels; with pop_clf a classifier table per
 //                                             (pop given)                    range too, staged once per launch in place of `clf`
+//   true   RolloutPopGateArgs                 scg_rollout_population_gate    SPEC §25.1: RolloutPop<false, false> whose value gate compares under a
+//          (the fifteenth)                    (pop and pop_gate given)       gate table per range, two sides per option, both straight from memory
 // Every REC instantiation shares ONE argument layout, RolloutVarArgs (the population's members lie behind it); the
 // non-recording interrupting kernel keeps its own, because `interrupts` at another offset changes its code.
 struct RolloutIntArgs : RolloutArgs {
@@ -94,6 +97,12 @@ template <bool I, bool B>
 struct RolloutPop : RolloutPopArgs {
     static constexpr bool INT = I, BEST = B, AUDIT = true, POP = true;
 };
+// SPEC §25.1: the gate of option k >= 1 reads max_a Q(s_next, a) under pol_gate[c][k][0] (the option side) against the same under
+// pol_gate[c][k][1] (the root side); everything else reads W[c] as before
+struct RolloutPopGateArgs : RolloutPopArgs {
+    static constexpr bool INT = false, BEST = false, AUDIT = true, POP = true, GATE = true;
+    const float *pol_gate;         // [n_pol][n_vf][2][5][1296], never null here (the LAST member: every offset above holds)
+};
 
 // per-VF counters of one launch, six 16-bit fields in three words (a launch takes at most 1 + SCG_ROLLOUT_MAX_STEPS steps)
 struct Ctr16 {
@@ -115,8 +124,9 @@ static_assert(SCG_ROLLOUT_MAX_STEPS + 1 < 65536, "16-bit launch counters");
 // (the instantiations: the table at the argument types)
 template <bool REC, typename Args>
 __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
-    constexpr bool INT = Args::INT, BEST = Args::BEST, AUDIT = Args::AUDIT, POP = Args::POP;
-    constexpr int QV_SLOTS = BEST ? MAX_VF : 2;               // BEST: one slot per value function
+    constexpr bool INT = Args::INT, BEST = Args::BEST, AUDIT = Args::AUDIT, POP = Args::POP, GATE = Args::GATE;
+    static_assert(!GATE || (POP && AUDIT && REC && !INT && !BEST), "the gate table: one instantiation (SPEC §25.1)");
+    constexpr int QV_SLOTS = BEST ? MAX_VF : GATE ? 4 : 2;    // BEST: one slot per value function; GATE: [2] / [3] the gate's two sides
     constexpr int QV_ROOT = BEST ? 0 : 1;                     // the slot of the root's Q beside the running VF's
     __shared__ __attribute__((aligned(16))) float s_w0[W_FLOATS];                 // W_0 in A-operand order (stage_w_cold's layout)
     __shared__ __attribute__((aligned(16))) float s_edges[MAX_EDGES * 8];
@@ -126,6 +136,8 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
     __shared__ uint16_t s_list[MAX_VF][RO_MAX_ENVS];                               // env index | slot << 8
     __shared__ int s_cnt[2][MAX_VF];                                               // list lengths, by step parity
     __shared__ float s_clf[MAX_VF * CLF_STRIDE];
+    __shared__ uint16_t s_glist[GATE ? MAX_VF : 1][GATE ? RO_MAX_ENVS : 1];        // GATE: the entering envs by candidate (both sides share a list)
+    __shared__ int s_gcnt[2][GATE ? MAX_VF : 1];                                   // GATE: their lengths, by step parity
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int epw = A.epw, N = A.n;
@@ -202,6 +214,9 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
     }
     if (tid < A.n_vf * CLF_STRIDE) s_clf[tid] = clfp[tid];
     if (tid < 2 * MAX_VF) (&s_cnt[0][0])[tid] = 0;
+    if constexpr (GATE) {
+        if (tid < 2 * MAX_VF) (&s_gcnt[0][0])[tid] = 0;
+    }
     __syncthreads();
 
     const unsigned known = enabled | A.gest;
@@ -296,12 +311,22 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
             if (w0) s_list[k][base + __popcll(b0 & below)] = (uint16_t)il;
             if (w1) s_list[k][base + n0 + __popcll(b1 & below)] = (uint16_t)(il | 0x100);
         }
+        if constexpr (GATE) {                                  // SPEC §25.1: an entering env also goes to the gate list of its cand (= on)
+#pragma unroll
+            for (int k = 1; k < MAX_VF; ++k) list_append(&s_gcnt[par][k], s_glist[k], entering && on == k, (uint16_t)il, lane);
+        }
         __syncthreads();
         // ------------------------------------------------------------ E
         int cnt[MAX_VF], units = 0;
 #pragma unroll
         for (int k = 0; k < MAX_VF; ++k) { cnt[k] = k < A.n_vf ? s_cnt[par][k] : 0; units += (cnt[k] + 7) >> 3; }
-        if (units == 0) break;                                 // (workgroup-uniform) nothing left to step
+        [[maybe_unused]] int gcnt[GATE ? MAX_VF : 1], gunits = 0;              // GATE: the gate lists and their units (every one also has an ordinary unit)
+        if constexpr (GATE) {
+            gcnt[0] = 0;
+#pragma unroll
+            for (int k = 1; k < MAX_VF; ++k) { gcnt[k] = k < A.n_vf ? s_gcnt[par][k] : 0; gunits += (gcnt[k] + 7) >> 3; }
+        }
+        if (units + gunits == 0) break;                        // (workgroup-uniform) nothing left to step
         {
             const int n16 = lane & 15, g = lane >> 4, bi = lane & 7, cp = lane >> 3;           // lane roles: scg_eval.hpp
             const int bcol = 8 * (bi >> 2) + (bi & 3);
@@ -333,9 +358,43 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
                 }
                 wave_lds_sync();                                   // the tables are rewritten by the next unit
             }
+            if constexpr (GATE) {
+                // SPEC §25.1: the gate lists behind the ordinary units, dealt on from the wave those ended at. ONE table build per
+                // unit, then both sides of option k's comparison from memory, into slots 2 (option side) and 3 (root side)
+                const float *gp = kernel_args<Args>()->pol_gate + (size_t)pol * A.n_vf * 2 * NACT * NF;
+                for (int uu = (wave + RO_WAVES - units % RO_WAVES) % RO_WAVES; uu < gunits; uu += RO_WAVES) {
+                    int k = 1, ub = uu, ck = gcnt[1];              // (gcnt by constant indices only: it stays in registers)
+                    bool on_k = false;
+#pragma unroll
+                    for (int kk = 1; kk < MAX_VF - 1; ++kk) {
+                        const int nu = (gcnt[kk] + 7) >> 3;
+                        on_k = on_k || ub < nu;
+                        if (!on_k) { ub -= nu; k = kk + 1; ck = gcnt[kk + 1]; }
+                    }
+                    const int nk = ck - 8 * ub;                    // items of this unit still ahead in the list (>= 1)
+                    const uint16_t *lst = &s_glist[k][8 * ub];
+                    build_tables(s_z1[lst[min(bi, nk - 1)] & 0xff], cp, bcol, cdk, abq);
+                    wave_lds_sync();
+                    float B[9], q[NACT];
+                    load_b(cdk, n16, g, B);
+#pragma unroll 1
+                    for (int side = 0; side < 2; ++side) {
+                        contract_mem<EO_TG>(gp + ((size_t)k * 2 + side) * NACT * NF, B, q, n16, g, ab_lane);
+                        if (out_lane && ocol_item < nk) {
+                            const int ent = lst[ocol_item];
+#pragma unroll
+                            for (int aa = 0; aa < NACT; ++aa) s_qv[2 + side][aa][ent] = q[aa];
+                        }
+                    }
+                    wave_lds_sync();
+                }
+            }
         }
         __syncthreads();
         if (tid < MAX_VF) s_cnt[par][tid] = 0;                   // next used at step j + 2, behind step j + 1's barrier
+        if constexpr (GATE) {
+            if (tid < MAX_VF) s_gcnt[par][tid] = 0;
+        }
         // ------------------------------------------------------------ G
         if (valid) {
             float qa[NACT];
@@ -367,13 +426,25 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
                 float q0[NACT];
 #pragma unroll
                 for (int aa = 0; aa < NACT; ++aa) q0[aa] = s_qv[QV_ROOT][aa][il];
-                declined = !gate_holds(qa, q0);
+                [[maybe_unused]] float gk[GATE ? NACT : 1];                    // GATE: Q(s_next, .) under the option side of cand's gate
+                if constexpr (GATE) {                          // SPEC §25.1: the comparison alone moves to the gate table's two sides
+                    float g0[NACT];
+#pragma unroll
+                    for (int aa = 0; aa < NACT; ++aa) { gk[aa] = s_qv[2][aa][il]; g0[aa] = s_qv[3][aa][il]; }
+                    declined = !gate_holds(gk, g0);
+                } else {
+                    declined = !gate_holds(qa, q0);
+                }
                 if constexpr (AUDIT) {
                     if (is_begin) {                            // SPEC §15's begin outputs, from the values the gate reads
                         const scg_audit U = kernel_args<Args>()->au;
                         float v = qa[0];
+                        if constexpr (GATE) v = gk[0];
 #pragma unroll
-                        for (int aa = 1; aa < NACT; ++aa) v = fmaxf(v, qa[aa]);
+                        for (int aa = 1; aa < NACT; ++aa) {
+                            if constexpr (GATE) v = fmaxf(v, gk[aa]);
+                            else v = fmaxf(v, qa[aa]);
+                        }
                         if (U.v_cand) U.v_cand[e] = v;
                     }
                     if (fk) declined = fk < 0;                 // the force replaces the gate's result
@@ -413,9 +484,10 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const Args A) {
                 if (fk) minc = amin;                           // a forced entry overrides where k != min C
                 if (is_begin) {
                     const scg_audit U = kernel_args<Args>()->au;
-                    float v = s_qv[entering ? QV_ROOT : 0][0][il];
+                    constexpr int QV_VROOT = GATE ? 3 : QV_ROOT;  // GATE: the root side of the gate an entering env was offered
+                    float v = s_qv[entering ? QV_VROOT : 0][0][il];
 #pragma unroll
-                    for (int aa = 1; aa < NACT; ++aa) v = fmaxf(v, s_qv[entering ? QV_ROOT : 0][aa][il]);
+                    for (int aa = 1; aa < NACT; ++aa) v = fmaxf(v, s_qv[entering ? QV_VROOT : 0][aa][il]);
                     if (U.v_root) U.v_root[e] = v;
                     if (U.cand) U.cand[e] = (int8_t)(entering ? cand : 0);
                     if (U.applied) U.applied[e] = fk ? 1 : 0;

@@ -189,6 +189,23 @@ class Trajectory:
         out["vf_next"] = np.where((oid >= 1) & (oid < self.n_vf), oid, 0)
         return out
 
+    def offer_rows(self, reoffer_period: int = 1, t0: int = 0, env_ids=None) -> dict:
+        """The recorded rows on which the root ran, the episode went on and an option was offered or stayed out of (vf = 0,
+        done = 0, option_id != 0), in env order: host arrays `flat` (the row's index in to_numpy()'s concatenated fields), `env`,
+        `row`, `option` (|option_id|: the candidate), `entered` (option_id > 0) and `stay`. On such a row the recorded state is
+        s_next, the state §4.2's value gate compared at (an episode's last row holds the state before its reset instead, and is
+        left out). A row is a `stay` where §4.2's re-offer schedule kept the env out of the option the row before it left it out
+        of — the id unchanged and negative, and ((t + env id) & (reoffer_period - 1)) != 0 with t = t0 + row (`t0`: the step
+        counter of each env's row 0; `env_ids`: the envs' global ids, default first .. first + n - 1): no offer was made there
+        and the gate compared nothing. Every other row is an offer whose outcome the sign of the id records. With the default
+        period of 1 every row is an offer. Needs the vf, done and option_id fields."""
+        return offer_rows(self.to_numpy(), reoffer_period, t0, env_ids)
+
+    def offer_states(self, limit=None):
+        """(x, y, vx, vy), float32 host arrays, of the first `limit` rows of offer_rows() in env order (None: all of them; the rows
+        an env stayed out of an option on are among them): states at which offers actually happen, for gate_audit(states=)."""
+        return offer_states(self.to_numpy(), limit)
+
     def to_numpy(self) -> dict:
         """Every env's rows flattened for saving: `offsets` [n + 1] into the concatenated fields, plus `first`."""
         per = [self.per_env(i) for i in range(self.n)]
@@ -197,6 +214,32 @@ class Trajectory:
         out = {f: np.concatenate([p[f] for p in per]) for f in self.fields}
         out["offsets"], out["first"] = off, np.int64(self.first)
         return out
+
+
+def offer_rows(flat: dict, reoffer_period: int = 1, t0: int = 0, env_ids=None) -> dict:
+    """Trajectory.offer_rows on to_numpy()'s dict `flat` (without `offsets`: the rows of one env, `first` 0)."""
+    period = int(reoffer_period)
+    if period < 1 or period & (period - 1):
+        raise ValueError("reoffer_period must be a power of two >= 1")
+    oid = np.asarray(flat["option_id"]).astype(np.int64)
+    off = np.asarray(flat.get("offsets", [0, len(oid)]), np.int64)
+    n = len(off) - 1
+    ids = int(flat.get("first", 0)) + np.arange(n, dtype=np.int64) if env_ids is None else np.asarray(env_ids, np.int64).reshape(-1)
+    if ids.shape != (n,):
+        raise ValueError(f"env_ids must hold {n} entries")
+    at = np.nonzero((np.asarray(flat["vf"]) == 0) & (np.asarray(flat["done"]) == 0) & (oid != 0))[0]
+    env = np.searchsorted(off, at, side="right") - 1
+    row = at - off[env]
+    prev = np.where(row > 0, oid[np.maximum(at - 1, 0)], 0)    # the id the step came in with (an env's row 0: none)
+    off_schedule = ((int(t0) + row + ids[env]) & (period - 1)) != 0
+    return {"flat": at, "env": env, "row": row, "option": np.abs(oid[at]), "entered": oid[at] > 0,
+            "stay": (oid[at] < 0) & (prev == oid[at]) & off_schedule}
+
+
+def offer_states(flat: dict, limit=None):
+    """Trajectory.offer_states on to_numpy()'s dict."""
+    at = offer_rows(flat)["flat"][:limit]
+    return tuple(np.ascontiguousarray(np.asarray(flat[f])[at], np.float32) for f in ("x", "y", "vx", "vy"))
 
 
 def _np_dtype(dt: torch.dtype):

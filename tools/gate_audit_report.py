@@ -32,11 +32,9 @@ def fmt_audit(res):
 
 def offer_states(traj, limit):
     """(x, y, vx, vy) of the recorded rows where the root ran, the episode went on and an option was offered or stayed out of:
-    the first `limit` of them in env order."""
-    import numpy as np
-    r = traj.to_numpy()
-    at = np.nonzero((r["vf"] == 0) & (r["done"] == 0) & (r["option_id"] != 0))[0][:limit]
-    return tuple(np.ascontiguousarray(r[f][at], np.float32) for f in ("x", "y", "vx", "vy"))
+    the first `limit` of them in env order (trajectory.offer_states has the selection; Trajectory.offer_states is this)."""
+    from skill_chaining_with_graphs_amd.trajectory import offer_states as select
+    return select(traj.to_numpy(), limit)
 
 
 def main():

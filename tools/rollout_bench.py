@@ -11,11 +11,13 @@ discounted return) against scg_rollout_select with the same rules, record and la
 population rollout (SPEC §21, scg_rollout_population) of C policies x 4096 envs against C sequential audited rollouts of 4096 envs
 and against one audited rollout of C x 4096 envs under a single weight table (bench_population). --population-clf C times the same
 population launch with a classifier table per policy (SPEC §24.1, scg_rollout_population_clf) against the launch without one
-(bench_population_clf), and --logits scg_classifier_logits against scg_classifier_predict at 65 536 points (bench_logits); both
+(bench_population_clf), --population-gate C the same launch with a gate table per policy as well (SPEC §25.1,
+scg_rollout_population_gate; bench_population_gate), and --logits scg_classifier_logits against scg_classifier_predict at 65 536 points (bench_logits); both
 print each arm's min - max over the rounds beside the ratio.
 
     python tools/rollout_bench.py [--sizes 4096 65536] [--k 64] [--rounds 7] [--epw 2 4 8 16 32] [--record none 1024 all]
                                   [--interrupt] [--choose] [--audit] [--population 1 4 8 16] [--population-clf 1 4 8 16] [--logits]
+                                  [--population-gate 1 4 8 16]
 """
 import argparse
 import json
@@ -294,6 +296,52 @@ def bench_population_clf(n_pol, k, rounds, n_per=4096, n_opt=5):
             "population_rounds_us": [round(v, 2) for v in side["pop"]["us"]], "population_clf_rounds_us": [round(v, 2) for v in side["clf"]["us"]]}
 
 
+def bench_population_gate(n_pol, k, rounds, n_per=4096, n_opt=5):
+    """µs per step of bench_population_clf's population rollout with a gate table per policy too (SPEC §25.1,
+    scg_rollout_population_gate; the table is gatefit.shipped_gate(W[c]), so the three arms act alike) against the same launch with
+    the classifier tables alone (--population-clf's arm) and with neither, each on a state of its own, timed alternately. What the
+    fifth POP kernel's gate units cost. `offers_per_env_step`: one more, untimed launch of the gated arm with the episode counters."""
+    import torch
+    import skill_chaining_with_graphs_amd as scg
+    from skill_chaining_with_graphs_amd import gatefit
+    from skill_chaining_with_graphs_amd.core import ScgContext
+    from skill_chaining_with_graphs_amd.evaluation import EpisodeStats, GateAudit
+    m = scg.load_map("pinball_simple")
+    n = n_pol * n_per
+    ctx = ScgContext(n, n_opt, m, device=0, seed=7, epsilon=0.05, max_episode_steps=2000)
+    mask = ((1 << (n_opt + 1)) - 1) & ~1
+    clf = torch.as_tensor(rig.chain_classifiers(m, n_opt), device=ctx.device)
+    tabs = clf.reshape(1, n_opt + 1, 8).repeat(n_pol, 1, 1).contiguous()
+    g = torch.Generator().manual_seed(3)
+    W = (torch.randn((n_pol, n_opt + 1, 5, 1296), generator=g) * 1e-3).to(ctx.device)
+    gates = torch.stack([gatefit.shipped_gate(W[c]) for c in range(n_pol)]).contiguous()
+    eps = torch.full((n_pol,), 0.05, dtype=torch.float32, device=ctx.device)
+    enabled = torch.full((n_pol,), mask, dtype=torch.int32, device=ctx.device)
+    tail = {"pop": (), "clf": (tabs,), "gate": (tabs, gates)}
+    side = {name: {"st": rig.state_on(ctx, m, n), "au": GateAudit(n, ctx.device), "t": 0, "us": []} for name in tail}
+
+    def roll(name, **kw):
+        s = side[name]
+        ctx.rollout(s["st"], W, clf.view(-1), mask, s["t"], k, audit=s["au"], population=(eps, enabled) + tail[name], **kw)
+        s["t"] += k
+
+    for name in side:
+        roll(name); roll(name)
+    for _ in range(rounds):
+        for name in side:
+            side[name]["us"].append(rig.timed(lambda: roll(name), 3) * 1e6 / k)
+    stats = EpisodeStats(n_opt + 1, n, ctx.device)
+    roll("gate", stats=stats)
+    torch.cuda.synchronize()
+    offers = float(stats.entries.sum() + stats.declines.sum()) / (n * k)
+    (pop, pop_mm), (pc, pc_mm), (pg, pg_mm) = (_arm(side[x]["us"]) for x in ("pop", "clf", "gate"))
+    return {"policies": n_pol, "n_per": n_per, "k": k, "options": n_opt, "population_us_per_step": pop, "population_min_max_us": pop_mm,
+            "population_clf_us_per_step": pc, "population_clf_min_max_us": pc_mm, "population_gate_us_per_step": pg,
+            "population_gate_min_max_us": pg_mm, "gate_over_clf": round(pg / pc, 4), "gate_over_population": round(pg / pop, 4),
+            "offers_per_env_step": round(offers, 5),
+            "population_clf_rounds_us": [round(v, 2) for v in side["clf"]["us"]], "population_gate_rounds_us": [round(v, 2) for v in side["gate"]["us"]]}
+
+
 def bench_logits(rounds, n=65536):
     """µs per call of scg_classifier_logits against scg_classifier_predict on n points and one row, timed alternately (100 calls a round)."""
     import torch
@@ -335,8 +383,14 @@ def main():
                     help="instead: a population rollout (SPEC §21) of C policies x 4096 envs against C sequential audited rollouts and one of C x 4096 envs")
     ap.add_argument("--population-clf", type=int, nargs="+", default=None,
                     help="instead: the population rollout with a classifier table per policy (SPEC §24.1) against the same launch without one")
+    ap.add_argument("--population-gate", type=int, nargs="+", default=None,
+                    help="instead: the population rollout with a gate table per policy (SPEC §25.1) against --population-clf's launch and the plain one")
     ap.add_argument("--logits", action="store_true", help="instead (or after --population-clf): scg_classifier_logits against scg_classifier_predict at 65 536 points")
     a = ap.parse_args()
+    if a.population_gate:
+        for c in a.population_gate:
+            print(json.dumps(bench_population_gate(c, a.k, a.rounds)), flush=True)
+        return
     if a.population_clf or a.logits:
         for c in a.population_clf or []:
             print(json.dumps(bench_population_clf(c, a.k, a.rounds)), flush=True)
