@@ -107,6 +107,22 @@ int scg_step(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *op
              uint8_t *done, float *W, const float *clf, uint32_t enabled_mask, uint64_t t,
              uint32_t flags, void *stream);
 
+/* scg_step under a gate table (SPEC §26.1). `gate` is a DEVICE array [n_vf][2][5][1296] in SPEC §25's layout: row [k][0] the option
+ * side, [k][1] the root side, row 0 never read. Bit k of gate_mask (1 <= k <= n_options): an env about to enter option k does so iff
+ * max_a Q(s_next, a) under gate[k][0] >= the same under gate[k][1] (SPEC §3.1's evaluation order, §5's max order; a NaN on either side
+ * declines). An option whose bit is clear keeps §4.2's comparison on this step's W. Nothing else differs from scg_step: an entered env's
+ * qcache is Q_k(s_next, .) under W, a declined one's Q_0(s_next, .) with option_id = -k; actions, events, ring, gestation counts, G, n_k
+ * and the applied W are scg_step's by bits, and the env order prepared by a learning step is that of the ids it leaves.
+ * gate_mask == 0 is scg_step (gate is not read; the same launches). Otherwise one small launch runs between the step kernel and the
+ * reduce / commit launch; `gate` is never written, the launch waits for no other workgroup and raises no asynchronous failure bit.
+ * Errors: scg_step's, in its sequence; behind them SCG_ERR_INVALID (nothing launched, nothing written), in this order:
+ * gate_mask != 0 with gate == NULL; gate_mask with bit 0 or a bit >= n_vf; gate_mask != 0 with SCG_STEP_INTERRUPT; gate_mask != 0 with
+ * the diagnostic flag 0x100. */
+int scg_step_gated(scg_ctx *ctx, float *x, float *y, float *vx, float *vy, int32_t *option_id,
+                   int32_t *opt_steps, int32_t *ep_steps, float *qcache, uint8_t *action, float *reward,
+                   uint8_t *done, float *W, const float *clf, uint32_t enabled_mask, uint64_t t,
+                   uint32_t flags, void *stream, const float *gate, uint32_t gate_mask);
+
 /* ---- acting rollouts (SPEC §8): K acting steps in ONE launch, no learning ----
  * scg_rollout advances the envs n_steps times from t0 exactly as n_steps calls of scg_step(flags = 0) at t = t0 .. t0+n_steps-1
  * would (state, option_id, opt_steps, ep_steps and qcache after every step; action / reward / done of the last step), bit for

@@ -170,6 +170,7 @@ _SIGS = {
     "scg_set_hparams": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "scg_set_map": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     "scg_step": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_uint32, _P]),
+    "scg_step_gated": (C.c_int, [_P] + [_P] * 13 + [C.c_uint32, C.c_uint64, C.c_uint32, _P, _P, C.c_uint32]),
     "scg_rollout": (C.c_int, _ROLLOUT + [_P]),
     "scg_option_trials": (C.c_int, _TRIALS + [_P]),
     "scg_rollout_record": (C.c_int, _ROLLOUT + [C.POINTER(Record), _P]),

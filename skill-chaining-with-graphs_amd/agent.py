@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from . import dist as _dist
+from . import gatefit
 from . import initfit
 from ._lib import CLF_STRIDE, NUM_ACTIONS, NUM_FEATURES, ScgError, auto_block_envs
 from .core import EnvState, ScgContext
@@ -76,6 +77,10 @@ class SkillChainingAgent:
         # SPEC §25.3: the gate table evaluate() / evaluate_policies() act under by default ([n_vf, 2, 5, 1296], gatefit), or None for
         # §4.2's own comparison; stored by improve_gate(apply=True). The learner and every other kernel ignore it; not in state_dict()
         self.gate = None
+        # SPEC §26.2: the gate table the LEARNER's step-batches take their entry decisions from (set_learner_gate), with the mask of
+        # the options that compare under it, or None for §4.2's own comparison on W. Independent of `gate`; not in state_dict()
+        self.learner_gate = None
+        self.learner_gate_mask = 0
         self.gest_mask = 0            # SPEC §4.4: options in gestation
         self._gest_need = {}
         self.t = 0
@@ -339,6 +344,35 @@ class SkillChainingAgent:
         g = torch.Generator(device="cpu").manual_seed(seed)
         self.W.copy_(torch.randn(self.W.shape, generator=g) * std)
 
+    # ------------------------------------------------------------------ SPEC §26.2: the learner's gate table
+    def _chk_learner_gate(self) -> None:
+        if self.group is not None:
+            raise ValueError("a learner gate is not available on a sharded agent (the table would have to be identical on every rank)")
+        if self.interrupt_learning:
+            raise ValueError("a learner gate with interrupt_learning=True is not defined (SPEC §26.1)")
+
+    def set_learner_gate(self, table, options=None) -> None:
+        """Let every following step_batch (learning or acting, chain_skills / grow_skill_tree included) take the entry decisions of
+        `options` from the gate table `table` ([n_vf, 2, 5, 1296], gatefit's layout) instead of from §4.2's comparison on W; every
+        other option keeps that comparison, and nothing else about the step changes (SPEC §26). `options` is an iterable of option
+        numbers; the default is every option whose row of `table` differs from all-zero on either side (so a table built by
+        gatefit.advantage_gate over gatefit.always_enter masks exactly the fitted options; for gatefit.always_enter itself, whose
+        rows are all zero, name the options). set_learner_gate(None) clears it. The table is copied to the agent's device and
+        kept as `learner_gate`, the mask as `learner_gate_mask`; `gate`, the evaluation gate, is independent and unchanged.
+        ValueError on a sharded agent, with interrupt_learning=True, for a misshapen table or an option outside 1 .. n_options."""
+        if table is None:
+            self.learner_gate, self.learner_gate_mask = None, 0
+            return
+        self._chk_learner_gate()
+        g = torch.as_tensor(table, dtype=torch.float32)
+        if tuple(g.shape) != (self.n_vf, 2, NUM_ACTIONS, NUM_FEATURES):
+            raise ValueError(f"set_learner_gate: the table must be [{self.n_vf}, 2, {NUM_ACTIONS}, {NUM_FEATURES}], not {tuple(g.shape)}")
+        if options is None:
+            options = gatefit.nonzero_options(g)
+        mask = gatefit.mask_of(options, self.n_vf)
+        self.learner_gate = g.to(self.ctx.device).contiguous().clone()
+        self.learner_gate_mask = mask
+
     # ------------------------------------------------------------------ the hot path
     def step_batch(self, learn: bool = True) -> None:
         """One fused step-batch over all envs (act, physics, options, features, Q, TD, update). A learning step-batch interrupts
@@ -347,8 +381,13 @@ class SkillChainingAgent:
         shared = self.group is not None and learn
         if shared and self.transport != "peer":
             gp = self.ctx.grad_packed()                  # G and the update counts: ONE all-reduce operand
-        self.ctx.step(self.state, self.W, self.clf, self.enabled_mask, self.t, learn=learn, apply=not shared,
-                      interrupt=learn and self.interrupt_learning)
+        if self.learner_gate is not None:                # SPEC §26.2: the masked options' entry decisions come from the table
+            self._chk_learner_gate()
+            self.ctx.step(self.state, self.W, self.clf, self.enabled_mask, self.t, learn=learn, apply=not shared,
+                          gate=self.learner_gate, gate_mask=self.learner_gate_mask)
+        else:
+            self.ctx.step(self.state, self.W, self.clf, self.enabled_mask, self.t, learn=learn, apply=not shared,
+                          interrupt=learn and self.interrupt_learning)
         if shared and self.transport == "peer":
             # the step left the operand in this rank's peer region: ONE call publishes it, waits for every rank's and applies their sum
             try:

@@ -157,12 +157,23 @@ class ScgContext:
         self._chk(W, f32, n_tables * self.n_vf * W_ROW, "W"); _chk_clf(self, clf)
 
     def step(self, st: "EnvState", W: torch.Tensor, clf: torch.Tensor, enabled_mask: int, t: int,
-             learn: bool = True, apply: bool = True, interrupt: bool = False) -> None:
+             learn: bool = True, apply: bool = True, interrupt: bool = False, gate: torch.Tensor = None, gate_mask: int = 0) -> None:
         """One fused step-batch (SPEC §1.3-§5). `interrupt` (learning steps only; with learn=False it raises ScgError): SPEC §12's
         interrupting learner — an option that would go on stops where the root's value at the next state is higher, and its
-        update item bootstraps from the root's value."""
+        update item bootstraps from the root's value. `gate` / `gate_mask` (SPEC §26.1, scg_step_gated): a gate table
+        [n_vf][2][5][1296] (SPEC §25's layout) on the context's device, and the options (bit k, 1 <= k <= n_options) whose entry
+        decisions compare under it instead of under this step's W; gate_mask = 0 is the plain step, and `gate` is then not looked at."""
         if not (0 <= t < 2 ** 64):                            # (before the cached fast path: C.c_uint64 would wrap it silently)
             raise ScgError("step: t must be a 64-bit unsigned step counter")
+        gate_mask = int(gate_mask)
+        name, tail = "scg_step", ()
+        if gate_mask:
+            if gate_mask < 0 or (gate_mask & 1) or (gate_mask >> self.n_vf):
+                raise ScgError(f"step: gate_mask {gate_mask:#x} names the root or an option beyond the context's {self.n_vf - 1}")
+            if not isinstance(gate, torch.Tensor) or tuple(gate.shape) != (self.n_vf, 2, NUM_ACTIONS, NUM_FEATURES):
+                raise ScgError(f"step: gate must be a tensor [{self.n_vf}, 2, {NUM_ACTIONS}, {NUM_FEATURES}] (SPEC §25's layout)")
+            self._chk(gate, torch.float32, self.n_vf * 2 * W_ROW, "gate")
+            name, tail = "scg_step_gated", (_ptr(gate), C.c_uint32(gate_mask))
         # the validated, pre-marshalled pointer arguments of the last call are reused while the same tensors come back
         # (one step is two kernel launches: the host side of a call matters in short runs)
         # (the key holds every tensor's storage address, not only the Python ids: `.data =` / `set_()` on the same object
@@ -173,8 +184,9 @@ class ScgContext:
         cached = getattr(self, "_step_args", None)
         if cached is not None and cached[0] == key:
             flags = self._step_flags(learn, apply, interrupt)
-            _lib.check(self._step_fn(self._ctx, *cached[1], C.c_uint32(enabled_mask), C.c_uint64(t), C.c_uint32(flags),
-                                     self._stream()), self._ctx, "scg_step", self.lib)
+            fn = getattr(self.lib, name) if tail else self._step_fn
+            _lib.check(fn(self._ctx, *cached[1], C.c_uint32(enabled_mask), C.c_uint64(t), C.c_uint32(flags), self._stream(), *tail),
+                       self._ctx, name, self.lib)
             return
         self._chk_operands(st, W, clf)
         flags = self._step_flags(learn, apply, interrupt)
@@ -187,7 +199,7 @@ class ScgContext:
         self._step_keep = (st, st.x, st.y, st.vx, st.vy, st.option_id, st.opt_steps, st.ep_steps, st.qcache, st.action,
                            st.reward, st.done, W, clf)    # keeps the ids (and the cached pointers) from being recycled
         self._step_args = (key, ptrs)
-        self._call("scg_step", *ptrs, C.c_uint32(enabled_mask), C.c_uint64(t), C.c_uint32(flags), self._stream())
+        self._call(name, *ptrs, C.c_uint32(enabled_mask), C.c_uint64(t), C.c_uint32(flags), self._stream(), *tail)
 
     def _chk_record(self, record, N: int, min_rows: int, what: str):
         """The scg_record of a Trajectory whose window lies inside N items, on this device (SPEC §10)."""

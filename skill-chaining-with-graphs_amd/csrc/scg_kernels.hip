@@ -28,6 +28,8 @@
 // scg_rollout_population.hip is a unit of the same kind: SPEC §21's four population instantiations of rollout_kernel,
 // reached through the same launch_rollout<REC, Args>; with SPEC §24.1's pop_clf the same four stage a classifier table per policy
 // (DESIGN §3.29); SPEC §25.1's pop_gate takes a fifth one, whose value gate compares under a gate table per policy.
+// scg_step_gate.hip is another: SPEC §26's step_gate_kernel (scg_step_gate_kernel.hpp: here its arguments and launch_step_gate's declaration
+// only), launched by scg_step_gated between td_kernel and the reduce launch.
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -56,6 +58,7 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 #include "scg_aux_kernels.hpp"
 #include "scg_gram_kernel.hpp"
 #include "scg_basis_kernels.hpp"
+#include "scg_step_gate_kernel.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -561,6 +564,31 @@ static int prof_begin(scg_ctx *c, hipStream_t s, hipEvent_t &ev1) {
 int scg_step(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
              int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done, float *W,
              const float *clf, uint32_t enabled_mask, uint64_t t, uint32_t flags, void *stream) {
+    return scg_step_gated(c, x, y, vx, vy, option_id, opt_steps, ep_steps, qcache, action, reward, done, W, clf, enabled_mask, t, flags,
+                          stream, nullptr, 0u);
+}
+
+// positions per workgroup of a step_gate_kernel launch: the largest of 64, 128, 256 that still gives every CU a workgroup (DESIGN
+// §3.31: a short range at small env counts, where the launch is latency, full units at large ones); the results do not depend on it.
+// SCG_STEP_GATE_ENVS (64, 128 or 256) pins it instead: a hook for tests and measurements, as SCG_ROLLOUT_EPW. false: another value
+static bool step_gate_envs(const scg_ctx *c, int &envs) {
+    envs = SG_MIN_ENVS;
+    while (envs < SG_MAX_ENVS && (long long)c->cfg.n_envs >= (long long)c->n_cu * envs * 2) envs *= 2;
+    if (const char *ov = getenv("SCG_STEP_GATE_ENVS")) {
+        const int v = atoi(ov);
+        if (v != 64 && v != 128 && v != 256) return false;
+        envs = v;
+    }
+    return true;
+}
+
+// SPEC §26.1: scg_step whose entry decisions of the options in gate_mask compare under a gate table. gate_mask == 0 is scg_step, launch
+// for launch; otherwise step_gate_kernel runs between td_kernel and the reduce launch (also in front of an acting-only step's commit
+// launch) and re-decides the entering envs from what td_kernel left in their result lines.
+int scg_step_gated(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *option_id, int32_t *opt_steps,
+                   int32_t *ep_steps, float *qcache, uint8_t *action, float *reward, uint8_t *done, float *W,
+                   const float *clf, uint32_t enabled_mask, uint64_t t, uint32_t flags, void *stream,
+                   const float *gate, uint32_t gate_mask) {
     if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_step: null ctx");
     if (!c->have_map) return fail(c, SCG_ERR_STATE, "scg_step: scg_set_map has not been called");
     if (!x || !y || !vx || !vy || !option_id || !opt_steps || !ep_steps || !qcache || !action || !reward ||
@@ -587,6 +615,16 @@ int scg_step(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *opti
                                               "(freed before scg_arm_collect(0)?); the trigger has been disarmed");
             }
         }
+    }
+    int gate_envs = 0;
+    if (gate_mask) {                                // SPEC §26.1's refusals, behind scg_step's own and in this order
+        if (!gate) return fail(c, SCG_ERR_INVALID, "scg_step_gated: gate_mask without a gate table");
+        if ((gate_mask & 1u) || (c->n_vf < 32 && (gate_mask >> c->n_vf)))
+            return fail(c, SCG_ERR_INVALID, "scg_step_gated: gate_mask names the root (bit 0) or an option the context does not have");
+        if (flags & SCG_STEP_INTERRUPT)
+            return fail(c, SCG_ERR_INVALID, "scg_step_gated: gate_mask with SCG_STEP_INTERRUPT (a gated interrupting learner is not defined)");
+        if (flags & 0x100u) return fail(c, SCG_ERR_INVALID, "scg_step_gated: gate_mask with the diagnostic flag 0x100 (no values to commit)");
+        if (!step_gate_envs(c, gate_envs)) return fail(c, SCG_ERR_INVALID, "scg_step_gated: SCG_STEP_GATE_ENVS must be 64, 128 or 256");
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     StepArgs A;
@@ -616,6 +654,13 @@ int scg_step(scg_ctx *c, float *x, float *y, float *vx, float *vy, int32_t *opti
     else
         hipLaunchKernelGGL(td_kernel<MODE_FUSED>, dim3(c->nblk), dim3(THREADS), 0, s, A);
     SCG_HIP(c, hipGetLastError());
+    if (gate_mask) {                                // SPEC §26.1: the masked options' entering envs are re-decided under the table
+        StepGateArgs GA;
+        memset(&GA, 0, sizeof(GA));
+        GA.outrec = c->d_outrec; GA.perm = c->d_perm; GA.hist_next = A.hist_next; GA.gate = gate; GA.fail_flag = c->d_fail;
+        GA.n = c->cfg.n_envs; GA.n_vf = c->n_vf; GA.mask = gate_mask;
+        SCG_HIP(c, launch_step_gate(GA, gate_envs, s));
+    }
     if (ev1) SCG_HIP(c, hipEventRecord(ev1, s));
     // results reach the caller's arrays through the commit workgroups of the reduce launch (or a commit launch)
     c->arm_rows_ready = c->arm_bits && c->events && c->ring_x;      // ... which also leave an announced trigger's row totals

@@ -74,3 +74,20 @@ def candidate_gates(W, u: dict) -> list:
     if len(ks) >= 2:
         out.append(("all", advantage_gate(base, {k: u[k] for k in ks})))
     return out
+
+
+def mask_of(options, n_vf: int) -> int:
+    """The gate mask of SPEC §26.1 for an iterable of option numbers: bit k for each k, 1 <= k < n_vf (ValueError otherwise)."""
+    mask = 0
+    for k in options:
+        k = int(k)
+        if not (1 <= k < int(n_vf)):
+            raise ValueError(f"mask_of: option {k} is outside 1 .. {int(n_vf) - 1}")
+        mask |= 1 << k
+    return mask
+
+
+def nonzero_options(gate) -> list:
+    """The options k >= 1 whose row of the table differs from all-zero on either side: set_learner_gate's default choice."""
+    g = _table(gate)
+    return [k for k in range(1, g.shape[0]) if bool((g[k] != 0).any())]
