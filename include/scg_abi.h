@@ -556,6 +556,30 @@ int scg_basis_gram_irls(scg_ctx *ctx, int32_t order, int64_t n, const float *x, 
 /* Option.policy value part (SPEC §3.1): q[5][n] = Q_k(s, .) for one VF Wk[5][1296]. */
 int scg_q_values(scg_ctx *ctx, int32_t n, const float *x, const float *y, const float *vx,
                  const float *vy, const float *Wk, float *q, void *stream);
+/* ---- lambda-return targets (SPEC §27): one greedy value per recorded row, and the backward scan over every env's rows.
+ * Reporting instruments of the value fits: nothing acts or learns with them. Both need no map and raise no asynchronous status. */
+#define SCG_ROW_NONE 255   /* a row's table entry that names no table */
+/* Row values (SPEC §27.1): v[i] = max_a Q_{tab[i]}(s_i, a) for the table W[tab[i]][5][1296], and a[i] the lowest index that attains it.
+ * Each Q has the bits scg_q_values gives for Wk = W[tab[i]] (SPEC §3.1's order); the max is SPEC §5's (m = Q[0]; m = max(m, Q[1]);
+ * ...). A row with tab[i] == SCG_ROW_NONE or tab[i] >= n_tab gets v = +0, a = 255, and its state is not read. n_tab in [1, n_vf]. The
+ * same bits from every block build and every launch geometry. Preconditions and stream behaviour are scg_q_values'; writes v and a
+ * only; n = 0 succeeds and writes nothing. SCG_ERR_INVALID, nothing launched, in this sequence: a null ctx, n < 0, a null array other
+ * than a, n_tab out of range. */
+int scg_row_values(scg_ctx *ctx, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                   const uint8_t *tab, const float *W /* [n_tab][5][1296] */, int32_t n_tab,
+                   float *v /* [n] */, uint8_t *a /* [n], may be NULL */, void *stream);
+/* Lambda returns (SPEC §27.2) of a record in (env, row) order: env e owns rows offsets[e] .. offsets[e + 1] - 1 of the `total` rows (the
+ * kernel clamps both ends into [0, total], so no offsets make it read or write outside the arrays). Per env, in binary64, every
+ * operation rounded once and none fused, backwards from the env's last row: the root stream y0 on every row (r; r + gamma v0 on the
+ * last row of a record cut before its episode ended; else r + gamma ((1 - lam) v0 + lam y0')) and the option stream yk on the rows with
+ * vf >= 1 (+0 elsewhere), which carries r_option_success on a SUCCESS row, goes over to the root stream where the option ends (term
+ * != 0) and bootstraps from vk while it goes on. Row 0 of an env is its begin row: +0 both. SPEC §27.2 has every case. A non-finite
+ * value leaves its env's outputs unspecified from that row backwards. Writes y0 and yk only. SCG_ERR_INVALID, nothing launched: a
+ * null ctx, n_env < 0, total < 0, a null array, gamma or lam outside [0, 1] or NaN. */
+int scg_lambda_returns(scg_ctx *ctx, int32_t n_env, const int64_t *offsets /* DEVICE [n_env + 1] */, int64_t total,
+                       const float *reward, const uint8_t *done, const uint8_t *vf, const uint8_t *term,
+                       const float *v0, const float *vk, double gamma, double lam, double r_option_success,
+                       double *y0, double *yk /* [total] */, void *stream);
 /* SkillChainingAgent.q_update on explicit transitions for one VF (SPEC §5): accumulates G_k and n_k
  * into the ctx gradient buffers at VF index k (other VFs zeroed), optionally applies to Wk_all. */
 int scg_q_update(scg_ctx *ctx, int32_t n, int32_t k, const float *x, const float *y, const float *vx,

@@ -798,7 +798,7 @@ class SkillChainingAgent:
 
     def fit_values_to_returns(self, n_episodes: int = 4096, epsilon: float = 0.1, seed: Optional[int] = None, vfs=None,
                               ridge: float = 1e-3, apply: bool = False, interrupt: bool = False, choose: Optional[str] = None,
-                              keep: bool = False, order: Optional[int] = None, trajectory=None):
+                              keep: bool = False, order: Optional[int] = None, trajectory=None, lam: Optional[float] = None, sweeps: int = 1):
         """The best linear fit of each Q_k to the returns its own policy realises (SPEC §16): record_episodes() with the current
         policy, Monte-Carlo targets by valuefit.returns_to_go, then per value function k of `vfs` (default: all) and action a the
         ridge regression of the residual y - Q_k^old on the 1296 features over the rows with vf = k, action = a of the EVEN envs
@@ -817,9 +817,24 @@ class SkillChainingAgent:
         The report adds "order" and "features" and, per value function, "delta" (float64 [5][F]); W_new is a plain copy of W, and
         apply=True is refused (no kernel acts on F != 1296 weights). order=None is the path above, untouched.
         `trajectory`: a kept record (report["trajectory"] of an earlier call) to fit on instead of recording, as fit_values_lstdq
-        takes one: several orders are then fitted to one record; report["episodes"] is None."""
+        takes one: several orders are then fitted to one record; report["episodes"] is None.
+        `lam` in [0, 1] is SPEC §27's fit to lambda-returns: the targets come from valuefit.lambda_targets under W (lam = 1: the
+        Monte-Carlo return, lam = 0: §17.2's one-step target); samples, split, Gram, ridge and report stay as above. `sweeps` = S
+        re-forms the targets under the previous sweep's W_new on the same record and refits from it (fitted policy evaluation);
+        W_new is the last sweep's. The report adds "lam" and "sweeps" (per sweep "vf" and "W"; report["vf"] is the last sweep's), and
+        per value function "mc": for "fit" and "held_out", old / new against the MONTE-CARLO targets of returns_to_go, so that every
+        lam is judged on §16's scale. `order` together with `lam` is refused, and so is sweeps != 1 without lam. lam=None is the
+        path above, untouched."""
         from .core import fourier_scale_table
         from .valuefit import error_stats, returns_to_go, ridge_solve
+        if lam is not None:
+            if order is not None:
+                raise ScgError("fit_values_to_returns: lam and order cannot be given together (the lambda-return bootstraps from the "
+                               "order-5 tables)")
+            if not (0.0 <= float(lam) <= 1.0):
+                raise ScgError("fit_values_to_returns: lam must be None or lie in [0, 1]")
+        if int(sweeps) < 1 or (lam is None and int(sweeps) != 1):
+            raise ScgError("fit_values_to_returns: sweeps must be >= 1, and 1 without lam")
         if order is not None:
             if order not in _lib.BASIS_ORDERS:
                 raise ScgError(f"fit_values_to_returns: order must be None or one of {_lib.BASIS_ORDERS}")
@@ -861,16 +876,28 @@ class SkillChainingAgent:
                 out[sl] = q[act[sl], np.arange(q.shape[1])]
             return out
 
-        for k in vfs:
+        W_cur = self.W                                         # what the targets bootstrap from and the residual is taken against
+        if lam is not None:
+            from .valuefit import lambda_targets
+            report["lam"], report["sweeps"] = float(lam), []
+        at_sweep = None
+        for sweep, k in ((s, k) for s in range(int(sweeps)) for k in vfs):
+            if lam is not None and sweep != at_sweep:          # a sweep begins: its targets under the sweep before's weights
+                if at_sweep is not None:
+                    report["sweeps"].append({"vf": report["vf"], "W": W_new.clone()})
+                at_sweep = sweep
+                W_cur = W_new.clone()
+                lt = lambda_targets(ectx, flat, W_cur, float(c.gamma), float(lam), float(c.r_option_success))
+                report["vf"] = {}
             rows = smp[flat["vf"][smp] == k]
             rows = np.concatenate([rows[env[rows] % 2 == 0], rows[env[rows] % 2 == 1]])      # the fit half, then the held-out half
             n_fit = int(np.sum(env[rows] % 2 == 0))
             by_action = np.argsort(flat["action"][rows[:n_fit]], kind="stable")
             rows[:n_fit] = rows[:n_fit][by_action]                 # the fit samples by action, (env, row) order within one
             act = flat["action"][rows].astype(np.int64)
-            y = tg["y"][rows]
+            y = tg["y"][rows] if lam is None else lt["y"][rows]
             states = [torch.from_numpy(np.ascontiguousarray(flat[f][rows - 1])).to(dev) for f in ("x", "y", "vx", "vy")]
-            q_old = q_of(states, self.W[k], act)
+            q_old = q_of(states, W_cur[k], act)
             d = (y - q_old.astype(np.float64)).astype(np.float32)
             n_a = np.bincount(act[:n_fit], minlength=NUM_ACTIONS).astype(np.int64)
             offsets = np.concatenate([[0], np.cumsum(n_a)]).astype(np.int64)
@@ -880,7 +907,7 @@ class SkillChainingAgent:
             else:                                              # (F up to 4096: factored on the device)
                 delta = ridge_solve(A, b, n_a, ridge, scale, device=dev)
             if order is None:
-                w_old = self.W[k].cpu().numpy()
+                w_old = W_cur[k].cpu().numpy()
                 w_new = (w_old.astype(np.float64) + delta).astype(np.float32)
                 w_new[n_a == 0] = w_old[n_a == 0]
                 W_new[k] = torch.from_numpy(w_new).to(dev)
@@ -896,12 +923,20 @@ class SkillChainingAgent:
                 rep["delta"] = delta
             for name, sl in half.items():
                 rep[name] = {"old": error_stats(q_old[sl], y[sl]), "new": error_stats(q_new[sl], y[sl])}
+            if lam is not None:
+                y_mc = tg["y"][rows]
+                rep["mc"] = {name: {"old": error_stats(q_old[sl], y_mc[sl]), "new": error_stats(q_new[sl], y_mc[sl])}
+                             for name, sl in half.items()}
             if keep:
                 rep["operands"] = {"states": states, "action": act, "y": y, "d": d, "offsets": offsets, "n_fit": n_fit, "A": A, "b": b,
                                    "rows": rows, "delta": delta}
             report["vf"][k] = rep
+        if lam is not None and at_sweep is not None:
+            report["sweeps"].append({"vf": report["vf"], "W": W_new.clone()})
         if keep:
             report["targets"], report["trajectory"] = tg, traj
+            if lam is not None:
+                report["lambda_targets"] = lt
         if apply:
             for k in vfs:
                 self.W[k].copy_(W_new[k])

@@ -732,6 +732,49 @@ class ScgContext:
         self._call("scg_q_values", n, _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(Wk), _ptr(q), self._stream())
         return q
 
+    # SPEC §27, the instruments of valuefit.lambda_targets
+    def row_values(self, s, tab: torch.Tensor, W: torch.Tensor, actions: bool = True):
+        """SPEC §27.1: (v float32 [n], a uint8 [n] or None) with v[i] = max_a Q_{tab[i]}(s_i, a) under the tables W [n_tab][5][1296]
+        (n_tab = W.shape[0] in 1 .. n_vf), the bits of q_values followed by valuefit.greedy_max, and a[i] the lowest index that
+        attains it. A row whose `tab` (uint8 [n]) is ROW_NONE or >= n_tab gets v = +0, a = 255; its state is not read. Any n."""
+        n = s[0].numel()
+        x, y, vx, vy = self._chk4(s, n, "state")
+        self._chk(tab, torch.uint8, n, "tab")
+        if not isinstance(W, torch.Tensor) or W.dim() != 3 or tuple(W.shape[1:]) != (NUM_ACTIONS, NUM_FEATURES) \
+                or not (1 <= W.shape[0] <= self.n_vf):
+            raise ScgError(f"row_values: W must be [n_tab][{NUM_ACTIONS}][{NUM_FEATURES}] with 1 <= n_tab <= {self.n_vf}")
+        n_tab = int(W.shape[0])
+        self._chk(W, torch.float32, n_tab * W_ROW, "W")
+        v = torch.empty(n, dtype=torch.float32, device=self.device)
+        a = torch.empty(n, dtype=torch.uint8, device=self.device) if actions else None
+        if n:                                                # (an empty tensor has no address; n = 0 writes nothing)
+            self._call("scg_row_values", C.c_int64(n), _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(tab), _ptr(W), n_tab, _ptr(v), _ptr(a),
+                       self._stream())
+        return v, a
+
+    def lambda_returns(self, offsets: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, vf: torch.Tensor, term: torch.Tensor,
+                       v0: torch.Tensor, vk: torch.Tensor, gamma: float, lam: float, r_option_success: float):
+        """SPEC §27.2: (y0, yk) float64 [total], the root and the option stream of the lambda-return over a record in (env, row)
+        order. `offsets`: int64 [n_env + 1] ON THE DEVICE (the kernel clamps them into [0, total]); reward, v0, vk float32 [total];
+        done, vf, term uint8 [total]. Rows no env owns keep +0."""
+        if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.numel() < 1:
+            raise ScgError("lambda_returns: offsets must be an int64 [n_env + 1] tensor on the device")
+        n_env, total = offsets.numel() - 1, reward.numel()
+        self._chk(offsets, torch.int64, n_env + 1, "offsets")
+        for t, name in ((reward, "reward"), (v0, "v0"), (vk, "vk")):
+            self._chk(t, torch.float32, total, name)
+        for t, name in ((done, "done"), (vf, "vf"), (term, "term")):
+            self._chk(t, torch.uint8, total, name)
+        if not (0.0 <= float(gamma) <= 1.0) or not (0.0 <= float(lam) <= 1.0):
+            raise ScgError("lambda_returns: gamma and lam must lie in [0, 1]")
+        y0 = torch.zeros(total, dtype=torch.float64, device=self.device)
+        yk = torch.zeros(total, dtype=torch.float64, device=self.device)
+        if n_env and total:                                  # (an empty tensor has no address)
+            self._call("scg_lambda_returns", n_env, _ptr(offsets), C.c_int64(total), _ptr(reward), _ptr(done), _ptr(vf), _ptr(term),
+                       _ptr(v0), _ptr(vk), C.c_double(gamma), C.c_double(lam), C.c_double(r_option_success), _ptr(y0), _ptr(yk),
+                       self._stream())
+        return y0, yk
+
     def q_update(self, k: int, s, action, r, cont, sn, W: torch.Tensor, apply: bool = True) -> None:
         n = s[0].numel()
         if n > self.n_envs:

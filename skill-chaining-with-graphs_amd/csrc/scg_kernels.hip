@@ -30,6 +30,8 @@
 // (DESIGN §3.29); SPEC §25.1's pop_gate takes a fifth one, whose value gate compares under a gate table per policy.
 // scg_step_gate.hip is another: SPEC §26's step_gate_kernel (scg_step_gate_kernel.hpp: here its arguments and launch_step_gate's declaration
 // only), launched by scg_step_gated between td_kernel and the reduce launch.
+// scg_returns.hip holds SPEC §27's two kernels (scg_returns.hpp: here their arguments and launches only), behind scg_row_values and
+// scg_lambda_returns.
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -59,6 +61,7 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 #include "scg_gram_kernel.hpp"
 #include "scg_basis_kernels.hpp"
 #include "scg_step_gate_kernel.hpp"
+#include "scg_returns.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -1507,6 +1510,39 @@ int scg_basis_values(scg_ctx *c, int32_t order, int64_t n, const float *x, const
     if (n == 0) return SCG_OK;
     const float *st[4] = {x, y, vx, vy};
     SCG_HIP(c, launch_basis_values(order, n, st, V, m, out, reinterpret_cast<hipStream_t>(stream)));
+    return SCG_OK;
+}
+
+// ---- SPEC §27: the instruments of the lambda-return targets
+int scg_row_values(scg_ctx *c, int64_t n, const float *x, const float *y, const float *vx, const float *vy, const uint8_t *tab,
+                   const float *W, int32_t n_tab, float *v, uint8_t *a, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_row_values: null ctx");
+    if (n < 0) return fail(c, SCG_ERR_INVALID, "scg_row_values: n must be >= 0");
+    if (!x || !y || !vx || !vy || !tab || !W || !v) return fail(c, SCG_ERR_INVALID, "scg_row_values: null array argument");
+    if (n_tab < 1 || n_tab > c->n_vf) return fail(c, SCG_ERR_INVALID, "scg_row_values: n_tab out of range [1, n_vf]");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_row_values");
+    if (n == 0) return SCG_OK;
+    const RowValuesArgs A = {x, y, vx, vy, tab, W, v, a, n, n_tab};
+    SCG_HIP(c, launch_row_values(A, reinterpret_cast<hipStream_t>(stream)));
+    return SCG_OK;
+}
+
+int scg_lambda_returns(scg_ctx *c, int32_t n_env, const int64_t *offsets, int64_t total, const float *reward, const uint8_t *done,
+                       const uint8_t *vf, const uint8_t *term, const float *v0, const float *vk, double gamma, double lam,
+                       double r_option_success, double *y0, double *yk, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_lambda_returns: null ctx");
+    if (n_env < 0) return fail(c, SCG_ERR_INVALID, "scg_lambda_returns: n_env must be >= 0");
+    if (total < 0) return fail(c, SCG_ERR_INVALID, "scg_lambda_returns: total must be >= 0");
+    if (!offsets || !reward || !done || !vf || !term || !v0 || !vk || !y0 || !yk)
+        return fail(c, SCG_ERR_INVALID, "scg_lambda_returns: null array argument");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(c, SCG_ERR_INVALID, "scg_lambda_returns: gamma must be in [0, 1]");
+    if (!(lam >= 0.0 && lam <= 1.0)) return fail(c, SCG_ERR_INVALID, "scg_lambda_returns: lam must be in [0, 1]");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_lambda_returns");
+    if (n_env == 0 || total == 0) return SCG_OK;
+    const LambdaReturnsArgs A = {offsets, reward, done, vf, term, v0, vk, y0, yk, gamma, lam, r_option_success, total, n_env};
+    SCG_HIP(c, launch_lambda_returns(A, reinterpret_cast<hipStream_t>(stream)));
     return SCG_OK;
 }
 

@@ -53,6 +53,44 @@ def returns_to_go(traj, gamma: float, r_option_success: float, device="cpu") -> 
     return {"offsets": off, "g": g[e, r].cpu().numpy(), "y": y[e, r].cpu().numpy(), "sample": row >= 1}
 
 
+def lambda_targets(ctx, flat, W, gamma: float, lam: float, r_option_success: float) -> dict:
+    """SPEC §27.3: the lambda-return targets of a record (a Trajectory or its to_numpy() dict) under the value tables W
+    [n_vf][5][1296] (a tensor on ctx's device), formed on the device: the flat record is uploaded, ScgContext.row_values gives
+    every row's bootstrap values — v0 under table 0 on the rows that are not done, vk under the row's own table on the rows with
+    vf >= 1 whose option goes on (term = 0, not done); +0 elsewhere, where §27.2 reads neither — and ScgContext.lambda_returns scans
+    the two streams. Returns, in (env, row) order as returns_to_go does: `offsets`, `y0` and `yk` (float64), `y` (yk on the rows
+    with vf >= 1, y0 elsewhere: consumable where returns_to_go()["y"] is), `sample` (False on every env's row 0) and `v0`, `vk`
+    (float32). lam = 1 with every env ending done gives returns_to_go's g in y0 by bits; lam = 0 gives SPEC §17.2's targets.
+    The offsets are checked here (non-decreasing, inside [0, total]) before anything is uploaded."""
+    from ._lib import NUM_ACTIONS, NUM_FEATURES, ROW_NONE
+    flat = flat.to_numpy() if isinstance(flat, Trajectory) else flat
+    off = np.ascontiguousarray(np.asarray(flat["offsets"], np.int64).reshape(-1))
+    total = len(flat["reward"])
+    if len(off) < 1 or off[0] < 0 or off[-1] > total or np.any(np.diff(off) < 0):
+        raise ScgError("lambda_targets: offsets must be non-decreasing and inside [0, total]")
+    if not (0.0 <= float(lam) <= 1.0) or not (0.0 <= float(gamma) <= 1.0):
+        raise ScgError("lambda_targets: gamma and lam must lie in [0, 1]")
+    dev = ctx.device
+    up = lambda v, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(v, dt))).to(dev)
+    done, vf, term = (np.asarray(flat[f], np.uint8) for f in ("done", "vf", "term"))
+    tab0 = np.where(done == 0, 0, ROW_NONE).astype(np.uint8)
+    tabk = np.where((vf >= 1) & (term == 0) & (done == 0), vf, ROW_NONE).astype(np.uint8)
+    states = [up(flat[f], np.float32) for f in ("x", "y", "vx", "vy")]
+    Wt = W.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES)
+    v0, _ = ctx.row_values(states, up(tab0, np.uint8), Wt[:1], actions=False)
+    vk, _ = ctx.row_values(states, up(tabk, np.uint8), Wt, actions=False)
+    y0, yk = ctx.lambda_returns(up(off, np.int64), up(flat["reward"], np.float32), up(done, np.uint8), up(vf, np.uint8),
+                                up(term, np.uint8), v0, vk, float(gamma), float(lam), float(r_option_success))
+    y0, yk = y0.cpu().numpy(), yk.cpu().numpy()
+    L = np.diff(off)
+    sample = np.zeros(total, bool)
+    if len(L):
+        env = np.repeat(np.arange(len(L)), L)
+        sample[off[0]: off[-1]] = (np.arange(off[0], off[-1]) - off[:-1][env]) >= 1
+    return {"offsets": off, "y0": y0, "yk": yk, "y": np.where(vf >= 1, yk, y0), "sample": sample,
+            "v0": v0.cpu().numpy(), "vk": vk.cpu().numpy()}
+
+
 def ridge_solve(A, b, n, ridge: float, scale, device=None) -> np.ndarray:
     """SPEC §16.3: Delta[a] = (A[a] + Lambda_a)^-1 b[a] with Lambda_a = diag(ridge max(n[a], 1) / scale_f^2), by a float64 Cholesky
     per action. A [n_act][F][F] symmetric (its lower triangle is read), b [n_act][F], n [n_act] sample counts, `scale` §3's
