@@ -580,6 +580,26 @@ int scg_lambda_returns(scg_ctx *ctx, int32_t n_env, const int64_t *offsets /* DE
                        const float *reward, const uint8_t *done, const uint8_t *vf, const uint8_t *term,
                        const float *v0, const float *vk, double gamma, double lam, double r_option_success,
                        double *y0, double *yk /* [total] */, void *stream);
+/* Trace returns (SPEC §28.1): scg_lambda_returns' scan with a trace coefficient per row. action[i] is row i's recorded action, ag[i] the
+ * greedy action at row i's state of the table that acts on row i + 1 (255: none). A row i that is not its env's row 0 carries
+ *   c_i = ((flags & SCG_TRACE_CUT) && action[i] != ag[i - 1]) ? +0 : lam_vf[vf[i] < n_lam ? vf[i] : 0]
+ * (selected, never computed), and the mix at local row j is (1 - c) b + c y' with c = c_{j+1}, 1 - c formed per row by one binary64
+ * subtraction; every case of the two streams is scg_lambda_returns'. Rows without a row j + 1 in their env read no coefficient.
+ * h (optional) is the root stream's effective length: +0 on row 0, 1 on a done row and on an env's last row, else 1 + c_{j+1} h_{j+1};
+ * with h == NULL nothing of it is formed. lam_vf is a HOST array of n_lam values, n_lam in [1, n_vf]. Without SCG_TRACE_CUT and with
+ * every lam_vf[k] = lam, y0 and yk are scg_lambda_returns' at lam by bits; so they are with the flag where action[i] == ag[i - 1] on
+ * every row whose coefficient is read; with the flag and no such row they are scg_lambda_returns' at lam = 0. Writes y0, yk and h only.
+ * SCG_ERR_INVALID, nothing launched, in this sequence: a null ctx, n_env < 0, total < 0, a null array other than h, n_lam out of
+ * range, gamma or a lam_vf[k] outside [0, 1] or NaN, flag bits other than SCG_TRACE_CUT. n_env = 0 and total = 0 succeed and write
+ * nothing. */
+#define SCG_TRACE_CUT 1u   /* cut the trace where the recorded action is not the greedy one (Watkins) */
+int scg_trace_returns(scg_ctx *ctx, int32_t n_env, const int64_t *offsets /* DEVICE [n_env + 1] */, int64_t total,
+                      const float *reward, const uint8_t *done, const uint8_t *vf, const uint8_t *term,
+                      const uint8_t *action, const uint8_t *ag /* [total] */,
+                      const float *v0, const float *vk,
+                      double gamma, const double *lam_vf /* HOST [n_lam] */, int32_t n_lam, uint32_t flags,
+                      double r_option_success,
+                      double *y0, double *yk, double *h /* [total]; h may be NULL */, void *stream);
 /* SkillChainingAgent.q_update on explicit transitions for one VF (SPEC §5): accumulates G_k and n_k
  * into the ctx gradient buffers at VF index k (other VFs zeroed), optionally applies to Wk_all. */
 int scg_q_update(scg_ctx *ctx, int32_t n, int32_t k, const float *x, const float *y, const float *vx,

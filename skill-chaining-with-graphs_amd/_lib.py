@@ -48,6 +48,7 @@ CROSS_GRAM_MACRO_TILE = 96  # include/scg_abi.h SCG_CROSS_GRAM_MACRO_TILE: one w
 BASIS_ORDERS = (3, 5, 7)    # SPEC §18: the orders of the basis-order probe (F = (order + 1)^4 = 256, 1296, 4096 features)
 BASIS_VALUES_MAX_ROWS = 8   # include/scg_abi.h SCG_BASIS_VALUES_MAX_ROWS
 ROW_NONE = 255              # include/scg_abi.h SCG_ROW_NONE: SPEC §27.1's table entry of a row without a table
+TRACE_CUT = 1               # include/scg_abi.h SCG_TRACE_CUT: SPEC §28.1's flag of scg_trace_returns
 
 
 def basis_features(order: int) -> int:
@@ -205,6 +206,8 @@ _SIGS = {
     "scg_basis_gram_irls": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 6 + [C.c_int32, _P, _P, _P, _P]),
     "scg_row_values": (C.c_int, [_P, C.c_int64] + [_P] * 6 + [C.c_int32, _P, _P, _P]),
     "scg_lambda_returns": (C.c_int, [_P, C.c_int32, _P, C.c_int64] + [_P] * 6 + [C.c_double] * 3 + [_P, _P, _P]),
+    "scg_trace_returns": (C.c_int, [_P, C.c_int32, _P, C.c_int64] + [_P] * 8 + [C.c_double, _P, C.c_int32, C.c_uint32, C.c_double]
+                          + [_P] * 4),
     "scg_q_values": (C.c_int, [_P, C.c_int32] + [_P] * 6 + [_P]),
     "scg_q_update": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 12 + [C.c_uint32, _P]),
     "scg_classifier_predict": (C.c_int, [_P, C.c_int32] + [_P] * 4 + [_P]),

@@ -798,7 +798,7 @@ class SkillChainingAgent:
 
     def fit_values_to_returns(self, n_episodes: int = 4096, epsilon: float = 0.1, seed: Optional[int] = None, vfs=None,
                               ridge: float = 1e-3, apply: bool = False, interrupt: bool = False, choose: Optional[str] = None,
-                              keep: bool = False, order: Optional[int] = None, trajectory=None, lam: Optional[float] = None, sweeps: int = 1):
+                              keep: bool = False, order: Optional[int] = None, trajectory=None, lam=None, sweeps: int = 1, trace: str = "peng"):
         """The best linear fit of each Q_k to the returns its own policy realises (SPEC §16): record_episodes() with the current
         policy, Monte-Carlo targets by valuefit.returns_to_go, then per value function k of `vfs` (default: all) and action a the
         ridge regression of the residual y - Q_k^old on the 1296 features over the rows with vf = k, action = a of the EVEN envs
@@ -824,15 +824,35 @@ class SkillChainingAgent:
         W_new is the last sweep's. The report adds "lam" and "sweeps" (per sweep "vf" and "W"; report["vf"] is the last sweep's), and
         per value function "mc": for "fit" and "held_out", old / new against the MONTE-CARLO targets of returns_to_go, so that every
         lam is judged on §16's scale. `order` together with `lam` is refused, and so is sweeps != 1 without lam. lam=None is the
-        path above, untouched."""
+        path above, untouched.
+        `trace` is SPEC §28's choice of the trace. "peng" (the default) with a float `lam` is the path above, call for call.
+        "watkins" takes the targets from valuefit.trace_targets(cut=True) under the sweep's W_cur: the trace is cut wherever the
+        recorded action is not the greedy action of the table bootstrapped from (re-formed every sweep), so the targets evaluate that
+        table's greedy policy. `lam` may be a sequence of n_vf floats, one per value function, with either trace ("peng": through
+        trace_targets(cut=False)). With trace_targets the report adds, per sweep and value function, "cut_share" (the share of its
+        sample rows whose incoming coefficient is 0), "off_greedy" (the share whose recorded action is not the greedy one) and
+        "horizon" (the mean effective length h of the root stream over them) and "a_changed" (the share whose greedy action differs
+        from the one under the sweep before's table; None in the first sweep); report["trace"] names the trace wherever lam is given.
+        Refused: a trace other than the two names, "watkins" without lam, a lam sequence of another length than n_vf or with an
+        entry outside [0, 1]."""
         from .core import fourier_scale_table
         from .valuefit import error_stats, returns_to_go, ridge_solve
+        if trace not in ("peng", "watkins"):
+            raise ScgError(f"fit_values_to_returns: trace must be 'peng' or 'watkins', not {trace!r}")
+        if trace == "watkins" and lam is None:
+            raise ScgError("fit_values_to_returns: trace='watkins' needs lam (the Monte-Carlo path has no trace to cut)")
+        lam_seq = lam is not None and np.ndim(lam) != 0
         if lam is not None:
             if order is not None:
                 raise ScgError("fit_values_to_returns: lam and order cannot be given together (the lambda-return bootstraps from the "
                                "order-5 tables)")
-            if not (0.0 <= float(lam) <= 1.0):
+            if lam_seq:
+                lam = [float(v) for v in lam]
+                if len(lam) != self.n_vf or not all(0.0 <= v <= 1.0 for v in lam):
+                    raise ScgError(f"fit_values_to_returns: a lam sequence must hold {self.n_vf} values in [0, 1], one per value function")
+            elif not (0.0 <= float(lam) <= 1.0):
                 raise ScgError("fit_values_to_returns: lam must be None or lie in [0, 1]")
+        traced = trace == "watkins" or lam_seq                 # SPEC §28: the targets come from trace_targets
         if int(sweeps) < 1 or (lam is None and int(sweeps) != 1):
             raise ScgError("fit_values_to_returns: sweeps must be >= 1, and 1 without lam")
         if order is not None:
@@ -878,8 +898,8 @@ class SkillChainingAgent:
 
         W_cur = self.W                                         # what the targets bootstrap from and the residual is taken against
         if lam is not None:
-            from .valuefit import lambda_targets
-            report["lam"], report["sweeps"] = float(lam), []
+            from .valuefit import lambda_targets, trace_targets
+            report["lam"], report["sweeps"], report["trace"] = (list(lam) if lam_seq else float(lam)), [], trace
         at_sweep = None
         for sweep, k in ((s, k) for s in range(int(sweeps)) for k in vfs):
             if lam is not None and sweep != at_sweep:          # a sweep begins: its targets under the sweep before's weights
@@ -887,7 +907,11 @@ class SkillChainingAgent:
                     report["sweeps"].append({"vf": report["vf"], "W": W_new.clone()})
                 at_sweep = sweep
                 W_cur = W_new.clone()
-                lt = lambda_targets(ectx, flat, W_cur, float(c.gamma), float(lam), float(c.r_option_success))
+                if traced:
+                    ag_prev = lt["ag"] if sweep else None      # the greedy actions under the table of the sweep before
+                    lt = trace_targets(ectx, flat, W_cur, float(c.gamma), lam, float(c.r_option_success), cut=trace == "watkins")
+                else:
+                    lt = lambda_targets(ectx, flat, W_cur, float(c.gamma), float(lam), float(c.r_option_success))
                 report["vf"] = {}
             rows = smp[flat["vf"][smp] == k]
             rows = np.concatenate([rows[env[rows] % 2 == 0], rows[env[rows] % 2 == 1]])      # the fit half, then the held-out half
@@ -927,6 +951,12 @@ class SkillChainingAgent:
                 y_mc = tg["y"][rows]
                 rep["mc"] = {name: {"old": error_stats(q_old[sl], y_mc[sl]), "new": error_stats(q_new[sl], y_mc[sl])}
                              for name, sl in half.items()}
+                if traced:
+                    nan = float("nan")
+                    rep["cut_share"] = float(np.mean(lt["c"][rows] == 0.0)) if len(rows) else nan
+                    rep["off_greedy"] = float(np.mean(lt["cut"][rows])) if len(rows) else nan
+                    rep["horizon"] = float(np.mean(lt["h"][rows])) if len(rows) else nan
+                    rep["a_changed"] = None if ag_prev is None else float(np.mean(lt["ag"][rows - 1] != ag_prev[rows - 1])) if len(rows) else nan
             if keep:
                 rep["operands"] = {"states": states, "action": act, "y": y, "d": d, "offsets": offsets, "n_fit": n_fit, "A": A, "b": b,
                                    "rows": rows, "delta": delta}

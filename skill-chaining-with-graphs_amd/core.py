@@ -775,6 +775,37 @@ class ScgContext:
                        self._stream())
         return y0, yk
 
+    def trace_returns(self, offsets: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, vf: torch.Tensor, term: torch.Tensor,
+                      action: torch.Tensor, ag: torch.Tensor, v0: torch.Tensor, vk: torch.Tensor, gamma: float, lam,
+                      r_option_success: float, cut: bool = True, horizon: bool = False):
+        """SPEC §28.1: (y0, yk, h or None) float64 [total], lambda_returns' two streams with a trace coefficient per row: a row
+        carries lam[its vf] (`lam`: a float, or a sequence of 1 .. n_vf floats; a vf beyond it reads lam[0]), and with `cut` +0 where
+        its recorded `action` is not `ag` of the row before it (uint8 [total] both; ag: the greedy action at a row's state of the
+        table that acts on the next row, 255 for none). `horizon` adds h, the root stream's effective length. The other arguments
+        are lambda_returns'. Rows no env owns keep +0."""
+        if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.numel() < 1:
+            raise ScgError("trace_returns: offsets must be an int64 [n_env + 1] tensor on the device")
+        n_env, total = offsets.numel() - 1, reward.numel()
+        self._chk(offsets, torch.int64, n_env + 1, "offsets")
+        for t, name in ((reward, "reward"), (v0, "v0"), (vk, "vk")):
+            self._chk(t, torch.float32, total, name)
+        for t, name in ((done, "done"), (vf, "vf"), (term, "term"), (action, "action"), (ag, "ag")):
+            self._chk(t, torch.uint8, total, name)
+        lam_vf = [float(lam)] if np.ndim(lam) == 0 else [float(v) for v in lam]
+        if not (1 <= len(lam_vf) <= self.n_vf):
+            raise ScgError(f"trace_returns: lam must be a float or a sequence of 1 .. {self.n_vf} floats")
+        if not (0.0 <= float(gamma) <= 1.0) or not all(0.0 <= v <= 1.0 for v in lam_vf):
+            raise ScgError("trace_returns: gamma and every lam must lie in [0, 1]")
+        y0 = torch.zeros(total, dtype=torch.float64, device=self.device)
+        yk = torch.zeros(total, dtype=torch.float64, device=self.device)
+        h = torch.zeros(total, dtype=torch.float64, device=self.device) if horizon else None
+        if n_env and total:                                  # (an empty tensor has no address)
+            self._call("scg_trace_returns", n_env, _ptr(offsets), C.c_int64(total), _ptr(reward), _ptr(done), _ptr(vf), _ptr(term),
+                       _ptr(action), _ptr(ag), _ptr(v0), _ptr(vk), C.c_double(gamma), (C.c_double * len(lam_vf))(*lam_vf), len(lam_vf),
+                       C.c_uint32(_lib.TRACE_CUT if cut else 0), C.c_double(r_option_success), _ptr(y0), _ptr(yk), _ptr(h),
+                       self._stream())
+        return y0, yk, h
+
     def q_update(self, k: int, s, action, r, cont, sn, W: torch.Tensor, apply: bool = True) -> None:
         n = s[0].numel()
         if n > self.n_envs:

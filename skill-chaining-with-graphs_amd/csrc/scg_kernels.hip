@@ -31,7 +31,7 @@
 // scg_step_gate.hip is another: SPEC §26's step_gate_kernel (scg_step_gate_kernel.hpp: here its arguments and launch_step_gate's declaration
 // only), launched by scg_step_gated between td_kernel and the reduce launch.
 // scg_returns.hip holds SPEC §27's two kernels (scg_returns.hpp: here their arguments and launches only), behind scg_row_values and
-// scg_lambda_returns.
+// scg_lambda_returns, and SPEC §28's trace_returns_kernel behind scg_trace_returns.
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -1543,6 +1543,31 @@ int scg_lambda_returns(scg_ctx *c, int32_t n_env, const int64_t *offsets, int64_
     if (n_env == 0 || total == 0) return SCG_OK;
     const LambdaReturnsArgs A = {offsets, reward, done, vf, term, v0, vk, y0, yk, gamma, lam, r_option_success, total, n_env};
     SCG_HIP(c, launch_lambda_returns(A, reinterpret_cast<hipStream_t>(stream)));
+    return SCG_OK;
+}
+
+// ---- SPEC §28: the scan with a trace coefficient per row
+int scg_trace_returns(scg_ctx *c, int32_t n_env, const int64_t *offsets, int64_t total, const float *reward, const uint8_t *done,
+                      const uint8_t *vf, const uint8_t *term, const uint8_t *action, const uint8_t *ag, const float *v0, const float *vk,
+                      double gamma, const double *lam_vf, int32_t n_lam, uint32_t flags, double r_option_success, double *y0, double *yk,
+                      double *h, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_trace_returns: null ctx");
+    if (n_env < 0) return fail(c, SCG_ERR_INVALID, "scg_trace_returns: n_env must be >= 0");
+    if (total < 0) return fail(c, SCG_ERR_INVALID, "scg_trace_returns: total must be >= 0");
+    if (!offsets || !reward || !done || !vf || !term || !action || !ag || !v0 || !vk || !lam_vf || !y0 || !yk)
+        return fail(c, SCG_ERR_INVALID, "scg_trace_returns: null array argument");
+    if (n_lam < 1 || n_lam > c->n_vf) return fail(c, SCG_ERR_INVALID, "scg_trace_returns: n_lam out of range [1, n_vf]");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(c, SCG_ERR_INVALID, "scg_trace_returns: gamma must be in [0, 1]");
+    for (int k = 0; k < n_lam; ++k)
+        if (!(lam_vf[k] >= 0.0 && lam_vf[k] <= 1.0)) return fail(c, SCG_ERR_INVALID, "scg_trace_returns: lam_vf must be in [0, 1]");
+    if (flags & ~SCG_TRACE_CUT) return fail(c, SCG_ERR_INVALID, "scg_trace_returns: unknown flag bits");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_trace_returns");
+    if (n_env == 0 || total == 0) return SCG_OK;
+    TraceReturnsArgs A = {offsets, reward, done, vf, term, action, ag, v0, vk, y0, yk, h, gamma, r_option_success, {}, total, n_env, n_lam,
+                          flags};
+    for (int k = 0; k < MAX_VF; ++k) A.lam[k] = k < n_lam ? lam_vf[k] : lam_vf[0];
+    SCG_HIP(c, launch_trace_returns(A, reinterpret_cast<hipStream_t>(stream)));
     return SCG_OK;
 }
 

@@ -1,5 +1,6 @@
 // scg_returns.hip — SPEC §27: row_values_kernel (one greedy value per row under a per-row table) and lambda_returns_kernel (the
-// backward scan of the lambda-return over every env's rows), and their launches.
+// backward scan of the lambda-return over every env's rows), SPEC §28: trace_returns_kernel (that scan with a trace coefficient per
+// row), and their launches.
 //
 // A unit of its own for the reason scg_step_gate.hip gives: what shares a module with a kernel may change that kernel's gfx950 code,
 // and here nothing can. The entry points and their checks are in scg_kernels.hip. The wave-phase header comes in for store_z1 and
@@ -185,5 +186,93 @@ __global__ __launch_bounds__(LR_WAVES * 64) void lambda_returns_kernel(const Lam
 
 hipError_t launch_lambda_returns(const LambdaReturnsArgs &A, hipStream_t s) {
     hipLaunchKernelGGL(lambda_returns_kernel, dim3((A.n_env + LR_WAVES - 1) / LR_WAVES), dim3(LR_WAVES * 64), 0, s, A);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ SPEC §28.1
+// lambda_returns_kernel's scan with the trace coefficient a per-row operand: a row's mix takes c = c_{j+1}, the coefficient of the
+// row behind it — +0 where SCG_TRACE_CUT is set and that row's recorded action is not the greedy action `ag` of the row in front,
+// else lam[vf of that row] — and omc = 1 - c, formed per row by one subtraction. c is selected, never computed. A lane reads
+// action[i + 1], ag[i] and vf[i + 1] only where its row has a row behind it in its env (j < L - 1), so i + 1 < hi <= total. The
+// cases, the operation sequence and the carry are lambda_returns_kernel's: with every c = lambda the bits are its bits. WITH_H adds
+// the root stream's horizon h_j = 1 + c h_{j+1} as a third carry; without it nothing of h is formed. A kernel of its own, so that
+// no instruction of lambda_returns_kernel moves.
+template <bool WITH_H>
+__global__ __launch_bounds__(LR_WAVES * 64) void trace_returns_kernel(const TraceReturnsArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int e = blockIdx.x * LR_WAVES + (threadIdx.x >> 6);
+    if (e >= A.n_env) return;                                  // (wave-uniform)
+    int64_t lo = A.offsets[e], hi = A.offsets[e + 1];
+    lo = lo < 0 ? 0 : (lo > A.total ? A.total : lo);           // no offsets reach outside [0, total)
+    hi = hi < lo ? lo : (hi > A.total ? A.total : hi);
+    const int64_t L = hi - lo;
+    const double gamma = A.gamma;
+    const bool cut_on = (A.flags & SCG_TRACE_CUT) != 0;
+    double c0n = 0.0, ckn = 0.0, chn = 0.0;                    // the carry: y0, yk and h of the row behind the chunk
+    for (int64_t top = L; top > 0; top -= 64) {
+        const int64_t base = top - 64, j = base + lane;        // this lane's local row (< top; < 0: no row)
+        int m0 = LR0_END, mk = LRK_NONE;
+        double r = 0.0, rb = 0.0, fix0 = 0.0, fixk = 0.0, mb0 = 0.0, mbk = 0.0, c = 0.0;
+        if (j >= 1) {
+            const int64_t i = lo + j;
+            const bool last = (j == L - 1), end = A.done[i] != 0;
+            const int o = A.vf[i], tm = A.term[i];
+            const double b0 = (double)A.v0[i], bk = (double)A.vk[i];
+            int vn = SCG_ROW_NONE;                             // vf[j + 1]; read, with the coefficient, where row j + 1 exists
+            if (!last) {
+                vn = A.vf[i + 1];
+                const int sel = vn < A.n_lam ? vn : 0;
+                double cl = A.lam[0];                          // (constant indices only: the table stays in scalar registers)
+#pragma unroll
+                for (int k = 1; k < MAX_VF; ++k) cl = (sel == k) ? A.lam[k] : cl;
+                c = (cut_on && A.action[i + 1] != A.ag[i]) ? 0.0 : cl;
+            }
+            const double omc = __dadd_rn(1.0, -c);             // 1 - c, per row
+            r = (double)A.reward[i];
+            m0 = end ? LR0_END : (last ? LR0_LAST : LR0_MIX);
+            fix0 = __dadd_rn(r, __dmul_rn(gamma, b0));         // r + gamma b0
+            mb0 = __dmul_rn(omc, b0);
+            if (o >= 1) {
+                rb = __dadd_rn(r, tm == SCG_TRIAL_SUCCESS ? A.r_succ : 0.0);
+                if (end) mk = LRK_END;
+                else if (tm != 0) {
+                    mk = last ? LRK_FIXED : LRK_ROOT;
+                    fixk = __dadd_rn(rb, __dmul_rn(gamma, b0));
+                } else {
+                    const bool same = !last && vn == o;
+                    mk = same ? LRK_OWN : LRK_FIXED;
+                    fixk = __dadd_rn(rb, __dmul_rn(gamma, bk));
+                    mbk = __dmul_rn(omc, bk);
+                }
+            }
+        }
+        double y0 = 0.0, yk = 0.0, h = 0.0;                    // (row 0, the begin row: +0 all)
+        const int first = base >= 1 ? 0 : (int)(1 - base);     // the chunk's lowest lane that holds a step row
+        for (int i = 63; i >= first; --i) {
+            const double g0 = __dmul_rn(gamma, __dadd_rn(mb0, __dmul_rn(c, c0n)));        // gamma mix(b0, y0')
+            const double gk = __dmul_rn(gamma, __dadd_rn(mbk, __dmul_rn(c, ckn)));        // gamma mix(bk, yk')
+            const double t0 = m0 == LR0_END ? r : (m0 == LR0_LAST ? fix0 : __dadd_rn(r, g0));
+            const double tk = mk == LRK_NONE ? 0.0 : mk == LRK_END ? rb : mk == LRK_FIXED ? fixk
+                            : __dadd_rn(rb, mk == LRK_ROOT ? g0 : gk);
+            if (lane == i) { y0 = t0; yk = tk; }
+            c0n = lane_value(t0, i);
+            ckn = lane_value(tk, i);
+            if (WITH_H) {
+                const double th = m0 == LR0_MIX ? __dadd_rn(1.0, __dmul_rn(c, chn)) : 1.0;
+                if (lane == i) h = th;
+                chn = lane_value(th, i);
+            }
+        }
+        if (j >= 0) {
+            A.y0[lo + j] = y0; A.yk[lo + j] = yk;
+            if (WITH_H) A.h[lo + j] = h;
+        }
+    }
+}
+
+hipError_t launch_trace_returns(const TraceReturnsArgs &A, hipStream_t s) {
+    const dim3 grid((A.n_env + LR_WAVES - 1) / LR_WAVES), block(LR_WAVES * 64);
+    if (A.h) hipLaunchKernelGGL(trace_returns_kernel<true>, grid, block, 0, s, A);
+    else hipLaunchKernelGGL(trace_returns_kernel<false>, grid, block, 0, s, A);
     return hipGetLastError();
 }

@@ -1,5 +1,5 @@
-// scg_returns.hpp — SPEC §27: the arguments and the launches of row_values_kernel and lambda_returns_kernel (both compiled in
-// scg_returns.hip; scg_kernels.hip includes this header for the two entry points' wrappers and holds no code of either kernel).
+// scg_returns.hpp — SPEC §27, §28: the arguments and the launches of row_values_kernel, lambda_returns_kernel and trace_returns_kernel
+// (all compiled in scg_returns.hip; scg_kernels.hip includes this header for the entry points' wrappers and holds no code of the kernels).
 #pragma once
 
 constexpr int RV_WAVES = 4;                    // waves per workgroup = table areas in LDS
@@ -29,5 +29,22 @@ struct LambdaReturnsArgs {
     int32_t n_env;
 };
 
+// SPEC §28.1: the scan with a trace coefficient per row. lambda_returns_kernel's records plus the recorded action and the greedy
+// action of the table that acts on the next row; the coefficients by value function travel in the argument struct.
+struct TraceReturnsArgs {
+    const int64_t *offsets;        // [n_env + 1], clamped as LambdaReturnsArgs'
+    const float *reward;           // [total]
+    const uint8_t *done, *vf, *term;
+    const uint8_t *action, *ag;    // [total] row i's recorded action; the greedy action at row i's state of the table acting on row i + 1
+    const float *v0, *vk;          // [total]
+    double *y0, *yk, *h;           // [total] the two streams and the root stream's horizon (h null: neither formed nor stored)
+    double gamma, r_succ;
+    double lam[scg::MAX_VF];       // lam[k]: the coefficient a row of value function k carries; vf >= n_lam reads lam[0]
+    int64_t total;
+    int32_t n_env, n_lam;          // n_lam in 1 .. MAX_VF
+    uint32_t flags;                // SCG_TRACE_CUT
+};
+
 hipError_t launch_row_values(const RowValuesArgs &A, hipStream_t s);             // A.n >= 1
 hipError_t launch_lambda_returns(const LambdaReturnsArgs &A, hipStream_t s);     // A.n_env >= 1
+hipError_t launch_trace_returns(const TraceReturnsArgs &A, hipStream_t s);       // A.n_env >= 1

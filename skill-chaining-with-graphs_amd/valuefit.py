@@ -53,6 +53,63 @@ def returns_to_go(traj, gamma: float, r_option_success: float, device="cpu") -> 
     return {"offsets": off, "g": g[e, r].cpu().numpy(), "y": y[e, r].cpu().numpy(), "sample": row >= 1}
 
 
+def _checked_offsets(name: str, flat) -> np.ndarray:
+    """The record's offsets as a contiguous int64 [n_env + 1], refused unless non-decreasing and inside [0, total]."""
+    off = np.ascontiguousarray(np.asarray(flat["offsets"], np.int64).reshape(-1))
+    if len(off) < 1 or off[0] < 0 or off[-1] > len(flat["reward"]) or np.any(np.diff(off) < 0):
+        raise ScgError(f"{name}: offsets must be non-decreasing and inside [0, total]")
+    return off
+
+
+def trace_targets(ctx, flat, W, gamma: float, lam, r_option_success: float, cut: bool = True) -> dict:
+    """SPEC §28.2: lambda_targets with a trace coefficient per row (ScgContext.trace_returns). `lam`: a float, or one float per value
+    function. Beside lambda_targets' two row_values calls a third gives `ag`, the greedy action at every row's state of the table
+    that ACTS on the next row — tabA[i] = vf[i + 1] where row i + 1 belongs to the same env and row i ended no episode (done = 0,
+    or an env's row 0: a recorded begin row carries done = 2), else ROW_NONE (ag = 255) —; with `cut` the trace is cut to +0 on
+    every row whose recorded action is not that action (Watkins's Q(lambda): the targets evaluate the greedy policy of W), without
+    it `ag` is formed for the report only. Returns lambda_targets' dict plus `ag` (uint8), `h` (float64: the root stream's effective
+    length, SPEC §28.1), `c` (float64: the coefficient each step row carries, formed here on the host; +0 on an env's row 0) and
+    `cut` (bool: the step rows whose recorded action is not the greedy one, whether or not `cut` is set)."""
+    from ._lib import NUM_ACTIONS, NUM_FEATURES, ROW_NONE
+    flat = flat.to_numpy() if isinstance(flat, Trajectory) else flat
+    off = _checked_offsets("trace_targets", flat)
+    total = len(flat["reward"])
+    dev = ctx.device
+    up = lambda v, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(v, dt))).to(dev)
+    done, vf, term, action = (np.asarray(flat[f], np.uint8) for f in ("done", "vf", "term", "action"))
+    Wt = W.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES)
+    lam_vf = [float(lam)] * int(Wt.shape[0]) if np.ndim(lam) == 0 else [float(v) for v in lam]
+    if len(lam_vf) != int(Wt.shape[0]) or not all(0.0 <= v <= 1.0 for v in lam_vf) or not (0.0 <= float(gamma) <= 1.0):
+        raise ScgError("trace_targets: gamma and lam (a float, or one per value function) must lie in [0, 1]")
+    L = np.diff(off)
+    sample, has_next, begin = (np.zeros(total, bool) for _ in range(3))
+    if len(L):
+        env = np.repeat(np.arange(len(L)), L)
+        row = np.arange(off[0], off[-1]) - off[:-1][env]
+        sample[off[0]: off[-1]] = row >= 1
+        has_next[off[0]: off[-1]] = row < L[env] - 1
+        begin[off[0]: off[-1]] = row == 0                      # (a recorded begin row has done = 2, SPEC §10, and ends no episode)
+    nxt = np.concatenate([vf[1:], np.zeros(min(total, 1), np.uint8)])                 # vf[i + 1] (unused on the last row)
+    tab0 = np.where(done == 0, 0, ROW_NONE).astype(np.uint8)
+    tabk = np.where((vf >= 1) & (term == 0) & (done == 0), vf, ROW_NONE).astype(np.uint8)
+    tabA = np.where(has_next & (begin | (done == 0)), nxt, ROW_NONE).astype(np.uint8)
+    states = [up(flat[f], np.float32) for f in ("x", "y", "vx", "vy")]
+    v0, _ = ctx.row_values(states, up(tab0, np.uint8), Wt[:1], actions=False)
+    vk, _ = ctx.row_values(states, up(tabk, np.uint8), Wt, actions=False)
+    _, ag = ctx.row_values(states, up(tabA, np.uint8), Wt, actions=True)
+    y0, yk, h = ctx.trace_returns(up(off, np.int64), up(flat["reward"], np.float32), up(done, np.uint8), up(vf, np.uint8),
+                                  up(term, np.uint8), up(action, np.uint8), ag, v0, vk, float(gamma), lam_vf, float(r_option_success),
+                                  cut=bool(cut), horizon=True)
+    y0, yk, h, ag = y0.cpu().numpy(), yk.cpu().numpy(), h.cpu().numpy(), ag.cpu().numpy()
+    off_greedy = np.zeros(total, bool)
+    off_greedy[1:] = sample[1:] & (action[1:] != ag[:-1])
+    c = np.where(sample, np.asarray(lam_vf, np.float64)[np.where(vf < len(lam_vf), vf, 0)], 0.0)
+    if cut:
+        c = np.where(off_greedy, 0.0, c)
+    return {"offsets": off, "y0": y0, "yk": yk, "y": np.where(vf >= 1, yk, y0), "sample": sample,
+            "v0": v0.cpu().numpy(), "vk": vk.cpu().numpy(), "ag": ag, "h": h, "c": c, "cut": off_greedy}
+
+
 def lambda_targets(ctx, flat, W, gamma: float, lam: float, r_option_success: float) -> dict:
     """SPEC §27.3: the lambda-return targets of a record (a Trajectory or its to_numpy() dict) under the value tables W
     [n_vf][5][1296] (a tensor on ctx's device), formed on the device: the flat record is uploaded, ScgContext.row_values gives
@@ -64,10 +121,8 @@ def lambda_targets(ctx, flat, W, gamma: float, lam: float, r_option_success: flo
     The offsets are checked here (non-decreasing, inside [0, total]) before anything is uploaded."""
     from ._lib import NUM_ACTIONS, NUM_FEATURES, ROW_NONE
     flat = flat.to_numpy() if isinstance(flat, Trajectory) else flat
-    off = np.ascontiguousarray(np.asarray(flat["offsets"], np.int64).reshape(-1))
+    off = _checked_offsets("lambda_targets", flat)
     total = len(flat["reward"])
-    if len(off) < 1 or off[0] < 0 or off[-1] > total or np.any(np.diff(off) < 0):
-        raise ScgError("lambda_targets: offsets must be non-decreasing and inside [0, total]")
     if not (0.0 <= float(lam) <= 1.0) or not (0.0 <= float(gamma) <= 1.0):
         raise ScgError("lambda_targets: gamma and lam must lie in [0, 1]")
     dev = ctx.device

@@ -13,6 +13,14 @@ by round as tools/gram_bench.py times its arms, every arm ending in a device syn
     lambda_returns_device  the kernel alone on uploaded arrays
     returns_to_go          valuefit.returns_to_go on the same flat record (host)
 
+  --trace: SPEC §28's scan instead of the above, on the same record, every arm the kernel alone on uploaded arrays at lambda = 0.9
+  (v0, vk: the record's row values under W; ag: the greedy action of the acting table, so that the cut falls where it would):
+    lambda_returns_device      ScgContext.lambda_returns, the baseline
+    trace_returns_uncut        ScgContext.trace_returns(cut=False), no horizon: the same targets
+    trace_returns_cut          cut=True, no horizon
+    trace_returns_cut_h        cut=True with the horizon h
+  each round times --reps calls of an arm behind one synchronise (a single call is well under a millisecond).
+
 One JSON line per comparison: per arm the median, fastest and slowest round in ms, the ratio of the medians, and same_bits (the two
 paths' values agree bit for bit; for the scan: y0 is returns_to_go's g where every episode ended done).
 
@@ -31,6 +39,8 @@ def main():
     ap.add_argument("--rows", type=int, default=1 << 20); ap.add_argument("--episodes", type=int, default=2048)
     ap.add_argument("--envs", type=int, default=65536); ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--epsilon", type=float, default=0.1); ap.add_argument("--out", default=None)
+    ap.add_argument("--trace", action="store_true", help="time scg_trace_returns against scg_lambda_returns instead (SPEC §28.4)")
+    ap.add_argument("--reps", type=int, default=20, help="--trace: calls per timed window")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -41,6 +51,13 @@ def main():
     flat = traj.to_numpy()
     total, lines = len(flat["reward"]), []
     up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+    if a.trace:
+        lines.append(json.dumps(trace_row(a, ag, flat, up)))
+        print(lines[-1], flush=True)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
 
     # ---- row values
     n = min(a.rows, total)
@@ -107,6 +124,40 @@ def main():
     if a.out:
         with open(a.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
+
+
+def trace_row(a, ag, flat, up):
+    """--trace: the JSON row of scg_trace_returns against scg_lambda_returns on the record `flat`."""
+    import numpy as np
+    import torch
+    from skill_chaining_with_graphs_amd.valuefit import trace_targets
+    ctx = ag.ctx
+    gamma, R, lam = float(ctx.cfg.gamma), float(ctx.cfg.r_option_success), 0.9
+    lt = trace_targets(ctx, flat, ag.W, gamma, lam, R, cut=True)
+    rec = [up(flat["offsets"]), up(flat["reward"])] + [up(flat[f].astype(np.uint8)) for f in ("done", "vf", "term")]
+    act, agr, v0, vk = up(flat["action"].astype(np.uint8)), up(lt["ag"]), up(lt["v0"]), up(lt["vk"])
+    runs = {"lambda_returns_device": lambda: ctx.lambda_returns(*rec, v0, vk, gamma, lam, R),
+            "trace_returns_uncut": lambda: ctx.trace_returns(*rec, act, agr, v0, vk, gamma, lam, R, cut=False),
+            "trace_returns_cut": lambda: ctx.trace_returns(*rec, act, agr, v0, vk, gamma, lam, R, cut=True),
+            "trace_returns_cut_h": lambda: ctx.trace_returns(*rec, act, agr, v0, vk, gamma, lam, R, cut=True, horizon=True)}
+    base, uncut = runs["lambda_returns_device"](), runs["trace_returns_uncut"]()
+    same = all(torch.equal(x.view(torch.int64), y.view(torch.int64)) for x, y in zip(base, uncut))
+    for fn in runs.values():                                   # every arm once more before the clock
+        fn()
+    times = {name: [] for name in runs}
+    for _ in range(a.rounds):
+        for name, fn in runs.items():
+            times[name].append(rig.timed(fn, a.reps) * 1e3)
+    med = {name: statistics.median(t) for name, t in times.items()}
+    L = np.diff(flat["offsets"])
+    smp = lt["sample"]
+    row = {"what": "trace returns at lambda = 0.9", "rows": len(flat["reward"]), "envs": int(len(L)), "longest_env": int(L.max()),
+           "rounds": a.rounds, "reps": a.reps, "cut_share": round(float(np.mean(lt["cut"][smp])), 4),
+           "mean_horizon": round(float(np.mean(lt["h"][smp])), 3), "uncut_same_bits_as_lambda_returns": bool(same)}
+    row.update({name: gram_bench.spread(t) for name, t in times.items()})
+    for name in list(runs)[1:]:
+        row[f"{name}_over_lambda_returns_device"] = round(med[name] / med["lambda_returns_device"], 4)
+    return row
 
 
 if __name__ == "__main__":
