@@ -600,6 +600,21 @@ int scg_trace_returns(scg_ctx *ctx, int32_t n_env, const int64_t *offsets /* DEV
                       double gamma, const double *lam_vf /* HOST [n_lam] */, int32_t n_lam, uint32_t flags,
                       double r_option_success,
                       double *y0, double *yk, double *h /* [total]; h may be NULL */, void *stream);
+/* Cross row values (SPEC §29.1): the value under one table of the action another table selects. For a row with a table k = tab[i] <
+ * n_tab: qs = Q^sel_k(s_i, .) and qv = Q^val_k(s_i, .) under W_sel[k] and W_val[k], each with the bits scg_q_values gives for that Wk;
+ * m = SPEC §5's max of qs, a* the lowest index that attains it (scg_row_values' rule: five NaNs give index 0); vs[i] = m, a[i] = a*,
+ * v[i] = qv[a*], selected by a chain of constant-index compares and never recomputed. With SCG_CROSS_GIVEN a* = act[i], only W_val is
+ * contracted (W_sel is not read and may be NULL), vs must be NULL, and a row with act[i] >= 5 is a row without a table. A row without
+ * a table (tab[i] == SCG_ROW_NONE or tab[i] >= n_tab) gets v = +0, a = 255, vs = +0, and its state is not read. With W_val == W_sel, v
+ * and a are scg_row_values' by bits and vs == v. The same bits from every block build and every launch geometry. Preconditions, stream
+ * behaviour and n = 0 are scg_row_values'; writes v, a and vs only. SCG_ERR_INVALID, nothing launched, in this sequence: a null ctx,
+ * n < 0, a null array other than a, vs, act (flag clear) and W_sel (flag set), n_tab outside [1, n_vf], flag bits other than
+ * SCG_CROSS_GIVEN, act == NULL or vs != NULL with the flag. */
+#define SCG_CROSS_GIVEN 1u   /* the selecting action is act[i]; W_sel is not read */
+int scg_row_values_cross(scg_ctx *ctx, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
+                         const uint8_t *tab, const float *W_sel, const float *W_val /* [n_tab][5][1296] each */, int32_t n_tab,
+                         const uint8_t *act /* [n]; with SCG_CROSS_GIVEN only, else NULL */, uint32_t flags,
+                         float *v /* [n] */, uint8_t *a /* [n], may be NULL */, float *vs /* [n], may be NULL */, void *stream);
 /* SkillChainingAgent.q_update on explicit transitions for one VF (SPEC §5): accumulates G_k and n_k
  * into the ctx gradient buffers at VF index k (other VFs zeroed), optionally applies to Wk_all. */
 int scg_q_update(scg_ctx *ctx, int32_t n, int32_t k, const float *x, const float *y, const float *vx,

@@ -49,6 +49,7 @@ BASIS_ORDERS = (3, 5, 7)    # SPEC §18: the orders of the basis-order probe (F 
 BASIS_VALUES_MAX_ROWS = 8   # include/scg_abi.h SCG_BASIS_VALUES_MAX_ROWS
 ROW_NONE = 255              # include/scg_abi.h SCG_ROW_NONE: SPEC §27.1's table entry of a row without a table
 TRACE_CUT = 1               # include/scg_abi.h SCG_TRACE_CUT: SPEC §28.1's flag of scg_trace_returns
+CROSS_GIVEN = 1             # include/scg_abi.h SCG_CROSS_GIVEN: SPEC §29.1's flag of scg_row_values_cross
 
 
 def basis_features(order: int) -> int:
@@ -205,6 +206,7 @@ _SIGS = {
     "scg_logistic_terms": (C.c_int, [_P, C.c_int64] + [_P] * 5 + [_P]),
     "scg_basis_gram_irls": (C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 6 + [C.c_int32, _P, _P, _P, _P]),
     "scg_row_values": (C.c_int, [_P, C.c_int64] + [_P] * 6 + [C.c_int32, _P, _P, _P]),
+    "scg_row_values_cross": (C.c_int, [_P, C.c_int64] + [_P] * 7 + [C.c_int32, _P, C.c_uint32, _P, _P, _P, _P]),
     "scg_lambda_returns": (C.c_int, [_P, C.c_int32, _P, C.c_int64] + [_P] * 6 + [C.c_double] * 3 + [_P, _P, _P]),
     "scg_trace_returns": (C.c_int, [_P, C.c_int32, _P, C.c_int64] + [_P] * 8 + [C.c_double, _P, C.c_int32, C.c_uint32, C.c_double]
                           + [_P] * 4),

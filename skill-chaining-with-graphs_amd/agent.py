@@ -798,7 +798,8 @@ class SkillChainingAgent:
 
     def fit_values_to_returns(self, n_episodes: int = 4096, epsilon: float = 0.1, seed: Optional[int] = None, vfs=None,
                               ridge: float = 1e-3, apply: bool = False, interrupt: bool = False, choose: Optional[str] = None,
-                              keep: bool = False, order: Optional[int] = None, trajectory=None, lam=None, sweeps: int = 1, trace: str = "peng"):
+                              keep: bool = False, order: Optional[int] = None, trajectory=None, lam=None, sweeps: int = 1, trace: str = "peng",
+                              double: bool = False):
         """The best linear fit of each Q_k to the returns its own policy realises (SPEC §16): record_episodes() with the current
         policy, Monte-Carlo targets by valuefit.returns_to_go, then per value function k of `vfs` (default: all) and action a the
         ridge regression of the residual y - Q_k^old on the 1296 features over the rows with vf = k, action = a of the EVEN envs
@@ -834,13 +835,19 @@ class SkillChainingAgent:
         "horizon" (the mean effective length h of the root stream over them) and "a_changed" (the share whose greedy action differs
         from the one under the sweep before's table; None in the first sweep); report["trace"] names the trace wherever lam is given.
         Refused: a trace other than the two names, "watkins" without lam, a lam sequence of another length than n_vf or with an
-        entry outside [0, 1]."""
+        entry outside [0, 1].
+        `double` is SPEC §29.2's double-estimator fit (_fit_values_double: two tables on two folds of the fit half, each
+        bootstrapping from the other's value of its own greedy action; W_new is their mean). It needs lam, is refused with order and
+        works with both traces. double=False is the path above, call for call."""
         from .core import fourier_scale_table
-        from .valuefit import error_stats, returns_to_go, ridge_solve
+        from .valuefit import error_stats, returns_to_go
         if trace not in ("peng", "watkins"):
             raise ScgError(f"fit_values_to_returns: trace must be 'peng' or 'watkins', not {trace!r}")
         if trace == "watkins" and lam is None:
             raise ScgError("fit_values_to_returns: trace='watkins' needs lam (the Monte-Carlo path has no trace to cut)")
+        if double and (lam is None or order is not None):
+            raise ScgError("fit_values_to_returns: double=True needs lam (the Monte-Carlo targets bootstrap from nothing) and "
+                           "cannot be given with order")
         lam_seq = lam is not None and np.ndim(lam) != 0
         if lam is not None:
             if order is not None:
@@ -876,6 +883,8 @@ class SkillChainingAgent:
             ectx = self._eval_context(int(traj.n), epsilon, seed, None)[0]
         flat = traj.to_numpy()
         tg = returns_to_go(flat, float(c.gamma), float(c.r_option_success))
+        if double:
+            return self._fit_values_double(ectx, traj, flat, tg, summary, vfs, ridge, lam, int(sweeps), trace, keep, apply)
         off = flat["offsets"]
         env = np.repeat(np.arange(traj.n), np.diff(off))
         smp = np.nonzero(tg["sample"])[0]                      # the rows that are steps, in (env, row) order; their s is the row before
@@ -923,21 +932,13 @@ class SkillChainingAgent:
             states = [torch.from_numpy(np.ascontiguousarray(flat[f][rows - 1])).to(dev) for f in ("x", "y", "vx", "vy")]
             q_old = q_of(states, W_cur[k], act)
             d = (y - q_old.astype(np.float64)).astype(np.float32)
-            n_a = np.bincount(act[:n_fit], minlength=NUM_ACTIONS).astype(np.int64)
-            offsets = np.concatenate([[0], np.cumsum(n_a)]).astype(np.int64)
-            A, b = gram(states, offsets, torch.from_numpy(d).to(dev))
             if order is None:
-                delta = ridge_solve(A.cpu().numpy(), b.cpu().numpy(), n_a, ridge, scale)
-            else:                                              # (F up to 4096: factored on the device)
-                delta = ridge_solve(A, b, n_a, ridge, scale, device=dev)
-            if order is None:
-                w_old = W_cur[k].cpu().numpy()
-                w_new = (w_old.astype(np.float64) + delta).astype(np.float32)
-                w_new[n_a == 0] = w_old[n_a == 0]
+                n_a, offsets, A, b, delta, w_new = self._refit_rows(gram, states, d, act[:n_fit], ridge, scale, W_cur[k])
                 W_new[k] = torch.from_numpy(w_new).to(dev)
                 q_new = q_of(states, W_new[k], act)
-            else:                                              # the correction lives at order p: Q^new = Q^old + Delta . phi^p
-                q_new = q_old.copy()
+            else:                                              # (F up to 4096: factored on the device)
+                n_a, offsets, A, b, delta, _ = self._refit_rows(gram, states, d, act[:n_fit], ridge, scale, None)
+                q_new = q_old.copy()                           # the correction lives at order p: Q^new = Q^old + Delta . phi^p
                 if len(act):
                     v = ectx.basis_values(order, states, torch.from_numpy(delta.astype(np.float32)).to(dev)).cpu().numpy()
                     q_new = (q_old.astype(np.float64) + v[act, np.arange(len(act))].astype(np.float64)).astype(np.float32)
@@ -971,6 +972,132 @@ class SkillChainingAgent:
             for k in vfs:
                 self.W[k].copy_(W_new[k])
         return report, W_new
+
+    def _refit_rows(self, gram, states, d, act_fit, ridge: float, scale, W_k):
+        """The refit of one table's rows to a residual (SPEC §16.3), the one copy of it: the per-action segments of the fit samples
+        (the first len(act_fit) of `states`, sorted by action), A and b by `gram` with yv = d, Delta by valuefit.ridge_solve — on the
+        host; with W_k None (the basis-order probe: F up to 4096) on the device, and no row is formed — and W_k[a] <-
+        float32(float64 W_k[a] + Delta[a]); an action without samples keeps its row bit for bit. Returns (n_a, offsets, A, b, delta,
+        w_new or None)."""
+        from .valuefit import ridge_solve
+        dev = self.W.device
+        n_a = np.bincount(act_fit, minlength=NUM_ACTIONS).astype(np.int64)
+        offsets = np.concatenate([[0], np.cumsum(n_a)]).astype(np.int64)
+        A, b = gram(states, offsets, torch.from_numpy(d).to(dev))
+        if W_k is None:
+            return n_a, offsets, A, b, ridge_solve(A, b, n_a, ridge, scale, device=dev), None
+        delta = ridge_solve(A.cpu().numpy(), b.cpu().numpy(), n_a, ridge, scale)
+        w_old = W_k.cpu().numpy()
+        w_new = (w_old.astype(np.float64) + delta).astype(np.float32)
+        w_new[n_a == 0] = w_old[n_a == 0]
+        return n_a, offsets, A, b, delta, w_new
+
+    def _fit_values_double(self, ectx, traj, flat, tg, summary, vfs, ridge: float, lam, sweeps: int, trace: str, keep: bool,
+                           apply: bool):
+        """fit_values_to_returns(double=True), SPEC §29.2. Two tables, W_A = W_B = W to start. Every sweep forms two target sets over
+        the whole record by valuefit.double_targets — AB: W_A selects the bootstrap action and W_B values it; BA the other way round —
+        and refits table A on fold A's rows (valuefit.fold_of: env % 4 == 0) to AB against its own Q^old under W_A, table B on fold B's
+        rows (env % 4 == 2) to BA, by _refit_rows. Q^old and Q^new of a sample list are one ScgContext.row_action_values call.
+        W_new = valuefit.mean_table(W_A, W_B); the odd envs stay held out and judge the mean table.
+        The report has the single path's layout: report["vf"][k] (the last sweep's; every sweep's under report["sweeps"][s], with "W"
+        the sweep's mean table and "W_a", "W_b") holds n (fit samples per action, both folds), delta_norm (of the mean table's row) and,
+        for "fit" and "held_out", old / new of the MEAN table against (y_AB + y_BA) / 2, "mc" the same against the Monte-Carlo
+        targets, "cut_share" / "off_greedy" / "horizon" as the mean of the two target sets' — and adds "folds": {"a", "b"}, each n,
+        delta_norm, "fit" and "mc" old / new of the fold's own table on the fold's rows against its own targets (`keep`: "operands"),
+        and "optimism": the mean, over the rows whose target reads a bootstrap value of value function k (k = 0: the rows that are not
+        done, v0; k >= 1: the rows with vf = k whose option goes on, vk) and both target sets, of vs - v, the selecting table's own
+        maximum less the other table's value of that action: the max's bias as the two tables estimate it, exactly 0 in sweep 1.
+        report["double"] = {"W_a", "W_b"} are the last sweep's tables; `keep` adds report["targets"], report["trajectory"] and
+        report["double_targets"] = {"AB", "BA"} (the last sweep's)."""
+        from .valuefit import double_targets, error_stats, fold_of, mean_table
+        c = self.ctx.cfg
+        gamma, r_succ = float(c.gamma), float(c.r_option_success)
+        dev = self.W.device
+        off = flat["offsets"]
+        env = np.repeat(np.arange(traj.n), np.diff(off))
+        smp = np.nonzero(tg["sample"])[0]
+        vf_rows, done = np.asarray(flat["vf"]), np.asarray(flat["done"])
+        lam_seq = np.ndim(lam) != 0
+        report = {"episodes": summary, "ridge": float(ridge), "vf": {}, "lam": list(lam) if lam_seq else float(lam), "sweeps": [],
+                  "trace": trace}
+        nan = float("nan")
+        mean = lambda v: float(np.mean(v)) if len(v) else nan
+        up_states = lambda at: [torch.from_numpy(np.ascontiguousarray(flat[f][at])).to(dev) for f in ("x", "y", "vx", "vy")]
+
+        def q_of(states, W, k, act):                           # Q_k(s_n, a_n) of a sample list under the tables W, one launch
+            n = len(act)
+            tab = torch.full((n,), int(k), dtype=torch.uint8, device=dev)
+            a = torch.from_numpy(np.ascontiguousarray(act.astype(np.uint8))).to(dev)
+            return ectx.row_action_values(states, tab, W.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES), a).cpu().numpy()
+
+        W_a, W_b = self.W.clone(), self.W.clone()
+        for sweep in range(sweeps):
+            cur = {"a": W_a.clone(), "b": W_b.clone()}         # what the sweep's targets bootstrap from and its residuals are taken against
+            W_mean_old = mean_table(cur["a"], cur["b"])
+            cut = trace == "watkins"
+            lt = {"a": double_targets(ectx, flat, cur["a"], cur["b"], gamma, lam, r_succ, cut=cut),        # AB
+                  "b": double_targets(ectx, flat, cur["b"], cur["a"], gamma, lam, r_succ, cut=cut)}        # BA
+            y_d = (lt["a"]["y"] + lt["b"]["y"]) / 2.0
+            new = {"a": W_a, "b": W_b}
+            per_vf = {}
+            for k in vfs:
+                rows_k = smp[vf_rows[smp] == k]
+                fold = fold_of(env[rows_k])
+                rep = {"folds": {}}
+                for f, name in enumerate(("a", "b")):
+                    rows = rows_k[fold == f]
+                    rows = rows[np.argsort(flat["action"][rows], kind="stable")]      # by action, (env, row) order within one
+                    act = flat["action"][rows].astype(np.int64)
+                    y = lt[name]["y"][rows]
+                    states = up_states(rows - 1)
+                    q_old = q_of(states, cur[name], k, act)
+                    d = (y - q_old.astype(np.float64)).astype(np.float32)
+                    n_a, offsets, A, b, delta, w_new = self._refit_rows(ectx.feature_gram, states, d, act, ridge, self.ctx.scale,
+                                                                        cur[name][k])
+                    new[name][k] = torch.from_numpy(w_new).to(dev)
+                    q_new = q_of(states, new[name], k, act)
+                    y_mc = tg["y"][rows]
+                    fr = {"n": [int(v) for v in n_a], "delta_norm": float(np.sqrt(np.sum(delta * delta))),
+                          "fit": {"old": error_stats(q_old, y), "new": error_stats(q_new, y)},
+                          "mc": {"old": error_stats(q_old, y_mc), "new": error_stats(q_new, y_mc)}}
+                    if keep:
+                        fr["operands"] = {"states": states, "action": act, "y": y, "d": d, "offsets": offsets, "A": A, "b": b,
+                                          "rows": rows, "delta": delta}
+                    rep["folds"][name] = fr
+                per_vf[k] = (rows_k, fold, rep)
+            W_mean = mean_table(W_a, W_b)
+            report["vf"] = {}
+            for k, (rows_k, fold, rep) in per_vf.items():      # the mean table, judged once both tables of the sweep stand
+                rep["n"] = [x + y for x, y in zip(rep["folds"]["a"]["n"], rep["folds"]["b"]["n"])]
+                dk = W_mean[k].double() - W_mean_old[k].double()
+                rep["delta_norm"] = float(torch.sqrt(torch.sum(dk * dk)))
+                rep["mc"] = {}
+                for half, at in (("fit", rows_k[fold >= 0]), ("held_out", rows_k[fold < 0])):
+                    act = flat["action"][at].astype(np.int64)
+                    states = up_states(at - 1)
+                    q_old, q_new = q_of(states, W_mean_old, k, act), q_of(states, W_mean, k, act)
+                    rep[half] = {"old": error_stats(q_old, y_d[at]), "new": error_stats(q_new, y_d[at])}
+                    rep["mc"][half] = {"old": error_stats(q_old, tg["y"][at]), "new": error_stats(q_new, tg["y"][at])}
+                if k == 0:
+                    boot, vs, v = done == 0, "vs0", "v0"
+                else:
+                    boot, vs, v = (vf_rows == k) & (np.asarray(flat["term"]) == 0) & (done == 0), "vsk", "vk"
+                gap = np.concatenate([t[vs][boot].astype(np.float64) - t[v][boot].astype(np.float64) for t in lt.values()])
+                rep["optimism"] = mean(gap)
+                rep["optimism_n"] = int(np.sum(boot))
+                rep["cut_share"] = mean([mean(t["c"][rows_k] == 0.0) for t in lt.values()]) if len(rows_k) else nan
+                rep["off_greedy"] = mean([mean(t["cut"][rows_k]) for t in lt.values()]) if len(rows_k) else nan
+                rep["horizon"] = mean([mean(t["h"][rows_k]) for t in lt.values()]) if len(rows_k) else nan
+                report["vf"][k] = rep
+            report["sweeps"].append({"vf": report["vf"], "W": W_mean.clone(), "W_a": W_a.clone(), "W_b": W_b.clone()})
+        report["double"] = {"W_a": W_a, "W_b": W_b}
+        if keep:
+            report["targets"], report["trajectory"] = tg, traj
+            report["double_targets"] = {"AB": lt["a"], "BA": lt["b"]}
+        if apply:
+            for k in vfs:
+                self.W[k].copy_(W_mean[k])
+        return report, W_mean
 
     def fit_values_lstdq(self, n_episodes: int = 4096, epsilon: float = 0.1, seed: Optional[int] = None, vfs=None,
                          ridge: float = 1e-3, rounds: int = 1, apply: bool = False, keep: bool = False, interrupt: bool = False,

@@ -752,6 +752,52 @@ class ScgContext:
                        self._stream())
         return v, a
 
+    # SPEC §29, the instruments of valuefit.double_targets
+    def _cross_call(self, name: str, s, tab, W_sel, W_val, act, want_a: bool, want_vs: bool):
+        """row_values' argument checks on the operands of scg_row_values_cross, then the call: (v, a or None, vs or None)."""
+        n = s[0].numel()
+        x, y, vx, vy = self._chk4(s, n, "state")
+        self._chk(tab, torch.uint8, n, "tab")
+        if W_val is None:
+            raise ScgError(f"{name}: the valuing tables must be a float32 [n_tab][{NUM_ACTIONS}][{NUM_FEATURES}] tensor")
+        n_tab = None
+        for W in (W_sel, W_val):
+            if W is None:                                    # (W_sel in the given mode: not read)
+                continue
+            if not isinstance(W, torch.Tensor) or W.dim() != 3 or tuple(W.shape[1:]) != (NUM_ACTIONS, NUM_FEATURES) \
+                    or not (1 <= W.shape[0] <= self.n_vf) or (n_tab is not None and int(W.shape[0]) != n_tab):
+                raise ScgError(f"{name}: the tables must be [n_tab][{NUM_ACTIONS}][{NUM_FEATURES}] with 1 <= n_tab <= {self.n_vf}, "
+                               "the same n_tab for both")
+            n_tab = int(W.shape[0])
+            self._chk(W, torch.float32, n_tab * W_ROW, "W")
+        if act is not None:
+            self._chk(act, torch.uint8, n, "act")
+        v = torch.empty(n, dtype=torch.float32, device=self.device)
+        a = torch.empty(n, dtype=torch.uint8, device=self.device) if want_a else None
+        vs = torch.empty(n, dtype=torch.float32, device=self.device) if want_vs else None
+        if n:                                                # (an empty tensor has no address; n = 0 writes nothing)
+            self._call("scg_row_values_cross", C.c_int64(n), _ptr(x), _ptr(y), _ptr(vx), _ptr(vy), _ptr(tab), _ptr(W_sel), _ptr(W_val),
+                       n_tab, _ptr(act), C.c_uint32(_lib.CROSS_GIVEN if act is not None else 0), _ptr(v), _ptr(a), _ptr(vs),
+                       self._stream())
+        return v, a, vs
+
+    def row_values_cross(self, s, tab: torch.Tensor, W_sel: torch.Tensor, W_val: torch.Tensor, actions: bool = True,
+                         sel_values: bool = False):
+        """SPEC §29.1: (v float32 [n], a uint8 [n] or None, vs float32 [n] or None). Under the tables W_sel and W_val ([n_tab][5][1296]
+        each) a[i] is the lowest index of max_a Q^sel_{tab[i]}(s_i, a), vs[i] that maximum and v[i] = Q^val_{tab[i]}(s_i, a[i]): the
+        valuing table's entry at the selecting table's argmax, each Q with the bits of q_values. With W_val = W_sel, (v, a) is
+        row_values' by bits and vs = v. A row whose `tab` is ROW_NONE or >= n_tab gets v = +0, a = 255, vs = +0. Any n."""
+        if W_sel is None:
+            raise ScgError(f"row_values_cross: the selecting tables must be a float32 [n_tab][{NUM_ACTIONS}][{NUM_FEATURES}] tensor")
+        return self._cross_call("row_values_cross", s, tab, W_sel, W_val, None, actions, sel_values)
+
+    def row_action_values(self, s, tab: torch.Tensor, W: torch.Tensor, act: torch.Tensor) -> torch.Tensor:
+        """SPEC §29.1's given mode: v float32 [n] with v[i] = Q_{tab[i]}(s_i, act[i]) under the tables W [n_tab][5][1296], the bits of
+        q_values(W[tab[i]])[act[i]]. `act`: uint8 [n]; a row with act[i] >= 5 or without a table gets +0. Any n."""
+        if act is None:
+            raise ScgError("row_action_values: act must be a uint8 [n] tensor")
+        return self._cross_call("row_action_values", s, tab, None, W, act, False, False)[0]
+
     def lambda_returns(self, offsets: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, vf: torch.Tensor, term: torch.Tensor,
                        v0: torch.Tensor, vk: torch.Tensor, gamma: float, lam: float, r_option_success: float):
         """SPEC §27.2: (y0, yk) float64 [total], the root and the option stream of the lambda-return over a record in (env, row)

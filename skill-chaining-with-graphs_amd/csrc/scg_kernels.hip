@@ -32,6 +32,7 @@
 // only), launched by scg_step_gated between td_kernel and the reduce launch.
 // scg_returns.hip holds SPEC §27's two kernels (scg_returns.hpp: here their arguments and launches only), behind scg_row_values and
 // scg_lambda_returns, and SPEC §28's trace_returns_kernel behind scg_trace_returns.
+// scg_returns_cross.hip holds SPEC §29's row_values_cross_kernel behind scg_row_values_cross.
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -62,6 +63,7 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 #include "scg_basis_kernels.hpp"
 #include "scg_step_gate_kernel.hpp"
 #include "scg_returns.hpp"
+#include "scg_returns_cross.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -1568,6 +1570,26 @@ int scg_trace_returns(scg_ctx *c, int32_t n_env, const int64_t *offsets, int64_t
                           flags};
     for (int k = 0; k < MAX_VF; ++k) A.lam[k] = k < n_lam ? lam_vf[k] : lam_vf[0];
     SCG_HIP(c, launch_trace_returns(A, reinterpret_cast<hipStream_t>(stream)));
+    return SCG_OK;
+}
+
+// ---- SPEC §29: the cross row values of the double-estimator targets
+int scg_row_values_cross(scg_ctx *c, int64_t n, const float *x, const float *y, const float *vx, const float *vy, const uint8_t *tab,
+                         const float *W_sel, const float *W_val, int32_t n_tab, const uint8_t *act, uint32_t flags, float *v,
+                         uint8_t *a, float *vs, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_row_values_cross: null ctx");
+    if (n < 0) return fail(c, SCG_ERR_INVALID, "scg_row_values_cross: n must be >= 0");
+    const bool given = (flags & SCG_CROSS_GIVEN) != 0;
+    if (!x || !y || !vx || !vy || !tab || !W_val || !v || (!given && !W_sel))
+        return fail(c, SCG_ERR_INVALID, "scg_row_values_cross: null array argument");
+    if (n_tab < 1 || n_tab > c->n_vf) return fail(c, SCG_ERR_INVALID, "scg_row_values_cross: n_tab out of range [1, n_vf]");
+    if (flags & ~SCG_CROSS_GIVEN) return fail(c, SCG_ERR_INVALID, "scg_row_values_cross: unknown flag bits");
+    if (given && (!act || vs)) return fail(c, SCG_ERR_INVALID, "scg_row_values_cross: SCG_CROSS_GIVEN needs act and takes no vs");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_row_values_cross");
+    if (n == 0) return SCG_OK;
+    const RowValuesCrossArgs A = {x, y, vx, vy, tab, W_sel, W_val, given ? act : nullptr, v, a, vs, n, n_tab};
+    SCG_HIP(c, launch_row_values_cross(A, given, reinterpret_cast<hipStream_t>(stream)));
     return SCG_OK;
 }
 

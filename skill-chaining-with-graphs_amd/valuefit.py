@@ -70,9 +70,24 @@ def trace_targets(ctx, flat, W, gamma: float, lam, r_option_success: float, cut:
     it `ag` is formed for the report only. Returns lambda_targets' dict plus `ag` (uint8), `h` (float64: the root stream's effective
     length, SPEC §28.1), `c` (float64: the coefficient each step row carries, formed here on the host; +0 on an env's row 0) and
     `cut` (bool: the step rows whose recorded action is not the greedy one, whether or not `cut` is set)."""
+    return _trace_targets("trace_targets", ctx, flat, W, None, gamma, lam, r_option_success, cut)
+
+
+def double_targets(ctx, flat, W_sel, W_val, gamma: float, lam, r_option_success: float, cut: bool = False) -> dict:
+    """SPEC §29.2: trace_targets with a double estimator in the bootstrap. `v0` and `vk` come from ScgContext.row_values_cross — the
+    greedy action of W_sel at the row's state, valued under W_val (tab0, tabk as trace_targets forms them) — and `ag` is the greedy
+    action under W_sel; the scan is ScgContext.trace_returns, untouched. Returns trace_targets' dict plus `vs0` and `vsk` (float32:
+    W_sel's own maximum on the same rows, what a single estimator would bootstrap from). With W_val = W_sel every entry is
+    trace_targets(W_sel)'s by bits and vs0 = v0, vsk = vk."""
+    return _trace_targets("double_targets", ctx, flat, W_sel, W_val, gamma, lam, r_option_success, cut)
+
+
+def _trace_targets(name: str, ctx, flat, W, W_val, gamma: float, lam, r_option_success: float, cut: bool) -> dict:
+    """trace_targets (W_val None: the bootstrap values by row_values under W) and double_targets (by row_values_cross: W selects,
+    W_val values), one copy."""
     from ._lib import NUM_ACTIONS, NUM_FEATURES, ROW_NONE
     flat = flat.to_numpy() if isinstance(flat, Trajectory) else flat
-    off = _checked_offsets("trace_targets", flat)
+    off = _checked_offsets(name, flat)
     total = len(flat["reward"])
     dev = ctx.device
     up = lambda v, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(v, dt))).to(dev)
@@ -80,7 +95,7 @@ def trace_targets(ctx, flat, W, gamma: float, lam, r_option_success: float, cut:
     Wt = W.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES)
     lam_vf = [float(lam)] * int(Wt.shape[0]) if np.ndim(lam) == 0 else [float(v) for v in lam]
     if len(lam_vf) != int(Wt.shape[0]) or not all(0.0 <= v <= 1.0 for v in lam_vf) or not (0.0 <= float(gamma) <= 1.0):
-        raise ScgError("trace_targets: gamma and lam (a float, or one per value function) must lie in [0, 1]")
+        raise ScgError(f"{name}: gamma and lam (a float, or one per value function) must lie in [0, 1]")
     L = np.diff(off)
     sample, has_next, begin = (np.zeros(total, bool) for _ in range(3))
     if len(L):
@@ -94,8 +109,17 @@ def trace_targets(ctx, flat, W, gamma: float, lam, r_option_success: float, cut:
     tabk = np.where((vf >= 1) & (term == 0) & (done == 0), vf, ROW_NONE).astype(np.uint8)
     tabA = np.where(has_next & (begin | (done == 0)), nxt, ROW_NONE).astype(np.uint8)
     states = [up(flat[f], np.float32) for f in ("x", "y", "vx", "vy")]
-    v0, _ = ctx.row_values(states, up(tab0, np.uint8), Wt[:1], actions=False)
-    vk, _ = ctx.row_values(states, up(tabk, np.uint8), Wt, actions=False)
+    extra = {}
+    if W_val is None:
+        v0, _ = ctx.row_values(states, up(tab0, np.uint8), Wt[:1], actions=False)
+        vk, _ = ctx.row_values(states, up(tabk, np.uint8), Wt, actions=False)
+    else:                                                      # SPEC §29.2: W's argmax valued under W_val
+        Wv = W_val.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES)
+        if Wv.shape != Wt.shape:
+            raise ScgError(f"{name}: W_sel and W_val must have one shape")
+        v0, _, vs0 = ctx.row_values_cross(states, up(tab0, np.uint8), Wt[:1], Wv[:1], actions=False, sel_values=True)
+        vk, _, vsk = ctx.row_values_cross(states, up(tabk, np.uint8), Wt, Wv, actions=False, sel_values=True)
+        extra = {"vs0": vs0.cpu().numpy(), "vsk": vsk.cpu().numpy()}
     _, ag = ctx.row_values(states, up(tabA, np.uint8), Wt, actions=True)
     y0, yk, h = ctx.trace_returns(up(off, np.int64), up(flat["reward"], np.float32), up(done, np.uint8), up(vf, np.uint8),
                                   up(term, np.uint8), up(action, np.uint8), ag, v0, vk, float(gamma), lam_vf, float(r_option_success),
@@ -107,7 +131,7 @@ def trace_targets(ctx, flat, W, gamma: float, lam, r_option_success: float, cut:
     if cut:
         c = np.where(off_greedy, 0.0, c)
     return {"offsets": off, "y0": y0, "yk": yk, "y": np.where(vf >= 1, yk, y0), "sample": sample,
-            "v0": v0.cpu().numpy(), "vk": vk.cpu().numpy(), "ag": ag, "h": h, "c": c, "cut": off_greedy}
+            "v0": v0.cpu().numpy(), "vk": vk.cpu().numpy(), "ag": ag, "h": h, "c": c, "cut": off_greedy, **extra}
 
 
 def lambda_targets(ctx, flat, W, gamma: float, lam: float, r_option_success: float) -> dict:
@@ -144,6 +168,27 @@ def lambda_targets(ctx, flat, W, gamma: float, lam: float, r_option_success: flo
         sample[off[0]: off[-1]] = (np.arange(off[0], off[-1]) - off[:-1][env]) >= 1
     return {"offsets": off, "y0": y0, "yk": yk, "y": np.where(vf >= 1, yk, y0), "sample": sample,
             "v0": v0.cpu().numpy(), "vk": vk.cpu().numpy()}
+
+
+def fold_of(env) -> np.ndarray:
+    """SPEC §29.2: the fold of each env of a record, int64: 0 (fold A) where env % 4 == 0, 1 (fold B) where env % 4 == 2 — together
+    the even envs, the fit half of every fit here — and -1 on the odd envs, which stay held out."""
+    env = np.asarray(env, np.int64)
+    return np.where(env % 4 == 0, 0, np.where(env % 4 == 2, 1, -1)).astype(np.int64)
+
+
+def mean_table(W_a, W_b):
+    """SPEC §29.2: float32((float64 W_a + float64 W_b) / 2), the table a double fit hands on. Both must be float32 and of one shape
+    (ValueError otherwise: a table of another type is not rounded to binary32 behind the caller's back). Tensors give a tensor on
+    W_a's device, arrays an array."""
+    as_np = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    a, b = as_np(W_a), as_np(W_b)
+    if a.dtype != np.float32 or b.dtype != np.float32:
+        raise ValueError(f"mean_table: the tables must be float32, not {a.dtype} and {b.dtype}")
+    if a.shape != b.shape:
+        raise ValueError(f"mean_table: W_a is {a.shape}, W_b {b.shape}")
+    out = ((a.astype(np.float64) + b.astype(np.float64)) / 2.0).astype(np.float32)
+    return torch.from_numpy(out).to(W_a.device) if isinstance(W_a, torch.Tensor) else out
 
 
 def ridge_solve(A, b, n, ridge: float, scale, device=None) -> np.ndarray:

@@ -1,0 +1,145 @@
+"""tests/double_model.py, the host model of SPEC §29, against lambda_model's row values and trace_model's targets where the two tables
+are one, on hand-made tables where they are not, and at its edges (NaN, act >= 5); valuefit.fold_of and mean_table. No GPU."""
+import numpy as np
+import pytest
+
+import double_model as DM
+import lambda_model as LM
+import trace_model as TM
+from skill_chaining_with_graphs_amd.valuefit import fold_of, mean_table
+from util import fourier_reference, random_weights
+
+NONE = LM.ROW_NONE
+
+
+def host_q(states, Wk):
+    """[5][m] binary32: a plain float64 product with the order-5 features, rounded once (a stand-in for scg_q_values)."""
+    phi = fourier_reference(*[np.asarray(s, np.float32) for s in states])
+    return (phi @ np.asarray(Wk, np.float64).reshape(5, 1296).T).astype(np.float32).T
+
+
+def table_q(states, Wk):
+    """hand-made tables: Wk IS the row of five values, whatever the state"""
+    return np.repeat(np.asarray(Wk, np.float32)[:, None], len(states[0]), axis=1)
+
+
+def some_states(n, seed):
+    rng = np.random.default_rng(seed)
+    return [rng.random(n).astype(np.float32), rng.random(n).astype(np.float32),
+            (rng.random(n) * 4 - 2).astype(np.float32), (rng.random(n) * 4 - 2).astype(np.float32)]
+
+
+def bits32(a):
+    return np.asarray(a, np.float32).view(np.uint32)
+
+
+def test_one_table_on_both_sides_is_row_values_by_bits():
+    n = 301
+    rng = np.random.default_rng(3)
+    W = random_weights(3, 7, std=0.05)
+    states = some_states(n, 1)
+    tab = rng.choice([0, 1, 2, 3, 254, NONE], n).astype(np.uint8)
+    want_v, want_a = LM.row_values(host_q, states, tab, W)
+    for W_val in (W, W.copy()):                                # the same object and an equal copy
+        v, a, vs = DM.row_values_cross(host_q, states, tab, W, W_val)
+        assert np.array_equal(bits32(v), bits32(want_v)) and np.array_equal(a, want_a) and np.array_equal(bits32(vs), bits32(v))
+    assert (want_a == 255).sum() > 50 and (want_a < 5).sum() > 100
+
+
+def test_the_valuing_tables_entry_at_the_selecting_tables_argmax():
+    W_sel = np.array([[1, 5, 2, 5, 0], [9, 1, 1, 1, 1]], np.float32)         # table 0: the max twice, the lowest index wins
+    W_val = np.array([[10, 20, 30, 40, 50], [-1, -2, -3, -4, 7]], np.float32)
+    tab = np.array([0, 1, 0, NONE, 2, 1], np.uint8)
+    v, a, vs = DM.row_values_cross(table_q, some_states(6, 2), tab, W_sel, W_val)
+    assert a.tolist() == [1, 0, 1, 255, 255, 0]
+    assert v.tolist() == [20.0, -1.0, 20.0, 0.0, 0.0, -1.0]    # not W_val's own maximum (50 / 7)
+    assert vs.tolist() == [5.0, 9.0, 5.0, 0.0, 0.0, 9.0]
+    assert not np.signbit(v[3:5]).any() and not np.signbit(vs[3:5]).any()
+
+
+def test_nan_in_the_selecting_values_gives_index_zero():
+    nan = np.float32(np.nan)
+    W_sel = np.array([[nan] * 5, [1, nan, 3, 2, 0]], np.float32)
+    W_val = np.array([[7, 8, 9, 10, 11], [1, 2, 3, 4, 5]], np.float32)
+    v, a, vs = DM.row_values_cross(table_q, some_states(2, 4), np.array([0, 1], np.uint8), W_sel, W_val)
+    assert a.tolist() == [0, 0] and v.tolist() == [7.0, 1.0] and np.isnan(vs).all()       # (the model's max hands a NaN on)
+    states = some_states(4, 5)
+    states[2][1] = np.nan                                      # a NaN state: five NaNs under every table
+    W = random_weights(2, 9, std=0.05)
+    v, a, vs = DM.row_values_cross(host_q, states, np.array([0, 1, 1, 0], np.uint8), W, W[::-1].copy())
+    assert a[1] == 0 and np.isnan(v[1]) and np.isnan(vs[1]) and np.isfinite(v[[0, 2, 3]]).all()
+
+
+def test_a_given_action_of_five_or_more_is_a_row_without_a_table():
+    W = np.array([[10, 20, 30, 40, 50], [-1, -2, -3, -4, 7]], np.float32)
+    tab = np.array([0, 1, 0, 1, NONE, 2, 0], np.uint8)
+    act = np.array([4, 2, 5, 255, 0, 0, 0], np.uint8)
+    v, a, vs = DM.row_values_cross(table_q, some_states(7, 6), tab, None, W, act=act)
+    assert vs is None
+    assert v.tolist() == [50.0, -3.0, 0.0, 0.0, 0.0, 0.0, 10.0] and a.tolist() == [4, 2, 255, 255, 255, 255, 0]
+    n = 97
+    rng = np.random.default_rng(8)
+    Wf, states = random_weights(3, 11, std=0.05), some_states(n, 12)
+    tab, act = rng.choice([0, 1, 2, 3, NONE], n).astype(np.uint8), rng.choice([0, 1, 2, 3, 4, 5, 255], n).astype(np.uint8)
+    v, a, _ = DM.row_values_cross(host_q, states, tab, None, Wf, act=act)
+    for i in range(n):
+        if tab[i] < 3 and act[i] < 5:
+            assert bits32(v[i]) == bits32(host_q([s[i: i + 1] for s in states], Wf[tab[i]])[act[i], 0]) and a[i] == act[i]
+        else:
+            assert bits32(v[i]) == 0 and a[i] == 255
+
+
+def test_fold_of_splits_the_fit_half_in_two():
+    f = fold_of(np.arange(12))
+    assert f.dtype == np.int64 and f.tolist() == [0, -1, 1, -1] * 3
+    assert np.array_equal(f >= 0, np.arange(12) % 2 == 0)      # the folds together are the even envs, the fit half as ever
+    assert fold_of([]).shape == (0,) and fold_of(np.array([4096, 4098, 4099])).tolist() == [0, 1, -1]
+
+
+def test_mean_table_is_the_float64_mean_rounded_once():
+    rng = np.random.default_rng(1)
+    a = (rng.standard_normal((3, 5, 1296)) * 100).astype(np.float32)
+    b = (rng.standard_normal((3, 5, 1296)) * 1e-3).astype(np.float32)
+    m = mean_table(a, b)
+    assert m.dtype == np.float32 and m.shape == a.shape
+    assert np.array_equal(bits32(m), bits32(((a.astype(np.float64) + b.astype(np.float64)) / 2).astype(np.float32)))
+    assert np.array_equal(bits32(mean_table(a, a)), bits32(a))                   # the mean of a table with itself is the table
+    big = np.full((1, 5, 1296), np.finfo(np.float32).max, np.float32)
+    assert np.array_equal(bits32(mean_table(big, big)), bits32(big))             # no overflow: the sum is formed in binary64
+    import torch
+    mt = mean_table(torch.from_numpy(a), torch.from_numpy(b))
+    assert isinstance(mt, torch.Tensor) and np.array_equal(bits32(mt.numpy()), bits32(m))
+    with pytest.raises(ValueError):
+        mean_table(a, b[:2])
+    with pytest.raises(ValueError, match="float32"):           # no silent rounding of a table of another type
+        mean_table(a.astype(np.float64), b)
+
+
+@pytest.mark.parametrize("cut", [False, True])
+def test_double_targets_with_one_table_are_trace_models_by_bits(cut):
+    rng = np.random.default_rng(21)
+    envs = [LM.synthetic_env(rng, L, end_done=bool(e % 2)) for e, L in enumerate((2, 14, 65, 33, 1, 90))]
+    LM.plant_edges(envs[1])
+    flat = LM.flatten(envs)
+    total = len(flat["reward"])
+    flat["action"] = rng.integers(0, 5, total).astype(np.uint8)
+    for f, s in zip(("x", "y", "vx", "vy"), some_states(total, 22)):
+        flat[f] = s
+    W = random_weights(3, 23, std=0.5)
+    gamma, lam_vf, R = 0.99, [0.9, 0.3, 1.0], 25.0
+    got = DM.double_targets(host_q, flat, W, W.copy(), gamma, lam_vf, R, cut)
+    # trace_model's own way to the same targets: lambda_model's row values on SPEC §28.2's tables, then the recurrence
+    states = [flat[f] for f in ("x", "y", "vx", "vy")]
+    tab0, tabk, tabA = DM.record_tables(flat)
+    v0, _ = LM.row_values(host_q, states, tab0, W[:1])
+    vk, _ = LM.row_values(host_q, states, tabk, W)
+    _, ag = LM.row_values(host_q, states, tabA, W)
+    y0, yk, h = TM.trace_returns(flat["offsets"], total, flat["reward"], flat["done"], flat["vf"], flat["term"], flat["action"], ag, v0, vk,
+                                 gamma, np.asarray(lam_vf), TM.TRACE_CUT if cut else 0, R)
+    for name, want in (("y0", y0), ("yk", yk), ("h", h)):
+        assert np.array_equal(got[name].view(np.uint64), want.view(np.uint64)), name
+    assert np.array_equal(got["ag"], ag) and np.array_equal(bits32(got["vs0"]), bits32(got["v0"]))
+    assert np.array_equal(bits32(got["vsk"]), bits32(got["vk"])) and (ag < 5).sum() > 50 and (tabk != NONE).sum() > 10
+    other = DM.double_targets(host_q, flat, W, random_weights(3, 24, std=0.5), gamma, lam_vf, R, cut)
+    assert not np.array_equal(other["y0"], y0) and np.array_equal(other["ag"], ag)           # the valuing table matters; ag is W_sel's
+    assert np.all(other["vs0"] == got["v0"]) and (other["v0"] < other["vs0"]).any()

@@ -21,6 +21,14 @@ by round as tools/gram_bench.py times its arms, every arm ending in a device syn
     trace_returns_cut_h        cut=True with the horizon h
   each round times --reps calls of an arm behind one synchronise (a single call is well under a millisecond).
 
+  --cross: SPEC §29's cross row values instead, on the record's first --rows rows, the row's table its vf, W_sel = W and W_val an
+  independent table of the same scale, every arm on uploaded arrays, --reps calls behind one synchronise:
+    row_values               one ScgContext.row_values call under W_sel: the yardstick
+    two_row_values_gather    what the cross target needs today at the least: row_values under W_sel for the action, a second call
+                             under W_val, and the gather of a [5][n] value array at that action on the device
+    row_values_cross         ScgContext.row_values_cross (v, a and vs)
+    row_values_cross_given   ScgContext.row_action_values at the recorded actions
+
 One JSON line per comparison: per arm the median, fastest and slowest round in ms, the ratio of the medians, and same_bits (the two
 paths' values agree bit for bit; for the scan: y0 is returns_to_go's g where every episode ended done).
 
@@ -40,7 +48,8 @@ def main():
     ap.add_argument("--envs", type=int, default=65536); ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--epsilon", type=float, default=0.1); ap.add_argument("--out", default=None)
     ap.add_argument("--trace", action="store_true", help="time scg_trace_returns against scg_lambda_returns instead (SPEC §28.4)")
-    ap.add_argument("--reps", type=int, default=20, help="--trace: calls per timed window")
+    ap.add_argument("--cross", action="store_true", help="time scg_row_values_cross against scg_row_values instead (SPEC §29.4)")
+    ap.add_argument("--reps", type=int, default=20, help="--trace, --cross: calls per timed window")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -51,8 +60,8 @@ def main():
     flat = traj.to_numpy()
     total, lines = len(flat["reward"]), []
     up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
-    if a.trace:
-        lines.append(json.dumps(trace_row(a, ag, flat, up)))
+    if a.trace or a.cross:
+        lines.append(json.dumps(trace_row(a, ag, flat, up) if a.trace else cross_row(a, ag, flat, up)))
         print(lines[-1], flush=True)
         if a.out:
             with open(a.out, "w") as fh:
@@ -157,6 +166,49 @@ def trace_row(a, ag, flat, up):
     row.update({name: gram_bench.spread(t) for name, t in times.items()})
     for name in list(runs)[1:]:
         row[f"{name}_over_lambda_returns_device"] = round(med[name] / med["lambda_returns_device"], 4)
+    return row
+
+
+def cross_row(a, ag, flat, up):
+    """--cross: the JSON row of scg_row_values_cross against scg_row_values on the first a.rows rows of the record `flat`."""
+    import numpy as np
+    import torch
+    ctx = ag.ctx
+    n = min(a.rows, len(flat["reward"]))
+    states = [up(flat[f][:n]) for f in ("x", "y", "vx", "vy")]
+    tab, act = up(flat["vf"][:n].astype(np.uint8)), up(np.minimum(flat["action"][:n], 4).astype(np.uint8))
+    W_sel = ag.W.contiguous().view(ag.n_vf, -1, 1296)
+    gen = torch.Generator(device="cpu").manual_seed(7)
+    W_val = (torch.randn(W_sel.shape, generator=gen) * float(W_sel.std())).to(W_sel.device)
+    q5 = torch.zeros((5, n), dtype=torch.float32, device=W_sel.device)         # the [5][n] array the gather reads
+    cols = torch.arange(n, device=W_sel.device)
+
+    def two_calls():
+        _, sel = ctx.row_values(states, tab, W_sel)
+        ctx.row_values(states, tab, W_val, actions=False)
+        return q5[sel.clamp(max=4).long(), cols]
+
+    runs = {"row_values": lambda: ctx.row_values(states, tab, W_sel),
+            "two_row_values_gather": two_calls,
+            "row_values_cross": lambda: ctx.row_values_cross(states, tab, W_sel, W_val, sel_values=True),
+            "row_values_cross_given": lambda: ctx.row_action_values(states, tab, W_val, act)}
+    (v1, a1), (v, sel, vs) = runs["row_values"](), runs["row_values_cross"]()
+    same = bool(torch.equal(vs.view(torch.int32), v1.view(torch.int32)) and torch.equal(sel, a1))
+    for fn in runs.values():                                   # every arm once more before the clock
+        fn()
+    times = {name: [] for name in runs}
+    for _ in range(a.rounds):
+        for name, fn in runs.items():
+            times[name].append(rig.timed(fn, a.reps) * 1e3)
+    med = {name: statistics.median(t) for name, t in times.items()}
+    row = {"what": "cross row values", "rows": n, "tables": ag.n_vf, "rounds": a.rounds, "reps": a.reps,
+           "rows_per_table": [int((tab == k).sum()) for k in range(ag.n_vf)],
+           "argmax_differs_share": round(float((ctx.row_values(states, tab, W_val)[1] != sel).float().mean()), 4),
+           "vs_and_a_same_bits_as_row_values": same}
+    row.update({name: gram_bench.spread(t) for name, t in times.items()})
+    for name in list(runs)[1:]:
+        row[f"{name}_over_row_values"] = round(med[name] / med["row_values"], 4)
+    row["row_values_cross_over_two_row_values_gather"] = round(med["row_values_cross"] / med["two_row_values_gather"], 4)
     return row
 
 
