@@ -615,6 +615,42 @@ int scg_row_values_cross(scg_ctx *ctx, int64_t n, const float *x, const float *y
                          const uint8_t *tab, const float *W_sel, const float *W_val /* [n_tab][5][1296] each */, int32_t n_tab,
                          const uint8_t *act /* [n]; with SCG_CROSS_GIVEN only, else NULL */, uint32_t flags,
                          float *v /* [n] */, uint8_t *a /* [n], may be NULL */, float *vs /* [n], may be NULL */, void *stream);
+/* ---- the device record store (SPEC §30.1): a record from the launch buffers to the operands of a value fit without leaving the device.
+ * A store keeps, for n envs with room for cap rows each, one [n][cap] array per field of scg_record (element (e, r) at e * cap + r; any
+ * may be NULL = not kept), have[n] (rows held per env) and overflow[1] (rows dropped so far); the caller zeroes have and overflow once.
+ * HOST struct of DEVICE pointers. All three calls are stream-ordered, sync nothing, need no map, raise no asynchronous status and give
+ * the same bits from every block build. */
+typedef struct {
+    float *x, *y, *vx, *vy, *reward;       /* [n][cap]; any may be NULL = not kept */
+    uint8_t *action, *done, *vf, *term;
+    int8_t *option_id;
+    int32_t *have;                         /* [n], required */
+    int32_t *overflow;                     /* [1], required */
+} scg_record_store;
+/* Append one launch's rows: for every env e of launch->n, dst[e * cap + have[e] + r] = src[r * n + e] for r < len[e] in every field kept
+ * on both sides (a field NULL on either side is skipped), then have[e] += len[e]. Rows that would pass cap are dropped: have[e] stops
+ * at cap and overflow[0] grows by their number. len is read clamped into [0, rows], have into [0, cap]; nothing else is written.
+ * launch->first is not read: the store's env e is the launch's column e. SCG_ERR_INVALID, nothing launched, in this sequence: a null
+ * ctx, a null launch or store, launch->len, store->have or store->overflow NULL, launch->n < 1, launch->rows < 1, cap < 1. */
+int scg_record_append(scg_ctx *ctx, const scg_record *launch, const scg_record_store *store, int32_t cap, void *stream);
+/* offsets[e] = have[0] + ... + have[e - 1], offsets[n] the total: the exclusive scan, int64. n = 0 writes offsets[0] = 0.
+ * SCG_ERR_INVALID, nothing launched: a null ctx, n < 0, offsets NULL, have NULL with n > 0. */
+int scg_record_offsets(scg_ctx *ctx, int32_t n, const int32_t *have, int64_t *offsets /* DEVICE [n + 1] */, void *stream);
+/* Pack the store into the flat record in (env, row) order: flat row offsets[e] + r holds env e's row r, field by field (a flat array
+ * that is NULL is skipped). Optional outputs, each [total], skipped when NULL: env[i] and row[i] (the flat row's env and local row) and
+ *   tab0[i] = done == 0 ? 0 : SCG_ROW_NONE
+ *   tabk[i] = (vf >= 1 && term == 0 && done == 0) ? vf : SCG_ROW_NONE
+ *   tabA[i] = (row i + 1 is the same env's && (row == 0 || done == 0)) ? vf[i + 1] : SCG_ROW_NONE
+ * the row tables of the lambda-return targets (a begin row carries done = 2 and ends no episode). The kernel clamps every env's range
+ * into [0, total] as the scans do and cuts it to cap rows: no offsets make it read outside the store or write outside [0, total).
+ * Writes the flat arrays given and nothing else. SCG_ERR_INVALID, nothing launched, in this sequence: a null ctx, n < 0, cap < 1,
+ * total < 0, a null store or offsets, a flat array whose field the store does not keep, a table without the store's done, vf and
+ * term. n = 0 and total = 0 succeed and write nothing. */
+int scg_record_pack(scg_ctx *ctx, int32_t n, int32_t cap, const scg_record_store *store, const int64_t *offsets /* DEVICE [n + 1] */,
+                    int64_t total, float *x, float *y, float *vx, float *vy, float *reward, uint8_t *action, uint8_t *done,
+                    uint8_t *vf, uint8_t *term, int8_t *option_id /* flat [total]; any may be NULL */,
+                    int32_t *env, int32_t *row, uint8_t *tab0, uint8_t *tabk, uint8_t *tabA /* [total]; any may be NULL */,
+                    void *stream);
 /* SkillChainingAgent.q_update on explicit transitions for one VF (SPEC §5): accumulates G_k and n_k
  * into the ctx gradient buffers at VF index k (other VFs zeroed), optionally applies to Wk_all. */
 int scg_q_update(scg_ctx *ctx, int32_t n, int32_t k, const float *x, const float *y, const float *vx,

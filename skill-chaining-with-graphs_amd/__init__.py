@@ -17,9 +17,9 @@ def __getattr__(name):
     if name in ("ScgContext", "EnvState", "fourier_scale_table"):
         from . import core
         return getattr(core, name)
-    if name == "Trajectory":
-        from .trajectory import Trajectory
-        return Trajectory
+    if name in ("Trajectory", "DeviceRecord"):
+        from . import trajectory
+        return getattr(trajectory, name)
     if name == "TrialResult":
         from .trials import TrialResult
         return TrialResult

@@ -134,6 +134,25 @@ class Record(C.Structure):
     ]
 
 
+class RecordStore(C.Structure):
+    """scg_record_store: SPEC §30.1's device store for n envs of cap rows each; device pointers of one [n][cap] array per record
+    field (NULL = not kept), have [n] and overflow [1] (int32, both required)."""
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("y", C.c_void_p),
+        ("vx", C.c_void_p),
+        ("vy", C.c_void_p),
+        ("reward", C.c_void_p),
+        ("action", C.c_void_p),
+        ("done", C.c_void_p),
+        ("vf", C.c_void_p),
+        ("term", C.c_void_p),
+        ("option_id", C.c_void_p),
+        ("have", C.c_void_p),
+        ("overflow", C.c_void_p),
+    ]
+
+
 class Audit(C.Structure):
     """scg_audit: device pointers of SPEC §15's per-env audit arrays, each [N] (any NULL = not given / not written)."""
     _fields_ = [
@@ -210,6 +229,9 @@ _SIGS = {
     "scg_lambda_returns": (C.c_int, [_P, C.c_int32, _P, C.c_int64] + [_P] * 6 + [C.c_double] * 3 + [_P, _P, _P]),
     "scg_trace_returns": (C.c_int, [_P, C.c_int32, _P, C.c_int64] + [_P] * 8 + [C.c_double, _P, C.c_int32, C.c_uint32, C.c_double]
                           + [_P] * 4),
+    "scg_record_append": (C.c_int, [_P, C.POINTER(Record), C.POINTER(RecordStore), C.c_int32, _P]),
+    "scg_record_offsets": (C.c_int, [_P, C.c_int32, _P, _P, _P]),
+    "scg_record_pack": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(RecordStore), _P, C.c_int64] + [_P] * 10 + [_P] * 5 + [_P]),
     "scg_q_values": (C.c_int, [_P, C.c_int32] + [_P] * 6 + [_P]),
     "scg_q_update": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 12 + [C.c_uint32, _P]),
     "scg_classifier_predict": (C.c_int, [_P, C.c_int32] + [_P] * 4 + [_P]),

@@ -23,7 +23,7 @@ from .evaluation import BranchResult, EpisodeStats, GateAudit, paired_difference
 from .maps import PinballMap, load_map
 from .option import Option
 from .pinball import PinballDomain
-from .trajectory import Trajectory
+from .trajectory import DeviceRecord, Trajectory
 from .trials import OUTCOMES, TrialResult
 
 
@@ -535,16 +535,19 @@ class SkillChainingAgent:
         return (out, stats.per_env()) if per_env else out
 
     def record_episodes(self, n_episodes: int = 256, states=None, epsilon: float = 0.0, seed: Optional[int] = None,
-                        steps_per_launch: int = 64, interrupt: bool = False, choose: Optional[str] = None):
+                        steps_per_launch: int = 64, interrupt: bool = False, choose: Optional[str] = None, device: bool = False):
         """evaluate() with every step recorded (SPEC §10): the same launches on the same evaluation context, each with a record
         of all envs that is appended to a Trajectory after the launch. Returns (Trajectory, the EpisodeStats summary, equal to
         evaluate()'s with the same arguments). Row 0 of each env is its begin row. The training run is left alone.
-        `interrupt`: as for evaluate(); an interrupted step's row has term INTERRUPTED (SPEC §11). `choose`: as for evaluate()."""
-        stats, traj = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record=True, choose=choose)
+        `interrupt`: as for evaluate(); an interrupted step's row has term INTERRUPTED (SPEC §11). `choose`: as for evaluate().
+        `device` (SPEC §30.1): the same launches, each appended to a trajectory.DeviceRecord by one scg_record_append call instead:
+        nothing is downloaded. Returns (DeviceRecord, the same summary); its to_numpy() is the Trajectory's by bits."""
+        stats, traj = self._eval_launches(n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record=True, choose=choose,
+                                          device=device)
         return traj, stats.summary()
 
     def _eval_launches(self, n_episodes, epsilon, seed, steps_per_launch, states, interrupt, record: bool = False, choose=None,
-                       audit=None, population=None):
+                       audit=None, population=None, W=None, device: bool = False):
         """The launches of evaluate() / record_episodes() on the evaluation context for this episode count and seed, its settings
         copied from training (epsilon aside), stats zeroed and, with `states`, the start states written into its env state: the
         first begins every episode at t0 = 0, launch i > 0 goes on at t0 = 1 + i * steps_per_launch. Returns (EpisodeStats, Trajectory or None).
@@ -554,7 +557,10 @@ class SkillChainingAgent:
         population rollout (SPEC §21) of C policies over n_episodes envs each: the context has C * n_episodes envs, the `states`
         are repeated for every policy, and `epsilon` is the context's own (no policy's, where the population gives one). A fourth
         element, a [C, n_vf, 8] classifier table (or None), gives every policy its own classifiers (SPEC §24.1), a fifth, a
-        [C, n_vf, 2, 5, 1296] gate table (or None), its own value gate (SPEC §25.1)."""
+        [C, n_vf, 2, 5, 1296] gate table (or None), its own value gate (SPEC §25.1).
+        `W`: the value tables the launches act under instead of the agent's (SPEC §30.3: a record under a table that is not the
+        agent's; self.W is not written). `device` with `record`: the launches' rows go to a DeviceRecord (SPEC §30.1), which is
+        returned in the Trajectory's place; the Trajectory then serves as the launch buffers only."""
         if choose not in (None, "value"):
             raise ValueError(f"choose must be None or 'value', not {choose!r}")
         if states is not None:
@@ -566,7 +572,7 @@ class SkillChainingAgent:
         if not (1 <= spl <= _lib.ROLLOUT_MAX_STEPS):
             raise ValueError(f"steps_per_launch must be in [1, {_lib.ROLLOUT_MAX_STEPS}]")
         c = self.ctx.cfg
-        W, kw = self.W, {}
+        W, kw = (self.W if W is None else W), {}
         if population is not None:
             W, pol_eps, pol_enabled, *pol_clf = population
             n_pol = int(W.shape[0])
@@ -577,6 +583,7 @@ class SkillChainingAgent:
             n, kw["population"] = n * n_pol, (pol_eps, pol_enabled, *pol_clf)
         ectx, st, stats = self._eval_context(n, epsilon, seed, states)
         traj = Trajectory(n, spl + 1, 0, ectx.device, n_vf=self.n_vf) if record else None
+        rec = DeviceRecord(ectx, n, int(c.max_episode_steps) + 1, n_vf=self.n_vf) if record and device else None
         if audit is not None:
             stats.audit = GateAudit(n, ectx.device, force=None if audit is True else audit)
             kw["audit"] = stats.audit
@@ -586,9 +593,11 @@ class SkillChainingAgent:
                          record=traj, interrupt=interrupt, choose=choose, **kw)
             if audit is not None:
                 stats.audit.force = None                       # the force is the begin pseudo-step's alone
-            if record:
+            if rec is not None:
+                rec.append(traj)
+            elif record:
                 traj.append()
-        return stats, traj
+        return stats, (traj if rec is None else rec)
 
     def evaluate_policies(self, W, epsilons=None, enabled=None, n_episodes: int = 4096, seed: Optional[int] = None,
                           steps_per_launch: int = 64, states=None, interrupt: bool = False, choose: Optional[str] = None,
@@ -799,7 +808,7 @@ class SkillChainingAgent:
     def fit_values_to_returns(self, n_episodes: int = 4096, epsilon: float = 0.1, seed: Optional[int] = None, vfs=None,
                               ridge: float = 1e-3, apply: bool = False, interrupt: bool = False, choose: Optional[str] = None,
                               keep: bool = False, order: Optional[int] = None, trajectory=None, lam=None, sweeps: int = 1, trace: str = "peng",
-                              double: bool = False):
+                              double: bool = False, pipeline: str = "host", fresh: bool = False):
         """The best linear fit of each Q_k to the returns its own policy realises (SPEC §16): record_episodes() with the current
         policy, Monte-Carlo targets by valuefit.returns_to_go, then per value function k of `vfs` (default: all) and action a the
         ridge regression of the residual y - Q_k^old on the 1296 features over the rows with vf = k, action = a of the EVEN envs
@@ -838,7 +847,17 @@ class SkillChainingAgent:
         entry outside [0, 1].
         `double` is SPEC §29.2's double-estimator fit (_fit_values_double: two tables on two folds of the fit half, each
         bootstrapping from the other's value of its own greedy action; W_new is their mean). It needs lam, is refused with order and
-        works with both traces. double=False is the path above, call for call."""
+        works with both traces. double=False is the path above, call for call.
+        `pipeline` = "device" (SPEC §30.2; needs lam, refused with order and double) is the same fit with the record, the targets,
+        the sample lists and the residual formed on the device (_fit_values_device): the record is a trajectory.DeviceRecord (recorded
+        with device=True; a Trajectory given as `trajectory` is uploaded once), Q^old and Q^new come from ScgContext.row_action_values,
+        the Gram call and the host ridge solve are the ones above. W_new, every sweep's W and every reported number equal the host
+        pipeline's. "host", the default, is the path above, call for call.
+        `fresh` (SPEC §30.3; needs lam, implies pipeline="device", refused with order and double): sweep 1 runs on the given or
+        recorded record; every later sweep s records `n_episodes` new episodes under the table the sweep before handed on, with this
+        call's epsilon, interrupt and choose and the seed `seed` + s - 1, and takes its targets, samples, split and held-out half from
+        that record. Every sweep's entry then holds "episodes" (its record's summary), its "mc" is against its own record's returns,
+        and "a_changed" is None: the rows differ between sweeps."""
         from .core import fourier_scale_table
         from .valuefit import error_stats, returns_to_go
         if trace not in ("peng", "watkins"):
@@ -848,6 +867,18 @@ class SkillChainingAgent:
         if double and (lam is None or order is not None):
             raise ScgError("fit_values_to_returns: double=True needs lam (the Monte-Carlo targets bootstrap from nothing) and "
                            "cannot be given with order")
+        if pipeline not in ("host", "device"):
+            raise ScgError(f"fit_values_to_returns: pipeline must be 'host' or 'device', not {pipeline!r}")
+        if fresh and (lam is None or double or order is not None):
+            raise ScgError("fit_values_to_returns: fresh=True needs lam and cannot be given with double or order")
+        if fresh:
+            pipeline = "device"
+        if pipeline == "device" and lam is None:
+            raise ScgError("fit_values_to_returns: pipeline='device' needs lam (the Monte-Carlo path stays on the host)")
+        if pipeline == "device" and order is not None:
+            raise ScgError("fit_values_to_returns: pipeline='device' cannot be given with order")
+        if pipeline == "device" and double:
+            raise ScgError("fit_values_to_returns: pipeline='device' cannot be given with double=True")
         lam_seq = lam is not None and np.ndim(lam) != 0
         if lam is not None:
             if order is not None:
@@ -875,6 +906,20 @@ class SkillChainingAgent:
         if any(not (0 <= k < self.n_vf) for k in vfs):
             raise ValueError(f"vfs must name value functions 0..{self.n_vf - 1}")
         c = self.ctx.cfg
+        if pipeline == "device":
+            if trajectory is None:
+                rec, summary = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose, device=True)
+                ectx = self._eval_ctx[int(n_episodes)][0]
+            else:
+                ectx, summary = self._eval_context(int(trajectory.n), epsilon, seed, None)[0], None
+                rec = trajectory if isinstance(trajectory, DeviceRecord) else DeviceRecord.from_trajectory(ectx, trajectory)
+            again = None
+            if fresh:                                          # SPEC §30.3: sweep s (from 1) records under the table handed on, at seed + s - 1
+                seed0 = int(c.seed) if seed is None else int(seed)
+                again = lambda s, W: self._record_under(W, n_episodes, epsilon, seed0 + s, interrupt, choose)
+            return self._fit_values_device(ectx, rec, summary, vfs, ridge, lam, int(sweeps), trace, keep, apply, again)
+        if isinstance(trajectory, DeviceRecord):
+            trajectory = trajectory.to_trajectory()
         if trajectory is None:
             traj, summary = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose)
             ectx = self._eval_ctx[int(n_episodes)][0]
@@ -968,6 +1013,126 @@ class SkillChainingAgent:
             report["targets"], report["trajectory"] = tg, traj
             if lam is not None:
                 report["lambda_targets"] = lt
+        if apply:
+            for k in vfs:
+                self.W[k].copy_(W_new[k])
+        return report, W_new
+
+    def _record_under(self, W, n_episodes, epsilon, seed, interrupt, choose):
+        """record_episodes(device=True) under the tables W instead of the agent's: (evaluation context, DeviceRecord, summary).
+        self.W is not written."""
+        stats, rec = self._eval_launches(n_episodes, epsilon, seed, 64, None, interrupt, record=True, choose=choose, W=W, device=True)
+        return self._eval_ctx[int(n_episodes)][0], rec, stats.summary()
+
+    def _fit_values_device(self, ectx, rec, summary, vfs, ridge: float, lam, sweeps: int, trace: str, keep: bool, apply: bool, again):
+        """fit_values_to_returns(pipeline="device"), SPEC §30.2: the host path's fit with every per-row and per-sample array formed on
+        the device from DeviceRecord.flat(). Per record: the flat tensors, the Monte-Carlo targets (valuefit.returns_to_go on ONE
+        download of the record: the report's "mc") and, per value function, the sample list — the step rows with vf = k of the even
+        envs in (env, row) order, sorted by action with a stable sort, then those of the odd envs: the host path's `rows` by value.
+        Per sweep: v0, vk (and ag) by the host path's row_values calls on the pack's tables, the scan by its lambda_returns /
+        trace_returns call, then per value function Q^old = row_action_values under the sweep's table, d = float32(y - float64 Q^old)
+        on the device, feature_gram, valuefit.ridge_solve on the host, Q^new = row_action_values under the new row. The statistics are
+        the host path's numpy expressions on the downloaded per-sample arrays. `again(s, W)` (SPEC §30.3, or None) gives sweep s >= 1
+        its own record under W."""
+        from .valuefit import error_stats, returns_to_go, ridge_solve
+        c = self.ctx.cfg
+        gamma, r_succ = float(c.gamma), float(c.r_option_success)
+        dev = self.W.device
+        lam_seq = np.ndim(lam) != 0
+        traced = trace == "watkins" or lam_seq
+        lam_vf = [float(v) for v in lam] if lam_seq else [float(lam)] * self.n_vf
+        report = {"episodes": summary, "ridge": float(ridge), "vf": {}, "lam": list(lam) if lam_seq else float(lam), "sweeps": [],
+                  "trace": trace}
+        nan = float("nan")
+        W_new = self.W.clone()
+        ag_prev = None
+        for sweep in range(sweeps):
+            W_cur = W_new.clone()                              # what the targets bootstrap from and the residual is taken against
+            if sweep and again is not None:
+                ectx, rec, summary = again(sweep, W_cur)
+            if sweep == 0 or again is not None:                # a new record: its flat tensors, Monte-Carlo targets and sample lists
+                fl = rec.flat(ectx)
+                if "tabA" not in fl or any(f not in fl for f in ("x", "y", "vx", "vy", "reward", "action")):
+                    raise ScgError("fit_values_to_returns: the record must hold the state, reward, action, done, vf and term fields")
+                tg = returns_to_go(rec.to_numpy(), gamma, r_succ)
+                step = fl["row"] >= 1
+                lists = {}
+                for k in vfs:
+                    mine = step & (fl["vf"] == k)
+                    fit = torch.nonzero(mine & (fl["env"] % 2 == 0)).view(-1)
+                    fit = fit[torch.sort(fl["action"][fit], stable=True)[1]]
+                    rows = torch.cat([fit, torch.nonzero(mine & (fl["env"] % 2 == 1)).view(-1)])
+                    lists[k] = (rows, int(fit.numel()), rows.cpu().numpy())
+            # ---- the sweep's targets: the host path's calls on the pack's tables
+            states_all = [fl[f] for f in ("x", "y", "vx", "vy")]
+            Wt = W_cur.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES)
+            v0, _ = ectx.row_values(states_all, fl["tab0"], Wt[:1], actions=False)
+            vk, _ = ectx.row_values(states_all, fl["tabk"], Wt, actions=False)
+            lt = {"v0": v0, "vk": vk}
+            if traced:
+                _, ag = ectx.row_values(states_all, fl["tabA"], Wt, actions=True)
+                y0, yk, h = ectx.trace_returns(fl["offsets"], fl["reward"], fl["done"], fl["vf"], fl["term"], fl["action"], ag, v0, vk,
+                                               gamma, lam_vf, r_succ, cut=trace == "watkins", horizon=True)
+                off_greedy = torch.zeros_like(step)
+                off_greedy[1:] = step[1:] & (fl["action"][1:] != ag[:-1])
+                vf_l = fl["vf"].long()
+                coef = torch.tensor(lam_vf, dtype=torch.float64, device=dev)[torch.where(vf_l < len(lam_vf), vf_l, torch.zeros_like(vf_l))]
+                coef = torch.where(step, coef, torch.zeros_like(coef))
+                if trace == "watkins":
+                    coef = torch.where(off_greedy, torch.zeros_like(coef), coef)
+                lt.update(ag=ag, h=h, c=coef, cut=off_greedy)
+            else:
+                y0, yk = ectx.lambda_returns(fl["offsets"], fl["reward"], fl["done"], fl["vf"], fl["term"], v0, vk, gamma, float(lam),
+                                             r_succ)
+            lt.update(y0=y0, yk=yk, y=torch.where(fl["vf"] >= 1, yk, y0))
+            report["vf"] = {}
+            for k in vfs:
+                rows, n_fit, rows_h = lists[k]
+                act = fl["action"][rows].contiguous()
+                states = [fl[f][rows - 1].contiguous() for f in ("x", "y", "vx", "vy")]
+                tab = torch.full((rows.numel(),), int(k), dtype=torch.uint8, device=dev)
+                y_d = lt["y"][rows]
+                q_old_d = ectx.row_action_values(states, tab, Wt, act)
+                d = (y_d - q_old_d.double()).float()           # float64 on the device, rounded once
+                n_a = torch.bincount(act[:n_fit].long(), minlength=NUM_ACTIONS).cpu().numpy().astype(np.int64)
+                offsets = np.concatenate([[0], np.cumsum(n_a)]).astype(np.int64)
+                A, b = ectx.feature_gram(states, offsets, d)
+                delta = ridge_solve(A.cpu().numpy(), b.cpu().numpy(), n_a, ridge, self.ctx.scale)
+                w_old = W_cur[k].cpu().numpy()
+                w_new = (w_old.astype(np.float64) + delta).astype(np.float32)
+                w_new[n_a == 0] = w_old[n_a == 0]
+                W_new[k] = torch.from_numpy(w_new).to(dev)
+                q_new_d = ectx.row_action_values(states, tab, W_new.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES), act)
+                # ---- the report: the host path's expressions on the per-sample arrays
+                q_old, q_new, y = q_old_d.cpu().numpy(), q_new_d.cpu().numpy(), y_d.cpu().numpy()
+                half = {"fit": slice(0, n_fit), "held_out": slice(n_fit, None)}
+                rep = {"n": [int(v) for v in n_a], "delta_norm": float(np.sqrt(np.sum(delta * delta)))}
+                for name, sl in half.items():
+                    rep[name] = {"old": error_stats(q_old[sl], y[sl]), "new": error_stats(q_new[sl], y[sl])}
+                y_mc = tg["y"][rows_h]
+                rep["mc"] = {name: {"old": error_stats(q_old[sl], y_mc[sl]), "new": error_stats(q_new[sl], y_mc[sl])}
+                             for name, sl in half.items()}
+                if traced:
+                    some = len(rows_h) > 0
+                    rep["cut_share"] = float(np.mean(lt["c"][rows].cpu().numpy() == 0.0)) if some else nan
+                    rep["off_greedy"] = float(np.mean(lt["cut"][rows].cpu().numpy())) if some else nan
+                    rep["horizon"] = float(np.mean(lt["h"][rows].cpu().numpy())) if some else nan
+                    rep["a_changed"] = None if ag_prev is None else \
+                        float(np.mean((lt["ag"][rows - 1] != ag_prev[rows - 1]).cpu().numpy())) if some else nan
+                if keep:
+                    rep["operands"] = {"states": states, "action": act.cpu().numpy().astype(np.int64), "y": y, "d": d.cpu().numpy(),
+                                       "offsets": offsets, "n_fit": n_fit, "A": A, "b": b, "rows": rows_h, "delta": delta}
+                report["vf"][k] = rep
+            entry = {"vf": report["vf"], "W": W_new.clone()}
+            if again is not None:
+                entry["episodes"] = summary
+            report["sweeps"].append(entry)
+            ag_prev = lt["ag"] if traced and again is None else None
+        if keep:
+            report["targets"], report["trajectory"] = tg, rec
+            host = {f: v.cpu().numpy() for f, v in lt.items()}
+            host.update(offsets=fl["offsets"].cpu().numpy(), sample=step.cpu().numpy())
+            report["lambda_targets"] = host
         if apply:
             for k in vfs:
                 self.W[k].copy_(W_new[k])

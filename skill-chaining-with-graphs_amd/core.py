@@ -852,6 +852,33 @@ class ScgContext:
                        self._stream())
         return y0, yk, h
 
+    # SPEC §30.1, the calls of trajectory.DeviceRecord (which owns the tensors and checks their shapes)
+    def record_append(self, launch, store, cap: int) -> None:
+        """One launch's rows behind the store's earlier ones: `launch` a _lib.Record of the launch buffers, `store` a
+        _lib.RecordStore of [n][cap] arrays (both of device pointers whose tensors the caller keeps alive). No sync, no download."""
+        self._call("scg_record_append", C.byref(launch), C.byref(store), int(cap), self._stream())
+
+    def record_offsets(self, have: torch.Tensor) -> torch.Tensor:
+        """The exclusive scan of `have` (int32 [n]) as int64 [n + 1] on the device."""
+        n = have.numel()
+        self._chk(have, torch.int32, n, "have")
+        off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        self._call("scg_record_offsets", n, _ptr(have if n else None), _ptr(off), self._stream())
+        return off
+
+    def record_pack(self, n: int, cap: int, store, offsets: torch.Tensor, total: int, flat: dict, extra: dict) -> None:
+        """The store's rows into the flat (env, row) arrays `flat` (field name -> [total] tensor) and the optional outputs `extra`
+        (env, row: int32; tab0, tabk, tabA: uint8; each [total]), all allocated by the caller on this device."""
+        self._chk(offsets, torch.int64, int(n) + 1, "offsets")
+        fields = ("x", "y", "vx", "vy", "reward", "action", "done", "vf", "term", "option_id")
+        for name, t in list(flat.items()) + list(extra.items()):
+            if t.device != self.device or not t.is_contiguous() or t.numel() != int(total):
+                raise ScgError(f"record_pack: {name} must be a contiguous [{int(total)}] tensor on {self.device}")
+        if total:                                            # (an empty tensor has no address; total = 0 writes nothing)
+            self._call("scg_record_pack", int(n), int(cap), C.byref(store), _ptr(offsets), C.c_int64(total),
+                       *[_ptr(flat.get(f)) for f in fields], *[_ptr(extra.get(f)) for f in ("env", "row", "tab0", "tabk", "tabA")],
+                       self._stream())
+
     def q_update(self, k: int, s, action, r, cont, sn, W: torch.Tensor, apply: bool = True) -> None:
         n = s[0].numel()
         if n > self.n_envs:

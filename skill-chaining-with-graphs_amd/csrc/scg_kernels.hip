@@ -33,6 +33,8 @@
 // scg_returns.hip holds SPEC §27's two kernels (scg_returns.hpp: here their arguments and launches only), behind scg_row_values and
 // scg_lambda_returns, and SPEC §28's trace_returns_kernel behind scg_trace_returns.
 // scg_returns_cross.hip holds SPEC §29's row_values_cross_kernel behind scg_row_values_cross.
+// scg_record_store.hip holds SPEC §30.1's record store kernels behind scg_record_append, scg_record_offsets and scg_record_pack
+// (DESIGN §3.35).
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -64,6 +66,7 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 #include "scg_step_gate_kernel.hpp"
 #include "scg_returns.hpp"
 #include "scg_returns_cross.hpp"
+#include "scg_record_store.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -1590,6 +1593,58 @@ int scg_row_values_cross(scg_ctx *c, int64_t n, const float *x, const float *y, 
     if (n == 0) return SCG_OK;
     const RowValuesCrossArgs A = {x, y, vx, vy, tab, W_sel, W_val, given ? act : nullptr, v, a, vs, n, n_tab};
     SCG_HIP(c, launch_row_values_cross(A, given, reinterpret_cast<hipStream_t>(stream)));
+    return SCG_OK;
+}
+
+// ---- SPEC §30.1: the device record store
+int scg_record_append(scg_ctx *c, const scg_record *launch, const scg_record_store *store, int32_t cap, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_record_append: null ctx");
+    if (!launch || !store) return fail(c, SCG_ERR_INVALID, "scg_record_append: null launch or store");
+    if (!launch->len || !store->have || !store->overflow)
+        return fail(c, SCG_ERR_INVALID, "scg_record_append: launch->len, store->have and store->overflow are required");
+    if (launch->n < 1) return fail(c, SCG_ERR_INVALID, "scg_record_append: launch->n must be >= 1");
+    if (launch->rows < 1) return fail(c, SCG_ERR_INVALID, "scg_record_append: launch->rows must be >= 1");
+    if (cap < 1) return fail(c, SCG_ERR_INVALID, "scg_record_append: cap must be >= 1");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_record_append");
+    const RecordAppendArgs A = {{{launch->x, store->x}, {launch->y, store->y}, {launch->vx, store->vx}, {launch->vy, store->vy},
+                                 {launch->reward, store->reward}, {launch->action, store->action}, {launch->done, store->done},
+                                 {launch->vf, store->vf}, {launch->term, store->term}, {launch->option_id, store->option_id}},
+                                launch->len, store->have, store->overflow, launch->n, launch->rows, cap};
+    SCG_HIP(c, launch_record_append(A, reinterpret_cast<hipStream_t>(stream)));
+    return SCG_OK;
+}
+
+int scg_record_offsets(scg_ctx *c, int32_t n, const int32_t *have, int64_t *offsets, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_record_offsets: null ctx");
+    if (n < 0) return fail(c, SCG_ERR_INVALID, "scg_record_offsets: n must be >= 0");
+    if (!offsets || (n > 0 && !have)) return fail(c, SCG_ERR_INVALID, "scg_record_offsets: null array argument");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_record_offsets");
+    SCG_HIP(c, launch_record_offsets(n, have, offsets, reinterpret_cast<hipStream_t>(stream)));
+    return SCG_OK;
+}
+
+int scg_record_pack(scg_ctx *c, int32_t n, int32_t cap, const scg_record_store *store, const int64_t *offsets, int64_t total, float *x,
+                    float *y, float *vx, float *vy, float *reward, uint8_t *action, uint8_t *done, uint8_t *vf, uint8_t *term,
+                    int8_t *option_id, int32_t *env, int32_t *row, uint8_t *tab0, uint8_t *tabk, uint8_t *tabA, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_record_pack: null ctx");
+    if (n < 0) return fail(c, SCG_ERR_INVALID, "scg_record_pack: n must be >= 0");
+    if (cap < 1) return fail(c, SCG_ERR_INVALID, "scg_record_pack: cap must be >= 1");
+    if (total < 0) return fail(c, SCG_ERR_INVALID, "scg_record_pack: total must be >= 0");
+    if (!store || !offsets) return fail(c, SCG_ERR_INVALID, "scg_record_pack: null store or offsets");
+    const RecordPackArgs A = {{{store->x, x}, {store->y, y}, {store->vx, vx}, {store->vy, vy}, {store->reward, reward},
+                               {store->action, action}, {store->done, done}, {store->vf, vf}, {store->term, term},
+                               {store->option_id, option_id}},
+                              store->done, store->vf, store->term, offsets, env, row, tab0, tabk, tabA, total, n, cap};
+    for (int k = 0; k < RS_FIELDS; ++k)
+        if (A.f[k].dst && !A.f[k].src) return fail(c, SCG_ERR_INVALID, "scg_record_pack: a flat array of a field the store does not keep");
+    if ((tab0 || tabk || tabA) && (!store->done || !store->vf || !store->term))
+        return fail(c, SCG_ERR_INVALID, "scg_record_pack: the tables need the store's done, vf and term");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_record_pack");
+    if (n == 0 || total == 0) return SCG_OK;
+    SCG_HIP(c, launch_record_pack(A, reinterpret_cast<hipStream_t>(stream)));
     return SCG_OK;
 }
 

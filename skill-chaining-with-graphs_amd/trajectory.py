@@ -1,4 +1,5 @@
-"""Trajectory — the per-step rows of recorded rollouts and option trials (SPEC §10) and their host-side views."""
+"""Trajectory — the per-step rows of recorded rollouts and option trials (SPEC §10) and their host-side views; DeviceRecord —
+the same rows kept on the device (SPEC §30.1)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -7,7 +8,7 @@ import numpy as np
 import torch
 
 from ._lib import (ROLLOUT_TERM_INTERRUPTED, TRIAL_EPISODE_END, TRIAL_LEFT_INITIATION, TRIAL_SUCCESS, TRIAL_TIMEOUT,
-                   Record)
+                   Record, RecordStore, ScgError)
 
 TERMS = {0: "", TRIAL_SUCCESS: "SUCCESS", TRIAL_EPISODE_END: "EPISODE_END", TRIAL_LEFT_INITIATION: "LEFT_INITIATION",
          TRIAL_TIMEOUT: "TIMEOUT", ROLLOUT_TERM_INTERRUPTED: "INTERRUPTED"}
@@ -214,6 +215,104 @@ class Trajectory:
         out = {f: np.concatenate([p[f] for p in per]) for f in self.fields}
         out["offsets"], out["first"] = off, np.int64(self.first)
         return out
+
+
+class DeviceRecord:
+    """SPEC §30.1's device store of a record: for `n` envs with room for `cap` rows each one [n][cap] tensor per recorded field,
+    `have` [n] (int32: rows held) and `overflow` [1] (int32: rows dropped because they passed cap), all on `ctx`'s device. What
+    Trajectory keeps on the host, kept where the launches write it: append() is one scg_record_append call, flat() gives the
+    record in (env, row) order — Trajectory.to_numpy()'s layout — as device tensors, with the row tables of the value fits."""
+
+    TABLES = ("env", "row", "tab0", "tabk", "tabA")
+    _TABLE_DTYPES = {"env": torch.int32, "row": torch.int32, "tab0": torch.uint8, "tabk": torch.uint8, "tabA": torch.uint8}
+
+    def __init__(self, ctx, n: int, cap: int, first: int = 0, fields=Trajectory.FIELDS, n_vf=None):
+        self.ctx, self.first, self.n, self.cap = ctx, int(first), int(n), int(cap)
+        self.n_vf = None if n_vf is None else int(n_vf)
+        if self.n < 1 or self.cap < 1 or self.first < 0:
+            raise ValueError("a device record needs n >= 1, cap >= 1 and first >= 0")
+        self.fields = tuple(fields)
+        if any(f not in Trajectory.DTYPES for f in self.fields):
+            raise ValueError(f"unknown record field in {self.fields}")
+        dev = ctx.device
+        for f in Trajectory.FIELDS:
+            setattr(self, f, torch.empty((self.n, self.cap), dtype=Trajectory.DTYPES[f], device=dev) if f in self.fields else None)
+        self.have = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self.overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._flat = None
+
+    @property
+    def device(self) -> torch.device:
+        return self.have.device
+
+    def c_struct(self) -> RecordStore:
+        """The scg_record_store of these tensors (device pointers; the tensors must stay alive while it is in use)."""
+        p = {f: C.c_void_p(getattr(self, f).data_ptr()) for f in self.fields}
+        return RecordStore(have=C.c_void_p(self.have.data_ptr()), overflow=C.c_void_p(self.overflow.data_ptr()), **p)
+
+    def append(self, launch: Trajectory) -> "DeviceRecord":
+        """Append the rows the last launch left in `launch`'s buffers (a Trajectory of the same n on this device; its host rows
+        are not touched): one scg_record_append call on the current stream, no download and no loop over the envs."""
+        if not isinstance(launch, Trajectory) or launch.n != self.n or launch.device != self.device:
+            raise ScgError(f"DeviceRecord.append: the launch buffers must be a Trajectory of {self.n} envs on {self.device}")
+        self.ctx.record_append(launch.c_struct(), self.c_struct(), self.cap)
+        self._flat = None
+        return self
+
+    @classmethod
+    def from_trajectory(cls, ctx, traj: Trajectory) -> "DeviceRecord":
+        """A host Trajectory's appended rows as a device record: one upload per field."""
+        flat = traj.to_numpy()
+        off = flat["offsets"]
+        L = np.diff(off)
+        rec = cls(ctx, traj.n, max(int(L.max()), 1), traj.first, traj.fields, traj.n_vf)
+        env = np.repeat(np.arange(traj.n), L)
+        row = np.arange(int(off[-1])) - off[:-1][env]
+        for f in rec.fields:
+            host = np.zeros((rec.n, rec.cap), flat[f].dtype)
+            host[env, row] = flat[f]
+            getattr(rec, f).copy_(torch.from_numpy(host))
+        rec.have.copy_(torch.from_numpy(L.astype(np.int32)))
+        return rec
+
+    def flat(self, ctx=None) -> dict:
+        """The record in (env, row) order as device tensors: `offsets` (int64 [n + 1]), one [total] tensor per recorded field, `env`
+        and `row` (int32) and, where done, vf and term are recorded, `tab0`, `tabk`, `tabA` (uint8: SPEC §30.1's row tables); plus
+        `total` (int). scg_record_offsets, ONE read-back (offsets[n] and overflow), scg_record_pack; cached until the next append.
+        `ctx`: the context that makes the calls (default: the one given at construction; any live context of the device serves).
+        Raises ScgError where rows were dropped: the record is not the episodes'."""
+        if self._flat is not None:
+            return self._flat
+        ctx = self.ctx if ctx is None else ctx
+        off = ctx.record_offsets(self.have)
+        total, dropped = (int(v) for v in torch.cat([off[-1:], self.overflow.to(torch.int64)]).cpu())
+        if dropped:
+            raise ScgError(f"DeviceRecord: {dropped} rows passed the capacity of {self.cap} rows per env and were dropped")
+        dev = self.device
+        out = {f: torch.empty(total, dtype=Trajectory.DTYPES[f], device=dev) for f in self.fields}
+        names = self.TABLES if all(f in self.fields for f in ("done", "vf", "term")) else self.TABLES[:2]
+        extra = {f: torch.empty(total, dtype=self._TABLE_DTYPES[f], device=dev) for f in names}
+        ctx.record_pack(self.n, self.cap, self.c_struct(), off, total, out, extra)
+        self._flat = {"offsets": off, "total": total, **out, **extra}
+        return self._flat
+
+    def to_numpy(self) -> dict:
+        """Trajectory.to_numpy()'s dict of this record, equal by bits."""
+        fl = self.flat()
+        out = {f: fl[f].cpu().numpy() for f in self.fields}
+        out["offsets"], out["first"] = fl["offsets"].cpu().numpy(), np.int64(self.first)
+        return out
+
+    def to_trajectory(self) -> Trajectory:
+        """The record as a host Trajectory (no launch buffers to speak of), for the host-side views: segments, summary,
+        resume_state, offer_rows."""
+        flat = self.to_numpy()
+        off = flat["offsets"]
+        traj = Trajectory(self.n, 1, self.first, "cpu", self.fields, self.n_vf)
+        for e in range(self.n):
+            if off[e + 1] > off[e]:
+                traj._chunks[e].append({f: flat[f][off[e]: off[e + 1]].copy() for f in self.fields})
+        return traj
 
 
 def offer_rows(flat: dict, reoffer_period: int = 1, t0: int = 0, env_ids=None) -> dict:

@@ -1,0 +1,123 @@
+"""SPEC §30.2 / §30.3: fit_values_to_returns(pipeline="device") equals the host pipeline by bits and in every reported number, and
+fresh=True gives every sweep after the first its own record — restated here as a second agent's host-pipeline fit."""
+import numpy as np
+import pytest
+import torch
+
+from skill_chaining_with_graphs_amd import ScgError
+from skill_chaining_with_graphs_amd.agent import SkillChainingAgent
+from skill_chaining_with_graphs_amd.trajectory import DeviceRecord
+from gpu_util import dev
+from test_gpu_lambda_returns import small_agent          # noqa: F401  (the fixture: 64 episodes at epsilon = 0.5, seed 9)
+from util import HP, dense_map, disc_weights
+
+pytestmark = pytest.mark.gpu
+
+KEPT = dict(epsilon=0.5, seed=9)
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def same_array(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def numbers(vf):
+    """A sweep's per-value-function report without the kept operands, as text: equal, not merely close (NaN equals NaN)."""
+    return repr({k: {f: v for f, v in rep.items() if f != "operands"} for k, rep in vf.items()})
+
+
+@pytest.mark.parametrize("lam", [0.9, [0.9, 0.3, 1.0]], ids=["lam0.9", "lam_per_vf"])
+@pytest.mark.parametrize("trace", ["peng", "watkins"])
+def test_device_pipeline_equals_the_host_pipeline(small_agent, trace, lam):
+    ag, report, _ = small_agent
+    traj = report["trajectory"]
+    W0 = ag.W.clone()
+    rep_h, W_h = ag.fit_values_to_returns(trajectory=traj, lam=lam, trace=trace, sweeps=2, keep=True, **KEPT)
+    rep_d, W_d = ag.fit_values_to_returns(trajectory=traj, lam=lam, trace=trace, sweeps=2, keep=True, pipeline="device", **KEPT)
+    torch.cuda.synchronize()
+    assert torch.equal(ag.W, W0) and not torch.equal(W_d, W0)
+    assert torch.equal(bits(W_d), bits(W_h))
+    assert len(rep_d["sweeps"]) == len(rep_h["sweeps"]) == 2
+    for s_d, s_h in zip(rep_d["sweeps"], rep_h["sweeps"]):
+        assert torch.equal(bits(s_d["W"]), bits(s_h["W"]))
+        assert numbers(s_d["vf"]) == numbers(s_h["vf"])
+    assert rep_d["lam"] == rep_h["lam"] and rep_d["trace"] == rep_h["trace"] == trace and rep_d["vf"] is rep_d["sweeps"][1]["vf"]
+    lt_d, lt_h = rep_d["lambda_targets"], rep_h["lambda_targets"]
+    assert set(lt_d) == set(lt_h)
+    for f in lt_h:
+        assert same_array(lt_d[f], lt_h[f]), f
+    for k in rep_h["vf"]:                                      # the sample lists: the host path's rows by value
+        op_d, op_h = rep_d["vf"][k]["operands"], rep_h["vf"][k]["operands"]
+        assert op_d["n_fit"] == op_h["n_fit"]
+        for f in ("rows", "action", "y", "d", "offsets", "delta"):
+            assert same_array(op_d[f], op_h[f]), (k, f)
+    assert same_array(rep_d["targets"]["y"], rep_h["targets"]["y"]) and isinstance(rep_d["trajectory"], DeviceRecord)
+    assert sum(rep_h["vf"][0]["n"]) > 100 and sum(rep_h["vf"][2]["n"]) > 20, "both value functions must run"
+
+
+def second_agent(W):
+    """small_agent's agent once more, loaded with the tables W."""
+    m = dense_map()
+    ag = SkillChainingAgent(m, 256, 2, seed=5, block_envs=256, **dict(HP, max_episode_steps=63, r_option_success=0.0))
+    sx, sy = (float(v) for v in m.starts[0])
+    clf = np.zeros((3, 8), np.float32)
+    clf[1], clf[2] = -disc_weights(sx, sy, 0.04), disc_weights(0.5, 0.5, 1.5)
+    ag.clf.copy_(dev(clf))
+    ag.enable_option(2)
+    ag.gest_mask = 0b010
+    ag.gest_counts = ag.ctx.set_gestation(ag.gest_mask)
+    ag.W.copy_(W)
+    return ag
+
+
+def test_a_fresh_sweep_is_a_fit_on_a_record_under_the_table_handed_on(small_agent):
+    ag, report, _ = small_agent
+    traj = report["trajectory"]
+    W0 = ag.W.clone()
+    kw = dict(lam=0.9, trace="watkins", n_episodes=64)
+    rep_f, W_f = ag.fit_values_to_returns(trajectory=traj, sweeps=2, fresh=True, apply=False, **kw, **KEPT)
+    assert torch.equal(ag.W, W0), "apply=False must leave the agent's tables alone"
+    rep_1, W_1 = ag.fit_values_to_returns(trajectory=traj, sweeps=1, **kw, **KEPT)          # the kept path, host pipeline
+    sw1, sw2 = rep_f["sweeps"]
+    assert torch.equal(bits(sw1["W"]), bits(W_1)) and numbers(sw1["vf"]) == numbers(rep_1["vf"])
+    other = second_agent(W_1)
+    try:
+        traj2, summary2 = other.record_episodes(64, epsilon=0.5, seed=10)
+        rep_2, W_2 = other.fit_values_to_returns(trajectory=traj2, epsilon=0.5, seed=10, lam=0.9, trace="watkins")
+    finally:
+        other.ctx.close()
+    assert torch.equal(bits(W_f), bits(W_2)) and torch.equal(bits(sw2["W"]), bits(W_2))
+    assert numbers(sw2["vf"]) == numbers(rep_2["vf"])
+    assert repr(sw2["episodes"]) == repr(summary2) and sw1["episodes"] is None          # (a kept record brings no summary)
+    assert all(rep["a_changed"] is None for rep in sw2["vf"].values())
+    for k in (0, 2):
+        assert 0.0 < sw2["vf"][k]["cut_share"] < 1.0, (k, sw2["vf"][k]["cut_share"])
+
+
+def test_at_epsilon_zero_a_fresh_sweep_cuts_nothing(small_agent):
+    ag, _, _ = small_agent
+    rep, _ = ag.fit_values_to_returns(n_episodes=64, epsilon=0.0, seed=9, lam=0.9, trace="watkins", sweeps=2, fresh=True)
+    assert rep["sweeps"][0]["episodes"] is rep["episodes"] and rep["sweeps"][1]["episodes"]["episodes"] == 64
+    ran = [rep_k for rep_k in rep["sweeps"][1]["vf"].values() if sum(rep_k["n"]) > 0]
+    assert ran and all(rep_k["cut_share"] == 0.0 for rep_k in ran), [rep_k["cut_share"] for rep_k in ran]
+
+
+def test_refusals(small_agent):
+    ag, report, _ = small_agent
+    traj = report["trajectory"]
+    fit = lambda **kw: ag.fit_values_to_returns(trajectory=traj, **KEPT, **kw)
+    with pytest.raises(ScgError, match="pipeline must be 'host' or 'device'"):
+        fit(lam=0.9, pipeline="gpu")
+    with pytest.raises(ScgError, match="pipeline='device' needs lam"):
+        fit(pipeline="device")
+    with pytest.raises(ScgError, match="pipeline='device' cannot be given with order"):
+        fit(pipeline="device", order=3, lam=0.5)
+    with pytest.raises(ScgError, match="pipeline='device' cannot be given with double"):
+        fit(pipeline="device", lam=0.5, double=True)
+    for kw in (dict(), dict(lam=0.5, double=True), dict(lam=0.5, order=3)):
+        with pytest.raises(ScgError, match="fresh=True needs lam and cannot be given with double or order"):
+            fit(fresh=True, **kw)
