@@ -7,6 +7,7 @@ nothing on the per-step path synchronises with or copies to the host."""
 from __future__ import annotations
 
 import contextlib
+import functools
 import os
 from typing import List, Optional
 
@@ -809,57 +810,50 @@ class SkillChainingAgent:
                               ridge: float = 1e-3, apply: bool = False, interrupt: bool = False, choose: Optional[str] = None,
                               keep: bool = False, order: Optional[int] = None, trajectory=None, lam=None, sweeps: int = 1, trace: str = "peng",
                               double: bool = False, pipeline: str = "host", fresh: bool = False):
-        """The best linear fit of each Q_k to the returns its own policy realises (SPEC §16): record_episodes() with the current
-        policy, Monte-Carlo targets by valuefit.returns_to_go, then per value function k of `vfs` (default: all) and action a the
-        ridge regression of the residual y - Q_k^old on the 1296 features over the rows with vf = k, action = a of the EVEN envs
-        (the odd envs are held out): A, b by ScgContext.feature_gram with the action as segment, Delta by valuefit.ridge_solve,
-        W_k[a] <- float32(W_k^old[a] + Delta). An action without samples keeps its row bit for bit.
-        Returns (report, W_new): W_new a copy of W with the fitted rows; report["vf"][k] holds n (fit samples per action),
-        delta_norm and, for "fit" and "held_out", old / new: n, rmse, mean_error of Q^old / Q^new against y. The held-out numbers
-        are the ones that count. `keep` adds the operands (report["vf"][k]["operands"]: states, action, y, d, offsets, A, b) and
-        report["targets"] (returns_to_go's dict) and report["trajectory"].
+        """The best linear fit of each Q_k to the returns its own policy realises (SPEC §16, §18, §27 - §30): one loop over a flat view
+        of a record (valuefit.flat_view / DeviceRecord.flat: the rows in (env, row) order on the device, with their row tables).
+        The record is record_episodes() with the current policy, or `trajectory`, a kept record (report["trajectory"] of an earlier
+        call; report["episodes"] is then None). Every sweep forms its targets y over all rows and then, per value function k of `vfs`
+        (default: all), runs one unit (_fit_unit): the sample list — the step rows with vf = k of the EVEN envs sorted by action with
+        a stable sort, then those of the odd envs, which are held out; a sample's state is that of the row before —, Q^old of the
+        samples, the residual d = float32(y - float64 Q^old), per action A, b by ScgContext.feature_gram with the action as segment,
+        Delta by valuefit.ridge_solve on the host, W_k[a] <- float32(W_k^old[a] + Delta) (an action without samples keeps its row bit
+        for bit), and Q^new. Returns (report, W_new): W_new a copy of W with the fitted rows; report["vf"][k] holds n (fit samples per
+        action), delta_norm and, for "fit" and "held_out", old / new: n, rmse, mean_error of Q^old / Q^new against y. The held-out
+        numbers are the ones that count. `keep` adds report["vf"][k]["operands"] (states, action, y, d, offsets, n_fit, A, b, rows,
+        delta), report["targets"] (returns_to_go's dict) and report["trajectory"].
         apply=False leaves the agent as evaluate() does: W, training state, t, env order, trace ring, gestation counts and peer
         counter untouched. apply=True copies the fitted rows of `vfs` into W; refused with shared weights (a sharded agent would
         fit its own rank's copy only, and the ranks' W would part).
-        `order` = p in (3, 5, 7) is SPEC §18's basis-order probe: the same samples, targets and split, the residual regressed on the
-        (p + 1)^4 features of order p (A, b by ScgContext.basis_gram, Lambda from order p's scale table) while Q^old stays the
-        agent's order-5 value: Q^new(s, a) = float32(Q^old + v), v = ScgContext.basis_values(float32(Delta))[a], the sum in float64.
-        The report adds "order" and "features" and, per value function, "delta" (float64 [5][F]); W_new is a plain copy of W, and
-        apply=True is refused (no kernel acts on F != 1296 weights). order=None is the path above, untouched.
-        `trajectory`: a kept record (report["trajectory"] of an earlier call) to fit on instead of recording, as fit_values_lstdq
-        takes one: several orders are then fitted to one record; report["episodes"] is None.
-        `lam` in [0, 1] is SPEC §27's fit to lambda-returns: the targets come from valuefit.lambda_targets under W (lam = 1: the
-        Monte-Carlo return, lam = 0: §17.2's one-step target); samples, split, Gram, ridge and report stay as above. `sweeps` = S
-        re-forms the targets under the previous sweep's W_new on the same record and refits from it (fitted policy evaluation);
-        W_new is the last sweep's. The report adds "lam" and "sweeps" (per sweep "vf" and "W"; report["vf"] is the last sweep's), and
-        per value function "mc": for "fit" and "held_out", old / new against the MONTE-CARLO targets of returns_to_go, so that every
-        lam is judged on §16's scale. `order` together with `lam` is refused, and so is sweeps != 1 without lam. lam=None is the
-        path above, untouched.
-        `trace` is SPEC §28's choice of the trace. "peng" (the default) with a float `lam` is the path above, call for call.
-        "watkins" takes the targets from valuefit.trace_targets(cut=True) under the sweep's W_cur: the trace is cut wherever the
-        recorded action is not the greedy action of the table bootstrapped from (re-formed every sweep), so the targets evaluate that
-        table's greedy policy. `lam` may be a sequence of n_vf floats, one per value function, with either trace ("peng": through
-        trace_targets(cut=False)). With trace_targets the report adds, per sweep and value function, "cut_share" (the share of its
-        sample rows whose incoming coefficient is 0), "off_greedy" (the share whose recorded action is not the greedy one) and
-        "horizon" (the mean effective length h of the root stream over them) and "a_changed" (the share whose greedy action differs
-        from the one under the sweep before's table; None in the first sweep); report["trace"] names the trace wherever lam is given.
-        Refused: a trace other than the two names, "watkins" without lam, a lam sequence of another length than n_vf or with an
-        entry outside [0, 1].
-        `double` is SPEC §29.2's double-estimator fit (_fit_values_double: two tables on two folds of the fit half, each
-        bootstrapping from the other's value of its own greedy action; W_new is their mean). It needs lam, is refused with order and
-        works with both traces. double=False is the path above, call for call.
-        `pipeline` = "device" (SPEC §30.2; needs lam, refused with order and double) is the same fit with the record, the targets,
-        the sample lists and the residual formed on the device (_fit_values_device): the record is a trajectory.DeviceRecord (recorded
-        with device=True; a Trajectory given as `trajectory` is uploaded once), Q^old and Q^new come from ScgContext.row_action_values,
-        the Gram call and the host ridge solve are the ones above. W_new, every sweep's W and every reported number equal the host
-        pipeline's. "host", the default, is the path above, call for call.
-        `fresh` (SPEC §30.3; needs lam, implies pipeline="device", refused with order and double): sweep 1 runs on the given or
-        recorded record; every later sweep s records `n_episodes` new episodes under the table the sweep before handed on, with this
-        call's epsilon, interrupt and choose and the seed `seed` + s - 1, and takes its targets, samples, split and held-out half from
-        that record. Every sweep's entry then holds "episodes" (its record's summary), its "mc" is against its own record's returns,
-        and "a_changed" is None: the rows differ between sweeps."""
+        The targets. lam=None: the Monte-Carlo targets of valuefit.returns_to_go, one sweep. `lam` in [0, 1] (SPEC §27): the
+        lambda-returns of valuefit.sweep_targets under the table the sweep starts from (lam = 1: the Monte-Carlo return, lam = 0:
+        §17.2's one-step target); `sweeps` = S re-forms them under the sweep before's W_new on the same record and refits from it
+        (fitted policy evaluation). The report adds "lam", "trace" and "sweeps" (per sweep "vf" and "W"; report["vf"] is the last
+        sweep's), per value function "mc" (the error block against the MONTE-CARLO targets, so that every lam is judged on §16's
+        scale) and with `keep` report["lambda_targets"] (valuefit.lambda_targets' / trace_targets' dict of the last sweep).
+        `trace` (SPEC §28): "watkins" cuts the trace wherever the recorded action is not the greedy action of the table bootstrapped
+        from, so the targets evaluate that table's greedy policy; `lam` may be a sequence of n_vf floats, one per value function,
+        with either trace. Both take the targets from ScgContext.trace_returns ("peng" with a float: lambda_returns) and add
+        valuefit.trace_stats' "cut_share", "off_greedy", "horizon" and "a_changed" (None in the first sweep) per value function.
+        `order` = p in (3, 5, 7) (SPEC §18's basis-order probe, Monte-Carlo targets only): the residual is regressed on the (p + 1)^4
+        features of order p (ScgContext.basis_gram, Lambda from order p's scale table, the solve on the device) while Q^old stays the
+        agent's order-5 value: Q^new = float32(Q^old + v), v = ScgContext.basis_values(float32(Delta))[a], the sum in float64. The
+        report adds "order", "features" and per value function "delta" (float64 [5][F]); W_new is a plain copy of W.
+        `double` (SPEC §29.2; needs lam): every sweep is _double_sweep — two tables on two folds of the fit half, each bootstrapping
+        from the other's value of its own greedy action, one unit per fold; W_new is their mean, which the held-out half judges.
+        `pipeline`: where the view comes from and how Q of a sample list is formed. "host": the Trajectory uploaded once per call,
+        ScgContext.q_values in chunks of the evaluation context's n_envs. "device" (SPEC §30.2; needs lam): a trajectory.DeviceRecord
+        (recorded with device=True; a Trajectory given as `trajectory` is uploaded into one), one ScgContext.row_action_values call,
+        as under `double`; report["trajectory"] is the DeviceRecord. W_new and every reported number are equal.
+        `fresh` (SPEC §30.3; needs lam, implies pipeline="device"): every sweep s after the first records `n_episodes` new episodes
+        under the table the sweep before handed on, with this call's epsilon, interrupt and choose and the seed `seed` + s - 1, and
+        takes its targets, samples and held-out half from that record. Every sweep's entry then holds "episodes" (its record's
+        summary), its "mc" is against its own record's returns, and "a_changed" is None: the rows differ between sweeps.
+        Refused (ScgError): a trace other than the two names; "watkins", double, pipeline="device" or fresh without lam; double,
+        pipeline="device", fresh or lam with order; pipeline="device" or fresh with double; a lam outside [0, 1] or a lam sequence of
+        another length than n_vf; sweeps < 1, or != 1 without lam; order with apply=True; apply=True with shared weights."""
         from .core import fourier_scale_table
-        from .valuefit import error_stats, returns_to_go
+        from .valuefit import flat_view, host_targets, returns_to_go, sweep_targets, trace_stats
         if trace not in ("peng", "watkins"):
             raise ScgError(f"fit_values_to_returns: trace must be 'peng' or 'watkins', not {trace!r}")
         if trace == "watkins" and lam is None:
@@ -906,113 +900,77 @@ class SkillChainingAgent:
         if any(not (0 <= k < self.n_vf) for k in vfs):
             raise ValueError(f"vfs must name value functions 0..{self.n_vf - 1}")
         c = self.ctx.cfg
-        if pipeline == "device":
-            if trajectory is None:
-                rec, summary = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose, device=True)
-                ectx = self._eval_ctx[int(n_episodes)][0]
-            else:
-                ectx, summary = self._eval_context(int(trajectory.n), epsilon, seed, None)[0], None
-                rec = trajectory if isinstance(trajectory, DeviceRecord) else DeviceRecord.from_trajectory(ectx, trajectory)
-            again = None
-            if fresh:                                          # SPEC §30.3: sweep s (from 1) records under the table handed on, at seed + s - 1
-                seed0 = int(c.seed) if seed is None else int(seed)
-                again = lambda s, W: self._record_under(W, n_episodes, epsilon, seed0 + s, interrupt, choose)
-            return self._fit_values_device(ectx, rec, summary, vfs, ridge, lam, int(sweeps), trace, keep, apply, again)
-        if isinstance(trajectory, DeviceRecord):
+        gamma, r_succ = float(c.gamma), float(c.r_option_success)
+        seed0 = int(c.seed) if seed is None else int(seed)
+        device = pipeline == "device"
+        if isinstance(trajectory, DeviceRecord) and not device:
             trajectory = trajectory.to_trajectory()
         if trajectory is None:
-            traj, summary = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose)
+            rec, summary = self.record_episodes(n_episodes, epsilon=epsilon, seed=seed, interrupt=interrupt, choose=choose, device=device)
             ectx = self._eval_ctx[int(n_episodes)][0]
         else:
-            traj, summary = trajectory, None
-            ectx = self._eval_context(int(traj.n), epsilon, seed, None)[0]
-        flat = traj.to_numpy()
-        tg = returns_to_go(flat, float(c.gamma), float(c.r_option_success))
-        if double:
-            return self._fit_values_double(ectx, traj, flat, tg, summary, vfs, ridge, lam, int(sweeps), trace, keep, apply)
-        off = flat["offsets"]
-        env = np.repeat(np.arange(traj.n), np.diff(off))
-        smp = np.nonzero(tg["sample"])[0]                      # the rows that are steps, in (env, row) order; their s is the row before
-        dev = self.W.device
-        W_new = self.W.clone()
+            rec, summary = trajectory, None
+            ectx = self._eval_context(int(rec.n), epsilon, seed, None)[0]
+            if device and not isinstance(rec, DeviceRecord):
+                rec = DeviceRecord.from_trajectory(ectx, rec)
         report = {"episodes": summary, "ridge": float(ridge), "vf": {}}
-        # the regression basis: the Gram of the fit samples and the scale table of the ridge term
-        gram = ectx.feature_gram if order is None else (lambda st, offs, yv: ectx.basis_gram(order, st, offs, yv))
-        scale = self.ctx.scale if order is None else fourier_scale_table(order)
         if order is not None:
             report["order"], report["features"] = int(order), _lib.basis_features(order)
-
-        def q_of(states, Wk, act):                             # Q_k(s_n, a_n) of a sample list, float32 as the kernel gives it
-            out = np.zeros(len(act), np.float32)
-            for i in range(0, len(act), ectx.n_envs):
-                sl = slice(i, i + ectx.n_envs)
-                q = ectx.q_values([t[sl].contiguous() for t in states], Wk.contiguous().view(-1)).cpu().numpy()
-                out[sl] = q[act[sl], np.arange(q.shape[1])]
-            return out
-
-        W_cur = self.W                                         # what the targets bootstrap from and the residual is taken against
         if lam is not None:
-            from .valuefit import lambda_targets, trace_targets
             report["lam"], report["sweeps"], report["trace"] = (list(lam) if lam_seq else float(lam)), [], trace
-        at_sweep = None
-        for sweep, k in ((s, k) for s in range(int(sweeps)) for k in vfs):
-            if lam is not None and sweep != at_sweep:          # a sweep begins: its targets under the sweep before's weights
-                if at_sweep is not None:
-                    report["sweeps"].append({"vf": report["vf"], "W": W_new.clone()})
-                at_sweep = sweep
-                W_cur = W_new.clone()
-                if traced:
-                    ag_prev = lt["ag"] if sweep else None      # the greedy actions under the table of the sweep before
-                    lt = trace_targets(ectx, flat, W_cur, float(c.gamma), lam, float(c.r_option_success), cut=trace == "watkins")
-                else:
-                    lt = lambda_targets(ectx, flat, W_cur, float(c.gamma), float(lam), float(c.r_option_success))
+        # the one difference in the arithmetic's calls: how Q of a sample list is formed
+        q_of = self._q_rows if device or double else self._q_chunks
+        scale = self.ctx.scale if order is None else fourier_scale_table(order)
+        W_new = self.W.clone()
+        W_a, W_b = (self.W.clone(), self.W.clone()) if double else (None, None)
+        ag_prev = None
+        for sweep in range(int(sweeps)):
+            if fresh and sweep:                                # SPEC §30.3: sweep s (from 1) records under the table handed on, at seed + s
+                ectx, rec, summary = self._record_under(W_new.clone(), n_episodes, epsilon, seed0 + sweep, interrupt, choose)
+            if fresh or not sweep:                             # a new record: its flat view, its halves and Monte-Carlo targets
+                if device:
+                    fl = rec.flat(ectx)
+                    if "tabA" not in fl or any(f not in fl for f in ("x", "y", "vx", "vy", "reward", "action")):
+                        raise ScgError("fit_values_to_returns: the record must hold the state, reward, action, done, vf and term fields")
+                flat = rec.to_numpy()                          # (of a DeviceRecord: ONE download of the record)
+                if not device:
+                    fl = flat_view(ectx, flat)
+                tg = returns_to_go(flat, gamma, r_succ)
+                even = fl["env"] % 2 == 0                      # the fit half, by action; the odd envs are held out
+                lists = {} if double else {k: (self._sample_rows(fl, k, even, by_action=True), self._sample_rows(fl, k, ~even))
+                                           for k in vfs}
+                unit = functools.partial(self._fit_unit, ectx, fl, None if lam is None else tg["y"], q_of, ridge, order, scale)
+            if double:
+                report["vf"], W_new, lt = self._double_sweep(unit, ectx, fl, tg["y"], q_of, vfs, W_a, W_b, gamma, lam, r_succ,
+                                                             trace == "watkins", keep)
+                entry = {"vf": report["vf"], "W": W_new.clone(), "W_a": W_a.clone(), "W_b": W_b.clone()}
+            else:
+                W_cur = W_new.clone()                          # what the targets bootstrap from and the residual is taken against
+                lt = {"y": torch.from_numpy(tg["y"]).to(W_cur.device)} if lam is None else \
+                    sweep_targets(ectx, fl, W_cur, gamma, lam, r_succ, traced=traced, cut=trace == "watkins")
                 report["vf"] = {}
-            rows = smp[flat["vf"][smp] == k]
-            rows = np.concatenate([rows[env[rows] % 2 == 0], rows[env[rows] % 2 == 1]])      # the fit half, then the held-out half
-            n_fit = int(np.sum(env[rows] % 2 == 0))
-            by_action = np.argsort(flat["action"][rows[:n_fit]], kind="stable")
-            rows[:n_fit] = rows[:n_fit][by_action]                 # the fit samples by action, (env, row) order within one
-            act = flat["action"][rows].astype(np.int64)
-            y = tg["y"][rows] if lam is None else lt["y"][rows]
-            states = [torch.from_numpy(np.ascontiguousarray(flat[f][rows - 1])).to(dev) for f in ("x", "y", "vx", "vy")]
-            q_old = q_of(states, W_cur[k], act)
-            d = (y - q_old.astype(np.float64)).astype(np.float32)
-            if order is None:
-                n_a, offsets, A, b, delta, w_new = self._refit_rows(gram, states, d, act[:n_fit], ridge, scale, W_cur[k])
-                W_new[k] = torch.from_numpy(w_new).to(dev)
-                q_new = q_of(states, W_new[k], act)
-            else:                                              # (F up to 4096: factored on the device)
-                n_a, offsets, A, b, delta, _ = self._refit_rows(gram, states, d, act[:n_fit], ridge, scale, None)
-                q_new = q_old.copy()                           # the correction lives at order p: Q^new = Q^old + Delta . phi^p
-                if len(act):
-                    v = ectx.basis_values(order, states, torch.from_numpy(delta.astype(np.float32)).to(dev)).cpu().numpy()
-                    q_new = (q_old.astype(np.float64) + v[act, np.arange(len(act))].astype(np.float64)).astype(np.float32)
-            half = {"fit": slice(0, n_fit), "held_out": slice(n_fit, None)}
-            rep = {"n": [int(v) for v in n_a], "delta_norm": float(np.sqrt(np.sum(delta * delta)))}
-            if order is not None:
-                rep["delta"] = delta
-            for name, sl in half.items():
-                rep[name] = {"old": error_stats(q_old[sl], y[sl]), "new": error_stats(q_new[sl], y[sl])}
+                for k in vfs:
+                    rows = torch.cat(lists[k])
+                    rep, operands = unit(k, rows, lists[k][0].numel(), lt["y"], W_cur, W_new)
+                    if traced:
+                        rep.update(trace_stats(lt, rows, ag_prev))
+                    if keep:
+                        rep["operands"] = operands
+                    report["vf"][k] = rep
+                entry = {"vf": report["vf"], "W": W_new.clone()}
+                ag_prev = lt["ag"] if traced and not fresh else None
+            if fresh:
+                entry["episodes"] = summary
             if lam is not None:
-                y_mc = tg["y"][rows]
-                rep["mc"] = {name: {"old": error_stats(q_old[sl], y_mc[sl]), "new": error_stats(q_new[sl], y_mc[sl])}
-                             for name, sl in half.items()}
-                if traced:
-                    nan = float("nan")
-                    rep["cut_share"] = float(np.mean(lt["c"][rows] == 0.0)) if len(rows) else nan
-                    rep["off_greedy"] = float(np.mean(lt["cut"][rows])) if len(rows) else nan
-                    rep["horizon"] = float(np.mean(lt["h"][rows])) if len(rows) else nan
-                    rep["a_changed"] = None if ag_prev is None else float(np.mean(lt["ag"][rows - 1] != ag_prev[rows - 1])) if len(rows) else nan
-            if keep:
-                rep["operands"] = {"states": states, "action": act, "y": y, "d": d, "offsets": offsets, "n_fit": n_fit, "A": A, "b": b,
-                                   "rows": rows, "delta": delta}
-            report["vf"][k] = rep
-        if lam is not None and at_sweep is not None:
-            report["sweeps"].append({"vf": report["vf"], "W": W_new.clone()})
+                report["sweeps"].append(entry)
+        if double:
+            report["double"] = {"W_a": W_a, "W_b": W_b}
         if keep:
-            report["targets"], report["trajectory"] = tg, traj
-            if lam is not None:
-                report["lambda_targets"] = lt
+            report["targets"], report["trajectory"] = tg, rec
+            if double:
+                report["double_targets"] = {"AB": host_targets(fl, lt["a"]), "BA": host_targets(fl, lt["b"])}
+            elif lam is not None:
+                report["lambda_targets"] = host_targets(fl, lt)
         if apply:
             for k in vfs:
                 self.W[k].copy_(W_new[k])
@@ -1023,120 +981,6 @@ class SkillChainingAgent:
         self.W is not written."""
         stats, rec = self._eval_launches(n_episodes, epsilon, seed, 64, None, interrupt, record=True, choose=choose, W=W, device=True)
         return self._eval_ctx[int(n_episodes)][0], rec, stats.summary()
-
-    def _fit_values_device(self, ectx, rec, summary, vfs, ridge: float, lam, sweeps: int, trace: str, keep: bool, apply: bool, again):
-        """fit_values_to_returns(pipeline="device"), SPEC §30.2: the host path's fit with every per-row and per-sample array formed on
-        the device from DeviceRecord.flat(). Per record: the flat tensors, the Monte-Carlo targets (valuefit.returns_to_go on ONE
-        download of the record: the report's "mc") and, per value function, the sample list — the step rows with vf = k of the even
-        envs in (env, row) order, sorted by action with a stable sort, then those of the odd envs: the host path's `rows` by value.
-        Per sweep: v0, vk (and ag) by the host path's row_values calls on the pack's tables, the scan by its lambda_returns /
-        trace_returns call, then per value function Q^old = row_action_values under the sweep's table, d = float32(y - float64 Q^old)
-        on the device, feature_gram, valuefit.ridge_solve on the host, Q^new = row_action_values under the new row. The statistics are
-        the host path's numpy expressions on the downloaded per-sample arrays. `again(s, W)` (SPEC §30.3, or None) gives sweep s >= 1
-        its own record under W."""
-        from .valuefit import error_stats, returns_to_go, ridge_solve
-        c = self.ctx.cfg
-        gamma, r_succ = float(c.gamma), float(c.r_option_success)
-        dev = self.W.device
-        lam_seq = np.ndim(lam) != 0
-        traced = trace == "watkins" or lam_seq
-        lam_vf = [float(v) for v in lam] if lam_seq else [float(lam)] * self.n_vf
-        report = {"episodes": summary, "ridge": float(ridge), "vf": {}, "lam": list(lam) if lam_seq else float(lam), "sweeps": [],
-                  "trace": trace}
-        nan = float("nan")
-        W_new = self.W.clone()
-        ag_prev = None
-        for sweep in range(sweeps):
-            W_cur = W_new.clone()                              # what the targets bootstrap from and the residual is taken against
-            if sweep and again is not None:
-                ectx, rec, summary = again(sweep, W_cur)
-            if sweep == 0 or again is not None:                # a new record: its flat tensors, Monte-Carlo targets and sample lists
-                fl = rec.flat(ectx)
-                if "tabA" not in fl or any(f not in fl for f in ("x", "y", "vx", "vy", "reward", "action")):
-                    raise ScgError("fit_values_to_returns: the record must hold the state, reward, action, done, vf and term fields")
-                tg = returns_to_go(rec.to_numpy(), gamma, r_succ)
-                step = fl["row"] >= 1
-                lists = {}
-                for k in vfs:
-                    mine = step & (fl["vf"] == k)
-                    fit = torch.nonzero(mine & (fl["env"] % 2 == 0)).view(-1)
-                    fit = fit[torch.sort(fl["action"][fit], stable=True)[1]]
-                    rows = torch.cat([fit, torch.nonzero(mine & (fl["env"] % 2 == 1)).view(-1)])
-                    lists[k] = (rows, int(fit.numel()), rows.cpu().numpy())
-            # ---- the sweep's targets: the host path's calls on the pack's tables
-            states_all = [fl[f] for f in ("x", "y", "vx", "vy")]
-            Wt = W_cur.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES)
-            v0, _ = ectx.row_values(states_all, fl["tab0"], Wt[:1], actions=False)
-            vk, _ = ectx.row_values(states_all, fl["tabk"], Wt, actions=False)
-            lt = {"v0": v0, "vk": vk}
-            if traced:
-                _, ag = ectx.row_values(states_all, fl["tabA"], Wt, actions=True)
-                y0, yk, h = ectx.trace_returns(fl["offsets"], fl["reward"], fl["done"], fl["vf"], fl["term"], fl["action"], ag, v0, vk,
-                                               gamma, lam_vf, r_succ, cut=trace == "watkins", horizon=True)
-                off_greedy = torch.zeros_like(step)
-                off_greedy[1:] = step[1:] & (fl["action"][1:] != ag[:-1])
-                vf_l = fl["vf"].long()
-                coef = torch.tensor(lam_vf, dtype=torch.float64, device=dev)[torch.where(vf_l < len(lam_vf), vf_l, torch.zeros_like(vf_l))]
-                coef = torch.where(step, coef, torch.zeros_like(coef))
-                if trace == "watkins":
-                    coef = torch.where(off_greedy, torch.zeros_like(coef), coef)
-                lt.update(ag=ag, h=h, c=coef, cut=off_greedy)
-            else:
-                y0, yk = ectx.lambda_returns(fl["offsets"], fl["reward"], fl["done"], fl["vf"], fl["term"], v0, vk, gamma, float(lam),
-                                             r_succ)
-            lt.update(y0=y0, yk=yk, y=torch.where(fl["vf"] >= 1, yk, y0))
-            report["vf"] = {}
-            for k in vfs:
-                rows, n_fit, rows_h = lists[k]
-                act = fl["action"][rows].contiguous()
-                states = [fl[f][rows - 1].contiguous() for f in ("x", "y", "vx", "vy")]
-                tab = torch.full((rows.numel(),), int(k), dtype=torch.uint8, device=dev)
-                y_d = lt["y"][rows]
-                q_old_d = ectx.row_action_values(states, tab, Wt, act)
-                d = (y_d - q_old_d.double()).float()           # float64 on the device, rounded once
-                n_a = torch.bincount(act[:n_fit].long(), minlength=NUM_ACTIONS).cpu().numpy().astype(np.int64)
-                offsets = np.concatenate([[0], np.cumsum(n_a)]).astype(np.int64)
-                A, b = ectx.feature_gram(states, offsets, d)
-                delta = ridge_solve(A.cpu().numpy(), b.cpu().numpy(), n_a, ridge, self.ctx.scale)
-                w_old = W_cur[k].cpu().numpy()
-                w_new = (w_old.astype(np.float64) + delta).astype(np.float32)
-                w_new[n_a == 0] = w_old[n_a == 0]
-                W_new[k] = torch.from_numpy(w_new).to(dev)
-                q_new_d = ectx.row_action_values(states, tab, W_new.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES), act)
-                # ---- the report: the host path's expressions on the per-sample arrays
-                q_old, q_new, y = q_old_d.cpu().numpy(), q_new_d.cpu().numpy(), y_d.cpu().numpy()
-                half = {"fit": slice(0, n_fit), "held_out": slice(n_fit, None)}
-                rep = {"n": [int(v) for v in n_a], "delta_norm": float(np.sqrt(np.sum(delta * delta)))}
-                for name, sl in half.items():
-                    rep[name] = {"old": error_stats(q_old[sl], y[sl]), "new": error_stats(q_new[sl], y[sl])}
-                y_mc = tg["y"][rows_h]
-                rep["mc"] = {name: {"old": error_stats(q_old[sl], y_mc[sl]), "new": error_stats(q_new[sl], y_mc[sl])}
-                             for name, sl in half.items()}
-                if traced:
-                    some = len(rows_h) > 0
-                    rep["cut_share"] = float(np.mean(lt["c"][rows].cpu().numpy() == 0.0)) if some else nan
-                    rep["off_greedy"] = float(np.mean(lt["cut"][rows].cpu().numpy())) if some else nan
-                    rep["horizon"] = float(np.mean(lt["h"][rows].cpu().numpy())) if some else nan
-                    rep["a_changed"] = None if ag_prev is None else \
-                        float(np.mean((lt["ag"][rows - 1] != ag_prev[rows - 1]).cpu().numpy())) if some else nan
-                if keep:
-                    rep["operands"] = {"states": states, "action": act.cpu().numpy().astype(np.int64), "y": y, "d": d.cpu().numpy(),
-                                       "offsets": offsets, "n_fit": n_fit, "A": A, "b": b, "rows": rows_h, "delta": delta}
-                report["vf"][k] = rep
-            entry = {"vf": report["vf"], "W": W_new.clone()}
-            if again is not None:
-                entry["episodes"] = summary
-            report["sweeps"].append(entry)
-            ag_prev = lt["ag"] if traced and again is None else None
-        if keep:
-            report["targets"], report["trajectory"] = tg, rec
-            host = {f: v.cpu().numpy() for f, v in lt.items()}
-            host.update(offsets=fl["offsets"].cpu().numpy(), sample=step.cpu().numpy())
-            report["lambda_targets"] = host
-        if apply:
-            for k in vfs:
-                self.W[k].copy_(W_new[k])
-        return report, W_new
 
     def _refit_rows(self, gram, states, d, act_fit, ridge: float, scale, W_k):
         """The refit of one table's rows to a residual (SPEC §16.3), the one copy of it: the per-action segments of the fit samples
@@ -1157,112 +1001,116 @@ class SkillChainingAgent:
         w_new[n_a == 0] = w_old[n_a == 0]
         return n_a, offsets, A, b, delta, w_new
 
-    def _fit_values_double(self, ectx, traj, flat, tg, summary, vfs, ridge: float, lam, sweeps: int, trace: str, keep: bool,
-                           apply: bool):
-        """fit_values_to_returns(double=True), SPEC §29.2. Two tables, W_A = W_B = W to start. Every sweep forms two target sets over
-        the whole record by valuefit.double_targets — AB: W_A selects the bootstrap action and W_B values it; BA the other way round —
-        and refits table A on fold A's rows (valuefit.fold_of: env % 4 == 0) to AB against its own Q^old under W_A, table B on fold B's
-        rows (env % 4 == 2) to BA, by _refit_rows. Q^old and Q^new of a sample list are one ScgContext.row_action_values call.
-        W_new = valuefit.mean_table(W_A, W_B); the odd envs stay held out and judge the mean table.
-        The report has the single path's layout: report["vf"][k] (the last sweep's; every sweep's under report["sweeps"][s], with "W"
-        the sweep's mean table and "W_a", "W_b") holds n (fit samples per action, both folds), delta_norm (of the mean table's row) and,
-        for "fit" and "held_out", old / new of the MEAN table against (y_AB + y_BA) / 2, "mc" the same against the Monte-Carlo
-        targets, "cut_share" / "off_greedy" / "horizon" as the mean of the two target sets' — and adds "folds": {"a", "b"}, each n,
-        delta_norm, "fit" and "mc" old / new of the fold's own table on the fold's rows against its own targets (`keep`: "operands"),
-        and "optimism": the mean, over the rows whose target reads a bootstrap value of value function k (k = 0: the rows that are not
-        done, v0; k >= 1: the rows with vf = k whose option goes on, vk) and both target sets, of vs - v, the selecting table's own
-        maximum less the other table's value of that action: the max's bias as the two tables estimate it, exactly 0 in sweep 1.
-        report["double"] = {"W_a", "W_b"} are the last sweep's tables; `keep` adds report["targets"], report["trajectory"] and
-        report["double_targets"] = {"AB", "BA"} (the last sweep's)."""
-        from .valuefit import double_targets, error_stats, fold_of, mean_table
-        c = self.ctx.cfg
-        gamma, r_succ = float(c.gamma), float(c.r_option_success)
+    @staticmethod
+    def _sample_rows(fl, k: int, envs, by_action: bool = False):
+        """The sample list of value function k in a flat view: the indices of the step rows (row >= 1) with vf = k among the rows
+        `envs` marks (a bool tensor over the rows: the envs of a half or a fold), in (env, row) order; with `by_action` sorted by
+        action with a stable sort, as the Gram's per-action segments want them. A device int64 tensor."""
+        rows = torch.nonzero((fl["row"] >= 1) & (fl["vf"] == int(k)) & envs).view(-1)
+        return rows[torch.sort(fl["action"][rows], stable=True)[1]] if by_action else rows
+
+    @staticmethod
+    def _q_chunks(ectx, states, W, k: int, act):
+        """Q_k(s_n, a_n) of a sample list under the tables W, a float32 host array as the kernel gives it: ScgContext.q_values in
+        chunks of the context's n_envs, the host pipeline's way."""
+        a = act.cpu().numpy().astype(np.int64)
+        out = np.zeros(len(a), np.float32)
+        for i in range(0, len(a), ectx.n_envs):
+            sl = slice(i, i + ectx.n_envs)
+            q = ectx.q_values([t[sl].contiguous() for t in states], W[k].contiguous().view(-1)).cpu().numpy()
+            out[sl] = q[a[sl], np.arange(q.shape[1])]
+        return out
+
+    @staticmethod
+    def _q_rows(ectx, states, W, k: int, act):
+        """_q_chunks' array by ONE ScgContext.row_action_values call: the device pipeline's and the double fit's way."""
+        tab = torch.full((act.numel(),), int(k), dtype=torch.uint8, device=act.device)
+        return ectx.row_action_values(states, tab, W.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES), act).cpu().numpy()
+
+    def _fit_unit(self, ectx, fl, y_mc, q_of, ridge: float, order, scale, k: int, rows, n_fit: int, y, W_old, W_to):
+        """The unit every fit_values_to_returns mode runs per value function (per fold under `double`): table k of W_old refitted on
+        the sample list `rows` of the flat view `fl` (a device index tensor; the first n_fit, sorted by action, are fitted, the rest
+        held out) to the targets y (a device tensor over all rows). Q^old by `q_of` (_q_chunks or _q_rows) under W_old, the residual
+        float32(y - float64 Q^old), _refit_rows, the new row written into W_to[k], Q^new by `q_of` under W_to; with `order` the
+        Gram and the solve are order p's, no row is written and Q^new = Q^old + basis_values(Delta). The statistics are
+        valuefit.fit_stats on the downloaded per-sample arrays (`y_mc`: the Monte-Carlo targets of all rows, a host array, or None).
+        Returns (the value function's report, its kept operands)."""
+        from .valuefit import fit_stats
         dev = self.W.device
-        off = flat["offsets"]
-        env = np.repeat(np.arange(traj.n), np.diff(off))
-        smp = np.nonzero(tg["sample"])[0]
-        vf_rows, done = np.asarray(flat["vf"]), np.asarray(flat["done"])
-        lam_seq = np.ndim(lam) != 0
-        report = {"episodes": summary, "ridge": float(ridge), "vf": {}, "lam": list(lam) if lam_seq else float(lam), "sweeps": [],
-                  "trace": trace}
-        nan = float("nan")
-        mean = lambda v: float(np.mean(v)) if len(v) else nan
-        up_states = lambda at: [torch.from_numpy(np.ascontiguousarray(flat[f][at])).to(dev) for f in ("x", "y", "vx", "vy")]
+        act_d = fl["action"][rows].contiguous()
+        act, rows_h, y = act_d.cpu().numpy().astype(np.int64), rows.cpu().numpy(), y[rows].cpu().numpy()
+        states = [fl[f][rows - 1].contiguous() for f in ("x", "y", "vx", "vy")]
+        q_old = q_of(ectx, states, W_old, k, act_d)
+        d = (y - q_old.astype(np.float64)).astype(np.float32)
+        if order is None:
+            n_a, offsets, A, b, delta, w_new = self._refit_rows(ectx.feature_gram, states, d, act[:n_fit], ridge, scale, W_old[k])
+            W_to[k] = torch.from_numpy(w_new).to(dev)
+            q_new = q_of(ectx, states, W_to, k, act_d)
+        else:                                                  # (F up to 4096: factored on the device)
+            gram = lambda st, offs, yv: ectx.basis_gram(order, st, offs, yv)
+            n_a, offsets, A, b, delta, _ = self._refit_rows(gram, states, d, act[:n_fit], ridge, scale, None)
+            q_new = q_old.copy()                               # the correction lives at order p: Q^new = Q^old + Delta . phi^p
+            if len(act):
+                v = ectx.basis_values(order, states, torch.from_numpy(delta.astype(np.float32)).to(dev)).cpu().numpy()
+                q_new = (q_old.astype(np.float64) + v[act, np.arange(len(act))].astype(np.float64)).astype(np.float32)
+        rep = {"n": [int(v) for v in n_a], "delta_norm": float(np.sqrt(np.sum(delta * delta)))}
+        if order is not None:
+            rep["delta"] = delta
+        rep.update(fit_stats(q_old, q_new, y, None if y_mc is None else y_mc[rows_h], n_fit))
+        return rep, {"states": states, "action": act, "y": y, "d": d, "offsets": offsets, "n_fit": n_fit, "A": A, "b": b,
+                     "rows": rows_h, "delta": delta}
 
-        def q_of(states, W, k, act):                           # Q_k(s_n, a_n) of a sample list under the tables W, one launch
-            n = len(act)
-            tab = torch.full((n,), int(k), dtype=torch.uint8, device=dev)
-            a = torch.from_numpy(np.ascontiguousarray(act.astype(np.uint8))).to(dev)
-            return ectx.row_action_values(states, tab, W.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES), a).cpu().numpy()
-
-        W_a, W_b = self.W.clone(), self.W.clone()
-        for sweep in range(sweeps):
-            cur = {"a": W_a.clone(), "b": W_b.clone()}         # what the sweep's targets bootstrap from and its residuals are taken against
-            W_mean_old = mean_table(cur["a"], cur["b"])
-            cut = trace == "watkins"
-            lt = {"a": double_targets(ectx, flat, cur["a"], cur["b"], gamma, lam, r_succ, cut=cut),        # AB
-                  "b": double_targets(ectx, flat, cur["b"], cur["a"], gamma, lam, r_succ, cut=cut)}        # BA
-            y_d = (lt["a"]["y"] + lt["b"]["y"]) / 2.0
-            new = {"a": W_a, "b": W_b}
-            per_vf = {}
-            for k in vfs:
-                rows_k = smp[vf_rows[smp] == k]
-                fold = fold_of(env[rows_k])
-                rep = {"folds": {}}
-                for f, name in enumerate(("a", "b")):
-                    rows = rows_k[fold == f]
-                    rows = rows[np.argsort(flat["action"][rows], kind="stable")]      # by action, (env, row) order within one
-                    act = flat["action"][rows].astype(np.int64)
-                    y = lt[name]["y"][rows]
-                    states = up_states(rows - 1)
-                    q_old = q_of(states, cur[name], k, act)
-                    d = (y - q_old.astype(np.float64)).astype(np.float32)
-                    n_a, offsets, A, b, delta, w_new = self._refit_rows(ectx.feature_gram, states, d, act, ridge, self.ctx.scale,
-                                                                        cur[name][k])
-                    new[name][k] = torch.from_numpy(w_new).to(dev)
-                    q_new = q_of(states, new[name], k, act)
-                    y_mc = tg["y"][rows]
-                    fr = {"n": [int(v) for v in n_a], "delta_norm": float(np.sqrt(np.sum(delta * delta))),
-                          "fit": {"old": error_stats(q_old, y), "new": error_stats(q_new, y)},
-                          "mc": {"old": error_stats(q_old, y_mc), "new": error_stats(q_new, y_mc)}}
-                    if keep:
-                        fr["operands"] = {"states": states, "action": act, "y": y, "d": d, "offsets": offsets, "A": A, "b": b,
-                                          "rows": rows, "delta": delta}
-                    rep["folds"][name] = fr
-                per_vf[k] = (rows_k, fold, rep)
-            W_mean = mean_table(W_a, W_b)
-            report["vf"] = {}
-            for k, (rows_k, fold, rep) in per_vf.items():      # the mean table, judged once both tables of the sweep stand
-                rep["n"] = [x + y for x, y in zip(rep["folds"]["a"]["n"], rep["folds"]["b"]["n"])]
-                dk = W_mean[k].double() - W_mean_old[k].double()
-                rep["delta_norm"] = float(torch.sqrt(torch.sum(dk * dk)))
-                rep["mc"] = {}
-                for half, at in (("fit", rows_k[fold >= 0]), ("held_out", rows_k[fold < 0])):
-                    act = flat["action"][at].astype(np.int64)
-                    states = up_states(at - 1)
-                    q_old, q_new = q_of(states, W_mean_old, k, act), q_of(states, W_mean, k, act)
-                    rep[half] = {"old": error_stats(q_old, y_d[at]), "new": error_stats(q_new, y_d[at])}
-                    rep["mc"][half] = {"old": error_stats(q_old, tg["y"][at]), "new": error_stats(q_new, tg["y"][at])}
-                if k == 0:
-                    boot, vs, v = done == 0, "vs0", "v0"
-                else:
-                    boot, vs, v = (vf_rows == k) & (np.asarray(flat["term"]) == 0) & (done == 0), "vsk", "vk"
-                gap = np.concatenate([t[vs][boot].astype(np.float64) - t[v][boot].astype(np.float64) for t in lt.values()])
-                rep["optimism"] = mean(gap)
-                rep["optimism_n"] = int(np.sum(boot))
-                rep["cut_share"] = mean([mean(t["c"][rows_k] == 0.0) for t in lt.values()]) if len(rows_k) else nan
-                rep["off_greedy"] = mean([mean(t["cut"][rows_k]) for t in lt.values()]) if len(rows_k) else nan
-                rep["horizon"] = mean([mean(t["h"][rows_k]) for t in lt.values()]) if len(rows_k) else nan
-                report["vf"][k] = rep
-            report["sweeps"].append({"vf": report["vf"], "W": W_mean.clone(), "W_a": W_a.clone(), "W_b": W_b.clone()})
-        report["double"] = {"W_a": W_a, "W_b": W_b}
-        if keep:
-            report["targets"], report["trajectory"] = tg, traj
-            report["double_targets"] = {"AB": lt["a"], "BA": lt["b"]}
-        if apply:
-            for k in vfs:
-                self.W[k].copy_(W_mean[k])
-        return report, W_mean
+    def _double_sweep(self, unit, ectx, fl, y_mc, q_of, vfs, W_a, W_b, gamma: float, lam, r_succ: float, cut: bool, keep: bool):
+        """One sweep of fit_values_to_returns(double=True), SPEC §29.2, on the tables W_a and W_b (W to start; refitted in place).
+        Two target sets over the whole record by valuefit.sweep_targets — AB: W_a selects the bootstrap action and W_b values it; BA
+        the other way round — then `unit` refits table A on fold A's rows (env % 4 == 0: valuefit.fold_of's fold 0) to AB against its
+        own Q^old under W_a, and table B on fold B's rows (env % 4 == 2) to BA. W_new = valuefit.mean_table(W_a, W_b); the odd envs
+        stay held out and judge the mean table. Returns (the sweep's per-vf report, W_new, {"a": AB, "b": BA}).
+        The report has the single fit's layout: per value function n (fit samples per action, both folds), delta_norm (of the mean
+        table's row) and valuefit.fit_stats' block of the MEAN table, before and after, against (y_AB + y_BA) / 2 and ("mc") the
+        Monte-Carlo targets; "cut_share" / "off_greedy" / "horizon" as the mean of the two target sets' — and adds "folds": {"a",
+        "b"}, each n, delta_norm, "fit" and "mc" old / new of the fold's own table on the fold's rows against its own targets
+        (`keep`: "operands"), and "optimism": the mean, over the rows whose target reads a bootstrap value of value function k (k = 0:
+        tab0's rows, v0; k >= 1: tabk's rows of table k, vk) and both target sets, of vs - v, the selecting table's own maximum less
+        the other table's value of that action: the max's bias as the two tables estimate it, exactly 0 in sweep 1."""
+        from .valuefit import fit_stats, mean_table, sweep_targets, trace_stats
+        cur = {"a": W_a.clone(), "b": W_b.clone()}             # what the sweep's targets bootstrap from and its residuals are taken against
+        new = {"a": W_a, "b": W_b}
+        W_mean_old = mean_table(W_a, W_b)
+        lt = {"a": sweep_targets(ectx, fl, cur["a"], gamma, lam, r_succ, traced=True, cut=cut, W_val=cur["b"]),
+              "b": sweep_targets(ectx, fl, cur["b"], gamma, lam, r_succ, traced=True, cut=cut, W_val=cur["a"])}
+        y_mean = (lt["a"]["y"] + lt["b"]["y"]) / 2.0
+        report = {}
+        for k in vfs:
+            report[k] = {"folds": {}}
+            for fold, name in enumerate(("a", "b")):
+                rows = self._sample_rows(fl, k, fl["env"] % 4 == 2 * fold, by_action=True)
+                rep, operands = unit(k, rows, rows.numel(), lt[name]["y"], cur[name], new[name])
+                rep = {"n": rep["n"], "delta_norm": rep["delta_norm"], "fit": rep["fit"], "mc": rep["mc"]["fit"]}
+                if keep:
+                    operands.pop("n_fit")                      # (a fold has no held-out part)
+                    rep["operands"] = operands
+                report[k]["folds"][name] = rep
+        W_mean = mean_table(W_a, W_b)
+        for k, rep in report.items():                          # the mean table, judged once both tables of the sweep stand
+            rep["n"] = [x + y for x, y in zip(rep["folds"]["a"]["n"], rep["folds"]["b"]["n"])]
+            dk = W_mean[k].double() - W_mean_old[k].double()
+            rep["delta_norm"] = float(torch.sqrt(torch.sum(dk * dk)))
+            halves = [self._sample_rows(fl, k, fl["env"] % 2 == r) for r in (0, 1)]
+            q = lambda W: np.concatenate([q_of(ectx, [fl[f][at - 1].contiguous() for f in ("x", "y", "vx", "vy")], W, k,
+                                               fl["action"][at].contiguous()) for at in halves])
+            at = torch.cat(halves)
+            stats = fit_stats(q(W_mean_old), q(W_mean), y_mean[at].cpu().numpy(), y_mc[at.cpu().numpy()], halves[0].numel())
+            rep["mc"] = stats.pop("mc")
+            rep.update(stats)
+            boot, vs, v = (fl["tab0"] == 0, "vs0", "v0") if k == 0 else (fl["tabk"] == k, "vsk", "vk")
+            gap = np.concatenate([(t[vs][boot].double() - t[v][boot].double()).cpu().numpy() for t in lt.values()])
+            rep["optimism"] = float(np.mean(gap)) if len(gap) else float("nan")
+            rep["optimism_n"] = int(boot.sum())
+            sets = [trace_stats(t, self._sample_rows(fl, k, fl["env"] >= 0)) for t in lt.values()]
+            for name in ("cut_share", "off_greedy", "horizon"):
+                rep[name] = float(np.mean([s[name] for s in sets]))
+        return report, W_mean, lt
 
     def fit_values_lstdq(self, n_episodes: int = 4096, epsilon: float = 0.1, seed: Optional[int] = None, vfs=None,
                          ridge: float = 1e-3, rounds: int = 1, apply: bool = False, keep: bool = False, interrupt: bool = False,

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from ._lib import TRIAL_SUCCESS, ScgError
-from .trajectory import Trajectory
+from .trajectory import DeviceRecord, Trajectory, _np_dtype
 
 
 def returns_to_go(traj, gamma: float, r_option_success: float, device="cpu") -> dict:
@@ -61,6 +61,90 @@ def _checked_offsets(name: str, flat) -> np.ndarray:
     return off
 
 
+def row_tables(flat) -> dict:
+    """The per-row tables of a flat record (to_numpy()'s dict), host arrays [total], the one host spelling of SPEC §28.2 / §30.1:
+      env, row  int32: the env that owns the row and the row's index in it; -1 and 0 on a row no env owns (offsets[0] > 0,
+                offsets[-1] < total)
+      sample    bool: row >= 1, a step row (False on every env's row 0, the begin row, and on the rows no env owns)
+      tab0      uint8: table 0 on the rows that are not done, else ROW_NONE
+      tabk      uint8: the row's own table on the rows with vf >= 1 whose option goes on (term = 0, not done), else ROW_NONE
+      tabA      uint8: the table that ACTS on the next row, vf[i + 1], where row i + 1 belongs to the same env and row i ended no
+                episode (done = 0, or an env's row 0: a recorded begin row carries done = 2, SPEC §10), else ROW_NONE."""
+    from ._lib import ROW_NONE
+    off = np.asarray(flat["offsets"], np.int64).reshape(-1)
+    done, vf, term = (np.asarray(flat[f], np.uint8) for f in ("done", "vf", "term"))
+    total = len(done)
+    L = np.diff(off)
+    env, row, last = np.full(total, -1, np.int32), np.zeros(total, np.int32), np.ones(total, bool)
+    if len(L):
+        e = np.repeat(np.arange(len(L)), L)
+        env[off[0]: off[-1]] = e
+        row[off[0]: off[-1]] = np.arange(off[0], off[-1]) - off[:-1][e]
+        last[off[0]: off[-1]] = row[off[0]: off[-1]] == L[e] - 1
+    nxt = np.concatenate([vf[1:], np.zeros(min(total, 1), np.uint8)])                 # vf[i + 1] (unused on the last row)
+    return {"env": env, "row": row, "sample": row >= 1,
+            "tab0": np.where(done == 0, 0, ROW_NONE).astype(np.uint8),
+            "tabk": np.where((vf >= 1) & (term == 0) & (done == 0), vf, ROW_NONE).astype(np.uint8),
+            "tabA": np.where(~last & ((row == 0) | (done == 0)), nxt, ROW_NONE).astype(np.uint8)}
+
+
+def flat_view(ctx, flat) -> dict:
+    """A flat record (Trajectory.to_numpy()'s dict) as DeviceRecord.flat() gives one: `offsets` (int64 [n + 1]), one [total] tensor
+    per recorded field in Trajectory's dtypes, `env`, `row`, `tab0`, `tabk`, `tabA` (row_tables') on ctx's device, and `total`
+    (int). One upload per array, no library call; by bits DeviceRecord.from_trajectory(ctx, traj).flat()."""
+    up = lambda v, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(v, dt))).to(ctx.device)
+    tabs = row_tables(flat)
+    out = {"offsets": up(np.reshape(flat["offsets"], -1), np.int64), "total": len(tabs["row"])}
+    out.update({f: up(flat[f], _np_dtype(Trajectory.DTYPES[f])) for f in Trajectory.FIELDS if f in flat})
+    out.update({f: up(tabs[f], tabs[f].dtype) for f in DeviceRecord.TABLES})
+    return out
+
+
+def sweep_targets(ctx, fl, W, gamma: float, lam, r_option_success: float, traced: bool = False, cut: bool = False, W_val=None) -> dict:
+    """The targets of one sweep over a flat view `fl` (flat_view's or DeviceRecord.flat()'s) under the tables W, as device tensors
+    [total]; the one values-then-scan sequence of SPEC §27.3 / §28.2 / §29.2. ScgContext.row_values gives `v0` (on tab0 under table
+    0) and `vk` (on tabk); with a valuing table `W_val` ScgContext.row_values_cross gives them instead — W's greedy action valued
+    under W_val — and `vs0`, `vsk`, W's own maxima. Not `traced` (`lam` a float): ScgContext.lambda_returns scans `y0`, `yk`.
+    `traced` (`lam` a float or one per table): a third row_values call gives `ag` on tabA, ScgContext.trace_returns scans `y0`,
+    `yk` and `h` with the trace cut at the off-greedy rows where `cut`, and formed here are `cut` (bool: the step rows whose recorded
+    action is not ag of the row before, whether or not the trace is cut) and `c` (float64: the coefficient each step row carries,
+    +0 on the other rows). `y` is yk on the rows with vf >= 1, y0 elsewhere."""
+    from ._lib import NUM_ACTIONS, NUM_FEATURES
+    Wt = W.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES)
+    states = [fl[f] for f in ("x", "y", "vx", "vy")]
+    out = {}
+    if W_val is None:
+        v0, _ = ctx.row_values(states, fl["tab0"], Wt[:1], actions=False)
+        vk, _ = ctx.row_values(states, fl["tabk"], Wt, actions=False)
+    else:
+        Wv = W_val.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES)
+        v0, _, out["vs0"] = ctx.row_values_cross(states, fl["tab0"], Wt[:1], Wv[:1], actions=False, sel_values=True)
+        vk, _, out["vsk"] = ctx.row_values_cross(states, fl["tabk"], Wt, Wv, actions=False, sel_values=True)
+    record = [fl[f] for f in ("offsets", "reward", "done", "vf", "term")]
+    if traced:
+        lam_vf = [float(lam)] * int(Wt.shape[0]) if np.ndim(lam) == 0 else [float(v) for v in lam]
+        _, ag = ctx.row_values(states, fl["tabA"], Wt, actions=True)
+        y0, yk, h = ctx.trace_returns(*record, fl["action"], ag, v0, vk, float(gamma), lam_vf, float(r_option_success), cut=bool(cut),
+                                      horizon=True)
+        step, vf = fl["row"] >= 1, fl["vf"].long()
+        off_greedy = torch.zeros_like(step)
+        off_greedy[1:] = step[1:] & (fl["action"][1:] != ag[:-1])
+        c = torch.tensor(lam_vf, dtype=torch.float64, device=vf.device)[torch.where(vf < len(lam_vf), vf, torch.zeros_like(vf))]
+        c = torch.where(step & ~off_greedy if cut else step, c, torch.zeros_like(c))
+        out = {"ag": ag, "h": h, "c": c, "cut": off_greedy, **out}
+    else:
+        y0, yk = ctx.lambda_returns(*record, v0, vk, float(gamma), float(lam), float(r_option_success))
+    return {"y0": y0, "yk": yk, "y": torch.where(fl["vf"] >= 1, yk, y0), "v0": v0, "vk": vk, **out}
+
+
+def host_targets(fl, targets) -> dict:
+    """sweep_targets' dict downloaded, with the view's `offsets` and `sample` (False on every env's row 0): what lambda_targets,
+    trace_targets and double_targets return."""
+    host = {f: v.cpu().numpy() for f, v in targets.items()}
+    return {"offsets": fl["offsets"].cpu().numpy(), **{f: host.pop(f) for f in ("y0", "yk", "y")},
+            "sample": (fl["row"] >= 1).cpu().numpy(), **host}
+
+
 def trace_targets(ctx, flat, W, gamma: float, lam, r_option_success: float, cut: bool = True) -> dict:
     """SPEC §28.2: lambda_targets with a trace coefficient per row (ScgContext.trace_returns). `lam`: a float, or one float per value
     function. Beside lambda_targets' two row_values calls a third gives `ag`, the greedy action at every row's state of the table
@@ -68,7 +152,7 @@ def trace_targets(ctx, flat, W, gamma: float, lam, r_option_success: float, cut:
     or an env's row 0: a recorded begin row carries done = 2), else ROW_NONE (ag = 255) —; with `cut` the trace is cut to +0 on
     every row whose recorded action is not that action (Watkins's Q(lambda): the targets evaluate the greedy policy of W), without
     it `ag` is formed for the report only. Returns lambda_targets' dict plus `ag` (uint8), `h` (float64: the root stream's effective
-    length, SPEC §28.1), `c` (float64: the coefficient each step row carries, formed here on the host; +0 on an env's row 0) and
+    length, SPEC §28.1), `c` (float64: the coefficient each step row carries; +0 on an env's row 0) and
     `cut` (bool: the step rows whose recorded action is not the greedy one, whether or not `cut` is set)."""
     return _trace_targets("trace_targets", ctx, flat, W, None, gamma, lam, r_option_success, cut)
 
@@ -85,53 +169,17 @@ def double_targets(ctx, flat, W_sel, W_val, gamma: float, lam, r_option_success:
 def _trace_targets(name: str, ctx, flat, W, W_val, gamma: float, lam, r_option_success: float, cut: bool) -> dict:
     """trace_targets (W_val None: the bootstrap values by row_values under W) and double_targets (by row_values_cross: W selects,
     W_val values), one copy."""
-    from ._lib import NUM_ACTIONS, NUM_FEATURES, ROW_NONE
+    from ._lib import NUM_ACTIONS, NUM_FEATURES
     flat = flat.to_numpy() if isinstance(flat, Trajectory) else flat
-    off = _checked_offsets(name, flat)
-    total = len(flat["reward"])
-    dev = ctx.device
-    up = lambda v, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(v, dt))).to(dev)
-    done, vf, term, action = (np.asarray(flat[f], np.uint8) for f in ("done", "vf", "term", "action"))
-    Wt = W.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES)
-    lam_vf = [float(lam)] * int(Wt.shape[0]) if np.ndim(lam) == 0 else [float(v) for v in lam]
-    if len(lam_vf) != int(Wt.shape[0]) or not all(0.0 <= v <= 1.0 for v in lam_vf) or not (0.0 <= float(gamma) <= 1.0):
+    _checked_offsets(name, flat)
+    n_tab = W.numel() // (NUM_ACTIONS * NUM_FEATURES)
+    lam_vf = [float(lam)] * n_tab if np.ndim(lam) == 0 else [float(v) for v in lam]
+    if len(lam_vf) != n_tab or not all(0.0 <= v <= 1.0 for v in lam_vf) or not (0.0 <= float(gamma) <= 1.0):
         raise ScgError(f"{name}: gamma and lam (a float, or one per value function) must lie in [0, 1]")
-    L = np.diff(off)
-    sample, has_next, begin = (np.zeros(total, bool) for _ in range(3))
-    if len(L):
-        env = np.repeat(np.arange(len(L)), L)
-        row = np.arange(off[0], off[-1]) - off[:-1][env]
-        sample[off[0]: off[-1]] = row >= 1
-        has_next[off[0]: off[-1]] = row < L[env] - 1
-        begin[off[0]: off[-1]] = row == 0                      # (a recorded begin row has done = 2, SPEC §10, and ends no episode)
-    nxt = np.concatenate([vf[1:], np.zeros(min(total, 1), np.uint8)])                 # vf[i + 1] (unused on the last row)
-    tab0 = np.where(done == 0, 0, ROW_NONE).astype(np.uint8)
-    tabk = np.where((vf >= 1) & (term == 0) & (done == 0), vf, ROW_NONE).astype(np.uint8)
-    tabA = np.where(has_next & (begin | (done == 0)), nxt, ROW_NONE).astype(np.uint8)
-    states = [up(flat[f], np.float32) for f in ("x", "y", "vx", "vy")]
-    extra = {}
-    if W_val is None:
-        v0, _ = ctx.row_values(states, up(tab0, np.uint8), Wt[:1], actions=False)
-        vk, _ = ctx.row_values(states, up(tabk, np.uint8), Wt, actions=False)
-    else:                                                      # SPEC §29.2: W's argmax valued under W_val
-        Wv = W_val.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES)
-        if Wv.shape != Wt.shape:
-            raise ScgError(f"{name}: W_sel and W_val must have one shape")
-        v0, _, vs0 = ctx.row_values_cross(states, up(tab0, np.uint8), Wt[:1], Wv[:1], actions=False, sel_values=True)
-        vk, _, vsk = ctx.row_values_cross(states, up(tabk, np.uint8), Wt, Wv, actions=False, sel_values=True)
-        extra = {"vs0": vs0.cpu().numpy(), "vsk": vsk.cpu().numpy()}
-    _, ag = ctx.row_values(states, up(tabA, np.uint8), Wt, actions=True)
-    y0, yk, h = ctx.trace_returns(up(off, np.int64), up(flat["reward"], np.float32), up(done, np.uint8), up(vf, np.uint8),
-                                  up(term, np.uint8), up(action, np.uint8), ag, v0, vk, float(gamma), lam_vf, float(r_option_success),
-                                  cut=bool(cut), horizon=True)
-    y0, yk, h, ag = y0.cpu().numpy(), yk.cpu().numpy(), h.cpu().numpy(), ag.cpu().numpy()
-    off_greedy = np.zeros(total, bool)
-    off_greedy[1:] = sample[1:] & (action[1:] != ag[:-1])
-    c = np.where(sample, np.asarray(lam_vf, np.float64)[np.where(vf < len(lam_vf), vf, 0)], 0.0)
-    if cut:
-        c = np.where(off_greedy, 0.0, c)
-    return {"offsets": off, "y0": y0, "yk": yk, "y": np.where(vf >= 1, yk, y0), "sample": sample,
-            "v0": v0.cpu().numpy(), "vk": vk.cpu().numpy(), "ag": ag, "h": h, "c": c, "cut": off_greedy, **extra}
+    if W_val is not None and W_val.numel() != W.numel():
+        raise ScgError(f"{name}: W_sel and W_val must have one shape")
+    fl = flat_view(ctx, flat)
+    return host_targets(fl, sweep_targets(ctx, fl, W, gamma, lam, r_option_success, traced=True, cut=cut, W_val=W_val))
 
 
 def lambda_targets(ctx, flat, W, gamma: float, lam: float, r_option_success: float) -> dict:
@@ -143,31 +191,12 @@ def lambda_targets(ctx, flat, W, gamma: float, lam: float, r_option_success: flo
     with vf >= 1, y0 elsewhere: consumable where returns_to_go()["y"] is), `sample` (False on every env's row 0) and `v0`, `vk`
     (float32). lam = 1 with every env ending done gives returns_to_go's g in y0 by bits; lam = 0 gives SPEC §17.2's targets.
     The offsets are checked here (non-decreasing, inside [0, total]) before anything is uploaded."""
-    from ._lib import NUM_ACTIONS, NUM_FEATURES, ROW_NONE
     flat = flat.to_numpy() if isinstance(flat, Trajectory) else flat
-    off = _checked_offsets("lambda_targets", flat)
-    total = len(flat["reward"])
+    _checked_offsets("lambda_targets", flat)
     if not (0.0 <= float(lam) <= 1.0) or not (0.0 <= float(gamma) <= 1.0):
         raise ScgError("lambda_targets: gamma and lam must lie in [0, 1]")
-    dev = ctx.device
-    up = lambda v, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(v, dt))).to(dev)
-    done, vf, term = (np.asarray(flat[f], np.uint8) for f in ("done", "vf", "term"))
-    tab0 = np.where(done == 0, 0, ROW_NONE).astype(np.uint8)
-    tabk = np.where((vf >= 1) & (term == 0) & (done == 0), vf, ROW_NONE).astype(np.uint8)
-    states = [up(flat[f], np.float32) for f in ("x", "y", "vx", "vy")]
-    Wt = W.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES)
-    v0, _ = ctx.row_values(states, up(tab0, np.uint8), Wt[:1], actions=False)
-    vk, _ = ctx.row_values(states, up(tabk, np.uint8), Wt, actions=False)
-    y0, yk = ctx.lambda_returns(up(off, np.int64), up(flat["reward"], np.float32), up(done, np.uint8), up(vf, np.uint8),
-                                up(term, np.uint8), v0, vk, float(gamma), float(lam), float(r_option_success))
-    y0, yk = y0.cpu().numpy(), yk.cpu().numpy()
-    L = np.diff(off)
-    sample = np.zeros(total, bool)
-    if len(L):
-        env = np.repeat(np.arange(len(L)), L)
-        sample[off[0]: off[-1]] = (np.arange(off[0], off[-1]) - off[:-1][env]) >= 1
-    return {"offsets": off, "y0": y0, "yk": yk, "y": np.where(vf >= 1, yk, y0), "sample": sample,
-            "v0": v0.cpu().numpy(), "vk": vk.cpu().numpy()}
+    fl = flat_view(ctx, flat)
+    return host_targets(fl, sweep_targets(ctx, fl, W, gamma, lam, r_option_success))
 
 
 def fold_of(env) -> np.ndarray:
@@ -385,6 +414,25 @@ def error_stats(q, y) -> dict:
         return {"n": 0, "rmse": float("nan"), "mean_error": float("nan")}
     e = q - y
     return {"n": int(len(y)), "rmse": float(np.sqrt(np.mean(e * e))), "mean_error": float(np.mean(e))}
+
+
+def fit_stats(q_old, q_new, y, y_mc, n_fit: int) -> dict:
+    """The error block of a fit's report over one sample list, its first n_fit samples the fit half and the rest held out: "fit"
+    and "held_out", each old / new error_stats of Q^old / Q^new against the targets y, and with y_mc (the Monte-Carlo targets of
+    the same samples) "mc": the same two halves against those."""
+    half = {"fit": slice(0, n_fit), "held_out": slice(n_fit, None)}
+    block = lambda t: {name: {"old": error_stats(q_old[sl], t[sl]), "new": error_stats(q_new[sl], t[sl])} for name, sl in half.items()}
+    return dict(block(y), mc=block(y_mc)) if y_mc is not None else block(y)
+
+
+def trace_stats(targets, rows, ag_prev=None) -> dict:
+    """What a traced fit reports of one target set (sweep_targets' dict) over the sample rows `rows` (a device index tensor), each
+    NaN without a row: "cut_share" (the share whose incoming coefficient is 0), "off_greedy" (the share whose recorded action is
+    not the greedy one), "horizon" (the mean effective length h of the root stream), the means in the order of `rows`, and
+    "a_changed": the share whose greedy action differs from `ag_prev`'s (the sweep before's `ag`), None without one."""
+    mean = lambda v: float(np.mean(v.cpu().numpy())) if len(rows) else float("nan")
+    return {"cut_share": mean(targets["c"][rows] == 0.0), "off_greedy": mean(targets["cut"][rows]), "horizon": mean(targets["h"][rows]),
+            "a_changed": None if ag_prev is None else mean(targets["ag"][rows - 1] != ag_prev[rows - 1])}
 
 
 TD_CONT, TD_BOOT, TD_END = 0, 1, 2      # SPEC §17.2's kinds: bootstrap from Q_k(s'), from the root's value of s' (§5's exit rule), from nothing

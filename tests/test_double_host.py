@@ -1,12 +1,12 @@
 """tests/double_model.py, the host model of SPEC §29, against lambda_model's row values and trace_model's targets where the two tables
-are one, on hand-made tables where they are not, and at its edges (NaN, act >= 5); valuefit.fold_of and mean_table. No GPU."""
+are one, on hand-made tables where they are not, and at its edges (NaN, act >= 5); valuefit.fold_of, mean_table and row_tables. No GPU."""
 import numpy as np
 import pytest
 
 import double_model as DM
 import lambda_model as LM
 import trace_model as TM
-from skill_chaining_with_graphs_amd.valuefit import fold_of, mean_table
+from skill_chaining_with_graphs_amd.valuefit import fold_of, mean_table, row_tables
 from util import fourier_reference, random_weights
 
 NONE = LM.ROW_NONE
@@ -87,6 +87,36 @@ def test_a_given_action_of_five_or_more_is_a_row_without_a_table():
             assert bits32(v[i]) == bits32(host_q([s[i: i + 1] for s in states], Wf[tab[i]])[act[i], 0]) and a[i] == act[i]
         else:
             assert bits32(v[i]) == 0 and a[i] == 255
+
+
+def test_row_tables_are_the_models_tables_by_bits():
+    rng = np.random.default_rng(31)
+    envs = [LM.synthetic_env(rng, L, end_done=d) for L, d in ((1, False), (14, True), (9, False), (33, True), (2, True))]
+    LM.plant_edges(envs[1])                                    # rows 1-2 TIMEOUT, then the same option entered again at once
+    for e in (0, 1, 3):
+        envs[e]["done"][0] = 2                                 # a recorded begin row (SPEC §10); the other envs' row 0 has done = 0
+    flat = LM.flatten(envs)
+    lead, trail = 3, 2                                         # rows no env owns, before and behind, that LOOK like live option rows
+    for f, junk in (("reward", -1.0), ("done", 0), ("vf", 1), ("term", 0)):
+        flat[f] = np.concatenate([np.full(lead, junk, flat[f].dtype), flat[f], np.full(trail, junk, flat[f].dtype)])
+    flat["offsets"] = flat["offsets"] + lead
+    off, total = flat["offsets"], len(flat["reward"])
+    assert off[0] > 0 and off[-1] < total and flat["done"][off[2] - 1] == 1 and flat["done"][off[3] - 1] == 0
+    got = row_tables(flat)
+    for name, want in zip(("tab0", "tabk", "tabA"), DM.record_tables(flat)):
+        assert got[name].dtype == np.uint8 and np.array_equal(got[name], want), name
+    owned = np.zeros(total, bool)
+    owned[off[0]: off[-1]] = True
+    first = np.zeros(total, bool)
+    first[off[:-1]] = True
+    assert got["sample"].dtype == bool and np.array_equal(got["sample"], owned & ~first)
+    assert np.all(got["tabA"][~owned] == NONE) and got["tabA"][off[0]] == NONE            # the env of one row has no next row
+    assert got["env"].dtype == got["row"].dtype == np.int32 and np.all(got["env"][~owned] == -1)
+    assert np.array_equal(got["env"][owned], np.repeat(np.arange(5), np.diff(off)))
+    assert np.array_equal(got["row"][owned], np.concatenate([np.arange(n) for n in np.diff(off)]))
+    assert (got["tabA"] != NONE).sum() > 30 and (got["tabk"] != NONE).sum() > 10
+    empty = row_tables({"offsets": [0], "done": [], "vf": [], "term": []})
+    assert all(len(v) == 0 for v in empty.values())
 
 
 def test_fold_of_splits_the_fit_half_in_two():

@@ -231,7 +231,7 @@ def run_pack_case(ctx):
     want = model_pack(store, off, total, n, cap, {f: out[f].start[GUARD: GUARD + total] for f in OUT_DTYPES})
     for f in OUT_DTYPES:
         assert np.array_equal(out[f].host(), out[f].expect(want[f])), f
-    # the tables once more, as valuefit._trace_targets forms them from the flat record
+    # the tables once more, as valuefit.row_tables forms them from the flat record
     done, vf, term, row = want["done"], want["vf"], want["term"], want["row"]
     has_next = row < L[want["env"]] - 1
     nxt = np.concatenate([vf[1:], [0]]).astype(np.uint8)

@@ -1,7 +1,8 @@
 """What SPEC §30's device record and device fit pipeline cost against the host paths they stand beside, in one run on one recorded
 set of episodes of the headline workload (tools/lambda_targets_bench.py's: chain classifiers, all options on, random weights). Arms
 interleaved round by round as tools/gram_bench.py times its arms, every arm ending in a device synchronise; the host arms are the
-unchanged code of the default paths.
+default paths. Both fit arms run fit_values_to_returns' one loop: they differ in where the flat view comes from (an upload of the
+Trajectory per call / DeviceRecord.flat()) and in how Q of a sample list is formed (q_values in chunks / one row_action_values).
 
   the record, --episodes episodes at --epsilon:
     record_host      agent.record_episodes(): every launch's buffers downloaded and cut per env on the host
