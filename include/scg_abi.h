@@ -553,6 +553,23 @@ int scg_logistic_terms(scg_ctx *ctx, int64_t n, const float *z, const uint8_t *l
 int scg_basis_gram_irls(scg_ctx *ctx, int32_t order, int64_t n, const float *x, const float *y, const float *vx, const float *vy,
                         const float *rw, const float *e, int32_t n_seg, const int64_t *offsets /* HOST */,
                         float *H /* [n_seg][F][F] */, float *grad /* [n_seg][F] */, void *stream);
+/* ---- the pinned-order ridge solve (SPEC §31): a batched binary64 Cholesky factor-and-solve of the Gram kernels' output where it lies.
+ * For each of n_mat matrices A[g][F][F] (binary32; only i >= j is read, the strict upper triangle may hold anything) with n_rhs
+ * right-hand sides B[g][c][F] (binary32), lam[F] (binary64, device) and the host scalars mu[g]:
+ *   M_ij = double(A_ij) (i > j),  M_ii = double(A_ii) + mu[g] * lam[i];   M = L L^T;   Delta[g][c] = M^-1 double(B[g][c])
+ * every operation binary64 and rounded on its own (no fma), in SPEC §31.1's order: per entry of L the updates in ascending k, the
+ * forward substitution ascending, the backward one descending from F - 1; sqrt and / correctly rounded. Nothing depends on the tiling,
+ * the grid, the block build or the batch. On return work[g]'s lower triangle holds L (its strict upper triangle is not written),
+ * Delta[n_mat][n_rhs][F] the solutions and info[g] (int32, device) 0, or j + 1 where the pivot of column j failed !(t > 0) (a NaN
+ * included): then Delta[g] = +0, work[g] holds the block columns of 16 finished before, and the other matrices are unaffected. skip[g] != 0 (HOST
+ * u8): Delta[g] = +0, info[g] = 0, A[g], B[g] and work[g] are not touched. A memset of info, F / 16 factor launches and one substitution launch on `stream`; no
+ * workgroup waits on another. Needs no map, raises no asynchronous status, writes Delta, work and info only. SCG_ERR_INVALID, nothing launched, in
+ * this sequence: a null ctx, F not a positive multiple of 16 up to SCG_RIDGE_MAX_F, n_mat outside [1, SCG_GRAM_MAX_SEGMENTS], n_rhs
+ * outside [1, SCG_GRAM_MAX_TARGETS], a null array. */
+#define SCG_RIDGE_MAX_F 4096
+int scg_ridge_solve(scg_ctx *ctx, int32_t F, int32_t n_mat, int32_t n_rhs, const float *A, const float *B, const double *lam,
+                    const double *mu /* HOST [n_mat] */, const uint8_t *skip /* HOST [n_mat] */, double *work /* [n_mat][F][F] */,
+                    double *Delta /* [n_mat][n_rhs][F] */, int32_t *info /* [n_mat] */, void *stream);
 /* Option.policy value part (SPEC §3.1): q[5][n] = Q_k(s, .) for one VF Wk[5][1296]. */
 int scg_q_values(scg_ctx *ctx, int32_t n, const float *x, const float *y, const float *vx,
                  const float *vy, const float *Wk, float *q, void *stream);

@@ -35,7 +35,7 @@ def __getattr__(name):
     if name in ("Option", "InitiationClassifier"):
         from . import option
         return getattr(option, name)
-    if name in ("returns_to_go", "ridge_solve", "td_samples", "lstdq_solve", "damped_tables", "choose_candidate"):
+    if name in ("returns_to_go", "ridge_solve", "ridge_solve_pinned", "ridge_solve_shared_pinned", "td_samples", "lstdq_solve", "damped_tables", "choose_candidate"):
         from . import valuefit
         return getattr(valuefit, name)
     if name in ("irls_fit", "FourierClassifier", "classification_stats"):

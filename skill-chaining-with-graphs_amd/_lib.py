@@ -50,6 +50,8 @@ BASIS_VALUES_MAX_ROWS = 8   # include/scg_abi.h SCG_BASIS_VALUES_MAX_ROWS
 ROW_NONE = 255              # include/scg_abi.h SCG_ROW_NONE: SPEC §27.1's table entry of a row without a table
 TRACE_CUT = 1               # include/scg_abi.h SCG_TRACE_CUT: SPEC §28.1's flag of scg_trace_returns
 CROSS_GIVEN = 1             # include/scg_abi.h SCG_CROSS_GIVEN: SPEC §29.1's flag of scg_row_values_cross
+RIDGE_TILE = 16             # SPEC §31: the matrix side of scg_ridge_solve is a positive multiple of it ...
+RIDGE_MAX_F = 4096          # ... up to include/scg_abi.h SCG_RIDGE_MAX_F
 
 
 def basis_features(order: int) -> int:
@@ -232,6 +234,7 @@ _SIGS = {
     "scg_record_append": (C.c_int, [_P, C.POINTER(Record), C.POINTER(RecordStore), C.c_int32, _P]),
     "scg_record_offsets": (C.c_int, [_P, C.c_int32, _P, _P, _P]),
     "scg_record_pack": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(RecordStore), _P, C.c_int64] + [_P] * 10 + [_P] * 5 + [_P]),
+    "scg_ridge_solve": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32] + [_P] * 8 + [_P]),
     "scg_q_values": (C.c_int, [_P, C.c_int32] + [_P] * 6 + [_P]),
     "scg_q_update": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 12 + [C.c_uint32, _P]),
     "scg_classifier_predict": (C.c_int, [_P, C.c_int32] + [_P] * 4 + [_P]),

@@ -809,8 +809,8 @@ class SkillChainingAgent:
     def fit_values_to_returns(self, n_episodes: int = 4096, epsilon: float = 0.1, seed: Optional[int] = None, vfs=None,
                               ridge: float = 1e-3, apply: bool = False, interrupt: bool = False, choose: Optional[str] = None,
                               keep: bool = False, order: Optional[int] = None, trajectory=None, lam=None, sweeps: int = 1, trace: str = "peng",
-                              double: bool = False, pipeline: str = "host", fresh: bool = False):
-        """The best linear fit of each Q_k to the returns its own policy realises (SPEC §16, §18, §27 - §30): one loop over a flat view
+                              double: bool = False, pipeline: str = "host", fresh: bool = False, solver: str = "host"):
+        """The best linear fit of each Q_k to the returns its own policy realises (SPEC §16, §18, §27 - §31): one loop over a flat view
         of a record (valuefit.flat_view / DeviceRecord.flat: the rows in (env, row) order on the device, with their row tables).
         The record is record_episodes() with the current policy, or `trajectory`, a kept record (report["trajectory"] of an earlier
         call; report["episodes"] is then None). Every sweep forms its targets y over all rows and then, per value function k of `vfs`
@@ -849,13 +849,21 @@ class SkillChainingAgent:
         under the table the sweep before handed on, with this call's epsilon, interrupt and choose and the seed `seed` + s - 1, and
         takes its targets, samples and held-out half from that record. Every sweep's entry then holds "episodes" (its record's
         summary), its "mc" is against its own record's returns, and "a_changed" is None: the rows differ between sweeps.
-        Refused (ScgError): a trace other than the two names; "watkins", double, pipeline="device" or fresh without lam; double,
+        `solver` (SPEC §31.3): who solves the refit's normal equations. "host": valuefit.ridge_solve on the downloaded Gram (with
+        `order` its device form, a vendor Cholesky per action). "device": valuefit.ridge_solve_pinned in every mode — both pipelines,
+        `double`, `fresh` and `order` —: A and b stay where the Gram call left them, the new rows are formed on the device by the same
+        two roundings, and only `info` and the 5 x F Delta of the report come back. Its W_new has the bits of a host model of SPEC
+        §31.1's order, not LAPACK's: the two solvers' tables differ in the last places.
+        Refused (ScgError): a trace other than the two names; a solver other than the two names; "watkins", double,
+        pipeline="device" or fresh without lam; double,
         pipeline="device", fresh or lam with order; pipeline="device" or fresh with double; a lam outside [0, 1] or a lam sequence of
         another length than n_vf; sweeps < 1, or != 1 without lam; order with apply=True; apply=True with shared weights."""
         from .core import fourier_scale_table
         from .valuefit import flat_view, host_targets, returns_to_go, sweep_targets, trace_stats
         if trace not in ("peng", "watkins"):
             raise ScgError(f"fit_values_to_returns: trace must be 'peng' or 'watkins', not {trace!r}")
+        if solver not in ("host", "device"):
+            raise ScgError(f"fit_values_to_returns: solver must be 'host' or 'device', not {solver!r}")
         if trace == "watkins" and lam is None:
             raise ScgError("fit_values_to_returns: trace='watkins' needs lam (the Monte-Carlo path has no trace to cut)")
         if double and (lam is None or order is not None):
@@ -939,7 +947,8 @@ class SkillChainingAgent:
                 even = fl["env"] % 2 == 0                      # the fit half, by action; the odd envs are held out
                 lists = {} if double else {k: (self._sample_rows(fl, k, even, by_action=True), self._sample_rows(fl, k, ~even))
                                            for k in vfs}
-                unit = functools.partial(self._fit_unit, ectx, fl, None if lam is None else tg["y"], q_of, ridge, order, scale)
+                unit = functools.partial(self._fit_unit, ectx, fl, None if lam is None else tg["y"], q_of, ridge, order, scale,
+                                         solver=solver)
             if double:
                 report["vf"], W_new, lt = self._double_sweep(unit, ectx, fl, tg["y"], q_of, vfs, W_a, W_b, gamma, lam, r_succ,
                                                              trace == "watkins", keep)
@@ -982,17 +991,26 @@ class SkillChainingAgent:
         stats, rec = self._eval_launches(n_episodes, epsilon, seed, 64, None, interrupt, record=True, choose=choose, W=W, device=True)
         return self._eval_ctx[int(n_episodes)][0], rec, stats.summary()
 
-    def _refit_rows(self, gram, states, d, act_fit, ridge: float, scale, W_k):
+    def _refit_rows(self, gram, states, d, act_fit, ridge: float, scale, W_k, solver: str = "host", ectx=None):
         """The refit of one table's rows to a residual (SPEC §16.3), the one copy of it: the per-action segments of the fit samples
         (the first len(act_fit) of `states`, sorted by action), A and b by `gram` with yv = d, Delta by valuefit.ridge_solve — on the
         host; with W_k None (the basis-order probe: F up to 4096) on the device, and no row is formed — and W_k[a] <-
         float32(float64 W_k[a] + Delta[a]); an action without samples keeps its row bit for bit. Returns (n_a, offsets, A, b, delta,
-        w_new or None)."""
-        from .valuefit import ridge_solve
+        w_new or None). With `solver` "device" (SPEC §31.3) Delta is valuefit.ridge_solve_pinned's under the context `ectx` in either
+        case: A and b are not downloaded, the rows are formed on the device by the same two roundings (w_new is then a device
+        tensor), and delta is the one 5 x F download."""
+        from .valuefit import ridge_solve, ridge_solve_pinned
         dev = self.W.device
         n_a = np.bincount(act_fit, minlength=NUM_ACTIONS).astype(np.int64)
         offsets = np.concatenate([[0], np.cumsum(n_a)]).astype(np.int64)
         A, b = gram(states, offsets, torch.from_numpy(d).to(dev))
+        if solver == "device":
+            delta_d = ridge_solve_pinned(ectx, A, b, n_a, ridge, scale)
+            if W_k is None:
+                return n_a, offsets, A, b, delta_d.cpu().numpy(), None
+            keep = torch.from_numpy(n_a == 0).to(dev)[:, None]
+            w_new = torch.where(keep, W_k, (W_k.double() + delta_d).float())
+            return n_a, offsets, A, b, delta_d.cpu().numpy(), w_new
         if W_k is None:
             return n_a, offsets, A, b, ridge_solve(A, b, n_a, ridge, scale, device=dev), None
         delta = ridge_solve(A.cpu().numpy(), b.cpu().numpy(), n_a, ridge, scale)
@@ -1027,14 +1045,14 @@ class SkillChainingAgent:
         tab = torch.full((act.numel(),), int(k), dtype=torch.uint8, device=act.device)
         return ectx.row_action_values(states, tab, W.contiguous().view(-1, NUM_ACTIONS, NUM_FEATURES), act).cpu().numpy()
 
-    def _fit_unit(self, ectx, fl, y_mc, q_of, ridge: float, order, scale, k: int, rows, n_fit: int, y, W_old, W_to):
+    def _fit_unit(self, ectx, fl, y_mc, q_of, ridge: float, order, scale, k: int, rows, n_fit: int, y, W_old, W_to, solver: str = "host"):
         """The unit every fit_values_to_returns mode runs per value function (per fold under `double`): table k of W_old refitted on
         the sample list `rows` of the flat view `fl` (a device index tensor; the first n_fit, sorted by action, are fitted, the rest
         held out) to the targets y (a device tensor over all rows). Q^old by `q_of` (_q_chunks or _q_rows) under W_old, the residual
         float32(y - float64 Q^old), _refit_rows, the new row written into W_to[k], Q^new by `q_of` under W_to; with `order` the
         Gram and the solve are order p's, no row is written and Q^new = Q^old + basis_values(Delta). The statistics are
         valuefit.fit_stats on the downloaded per-sample arrays (`y_mc`: the Monte-Carlo targets of all rows, a host array, or None).
-        Returns (the value function's report, its kept operands)."""
+        `solver`: _refit_rows'. Returns (the value function's report, its kept operands)."""
         from .valuefit import fit_stats
         dev = self.W.device
         act_d = fl["action"][rows].contiguous()
@@ -1043,12 +1061,13 @@ class SkillChainingAgent:
         q_old = q_of(ectx, states, W_old, k, act_d)
         d = (y - q_old.astype(np.float64)).astype(np.float32)
         if order is None:
-            n_a, offsets, A, b, delta, w_new = self._refit_rows(ectx.feature_gram, states, d, act[:n_fit], ridge, scale, W_old[k])
-            W_to[k] = torch.from_numpy(w_new).to(dev)
+            n_a, offsets, A, b, delta, w_new = self._refit_rows(ectx.feature_gram, states, d, act[:n_fit], ridge, scale, W_old[k],
+                                                                solver, ectx)
+            W_to[k] = w_new if isinstance(w_new, torch.Tensor) else torch.from_numpy(w_new).to(dev)
             q_new = q_of(ectx, states, W_to, k, act_d)
         else:                                                  # (F up to 4096: factored on the device)
             gram = lambda st, offs, yv: ectx.basis_gram(order, st, offs, yv)
-            n_a, offsets, A, b, delta, _ = self._refit_rows(gram, states, d, act[:n_fit], ridge, scale, None)
+            n_a, offsets, A, b, delta, _ = self._refit_rows(gram, states, d, act[:n_fit], ridge, scale, None, solver, ectx)
             q_new = q_old.copy()                               # the correction lives at order p: Q^new = Q^old + Delta . phi^p
             if len(act):
                 v = ectx.basis_values(order, states, torch.from_numpy(delta.astype(np.float32)).to(dev)).cpu().numpy()

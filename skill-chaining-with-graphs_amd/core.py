@@ -724,6 +724,39 @@ class ScgContext:
                    off.ctypes.data_as(C.c_void_p), _ptr(H), _ptr(grad), self._stream())
         return H, grad
 
+    def ridge_solve(self, A: torch.Tensor, B: torch.Tensor, lam: torch.Tensor, mu, skip=None):
+        """SPEC §31: the pinned-order ridge solve on the device. `A` float32 [n_mat][F][F] as the Gram calls leave it (its lower
+        triangle is read), `B` float32 [n_mat][n_rhs][F] or [n_mat][F], `lam` float64 [F] on the device, `mu` host floats [n_mat]
+        (M_ii = A_ii + mu[g] * lam[i]), `skip` host flags [n_mat] (None: none). F a multiple of 16 up to 4096, n_mat <= 64, n_rhs <=
+        16. Returns device tensors (Delta float64 of B's shape, L float64 [n_mat][F][F] — the factor in the lower triangle, the strict
+        upper triangle unspecified —, info int32 [n_mat]: 0, or j + 1 for a failed pivot of column j, whose Delta is +0). A skipped
+        matrix gets Delta = +0 and info = 0; its L is not written. Nothing is read back."""
+        if not isinstance(A, torch.Tensor) or A.dim() != 3 or A.shape[1] != A.shape[2]:
+            raise ScgError("ridge_solve: A must be [n_mat][F][F]")
+        n_mat, F = int(A.shape[0]), int(A.shape[1])
+        if F < 1 or F % _lib.RIDGE_TILE or F > _lib.RIDGE_MAX_F:
+            raise ScgError(f"ridge_solve: F must be a positive multiple of {_lib.RIDGE_TILE} up to {_lib.RIDGE_MAX_F}")
+        if not (1 <= n_mat <= _lib.GRAM_MAX_SEGMENTS):
+            raise ScgError(f"ridge_solve: 1 .. {_lib.GRAM_MAX_SEGMENTS} matrices")
+        if not isinstance(B, torch.Tensor) or B.dim() not in (2, 3) or B.shape[0] != n_mat or B.shape[-1] != F:
+            raise ScgError(f"ridge_solve: B must be [{n_mat}][n_rhs][{F}] or [{n_mat}][{F}]")
+        n_rhs = int(B.shape[1]) if B.dim() == 3 else 1
+        if not (1 <= n_rhs <= _lib.GRAM_MAX_TARGETS):
+            raise ScgError(f"ridge_solve: 1 .. {_lib.GRAM_MAX_TARGETS} right-hand sides per matrix")
+        self._chk(A, torch.float32, n_mat * F * F, "A")
+        self._chk(B, torch.float32, n_mat * n_rhs * F, "B")
+        self._chk(lam, torch.float64, F, "lam")
+        mu = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
+        skip = np.zeros(n_mat, np.uint8) if skip is None else np.ascontiguousarray((np.asarray(skip).reshape(-1) != 0).astype(np.uint8))
+        if len(mu) != n_mat or len(skip) != n_mat:
+            raise ScgError(f"ridge_solve: mu and skip must hold {n_mat} entries")
+        L = torch.empty((n_mat, F, F), dtype=torch.float64, device=self.device)
+        delta = torch.empty(tuple(B.shape), dtype=torch.float64, device=self.device)
+        info = torch.empty(n_mat, dtype=torch.int32, device=self.device)
+        self._call("scg_ridge_solve", F, n_mat, n_rhs, _ptr(A), _ptr(B), _ptr(lam), mu.ctypes.data_as(C.c_void_p),
+                   skip.ctypes.data_as(C.c_void_p), _ptr(L), _ptr(delta), _ptr(info), self._stream())
+        return delta, L, info
+
     def q_values(self, s, Wk: torch.Tensor) -> torch.Tensor:
         n = s[0].numel()
         x, y, vx, vy = self._chk4(s, n, "state")

@@ -35,6 +35,8 @@
 // scg_returns_cross.hip holds SPEC §29's row_values_cross_kernel behind scg_row_values_cross.
 // scg_record_store.hip holds SPEC §30.1's record store kernels behind scg_record_append, scg_record_offsets and scg_record_pack
 // (DESIGN §3.35).
+// scg_ridge.hip holds SPEC §31's pinned-order ridge solve, ridge_factor_kernel (one launch per block column of 16) and
+// ridge_subst_kernel, behind scg_ridge_solve (scg_ridge.hpp: here their arguments and the launch only).
 // Every sum has the pinned order of SPEC §3.1 / §5 / §6 (no atomics on data): the CPU oracle reproduces every bit.
 // No upstream code exists to cite (reference = README.md:1-2); sections cite SPEC.md.
 #include "scg_device.hpp"
@@ -67,6 +69,7 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 #include "scg_returns.hpp"
 #include "scg_returns_cross.hpp"
 #include "scg_record_store.hpp"
+#include "scg_ridge.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side: the C-ABI
@@ -1645,6 +1648,26 @@ int scg_record_pack(scg_ctx *c, int32_t n, int32_t cap, const scg_record_store *
     SCG_ON_DEVICE(c, "scg_record_pack");
     if (n == 0 || total == 0) return SCG_OK;
     SCG_HIP(c, launch_record_pack(A, reinterpret_cast<hipStream_t>(stream)));
+    return SCG_OK;
+}
+
+// ---- SPEC §31: the pinned-order ridge solve
+int scg_ridge_solve(scg_ctx *c, int32_t F, int32_t n_mat, int32_t n_rhs, const float *A, const float *B, const double *lam,
+                    const double *mu, const uint8_t *skip, double *work, double *Delta, int32_t *info, void *stream) {
+    if (!c) return fail(nullptr, SCG_ERR_INVALID, "scg_ridge_solve: null ctx");
+    if (F < RIDGE_TILE || F > SCG_RIDGE_MAX_F || F % RIDGE_TILE != 0)
+        return fail(c, SCG_ERR_INVALID, "scg_ridge_solve: F must be a positive multiple of 16 up to SCG_RIDGE_MAX_F");
+    if (n_mat < 1 || n_mat > SCG_GRAM_MAX_SEGMENTS) return fail(c, SCG_ERR_INVALID, "scg_ridge_solve: n_mat out of range [1, SCG_GRAM_MAX_SEGMENTS]");
+    if (n_rhs < 1 || n_rhs > SCG_GRAM_MAX_TARGETS) return fail(c, SCG_ERR_INVALID, "scg_ridge_solve: n_rhs out of range [1, SCG_GRAM_MAX_TARGETS]");
+    if (!A || !B || !lam || !mu || !skip || !work || !Delta || !info) return fail(c, SCG_ERR_INVALID, "scg_ridge_solve: null array argument");
+    SCG_CHECK_ASYNC(c);
+    SCG_ON_DEVICE(c, "scg_ridge_solve");
+    RidgeArgs P = {A, B, lam, work, Delta, info, {}, 0, F, n_mat, n_rhs, 0};
+    for (int g = 0; g < n_mat; ++g) {
+        P.mu[g] = mu[g];
+        if (skip[g]) P.skip |= 1ull << g;
+    }
+    SCG_HIP(c, launch_ridge_solve(P, reinterpret_cast<hipStream_t>(stream)));
     return SCG_OK;
 }
 

@@ -274,6 +274,38 @@ def ridge_solve_shared(A, B, n, ridge: float, scale) -> np.ndarray:
     return out
 
 
+def _pinned(name: str, ctx, A, B, n, ridge: float, scale, what: str):
+    """ridge_solve_pinned and ridge_solve_shared_pinned, one copy: ScgContext.ridge_solve on A [n_mat][F][F] and B with lam = 1 /
+    scale^2 and mu[g] = ridge max(n[g], 1) as ridge_solve forms them, the matrices with n[g] = 0 skipped; `info` is the one
+    read-back, and a failed pivot raises ScgError naming the matrix (`what`) and the leading minor."""
+    n = np.asarray(n, np.int64).reshape(-1)
+    lam = torch.from_numpy(1.0 / np.asarray(scale, np.float64) ** 2).to(ctx.device)
+    mu = [float(ridge) * max(int(v), 1) for v in n]
+    delta, _, info = ctx.ridge_solve(A, B, lam, mu, skip=n == 0)
+    info = info.cpu().numpy()
+    if info.any():
+        g = int(np.nonzero(info)[0][0])
+        raise ScgError(f"{name}: the matrix{what.format(g)} is not positive definite (leading minor {int(info[g])})")
+    return delta
+
+
+def ridge_solve_pinned(ctx, A, b, n, ridge: float, scale) -> torch.Tensor:
+    """SPEC §31.3: ridge_solve's system by ScgContext.ridge_solve — a float64 Cholesky on the device in SPEC §31.1's pinned order, the
+    bits of which a host model reproduces, not LAPACK's. A float32 [n_act][F][F] and b float32 [n_act][F] are device tensors as the
+    Gram calls return them and are not downloaded; n, ridge and `scale` as ridge_solve takes them; an action with n[a] = 0 gets
+    Delta = 0 exactly; ScgError names the action and the leading minor of a matrix that is not positive definite. Returns Delta
+    float64 [n_act][F] on the device."""
+    return _pinned("ridge_solve_pinned", ctx, A, b, n, ridge, scale, " of action {}")
+
+
+def ridge_solve_shared_pinned(ctx, A, B, n, ridge: float, scale) -> torch.Tensor:
+    """SPEC §31.3: ridge_solve_shared's system by ScgContext.ridge_solve: ONE factorisation of A float32 [F][F] with the C rows of B
+    float32 [C][F] as its right-hand sides (C <= 16), by bits ridge_solve_pinned(repeat(A, C), B, [n] * C, ridge, scale). n = 0
+    gives zeros exactly. Returns Delta float64 [C][F] on the device."""
+    F = int(A.shape[-1])
+    return _pinned("ridge_solve_shared_pinned", ctx, A.view(1, F, F), B.view(1, -1, F), [int(n)], ridge, scale, "")[0]
+
+
 def branch_targets(g, q_old):
     """SPEC §20.2: what a fit of Q to all-action branch returns regresses. g [M][A][R] (BranchResult.g: binary32), q_old [M][A]
     float32 (Q^old(s_i, a): the result's qcache). Returns
